@@ -23,11 +23,16 @@ chains, every step is complete at the closing barrier + synchronize that bracket
 step's pairs 45 % / 55 % over two contexts from here: --submit python, or PUTSLAM_HIP_QUEUE_SPLIT_FROM=20 for the same inside the
 library; whole batches in turn read 608 k against 559 k, profiles/r06h/queue_split_vs_turns.txt.)
 
-The timed region of K steps is run --repeats times (default 5, each bracketed by barrier + synchronize, max over
-ranks); `value` / `ms_per_step` are the MEDIAN region, `value_min` / `value_max` the spread, `timed_regions_ms_per_step`
-all of them.
+The timed region of K steps is run --repeats times (default 1, so that K is the number of timed steps; 5 with --full; each
+bracketed by barrier + synchronize, max over ranks); `value` / `ms_per_step` are the MEDIAN region, `value_min` / `value_max`
+the spread, `timed_regions_ms_per_step` all of them.
 
-After the timed regions (never part of `value`) rank 0 of a single-GPU run adds short legs:
+A plain run does only what the headline needs: set up, warm up, time the regions, write the outputs (--dump-outputs DIR: the
+arrays the last timed step returned -- matches, inlier masks, poses, statistics -- as DIR/<name>.npy in float32 / float64),
+print the line.  Everything else is measured with --full only.
+
+With --full, after the timed regions (never part of `value`) a few instrumented steps give `timed_region_kernel_ms`, and
+rank 0 of a single-GPU run adds short legs:
   * a single-chain leg -- the same step as ONE launch chain on one stream, HIP events around every kernel: the
     kernels' own durations.  `kernel_ms`, `roofline`, `kernel_bounds`, `single_chain` come from it (the timed region's
     per-launch figures, measured while the chains share the CUs, are kept as `timed_region_kernel_ms`);
@@ -129,8 +134,14 @@ def parse():
                     help="test hook: write the per-pair records rank 0 holds after the last step (numpy .npy)")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="test hook: single-rank run with the sequence and seed of this rank of a multi-rank run")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps each; value = the median region, value_min/max = the spread")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps each (default 1; 5 with --full); value = the median region, value_min/max = the spread")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else: per-kernel durations, the single-chain leg, roofline / "
+                         "kernel bounds, the other modes, sizes and C++ hosts, the CPU baseline (off: a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them returned (matches, inlier masks, poses, statistics) "
+                         "as DIR/<name>.npy in float32 / float64, at most 64 MB in all (a fixed sample of the pairs beyond that)")
     ap.add_argument("--shard", default="pairs", choices=["pairs", "sequence"],
                     help="N > 1: 'pairs' = one sequence per GPU (BASELINE configs[3], weak scaling); 'sequence' = ONE "
                          "sequence of --frames frames split over the ranks with a one-frame halo "
@@ -152,6 +163,8 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU work budget of the cpu_baseline leg")
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
     if a.preset == "demoMatching":
         a.frames = 2
     elif a.preset == "stress":
@@ -425,8 +438,12 @@ def main():
             el = float(tt.item())
         region_s.append(el)
     elapsed = float(np.median(region_s))
+    # what the last timed step returned (every step computes the same: same frames, same seed), before any leg below writes a block
+    res = pbs[(state["step"] - 1) % len(pbs)].download()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     instrumented_steps = 0
-    if not timed_events:
+    if args.full and not timed_events:
         # per-launch durations under the contended submission (and the only per-kernel figures of a multi-rank run): a few
         # extra steps with HIP events on, outside the timed regions
         for c in ctxs:
@@ -449,8 +466,8 @@ def main():
     parked_frac = None
     evals_made = 0
     evals_frac = None
-    if world == 1:
-        c0 = ctxs[0]
+    c0 = ctxs[0]
+    if world == 1 and args.full:
         solo_steps = max(3, min(8, args.steps))
 
         def solo_step():
@@ -476,7 +493,6 @@ def main():
             c0.set_option("score_stats", 0)
             parked_frac = pk / ev if ev else None
             evals_made = ev
-    res = pb.download()
     if evals_made:
         # staged scoring: evaluations made / evaluations of the complete H x M sweep (whole wavefronts, like the counter)
         mv = res["stats"]["numMatchesValid"].astype(np.int64)
@@ -486,7 +502,7 @@ def main():
     # and all configs/*), same sequence, ONE launch chain, HIP events around every kernel; results go to a second output
     # block so that `res` above stays the timed workload's
     other_modes = None
-    if world == 1 and not args.no_other_modes:
+    if world == 1 and args.full and not args.no_other_modes:
         other_modes = {}
         pb2 = PairBatchDevice(seq["pairs"], fs.max_kpts, device=str(dev))
         legs = [("E0/fixed/4096", 0, EST_FIXED, 4096, 1), ("E0/ransac/487", 0, EST_RANSAC, 487, 1)]
@@ -622,118 +638,119 @@ def main():
         score = ({1: "fast", 2: "mfma"}.get(ctx.get_option("score"), "exact") if args.error_version == 1 else
                  ("fast" if (args.error_version in (0, 4) and ctx.get_option("score") >= 1) else "exact"))
 
-        def kernel_bounds(kms, pairs_per_launch):
-            """What actually bounds the two sweeps (the path is compute-bound, not HBM-bound): achieved rate of the
-            bounding unit / its nominal peak (MI355X_MICROARCH.md).  Instruction counts: profiles/isa_mix.json."""
-            out = {}
-            if "ps_hamming_mfma" in kms:
-                flops = 2.0 * 256.0 * args.kpts * args.kpts * pairs_per_launch
-                ach = flops / (kms["ps_hamming_mfma"] * 1e-3) / 1e12
-                out["ps_hamming_mfma"] = {"bound": "mfma", "dtype": "fp4 (e2m1) x fp4 -> f32", "achieved": ach,
-                                          "peak": MFMA_FP4_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                          "frac": ach / MFMA_FP4_PEAK_TFLOPS}
-            vk = {"ps_hamming_nn": (VALU_PER_UNIT["ps_hamming_nn"], args.kpts * float(args.kpts) * pairs_per_launch / 64.0),
-                  # evaluations the scoring step really made (staged scoring: a fraction of the complete H x M sweep; the
-                  # counter of the statistics pass), not the sweep it stands for
-                  "ps_ransac_score": (VALU_PER_UNIT["ps_ransac_score_%s<%d>" % (score, args.error_version)]
-                                      if ("ps_ransac_score_%s<%d>" % (score, args.error_version)) in VALU_PER_UNIT else None,
-                                      (evals_made / 64.0 * pairs_per_launch / P) if evals_made
-                                      else Hs * m_valid * pairs_per_launch / 64.0)}
-            for name, (per_unit, wave_units) in vk.items():
-                if name in kms and per_unit:
-                    ach = wave_units * per_unit * 64.0 / (kms[name] * 1e-3) / 1e12
-                    out[name] = {"bound": "valu", "valu_instructions_per_unit": per_unit, "instruction_counts_from": ISA_MIX_SOURCE, "achieved": ach,
-                                 "peak": VALU_PEAK_TOPS, "unit": "T lane-instructions/s", "frac": ach / VALU_PEAK_TOPS}
-                    pk = PK_PER_UNIT.get("%s_%s<%d>" % (name, score, args.error_version)) if name == "ps_ransac_score" else None
-                    if pk:
-                        # f32 lane OPERATIONS (a packed instruction = two): the figure to hold against the f32 vector peak
-                        out[name]["lane_ops_per_unit"] = per_unit + pk
-                        out[name]["achieved_lane_ops"] = ach * (per_unit + pk) / per_unit
-                        out[name]["frac_lane_ops"] = out[name]["achieved_lane_ops"] / VALU_PEAK_TOPS
-                    if name == "ps_ransac_score" and evals_made:
-                        out[name]["note"] = ("instructions of the evaluation loops only (evaluations really made x instructions "
-                                             "per evaluation; stage 1's pre-tested front costs less than that per evaluation); the "
-                                             "per-hypothesis prologue (sample -> Umeyama -> SVD: measured per wavefront in "
-                                             "profiles/<tag>/sq_counters_by_grid.json) and the reorder launch are inside the time "
-                                             "but not in the count; `all_in` next to this has every vector instruction of the step")
-                        out[name]["complete_sweep_equivalent"] = Hs * m_valid * pairs_per_launch * per_unit / (kms[name] * 1e-3) / 1e12
-            return out
+        if args.full:
+            def kernel_bounds(kms, pairs_per_launch):
+                """What actually bounds the two sweeps (the path is compute-bound, not HBM-bound): achieved rate of the
+                bounding unit / its nominal peak (MI355X_MICROARCH.md).  Instruction counts: profiles/isa_mix.json."""
+                out = {}
+                if "ps_hamming_mfma" in kms:
+                    flops = 2.0 * 256.0 * args.kpts * args.kpts * pairs_per_launch
+                    ach = flops / (kms["ps_hamming_mfma"] * 1e-3) / 1e12
+                    out["ps_hamming_mfma"] = {"bound": "mfma", "dtype": "fp4 (e2m1) x fp4 -> f32", "achieved": ach,
+                                              "peak": MFMA_FP4_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                              "frac": ach / MFMA_FP4_PEAK_TFLOPS}
+                vk = {"ps_hamming_nn": (VALU_PER_UNIT["ps_hamming_nn"], args.kpts * float(args.kpts) * pairs_per_launch / 64.0),
+                      # evaluations the scoring step really made (staged scoring: a fraction of the complete H x M sweep; the
+                      # counter of the statistics pass), not the sweep it stands for
+                      "ps_ransac_score": (VALU_PER_UNIT["ps_ransac_score_%s<%d>" % (score, args.error_version)]
+                                          if ("ps_ransac_score_%s<%d>" % (score, args.error_version)) in VALU_PER_UNIT else None,
+                                          (evals_made / 64.0 * pairs_per_launch / P) if evals_made
+                                          else Hs * m_valid * pairs_per_launch / 64.0)}
+                for name, (per_unit, wave_units) in vk.items():
+                    if name in kms and per_unit:
+                        ach = wave_units * per_unit * 64.0 / (kms[name] * 1e-3) / 1e12
+                        out[name] = {"bound": "valu", "valu_instructions_per_unit": per_unit, "instruction_counts_from": ISA_MIX_SOURCE, "achieved": ach,
+                                     "peak": VALU_PEAK_TOPS, "unit": "T lane-instructions/s", "frac": ach / VALU_PEAK_TOPS}
+                        pk = PK_PER_UNIT.get("%s_%s<%d>" % (name, score, args.error_version)) if name == "ps_ransac_score" else None
+                        if pk:
+                            # f32 lane OPERATIONS (a packed instruction = two): the figure to hold against the f32 vector peak
+                            out[name]["lane_ops_per_unit"] = per_unit + pk
+                            out[name]["achieved_lane_ops"] = ach * (per_unit + pk) / per_unit
+                            out[name]["frac_lane_ops"] = out[name]["achieved_lane_ops"] / VALU_PEAK_TOPS
+                        if name == "ps_ransac_score" and evals_made:
+                            out[name]["note"] = ("instructions of the evaluation loops only (evaluations really made x instructions "
+                                                 "per evaluation; stage 1's pre-tested front costs less than that per evaluation); the "
+                                                 "per-hypothesis prologue (sample -> Umeyama -> SVD: measured per wavefront in "
+                                                 "profiles/<tag>/sq_counters_by_grid.json) and the reorder launch are inside the time "
+                                                 "but not in the count; `all_in` next to this has every vector instruction of the step")
+                            out[name]["complete_sweep_equivalent"] = Hs * m_valid * pairs_per_launch * per_unit / (kms[name] * 1e-3) / 1e12
+                return out
 
-        rk = solo if solo else kern                      # kernels' own durations when the single-chain leg ran
-        r_pairs = P if (solo or queue_whole) else P / S
-        dom = max((k for k in rk if k != "ps_expand_query_fp4"), key=rk.get)
-        dom_ms = rk[dom]
-        achieved = bytes_per_pair * r_pairs / (dom_ms * 1e-3) / 1e9
-        bounds_solo = kernel_bounds(rk, r_pairs)
-        traffic = None
-        tf = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tf):
+            rk = solo if solo else kern                      # kernels' own durations when the single-chain leg ran
+            r_pairs = P if (solo or queue_whole) else P / S
+            dom = max((k for k in rk if k != "ps_expand_query_fp4"), key=rk.get)
+            dom_ms = rk[dom]
+            achieved = bytes_per_pair * r_pairs / (dom_ms * 1e-3) / 1e9
+            bounds_solo = kernel_bounds(rk, r_pairs)
+            traffic = None
+            tf = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tf):
+                try:
+                    t = json.load(open(tf))
+                    key = f"{args.frames}x{args.kpts}xH{args.hyp}xE{args.error_version}x{args.estimator}x{matcher}x{score}"
+                    traffic = t.get(key, {}).get(dom)
+                    # pipe-busy fractions of the same profiled workload (SQ counters of the rocprofv3 pass next to the
+                    # traffic pass): share of the kernel's cycles in which the vector ALU / the matrix pipe of a SIMD is busy
+                    sq = json.load(open(os.path.join(ROOT, os.path.dirname(t[key]["_source"]), "sq_counters.json")))
+                    src = os.path.dirname(t[key]["_source"]) + "/sq_counters.json (profiled run, not this one)"
+                    step_of = {"ps_ransac_score_fast": "ps_ransac_score", "ps_stage_reorder": "ps_ransac_score",
+                               "ps_ransac_score_euclid": "ps_ransac_score", "ps_hamming_mfma_fused": "ps_hamming_mfma"}
+                    acc, parts = {}, {}
+                    for kname, c in sq.items():
+                        short = kname.split("<")[0]
+                        short = step_of.get(short, short)
+                        if not c.get("GRBM_GUI_ACTIVE"):
+                            continue
+                        a_ = acc.setdefault(short, {})
+                        for cn in ("GRBM_GUI_ACTIVE", "SQ_ACTIVE_INST_VALU", "SQ_VALU_MFMA_BUSY_CYCLES", "SQ_INSTS_VALU", "SQ_INSTS_SALU"):
+                            a_[cn] = a_.get(cn, 0.0) + float(c.get(cn, 0.0))
+                        parts.setdefault(short, {})[kname] = c
+
+                    def busy(c):
+                        cyc = c["GRBM_GUI_ACTIVE"] / 8.0 * 1024.0      # kernel cycles x SIMDs (8 XCDs report separately)
+                        return {"valu_active_frac": 4.0 * c.get("SQ_ACTIVE_INST_VALU", 0.0) / cyc,
+                                "mfma_busy_frac": c.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0) / cyc}
+
+                    for short, c in acc.items():
+                        if short not in bounds_solo:
+                            continue
+                        # the STEP's figure: the counters of every launch of the step summed (the scoring step is six launches
+                        # of four kernels; round 3's line let the last kernel of the file win)
+                        pb_ = busy(c)
+                        pb_["source"] = src
+                        if len(parts[short]) > 1:
+                            pb_["by_kernel"] = {k: busy(v) for k, v in parts[short].items()}
+                        bounds_solo[short]["pipe_busy_pmc"] = pb_
+                        if short in rk and c.get("SQ_INSTS_VALU"):
+                            # ALL vector instructions the step issued (prologue, stages, reorder included) over the step's
+                            # own duration in THIS run: the all-in rate next to the loops-only `frac`
+                            allin = c["SQ_INSTS_VALU"] * 64.0 / (rk[short] * 1e-3) / 1e12
+                            bounds_solo[short]["all_in"] = {"valu_wave_instructions_per_step": c["SQ_INSTS_VALU"],
+                                                            "salu_instructions_per_step": c.get("SQ_INSTS_SALU"),
+                                                            "achieved": allin, "unit": "T lane-instructions/s",
+                                                            "frac": allin / VALU_PEAK_TOPS,
+                                                            "note": "SQ_INSTS_VALU of the profiled run / this run's duration"}
+                except Exception:
+                    pass
+            # What the step needs of the chip's ISSUE capacity -- the unit that binds it (DESIGN.md section 4): busy SIMD-cycles of the
+            # profiled run (4 cycles per vector wave-instruction, SQ_ACTIVE_INST_VALU, + the matrix pipe's busy cycles, which add up
+            # on gfx950) over 1024 SIMDs at 2.4 GHz, against THIS run's time per step
+            issue = None
             try:
-                t = json.load(open(tf))
+                t = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
                 key = f"{args.frames}x{args.kpts}xH{args.hyp}xE{args.error_version}x{args.estimator}x{matcher}x{score}"
-                traffic = t.get(key, {}).get(dom)
-                # pipe-busy fractions of the same profiled workload (SQ counters of the rocprofv3 pass next to the
-                # traffic pass): share of the kernel's cycles in which the vector ALU / the matrix pipe of a SIMD is busy
-                sq = json.load(open(os.path.join(ROOT, os.path.dirname(t[key]["_source"]), "sq_counters.json")))
-                src = os.path.dirname(t[key]["_source"]) + "/sq_counters.json (profiled run, not this one)"
-                step_of = {"ps_ransac_score_fast": "ps_ransac_score", "ps_stage_reorder": "ps_ransac_score",
-                           "ps_ransac_score_euclid": "ps_ransac_score", "ps_hamming_mfma_fused": "ps_hamming_mfma"}
-                acc, parts = {}, {}
-                for kname, c in sq.items():
-                    short = kname.split("<")[0]
-                    short = step_of.get(short, short)
-                    if not c.get("GRBM_GUI_ACTIVE"):
-                        continue
-                    a_ = acc.setdefault(short, {})
-                    for cn in ("GRBM_GUI_ACTIVE", "SQ_ACTIVE_INST_VALU", "SQ_VALU_MFMA_BUSY_CYCLES", "SQ_INSTS_VALU", "SQ_INSTS_SALU"):
-                        a_[cn] = a_.get(cn, 0.0) + float(c.get(cn, 0.0))
-                    parts.setdefault(short, {})[kname] = c
-
-                def busy(c):
-                    cyc = c["GRBM_GUI_ACTIVE"] / 8.0 * 1024.0      # kernel cycles x SIMDs (8 XCDs report separately)
-                    return {"valu_active_frac": 4.0 * c.get("SQ_ACTIVE_INST_VALU", 0.0) / cyc,
-                            "mfma_busy_frac": c.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0) / cyc}
-
-                for short, c in acc.items():
-                    if short not in bounds_solo:
-                        continue
-                    # the STEP's figure: the counters of every launch of the step summed (the scoring step is six launches
-                    # of four kernels; round 3's line let the last kernel of the file win)
-                    pb_ = busy(c)
-                    pb_["source"] = src
-                    if len(parts[short]) > 1:
-                        pb_["by_kernel"] = {k: busy(v) for k, v in parts[short].items()}
-                    bounds_solo[short]["pipe_busy_pmc"] = pb_
-                    if short in rk and c.get("SQ_INSTS_VALU"):
-                        # ALL vector instructions the step issued (prologue, stages, reorder included) over the step's
-                        # own duration in THIS run: the all-in rate next to the loops-only `frac`
-                        allin = c["SQ_INSTS_VALU"] * 64.0 / (rk[short] * 1e-3) / 1e12
-                        bounds_solo[short]["all_in"] = {"valu_wave_instructions_per_step": c["SQ_INSTS_VALU"],
-                                                        "salu_instructions_per_step": c.get("SQ_INSTS_SALU"),
-                                                        "achieved": allin, "unit": "T lane-instructions/s",
-                                                        "frac": allin / VALU_PEAK_TOPS,
-                                                        "note": "SQ_INSTS_VALU of the profiled run / this run's duration"}
+                sqp = os.path.join(ROOT, os.path.dirname(t[key]["_source"]), "sq_counters.json")
+                sq = json.load(open(sqp))
+                busy = sum(4.0 * float(c.get("SQ_ACTIVE_INST_VALU", 0.0)) + float(c.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0)) for c in sq.values())
+                floor_ms = busy / (1024.0 * 2.4e9) * 1e3
+                step_ms = elapsed / args.steps * 1e3
+                issue = {"bound": "issue (vector + matrix pipe, 1024 SIMDs x 2.4 GHz)", "busy_simd_cycles_per_step": busy,
+                         "ms_per_step_at_full_issue": floor_ms, "ms_per_step": step_ms, "frac": floor_ms / step_ms,
+                         "source": os.path.relpath(sqp, ROOT) + " (profiled single-chain run of the same workload, not this one)",
+                         "note": "the two pipes' busy cycles are SUMMED: the time they need if they never overlap; with four chains they "
+                                 "overlap by a few per cent, so frac can read 1.00 - 1.03"}
             except Exception:
                 pass
-        # What the step needs of the chip's ISSUE capacity -- the unit that binds it (DESIGN.md section 4): busy SIMD-cycles of the
-        # profiled run (4 cycles per vector wave-instruction, SQ_ACTIVE_INST_VALU, + the matrix pipe's busy cycles, which add up
-        # on gfx950) over 1024 SIMDs at 2.4 GHz, against THIS run's time per step
-        issue = None
-        try:
-            t = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-            key = f"{args.frames}x{args.kpts}xH{args.hyp}xE{args.error_version}x{args.estimator}x{matcher}x{score}"
-            sqp = os.path.join(ROOT, os.path.dirname(t[key]["_source"]), "sq_counters.json")
-            sq = json.load(open(sqp))
-            busy = sum(4.0 * float(c.get("SQ_ACTIVE_INST_VALU", 0.0)) + float(c.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0)) for c in sq.values())
-            floor_ms = busy / (1024.0 * 2.4e9) * 1e3
-            step_ms = elapsed / args.steps * 1e3
-            issue = {"bound": "issue (vector + matrix pipe, 1024 SIMDs x 2.4 GHz)", "busy_simd_cycles_per_step": busy,
-                     "ms_per_step_at_full_issue": floor_ms, "ms_per_step": step_ms, "frac": floor_ms / step_ms,
-                     "source": os.path.relpath(sqp, ROOT) + " (profiled single-chain run of the same workload, not this one)",
-                     "note": "the two pipes' busy cycles are SUMMED: the time they need if they never overlap; with four chains they "
-                             "overlap by a few per cent, so frac can read 1.00 - 1.03"}
-        except Exception:
-            pass
         out = {
             "metric": "frame-pairs/s (match+RANSAC+Kabsch), 640x480 @ 2000 kpts",
             "value": value, "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -769,42 +786,75 @@ def main():
                 "mean_inliers": float(stats["numInliers"].mean()),
                 "accepted_pairs": int(stats["accepted"].sum()),
             },
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "algorithmic_bytes_per_pair": bytes_per_pair, "pairs_per_launch": r_pairs,
-                         "avg_launch_ms": dom_ms,
-                         "leg": ("single launch chain (--streams 1 equivalent), run inside this process after the timed "
-                                 "region: the kernel alone on the chip" if solo else "timed region"),
-                         "bound_actual": bounds_solo.get(dom, {}).get("bound"),
-                         "bound_actual_frac": bounds_solo.get(dom, {}).get("frac"),
-                         "issue": issue,
-                         "note": "the path is compute-bound (VALU issue for the scoring sweep, MFMA for the Hamming "
-                                 "sweep), not HBM-bound: see kernel_bounds"},
-            "kernel_ms": rk,
-            "kernel_bounds": bounds_solo,
-            "single_chain": ({"ms_per_step": solo_ms_per_step, "pairs_per_s": P / (solo_ms_per_step * 1e-3),
-                              "kernel_ms_sum": sum(solo.values())} if solo else None),
-            "timed_region_kernel_ms": kern,
-            "score_parked_frac": parked_frac,
-            "score_evals_frac": evals_frac,
             "staged_scoring": bool(ctx.get_option("prune")),
-            "other_modes": other_modes,
-            "streams_note": (None if S == 1 else
-                             f"value / ms_per_step: {S} sub-batch chains on {S} HIP streams (join={args.join}); "
-                             "timed_region_kernel_ms are per-launch durations of sub-batches measured while the other "
-                             "chains' kernels share the CUs (they sum to more than ms_per_step); kernel_ms / roofline / "
-                             "kernel_bounds come from the single-chain leg (DESIGN.md section 5)"),
         }
+        if args.full:
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                             "algorithmic_bytes_per_pair": bytes_per_pair, "pairs_per_launch": r_pairs,
+                             "avg_launch_ms": dom_ms,
+                             "leg": ("single launch chain (--streams 1 equivalent), run inside this process after the timed "
+                                     "region: the kernel alone on the chip" if solo else "timed region"),
+                             "bound_actual": bounds_solo.get(dom, {}).get("bound"),
+                             "bound_actual_frac": bounds_solo.get(dom, {}).get("frac"),
+                             "issue": issue,
+                             "note": "the path is compute-bound (VALU issue for the scoring sweep, MFMA for the Hamming "
+                                     "sweep), not HBM-bound: see kernel_bounds"},
+                "kernel_ms": rk,
+                "kernel_bounds": bounds_solo,
+                "single_chain": ({"ms_per_step": solo_ms_per_step, "pairs_per_s": P / (solo_ms_per_step * 1e-3),
+                                  "kernel_ms_sum": sum(solo.values())} if solo else None),
+                "timed_region_kernel_ms": kern,
+                "score_parked_frac": parked_frac,
+                "score_evals_frac": evals_frac,
+                "other_modes": other_modes,
+                "streams_note": (None if S == 1 else
+                                 f"value / ms_per_step: {S} sub-batch chains on {S} HIP streams (join={args.join}); "
+                                 "timed_region_kernel_ms are per-launch durations of sub-batches measured while the other "
+                                 "chains' kernels share the CUs (they sum to more than ms_per_step); kernel_ms / roofline / "
+                                 "kernel_bounds come from the single-chain leg (DESIGN.md section 5)"),
+            })
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
         # the CPU figure beside the line, on rank 0's host cores -- after the closing barrier of a multi-rank run, so that no
         # rank waits in a collective while rank 0 computes (its peers have left; their GPUs are idle, the cores are rank 0's)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out.update(cpu_baseline(args, seq, prm, cfg, est))
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: the arrays one step hands its caller (PairBatchDevice.download()) as <path>/<name>.npy, float32 where that
+    is exact (indices, masks, distances, poses) and float64 for the statistics.  Match slots beyond a pair's numMatches hold
+    nothing the caller reads and are written as 0.  Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of the pairs is written
+    (pair_index.npy names them)."""
+    num = res["numMatches"].astype(np.int64)
+    P, cap = res["matches"].shape
+    per_pair = 5 * cap * 4 + 16 * 4 + 8 * (2 + len(res["stats"].dtype.names))     # bytes written per pair
+    idx = np.arange(P)
+    if P * per_pair > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(P, DUMP_LIMIT_BYTES // per_pair, replace=False))
+    valid = np.arange(cap)[None, :] < num[idx, None]
+    m = res["matches"][idx]
+    arrays = {"pair_index": idx.astype(np.float64), "num_matches": num[idx].astype(np.float64),
+              "match_query_idx": np.where(valid, m["queryIdx"], 0).astype(np.float32),
+              "match_train_idx": np.where(valid, m["trainIdx"], 0).astype(np.float32),
+              "match_img_idx": np.where(valid, m["imgIdx"], 0).astype(np.float32),
+              "match_distance": np.where(valid, m["distance"], 0).astype(np.float32),
+              "inlier_mask": np.where(valid, res["inlierMask"][idx], 0).astype(np.float32),
+              "pose": res["pose"][idx].astype(np.float32)}
+    for name in res["stats"].dtype.names:
+        arrays["stats_" + name] = res["stats"][name][idx].astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 PCIE_GEN5_X16_GBS = 63.0        # PCIe 5.0 x16, one direction, after 128b/130b encoding (the MI355X host link)

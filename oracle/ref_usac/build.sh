@@ -11,8 +11,11 @@ REF=${PUTSLAM_REFERENCE:-/root/reference}
 OUT=$ROOT/oracle/_ref
 mkdir -p "$OUT/usac_inc/src" "$OUT/usac_inc/include"
 ln -sfn "$REF/include/putslam/USAC" "$OUT/usac_inc/include/USAC"
-make -s -C "$ROOT/oracle" >/dev/null
-g++ -O2 -std=c++14 -w -I "$REF/include/putslam/USAC" -I "$OUT/usac_inc/src" "$HERE/usac_harness.cpp" -o "$OUT/usac_harness" \
-    -L "$ROOT/oracle/_build" -lputslam_oracle -Wl,-rpath,"$ROOT/oracle/_build"
+# the oracle's source is compiled into the harness (portable flags: the harness only draws the oracle's integer sample stream), so
+# the binary needs no library at the path it was built in and runs wherever oracle/_ref/ is
+gcc -O2 -std=c11 -fPIC -ffp-contract=off -fno-fast-math -fopenmp -w -c "$ROOT/oracle/putslam_oracle.c" -o "$OUT/putslam_oracle.o"
+g++ -O2 -std=c++14 -w -I "$REF/include/putslam/USAC" -I "$OUT/usac_inc/src" "$HERE/usac_harness.cpp" "$OUT/putslam_oracle.o" \
+    -o "$OUT/usac_harness" -fopenmp -lm
+rm -f "$OUT/putslam_oracle.o"
 rm -f "$OUT/usac_inc/include/USAC"   # (a link into /root/reference must not travel)
 echo "$OUT/usac_harness"

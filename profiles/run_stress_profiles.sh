@@ -11,7 +11,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 for E in 0 1; do
   OUT=$ROOT/gpurun_out/prof_${TAG}_E$E
   mkdir -p $OUT
-  ARGS="--preset stress --error-version $E --streams 1 --submit python --steps 10 --warmup 10 --warm-seconds 0 --repeats 1 --no-other-modes --no-cpu-baseline"
+  ARGS="--full --preset stress --error-version $E --streams 1 --submit python --steps 10 --warmup 10 --warm-seconds 0 --repeats 1 --no-other-modes --no-cpu-baseline"
   cd /tmp && export TMPDIR=/tmp
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 $ROOT/bench.py $ARGS > $OUT/bench_trace.log 2>&1
   timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o bench -- python3 $ROOT/bench.py $ARGS > $OUT/bench_fetch.log 2>&1

@@ -8,7 +8,7 @@ for v in _prev "" _prev "" _prev ""; do
   lib=$PWD/putslam_amd/libputslam_hip$v.so
   [ -f $lib ] || continue
   i=$((i+1))
-  PUTSLAM_HIP_LIB=$lib python3 bench.py --streams 1 --steps 20 --warmup 20 --repeats 3 --no-cpu-baseline --no-other-modes "$@" > $out/run${i}${v:-_new}.json 2>> $out/err.txt
+  PUTSLAM_HIP_LIB=$lib python3 bench.py --full --streams 1 --steps 20 --warmup 20 --repeats 3 --no-cpu-baseline --no-other-modes "$@" > $out/run${i}${v:-_new}.json 2>> $out/err.txt
 done
 python3 - <<PY
 import json,glob

@@ -8,7 +8,7 @@ for rep in 1 2 3; do for v in $sufs; do
   lib=$PWD/putslam_amd/libputslam_hip$v.so
   [ -f $lib ] || continue
   i=$((i+1))
-  PUTSLAM_HIP_LIB=$lib python3 bench.py --streams 1 --steps 20 --warmup 20 --repeats 3 --no-cpu-baseline --no-other-modes "$@" > $out/run${i}${v:-_cur}.json 2>> $out/err.txt
+  PUTSLAM_HIP_LIB=$lib python3 bench.py --full --streams 1 --steps 20 --warmup 20 --repeats 3 --no-cpu-baseline --no-other-modes "$@" > $out/run${i}${v:-_cur}.json 2>> $out/err.txt
 done; done
 python3 - <<PY
 import json,glob

@@ -1,5 +1,5 @@
 # multi-stream bench configurations (bench.py --streams S --join step|end), three repeats of the two candidates
-B="python bench.py --steps 40 --warmup 3 --no-cpu-baseline"
+B="python bench.py --full --steps 40 --warmup 3 --no-cpu-baseline"
 show() { python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$1', round(d['value']), round(d['ms_per_step'],3), {k:round(v,3) for k,v in d['kernel_ms'].items()})"; }

@@ -102,7 +102,9 @@ def test_queue_many_batches_tickets_and_stream_wait(ctx, oracle):
 def test_batches_sharing_an_output_block_are_kept_in_order(ctx):
     """Whole batches run side by side on different chains; a host that reuses ONE output block for consecutive batches (different
     seeds: different results) must still find the LAST batch's results there -- the queue queues such a batch behind the one that
-    is in flight on the other chain instead of letting them race."""
+    is in flight on the other chain instead of letting them race.  A batch whose predecessor on the block is already complete when
+    it is submitted has nothing to race and goes to the chains in turn: whether the GPU finishes a batch before the host submits the
+    next one is timing, so the test holds every chain change to that rule instead of expecting one chain per round."""
     from putslam_amd.device_batch import FrameSetDevice, PairBatchDevice, run_pairs, run_pairs_queue
     seq = synth.make_sequence(40, 600, config=3, index=4711)
     prm = default_ransac_params(REPROJECTION_ERROR)
@@ -110,18 +112,22 @@ def test_batches_sharing_an_output_block_are_kept_in_order(ctx):
     out = PairBatchDevice(seq["pairs"], fs.max_kpts)
     q = api.BatchQueue(ctx, 2)
     for rnd in range(5):
-        chains_used = set()
+        prev = None
         for b in range(6):
             cfg, _ = make_config(EST_FIXED, 1500, seed=50 + 10 * rnd + b)
             t = run_pairs_queue(q, prm, cfg, TUM_FR1_K, fs, out)
             sp = q.last_split()
-            chains_used.add([i for i in range(2) if sp[i + 1] > sp[i]][0])
+            chain = [i for i in range(2) if sp[i + 1] > sp[i]][0]
+            if prev is not None and chain != prev[1]:
+                # back to back on one block: another chain only when the batch before was complete at submission (completion
+                # is for good, so it still reads complete now; one that had been in flight would have kept the chain)
+                assert q.query(prev[0]), f"round {rnd}, batch {b}: chain {prev[1]} -> {chain} while the batch before was in flight"
+            prev = (t, chain)
         q.wait(t)
         assert q.query(t)
         ref = PairBatchDevice(seq["pairs"], fs.max_kpts)
         run_pairs(ctx, prm, cfg, TUM_FR1_K, fs, ref)
         _compare(out.download(), ref.download(), len(seq["pairs"]))
-        assert len(chains_used) == 1                      # back to back on one block: one chain
         q.synchronize()
     q.close()
 

@@ -232,3 +232,41 @@ def test_pack_records_device_equals_the_torch_packing(ctx):
     part = sharding.pack_records_device(ctx, pb.pose[2:7], st32[2:7])
     torch.cuda.synchronize()
     assert part.cpu().numpy().tobytes() == want[2:7].cpu().numpy().tobytes()
+
+
+def test_bench_dump_outputs_are_the_timed_steps_results(ctx, tmp_path):
+    """--dump-outputs: what the last timed step returned -- one ps_vo_pairs_device call's results on the bench's sequence and
+    seed --, the same bytes from two runs with the same arguments."""
+    from putslam_amd import synth
+    from putslam_amd._abi import EST_FIXED, REPROJECTION_ERROR, TUM_FR1_K, default_ransac_params, make_config
+    from putslam_amd.device_batch import FrameSetDevice, PairBatchDevice, run_pairs
+    bench = os.path.join(ROOT, "bench.py")
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, bench, "--gpus", "1", "--dump-outputs", str(tmp_path / d)] + ARGS,
+                           env=_env(WORLD_SIZE=1, RANK=0, LOCAL_RANK=0), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout + p.stderr
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "pose.npy" in files
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert got[f[:-4]].dtype in (np.float32, np.float64)
+        assert got[f[:-4]].tobytes() == np.load(tmp_path / "b" / f).tobytes(), f
+    seq = synth.make_sequence(14, 700, config=3, index=0)
+    cfg, _ = make_config(EST_FIXED, 768, seed=0xB0B0)
+    fs = FrameSetDevice(seq["desc"], seq["pts"], seq["nkpts"])
+    ref = PairBatchDevice(seq["pairs"], fs.max_kpts)
+    run_pairs(ctx, default_ransac_params(REPROJECTION_ERROR), cfg, TUM_FR1_K, fs, ref)
+    r = ref.download()
+    P = len(seq["pairs"])
+    assert got["pair_index"].tolist() == list(range(P))
+    assert got["pose"].tobytes() == r["pose"].tobytes()
+    assert got["num_matches"].tolist() == r["numMatches"].tolist()
+    for name in r["stats"].dtype.names:
+        assert got["stats_" + name].tolist() == r["stats"][name].tolist(), name
+    for p in range(P):
+        n = int(r["numMatches"][p])
+        assert got["match_query_idx"][p, :n].tolist() == r["matches"]["queryIdx"][p, :n].tolist()
+        assert got["match_train_idx"][p, :n].tolist() == r["matches"]["trainIdx"][p, :n].tolist()
+        assert got["match_distance"][p, :n].tobytes() == r["matches"]["distance"][p, :n].tobytes()
+        assert got["inlier_mask"][p, :n].tolist() == r["inlierMask"][p, :n].tolist()
+    assert got["stats_numInliers"].sum() > 0

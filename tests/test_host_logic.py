@@ -177,3 +177,42 @@ def test_bench_launcher_sets_the_rank_environment_and_returns_the_worst_exit_cod
     assert len(lines) == 1 and lines[0].split()[:5] == ["rank", "0", "0", "4", "127.0.0.1"]      # only rank 0's stdout comes through
     bad = subprocess.run([sys.executable, str(fake), "--gpus", "2", "--steps", "99"], env=env, capture_output=True, text=True, timeout=120)
     assert bad.returncode == 3
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_samples_beyond_the_limit(tmp_path):
+    """bench.py --dump-outputs: every array as float32 / float64, match slots beyond a pair's count zeroed, and beyond the size
+    limit a fixed sample of the pairs (the same one every run), named by pair_index.npy."""
+    import importlib.util
+    from putslam_amd._abi import DMATCH_DTYPE, STATS_DTYPE
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    P, cap = 40, 64
+    m = np.zeros((P, cap), DMATCH_DTYPE)
+    m["queryIdx"] = rng.integers(0, 1000, (P, cap))
+    m["trainIdx"] = rng.integers(0, 1000, (P, cap))
+    m["distance"] = rng.random((P, cap), np.float32)
+    stats = np.zeros(P, STATS_DTYPE)
+    stats["numInliers"] = rng.integers(0, cap, P)
+    stats["pointInlierRatio"] = rng.random(P)
+    res = dict(matches=m, numMatches=rng.integers(0, cap + 1, P).astype(np.int32), inlierMask=rng.integers(0, 2, (P, cap)).astype(np.uint8),
+               pose=rng.random((P, 16), np.float32), stats=stats)
+    bench.dump_outputs(str(tmp_path / "all"), res)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["pair_index"].tolist() == list(range(P)) and got["pose"].tobytes() == res["pose"].tobytes()
+    assert got["stats_pointInlierRatio"].tobytes() == stats["pointInlierRatio"].tobytes()
+    for p in range(P):
+        n = res["numMatches"][p]
+        assert (got["match_query_idx"][p, :n] == m["queryIdx"][p, :n]).all() and not got["match_query_idx"][p, n:].any()
+        assert (got["inlier_mask"][p, :n] == res["inlierMask"][p, :n]).all() and not got["inlier_mask"][p, n:].any()
+    bench.DUMP_LIMIT_BYTES = 10 * 1500
+    bench.dump_outputs(str(tmp_path / "a"), res)
+    bench.dump_outputs(str(tmp_path / "b"), res)
+    idx = np.load(tmp_path / "a" / "pair_index.npy")
+    assert 0 < len(idx) < P and np.all(np.diff(idx) > 0)
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= bench.DUMP_LIMIT_BYTES
+    for f in os.listdir(tmp_path / "a"):
+        assert np.load(tmp_path / "a" / f).tobytes() == np.load(tmp_path / "b" / f).tobytes()
+    assert np.load(tmp_path / "a" / "pose.npy").tobytes() == res["pose"][idx.astype(int)].tobytes()

@@ -83,10 +83,15 @@ def test_end_to_end_usac_runs_equal_the_reference_loop(oracle):
 def test_live_harness_agrees_on_fresh_cases(oracle):
     """Where the harness binary is present (the build container): new random cases, answered by the reference's code now."""
     rng = np.random.default_rng(int.from_bytes(os.urandom(4), "little"))
+    # (a harness from an earlier recipe links the oracle's library by the path of the tree it was built in: this tree's own build
+    #  of the same library is handed to the loader, so the harness runs wherever oracle/_ref/ was copied to)
+    lib_dir = os.path.dirname(os.path.abspath(oracle._SO))
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(x for x in (lib_dir, os.environ.get("LD_LIBRARY_PATH")) if x))
     # (counts from 50 up for the larger M: below, the reference's cast is undefined -- test_stopping_rule_equals_the_reference)
     q = [(int(c), int(M)) for M in rng.integers(3, 30000, 40) for c in rng.integers(50 if M > 1700 else 0, M + 1, 60)]
-    p = subprocess.run([HARNESS], input="stop %d\n" % len(q) + "".join("%d %d\n" % t for t in q), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0
+    p = subprocess.run([HARNESS], input="stop %d\n" % len(q) + "".join("%d %d\n" % t for t in q), capture_output=True, text=True,
+                       timeout=300, env=env)
+    assert p.returncode == 0, p.stderr
     want = [int(x) for x in p.stdout.split()]
     assert [oracle.usac_stopping(a, b, 3) for a, b in q] == want
     for _ in range(20):
@@ -94,6 +99,7 @@ def test_live_harness_agrees_on_fresh_cases(oracle):
         counts = np.minimum(rng.integers(0, max(4, M // 3), n) * (rng.random(n) < 0.1) + rng.integers(0, 5, n), M).astype(np.int32)
         valid = (rng.random(n) > 0.05).astype(np.int32)
         p = subprocess.run([HARNESS], input="solve %d %d\n" % (M, n) + "".join("%d %d\n" % t for t in zip(valid, counts)),
-                           capture_output=True, text=True, timeout=300)
+                           capture_output=True, text=True, timeout=300, env=env)
+        assert p.returncode == 0, p.stderr
         ok, hyp, best, stored = (int(x) for x in p.stdout.split())
         assert (hyp, best, stored) == oracle.usac_replay(valid, counts, 850000, M)
