@@ -47,6 +47,8 @@ constexpr StagedFrom kStagedFromEuclidFixed = {7.8e5, 250.0}, kStagedFromReprojF
 // bench workload's shape gain 1.26 / 1.58 x with the reprojection error, 1.27 / 1.58 x with the Euclidean one)
 constexpr StagedFrom kStagedFromEuclidFixedSbs = {4.5e5, 75.0}, kStagedFromReprojFixedSbs = {3.0e5, 90.0},
                      kStagedFromEuclidAdaptiveSbs = {2.4e4, 0.0}, kStagedFromReprojAdaptiveSbs = {2.4e4, 0.0};
+constexpr int kGenPlainFrom = 2; // complete scoring generates its models by a launch of their own from this many pairs on (Plan::genPlain)
+constexpr int kMfmaTT = 4;       // train tiles per wave of the MFMA matcher (ps_hamming_mfma<TT>, ps_matcher_mfma.h)
 } // namespace
 
 namespace {
@@ -140,8 +142,14 @@ int effective_mode(int errorVersion)
     }
 }
 
+// Which kernel 3 scores a call: the value-exact ps_ransac_score (option "score" = 0, and the Mahalanobis error), else the
+// decision-exact Euclidean ps_ransac_score_euclid (errorVersion 0 / 4) or reprojection ps_ransac_score_fast (1 / 2).  Kernel 2
+// writes the records that family reads (rec_ptrs, PrepArgs::skipE / skipF).
+enum class Scoring { Value, Euclid, Reproj };
+
 struct Plan {
     int mode = 0;
+    Scoring score = Scoring::Value; // (make_plan)
     int H = 0;        // hypotheses scored
     int minRun = 3;
     ScoreConsts sc{};
@@ -159,6 +167,7 @@ struct Plan {
     int bailSlot = 0;       // ... for this kind of call (PsContext::bailKinds)
     int prefix = 0;     // 256 (fixed schedule) or 64 (adaptive schedules)
     int lastStage = 0;  // staged scoring: 1 = ONE stage after the prefix (adaptive schedules without reordering), else kStages
+    bool big0 = false;  // Scoring::Reproj: stage 0 or the complete scoring runs the build for big launches (prepare_score)
 };
 
 int make_plan(PsContext *ctx, const PsRansacParams *prm, const PsRansacConfig *cfg, const float *K, int cap,
@@ -171,6 +180,8 @@ int make_plan(PsContext *ctx, const PsRansacParams *prm, const PsRansacConfig *c
     if (cfg->estimator < PS_EST_RANSAC || cfg->estimator > PS_EST_FIXED)
         return fail(ctx, PS_ERR_BAD_ARG, "unknown estimator");
     pl.mode = effective_mode(prm->errorVersion);
+    if (ctx->scoreFast == 0 || pl.mode == PS_MAHALANOBIS_ERROR) pl.score = Scoring::Value;
+    else pl.score = (pl.mode == PS_EUCLIDEAN_ERROR || pl.mode == PS_ADAPTIVE_ERROR) ? Scoring::Euclid : Scoring::Reproj;
     float k[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (K) memcpy(k, K, sizeof k);
     pl.sc.fx = k[0]; pl.sc.fy = k[4]; pl.sc.cx = k[2]; pl.sc.cy = k[5];
@@ -274,15 +285,10 @@ void tick(PsContext *ctx, int slot, bool stop)
 
 // The Euclidean fast scoring kernel reads its own pair-interleaved record, kept in the block the reprojection kernels use
 // for theirs (recF): kernel 2 writes one or the other.
-bool with_euclid_fast(const PsContext *ctx, int mode)
-{
-    return ctx->scoreFast != 0 && (mode == PS_EUCLIDEAN_ERROR || mode == PS_ADAPTIVE_ERROR);
-}
-
-RecPtrs rec_ptrs(PsContext *ctx, int cap, int mode)
+RecPtrs rec_ptrs(PsContext *ctx, Scoring score)
 {
     RecPtrs r;
-    r.G = with_euclid_fast(ctx, mode) ? (float *)ctx->recF.p : nullptr;
+    r.G = score == Scoring::Euclid ? (float *)ctx->recF.p : nullptr;
     r.A = (float4 *)ctx->recA.p; r.B = (float4 *)ctx->recB.p; r.C = (float4 *)ctx->recC.p; r.D = (int4 *)ctx->recD.p;
     r.E = (float4 *)ctx->recE.p;
     r.F = (float2 *)ctx->recF.p;
@@ -311,11 +317,11 @@ void launch_score(PsContext *ctx, dim3 grid, const Plan &pl, int cap, int msplit
                        (const float2 *)ctx->cmax.p, pl.ma, pl.sc, pl.H, cap, pl.minRun, msplit, (int32_t *)ctx->counts.p);
 }
 
-// Decisions of the scoring stage that the preceding kernels need to know: how the match range is split (kernel 2 then
-// clears the counts, instead of a memset launch) and whether kernel 3 parks its models for kernel 4.
 // launches of the reprojection kernels with more work-groups than this use the packed match record (ps_score_fast.h, BIG)
 unsigned big_limit(int mode) { return mode == PS_REPROJECTION_ERROR ? 1536u : 1280u; }
 
+// Decisions of the scoring stage that the preceding kernels need to know: how the match range is split (kernel 2 then
+// clears the counts, instead of a memset launch), whether kernel 3 parks its models for kernel 4 and which records it reads.
 // complete = true: every hypothesis is scored completely whatever the batch size (ps_debug_ransac_counts returns the counts
 // themselves: the staged scoring leaves lower bounds for abandoned hypotheses)
 int prepare_score(PsContext *ctx, Plan &pl, int P, int cap, bool complete = false, bool adaptive = false, const void *dataKey = nullptr)
@@ -323,9 +329,7 @@ int prepare_score(PsContext *ctx, Plan &pl, int P, int cap, bool complete = fals
     const int H = pl.H;
     const int hb = (H + kBlock - 1) / kBlock;
     // pruned scoring: worth its second launch when the hypotheses beyond the prefix fill the chip by themselves
-    const bool prunable = with_euclid_fast(ctx, pl.mode) ||
-                          (pl.mode == PS_REPROJECTION_ERROR && ctx->scoreFast == 1) ||
-                          (pl.mode == PS_EUCLIDEAN_AND_REPROJECTION_ERROR && ctx->scoreFast != 0);
+    const bool prunable = pl.score != Scoring::Value;
     // (the later stages read the models back from HBM, 48 B per hypothesis: ps_score_fast.h)
     const size_t mbytes = (size_t)P * H * 12 * sizeof(float);
     pl.prefix = pl.sa.estimator == PS_EST_FIXED ? kPrefixFixed : kPrefixAdaptive;
@@ -341,12 +345,12 @@ int prepare_score(PsContext *ctx, Plan &pl, int P, int cap, bool complete = fals
     // section 8 knew to be 2 - 14 % off on either side; adaptive schedules gain from far smaller batches than they were given).
     // Option "prune" = 2 takes the staged form whenever the kernels have it (tests; A/B).
     const double units = (double)P * (double)(hb - 1) * (double)cap;
-    const StagedFrom sf = with_euclid_fast(ctx, pl.mode) ? (pl.sa.estimator == PS_EST_FIXED ? kStagedFromEuclidFixed : kStagedFromEuclidAdaptive)
-                                                         : (pl.sa.estimator == PS_EST_FIXED ? kStagedFromReprojFixed : kStagedFromReprojAdaptive);
+    const StagedFrom sf = pl.score == Scoring::Euclid ? (pl.sa.estimator == PS_EST_FIXED ? kStagedFromEuclidFixed : kStagedFromEuclidAdaptive)
+                                                      : (pl.sa.estimator == PS_EST_FIXED ? kStagedFromReprojFixed : kStagedFromReprojAdaptive);
     double stagedFrom = sf.base + sf.perRow * (double)cap;
     if (ctx->sideBySide >= 2) {
-        const StagedFrom sb = with_euclid_fast(ctx, pl.mode) ? (pl.sa.estimator == PS_EST_FIXED ? kStagedFromEuclidFixedSbs : kStagedFromEuclidAdaptiveSbs)
-                                                             : (pl.sa.estimator == PS_EST_FIXED ? kStagedFromReprojFixedSbs : kStagedFromReprojAdaptiveSbs);
+        const StagedFrom sb = pl.score == Scoring::Euclid ? (pl.sa.estimator == PS_EST_FIXED ? kStagedFromEuclidFixedSbs : kStagedFromEuclidAdaptiveSbs)
+                                                          : (pl.sa.estimator == PS_EST_FIXED ? kStagedFromReprojFixedSbs : kStagedFromReprojAdaptiveSbs);
         const double sbs = sb.base + sb.perRow * (double)cap;
         // (two chains hide half of one another's gaps: half way between the two crossovers, on the logarithmic scale)
         stagedFrom = ctx->sideBySide >= 3 ? sbs : std::sqrt(sbs * stagedFrom);
@@ -355,7 +359,7 @@ int prepare_score(PsContext *ctx, Plan &pl, int P, int cap, bool complete = fals
     pl.bailWatch = false;
     pl.bailSlot = 0;
     const bool willReorder = ctx->reorder == 1 || (ctx->reorder == 2 && pl.sa.estimator == PS_EST_FIXED);
-    if (adaptive && pl.prune && willReorder && ctx->bail != 0 && with_euclid_fast(ctx, pl.mode) && pl.sa.estimator == PS_EST_FIXED) {
+    if (adaptive && pl.prune && willReorder && ctx->bail != 0 && pl.score == Scoring::Euclid && pl.sa.estimator == PS_EST_FIXED) {
         if (!ctx->bailHost) {
             const size_t nb = (size_t)PsContext::kBailKinds * 2 * sizeof(unsigned);
             if (hipHostMalloc((void **)&ctx->bailHost, nb, hipHostMallocMapped) == hipSuccess &&
@@ -453,31 +457,19 @@ int prepare_score(PsContext *ctx, Plan &pl, int P, int cap, bool complete = fals
     // call for 2 ... 48 pairs (profiles/r04h/ab_gen_plain.txt).  A single pair keeps one launch: the chain's latency is all
     // there is, and a second launch costs 3 - 5 us more than it saves.
     pl.genPlain = false;
-    {
-        const bool fastKernels = with_euclid_fast(ctx, pl.mode) || (pl.mode == PS_REPROJECTION_ERROR && ctx->scoreFast == 1) ||
-                                 (pl.mode == PS_EUCLIDEAN_AND_REPROJECTION_ERROR && ctx->scoreFast != 0);
-#ifndef PS_GENPLAIN_FROM
-#define PS_GENPLAIN_FROM 2
-#endif
-        if (!pl.prune && fastKernels && ctx->genSplit != 0 && pl.msplit > 1 && P >= PS_GENPLAIN_FROM && mbytes <= ((size_t)1 << 30)) {
-            PS_ENSURE(ctx->models, mbytes);
-            pl.ma.models = (float *)ctx->models.p;
-            PS_ENSURE(ctx->validMask, (size_t)P * ((H + 63) / 64) * sizeof(unsigned long long));
-            pl.genPlain = true;
-        }
+    if (!pl.prune && pl.score != Scoring::Value && ctx->genSplit != 0 && pl.msplit > 1 && P >= kGenPlainFrom && mbytes <= ((size_t)1 << 30)) {
+        PS_ENSURE(ctx->models, mbytes);
+        pl.ma.models = (float *)ctx->models.p;
+        PS_ENSURE(ctx->validMask, (size_t)P * ((H + 63) / 64) * sizeof(unsigned long long));
+        pl.genPlain = true;
     }
     pl.pa.zeroSurvA = pl.pa.zeroSurvB = nullptr;
-    {
-        // which record form of the reprojection kernels the launches of this call read (kernel 2 writes only those:
-        // 16 + 40 bytes per match otherwise): the packed form F for launches that fill the chip and every stage after
-        // the prefix, the three-record form (A, B, E) for small ones -- the same decisions as in run_ransac_stage
-        const bool fastRep = (pl.mode == PS_REPROJECTION_ERROR && ctx->scoreFast == 1) ||
-                             (pl.mode == PS_EUCLIDEAN_AND_REPROJECTION_ERROR && ctx->scoreFast != 0);
-        const unsigned bigLimit = big_limit(pl.mode);
-        const bool firstBig = (unsigned)pl.msplit * (unsigned)P * (pl.prune ? 1u : (unsigned)hb) > bigLimit;
-        pl.pa.skipF = !(fastRep && (pl.prune || firstBig));
-        pl.pa.skipE = !(fastRep && !firstBig);
-    }
+    // which record form of the reprojection kernels the launches of this call read (kernel 2 writes only those: 16 + 40 bytes
+    // per match otherwise): the packed form F for launches that fill the chip (the build for big launches, BIG) and every stage
+    // after the prefix, the three-record form (A, B, E) for small ones
+    pl.big0 = (unsigned)pl.msplit * (unsigned)P * (pl.prune ? 1u : (unsigned)hb) > big_limit(pl.mode);
+    pl.pa.skipF = !(pl.score == Scoring::Reproj && (pl.prune || pl.big0));
+    pl.pa.skipE = !(pl.score == Scoring::Reproj && !pl.big0);
     if (pl.prune) {
         if (pl.lastStage > 1) { // (only hypotheses with a model slot are ever listed)
             PS_ENSURE(ctx->survA, (size_t)P * pl.ma.modelH * sizeof(int32_t));
@@ -503,26 +495,76 @@ int prepare_score(PsContext *ctx, Plan &pl, int P, int cap, bool complete = fals
     return PS_OK;
 }
 
-// Kernels 3 + 4 over records already in the arena.
-int run_ransac_stage(PsContext *ctx, const Plan &pl, int P, int cap, const PsDMatch *dMatches,
-                     const int32_t *dNumMatches, int matchStride, float *dPose, uint8_t *dMask, PsRansacStats *dStats,
-                     int slot0)
-{
-    const int H = pl.H;
-    PS_ENSURE(ctx->counts, (size_t)P * H * sizeof(int32_t));
-    PS_ENSURE(ctx->idxList, (size_t)P * cap * sizeof(int32_t));
-    const int hb = (H + kBlock - 1) / kBlock;
-    const int msplit = pl.msplit; // counts were cleared by kernel 2 when the range is split (prepare_score)
-    dim3 grid((unsigned)hb * (unsigned)msplit * (unsigned)P);
-    tick(ctx, slot0, false);
-    unsigned long long *dbgE = nullptr;
-    if (ctx->scoreStats && with_euclid_fast(ctx, pl.mode)) {
-        PS_ENSURE(ctx->dbgCnt, 8 * sizeof(unsigned long long));
-        PS_HIP(hipMemsetAsync(ctx->dbgCnt.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
-        dbgE = (unsigned long long *)ctx->dbgCnt.p;
+// What the kernel-3 launches of one call share (run_ransac_stage).
+struct K3Call {
+    PsContext *ctx;
+    const Plan &pl;
+    int P, cap;
+    const float2 *hotF;      // the hot record of stages 1+: reordered between stage 0 and stage 1 (ps_stage_reorder) unless the option is off
+    unsigned long long *dbg; // option "score_stats": the decision-exact kernels' counters, else null
+};
+
+// A launch of kernel 3 of KIND 0 (stage 0 / the complete scoring), 1 (stage 1; LOOP: looping work-groups) or 2 (stages 2+);
+// a family's launcher runs it with the given StageArgs over groups x msplit x P work-groups.
+template <int KIND, bool LOOP = false> struct Kind {};
+
+template <int MODE> struct EuclidK3 {
+    const K3Call &c;
+    template <int KIND, bool LOOP> void operator()(Kind<KIND, LOOP>, const StageArgs &st, unsigned groups, int msplit) const
+    {
+        PsContext *ctx = c.ctx;
+        hipLaunchKernelGGL((ps_ransac_score_euclid<MODE, KIND, LOOP>), dim3(groups * (unsigned)msplit * (unsigned)c.P), dim3(kBlock),
+                           0, ctx->stream, (const float4 *)ctx->recA.p, (const float4 *)ctx->recB.p,
+                           KIND >= 1 ? c.hotF : (const float2 *)ctx->recF.p, (const int32_t *)ctx->mvalid.p,
+                           (const float2 *)ctx->cmax.p, c.pl.ma, c.pl.sc, c.pl.ec, c.pl.sa, st, c.pl.H, c.cap, c.pl.minRun, msplit,
+                           (int32_t *)ctx->counts.p, c.dbg);
     }
-    // Staged scoring (ps_score_fast.h): stage 0 = the prefix completely, stages 1 .. 3 = the rest with hypotheses abandoned
-    // between the launches.  stage_args(i) describes launch i.
+};
+
+template <int MODE> struct ReprojK3 {
+    const K3Call &c;
+    template <bool BIG, int KIND, bool LOOP> void launch(const StageArgs &st, unsigned groups, int msplit) const
+    {
+        PsContext *ctx = c.ctx;
+        hipLaunchKernelGGL((ps_ransac_score_fast<MODE, BIG, KIND, LOOP>), dim3(groups * (unsigned)msplit * (unsigned)c.P),
+                           dim3(kBlock), 0, ctx->stream, (const float4 *)ctx->recA.p, (const float4 *)ctx->recB.p,
+                           (const float4 *)ctx->recC.p, st.frontRec ? (const float4 *)st.frontRec : (const float4 *)ctx->recE.p,
+                           KIND >= 1 ? c.hotF : (const float2 *)ctx->recF.p, (const int32_t *)ctx->mvalid.p,
+                           (const float2 *)ctx->cmax.p, c.pl.ma, c.pl.sc, c.pl.fc, c.pl.ec, c.pl.sa, st, c.pl.H, c.cap, c.pl.minRun,
+                           msplit, (int32_t *)ctx->counts.p, c.dbg);
+    }
+    // more work-groups than fit at once (256 CUs x 6): the build for big launches (ps_score_fast.h) -- for stage 0 and the
+    // complete scoring as prepare_score decided (Plan::big0), always for the stages after the prefix
+    template <int KIND, bool LOOP> void operator()(Kind<KIND, LOOP>, const StageArgs &st, unsigned groups, int msplit) const
+    {
+        if constexpr (KIND == 0) {
+            if (!c.pl.big0) return launch<false, KIND, LOOP>(st, groups, msplit);
+        }
+        launch<true, KIND, LOOP>(st, groups, msplit);
+    }
+};
+
+// Kernel 3 of the decision-exact scoring (ps_score_fast.h, ps_score_euclid.h) through one family's launcher k3.  Staged
+// scoring: stage 0 = the prefix completely, stages 1 .. lastStage = the rest with hypotheses abandoned between the launches;
+// otherwise every hypothesis of [0, H) completely.
+template <int MODE, class K3> void score_schedule(const K3Call &c, const K3 &k3)
+{
+    PsContext *ctx = c.ctx;
+    const Plan &pl = c.pl;
+    const int P = c.P;
+    auto groups = [](int hCount) { return (unsigned)((hCount + kBlock - 1) / kBlock); };
+    if (!pl.prune) {
+        StageArgs st{}; // the plain launch: every hypothesis of [0, H) completely
+        st.hCount = pl.H;
+        if (pl.genPlain) { // the same as two launches (Plan::genPlain): models, then the sweep
+            st.validMask = (unsigned long long *)ctx->validMask.p;
+            st.genOnly = 1;
+            k3(Kind<0>{}, st, groups(pl.H), 1);
+            st.genOnly = 0;
+        }
+        k3(Kind<0>{}, st, groups(pl.H), pl.msplit);
+        return;
+    }
     // stages 2+: work-groups per pair (they loop over longer lists; after the reordered stage 1 few hypotheses are left)
     auto list_groups = [&](int stage) {
         const int listed = (pl.H < pl.ma.modelH ? pl.H : pl.ma.modelH) - pl.prefix; // hypotheses that can be on a survivor list
@@ -534,7 +576,7 @@ int run_ransac_stage(PsContext *ctx, const Plan &pl, int P, int cap, const PsDMa
         // there --, two looping groups with the Euclidean ones, whose counts saturate: hardly anything survives and the
         // launch is mostly work-groups that find nothing, 2 - 3 % of the step at every inlier share tried,
         // profiles/r04b/ab_euclid_list_groups.txt)
-        const int auto2 = with_euclid_fast(ctx, pl.mode) ? (all / 8 > 2 ? all / 8 : 2) : 64; // (many hypotheses: lists can be long)
+        const int auto2 = pl.score == Scoring::Euclid ? (all / 8 > 2 ? all / 8 : 2) : 64; // (many hypotheses: lists can be long)
         const int want = pl.reorder ? (stage == 2 ? (ctx->listGroups2 > 0 ? ctx->listGroups2 : auto2)
                                                   : auto3) : all;
         return want < all ? want : all;
@@ -545,20 +587,20 @@ int run_ransac_stage(PsContext *ctx, const Plan &pl, int P, int cap, const PsDMa
     // stage 1's one-direction pre-test on the far-off front of the reordered record: the reprojection metrics (ps_score_fast.h)
     const bool usePretest = pl.reorder && ctx->pretest != 0 &&
                             (pl.mode == PS_EUCLIDEAN_AND_REPROJECTION_ERROR || pl.mode == PS_REPROJECTION_ERROR);
-    const int lastStage = pl.lastStage;
     // Stage 1 of an adaptive schedule with a long cap (USAC's 850 000 = 3320 blocks of 256 hypotheses per pair, of which the
     // trip limit leaves a handful): one work-group per block is hundreds of thousands of work-groups that look at the limit and
     // leave -- 0.9 ms per 210 pairs.  From 64 blocks per pair on a fixed number of work-groups per pair walks the blocks and
     // stops at the first one beyond the limit (enough of them to fill the chip when the limit does stay at the cap).
     const int blocks1 = (pl.H - pl.prefix + kBlock - 1) / kBlock;
     int loopGroups = 0;
-    if (pl.prune && pl.sa.estimator != PS_EST_FIXED && blocks1 > 64) {
+    if (pl.sa.estimator != PS_EST_FIXED && blocks1 > 64) {
         // (64 per pair at the least until round 5: 32 000 work-groups per 499 pairs that read the limit and leave, a third of the
         // scoring step under USAC's cap; 4096 in all still fill the chip when the limits do stay at the cap)
         loopGroups = (4096 + P - 1) / P;
         loopGroups = loopGroups < 4 ? 4 : loopGroups;
         loopGroups = loopGroups > blocks1 ? blocks1 : loopGroups;
     }
+    // stage_args(i) describes launch i
     auto stage_args = [&](int stage) {
         StageArgs st{};
         st.stage = stage;
@@ -574,27 +616,12 @@ int run_ransac_stage(PsContext *ctx, const Plan &pl, int P, int cap, const PsDMa
         if (stage == 1 && usePretest) st.frontRec = (const float2 *)ctx->frontRec.p;
         st.listStride = pl.ma.modelH;
         st.loopGroups = stage == 1 ? loopGroups : 0;
-        st.single = lastStage == 1 ? 1 : 0;
+        st.single = pl.lastStage == 1 ? 1 : 0;
         st.margin = ctx->reorderMargin;
         st.gran = kReorderGran;
         st.c2div = kReorderC2div;
         return st;
     };
-    // the hot record of stages 1+: reordered between stage 0 and stage 1 (ps_stage_reorder) unless the option is off
-    const float2 *hotF = (const float2 *)(pl.reorder ? ctx->recF2.p : ctx->recF.p);
-#define PS_LAUNCH_REORDER(MODE)                                                                                        \
-    do {                                                                                                               \
-        if (pl.reorder)                                                                                                \
-            hipLaunchKernelGGL(ps_stage_reorder<MODE>, dim3((unsigned)P), dim3(kBlock), 0, ctx->stream,                \
-                               (const float4 *)ctx->recA.p, (const float4 *)ctx->recB.p, (const float4 *)ctx->recC.p,  \
-                               (const float2 *)ctx->recF.p, (const int32_t *)ctx->mvalid.p, pl.ma, pl.sc, pl.sa,       \
-                               pl.prefix, ctx->reorderTop,                                                              \
-                               (ctx->bail != 0 && with_euclid_fast(ctx, pl.mode)) ? 64 : 0, ctx->reorderMargin, pl.H, cap,  \
-                               pl.minRun, (const int32_t *)ctx->counts.p, (float2 *)ctx->recF2.p,                       \
-                               (int32_t *)ctx->permBuf.p, (int32_t *)ctx->prefInfo.p,                            \
-                               usePretest ? (float2 *)ctx->frontRec.p : (float2 *)nullptr,                             \
-                               pl.bailWatch ? (unsigned *)ctx->bailCnt.p + 2 * pl.bailSlot : (unsigned *)nullptr);     \
-    } while (0)
     // stage 0 as two launches: models + validity, then the sweep reading them back
     auto stage0_args = [&](bool gen) {
         StageArgs st = stage_args(0);
@@ -604,133 +631,59 @@ int run_ransac_stage(PsContext *ctx, const Plan &pl, int P, int cap, const PsDMa
         }
         return st;
     };
-    StageArgs stAll{}; // the plain launch: every hypothesis of [0, H) completely
-    stAll.hCount = pl.H;
-    StageArgs stAllGen = stAll, stAllSweep = stAll; // the same as two launches (Plan::genPlain): models, then the sweep
-    if (pl.genPlain) {
-        stAllGen.validMask = stAllSweep.validMask = (unsigned long long *)ctx->validMask.p;
-        stAllGen.genOnly = 1;
+    if (pl.genSplit) k3(Kind<0>{}, stage0_args(true), groups(pl.prefix), 1);
+    k3(Kind<0>{}, stage0_args(false), groups(pl.prefix), pl.msplit);
+    if (pl.reorder)
+        hipLaunchKernelGGL(ps_stage_reorder<MODE>, dim3((unsigned)P), dim3(kBlock), 0, ctx->stream, (const float4 *)ctx->recA.p,
+                           (const float4 *)ctx->recB.p, (const float4 *)ctx->recC.p, (const float2 *)ctx->recF.p,
+                           (const int32_t *)ctx->mvalid.p, pl.ma, pl.sc, pl.sa, pl.prefix, ctx->reorderTop,
+                           (ctx->bail != 0 && pl.score == Scoring::Euclid) ? 64 : 0, ctx->reorderMargin, pl.H, c.cap, pl.minRun,
+                           (const int32_t *)ctx->counts.p, (float2 *)ctx->recF2.p, (int32_t *)ctx->permBuf.p,
+                           (int32_t *)ctx->prefInfo.p, usePretest ? (float2 *)ctx->frontRec.p : (float2 *)nullptr,
+                           pl.bailWatch ? (unsigned *)ctx->bailCnt.p + 2 * pl.bailSlot : (unsigned *)nullptr);
+    if (loopGroups > 0)
+        k3(Kind<1, true>{}, stage_args(1), (unsigned)loopGroups, 1);
+    else
+        k3(Kind<1>{}, stage_args(1), groups(pl.H - pl.prefix), 1);
+    for (int sg = 2; sg <= pl.lastStage; ++sg) k3(Kind<2>{}, stage_args(sg), (unsigned)list_groups(sg), list_rsplit(sg));
+}
+
+// Kernel 3 of one call under error MODE: the family the plan chose (Plan::score).
+template <int MODE> void launch_k3(const K3Call &c)
+{
+    if constexpr (MODE == PS_EUCLIDEAN_ERROR || MODE == PS_ADAPTIVE_ERROR) {
+        if (c.pl.score == Scoring::Euclid) return score_schedule<MODE>(c, EuclidK3<MODE>{c});
     }
-#define PS_LAUNCH_EUCLID_ONE(MODE, KIND, ST, HCOUNT, MSPLIT)                                                           \
-    hipLaunchKernelGGL((ps_ransac_score_euclid<MODE, KIND>),                                                           \
-                       dim3((unsigned)(((HCOUNT) + kBlock - 1) / kBlock) * (unsigned)(MSPLIT) * (unsigned)P),          \
-                       dim3(kBlock), 0, ctx->stream, (const float4 *)ctx->recA.p, (const float4 *)ctx->recB.p,         \
-                       (KIND) >= 1 ? hotF : (const float2 *)ctx->recF.p, (const int32_t *)ctx->mvalid.p,               \
-                       (const float2 *)ctx->cmax.p,                                                                    \
-                       pl.ma, pl.sc, pl.ec, pl.sa, (ST), pl.H, cap, pl.minRun, (MSPLIT), (int32_t *)ctx->counts.p, dbgE)
-#define PS_LAUNCH_EUCLID(MODE)                                                                                         \
-    do {                                                                                                               \
-        if (pl.prune) {                                                                                                \
-            if (pl.genSplit) PS_LAUNCH_EUCLID_ONE(MODE, 0, stage0_args(true), pl.prefix, 1);                           \
-            PS_LAUNCH_EUCLID_ONE(MODE, 0, stage0_args(false), pl.prefix, msplit);                                      \
-            PS_LAUNCH_REORDER(MODE);                                                                                   \
-            if (loopGroups > 0)                                                                                        \
-                hipLaunchKernelGGL((ps_ransac_score_euclid<MODE, 1, true>), dim3((unsigned)loopGroups * (unsigned)P),  \
-                                   dim3(kBlock), 0, ctx->stream, (const float4 *)ctx->recA.p, (const float4 *)ctx->recB.p, \
-                                   hotF, (const int32_t *)ctx->mvalid.p, (const float2 *)ctx->cmax.p, pl.ma, pl.sc, pl.ec, \
-                                   pl.sa, stage_args(1), pl.H, cap, pl.minRun, 1, (int32_t *)ctx->counts.p, dbgE);     \
-            else                                                                                                       \
-                PS_LAUNCH_EUCLID_ONE(MODE, 1, stage_args(1), pl.H - pl.prefix, 1);                                     \
-            for (int sg = 2; sg <= lastStage; ++sg)                                                                    \
-                PS_LAUNCH_EUCLID_ONE(MODE, 2, stage_args(sg), list_groups(sg) * kBlock, list_rsplit(sg));              \
-        } else if (pl.genPlain) {                                                                                      \
-            PS_LAUNCH_EUCLID_ONE(MODE, 0, stAllGen, pl.H, 1);                                                          \
-            PS_LAUNCH_EUCLID_ONE(MODE, 0, stAllSweep, pl.H, msplit);                                                   \
-        } else                                                                                                         \
-            PS_LAUNCH_EUCLID_ONE(MODE, 0, stAll, pl.H, msplit);                                                        \
-    } while (0)
+    if constexpr (MODE == PS_REPROJECTION_ERROR || MODE == PS_EUCLIDEAN_AND_REPROJECTION_ERROR) {
+        if (c.pl.score == Scoring::Reproj) return score_schedule<MODE>(c, ReprojK3<MODE>{c});
+    }
+    // counts were cleared by kernel 2 when the range is split (prepare_score)
+    launch_score<MODE>(c.ctx, dim3((unsigned)((c.pl.H + kBlock - 1) / kBlock) * (unsigned)c.pl.msplit * (unsigned)c.P), c.pl, c.cap,
+                       c.pl.msplit);
+}
+
+// Kernels 3 + 4 over records already in the arena.
+int run_ransac_stage(PsContext *ctx, const Plan &pl, int P, int cap, const PsDMatch *dMatches,
+                     const int32_t *dNumMatches, int matchStride, float *dPose, uint8_t *dMask, PsRansacStats *dStats,
+                     int slot0)
+{
+    PS_ENSURE(ctx->counts, (size_t)P * pl.H * sizeof(int32_t));
+    PS_ENSURE(ctx->idxList, (size_t)P * cap * sizeof(int32_t));
+    tick(ctx, slot0, false);
+    unsigned long long *dbg = nullptr;
+    if (ctx->scoreStats && pl.score != Scoring::Value) {
+        PS_ENSURE(ctx->dbgCnt, 8 * sizeof(unsigned long long));
+        PS_HIP(hipMemsetAsync(ctx->dbgCnt.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
+        dbg = (unsigned long long *)ctx->dbgCnt.p;
+    }
+    const K3Call c{ctx, pl, P, cap, (const float2 *)(pl.reorder ? ctx->recF2.p : ctx->recF.p), dbg};
     switch (pl.mode) {
-    case PS_EUCLIDEAN_ERROR:
-        if (with_euclid_fast(ctx, pl.mode))
-            PS_LAUNCH_EUCLID(PS_EUCLIDEAN_ERROR);
-        else
-            launch_score<PS_EUCLIDEAN_ERROR>(ctx, grid, pl, cap, msplit);
-        break;
-    case PS_REPROJECTION_ERROR:
-        if (ctx->scoreFast >= 1) {
-            unsigned long long *dbg = nullptr;
-            if (ctx->scoreStats) {
-                PS_ENSURE(ctx->dbgCnt, 8 * sizeof(unsigned long long));
-                PS_HIP(hipMemsetAsync(ctx->dbgCnt.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
-                dbg = (unsigned long long *)ctx->dbgCnt.p;
-            }
-            // more work-groups than fit at once (256 CUs x 6): the build for big launches (ps_score_fast.h)
-#define PS_LAUNCH_FAST_ONE(MODE, BIG, KIND, ST, HCOUNT, MSPLIT)                                                        \
-    hipLaunchKernelGGL((ps_ransac_score_fast<MODE, BIG, KIND>),                                                        \
-                       dim3((unsigned)(((HCOUNT) + kBlock - 1) / kBlock) * (unsigned)(MSPLIT) * (unsigned)P),          \
-                       dim3(kBlock), 0, ctx->stream, (const float4 *)ctx->recA.p, (const float4 *)ctx->recB.p,         \
-                       (const float4 *)ctx->recC.p,                                                                    \
-                       ((KIND) == 1 && (ST).frontRec != nullptr) ? (const float4 *)(ST).frontRec : (const float4 *)ctx->recE.p, \
-                       (KIND) >= 1 ? hotF : (const float2 *)ctx->recF.p,                                               \
-                       (const int32_t *)ctx->mvalid.p, (const float2 *)ctx->cmax.p, pl.ma, pl.sc, pl.fc, pl.ec, pl.sa, \
-                       (ST), pl.H, cap, pl.minRun, (MSPLIT), (int32_t *)ctx->counts.p, dbg)
-    // more work-groups than fit at once: the build for big launches (ps_score_fast.h); staged: prefix, then the stages
-#define PS_LAUNCH_FAST(MODE, BIGLIMIT)                                                                                 \
-    do {                                                                                                               \
-        if (pl.prune) {                                                                                                \
-            if ((unsigned)msplit * (unsigned)P > (BIGLIMIT)) {                                                         \
-                if (pl.genSplit) PS_LAUNCH_FAST_ONE(MODE, true, 0, stage0_args(true), pl.prefix, 1);                   \
-                PS_LAUNCH_FAST_ONE(MODE, true, 0, stage0_args(false), pl.prefix, msplit);                              \
-            } else {                                                                                                   \
-                if (pl.genSplit) PS_LAUNCH_FAST_ONE(MODE, false, 0, stage0_args(true), pl.prefix, 1);                  \
-                PS_LAUNCH_FAST_ONE(MODE, false, 0, stage0_args(false), pl.prefix, msplit);                             \
-            }                                                                                                          \
-            PS_LAUNCH_REORDER(MODE);                                                                                   \
-            if (loopGroups > 0) {                                                                                      \
-                const StageArgs st1 = stage_args(1);                                                                   \
-                hipLaunchKernelGGL((ps_ransac_score_fast<MODE, true, 1, true>),                                        \
-                                   dim3((unsigned)loopGroups * (unsigned)P), dim3(kBlock), 0, ctx->stream,             \
-                                   (const float4 *)ctx->recA.p, (const float4 *)ctx->recB.p, (const float4 *)ctx->recC.p, \
-                                   st1.frontRec != nullptr ? (const float4 *)st1.frontRec : (const float4 *)ctx->recE.p, \
-                                   hotF, (const int32_t *)ctx->mvalid.p, (const float2 *)ctx->cmax.p, pl.ma, pl.sc, pl.fc, \
-                                   pl.ec, pl.sa, st1, pl.H, cap, pl.minRun, 1, (int32_t *)ctx->counts.p, dbg);         \
-            } else                                                                                                     \
-                PS_LAUNCH_FAST_ONE(MODE, true, 1, stage_args(1), pl.H - pl.prefix, 1);                                 \
-            for (int sg = 2; sg <= lastStage; ++sg)                                                                    \
-                PS_LAUNCH_FAST_ONE(MODE, true, 2, stage_args(sg), list_groups(sg) * kBlock, list_rsplit(sg));          \
-        } else if (grid.x > (BIGLIMIT)) {                                                                              \
-            if (pl.genPlain) {                                                                                         \
-                PS_LAUNCH_FAST_ONE(MODE, true, 0, stAllGen, pl.H, 1);                                                  \
-                PS_LAUNCH_FAST_ONE(MODE, true, 0, stAllSweep, pl.H, msplit);                                           \
-            } else                                                                                                     \
-                PS_LAUNCH_FAST_ONE(MODE, true, 0, stAll, pl.H, msplit);                                                \
-        } else {                                                                                                       \
-            if (pl.genPlain) {                                                                                         \
-                PS_LAUNCH_FAST_ONE(MODE, false, 0, stAllGen, pl.H, 1);                                                 \
-                PS_LAUNCH_FAST_ONE(MODE, false, 0, stAllSweep, pl.H, msplit);                                          \
-            } else                                                                                                     \
-                PS_LAUNCH_FAST_ONE(MODE, false, 0, stAll, pl.H, msplit);                                               \
-        }                                                                                                              \
-    } while (0)
-            PS_LAUNCH_FAST(PS_REPROJECTION_ERROR, big_limit(PS_REPROJECTION_ERROR));
-        } else
-            launch_score<PS_REPROJECTION_ERROR>(ctx, grid, pl, cap, msplit);
-        break;
-    case PS_EUCLIDEAN_AND_REPROJECTION_ERROR:
-        if (ctx->scoreFast != 0) {
-            unsigned long long *dbg = nullptr;
-            if (ctx->scoreStats) {
-                PS_ENSURE(ctx->dbgCnt, 8 * sizeof(unsigned long long));
-                PS_HIP(hipMemsetAsync(ctx->dbgCnt.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
-                dbg = (unsigned long long *)ctx->dbgCnt.p;
-            }
-            PS_LAUNCH_FAST(PS_EUCLIDEAN_AND_REPROJECTION_ERROR, big_limit(PS_EUCLIDEAN_AND_REPROJECTION_ERROR));
-        } else
-            launch_score<PS_EUCLIDEAN_AND_REPROJECTION_ERROR>(ctx, grid, pl, cap, msplit);
-        break;
-    case PS_ADAPTIVE_ERROR:
-        if (with_euclid_fast(ctx, pl.mode))
-            PS_LAUNCH_EUCLID(PS_ADAPTIVE_ERROR);
-        else
-            launch_score<PS_ADAPTIVE_ERROR>(ctx, grid, pl, cap, msplit);
-        break;
-    default: launch_score<PS_MAHALANOBIS_ERROR>(ctx, grid, pl, cap, msplit); break;
+    case PS_EUCLIDEAN_ERROR: launch_k3<PS_EUCLIDEAN_ERROR>(c); break;
+    case PS_REPROJECTION_ERROR: launch_k3<PS_REPROJECTION_ERROR>(c); break;
+    case PS_EUCLIDEAN_AND_REPROJECTION_ERROR: launch_k3<PS_EUCLIDEAN_AND_REPROJECTION_ERROR>(c); break;
+    case PS_ADAPTIVE_ERROR: launch_k3<PS_ADAPTIVE_ERROR>(c); break;
+    default: launch_k3<PS_MAHALANOBIS_ERROR>(c); break;
     }
-#undef PS_LAUNCH_REORDER
-#undef PS_LAUNCH_EUCLID
-#undef PS_LAUNCH_EUCLID_ONE
-#undef PS_LAUNCH_FAST
-#undef PS_LAUNCH_FAST_ONE
     tick(ctx, slot0, true);
     PS_HIP(hipGetLastError());
     SelectArgs sa = pl.sa;
@@ -772,9 +725,20 @@ int ensure_records(PsContext *ctx, size_t P, size_t cap)
     return PS_OK;
 }
 
-// Kernels 1 + 2 for P pairs of a device-resident frame set.
-int run_match_stage(PsContext *ctx, const PsFrameSet &fs, const int32_t *dPairs, int P, bool withRecords,
-                    const PrepArgs &paIn, PsDMatch *dMatches, int32_t *dNumMatches, int slot0)
+// Kernel 2 with (REC) or without the scoring records, BLK threads per work-group.
+template <bool REC, int BLK>
+void launch_prep(PsContext *ctx, const PsFrameSet &fs, const int32_t *dPairs, int P, const PrepArgs &pa, const RecPtrs &rp,
+                 PsDMatch *dMatches, int32_t *dNumMatches)
+{
+    hipLaunchKernelGGL((ps_crosscheck_prep<REC, BLK>), dim3((unsigned)P), dim3(BLK), (size_t)fs.maxKpts * sizeof(uint32_t), ctx->stream,
+                       fs.pts, fs.nkpts, dPairs, (uint32_t *)ctx->keys.p, pa, dMatches, dNumMatches, rp, (int32_t *)ctx->mvalid.p,
+                       (float2 *)ctx->cmax.p, ctx->stampsOn ? (unsigned long long *)ctx->stamps.p : (unsigned long long *)nullptr);
+}
+
+// Kernels 1 + 2 for P pairs of a device-resident frame set: kernel 2 writes the records of plan `pl`, or matches only
+// (pl = null).
+int run_match_stage(PsContext *ctx, const PsFrameSet &fs, const int32_t *dPairs, int P, const Plan *pl, PsDMatch *dMatches,
+                    int32_t *dNumMatches, int slot0)
 {
     const int cap = fs.maxKpts;
     // frame strides (PsFrameSet, ABI 2): dense unless the frames keep descriptors and points together
@@ -785,12 +749,13 @@ int run_match_stage(PsContext *ctx, const PsFrameSet &fs, const int32_t *dPairs,
         return fail(ctx, PS_ERR_BAD_ARG, "frame set: descFrameStride must be a multiple of 16 and >= maxKpts x 32 (desc 16-byte aligned), "
                                          "ptsFrameStride a multiple of 4 and >= maxKpts x 12");
     const int fstrideDw = (int)(descStride / 4);
-    PrepArgs pa = paIn;
+    PrepArgs pa = pl ? pl->pa : PrepArgs{};
+    if (!pl) pa.cap = cap;
     pa.ptsStride = (int)(ptsStride / 4);
     PS_ENSURE(ctx->keys, (size_t)P * cap * sizeof(uint32_t));
     PS_ENSURE(ctx->mvalid, (size_t)P * sizeof(int32_t));
     PS_ENSURE(ctx->cmax, (size_t)P * sizeof(float2));
-    if (withRecords) {
+    if (pl) {
         int rc = ensure_records(ctx, (size_t)P, (size_t)cap);
         if (rc != PS_OK) return rc;
     }
@@ -809,10 +774,7 @@ int run_match_stage(PsContext *ctx, const PsFrameSet &fs, const int32_t *dPairs,
     } keysInUse{ctx, cleanBefore};
     if (useMfma) {
         // matrix-core form: expand every pair's query frame to FP4 once, then the MFMA sweep
-#ifndef PS_MFMA_TT
-#define PS_MFMA_TT 4
-#endif
-        constexpr int TT = PS_MFMA_TT;
+        constexpr int TT = kMfmaTT;
         const int tpf = (cap + kTileRows - 1) / kTileRows;
         const int groups = (tpf + kWavesPerWG * TT - 1) / (kWavesPerWG * TT);
         int qsplit = pick_split((long long)P * groups, tpf, 1, tpf);
@@ -867,28 +829,11 @@ int run_match_stage(PsContext *ctx, const PsFrameSet &fs, const int32_t *dPairs,
         tick(ctx, slot0, true);
         PS_HIP(hipGetLastError());
     }
-    size_t lds = (size_t)cap * sizeof(uint32_t);
     tick(ctx, slot0 + 1, false);
     const bool wide = P <= kWidePairs; // a handful of pairs: 1024-thread work-groups shorten the per-pair serial walk
-#define PS_LAUNCH_PREP(REC, BLK)                                                                                       \
-    hipLaunchKernelGGL((ps_crosscheck_prep<REC, BLK>), dim3((unsigned)P), dim3(BLK), lds, ctx->stream, fs.pts, fs.nkpts, \
-                       dPairs, (uint32_t *)ctx->keys.p, pa, dMatches, dNumMatches, rp,                                 \
-                       (int32_t *)ctx->mvalid.p, (float2 *)ctx->cmax.p,                                                \
-                       ctx->stampsOn ? (unsigned long long *)ctx->stamps.p : (unsigned long long *)nullptr)
-    RecPtrs rp{};
-    if (withRecords) {
-        rp = rec_ptrs(ctx, cap, pa.mode);
-        if (wide)
-            PS_LAUNCH_PREP(true, 1024);
-        else
-            PS_LAUNCH_PREP(true, kBlock);
-    } else {
-        if (wide)
-            PS_LAUNCH_PREP(false, 1024);
-        else
-            PS_LAUNCH_PREP(false, kBlock);
-    }
-#undef PS_LAUNCH_PREP
+    const auto prep = pl ? (wide ? launch_prep<true, 1024> : launch_prep<true, kBlock>)
+                         : (wide ? launch_prep<false, 1024> : launch_prep<false, kBlock>);
+    prep(ctx, fs, dPairs, P, pa, pl ? rec_ptrs(ctx, pl->score) : RecPtrs{}, dMatches, dNumMatches);
     tick(ctx, slot0 + 1, true);
     PS_HIP(hipGetLastError());
     keysInUse.done = true;
@@ -957,10 +902,7 @@ int ps_match_hamming256(PsContext *ctx, const uint8_t *query, int nq, size_t qst
     fs.numFrames = 2;
     fs.maxKpts = cap;
     fs.descFrameStride = fs.ptsFrameStride = 0;
-    PrepArgs pa{};
-    pa.cap = cap;
-    rc = run_match_stage(ctx, fs, (const int32_t *)ctx->sNk.p + 2, 1, false, pa, (PsDMatch *)ctx->sMatches.p,
-                         (int32_t *)ctx->sNumM.p, 0);
+    rc = run_match_stage(ctx, fs, (const int32_t *)ctx->sNk.p + 2, 1, nullptr, (PsDMatch *)ctx->sMatches.p, (int32_t *)ctx->sNumM.p, 0);
     if (rc) return rc;
     int32_t n = 0;
     PS_HIP(hipMemcpyAsync(&n, ctx->sNumM.p, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1030,7 +972,7 @@ static int ransac_host_entry(PsContext *ctx, const PsRansacParams *params, const
     int32_t mm = m;
     PS_HIP(hipMemcpyAsync(ctx->sNumM.p, &mm, sizeof mm, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(ps_prep_from_matches, dim3(1), dim3(kBlock), 0, ctx->stream, (const float *)ctx->sMisc0.p,
-                       (const float *)ctx->sMisc1.p, (const PsDMatch *)ctx->sMatches.p, m, pl.pa, rec_ptrs(ctx, cap, pl.pa.mode),
+                       (const float *)ctx->sMisc1.p, (const PsDMatch *)ctx->sMatches.p, m, pl.pa, rec_ptrs(ctx, pl.score),
                        (int32_t *)ctx->mvalid.p, (float2 *)ctx->cmax.p);
     PS_HIP(hipGetLastError());
     rc = run_ransac_stage(ctx, pl, 1, cap, (const PsDMatch *)ctx->sMatches.p, (const int32_t *)ctx->sNumM.p, cap,
@@ -1344,7 +1286,7 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
     } handoffGuard{ctx};
     rc = prepare_score(ctx, pl, P, cap, false, true, frames->desc);
     if (rc) return rc;
-    rc = run_match_stage(ctx, *frames, pairs, P, true, pl.pa, out->matches, out->numMatches, 0);
+    rc = run_match_stage(ctx, *frames, pairs, P, &pl, out->matches, out->numMatches, 0);
     if (rc) return rc;
     rc = run_ransac_stage(ctx, pl, P, cap, out->matches, out->numMatches, cap, out->pose, out->inlierMask, out->stats, 2);
     return rc;

@@ -419,7 +419,7 @@ int mini_enqueue(PsVoStream *s, AsyncLane &l, PsContext *lc, const Plan &pl, int
     fs.maxKpts = s->cap;
     fs.descFrameStride = fs.ptsFrameStride = a->packStride;
     uint8_t *dres = (uint8_t *)l.res.p;
-    int rc = run_match_stage(lc, fs, dm->pairs, P, true, pl.pa, (PsDMatch *)dres, (int32_t *)(dres + a->offNum), 0);
+    int rc = run_match_stage(lc, fs, dm->pairs, P, &pl, (PsDMatch *)dres, (int32_t *)(dres + a->offNum), 0);
     if (rc == PS_OK)
         rc = run_ransac_stage(lc, pl, P, s->cap, (const PsDMatch *)dres, (const int32_t *)(dres + a->offNum), s->cap, (float *)(dres + a->offPose),
                               dres + a->offMask, (PsRansacStats *)(dres + a->offStats), 2);

@@ -230,7 +230,7 @@ int ps_vo_stream_push(PsVoStream *s, const PsRansacParams *params, const PsRansa
     auto enqueue = [&](size_t rows) -> int {
         int r = copy_in(rows);
         if (r) return r;
-        r = run_match_stage(ctx, fs, (const int32_t *)s->meta.p + 2, 1, true, pl.pa, (PsDMatch *)(dres + s->offMatches),
+        r = run_match_stage(ctx, fs, (const int32_t *)s->meta.p + 2, 1, &pl, (PsDMatch *)(dres + s->offMatches),
                             (int32_t *)(dres + s->offNum), 0);
         if (r) return r;
         r = run_ransac_stage(ctx, pl, 1, s->cap, (const PsDMatch *)(dres + s->offMatches),
