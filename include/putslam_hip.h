@@ -244,6 +244,25 @@ int ps_remove_image_distortion(PsContext *ctx, const float *xy, int n, const flo
 /* ---- A3: RGBD::point3Dto2D, src/RGBD/RGBD.cpp:92-98 (n points). */
 int ps_points3Dto2D(PsContext *ctx, const float *xyz, int n, const float *K, float *uv);
 
+/* ---- DBScan keypoint thinning: DBScan(eps, minPts, featuresFromCluster).run(keypoints), src/Matcher/dbscan.cpp
+ * (include/putslam/Matcher/dbscan.h; run between detection and description, matcher.cpp:24-26,221-223,459-461,561-563).
+ * Two keypoints are neighbours iff (float)cv::norm(pt_i - pt_j) < eps; a cluster keeps its first featuresFromCluster
+ * members in index order (none if that is <= 0), noise is kept, and a keypoint whose octave already is -5 (the reference's
+ * erase marker) is removed.  keptIdx (room for n entries: the call may write all n) receives the survivors' indices in
+ * ascending order, *nkept their number.
+ * xy: n points of two floats, xyStride BYTES apart (0 = 8: packed cv::Point2f; sizeof(cv::KeyPoint) with &kps[0].pt);
+ * octave: n int32, octaveStride BYTES apart (0 = 4), or NULL (no -5 rule).  Host pointers; synchronous on the context's
+ * stream.  n <= PS_DBSCAN_MAX_KPTS (per-point state lives in LDS). */
+#define PS_DBSCAN_MAX_KPTS 8000
+int ps_dbscan_thin(PsContext *ctx, const float *xy, size_t xyStride, const int32_t *octave, size_t octaveStride, int n,
+                   double eps, int minPts, int featuresFromCluster, int32_t *keptIdx, int *nkept);
+/* The same over a DEVICE-resident batch, one work-group per frame: xy frames x capacity x 2 floats, octave frames x capacity
+ * int32 (or NULL), counts frames int32 (points of each frame, 0 .. capacity); keptIdx frames x capacity int32 (frame f's
+ * survivors at f x capacity, ascending), nkept frames int32 (-1 for a frame whose count lies outside 0 .. capacity).
+ * capacity <= PS_DBSCAN_MAX_KPTS.  Asynchronous on the context's stream; uses no scratch of the context. */
+int ps_dbscan_thin_device(PsContext *ctx, const float *xy, const int32_t *octave, const int32_t *counts, int frames,
+                          int capacity, double eps, int minPts, int featuresFromCluster, int32_t *keptIdx, int32_t *nkept);
+
 /* ---- N2: guided map matching, core of Matcher::matchXYZ, src/Matcher/matcher.cpp:606-746.
  * For every map feature j: candidates i among the current frame's keypoints with
  * |mapPos[j] - curPos[i]| < sphereRadius and |curLevel[i] - mapLevel[j]| <= 1 (:699-711); their value is
@@ -558,6 +577,9 @@ int ps_debug_stage_order(PsContext *ctx, int P, int cap, int32_t *perm, int32_t 
  * wrote into a private buffer: out16[0..3] = ps_crosscheck_prep (start, best[q] built, matches compacted + records written,
  * end), out16[4..9] = ps_select_refit (start, selection replayed, winner's inlier pass, refit, re-selection, end). */
 int ps_debug_stamps(PsContext *ctx, uint64_t *out16);
+/* DBScan's neighbour predicate in the square domain: the least double s* with (double)(float)sqrt(s*) >= eps (0 for eps <= 0
+ * or NaN), so that (float)sqrt(s) < eps  <=>  s < s*.  Pure host arithmetic. */
+double ps_debug_dbscan_bound(double eps);
 /* sizeof() of the PODs as compiled into the library (layout check for foreign-language bindings). */
 size_t ps_abi_sizeof_dmatch(void);
 size_t ps_abi_sizeof_params(void);

@@ -23,6 +23,11 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def dbscan_bound(eps):
+    """ps_debug_dbscan_bound: the least double s* with (double)(float)sqrt(s*) >= eps (DBScan's predicate is s < s*)."""
+    return float(_lib.load().ps_debug_dbscan_bound(float(eps)))
+
+
 class Context:
     """One HIP stream + scratch arena (PsContext).  Not shared between threads."""
 
@@ -240,6 +245,33 @@ class Context:
         out = np.zeros_like(xy)
         self._chk(self._L.ps_remove_image_distortion(self._h, _p(xy), xy.shape[0], _p(K), _p(d), _p(out)))
         return out
+
+    def dbscan_thin(self, xy, octave=None, eps=10.0, min_pts=2, features_from_cluster=1):
+        """DBScan(eps, minPts, featuresFromCluster).run (src/Matcher/dbscan.cpp; defaults: the reference constructor's):
+        the indices, ascending int32, of the keypoints it leaves in the vector.  xy: n x 2 float32 (a view with any row
+        stride, e.g. the pt fields of a structured keypoint array), octave: n int32 or None (no -5 rule)."""
+        xy = np.asarray(xy, np.float32)
+        assert xy.ndim == 2 and xy.shape[1] == 2
+        if xy.strides[1] != 4 or xy.strides[0] < 8 or xy.strides[0] % 4:
+            xy = np.ascontiguousarray(xy)
+        n = xy.shape[0]
+        if octave is not None:
+            octave = np.asarray(octave, np.int32).reshape(n)
+            if octave.strides[0] < 4 or octave.strides[0] % 4:
+                octave = np.ascontiguousarray(octave)
+        kept = np.zeros(max(n, 1), np.int32)
+        nk = C.c_int(0)
+        self._chk(self._L.ps_dbscan_thin(self._h, _p(xy), xy.strides[0] if n else 8, _p(octave),
+                                         octave.strides[0] if octave is not None and n else 4, n, float(eps), int(min_pts),
+                                         int(features_from_cluster), _p(kept), C.byref(nk)))
+        return kept[:nk.value].copy()
+
+    def dbscan_thin_device(self, xy_ptr, octave_ptr, counts_ptr, frames, capacity, kept_ptr, nkept_ptr, eps=10.0, min_pts=2,
+                           features_from_cluster=1):
+        """ps_dbscan_thin_device on device pointers (asynchronous on the context's stream): device_batch.dbscan_thin_device."""
+        self._chk(self._L.ps_dbscan_thin_device(self._h, C.c_void_p(xy_ptr), C.c_void_p(octave_ptr or None),
+                                                C.c_void_p(counts_ptr), int(frames), int(capacity), float(eps), int(min_pts),
+                                                int(features_from_cluster), C.c_void_p(kept_ptr), C.c_void_p(nkept_ptr)))
 
     def points3Dto2D(self, xyz, K):
         xyz = np.ascontiguousarray(xyz, np.float32)

@@ -213,6 +213,32 @@ std::vector<Eigen::Vector3f> RGBD::keypoints2Dto3D(std::vector<cv::Point2f> f2d,
     return out;
 }
 
+// ---------------------------------------------------------------------------------------------
+DBScan::DBScan(double eps_, int minPts_, int featuresFromCluster_) : eps(eps_), minPts(minPts_), featuresFromCluster(featuresFromCluster_)
+{
+}
+
+void DBScan::run(std::vector<cv::KeyPoint> &clusteringSet)
+{
+    const size_t n = clusteringSet.size();
+    if (n == 0) return;
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return;
+    std::vector<int32_t> kept(n);
+    int nkept = 0;
+    status = ps_dbscan_thin(ctx, &clusteringSet[0].pt.x, sizeof(cv::KeyPoint), &clusteringSet[0].octave, sizeof(cv::KeyPoint),
+                            (int)n, eps, minPts, featuresFromCluster, kept.data(), &nkept);
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        return;
+    }
+    // kept[] ascends and kept[j] >= j: compacting in place never overwrites a survivor before it is moved
+    for (int j = 0; j < nkept; ++j)
+        if (kept[j] != j) clusteringSet[j] = clusteringSet[kept[j]];
+    clusteringSet.resize((size_t)nkept);
+}
+
 std::vector<cv::Point2f> RGBD::removeImageDistortion(std::vector<cv::Point2f> &features, cv::Mat cameraMatrix, cv::Mat distCoeffs)
 {
     if (features.size() == 0) return std::vector<cv::Point2f>(); // RGBD.cpp:258-259

@@ -17,6 +17,7 @@
 //                                  descriptors, std::vector<MapFeature>, framesIds[2], pairedFeatures), as templates;
 //   INTEGRATION.md section 2       the bodies a maintainer puts into matcher.cpp / matcherOpenCV.cpp.
 //   RGBD helpers                   include/putslam/RGBD/RGBD.h:38-51, src/RGBD/RGBD.cpp:10-16,30-65,92-98
+//   ::DBScan                       include/putslam/Matcher/dbscan.h:14-24, src/Matcher/dbscan.cpp (keypoint thinning)
 //
 // Everything computes on the GPU through libputslam_hip.so; there is no host fallback.
 #pragma once
@@ -118,6 +119,30 @@ class RGBD {
     static std::vector<cv::Point2f> removeImageDistortion(std::vector<cv::Point2f> &features, cv::Mat cameraMatrix,
                                                           cv::Mat distCoeffs);
 };
+
+// ---------------------------------------------------------------------------------------------
+// Keypoint thinning between detection and description (matcher.cpp:24-26,221-223,459-461,561-563): run() is ps_dbscan_thin
+// on the calling thread's context and keeps every field of the surviving keypoints, in their input order.  The data members
+// keep the layout of the reference class, so a translation unit compiled against the reference's dbscan.h (matcher.cpp)
+// constructs and destroys this one correctly; the three containers stay empty.  The class sits behind the reference header's
+// own include guard: a translation unit that includes both (matcher.cpp: Matcher/dbscan.h, and this header through the glue)
+// sees ONE definition, whichever comes first -- the two are token-for-token the same interface and layout.
+#ifndef _DBSCAN
+#define _DBSCAN
+class DBScan {
+  public:
+    DBScan(double eps = 10, int minPts = 2, int featuresFromCluster = 1);
+    void run(std::vector<cv::KeyPoint> &clusteringSet);
+
+  private:
+    double eps;
+    int minPts;
+    int featuresFromCluster;
+    std::vector<std::vector<float>> dist;
+    std::vector<bool> visited;
+    std::vector<int> cluster;
+};
+#endif
 
 namespace putslam {
 

@@ -855,6 +855,9 @@ struct TimingOff {
 
 } // namespace
 
+// (DBScan's launch attribute: defined with the rest of DBScan at the end of this file)
+static void dbscan_kernel_attributes();
+
 extern "C" {
 
 void psi_kernel_attributes(void)
@@ -868,6 +871,7 @@ void psi_kernel_attributes(void)
                               hipFuncAttributeMaxDynamicSharedMemorySize, PS_MAX_KPTS * 4);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_crosscheck_prep<false, 1024>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, PS_MAX_KPTS * 4);
+    dbscan_kernel_attributes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1297,3 +1301,100 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
 } // extern "C"
 
 #include "ps_stream_async.h"
+
+#include "ps_dbscan.h"
+
+// ---------------------------------------------------------------------------------------------
+// DBScan keypoint thinning (ps_dbscan.h): apart from the VO path, at the end of this translation unit
+namespace {
+// the least double s with (double)(float)sqrt(s) >= eps: bisection over the bit patterns of the non-negative doubles, whose
+// order is theirs; the rounded root is monotone in s
+double dbscan_bound(double eps)
+{
+    if (!(eps > 0.0)) return 0.0; // also NaN: nothing is a neighbour
+    uint64_t lo = 0, hi = 0x7FF0000000000000ull; // +inf: its root reaches every eps
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        double s;
+        std::memcpy(&s, &mid, 8);
+        if ((double)(float)std::sqrt(s) >= eps)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    double s;
+    std::memcpy(&s, &lo, 8);
+    return s;
+}
+
+int dbscan_launch(PsContext *ctx, const float *xy, const int32_t *octave, const int32_t *counts, int n0, int frames, int cap,
+                  double eps, int minPts, int ffc, int32_t *keptIdx, int32_t *nkept)
+{
+    hipLaunchKernelGGL(ps_dbscan_kernel, dim3((unsigned)frames), dim3(kDbBlock), dbscan_lds_bytes(cap), ctx->stream,
+                       reinterpret_cast<const float2 *>(xy), octave, counts, n0, cap, dbscan_bound(eps), minPts, ffc, keptIdx,
+                       nkept);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+} // namespace
+
+static void dbscan_kernel_attributes()
+{
+    // 20 bytes of per-point state per keypoint
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_dbscan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)dbscan_lds_bytes(PS_DBSCAN_MAX_KPTS));
+}
+
+extern "C" {
+
+double ps_debug_dbscan_bound(double eps) { return dbscan_bound(eps); }
+
+int ps_dbscan_thin(PsContext *ctx, const float *xy, size_t xyStride, const int32_t *octave, size_t octaveStride, int n,
+                   double eps, int minPts, int featuresFromCluster, int32_t *keptIdx, int *nkept)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (nkept) *nkept = 0;
+    if (xyStride == 0) xyStride = 8;
+    if (octaveStride == 0) octaveStride = 4;
+    if (!nkept || n < 0 || n > PS_DBSCAN_MAX_KPTS || xyStride < 8 || octaveStride < 4 || (n > 0 && (!xy || !keptIdx)))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_dbscan_thin: bad argument (n must lie in 0 .. PS_DBSCAN_MAX_KPTS, strides >= 8 / 4 bytes)");
+    if (n == 0) return PS_OK;
+    std::vector<float> hxy((size_t)n * 2);
+    const char *pxy = reinterpret_cast<const char *>(xy);
+    for (int i = 0; i < n; ++i) std::memcpy(&hxy[(size_t)i * 2], pxy + (size_t)i * xyStride, 8);
+    std::vector<int32_t> hoct;
+    if (octave) {
+        hoct.resize((size_t)n);
+        const char *po = reinterpret_cast<const char *>(octave);
+        for (int i = 0; i < n; ++i) std::memcpy(&hoct[(size_t)i], po + (size_t)i * octaveStride, 4);
+    }
+    PS_ENSURE(ctx->sMisc0, (size_t)n * 8);
+    if (octave) PS_ENSURE(ctx->sMisc1, (size_t)n * 4);
+    PS_ENSURE(ctx->sMisc2, (size_t)n * 4);
+    PS_ENSURE(ctx->sNumM, sizeof(int32_t));
+    PS_HIP(hipMemcpyAsync(ctx->sMisc0.p, hxy.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (octave) PS_HIP(hipMemcpyAsync(ctx->sMisc1.p, hoct.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    rc = dbscan_launch(ctx, (const float *)ctx->sMisc0.p, octave ? (const int32_t *)ctx->sMisc1.p : nullptr, nullptr, n, 1, n, eps,
+                       minPts, featuresFromCluster, (int32_t *)ctx->sMisc2.p, (int32_t *)ctx->sNumM.p);
+    if (rc) return rc;
+    int32_t nk = 0;
+    PS_HIP(hipMemcpyAsync(&nk, ctx->sNumM.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PS_HIP(hipMemcpyAsync(keptIdx, ctx->sMisc2.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PS_HIP(hipStreamSynchronize(ctx->stream));
+    *nkept = nk;
+    return PS_OK;
+}
+
+int ps_dbscan_thin_device(PsContext *ctx, const float *xy, const int32_t *octave, const int32_t *counts, int frames, int capacity,
+                          double eps, int minPts, int featuresFromCluster, int32_t *keptIdx, int32_t *nkept)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (frames < 0 || (frames > 0 && (capacity < 1 || capacity > PS_DBSCAN_MAX_KPTS || !xy || !counts || !keptIdx || !nkept)))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_dbscan_thin_device: bad argument (capacity must lie in 1 .. PS_DBSCAN_MAX_KPTS)");
+    if (frames == 0) return PS_OK;
+    return dbscan_launch(ctx, xy, octave, counts, 0, frames, capacity, eps, minPts, featuresFromCluster, keptIdx, nkept);
+}
+
+} // extern "C"

@@ -165,3 +165,29 @@ def run_pairs_queue(queue, params, cfg, K, frames: FrameSetDevice, batch: PairBa
     own (two `PairBatchDevice`s used in turn).  Asynchronous; returns the batch's ticket -- `queue.wait(ticket)` (host),
     `queue.wait_on_stream(ticket, stream)` (a stream of the caller's) or `queue.synchronize()` before the results are read."""
     return queue.submit(params, cfg, K, frames.view(), batch.pairs.data_ptr(), batch.P, batch.view())
+
+
+def dbscan_thin_device(ctx, xy, counts, octave=None, eps=10.0, min_pts=2, features_from_cluster=1):
+    """DBScan keypoint thinning of a device-resident batch (ps_dbscan_thin_device): xy (F, cap, 2) float32, counts (F,) int32,
+    octave (F, cap) int32 or None -- torch tensors on the context's device.  Returns (kept (F, cap) int32, nkept (F,) int32),
+    device tensors written asynchronously on the context's stream: frame f keeps kept[f, :nkept[f]] (ascending)."""
+    assert xy.dtype == torch.float32 and xy.dim() == 3 and xy.shape[2] == 2 and xy.is_contiguous()
+    assert counts.dtype == torch.int32 and counts.shape == (xy.shape[0],) and counts.is_contiguous()
+    if octave is not None:
+        assert octave.dtype == torch.int32 and octave.shape == xy.shape[:2] and octave.is_contiguous()
+    F, cap = xy.shape[0], xy.shape[1]
+    kept = torch.empty((F, cap), dtype=torch.int32, device=xy.device)
+    nkept = torch.empty((F,), dtype=torch.int32, device=xy.device)
+    args = (xy.data_ptr(), octave.data_ptr() if octave is not None else 0, counts.data_ptr(), F, cap, kept.data_ptr(),
+            nkept.data_ptr(), eps, min_pts, features_from_cluster)
+    cur = torch.cuda.current_stream(xy.device)   # ordered like run_pairs: after torch's queued work, before its later work
+    if cur.cuda_stream != 0:
+        ctx.set_stream(cur.cuda_stream)
+        ctx.dbscan_thin_device(*args)
+        return kept, nkept
+    st = _work_stream(xy.device)
+    st.wait_stream(cur)
+    ctx.set_stream(st.cuda_stream)
+    ctx.dbscan_thin_device(*args)
+    cur.wait_stream(st)
+    return kept, nkept
