@@ -13,7 +13,7 @@ $(LIB): $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/*.cpp) include/putslam_hip.
 	python -c "from putslam_amd import _build; _build.build_hip()"
 
 $(DROPIN): $(CSRC)/dropin/putslam_dropin.cpp $(CSRC)/dropin/putslam_dropin.h $(CSRC)/dropin/putslam_compat_types.h $(LIB)
-	g++ -O2 -std=c++17 -fPIC -shared -Wall -Iinclude -I$(CSRC)/dropin $< -o $@ -Lputslam_amd -lputslam_hip '-Wl,-rpath,$$ORIGIN'
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -I$(CSRC)/dropin $< -o $@ -Lputslam_amd -lputslam_hip -L/opt/rocm/lib -lamdhip64 '-Wl,-rpath,$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
 $(SHARD): $(CSRC)/ps_shard.hip include/putslam_shard.h include/putslam_hip.h $(LIB)
 	$(HIPCC) --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -shared -Iinclude $< -o $@ -Lputslam_amd -lputslam_hip -L/opt/rocm/lib -lrccl '-Wl,-rpath,$$ORIGIN' -Wl,-rpath,/opt/rocm/lib

@@ -318,6 +318,57 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
                        const float *K, const PsFrameSet *frames,
                        const int32_t *pairs, int P, const PsPairResults *out);
 
+/* ---- N2 for a device-resident batch: Matcher::matchXYZ (src/Matcher/matcher.cpp:606-798) for P (map view, frame) pairs --
+ * guided matching, then the estimator -- as ONE launch chain.  PUTSLAM calls matchXYZ once per frame and retries it up to ten
+ * times with a wider sphere and a looser ratio while the inlier ratio stays under 0.1 (src/PUTSLAM/PUTSLAM.cpp:788-798): the
+ * tries of one frame, or the frames of many sequences, are one batch here.
+ * ps_map_sphere_bound: the least float B with  (float)|a - b| < sphereRadius  <=>  squared sum < B  (what ps_match_xyz computes
+ * internally); 0 for a radius that is 0, negative or NaN (nothing passes), +inf beyond sqrt(FLT_MAX).  Pure host arithmetic,
+ * so a caller can fill a per-pair array. */
+float ps_map_sphere_bound(double sphereRadius);
+
+typedef struct PsMapBatch {
+    PsFrameSet maps;              /* "map views": per view the visible map features -- desc = the descriptor chosen for
+                                     each (matcher.cpp:675-679), pts = (float) casts of MapFeature::position in the
+                                     camera frame (:700-701), nkpts = features per view.  Strides as in ABI 2. */
+    const int32_t *mapLevel;      /* maps.numFrames x maps.maxKpts predicted levels (ps_predicted_level, :681-692) */
+    PsFrameSet frames;            /* current frames: descriptors + back-projected points */
+    const int32_t *curLevel;      /* frames.numFrames x frames.maxKpts (:639-652) */
+    const int32_t *pairs;         /* P x 2 (map view, frame), device */
+    int32_t P;
+    int32_t maxMatches;           /* row capacity of out->matches / out->inlierMask for every pair */
+    float radiusBound;            /* ps_map_sphere_bound(radius), used when radiusBoundPerPair is NULL */
+    double acceptRatio;           /* used when acceptRatioPerPair is NULL */
+    const float *radiusBoundPerPair;   /* device, P, or NULL */
+    const double *acceptRatioPerPair;  /* device, P, or NULL */
+} PsMapBatch;
+
+/* All pointers inside PsMapBatch and PsPairResults are DEVICE pointers.  Both calls are asynchronous on the context's stream,
+ * copy nothing to or from the host and do not synchronise (growing the context's scratch on a first call aside, as with
+ * ps_vo_pairs_device).
+ *   matches: P x maxMatches; pair p's list is exactly what ps_match_xyz returns for that map view and frame with that pair's
+ *     radius and ratio: candidates by sphere and |level difference| <= 1 (:699-711), value = popcount of the per-byte
+ *     SATURATING difference mapDesc - curDesc (:719-721), best = smallest value with the first index on ties (:714-727), every
+ *     candidate with acceptRatio * value <= best emitted as DMatch(j, i, -1, value) (:734-746), ordered by (j, i).
+ *   numMatches[p]: the count.  If it exceeds maxMatches, numMatches[p] = -(count), nothing of that pair's rows need be
+ *     meaningful and the estimator treats the pair as having no matches; other pairs are unaffected (ps_match_xyz's "returns
+ *     the needed capacity" rule, per pair and without a round trip).  A pair that names a view or a frame outside its set has
+ *     no matches.
+ * ps_map_pairs_device then runs the estimator of cfg with params->errorVersion as given (the caller sets errorVersionMap, as
+ * with ps_ransac_rigid3d) on prev = maps.pts, cur = frames.pts; pair p draws from cfg->seed + p; cfg->sampleIdx must be NULL.
+ * Mask, pose and every field of PsRansacStats are byte for byte those of ps_match_xyz followed by ps_ransac_rigid3d with
+ * seed + p on the same pair.  A pair without matches gives identity, numInliers = 0, accepted = 0, pointInlierRatio = NaN
+ * (the wrappers turn that into the reference's -1.0, matcher.cpp:755-756); an overflowed pair's stats.numMatchesIn is 0.
+ * Limits: maxKpts of either set above PS_MAX_KPTS or maxMatches above 1 << 22 -> PS_ERR_UNSUPPORTED; maxMatches < 1, bad
+ * strides (the rule of PsFrameSet), NULL where an array is needed, P < 0 -> PS_ERR_BAD_ARG (text: ps_last_error); outputs are
+ * not touched.  P == 0 is PS_OK.
+ * Scratch grows with P x maxMatches: 16 B a match for the staging rows and, for ps_map_pairs_device, about 150 B a match for
+ * the scoring records (0.6 GB for 499 pairs x 8000); size maxMatches to the tries that are run (4 x maxKpts holds the tenth
+ * try of the retry ladder on the test scenes, maxKpts the first).  The keys block the VO calls share is not touched. */
+int ps_match_xyz_device(PsContext *ctx, const PsMapBatch *b, PsDMatch *matches, int32_t *numMatches);
+int ps_map_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                        const PsMapBatch *b, const PsPairResults *out);
+
 /* ---- A2, for a host that loops over batches (the loop of src/PUTSLAM/PUTSLAM.cpp:677-740 around Matcher::match,
  * src/Matcher/matcher.cpp:470-515): ps_vo_pairs_device through launch chains that are never joined.
  * One context is one launch chain: a batch's matrix-core Hamming sweep, then its vector scoring stages, dependent launches with
@@ -588,6 +639,7 @@ size_t ps_abi_sizeof_stats(void);
 size_t ps_abi_sizeof_frameset(void);
 size_t ps_abi_sizeof_results(void);
 size_t ps_abi_sizeof_host_results(void);
+size_t ps_abi_sizeof_map_batch(void);
 
 #ifdef __cplusplus
 }

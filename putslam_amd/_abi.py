@@ -61,6 +61,12 @@ class PsPairResults(C.Structure):
                 ("pose", C.c_void_p), ("stats", C.c_void_p)]
 
 
+class PsMapBatch(C.Structure):
+    _fields_ = [("maps", PsFrameSet), ("mapLevel", C.c_void_p), ("frames", PsFrameSet), ("curLevel", C.c_void_p),
+                ("pairs", C.c_void_p), ("P", C.c_int32), ("maxMatches", C.c_int32), ("radiusBound", C.c_float),
+                ("acceptRatio", C.c_double), ("radiusBoundPerPair", C.c_void_p), ("acceptRatioPerPair", C.c_void_p)]
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

@@ -6,7 +6,7 @@ object is missing the import fails loudly and tells the caller how to build it.
 import ctypes as C
 import os
 
-from ._abi import PsDMatch, PsFrameSet, PsHostPairResults, PsPairResults, PsRansacConfig, PsRansacParams, PsRansacStats
+from ._abi import PsDMatch, PsFrameSet, PsHostPairResults, PsMapBatch, PsPairResults, PsRansacConfig, PsRansacParams, PsRansacStats
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -36,6 +36,7 @@ EXPORTED = [
     "ps_debug_ransac_counts", "ps_debug_limits", "ps_debug_keys_clean", "ps_debug_fastdiv", "ps_debug_mathcheck", "ps_debug_score_stats", "ps_debug_score_stats_ex", "ps_debug_stage_survivors", "ps_debug_stage_order", "ps_debug_stamps",
     "ps_abi_sizeof_dmatch", "ps_abi_sizeof_params", "ps_abi_sizeof_config", "ps_abi_sizeof_stats",
     "ps_abi_sizeof_frameset", "ps_abi_sizeof_results", "ps_abi_sizeof_host_results",
+    "ps_map_sphere_bound", "ps_match_xyz_device", "ps_map_pairs_device", "ps_abi_sizeof_map_batch",
 ]
 
 _lib = None
@@ -170,6 +171,11 @@ def load_path(path):
     L.ps_host_free.restype = None
     L.ps_vo_pairs_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp,
                                      C.POINTER(PsFrameSet), vp, i32, C.POINTER(PsPairResults)]
+    L.ps_map_sphere_bound.argtypes = [C.c_double]
+    L.ps_map_sphere_bound.restype = C.c_float
+    L.ps_match_xyz_device.argtypes = [vp, C.POINTER(PsMapBatch), vp, vp]
+    L.ps_map_pairs_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsMapBatch),
+                                      C.POINTER(PsPairResults)]
     L.ps_batch_queue_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.ps_batch_queue_destroy.argtypes = [vp]
     L.ps_batch_queue_destroy.restype = None
@@ -190,7 +196,7 @@ def load_path(path):
     L.ps_last_kernel_times_ms.argtypes = [vp, vp]
     L.ps_kernel_time_totals.argtypes = [vp, vp, vp]
     L.ps_context_enable_timing.argtypes = [vp, i32]
-    for n in ("dmatch", "params", "config", "stats", "frameset", "results", "host_results"):
+    for n in ("dmatch", "params", "config", "stats", "frameset", "results", "host_results", "map_batch"):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -199,4 +205,4 @@ def load_path(path):
 def struct_sizes():
     return dict(dmatch=C.sizeof(PsDMatch), params=C.sizeof(PsRansacParams), config=C.sizeof(PsRansacConfig),
                 stats=C.sizeof(PsRansacStats), frameset=C.sizeof(PsFrameSet), results=C.sizeof(PsPairResults),
-                host_results=C.sizeof(PsHostPairResults))
+                host_results=C.sizeof(PsHostPairResults), map_batch=C.sizeof(PsMapBatch))

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_OK, PsFrameSet, PsHostPairResults, PsPairResults,  # noqa: F401
+from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_OK, PsFrameSet, PsHostPairResults, PsMapBatch, PsPairResults,  # noqa: F401
                    PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
 
 
@@ -26,6 +26,27 @@ def _p(a):
 def dbscan_bound(eps):
     """ps_debug_dbscan_bound: the least double s* with (double)(float)sqrt(s*) >= eps (DBScan's predicate is s < s*)."""
     return float(_lib.load().ps_debug_dbscan_bound(float(eps)))
+
+
+def map_sphere_bound(radius):
+    """ps_map_sphere_bound: the least float B with  (float)|a - b| < radius  <=>  squared sum < B  (PsMapBatch.radiusBound)."""
+    return float(_lib.load().ps_map_sphere_bound(float(radius)))
+
+
+def ladder_try(radius, ratio, k):
+    """(sphere radius, accept ratio) of try k = 1, 2, ... of Matcher::matchXYZ (matcher.cpp:617-622)."""
+    if k > 1:
+        return radius + 0.02 * (k - 1), max(0.1, ratio - 0.05 * (k - 1))
+    return radius, ratio
+
+
+def ladder_pick(ratios, min_ratio=0.1):
+    """The try the loop of PUTSLAM.cpp:788-798 ends on (0-based): the first whose inlier ratio is not below min_ratio, else
+    the last.  A NaN ratio (no matches) counts as the reference's -1.0 (matcher.cpp:755-756)."""
+    for k, r in enumerate(ratios):
+        if (-1.0 if r != r else r) >= min_ratio:
+            return k
+    return len(ratios) - 1
 
 
 class Context:
@@ -316,6 +337,78 @@ class Context:
         self._chk(self._L.ps_vo_pairs_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(fs),
                                              C.c_void_p(pairs_dev_ptr), int(P), C.byref(res)))
 
+    # ---- N2, device-resident batch ----
+    def _map_batch(self, b: "DeviceMapBatch"):
+        mb = PsMapBatch()
+        for dst, f in ((mb.maps, b.maps), (mb.frames, b.frames)):
+            dst.desc, dst.pts, dst.nkpts = f.desc_ptr, f.pts_ptr, f.nkpts_ptr
+            dst.numFrames, dst.maxKpts = f.num_frames, f.max_kpts
+            dst.descFrameStride, dst.ptsFrameStride = f.desc_stride, f.pts_stride
+        mb.mapLevel, mb.curLevel, mb.pairs = b.map_level_ptr, b.cur_level_ptr, b.pairs_ptr
+        mb.P, mb.maxMatches = b.P, b.max_matches
+        mb.radiusBound, mb.acceptRatio = b.radius_bound, b.accept_ratio
+        mb.radiusBoundPerPair, mb.acceptRatioPerPair = b.radius_bound_per_pair_ptr, b.accept_ratio_per_pair_ptr
+        return mb
+
+    def match_xyz_device(self, batch: "DeviceMapBatch", matches_ptr, num_matches_ptr):
+        """ps_match_xyz_device: the guided matching of every pair of the batch; asynchronous, device pointers."""
+        mb = self._map_batch(batch)
+        self._chk(self._L.ps_match_xyz_device(self._h, C.byref(mb), C.c_void_p(matches_ptr), C.c_void_p(num_matches_ptr)))
+
+    def map_pairs_device(self, params, cfg, K, batch: "DeviceMapBatch", out: "DeviceResults"):
+        """ps_map_pairs_device: guided matching + the estimator for every pair; asynchronous, device pointers."""
+        K = None if K is None else np.ascontiguousarray(K, np.float32)
+        mb = self._map_batch(batch)
+        res = PsPairResults(out.matches_ptr, out.num_matches_ptr, out.mask_ptr, out.pose_ptr, out.stats_ptr)
+        self._chk(self._L.ps_map_pairs_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(mb), C.byref(res)))
+
+    def match_xyz_ladder(self, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, params, cfg, K, radius=0.12,
+                         ratio=0.55, max_tries=10, min_ratio=0.1, max_matches=None, device=None):
+        """The retry loop of PUTSLAM.cpp:788-798 around Matcher::matchXYZ as ONE ps_map_pairs_device call of `max_tries` pairs
+        that all name the same map view and frame: try k = 1 .. max_tries has radius + 0.02 (k - 1) and
+        max(0.1, ratio - 0.05 (k - 1)) (matcher.cpp:617-622) and draws from cfg.seed + k - 1.  Returns the first try whose
+        pointInlierRatio (-1.0 for "no matches") is not below min_ratio, else the last: dict(matches, mask, pose (4 x 4), stats,
+        inlier_ratio, try_used (1-based), num_matches).  max_matches (default 4 x map features) is the rows' first capacity: if
+        any try overflows it the call is repeated once with the largest reported count, so no try is ever passed over.
+        The call does max_tries times the work of a first try that succeeds -- it is meant for hosts that care about the
+        worst frame, whose ten sequential tries are ten round trips; a host that cares about the average frame calls
+        match_xyz + ransac_rigid3d and retries.  Measured (profiles/r08a/map_pairs.txt): 0.55 ms at 500 x 500 and 0.85 ms at
+        2000 x 2000 against 0.23 / 0.68 / 2.3 ms and 0.30 / 0.89 / 3.2 ms for one / three / ten sequential tries -- the ladder
+        wins from the third try on."""
+        from . import device_batch
+        map_pos = np.ascontiguousarray(map_pos, np.float32)
+        cur_pos = np.ascontiguousarray(cur_pos, np.float32)
+        nmap, ncur = map_pos.shape[0], cur_pos.shape[0]
+        dev = device if device is not None else "cuda:%d" % self._L.ps_context_device(self._h)
+
+        def side(desc, pos, level, n):       # one view / frame as a frame set of its own (capacity >= 1)
+            cap = max(n, 1)
+            d, q, lv = np.zeros((1, cap, 32), np.uint8), np.zeros((1, cap, 3), np.float32), np.zeros((1, cap), np.int32)
+            if n:
+                d[0], q[0], lv[0] = np.asarray(desc, np.uint8).reshape(n, 32), pos, np.asarray(level, np.int32).reshape(n)
+            return device_batch.FrameSetDevice(d, q, [n], dev), lv
+
+        views, mlv = side(map_desc, map_pos, map_level, nmap)
+        frames, clv = side(cur_desc, cur_pos, cur_level, ncur)
+        tries = [ladder_try(float(radius), float(ratio), k) for k in range(1, int(max_tries) + 1)]
+        cap = int(max_matches) if max_matches is not None else max(1, 4 * nmap)
+        for attempt in range(2):
+            batch = device_batch.MapBatchDevice(views, mlv, frames, clv, np.zeros((len(tries), 2), np.int32), cap,
+                                                radius=[t[0] for t in tries], ratio=[t[1] for t in tries])
+            device_batch.run_map_pairs(self, params, cfg, K, batch)
+            r = batch.download()
+            need = int(-r["numMatches"].min()) if len(tries) else 0
+            if need <= cap:
+                break
+            cap = need      # a try overflowed its rows (-(count)): once more with room for the largest, as the loop would see it
+        ratios = [float(x) for x in r["stats"]["pointInlierRatio"]]
+        k = ladder_pick(ratios, min_ratio)
+        n = max(int(r["numMatches"][k]), 0)
+        ir = ratios[k]
+        return dict(matches=r["matches"][k, :n].copy(), mask=r["inlierMask"][k, :n].copy(), pose=r["pose"][k].reshape(4, 4).T.copy(),
+                    stats=r["stats"][k].copy(), inlier_ratio=-1.0 if ir != ir else ir, try_used=k + 1,
+                    num_matches=int(r["numMatches"][k]))
+
 
 class _ChainContext(Context):
     """A chain context of a BatchQueue: owned by the queue (never destroyed from here)."""
@@ -575,6 +668,18 @@ class DeviceResults:
     def __init__(self, matches_ptr, num_matches_ptr, mask_ptr, pose_ptr, stats_ptr):
         self.matches_ptr, self.num_matches_ptr, self.mask_ptr = matches_ptr, num_matches_ptr, mask_ptr
         self.pose_ptr, self.stats_ptr = pose_ptr, stats_ptr
+
+
+class DeviceMapBatch:
+    """Raw device pointers of a map-matching batch (PsMapBatch): maps / frames are DeviceFrames."""
+
+    def __init__(self, maps: DeviceFrames, map_level_ptr, frames: DeviceFrames, cur_level_ptr, pairs_ptr, P, max_matches,
+                 radius_bound=0.0, accept_ratio=0.0, radius_bound_per_pair_ptr=None, accept_ratio_per_pair_ptr=None):
+        self.maps, self.frames = maps, frames
+        self.map_level_ptr, self.cur_level_ptr, self.pairs_ptr = map_level_ptr, cur_level_ptr, pairs_ptr
+        self.P, self.max_matches = int(P), int(max_matches)
+        self.radius_bound, self.accept_ratio = float(radius_bound), float(accept_ratio)
+        self.radius_bound_per_pair_ptr, self.accept_ratio_per_pair_ptr = radius_bound_per_pair_ptr, accept_ratio_per_pair_ptr
 
 
 def kernel_names():

@@ -16,6 +16,8 @@
 
 #include "putslam_hip.h"
 
+#include <hip/hip_runtime_api.h> // device block of matchXYZLadder (the C ABI takes device pointers there)
+
 static_assert(sizeof(cv::DMatch) == sizeof(PsDMatch), "cv::DMatch layout");
 static_assert(sizeof(Eigen::Vector3f) == 12, "Eigen::Vector3f storage");
 
@@ -700,6 +702,195 @@ double FrameMatcher::matchXYZ(const std::vector<MapFeatureXYZ> &mapFeatures, cv:
     if (seeded_) ransac.setSampleSeed(seed_ + 0x51ED270B0B5ull + (uint64_t)frameCounter);
     estimatedTransformation = ransac.estimateTransformation(mapFeaturePositions3D, currentPoseFeatures3D, matches, inlierMatches);
     return RANSAC::pointInlierRatio(inlierMatches, matches);
+}
+
+namespace {
+// device block of matchXYZLadder, kept per thread like the context it is used with
+struct LadderBlock {
+    void *p = nullptr;
+    size_t cap = 0;
+    ~LadderBlock()
+    {
+        if (p) (void)hipFree(p);
+    }
+    int device = -1;
+    bool room(size_t bytes) // (the calling thread's current device is the context's)
+    {
+        int dev = -1;
+        if (hipGetDevice(&dev) != hipSuccess) return false;
+        if (dev != device && p) { // (the thread's context is on another device than the block)
+            (void)hipFree(p);
+            p = nullptr;
+            cap = 0;
+        }
+        device = dev;
+        if (bytes <= cap) return true;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        if (hipMalloc(&p, bytes + bytes / 4) != hipSuccess) return false;
+        cap = bytes + bytes / 4;
+        return true;
+    }
+};
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+} // namespace
+
+double FrameMatcher::matchXYZLadder(const std::vector<MapFeatureXYZ> &mapFeatures, cv::Mat currentPoseDescriptors,
+                                    std::vector<Eigen::Vector3f> &currentPoseFeatures3D, const std::vector<int> &currentPoseOctaves,
+                                    const std::vector<double> &currentPoseDetDists, Eigen::Matrix4f &estimatedTransformation,
+                                    std::vector<cv::DMatch> &inlierMatches, int maxTries, double minRatio, int *tryUsed)
+{
+    if (maxTries < 1) maxTries = 1;
+    if (tryUsed) *tryUsed = maxTries; // (no try reaches minRatio: the last one is returned)
+    const size_t nmap = mapFeatures.size(), ncur = currentPoseFeatures3D.size();
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx || nmap == 0 || ncur == 0) return -1.0; // every try of matchXYZ returns -1.0
+    const int T = maxTries;
+    int cap = (int)(4 * nmap + 16);
+    // inputs, in one host block that mirrors the device block: descriptors | points | levels | counts | pairs | bounds | ratios
+    const size_t oMapDesc = 0, oCurDesc = oMapDesc + nmap * 32, oMapPts = oCurDesc + ncur * 32, oCurPts = up16(oMapPts + nmap * 12),
+                 oMapLvl = up16(oCurPts + ncur * 12), oCurLvl = up16(oMapLvl + nmap * 4), oCounts = up16(oCurLvl + ncur * 4),
+                 oPairs = oCounts + 16, oBound = up16(oPairs + (size_t)T * 8), oRatio = up16(oBound + (size_t)T * 4),
+                 inBytes = up16(oRatio + (size_t)T * 8);
+    std::vector<unsigned char> in(inBytes, 0);
+    for (size_t j = 0; j < nmap; ++j) { // matcher.cpp:681-692,701-702
+        const MapFeatureXYZ &f = mapFeatures[j];
+        const double curDist = std::sqrt(f.position[0] * f.position[0] + f.position[1] * f.position[1] + f.position[2] * f.position[2]);
+        const int32_t lvl = ps_predicted_level(f.octave, f.detDist, curDist);
+        const float pos[3] = {(float)f.position[0], (float)f.position[1], (float)f.position[2]};
+        std::memcpy(&in[oMapLvl + j * 4], &lvl, 4);
+        std::memcpy(&in[oMapPts + j * 12], pos, 12);
+        if (!f.descriptor.empty()) std::memcpy(&in[oMapDesc + j * 32], f.descriptor.data, 32);
+    }
+    for (size_t i = 0; i < ncur; ++i) { // :639-652; curDist = Eigen float norm()
+        const Eigen::Vector3f &p = currentPoseFeatures3D[i];
+        const float nrm = std::sqrt(p[0] * p[0] + (p[1] * p[1] + p[2] * p[2]));
+        const int32_t lvl = ps_predicted_level(currentPoseOctaves[i], currentPoseDetDists[i], (double)nrm);
+        std::memcpy(&in[oCurLvl + i * 4], &lvl, 4);
+        std::memcpy(&in[oCurDesc + i * 32], currentPoseDescriptors.data + i * (size_t)currentPoseDescriptors.step, 32);
+    }
+    std::memcpy(&in[oCurPts], currentPoseFeatures3D.data(), ncur * 12);
+    const int32_t counts[2] = {(int32_t)nmap, (int32_t)ncur};
+    std::memcpy(&in[oCounts], counts, 8);
+    for (int k = 1; k <= T; ++k) { // matcher.cpp:616-622 for computationNumber = k; the pairs all name view 0, frame 0
+        double radius = matcherParameters.OpenCVParams.matchingXYZSphereRadius;
+        double ratio = matcherParameters.OpenCVParams.matchingXYZacceptRatioOfBestMatch;
+        if (k > 1) {
+            radius += 0.02 * (k - 1);
+            ratio = std::max(0.1, ratio - 0.05 * (k - 1));
+        }
+        const float bound = ps_map_sphere_bound(radius);
+        std::memcpy(&in[oBound + (size_t)(k - 1) * 4], &bound, 4);
+        std::memcpy(&in[oRatio + (size_t)(k - 1) * 8], &ratio, 8);
+    }
+    matcherParameters.RANSACParams.errorVersion = matcherParameters.RANSACParams.errorVersionMap; // :760-761
+    RANSAC::parameters rp = matcherParameters.RANSACParams;
+    rp.iterationCount = ransacIterations(0.20); // RANSAC.cpp:30
+    const PsRansacParams prm = toPs(rp);
+    int a = ransacIterations(0.20), b = ransacIterations(rp.minimalInlierRatioThreshold); // (RANSAC::estimateTransformation above)
+    int H = a > b ? a : b;
+    if (H < 1) H = 1;
+    if (H > PS_MAX_HYPOTHESES) H = PS_MAX_HYPOTHESES;
+    PsRansacConfig cfg;
+    cfg.estimator = PS_EST_RANSAC;
+    cfg.numHypotheses = H;
+    cfg.seed = seeded_ ? seed_ + 0x51ED270B0B5ull + (uint64_t)frameCounter : (uint64_t)std::time(nullptr); // try k: + (k - 1)
+    cfg.sampleIdx = nullptr;
+    float K[9];
+    bool haveK;
+    cameraToK(matcherParameters.cameraMatrixMat, K, haveK);
+
+    static thread_local LadderBlock block;
+    std::vector<unsigned char> out;
+    size_t oMatches = 0, oNum = 0, oMask = 0, oPose = 0, oStats = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        oMatches = 0;
+        oNum = oMatches + (size_t)T * cap * sizeof(PsDMatch);
+        oMask = up16(oNum + (size_t)T * 4);
+        oPose = up16(oMask + (size_t)T * cap);
+        oStats = oPose + (size_t)T * 64;
+        const size_t outBytes = up16(oStats + (size_t)T * sizeof(PsRansacStats));
+        // the block lives on the context's device, and the upload is queued on the context's stream, in front of the launches
+        // that read it (`in` outlives the synchronisation below)
+        hipStream_t stream = static_cast<hipStream_t>(ps_context_stream(ctx));
+        if (hipSetDevice(ps_context_device(ctx)) != hipSuccess || !block.room(inBytes + outBytes) ||
+            hipMemcpyAsync(block.p, in.data(), inBytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
+            std::cerr << "putslam_hip: matchXYZLadder: no device memory" << std::endl;
+            return -1.0;
+        }
+        unsigned char *d = static_cast<unsigned char *>(block.p), *o = d + inBytes;
+        PsMapBatch mb;
+        std::memset(&mb, 0, sizeof mb);
+        mb.maps.desc = d + oMapDesc;
+        mb.maps.pts = reinterpret_cast<const float *>(d + oMapPts);
+        mb.maps.nkpts = reinterpret_cast<const int32_t *>(d + oCounts);
+        mb.maps.numFrames = 1;
+        mb.maps.maxKpts = (int32_t)nmap;
+        mb.mapLevel = reinterpret_cast<const int32_t *>(d + oMapLvl);
+        mb.frames.desc = d + oCurDesc;
+        mb.frames.pts = reinterpret_cast<const float *>(d + oCurPts);
+        mb.frames.nkpts = reinterpret_cast<const int32_t *>(d + oCounts) + 1;
+        mb.frames.numFrames = 1;
+        mb.frames.maxKpts = (int32_t)ncur;
+        mb.curLevel = reinterpret_cast<const int32_t *>(d + oCurLvl);
+        mb.pairs = reinterpret_cast<const int32_t *>(d + oPairs);
+        mb.P = T;
+        mb.maxMatches = cap;
+        mb.radiusBoundPerPair = reinterpret_cast<const float *>(d + oBound);
+        mb.acceptRatioPerPair = reinterpret_cast<const double *>(d + oRatio);
+        PsPairResults res;
+        res.matches = reinterpret_cast<PsDMatch *>(o + oMatches);
+        res.numMatches = reinterpret_cast<int32_t *>(o + oNum);
+        res.inlierMask = o + oMask;
+        res.pose = reinterpret_cast<float *>(o + oPose);
+        res.stats = reinterpret_cast<PsRansacStats *>(o + oStats);
+        status = ps_map_pairs_device(ctx, &prm, &cfg, haveK ? K : nullptr, &mb, &res);
+        out.resize(outBytes);
+        const bool copied = status == PS_OK && hipMemcpyAsync(out.data(), o, outBytes, hipMemcpyDeviceToHost, stream) == hipSuccess;
+        const int sync = ps_context_synchronize(ctx); // (also after a failed call: the upload may still be reading `in`)
+        if (status == PS_OK) status = sync;
+        if (status != PS_OK) {
+            std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+            return -1.0;
+        }
+        if (!copied) return -1.0;
+        int32_t need = 0; // a try that overflowed its rows reports -(count): once more with room for the largest
+        for (int k = 0; k < T; ++k) {
+            int32_t n;
+            std::memcpy(&n, &out[oNum + (size_t)k * 4], 4);
+            if (-n > need) need = -n;
+        }
+        if (need <= cap) break;
+        cap = need;
+    }
+    // the loop of PUTSLAM.cpp:788-798: the first try whose ratio is not below minRatio, else the last
+    int pick = T - 1;
+    double ratioOf = -1.0;
+    for (int k = 0; k < T; ++k) {
+        int32_t n;
+        PsRansacStats st;
+        std::memcpy(&n, &out[oNum + (size_t)k * 4], 4);
+        std::memcpy(&st, &out[oStats + (size_t)k * sizeof(PsRansacStats)], sizeof st);
+        ratioOf = n <= 0 ? -1.0 : st.pointInlierRatio; // matcher.cpp:755-756
+        if (ratioOf >= minRatio) {
+            pick = k;
+            break;
+        }
+    }
+    if (tryUsed) *tryUsed = pick + 1;
+    int32_t n;
+    std::memcpy(&n, &out[oNum + (size_t)pick * 4], 4);
+    if (matcherParameters.verbose > 0) std::cout << "MatchesXYZ - we found : " << (n > 0 ? n : 0) << std::endl;
+    if (n <= 0) return -1.0;
+    const PsDMatch *m = reinterpret_cast<const PsDMatch *>(&out[oMatches]) + (size_t)pick * cap;
+    const unsigned char *mask = &out[oMask + (size_t)pick * cap];
+    inlierMatches.clear();
+    for (int i = 0; i < n; ++i)
+        if (mask[i]) inlierMatches.push_back(cv::DMatch(m[i].queryIdx, m[i].trainIdx, m[i].imgIdx, m[i].distance));
+    std::memcpy(estimatedTransformation.data(), &out[oPose + (size_t)pick * 64], 64);
+    return ratioOf;
 }
 
 void VOTrajectory::addIncrement(Eigen::Matrix4f inc)

@@ -245,6 +245,16 @@ class FrameMatcher {
                     std::vector<Eigen::Vector3f> &currentPoseFeatures3D, const std::vector<int> &currentPoseOctaves,
                     const std::vector<double> &currentPoseDetDists, Eigen::Matrix4f &estimatedTransformation,
                     std::vector<cv::DMatch> &inlierMatches, int computationNumber = 1);
+    // The retry loop of PUTSLAM.cpp:788-798 around matchXYZ as ONE device call (ps_map_pairs_device): tries 1 .. maxTries -- radius
+    // + 0.02 (k - 1), ratio max(0.1, a - 0.05 (k - 1)), matcher.cpp:617-622 -- run side by side on the view and the frame uploaded
+    // once, and the first try whose inlier ratio is not below minRatio is returned, else the last (*tryUsed = its number).  Try k
+    // draws from seed + 0x51ED270B0B5 + frameCounter + (k - 1): equal to matchXYZ at try 1; matchXYZ's later tries all draw from
+    // the one seed, so the sample streams differ from try 2 on.  It does maxTries times the work of a first try that succeeds: for
+    // hosts that care about the worst frame (ten sequential tries are ten round trips).
+    double matchXYZLadder(const std::vector<MapFeatureXYZ> &mapFeatures, cv::Mat currentPoseDescriptors,
+                          std::vector<Eigen::Vector3f> &currentPoseFeatures3D, const std::vector<int> &currentPoseOctaves,
+                          const std::vector<double> &currentPoseDetDists, Eigen::Matrix4f &estimatedTransformation,
+                          std::vector<cv::DMatch> &inlierMatches, int maxTries = 10, double minRatio = 0.1, int *tryUsed = nullptr);
     // ---- pipelined form of runVO (ps_vo_stream_push_async / ps_vo_stream_pop, include/putslam_hip.h): the same call shape --
     // one frame per call, the previous frame kept as state (matcher.cpp:452-516) -- with the result returned with a LAG, so that
     // uploads, kernels and downloads of consecutive frames overlap (BASELINE configs[2]: a sequence streamed through the matcher).

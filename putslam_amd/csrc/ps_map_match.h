@@ -1,0 +1,368 @@
+// ps_map_match.h -- batched, device-resident guided map matching: Matcher::matchXYZ (reference src/Matcher/matcher.cpp:694-746)
+// for P (map view, frame) pairs in two launches, no host step (ps_match_xyz_device / ps_map_pairs_device, include/putslam_hip.h).
+// The rule is ps_match_xyz_kernel's (ps_kernels.h), which sweeps a frame twice between a count, a scan and a write launch:
+//
+//   ps_map_sweep<F>   grid P x chunks, a chunk = 4 waves x F map features.  The frame's positions and levels pass through LDS
+//                     once per work-group, 1024 keypoints at a time; a wave holds its F features in scalar registers, so one LDS
+//                     read serves F sphere tests.  Candidates are rare (0 - 3 per feature at the first try of the retry ladder,
+//                     up to 14 at the tenth): a feature's candidates (i, value) are appended in ballot order -- ascending i -- to
+//                     a stash of kMapStash entries in LDS, and best / ratio / emit work on that list.  A feature with more
+//                     candidates than the stash holds is swept again from global memory (map_resweep, the old kernel's second
+//                     sweep).  The chunk's accepted matches, ordered by (j, i), go to a place in the pair's row of a staging
+//                     block that the chunk reserves with ONE atomic add; (start, count) are kept per chunk.
+//   ps_map_emit       grid P.  Scans the pair's chunk counts and moves the chunks to the output row in chunk order -- the
+//                     (j, i) order of the reference's push_back loop whatever order the chunks ran in -- and, in the same pass
+//                     over the matches, does what ps_prep_from_matches does for one pair: depth filter, ordered compaction,
+//                     scoring records, bounds, the scoring stage's counters cleared.
+// A pair whose count exceeds the row capacity reports -(count) and is handed to RANSAC with no matches.
+#pragma once
+
+#include "ps_kernels.h"
+
+namespace psdev {
+
+constexpr int kMapBlock = 256;  // 4 waves
+constexpr int kMapWaves = kMapBlock / 64;
+constexpr int kMapTile = 1024;  // keypoints staged per trip: 16 KiB of LDS
+constexpr int kMapStash = 16;   // candidates kept per map feature
+
+struct MapArgs {
+    const float *mapPts, *curPts;     // frame sets' points
+    const uint4 *mapDesc, *curDesc;   // ... descriptors
+    const int32_t *mapN, *curN;       // ... keypoint counts
+    const int32_t *mapLevel, *curLevel; // [numFrames][maxKpts]
+    int mapFrames, curFrames, mapCap, curCap;
+    int mapPtsStride, curPtsStride;   // floats between frames
+    int mapDescStride, curDescStride; // uint4 between frames
+    const int32_t *pairs;             // P x (map view, frame)
+    float radiusBound;
+    double acceptRatio;
+    const float *radiusPer;           // P or null
+    const double *ratioPer;           // P or null
+    int maxMatches;                   // row capacity
+    int chunks;                       // chunks per pair = ceil(mapCap / chunk size)
+    int chunkFeatures;                // 4 x F
+    PsDMatch *tmp;                    // [P][maxMatches] staging rows
+    int32_t *tmpCount;                // [P] matches reserved so far (cleared before the sweep)
+    int32_t *chunkStart, *chunkCount; // [P][chunks]
+};
+
+// keypoints of a view / frame a pair may touch: 0 for an index outside the set, counts clamped to the row capacity
+PS_D int map_count(const int32_t *__restrict__ n, int frame, int frames, int cap)
+{
+    if (frame < 0 || frame >= frames) return 0;
+    const int v = n[frame];
+    return v < 0 ? 0 : (v > cap ? cap : v);
+}
+
+PS_D unsigned long long wave_min_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        unsigned long long other = __shfl_down(v, o, 64);
+        v = other < v ? other : v;
+    }
+    return __shfl(v, 0, 64);
+}
+
+// One wave, one map feature, the whole frame from global memory: every candidate within the accept ratio of bestVal,
+// ascending i.  Returns their number; WRITE emits them from out[0] on.
+template <bool WRITE>
+PS_D int map_resweep(float mx, float my, float mz, int lj, const uint4 &a0, const uint4 &a1, const float *__restrict__ curPos,
+                     const uint4 *__restrict__ curDesc, const int32_t *__restrict__ curLevel, int ncur, float radiusBound,
+                     double acceptRatio, float bestVal, int j, PsDMatch *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    int n = 0;
+    for (int i0 = 0; i0 < ncur; i0 += 64) {
+        const int i = i0 + lane;
+        bool acc = false;
+        float value = 0.f;
+        if (i < ncur) {
+            const float d0 = mx - curPos[3 * i], d1 = my - curPos[3 * i + 1], d2 = mz - curPos[3 * i + 2];
+            const float s = d0 * d0 + (d1 * d1 + d2 * d2);
+            const int li = curLevel[i];
+            if (s < radiusBound && li - 1 <= lj && lj <= li + 1) {
+                value = (float)satdiff_popc256(a0, a1, curDesc[2 * i], curDesc[2 * i + 1]);
+                acc = acceptRatio * (double)value <= (double)bestVal;
+            }
+        }
+        const unsigned long long bal = __ballot(acc);
+        if (WRITE && acc) {
+            PsDMatch m;
+            m.queryIdx = j;
+            m.trainIdx = i;
+            m.imgIdx = -1; // default-constructed cv::DMatch (matcher.cpp:741)
+            m.distance = value;
+            out[n + __popcll(bal & ((1ull << lane) - 1ull))] = m;
+        }
+        n += __popcll(bal);
+    }
+    return n;
+}
+
+template <int F>
+__global__ __launch_bounds__(kMapBlock) void ps_map_sweep(MapArgs a)
+{
+    constexpr int CH = kMapWaves * F;
+    __shared__ uint4 s_tile[kMapTile];
+    __shared__ uint2 s_stash[CH * kMapStash];
+    __shared__ int s_n[CH];
+    __shared__ int s_start;
+    const int p = blockIdx.x / a.chunks, c = blockIdx.x - p * a.chunks;
+    const int view = a.pairs[2 * p], frame = a.pairs[2 * p + 1];
+    const int nmap = map_count(a.mapN, view, a.mapFrames, a.mapCap);
+    const int ncur = map_count(a.curN, frame, a.curFrames, a.curCap);
+    const int j0 = c * CH;
+    if (j0 >= nmap || ncur == 0) { // (the whole work-group)
+        if (threadIdx.x == 0) {
+            a.chunkStart[(size_t)p * a.chunks + c] = 0;
+            a.chunkCount[(size_t)p * a.chunks + c] = 0;
+        }
+        return;
+    }
+    const float radiusBound = a.radiusPer ? a.radiusPer[p] : a.radiusBound;
+    const double acceptRatio = a.ratioPer ? a.ratioPer[p] : a.acceptRatio;
+    const float *__restrict__ mapPos = a.mapPts + (size_t)view * a.mapPtsStride;
+    const uint4 *__restrict__ mapDesc = a.mapDesc + (size_t)view * a.mapDescStride;
+    const int32_t *__restrict__ mapLevel = a.mapLevel + (size_t)view * a.mapCap;
+    const float *__restrict__ curPos = a.curPts + (size_t)frame * a.curPtsStride;
+    const uint4 *__restrict__ curDesc = a.curDesc + (size_t)frame * a.curDescStride;
+    const int32_t *__restrict__ curLevel = a.curLevel + (size_t)frame * a.curCap;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned long long below = (1ull << lane) - 1ull;
+
+    // the wave's F map features: wave-uniform (a feature beyond the view gets a NaN position: no test passes)
+    float mx[F], my[F], mz[F];
+    int lj[F], cnt[F];
+    unsigned long long best[F]; // per lane: least (value, i) among the candidates it has seen
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        const int j = j0 + w * F + f;
+        const bool has = j < nmap;
+        const int jc = has ? j : nmap - 1;
+        mx[f] = has ? mapPos[3 * jc] : __builtin_nanf("");
+        my[f] = mapPos[3 * jc + 1];
+        mz[f] = mapPos[3 * jc + 2];
+        lj[f] = mapLevel[jc];
+        cnt[f] = 0;
+        best[f] = ~0ull;
+    }
+
+    for (int t0 = 0; t0 < ncur; t0 += kMapTile) {
+        const int nt = ncur - t0 < kMapTile ? ncur - t0 : kMapTile;
+        __syncthreads(); // (the previous tile has been read)
+        for (int i = threadIdx.x; i < nt; i += kMapBlock) {
+            const int g = t0 + i;
+            s_tile[i] = make_uint4(__float_as_uint(curPos[3 * g]), __float_as_uint(curPos[3 * g + 1]),
+                                   __float_as_uint(curPos[3 * g + 2]), (uint32_t)curLevel[g]);
+        }
+        __syncthreads();
+        for (int i0 = 0; i0 < nt; i0 += 64) {
+            const int i = i0 + lane;
+            const bool inb = i < nt;
+            const uint4 q = s_tile[inb ? i : nt - 1];
+            const float px = __uint_as_float(q.x), py = __uint_as_float(q.y), pz = __uint_as_float(q.z);
+            const int li = (int)q.w;
+#pragma unroll
+            for (int f = 0; f < F; ++f) {
+                const float d0 = mx[f] - px, d1 = my[f] - py, d2 = mz[f] - pz;
+                const float s = d0 * d0 + (d1 * d1 + d2 * d2); // the reference's rounding (no contraction)
+                const bool hit = inb && s < radiusBound && li - 1 <= lj[f] && lj[f] <= li + 1;
+                const unsigned long long bal = __ballot(hit);
+                if (bal != 0ull) { // (rare; wave-uniform)
+                    const int j = j0 + w * F + f, g = t0 + i;
+                    if (hit) {
+                        const uint32_t v = satdiff_popc256(mapDesc[2 * j], mapDesc[2 * j + 1], curDesc[2 * g], curDesc[2 * g + 1]);
+                        const unsigned long long key = ((unsigned long long)v << 32) | (unsigned)g;
+                        best[f] = key < best[f] ? key : best[f];
+                        const int pos = cnt[f] + __popcll(bal & below);
+                        if (pos < kMapStash) s_stash[(w * F + f) * kMapStash + pos] = make_uint2((uint32_t)g, v);
+                    }
+                    cnt[f] += __popcll(bal);
+                }
+            }
+        }
+    }
+    __syncthreads(); // the stash is complete
+
+    // best / ratio over the short list (or a second sweep), the feature's accepted count
+    unsigned long long accMask[F];
+    float bestVal[F];
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        const int j = j0 + w * F + f;
+        accMask[f] = 0ull;
+        bestVal[f] = 0.f;
+        int n = 0;
+        if (cnt[f] > 0) {
+            bestVal[f] = (float)(uint32_t)(wave_min_u64(best[f]) >> 32);
+            if (cnt[f] <= kMapStash) {
+                bool acc = false;
+                if (lane < cnt[f]) acc = acceptRatio * (double)(float)s_stash[(w * F + f) * kMapStash + lane].y <= (double)bestVal[f];
+                accMask[f] = __ballot(acc);
+                n = __popcll(accMask[f]);
+            } else {
+                n = map_resweep<false>(mx[f], my[f], mz[f], lj[f], mapDesc[2 * j], mapDesc[2 * j + 1], curPos, curDesc, curLevel, ncur,
+                                       radiusBound, acceptRatio, bestVal[f], j, nullptr);
+            }
+        }
+        if (lane == 0) s_n[w * F + f] = n;
+    }
+    __syncthreads();
+    int total = 0, before = 0; // accepted matches of the chunk / of the features in front of this wave's
+    for (int k = 0; k < CH; ++k) {
+        const int n = s_n[k];
+        if (k < w * F) before += n;
+        total += n;
+    }
+    if (threadIdx.x == 0) {
+        const int start = total > 0 ? atomicAdd(&a.tmpCount[p], total) : 0;
+        s_start = start;
+        a.chunkStart[(size_t)p * a.chunks + c] = start;
+        a.chunkCount[(size_t)p * a.chunks + c] = total;
+    }
+    __syncthreads();
+    const int start = s_start;
+    // the pair overflows its row (ps_map_emit reports it from the total): nothing of it is kept
+    if (total == 0 || start < 0 || start > a.maxMatches - total) return;
+    PsDMatch *__restrict__ out = a.tmp + (size_t)p * a.maxMatches + start + before;
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        const int j = j0 + w * F + f;
+        if (cnt[f] == 0) continue;
+        if (cnt[f] <= kMapStash) {
+            if ((accMask[f] >> lane) & 1ull) {
+                const uint2 e = s_stash[(w * F + f) * kMapStash + lane];
+                PsDMatch m;
+                m.queryIdx = j;
+                m.trainIdx = (int)e.x;
+                m.imgIdx = -1; // default-constructed cv::DMatch (matcher.cpp:741)
+                m.distance = (float)e.y;
+                out[__popcll(accMask[f] & below)] = m;
+            }
+            out += __popcll(accMask[f]);
+        } else {
+            out += map_resweep<true>(mx[f], my[f], mz[f], lj[f], mapDesc[2 * j], mapDesc[2 * j + 1], curPos, curDesc, curLevel, ncur,
+                                     radiusBound, acceptRatio, bestVal[f], j, out);
+        }
+    }
+}
+
+// exclusive prefix of v over the work-group, in thread order; total = the sum
+template <int BLOCK> PS_D int block_scan_int(int v, int &total, int *wsum)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    int off = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < BLOCK / 64; ++i) {
+        const int s = wsum[i];
+        if (i < w) off += s;
+        total += s;
+    }
+    __syncthreads();
+    return off + incl - v;
+}
+
+// One work-group per pair: the chunks' matches in (j, i) order, the signed and the clamped count, and (REC) the scoring
+// records of the depth-valid ones as ps_prep_from_matches builds them for a single pair.
+template <bool REC, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void ps_map_emit(MapArgs a, PrepArgs pa, RecPtrs rec, PsDMatch *__restrict__ matches,
+                                                     int32_t *__restrict__ numMatches, int32_t *__restrict__ numClamped,
+                                                     int32_t *__restrict__ mvalid, float2 *__restrict__ cmaxOut)
+{
+    extern __shared__ __align__(16) int s_off[]; // chunks + 1 exclusive offsets
+    __shared__ int s_wsum[BLOCK / 64];
+    __shared__ float s_red[BLOCK / 64];
+    const int p = blockIdx.x;
+    const int view = a.pairs[2 * p], frame = a.pairs[2 * p + 1];
+    const int nmap = map_count(a.mapN, view, a.mapFrames, a.mapCap);
+    const int total = a.tmpCount[p];
+    const bool over = total < 0 || total > a.maxMatches;
+    const int m = over ? 0 : total;
+    const int chunks = m > 0 ? (nmap + a.chunkFeatures - 1) / a.chunkFeatures : 0;
+    const int32_t *__restrict__ cStart = a.chunkStart + (size_t)p * a.chunks;
+    const int32_t *__restrict__ cCount = a.chunkCount + (size_t)p * a.chunks;
+    int carry = 0;
+    for (int c0 = 0; c0 < chunks; c0 += BLOCK) {
+        const int c = c0 + threadIdx.x;
+        const int v = c < chunks ? cCount[c] : 0;
+        int sum;
+        const int ex = block_scan_int<BLOCK>(v, sum, s_wsum);
+        if (c < chunks) s_off[c] = carry + ex;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) s_off[chunks] = carry; // (= m)
+    __syncthreads();
+    const PsDMatch *__restrict__ tmp = a.tmp + (size_t)p * a.maxMatches;
+    PsDMatch *__restrict__ out = matches + (size_t)p * a.maxMatches;
+    const float *__restrict__ prev = a.mapPts + (size_t)(m > 0 ? view : 0) * a.mapPtsStride;
+    const float *__restrict__ cur = a.curPts + (size_t)(m > 0 ? frame : 0) * a.curPtsStride;
+    float cm = 0.0f, um = 0.0f;
+    int vbase = 0;
+    const float fixedBound = (REC && pa.mode != PS_ADAPTIVE_ERROR) ? sq_bound_f32(pa.thrE) : 0.0f;
+    for (int i0 = 0; i0 < m; i0 += BLOCK) {
+        const int i = i0 + threadIdx.x;
+        float px = 0, py = 0, pz = 0, cx_ = 0, cy_ = 0, cz_ = 0;
+        int q = 0, t = 0;
+        bool ok = false;
+        if (i < m) {
+            // the chunk that holds output position i: the last one whose offset is <= i (empty chunks share an offset)
+            int lo = 0, hi = chunks; // s_off[lo] <= i < s_off[hi]
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (s_off[mid] <= i) lo = mid;
+                else hi = mid;
+            }
+            const PsDMatch mt = tmp[cStart[lo] + (i - s_off[lo])];
+            out[i] = mt;
+            q = mt.queryIdx;
+            t = mt.trainIdx;
+            if (REC) {
+                px = prev[3 * q]; py = prev[3 * q + 1]; pz = prev[3 * q + 2];
+                cx_ = cur[3 * t]; cy_ = cur[3 * t + 1]; cz_ = cur[3 * t + 2];
+                ok = depth_ok(px, py, pz) && depth_ok(cx_, cy_, cz_);
+            }
+        }
+        if (REC) {
+            int vtotal;
+            const int vpos = block_scan_flag<BLOCK>(ok, vtotal, s_wsum);
+            if (ok) {
+                um = fmaxf(um, write_records(pa, rec, p, vbase + vpos, i, q, t, px, py, pz, cx_, cy_, cz_, fixedBound));
+                cm = fmaxf(cm, fmaxf(fmaxf(fabsf(px), fabsf(py)), fmaxf(fabsf(pz), fmaxf(fabsf(cx_), fmaxf(fabsf(cy_), fabsf(cz_))))));
+            }
+            vbase += vtotal;
+        }
+    }
+    if (REC) {
+        const float cc = block_max<BLOCK>(cm, s_red);
+        const float uu = block_max<BLOCK>(um, s_red);
+        if (threadIdx.x == 0) {
+            mvalid[p] = vbase;
+            cmaxOut[p] = make_float2(cc, uu);
+            finish_pair_records(pa, rec, p, vbase); // (block_max ends with a barrier: the records are visible)
+        }
+        if (pa.zeroCounts)
+            for (int i = threadIdx.x; i < pa.zeroH; i += BLOCK) pa.zeroCounts[(size_t)p * pa.zeroStride + i] = 0;
+        if (threadIdx.x == 0 && pa.zeroSurvA) { // the staged scoring's survivor counters, as ps_crosscheck_prep does
+            pa.zeroSurvA[p] = 0;
+            pa.zeroSurvB[p] = 0;
+        }
+    }
+    if (threadIdx.x == 0) {
+        numMatches[p] = over ? -total : total;
+        if (numClamped) numClamped[p] = m;
+    }
+}
+
+} // namespace psdev

@@ -191,3 +191,92 @@ def dbscan_thin_device(ctx, xy, counts, octave=None, eps=10.0, min_pts=2, featur
     ctx.dbscan_thin_device(*args)
     cur.wait_stream(st)
     return kept, nkept
+
+
+class MapBatchDevice:
+    """A map-matching batch in HBM (PsMapBatch): the map views and frames (FrameSetDevice / PackedFrameSetDevice), their levels
+    (views x maxKpts / frames x maxKpts int32), pairs (P, 2) of (map view, frame), the sphere radius and accept ratio -- scalars, or
+    sequences of P for per-pair values -- and the output block with `max_matches` rows per pair."""
+
+    def __init__(self, maps, map_level, frames, cur_level, pairs, max_matches, radius=0.12, ratio=0.55, device=None):
+        self.device = torch.device(device) if device is not None else maps.device
+        self.maps, self.frames = maps, frames
+        map_level = np.ascontiguousarray(map_level, np.int32)
+        cur_level = np.ascontiguousarray(cur_level, np.int32)
+        assert map_level.shape == (maps.num_frames, maps.max_kpts) and cur_level.shape == (frames.num_frames, frames.max_kpts)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        self.P, self.cap = pairs.shape[0], int(max_matches)
+        self.map_level = torch.from_numpy(map_level).to(self.device)
+        self.cur_level = torch.from_numpy(cur_level).to(self.device)
+        self.pairs = torch.from_numpy(pairs).to(self.device)
+        self.radius_bound = self.accept_ratio = 0.0
+        self.radius_per = self.ratio_per = None
+        if np.ndim(radius) == 0:
+            self.radius_bound = api.map_sphere_bound(radius)
+        else:
+            assert len(radius) == self.P
+            self.radius_per = torch.from_numpy(np.array([api.map_sphere_bound(r) for r in radius], np.float32)).to(self.device)
+        if np.ndim(ratio) == 0:
+            self.accept_ratio = float(ratio)
+        else:
+            assert len(ratio) == self.P
+            self.ratio_per = torch.from_numpy(np.array(ratio, np.float64)).to(self.device)
+        P, cap = max(self.P, 1), self.cap
+        self.matches = torch.zeros((P, cap, 16), dtype=torch.uint8, device=self.device)
+        self.num_matches = torch.zeros(P, dtype=torch.int32, device=self.device)
+        self.mask = torch.zeros((P, cap), dtype=torch.uint8, device=self.device)
+        self.pose = torch.zeros((P, 16), dtype=torch.float32, device=self.device)
+        self.stats = torch.zeros((P, STATS_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()    # (the fills are done before a chain writes: PairBatchDevice)
+
+    def batch_view(self, lo=0, hi=None):
+        """PsMapBatch of pairs [lo, hi)."""
+        hi = self.P if hi is None else hi
+        return api.DeviceMapBatch(self.maps.view(), self.map_level.data_ptr(), self.frames.view(), self.cur_level.data_ptr(),
+                                  self.pairs[lo:].data_ptr() if lo < self.P else self.pairs.data_ptr(), hi - lo, self.cap,
+                                  self.radius_bound, self.accept_ratio,
+                                  self.radius_per[lo:].data_ptr() if self.radius_per is not None else None,
+                                  self.ratio_per[lo:].data_ptr() if self.ratio_per is not None else None)
+
+    def view(self, lo=0):
+        return api.DeviceResults(self.matches[lo:].data_ptr(), self.num_matches[lo:].data_ptr(), self.mask[lo:].data_ptr(),
+                                 self.pose[lo:].data_ptr(), self.stats[lo:].data_ptr())
+
+    def download(self):
+        torch.cuda.synchronize(self.device)
+        P = self.P
+        return dict(matches=self.matches.cpu().numpy().view(DMATCH_DTYPE).reshape(max(P, 1), self.cap)[:P],
+                    numMatches=self.num_matches.cpu().numpy()[:P],
+                    inlierMask=self.mask.cpu().numpy()[:P],
+                    pose=self.pose.cpu().numpy()[:P],
+                    stats=self.stats.cpu().numpy().view(STATS_DTYPE).reshape(-1)[:P])
+
+
+def _on_torch_stream(ctx, device, call, use_torch_stream):
+    if not use_torch_stream:
+        call()
+        return
+    cur = torch.cuda.current_stream(device)
+    if cur.cuda_stream != 0:
+        ctx.set_stream(cur.cuda_stream)
+        call()
+        return
+    st = _work_stream(device)
+    st.wait_stream(cur)
+    ctx.set_stream(st.cuda_stream)
+    call()
+    cur.wait_stream(st)
+
+
+def run_map_pairs(ctx, params, cfg, K, batch: MapBatchDevice, use_torch_stream=True):
+    """Asynchronous: guided map matching -> RANSAC -> refit for every pair of the batch (ps_map_pairs_device), ordered like
+    `run_pairs`: after the work already queued on torch's current stream, which waits for the results."""
+    _on_torch_stream(ctx, batch.device, lambda: ctx.map_pairs_device(params, cfg, K, batch.batch_view(), batch.view()),
+                     use_torch_stream)
+
+
+def run_match_xyz(ctx, batch: MapBatchDevice, use_torch_stream=True):
+    """Asynchronous: the guided matching alone (ps_match_xyz_device) into the batch's matches / num_matches."""
+    _on_torch_stream(ctx, batch.device,
+                     lambda: ctx.match_xyz_device(batch.batch_view(), batch.matches.data_ptr(), batch.num_matches.data_ptr()),
+                     use_torch_stream)
