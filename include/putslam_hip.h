@@ -263,6 +263,75 @@ int ps_dbscan_thin(PsContext *ctx, const float *xy, size_t xyStride, const int32
 int ps_dbscan_thin_device(PsContext *ctx, const float *xy, const int32_t *octave, const int32_t *counts, int frames,
                           int capacity, double eps, int minPts, int featuresFromCluster, int32_t *keptIdx, int32_t *nkept);
 
+/* ---- Spatial-exclusion filters: candidates that lie too close to features already held are rejected.  One rule type covers
+ * the three loops of the reference's front end; every predicate is decided as  squared sum < bound  with the bound found on
+ * the host (no device sqrt), and is false when a NaN is involved.
+ *   form3 = PS_EXCL_F32: float differences, float sum d0*d0 + (d1*d1 + d2*d2), (double)sum < bound3 -- Eigen's
+ *           (a - b).norm() < d on Vector3f with bound3 = ps_map_sphere_bound(d) (PUTSLAM.cpp:58-62,81-85);
+ *   form3 = PS_EXCL_F64: the doubles of the float differences, x*x + y*y + z*z summed left to right, sum < bound3
+ *           (matcher.cpp:905-908 with bound3 = ps_sqrt_bound_f64(d));
+ *   form2 = PS_EXCL_F64: (double)du*du + (double)dv*dv < bound2 with float du, dv -- cv::norm(p - q) < d with
+ *           bound2 = ps_sqrt_bound_f64(d) (matcher.cpp:114-116,910-912), (float)cv::norm(p - q) < d with
+ *           bound2 = ps_debug_dbscan_bound(d) (PUTSLAM.cpp:66-68,89-91);
+ *   PS_EXCL_NONE: that test is absent.  Two points are near iff either test passes.
+ *   mode PS_EXCL_GREEDY: candidates are walked in ascending index; one is accepted iff it passes the depth gate, no
+ *           existing feature is near it and no candidate accepted before is near it.
+ *   mode PS_EXCL_ALL_EARLIER: a candidate is kept iff it passes the depth gate, no existing feature is near it and NO
+ *           earlier candidate is near it, kept or not.
+ *   depthGate != 0: only candidates with (double)z > depthMin && (double)z < depthMax pass (PUTSLAM.cpp:117).
+ *   maxKeep >= 0: the result is cut after its first maxKeep members (PUTSLAM.cpp:113); < 0: no cap. */
+enum { PS_EXCL_NONE = 0, PS_EXCL_F32 = 1, PS_EXCL_F64 = 2 };
+enum { PS_EXCL_GREEDY = 0, PS_EXCL_ALL_EARLIER = 1 };
+typedef struct PsExclusionRule {
+    double bound3;
+    double bound2;
+    double depthMin, depthMax;
+    int32_t form3;     /* PS_EXCL_NONE / PS_EXCL_F32 / PS_EXCL_F64 */
+    int32_t form2;     /* PS_EXCL_NONE / PS_EXCL_F64 */
+    int32_t mode;      /* PS_EXCL_GREEDY / PS_EXCL_ALL_EARLIER */
+    int32_t maxKeep;
+    int32_t depthGate;
+    int32_t reserved;  /* 0 */
+} PsExclusionRule;
+size_t ps_abi_sizeof_exclusion_rule(void);
+
+/* The least double s with sqrt(s) >= d (the correctly rounded double root): sqrt(t) < d  <=>  t < s for every t >= 0.
+ * 0 for d <= 0 or NaN (nothing passes), +inf for d = +inf.  Pure host arithmetic. */
+double ps_sqrt_bound_f64(double d);
+
+/* Rule constructors, pure host arithmetic (no context, no device); PS_ERR_BAD_ARG for a NULL rule.
+ * new_map_features: PUTSLAM::chooseFeaturesToAddToMap + removeCloseFeatures, src/PUTSLAM/PUTSLAM.cpp:53-178 -- greedy, 3-D float
+ *   norm or 2-D float-rounded norm, depth gate (0.8, 6.0), cap maxOnceFeatureAdd (<= 0: nothing is accepted).  Both thresholds
+ *   pass through a float parameter there (:101) and are rounded to float here.  A caller that continues a count passes
+ *   maxOnceFeatureAdd - addedCounter.
+ * merge_tracked: Matcher::mergeTrackedFeatures, src/Matcher/matcher.cpp:97-130 -- greedy, 2-D double norm, no gate, no cap.
+ * too_close: Matcher::removeTooCloseFeatures, matcher.cpp:886-974 -- all-earlier, 3-D and 2-D double norms. */
+int ps_exclusion_rule_new_map_features(double minEuclideanDistanceOfFeatures, double minImageDistanceOfFeatures,
+                                       int maxOnceFeatureAdd, PsExclusionRule *rule);
+int ps_exclusion_rule_merge_tracked(double minimalReprojDistanceNewTrackingFeatures, PsExclusionRule *rule);
+int ps_exclusion_rule_too_close(double minimalEuclidDistanceNewTrackingFeatures, double minimalReprojDistanceNewTrackingFeatures,
+                                PsExclusionRule *rule);
+
+/* The filter.  cand3: n x 3 floats (feature3D), cand2: n x 2 floats (undistortedFeature2D); exist3 / exist2: the m features
+ * already held, the float casts of their position and (u, v) made by the caller (as with mapPos of ps_match_xyz).  A 3-D array
+ * may be NULL when the rule has neither a 3-D test nor a depth gate, a 2-D array when it has no 2-D test; the existing arrays
+ * also when m = 0.  keptIdx (room for n entries) receives the indices of the accepted candidates, ascending, *nkept their
+ * number.  Host pointers; synchronous on the context's stream.
+ * n <= PS_EXCL_MAX_CAND (per-candidate state lives in LDS), m <= PS_MAX_KPTS, else PS_ERR_UNSUPPORTED; a NULL where an array is
+ * needed, a negative count or a rule with an unknown form or mode -> PS_ERR_BAD_ARG (text: ps_last_error).  Outputs are not
+ * touched on an error. */
+#define PS_EXCL_MAX_CAND 8192
+int ps_exclude(PsContext *ctx, const PsExclusionRule *rule, const float *cand3, const float *cand2, int n, const float *exist3,
+               const float *exist2, int m, int32_t *keptIdx, int *nkept);
+/* The same over a DEVICE-resident batch of frames: cand3 frames x candCapacity x 3, cand2 frames x candCapacity x 2, candCounts
+ * frames int32; exist3 / exist2 / existCounts likewise with existCapacity (0: no existing set, the three may be NULL).
+ * keptIdx frames x candCapacity int32 (frame f's survivors at f x candCapacity), nkept frames int32: -1 for a frame one of whose
+ * counts lies outside 0 .. its capacity.  Asynchronous on the context's stream, copies nothing; the context's scratch holds
+ * 5 bytes per frame and candidate slot. */
+int ps_exclude_device(PsContext *ctx, const PsExclusionRule *rule, const float *cand3, const float *cand2,
+                      const int32_t *candCounts, int candCapacity, const float *exist3, const float *exist2,
+                      const int32_t *existCounts, int existCapacity, int frames, int32_t *keptIdx, int32_t *nkept);
+
 /* ---- N2: guided map matching, core of Matcher::matchXYZ, src/Matcher/matcher.cpp:606-746.
  * For every map feature j: candidates i among the current frame's keypoints with
  * |mapPos[j] - curPos[i]| < sphereRadius and |curLevel[i] - mapLevel[j]| <= 1 (:699-711); their value is

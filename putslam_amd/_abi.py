@@ -67,6 +67,18 @@ class PsMapBatch(C.Structure):
                 ("acceptRatio", C.c_double), ("radiusBoundPerPair", C.c_void_p), ("acceptRatioPerPair", C.c_void_p)]
 
 
+# PsExclusionRule forms and modes (include/putslam_hip.h)
+PS_EXCL_NONE, PS_EXCL_F32, PS_EXCL_F64 = 0, 1, 2
+PS_EXCL_GREEDY, PS_EXCL_ALL_EARLIER = 0, 1
+PS_EXCL_MAX_CAND = 8192
+
+
+class PsExclusionRule(C.Structure):
+    _fields_ = [("bound3", C.c_double), ("bound2", C.c_double), ("depthMin", C.c_double), ("depthMax", C.c_double),
+                ("form3", C.c_int32), ("form2", C.c_int32), ("mode", C.c_int32), ("maxKeep", C.c_int32),
+                ("depthGate", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

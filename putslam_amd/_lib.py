@@ -6,7 +6,7 @@ object is missing the import fails loudly and tells the caller how to build it.
 import ctypes as C
 import os
 
-from ._abi import PsDMatch, PsFrameSet, PsHostPairResults, PsMapBatch, PsPairResults, PsRansacConfig, PsRansacParams, PsRansacStats
+from ._abi import PsDMatch, PsExclusionRule, PsFrameSet, PsHostPairResults, PsMapBatch, PsPairResults, PsRansacConfig, PsRansacParams, PsRansacStats
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -37,6 +37,8 @@ EXPORTED = [
     "ps_abi_sizeof_dmatch", "ps_abi_sizeof_params", "ps_abi_sizeof_config", "ps_abi_sizeof_stats",
     "ps_abi_sizeof_frameset", "ps_abi_sizeof_results", "ps_abi_sizeof_host_results",
     "ps_map_sphere_bound", "ps_match_xyz_device", "ps_map_pairs_device", "ps_abi_sizeof_map_batch",
+    "ps_abi_sizeof_exclusion_rule", "ps_sqrt_bound_f64", "ps_exclusion_rule_new_map_features", "ps_exclusion_rule_merge_tracked",
+    "ps_exclusion_rule_too_close", "ps_exclude", "ps_exclude_device",
 ]
 
 _lib = None
@@ -176,6 +178,13 @@ def load_path(path):
     L.ps_match_xyz_device.argtypes = [vp, C.POINTER(PsMapBatch), vp, vp]
     L.ps_map_pairs_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsMapBatch),
                                       C.POINTER(PsPairResults)]
+    L.ps_sqrt_bound_f64.argtypes = [C.c_double]
+    L.ps_sqrt_bound_f64.restype = C.c_double
+    L.ps_exclusion_rule_new_map_features.argtypes = [C.c_double, C.c_double, i32, C.POINTER(PsExclusionRule)]
+    L.ps_exclusion_rule_merge_tracked.argtypes = [C.c_double, C.POINTER(PsExclusionRule)]
+    L.ps_exclusion_rule_too_close.argtypes = [C.c_double, C.c_double, C.POINTER(PsExclusionRule)]
+    L.ps_exclude.argtypes = [vp, C.POINTER(PsExclusionRule), vp, vp, i32, vp, vp, i32, vp, C.POINTER(i32)]
+    L.ps_exclude_device.argtypes = [vp, C.POINTER(PsExclusionRule), vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]
     L.ps_batch_queue_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.ps_batch_queue_destroy.argtypes = [vp]
     L.ps_batch_queue_destroy.restype = None
@@ -196,7 +205,7 @@ def load_path(path):
     L.ps_last_kernel_times_ms.argtypes = [vp, vp]
     L.ps_kernel_time_totals.argtypes = [vp, vp, vp]
     L.ps_context_enable_timing.argtypes = [vp, i32]
-    for n in ("dmatch", "params", "config", "stats", "frameset", "results", "host_results", "map_batch"):
+    for n in ("dmatch", "params", "config", "stats", "frameset", "results", "host_results", "map_batch", "exclusion_rule"):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -205,4 +214,5 @@ def load_path(path):
 def struct_sizes():
     return dict(dmatch=C.sizeof(PsDMatch), params=C.sizeof(PsRansacParams), config=C.sizeof(PsRansacConfig),
                 stats=C.sizeof(PsRansacStats), frameset=C.sizeof(PsFrameSet), results=C.sizeof(PsPairResults),
-                host_results=C.sizeof(PsHostPairResults), map_batch=C.sizeof(PsMapBatch))
+                host_results=C.sizeof(PsHostPairResults), map_batch=C.sizeof(PsMapBatch),
+                exclusion_rule=C.sizeof(PsExclusionRule))

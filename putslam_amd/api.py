@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_OK, PsFrameSet, PsHostPairResults, PsMapBatch, PsPairResults,  # noqa: F401
+from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_OK, PsExclusionRule, PsFrameSet, PsHostPairResults, PsMapBatch, PsPairResults,  # noqa: F401
                    PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
 
 
@@ -31,6 +31,35 @@ def dbscan_bound(eps):
 def map_sphere_bound(radius):
     """ps_map_sphere_bound: the least float B with  (float)|a - b| < radius  <=>  squared sum < B  (PsMapBatch.radiusBound)."""
     return float(_lib.load().ps_map_sphere_bound(float(radius)))
+
+
+def sqrt_bound_f64(d):
+    """ps_sqrt_bound_f64: the least double s with sqrt(s) >= d (sqrt(t) < d  <=>  t < s)."""
+    return float(_lib.load().ps_sqrt_bound_f64(float(d)))
+
+
+def _rule(rc, rule):
+    if rc != PS_OK:
+        raise PsError(rc, "exclusion rule constructor failed")
+    return rule
+
+
+def rule_new_map_features(min_euclid=0.03, min_image=2.0, max_add=200):
+    """PsExclusionRule of PUTSLAM::chooseFeaturesToAddToMap (PUTSLAM.cpp:98-178); the thresholds are rounded to float as there."""
+    r = PsExclusionRule()
+    return _rule(_lib.load().ps_exclusion_rule_new_map_features(float(min_euclid), float(min_image), int(max_add), C.byref(r)), r)
+
+
+def rule_merge_tracked(min_reproj):
+    """PsExclusionRule of Matcher::mergeTrackedFeatures (matcher.cpp:97-130)."""
+    r = PsExclusionRule()
+    return _rule(_lib.load().ps_exclusion_rule_merge_tracked(float(min_reproj), C.byref(r)), r)
+
+
+def rule_too_close(min_euclid, min_reproj):
+    """PsExclusionRule of Matcher::removeTooCloseFeatures (matcher.cpp:886-974)."""
+    r = PsExclusionRule()
+    return _rule(_lib.load().ps_exclusion_rule_too_close(float(min_euclid), float(min_reproj), C.byref(r)), r)
 
 
 def ladder_try(radius, ratio, k):
@@ -293,6 +322,47 @@ class Context:
         self._chk(self._L.ps_dbscan_thin_device(self._h, C.c_void_p(xy_ptr), C.c_void_p(octave_ptr or None),
                                                 C.c_void_p(counts_ptr), int(frames), int(capacity), float(eps), int(min_pts),
                                                 int(features_from_cluster), C.c_void_p(kept_ptr), C.c_void_p(nkept_ptr)))
+
+    # ---- spatial-exclusion filters (ps_exclusion.h) ----
+    def exclude(self, rule, cand3, cand2, exist3=None, exist2=None):
+        """ps_exclude: the indices, ascending int32, of the candidates `rule` (PsExclusionRule) accepts.  cand3 (n, 3) / cand2
+        (n, 2) float32, exist3 (m, 3) / exist2 (m, 2) float32 or None; an array the rule does not read may be None."""
+        def arr(a, w):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float32)
+            assert a.ndim == 2 and a.shape[1] == w
+            return a
+        cand3, cand2, exist3, exist2 = arr(cand3, 3), arr(cand2, 2), arr(exist3, 3), arr(exist2, 2)
+        n = (cand2 if cand2 is not None else cand3).shape[0]
+        m = 0 if exist3 is None and exist2 is None else (exist2 if exist2 is not None else exist3).shape[0]
+        assert all(a is None or a.shape[0] == n for a in (cand3, cand2)) and all(a is None or a.shape[0] == m for a in (exist3, exist2))
+        kept = np.zeros(max(n, 1), np.int32)
+        nk = C.c_int(0)
+        self._chk(self._L.ps_exclude(self._h, C.byref(rule), _p(cand3), _p(cand2), n, _p(exist3), _p(exist2), m, _p(kept),
+                                     C.byref(nk)))
+        return kept[:nk.value].copy()
+
+    def choose_new_features(self, feature3D, undistorted2D, map3D, map2D, min_euclid=0.03, min_image=2.0, max_add=200):
+        """PUTSLAM::chooseFeaturesToAddToMap (PUTSLAM.cpp:98-178) from addedCounter = 0: the indices of the features it adds.
+        map3D / map2D: the float casts of the visible map features' position and (u, v)."""
+        return self.exclude(rule_new_map_features(min_euclid, min_image, max_add), feature3D, undistorted2D, map3D, map2D)
+
+    def merge_tracked_features(self, undistorted2D, sandbox_undistorted2D, min_reproj):
+        """Matcher::mergeTrackedFeatures (matcher.cpp:97-130): the indices of the sandbox features that are appended."""
+        return self.exclude(rule_merge_tracked(min_reproj), None, sandbox_undistorted2D, None, undistorted2D)
+
+    def remove_too_close_features(self, features3D, undistorted2D, min_euclid, min_reproj):
+        """Matcher::removeTooCloseFeatures (matcher.cpp:886-974): the indices of the features that stay."""
+        return self.exclude(rule_too_close(min_euclid, min_reproj), features3D, undistorted2D)
+
+    def exclude_device(self, rule, cand3_ptr, cand2_ptr, cand_counts_ptr, cand_capacity, exist3_ptr, exist2_ptr, exist_counts_ptr,
+                       exist_capacity, frames, kept_ptr, nkept_ptr):
+        """ps_exclude_device on device pointers (asynchronous on the context's stream): device_batch.exclude_device."""
+        v = lambda p: C.c_void_p(p or None)   # noqa: E731
+        self._chk(self._L.ps_exclude_device(self._h, C.byref(rule), v(cand3_ptr), v(cand2_ptr), v(cand_counts_ptr), int(cand_capacity),
+                                            v(exist3_ptr), v(exist2_ptr), v(exist_counts_ptr), int(exist_capacity), int(frames),
+                                            v(kept_ptr), v(nkept_ptr)))
 
     def points3Dto2D(self, xyz, K):
         xyz = np.ascontiguousarray(xyz, np.float32)

@@ -20,6 +20,7 @@
 
 static_assert(sizeof(cv::DMatch) == sizeof(PsDMatch), "cv::DMatch layout");
 static_assert(sizeof(Eigen::Vector3f) == 12, "Eigen::Vector3f storage");
+static_assert(sizeof(cv::Point2f) == 8, "cv::Point2f storage");
 
 namespace {
 
@@ -240,6 +241,132 @@ void DBScan::run(std::vector<cv::KeyPoint> &clusteringSet)
         if (kept[j] != j) clusteringSet[j] = clusteringSet[kept[j]];
     clusteringSet.resize((size_t)nkept);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Spatial-exclusion filters (ps_exclude)
+namespace {
+// the accepted candidate indices under `rule`; false (and the text on stderr) if the call failed
+bool excludeCall(const PsExclusionRule &rule, const std::vector<Eigen::Vector3f> *cand3, const std::vector<cv::Point2f> &cand2,
+                 const std::vector<Eigen::Vector3f> *exist3, const std::vector<cv::Point2f> &exist2, std::vector<int32_t> &kept)
+{
+    kept.clear();
+    const size_t n = cand2.size(), m = exist2.size();
+    if (n == 0) return true;
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return false;
+    kept.resize(n);
+    int nkept = 0;
+    status = ps_exclude(ctx, &rule, cand3 ? reinterpret_cast<const float *>(cand3->data()) : nullptr,
+                        reinterpret_cast<const float *>(cand2.data()), (int)n,
+                        exist3 && m ? reinterpret_cast<const float *>(exist3->data()) : nullptr,
+                        m ? reinterpret_cast<const float *>(exist2.data()) : nullptr, (int)m, kept.data(), &nkept);
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        kept.clear();
+        return false;
+    }
+    kept.resize((size_t)nkept);
+    return true;
+}
+
+// v keeps the entries at the ascending positions stay[] (std::remove_if with a counting predicate, matcher.cpp:922-956)
+template <class T> void keepPositions(std::vector<T> &v, const std::vector<int32_t> &stay)
+{
+    for (size_t j = 0; j < stay.size(); ++j)
+        if ((size_t)stay[j] != j) v[j] = v[(size_t)stay[j]];
+    v.resize(stay.size());
+}
+} // namespace
+
+namespace putslam_hip {
+
+int chooseFeaturesToAddToMap(const std::vector<Eigen::Vector3f> &feature3D, const std::vector<cv::Point2f> &undistortedFeature2D,
+                             int addedCounter, int maxOnceFeatureAdd, const std::vector<Eigen::Vector3f> &mapFeaturePositions,
+                             const std::vector<cv::Point2f> &mapFeatureUV, float minEuclideanDistanceOfFeatures,
+                             float minImageDistanceOfFeatures, std::vector<int> &acceptedIndices)
+{
+    acceptedIndices.clear();
+    if (feature3D.size() != undistortedFeature2D.size() || mapFeaturePositions.size() != mapFeatureUV.size()) {
+        std::cerr << "putslam_hip: chooseFeaturesToAddToMap: list sizes differ" << std::endl; // (the reference asserts, :104-109)
+        return addedCounter;
+    }
+    if (addedCounter >= maxOnceFeatureAdd) return addedCounter; // :113
+    PsExclusionRule rule;
+    // (the difference is formed as long long: maxOnceFeatureAdd - addedCounter may not fit an int for a negative counter)
+    const long long room = (long long)maxOnceFeatureAdd - (long long)addedCounter;
+    ps_exclusion_rule_new_map_features((double)minEuclideanDistanceOfFeatures, (double)minImageDistanceOfFeatures,
+                                       room > 0x7fffffffLL ? 0x7fffffff : (int)room, &rule);
+    std::vector<int32_t> kept;
+    if (!excludeCall(rule, &feature3D, undistortedFeature2D, &mapFeaturePositions, mapFeatureUV, kept)) return addedCounter;
+    acceptedIndices.assign(kept.begin(), kept.end());
+    return addedCounter + (int)kept.size();
+}
+
+void FrameMatcher::mergeTrackedFeatures(std::vector<cv::Point2f> &undistortedFeatures2D,
+                                        const std::vector<cv::Point2f> &featuresSandBoxUndistorted,
+                                        std::vector<cv::Point2f> &distortedFeatures2D,
+                                        const std::vector<cv::Point2f> &featuresSandBoxDistorted,
+                                        std::vector<Eigen::Vector3f> &features3D, const std::vector<Eigen::Vector3f> &features3DSandBox,
+                                        std::vector<cv::KeyPoint> &keyPoints, const std::vector<cv::KeyPoint> &keyPointsSandBox,
+                                        std::vector<double> &detDists, const std::vector<double> &detDistsSandBox)
+{
+    PsExclusionRule rule;
+    ps_exclusion_rule_merge_tracked(matcherParameters.OpenCVParams.minimalReprojDistanceNewTrackingFeatures, &rule);
+    std::vector<int32_t> kept;
+    if (!excludeCall(rule, nullptr, featuresSandBoxUndistorted, nullptr, undistortedFeatures2D, kept)) return;
+    for (int32_t i : kept) { // :121-127
+        undistortedFeatures2D.push_back(featuresSandBoxUndistorted[(size_t)i]);
+        distortedFeatures2D.push_back(featuresSandBoxDistorted[(size_t)i]);
+        features3D.push_back(features3DSandBox[(size_t)i]);
+        keyPoints.push_back(keyPointsSandBox[(size_t)i]);
+        detDists.push_back(detDistsSandBox[(size_t)i]);
+    }
+}
+
+std::set<int> FrameMatcher::removeTooCloseFeatures(std::vector<cv::Point2f> &distortedFeatures2D,
+                                                   std::vector<cv::Point2f> &undistortedFeatures2D,
+                                                   std::vector<Eigen::Vector3f> &features3D, std::vector<cv::KeyPoint> &keyPoints,
+                                                   std::vector<double> &detDists, std::vector<cv::DMatch> &matches)
+{
+    std::set<int> featuresToRemove;
+    if (undistortedFeatures2D.size() != features3D.size()) { // (the reference asserts, :895-898)
+        std::cerr << "putslam_hip: removeTooCloseFeatures: list sizes differ" << std::endl;
+        return featuresToRemove;
+    }
+    PsExclusionRule rule;
+    ps_exclusion_rule_too_close(matcherParameters.OpenCVParams.minimalEuclidDistanceNewTrackingFeatures,
+                                matcherParameters.OpenCVParams.minimalReprojDistanceNewTrackingFeatures, &rule);
+    std::vector<int32_t> stay;
+    const std::vector<cv::Point2f> none;
+    if (!excludeCall(rule, &features3D, undistortedFeatures2D, nullptr, none, stay)) return featuresToRemove;
+    const int n = (int)features3D.size();
+    for (int i = 0, j = 0; i < n; ++i) {
+        if (j < (int)stay.size() && stay[(size_t)j] == i)
+            ++j;
+        else
+            featuresToRemove.insert(i);
+    }
+    // each list loses the positions in featuresToRemove that it has (:921-956: the counting predicate runs over the list's own length)
+    auto erase = [&](auto &v) {
+        std::vector<int32_t> s;
+        for (int32_t i : stay)
+            if ((size_t)i < v.size()) s.push_back(i);
+        for (size_t i = (size_t)n; i < v.size(); ++i) s.push_back((int32_t)i);
+        keepPositions(v, s);
+    };
+    erase(distortedFeatures2D);
+    erase(undistortedFeatures2D);
+    erase(features3D);
+    erase(keyPoints);
+    erase(detDists);
+    matches.erase(std::remove_if(matches.begin(), matches.end(),
+                                 [&](const cv::DMatch &o) { return featuresToRemove.find(o.trainIdx) != featuresToRemove.end(); }),
+                  matches.end()); // :960-963
+    return featuresToRemove;
+}
+
+} // namespace putslam_hip
 
 std::vector<cv::Point2f> RGBD::removeImageDistortion(std::vector<cv::Point2f> &features, cv::Mat cameraMatrix, cv::Mat distCoeffs)
 {

@@ -192,6 +192,8 @@ class FrameMatcher {
         struct {
             double matchingXYZSphereRadius = 0.12;            // putslammatcherOpenCVParameters.xml:71
             double matchingXYZacceptRatioOfBestMatch = 0.55;  // :72
+            double minimalReprojDistanceNewTrackingFeatures = 3;     // :68
+            double minimalEuclidDistanceNewTrackingFeatures = 0.01;  // :69
         } OpenCVParams;
         MatcherParameters();
     };
@@ -255,6 +257,21 @@ class FrameMatcher {
                           std::vector<Eigen::Vector3f> &currentPoseFeatures3D, const std::vector<int> &currentPoseOctaves,
                           const std::vector<double> &currentPoseDetDists, Eigen::Matrix4f &estimatedTransformation,
                           std::vector<cv::DMatch> &inlierMatches, int maxTries = 10, double minRatio = 0.1, int *tryUsed = nullptr);
+    // Matcher::mergeTrackedFeatures (matcher.cpp:97-130): a sandbox feature is appended to the five lists unless an existing
+    // feature, or a sandbox feature appended before it, lies closer in the undistorted image than
+    // OpenCVParams.minimalReprojDistanceNewTrackingFeatures (ps_exclude with ps_exclusion_rule_merge_tracked).
+    void mergeTrackedFeatures(std::vector<cv::Point2f> &undistortedFeatures2D, const std::vector<cv::Point2f> &featuresSandBoxUndistorted,
+                              std::vector<cv::Point2f> &distortedFeatures2D, const std::vector<cv::Point2f> &featuresSandBoxDistorted,
+                              std::vector<Eigen::Vector3f> &features3D, const std::vector<Eigen::Vector3f> &features3DSandBox,
+                              std::vector<cv::KeyPoint> &keyPoints, const std::vector<cv::KeyPoint> &keyPointsSandBox,
+                              std::vector<double> &detDists, const std::vector<double> &detDistsSandBox);
+    // Matcher::removeTooCloseFeatures (matcher.cpp:886-974): feature j goes iff some earlier feature lies closer than
+    // minimalEuclidDistanceNewTrackingFeatures in space or minimalReprojDistanceNewTrackingFeatures in the undistorted image
+    // (ps_exclusion_rule_too_close).  The five lists lose those entries; `matches` loses the matches whose trainIdx was removed
+    // and is NOT renumbered (:960-963).  Returns featuresToRemove.
+    std::set<int> removeTooCloseFeatures(std::vector<cv::Point2f> &distortedFeatures2D, std::vector<cv::Point2f> &undistortedFeatures2D,
+                                         std::vector<Eigen::Vector3f> &features3D, std::vector<cv::KeyPoint> &keyPoints,
+                                         std::vector<double> &detDists, std::vector<cv::DMatch> &matches);
     // ---- pipelined form of runVO (ps_vo_stream_push_async / ps_vo_stream_pop, include/putslam_hip.h): the same call shape --
     // one frame per call, the previous frame kept as state (matcher.cpp:452-516) -- with the result returned with a LAG, so that
     // uploads, kernels and downloads of consecutive frames overlap (BASELINE configs[2]: a sequence streamed through the matcher).
@@ -314,6 +331,16 @@ class FrameMatcher {
                         Eigen::Matrix4f &estimatedTransformation, std::vector<cv::DMatch> &inlierMatches,
                         double &pointInlierRatio);
 };
+
+// PUTSLAM::chooseFeaturesToAddToMap (src/PUTSLAM/PUTSLAM.cpp:98-178) on the positions it reads: feature3D / undistortedFeature2D of
+// the frame's featureSet, and of every visible map feature the float casts of position and (u, v) (:58-60,66;
+// putslam_matcher_glue.h makes them from std::vector<MapFeature>).  Starts from `addedCounter` and returns the new one, as the
+// reference does; acceptedIndices receives the indices j it accepted, in order.  Building the RGBDFeature of each (descriptor row,
+// ExtendedDescriptor, :138-170) stays with the caller.  On an error nothing is accepted (the text goes to stderr).
+int chooseFeaturesToAddToMap(const std::vector<Eigen::Vector3f> &feature3D, const std::vector<cv::Point2f> &undistortedFeature2D,
+                             int addedCounter, int maxOnceFeatureAdd, const std::vector<Eigen::Vector3f> &mapFeaturePositions,
+                             const std::vector<cv::Point2f> &mapFeatureUV, float minEuclideanDistanceOfFeatures,
+                             float minImageDistanceOfFeatures, std::vector<int> &acceptedIndices);
 
 // MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) as a free function over the calling thread's context.
 std::vector<cv::DMatch> hammingCrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors);

@@ -144,4 +144,24 @@ double matchXYZ(FrameMatcher &hot, std::vector<MapFeatureT> mapFeatures, int sen
     return ratio;
 }
 
+// PUTSLAM::chooseFeaturesToAddToMap (PUTSLAM.cpp:98-178) with the reference's arguments: `features` is the Matcher::featureSet
+// (feature3D, undistortedFeature2D), mapFeatures the visible map features (position, u, v).  The accepted indices come back in
+// acceptedIndices instead of mapFeaturesToAdd: the caller builds the RGBDFeature of each (descriptor row, ExtendedDescriptor,
+// :138-170), which needs cv::Mat rows and its own types.  Returns the new addedCounter.
+template <class FeatureSetT, class MapFeatureT>
+int chooseFeaturesToAddToMap(const FeatureSetT &features, int addedCounter, int maxOnceFeatureAdd,
+                             const std::vector<MapFeatureT> &mapFeatures, float minEuclideanDistanceOfFeatures,
+                             float minImageDistanceOfFeatures, std::vector<int> &acceptedIndices)
+{
+    std::vector<Eigen::Vector3f> pos(mapFeatures.size());
+    std::vector<cv::Point2f> uv(mapFeatures.size());
+    for (size_t k = 0; k < mapFeatures.size(); ++k) { // the casts of removeCloseFeatures, :81-83,89
+        pos[k] = Eigen::Vector3f((float)mapFeatures[k].position.x(), (float)mapFeatures[k].position.y(),
+                                 (float)mapFeatures[k].position.z());
+        uv[k] = cv::Point2f((float)mapFeatures[k].u, (float)mapFeatures[k].v);
+    }
+    return chooseFeaturesToAddToMap(features.feature3D, features.undistortedFeature2D, addedCounter, maxOnceFeatureAdd, pos, uv,
+                                    minEuclideanDistanceOfFeatures, minImageDistanceOfFeatures, acceptedIndices);
+}
+
 } // namespace putslam_hip

@@ -51,6 +51,7 @@ struct PsContext {
     Buf tabR, tabU;
     // staging for the host-pointer entry points (device)
     Buf sDesc, sNk, sMatches, sNumM, sMask, sPose, sStats, sMisc0, sMisc1, sMisc2;
+    Buf exFlag, exPar; // exclusion filters (ps_exclusion.h): per frame and candidate slot, the sweep's flag and the union-find's parent
     // cached stop tables
     int tabEstimator = -1, tabH = -1, tabRN = 0, tabUN = 0, tabIter0 = 0;
     double tabMinRatio = -1.0;

@@ -193,6 +193,40 @@ def dbscan_thin_device(ctx, xy, counts, octave=None, eps=10.0, min_pts=2, featur
     return kept, nkept
 
 
+def exclude_device(ctx, rule, cand3, cand2, cand_counts, exist3=None, exist2=None, exist_counts=None):
+    """The exclusion filter `rule` (api.rule_*) over a device-resident batch (ps_exclude_device): cand3 (F, cap, 3) / cand2
+    (F, cap, 2) float32, cand_counts (F,) int32; exist3 (F, ecap, 3) / exist2 (F, ecap, 2) / exist_counts (F,) or None -- torch
+    tensors on the context's device; an array the rule does not read may be None.  Returns (kept (F, cap) int32, nkept (F,)
+    int32), device tensors written asynchronously on the context's stream: frame f keeps kept[f, :nkept[f]] (ascending)."""
+    lead = cand2 if cand2 is not None else cand3
+    F, cap = lead.shape[0], lead.shape[1]
+    for t, w in ((cand3, 3), (cand2, 2)):
+        assert t is None or (t.dtype == torch.float32 and t.shape == (F, cap, w) and t.is_contiguous())
+    assert cand_counts.dtype == torch.int32 and cand_counts.shape == (F,) and cand_counts.is_contiguous()
+    elead = exist2 if exist2 is not None else exist3
+    ecap = 0 if elead is None else elead.shape[1]
+    if ecap:
+        for t, w in ((exist3, 3), (exist2, 2)):
+            assert t is None or (t.dtype == torch.float32 and t.shape == (F, ecap, w) and t.is_contiguous())
+        assert exist_counts.dtype == torch.int32 and exist_counts.shape == (F,) and exist_counts.is_contiguous()
+    kept = torch.empty((F, cap), dtype=torch.int32, device=lead.device)
+    nkept = torch.empty((F,), dtype=torch.int32, device=lead.device)
+    ptr = lambda t: t.data_ptr() if t is not None else 0   # noqa: E731
+    args = (rule, ptr(cand3), ptr(cand2), cand_counts.data_ptr(), cap, ptr(exist3) if ecap else 0, ptr(exist2) if ecap else 0,
+            exist_counts.data_ptr() if ecap else 0, ecap, F, kept.data_ptr(), nkept.data_ptr())
+    cur = torch.cuda.current_stream(lead.device)   # ordered like dbscan_thin_device
+    if cur.cuda_stream != 0:
+        ctx.set_stream(cur.cuda_stream)
+        ctx.exclude_device(*args)
+        return kept, nkept
+    st = _work_stream(lead.device)
+    st.wait_stream(cur)
+    ctx.set_stream(st.cuda_stream)
+    ctx.exclude_device(*args)
+    cur.wait_stream(st)
+    return kept, nkept
+
+
 class MapBatchDevice:
     """A map-matching batch in HBM (PsMapBatch): the map views and frames (FrameSetDevice / PackedFrameSetDevice), their levels
     (views x maxKpts / frames x maxKpts int32), pairs (P, 2) of (map view, frame), the sphere radius and accept ratio -- scalars, or
