@@ -438,6 +438,108 @@ int ps_match_xyz_device(PsContext *ctx, const PsMapBatch *b, PsDMatch *matches, 
 int ps_map_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
                         const PsMapBatch *b, const PsPairResults *out);
 
+/* ---- Map views built on the device from a RESIDENT feature map: what a host does per frame and per visible map feature before
+ * matchXYZ -- FeaturesMap::findNearestFrame (src/Map/featuresMap.cpp:528-563), PUTSLAM::removeMapFeaturesWithoutGoodObservationAngle
+ * (src/PUTSLAM/PUTSLAM.cpp:932-950), moveMapFeaturesToLocalCordinateSystem (PUTSLAM.cpp:28-51), the predicted level of
+ * matcher.cpp:681-692 and the copy of the chosen descriptor (:675-679) -- for V views in one launch chain.  The output IS a
+ * PsFrameSet + mapLevel, what PsMapBatch::maps / mapLevel read.
+ *
+ * The level without a device log: clamp(ceil(log(x) / log 1.2), 0, 7) is an integer decision in one monotone variable.
+ * ps_level_thresholds: t[k], k = 0 .. 6, the least double with ceil(log(x) / log(1.2)) > k, found by bisection over bit patterns
+ * with the host's libm evaluated exactly as ps_predicted_level evaluates it; the predicate is then checked to be clean -- true
+ * from t[k] on, false below -- for every double within 4096 ulps of each t[k]: PS_ERR_UNSUPPORTED if it is not (a libm that is
+ * not locally monotone: nothing is guessed).  Pure host arithmetic, no context.
+ * THE LEVEL RULE of the two device calls below:  x = (T[octave] * detDist) / curDist  in double, left to right, with
+ * T[o] = pow(1.2, o) from a host-filled table for o = PS_LEVEL_OCTAVE_MIN .. PS_LEVEL_OCTAVE_MAX; level = #{k : x >= t[k]} if x
+ * is finite, else 0 -- what ps_predicted_level returns, NaN, +-inf, 0 and negative x included.  An octave outside the table never
+ * gives a silent level: it invalidates the view (ps_map_views_device) or writes -1 (ps_frame_levels_device). */
+#define PS_LEVEL_OCTAVE_MIN (-16)
+#define PS_LEVEL_OCTAVE_MAX 47
+int ps_level_thresholds(double t[7]);
+
+/* The angle table of featuresMap.cpp:534-556 for one current pose: featureGlob there has an identity rotation, so
+ * featureGlob.inverse() * camPose has camPose's rotation and the "view vector" is the pose's third rotation column whatever the
+ * feature -- the angle depends on the pair (historical pose, current pose) only.  curPose16 / poses16: column-major 4x4 doubles
+ * (Mat34 storage).  For pose q: a = float casts of the current pose's elements (0,2), (1,2), (2,2), b = those of pose q;
+ * float dot = a0*b0 + (a1*b1 + a2*b2) and the two float norms in the same order (Eigen's Vector3f reductions as DESIGN.md 8.2
+ * reads them) with a correctly rounded sqrtf; r = dot / (nb * na) in float; angle[q] = fabs(acos((double)r)) -- the DOUBLE acos
+ * (whether the reference's unqualified acos on a float picks the float overload depends on its headers: DESIGN.md 8.4; the table
+ * is an INPUT of ps_map_views_device, a host with the real build can supply its own).  Pure host arithmetic (libm). */
+int ps_view_angles(const double *curPose16, const double *poses16, int numPoses, double *angle);
+
+typedef struct PsMapStore {       /* DEVICE pointers: what FeaturesMap's front-end map holds */
+    const double  *pos;           /* F x 3, MapFeature::position, global frame */
+    const int32_t *obsStart;      /* F + 1: feature f's observations, ascending poseId
+                                     (the order of std::map<poseId, ExtendedDescriptor>) */
+    const int32_t *obsPose;       /* O, 0 .. numPoses-1 */
+    const uint8_t *obsDesc;       /* O x 32, 16-byte aligned */
+    const int32_t *obsOctave;     /* O */
+    const double  *obsDetDist;    /* O */
+    int32_t numFeatures, numObs, numPoses, reserved;
+} PsMapStore;
+
+enum { PS_VIEW_REQUIRE_VISIBLE = 1 };
+typedef struct PsMapViewRequest { /* pointers: DEVICE */
+    const double *camInv;         /* V x 16 column-major: cameraPose.inverse().matrix() (the caller inverts) */
+    const double *poseAngle;      /* V x numPoses: ps_view_angles of each view's pose */
+    const int32_t *cand;          /* V x candCapacity feature indices (the std::set order of getCovisibleFeatures), or NULL =
+                                     every feature of the store in index order */
+    const int32_t *candCounts;    /* V, 0 .. candCapacity (read only when cand is given) */
+    double maxAngle;
+    double fx, fy, cx, cy, imageW, imageH;   /* DepthSensorModel's focalLength / focalAxis / imageSize */
+    int32_t V, candCapacity;
+    int32_t flags;                /* PS_VIEW_REQUIRE_VISIBLE */
+    int32_t reserved;
+} PsMapViewRequest;
+
+typedef struct PsMapViewOut {     /* pointers: DEVICE, written by the call */
+    PsFrameSet views;             /* desc / pts / nkpts as a PsFrameSet of numFrames >= V views (dense or ABI 2 strides),
+                                     maxKpts <= PS_MAX_KPTS: drops into PsMapBatch::maps */
+    int32_t *mapLevel;            /* numFrames x maxKpts: PsMapBatch::mapLevel */
+    int32_t *viewCount;           /* V, see below */
+    /* side arrays for the host, each V x maxKpts rows or NULL: */
+    int32_t *featIdx;             /* the feature */
+    int32_t *obsIdx;              /* the chosen observation (index into the store's obs arrays) */
+    double *posCam;               /* x 3: position in the camera frame */
+    double *uv;                   /* x 2: MapFeature::u / v (-1, -1 when not visible) */
+    double *angle;                /* angles[] of findNearestFrame */
+} PsMapViewOut;
+size_t ps_abi_sizeof_map_store(void);
+size_t ps_abi_sizeof_map_view_request(void);
+size_t ps_abi_sizeof_map_view_out(void);
+
+/* For view v and candidate f, in candidate order:
+ *  1. observation choice (featuresMap.cpp:537-561): f's observations are walked in order, the first with angle < best is kept
+ *     (strict; best starts at 10; a NaN angle is never chosen); f is dropped if none is chosen or if the chosen angle is
+ *     > maxAngle (equality keeps it);
+ *  2. camera-frame position (PUTSLAM.cpp:35-40), M = camInv of v: p_i = ((M(i,0)*x + M(i,1)*y) + M(i,2)*z) + M(i,3) in double,
+ *     every product and sum rounded (Eigen's fixed 4x4 product in a build without FMA);
+ *  3. projection (depthSensorModel.cpp:18-25): u = ((fx*p0)/p2) + cx, v = ((fy*p1)/p2) + cy, both -1 if
+ *     u<0 || u>imageW || v<0 || v>imageH || p2<0.8 || p2>6.0 (NaNs fall through); with PS_VIEW_REQUIRE_VISIBLE a feature whose
+ *     u == -1 is dropped (featuresMap.cpp:471-474 without the lifeValue bookkeeping, which stays with the host);
+ *  4. level (matcher.cpp:681-692): curDist = sqrt((p0*p0 + p1*p1) + p2*p2) in double, then the level rule with the chosen
+ *     observation's octave and detDist;
+ *  5. the next row of view v receives pts = float casts of p (:700-701), desc = the chosen observation's 32 bytes, mapLevel, and
+ *     the side arrays.
+ * views.nkpts[v] = viewCount[v] = the count.  If it exceeds maxKpts: viewCount[v] = -(count), nkpts[v] = 0, the rows need not be
+ * meaningful, other views are unaffected (the rule of numMatches above; call again with that capacity).  viewCount[v] = INT32_MIN,
+ * nkpts[v] = 0 for a view with a candidate count outside 0 .. candCapacity, a candidate index outside the store, a pose id
+ * outside 0 .. numPoses-1 among a candidate's observations, an obsStart range that is not ascending inside 0 .. numObs, or an
+ * EMITTED feature whose chosen observation's octave lies outside the table.  Rows beyond the count are not written.
+ * Asynchronous on the context's stream, copies nothing and does not synchronise (growing scratch on a first call aside: 36 bytes
+ * per view and 256 candidate slots).  NULL where an array is needed, a negative count, views.numFrames < V, maxKpts < 1, bad
+ * strides -> PS_ERR_BAD_ARG (text: ps_last_error); maxKpts > PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; outputs untouched.  V == 0 is
+ * PS_OK.  Out of scope: incremental updates of the store (it is replaced whole), the covisibility walk, lifeValue, the inverse. */
+int ps_map_views_device(PsContext *ctx, const PsMapStore *store, const PsMapViewRequest *req, const PsMapViewOut *out);
+
+/* The frame side, matcher.cpp:639-652: curLevel[f][i] for the keypoints of a device-resident frame set.  octave / detDist /
+ * curLevel: numFrames x maxKpts (rows beyond nkpts[f] are not written).  curDist = (double)sqrtf(p0*p0 + (p1*p1 + p2*p2)) in
+ * float (Vector3f::norm), then the level rule.  An octave outside the table writes -1, never a level: the caller checks for it
+ * (ps_match_xyz's test |curLevel - mapLevel| <= 1 fails for such a keypoint against map levels 1 .. 7, but NOT against map
+ * level 0 -- a -1 must not reach the matcher unexamined).  Asynchronous, no scratch. */
+int ps_frame_levels_device(PsContext *ctx, const PsFrameSet *frames, const int32_t *octave, const double *detDist,
+                           int32_t *curLevel);
+
 /* ---- A2, for a host that loops over batches (the loop of src/PUTSLAM/PUTSLAM.cpp:677-740 around Matcher::match,
  * src/Matcher/matcher.cpp:470-515): ps_vo_pairs_device through launch chains that are never joined.
  * One context is one launch chain: a batch's matrix-core Hamming sweep, then its vector scoring stages, dependent launches with

@@ -79,6 +79,30 @@ class PsExclusionRule(C.Structure):
                 ("depthGate", C.c_int32), ("reserved", C.c_int32)]
 
 
+# ps_map_views_device (include/putslam_hip.h): the resident feature map, the request and the output block
+PS_VIEW_REQUIRE_VISIBLE = 1
+PS_LEVEL_OCTAVE_MIN, PS_LEVEL_OCTAVE_MAX = -16, 47
+PS_VIEW_INVALID = -2 ** 31      # viewCount of a view with a bad count, index, pose id or octave
+
+
+class PsMapStore(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("obsStart", C.c_void_p), ("obsPose", C.c_void_p), ("obsDesc", C.c_void_p),
+                ("obsOctave", C.c_void_p), ("obsDetDist", C.c_void_p),
+                ("numFeatures", C.c_int32), ("numObs", C.c_int32), ("numPoses", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PsMapViewRequest(C.Structure):
+    _fields_ = [("camInv", C.c_void_p), ("poseAngle", C.c_void_p), ("cand", C.c_void_p), ("candCounts", C.c_void_p),
+                ("maxAngle", C.c_double), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("imageW", C.c_double), ("imageH", C.c_double),
+                ("V", C.c_int32), ("candCapacity", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PsMapViewOut(C.Structure):
+    _fields_ = [("views", PsFrameSet), ("mapLevel", C.c_void_p), ("viewCount", C.c_void_p), ("featIdx", C.c_void_p),
+                ("obsIdx", C.c_void_p), ("posCam", C.c_void_p), ("uv", C.c_void_p), ("angle", C.c_void_p)]
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

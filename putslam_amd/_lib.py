@@ -6,7 +6,8 @@ object is missing the import fails loudly and tells the caller how to build it.
 import ctypes as C
 import os
 
-from ._abi import PsDMatch, PsExclusionRule, PsFrameSet, PsHostPairResults, PsMapBatch, PsPairResults, PsRansacConfig, PsRansacParams, PsRansacStats
+from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsHostPairResults, PsMapBatch, PsMapStore, PsMapViewOut, PsMapViewRequest,
+                   PsPairResults, PsRansacConfig, PsRansacParams, PsRansacStats)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -39,6 +40,8 @@ EXPORTED = [
     "ps_map_sphere_bound", "ps_match_xyz_device", "ps_map_pairs_device", "ps_abi_sizeof_map_batch",
     "ps_abi_sizeof_exclusion_rule", "ps_sqrt_bound_f64", "ps_exclusion_rule_new_map_features", "ps_exclusion_rule_merge_tracked",
     "ps_exclusion_rule_too_close", "ps_exclude", "ps_exclude_device",
+    "ps_level_thresholds", "ps_view_angles", "ps_map_views_device", "ps_frame_levels_device",
+    "ps_abi_sizeof_map_store", "ps_abi_sizeof_map_view_request", "ps_abi_sizeof_map_view_out",
 ]
 
 _lib = None
@@ -185,6 +188,10 @@ def load_path(path):
     L.ps_exclusion_rule_too_close.argtypes = [C.c_double, C.c_double, C.POINTER(PsExclusionRule)]
     L.ps_exclude.argtypes = [vp, C.POINTER(PsExclusionRule), vp, vp, i32, vp, vp, i32, vp, C.POINTER(i32)]
     L.ps_exclude_device.argtypes = [vp, C.POINTER(PsExclusionRule), vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]
+    L.ps_level_thresholds.argtypes = [C.POINTER(C.c_double)]
+    L.ps_view_angles.argtypes = [vp, vp, i32, vp]
+    L.ps_map_views_device.argtypes = [vp, C.POINTER(PsMapStore), C.POINTER(PsMapViewRequest), C.POINTER(PsMapViewOut)]
+    L.ps_frame_levels_device.argtypes = [vp, C.POINTER(PsFrameSet), vp, vp, vp]
     L.ps_batch_queue_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.ps_batch_queue_destroy.argtypes = [vp]
     L.ps_batch_queue_destroy.restype = None
@@ -205,7 +212,8 @@ def load_path(path):
     L.ps_last_kernel_times_ms.argtypes = [vp, vp]
     L.ps_kernel_time_totals.argtypes = [vp, vp, vp]
     L.ps_context_enable_timing.argtypes = [vp, i32]
-    for n in ("dmatch", "params", "config", "stats", "frameset", "results", "host_results", "map_batch", "exclusion_rule"):
+    for n in ("dmatch", "params", "config", "stats", "frameset", "results", "host_results", "map_batch", "exclusion_rule",
+              "map_store", "map_view_request", "map_view_out"):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -215,4 +223,5 @@ def struct_sizes():
     return dict(dmatch=C.sizeof(PsDMatch), params=C.sizeof(PsRansacParams), config=C.sizeof(PsRansacConfig),
                 stats=C.sizeof(PsRansacStats), frameset=C.sizeof(PsFrameSet), results=C.sizeof(PsPairResults),
                 host_results=C.sizeof(PsHostPairResults), map_batch=C.sizeof(PsMapBatch),
-                exclusion_rule=C.sizeof(PsExclusionRule))
+                exclusion_rule=C.sizeof(PsExclusionRule), map_store=C.sizeof(PsMapStore),
+                map_view_request=C.sizeof(PsMapViewRequest), map_view_out=C.sizeof(PsMapViewOut))

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_OK, PsExclusionRule, PsFrameSet, PsHostPairResults, PsMapBatch, PsPairResults,  # noqa: F401
-                   PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
+                   PsMapStore, PsMapViewOut, PsMapViewRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
 
 
 class PsError(RuntimeError):
@@ -60,6 +60,28 @@ def rule_too_close(min_euclid, min_reproj):
     """PsExclusionRule of Matcher::removeTooCloseFeatures (matcher.cpp:886-974)."""
     r = PsExclusionRule()
     return _rule(_lib.load().ps_exclusion_rule_too_close(float(min_euclid), float(min_reproj), C.byref(r)), r)
+
+
+def level_thresholds():
+    """ps_level_thresholds: t[k], k = 0 .. 6, the least double x with ceil(log(x) / log(1.2)) > k under the host's libm; the
+    predicted level of x is the number of t[k] it reaches (finite x).  Raises if the host's log is not clean around one of them."""
+    t = (C.c_double * 7)()
+    rc = _lib.load().ps_level_thresholds(t)
+    if rc != PS_OK:
+        raise PsError(rc, "ps_level_thresholds: the host's libm is not monotone around a switching point")
+    return np.array(t[:], np.float64)
+
+
+def view_angles(cur_pose, poses):
+    """ps_view_angles: the angle table of FeaturesMap::findNearestFrame (featuresMap.cpp:534-556) for one current pose.
+    cur_pose (4, 4), poses (N, 4, 4): matrices in the usual row / column indexing (stored column-major for the call)."""
+    cur = np.ascontiguousarray(np.asarray(cur_pose, np.float64).reshape(4, 4).T)
+    ps = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1))
+    out = np.zeros(ps.shape[0], np.float64)
+    rc = _lib.load().ps_view_angles(_p(cur), _p(ps), ps.shape[0], _p(out))
+    if rc != PS_OK:
+        raise PsError(rc, "ps_view_angles failed")
+    return out
 
 
 def ladder_try(radius, ratio, k):
@@ -397,6 +419,18 @@ class Context:
 
     def predicted_level(self, octave, det_dist, cur_dist):
         return self._L.ps_predicted_level(int(octave), float(det_dist), float(cur_dist))
+
+    # ---- map views from a resident feature map ----
+    def map_views_device(self, store: PsMapStore, request: PsMapViewRequest, out: PsMapViewOut):
+        """ps_map_views_device on filled structs of device pointers (asynchronous): device_batch.build_map_views."""
+        self._chk(self._L.ps_map_views_device(self._h, C.byref(store), C.byref(request), C.byref(out)))
+
+    def frame_levels_device(self, frames: "DeviceFrames", octave_ptr, det_dist_ptr, cur_level_ptr):
+        """ps_frame_levels_device: predicted levels of the keypoints of a device-resident frame set (asynchronous)."""
+        fs = PsFrameSet(frames.desc_ptr, frames.pts_ptr, frames.nkpts_ptr, frames.num_frames, frames.max_kpts,
+                        frames.desc_stride, frames.pts_stride)
+        v = lambda p: C.c_void_p(p or None)   # noqa: E731
+        self._chk(self._L.ps_frame_levels_device(self._h, C.byref(fs), v(octave_ptr), v(det_dist_ptr), v(cur_level_ptr)))
 
     # ---- A2 / A12: device-resident batch ----
     def vo_pairs_device(self, params, cfg, K, frames: "DeviceFrames", pairs_dev_ptr, P, out: "DeviceResults"):

@@ -259,7 +259,7 @@ void ps_context_destroy(PsContext *ctx)
     Buf *all[] = {&ctx->keys, &ctx->recA, &ctx->recB, &ctx->recC, &ctx->recD, &ctx->recE, &ctx->recF, &ctx->recShadow, &ctx->models, &ctx->survA, &ctx->survB, &ctx->survN, &ctx->recF2, &ctx->permBuf, &ctx->prefInfo, &ctx->frontRec, &ctx->validMask, &ctx->stamps, &ctx->dbgCnt, &ctx->bailCnt, &ctx->counts, &ctx->mvalid,
                   &ctx->cmax, &ctx->idxList, &ctx->raw, &ctx->xq, &ctx->tabR, &ctx->tabU, &ctx->sDesc, &ctx->sNk,
                   &ctx->sMatches, &ctx->sNumM, &ctx->sMask, &ctx->sPose, &ctx->sStats,
-                  &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar};
+                  &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab};
     for (Buf *b : all) release(*b);
     for (hipEvent_t e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
@@ -326,7 +326,7 @@ int ps_context_get_option(const PsContext *ctx, const char *name)
                             &ctx->survA, &ctx->survB, &ctx->survN, &ctx->recF2, &ctx->permBuf, &ctx->prefInfo, &ctx->frontRec,
                             &ctx->validMask, &ctx->stamps, &ctx->dbgCnt, &ctx->bailCnt, &ctx->counts, &ctx->mvalid, &ctx->cmax,
                             &ctx->idxList, &ctx->raw, &ctx->xq, &ctx->tabR, &ctx->tabU, &ctx->sDesc, &ctx->sNk, &ctx->sMatches,
-                            &ctx->sNumM, &ctx->sMask, &ctx->sPose, &ctx->sStats, &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar};
+                            &ctx->sNumM, &ctx->sMask, &ctx->sPose, &ctx->sStats, &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab};
         size_t sum = 0;
         for (const Buf *b : all) sum += b->cap;
         return (int)((sum + (((size_t)1 << 20) - 1)) >> 20);
@@ -442,6 +442,61 @@ int ps_predicted_level(int octave, double detDist, double curDist)
     if (curLevel < 0) curLevel = 0;
     if (curLevel > nLevels - 1) curLevel = nLevels - 1;
     return curLevel;
+}
+
+// ceil(log(x) / log(1.2)) > k, the libm calls of ps_predicted_level on x itself
+static bool level_above(double x, int k) { return std::ceil(std::log(x) / std::log(1.2)) > (double)k; }
+
+int psi_level_tables(double *t7, double *pow64)
+{
+    static double T[7], P[PS_LEVEL_OCTAVE_MAX - PS_LEVEL_OCTAVE_MIN + 1];
+    static int state = 0; // 0 not computed, 1 clean, -1 the libm is not locally monotone
+    if (state == 0) {
+        auto bits = [](double d) { uint64_t b; std::memcpy(&b, &d, 8); return b; };
+        auto val = [](uint64_t b) { double d; std::memcpy(&d, &b, 8); return d; };
+        bool clean = true;
+        for (int k = 0; k < 7 && clean; ++k) {
+            uint64_t lo = bits(0.5), hi = bits(8.0); // 1.2^k lies in [1, 3.6): false at 0.5, true at 8
+            while (lo < hi) {
+                const uint64_t mid = lo + (hi - lo) / 2;
+                if (level_above(val(mid), k))
+                    hi = mid;
+                else
+                    lo = mid + 1;
+            }
+            T[k] = val(lo);
+            for (int64_t d = -4096; d <= 4096 && clean; ++d) clean = level_above(val(lo + (uint64_t)d), k) == (d >= 0);
+        }
+        for (int o = PS_LEVEL_OCTAVE_MIN; o <= PS_LEVEL_OCTAVE_MAX; ++o) P[o - PS_LEVEL_OCTAVE_MIN] = std::pow(1.2, o);
+        state = clean ? 1 : -1;
+    }
+    if (state < 0) return PS_ERR_UNSUPPORTED;
+    if (t7) std::memcpy(t7, T, sizeof(T));
+    if (pow64) std::memcpy(pow64, P, sizeof(P));
+    return PS_OK;
+}
+
+int ps_level_thresholds(double t[7])
+{
+    if (!t) return PS_ERR_BAD_ARG;
+    return psi_level_tables(t, nullptr);
+}
+
+int ps_view_angles(const double *curPose16, const double *poses16, int numPoses, double *angle)
+{
+    // FeaturesMap::findNearestFrame, featuresMap.cpp:534-556: the view vectors are the third rotation columns
+    if (!curPose16 || numPoses < 0 || (numPoses > 0 && (!poses16 || !angle))) return PS_ERR_BAD_ARG;
+    const float a0 = (float)curPose16[8], a1 = (float)curPose16[9], a2 = (float)curPose16[10];
+    const float na = std::sqrt(a0 * a0 + (a1 * a1 + a2 * a2));
+    for (int q = 0; q < numPoses; ++q) {
+        const double *m = poses16 + (size_t)q * 16;
+        const float b0 = (float)m[8], b1 = (float)m[9], b2 = (float)m[10];
+        const float dot = b0 * a0 + (b1 * a1 + b2 * a2);
+        const float nb = std::sqrt(b0 * b0 + (b1 * b1 + b2 * b2));
+        const float r = dot / (nb * na);
+        angle[q] = std::fabs(std::acos((double)r));
+    }
+    return PS_OK;
 }
 
 

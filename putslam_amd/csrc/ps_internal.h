@@ -52,6 +52,8 @@ struct PsContext {
     // staging for the host-pointer entry points (device)
     Buf sDesc, sNk, sMatches, sNumM, sMask, sPose, sStats, sMisc0, sMisc1, sMisc2;
     Buf exFlag, exPar; // exclusion filters (ps_exclusion.h): per frame and candidate slot, the sweep's flag and the union-find's parent
+    Buf viewChunks;    // map views (ps_map_view.h): per view and chunk of 256 candidate slots the kept flags and their count, per view a flag
+    Buf levelTab;      // the level rule's constant block (psdev::LevelBlock), filled at the first call that needs it
     // cached stop tables
     int tabEstimator = -1, tabH = -1, tabRN = 0, tabUN = 0, tabIter0 = 0;
     double tabMinRatio = -1.0;
@@ -232,4 +234,7 @@ int psi_hw_queues_seen(void);
 int psi_hw_queues_defaulted(void);
 // (device translation unit) launch attributes of the kernels that need them; called once per context
 void psi_kernel_attributes(void);
+// ps_level_thresholds' t[7] and T[o] = pow(1.2, o), o = PS_LEVEL_OCTAVE_MIN .. PS_LEVEL_OCTAVE_MAX (either may be null), computed once
+// per process with the host's libm (ps_context.cpp); PS_ERR_UNSUPPORTED if the thresholds are not clean.
+int psi_level_tables(double *t7, double *powTable);
 }

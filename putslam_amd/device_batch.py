@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import api
-from ._abi import DMATCH_DTYPE, STATS_DTYPE
+from ._abi import DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsMapStore, PsMapViewOut, PsMapViewRequest
 
 
 class FrameSetDevice:
@@ -235,13 +235,10 @@ class MapBatchDevice:
     def __init__(self, maps, map_level, frames, cur_level, pairs, max_matches, radius=0.12, ratio=0.55, device=None):
         self.device = torch.device(device) if device is not None else maps.device
         self.maps, self.frames = maps, frames
-        map_level = np.ascontiguousarray(map_level, np.int32)
-        cur_level = np.ascontiguousarray(cur_level, np.int32)
-        assert map_level.shape == (maps.num_frames, maps.max_kpts) and cur_level.shape == (frames.num_frames, frames.max_kpts)
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         self.P, self.cap = pairs.shape[0], int(max_matches)
-        self.map_level = torch.from_numpy(map_level).to(self.device)
-        self.cur_level = torch.from_numpy(cur_level).to(self.device)
+        self.map_level = self._levels(map_level, maps)
+        self.cur_level = self._levels(cur_level, frames)
         self.pairs = torch.from_numpy(pairs).to(self.device)
         self.radius_bound = self.accept_ratio = 0.0
         self.radius_per = self.ratio_per = None
@@ -262,6 +259,17 @@ class MapBatchDevice:
         self.pose = torch.zeros((P, 16), dtype=torch.float32, device=self.device)
         self.stats = torch.zeros((P, STATS_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
         torch.cuda.current_stream(self.device).synchronize()    # (the fills are done before a chain writes: PairBatchDevice)
+
+    def _levels(self, level, fs):
+        """Levels of a frame set: a numpy array is uploaded; a device tensor (build_map_views' / frame_levels_device's
+        output) is used where it lies."""
+        if isinstance(level, torch.Tensor):
+            assert level.dtype == torch.int32 and level.is_contiguous() and level.device == self.device
+            assert tuple(level.shape) == (fs.num_frames, fs.max_kpts)
+            return level
+        level = np.ascontiguousarray(level, np.int32)
+        assert level.shape == (fs.num_frames, fs.max_kpts)
+        return torch.from_numpy(level).to(self.device)
 
     def batch_view(self, lo=0, hi=None):
         """PsMapBatch of pairs [lo, hi)."""
@@ -314,3 +322,144 @@ def run_match_xyz(ctx, batch: MapBatchDevice, use_torch_stream=True):
     _on_torch_stream(ctx, batch.device,
                      lambda: ctx.match_xyz_device(batch.batch_view(), batch.matches.data_ptr(), batch.num_matches.data_ptr()),
                      use_torch_stream)
+
+
+class MapStoreDevice:
+    """The front-end feature map resident in HBM (PsMapStore), uploaded once and replaced whole: pos (F, 3) float64 global
+    positions; obs_start (F + 1,) int32 -- feature f's observations are rows obs_start[f] .. obs_start[f + 1] of the observation
+    arrays, ascending pose id; obs_pose (O,) int32, obs_desc (O, 32) uint8, obs_octave (O,) int32, obs_det_dist (O,) float64."""
+
+    def __init__(self, pos, obs_start, obs_pose, obs_desc, obs_octave, obs_det_dist, num_poses, device="cuda:0"):
+        self.device = torch.device(device)
+        pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+        obs_start = np.ascontiguousarray(obs_start, np.int32)
+        obs_pose = np.ascontiguousarray(obs_pose, np.int32)
+        obs_desc = np.ascontiguousarray(obs_desc, np.uint8).reshape(-1, 32)
+        obs_octave = np.ascontiguousarray(obs_octave, np.int32)
+        obs_det_dist = np.ascontiguousarray(obs_det_dist, np.float64)
+        self.num_features, self.num_obs, self.num_poses = pos.shape[0], obs_pose.shape[0], int(num_poses)
+        assert obs_start.shape == (self.num_features + 1,)
+        assert obs_desc.shape[0] == obs_octave.shape[0] == obs_det_dist.shape[0] == self.num_obs
+        up = lambda a: torch.from_numpy(a).to(self.device)   # noqa: E731
+        self.pos, self.obs_start, self.obs_pose = up(pos), up(obs_start), up(obs_pose)
+        self.obs_desc, self.obs_octave, self.obs_det_dist = up(obs_desc), up(obs_octave), up(obs_det_dist)
+        torch.cuda.current_stream(self.device).synchronize()   # (resident before a context's own stream reads it)
+
+    def view(self):
+        return PsMapStore(self.pos.data_ptr(), self.obs_start.data_ptr(), self.obs_pose.data_ptr(), self.obs_desc.data_ptr(),
+                          self.obs_octave.data_ptr(), self.obs_det_dist.data_ptr(), self.num_features, self.num_obs,
+                          self.num_poses, 0)
+
+
+class MapViewsDevice:
+    """What ps_map_views_device wrote: a frame set (desc / pts / nkpts; usable as MapBatchDevice.maps), map_level (V, cap) int32
+    for MapBatchDevice's map_level, view_count (V,) and the side arrays feat_idx / obs_idx (V, cap) int32, pos_cam (V, cap, 3),
+    uv (V, cap, 2), angle (V, cap) float64 -- device tensors.  packed_stride: bytes per view of ONE block
+    [cap x 32 B descriptors][cap x 12 B points] (PsFrameSet strides) instead of two dense arrays."""
+
+    def __init__(self, V, max_kpts, device, packed_stride=None):
+        self.device = torch.device(device)
+        self.num_frames, self.max_kpts = int(V), int(max_kpts)
+        n, cap = max(self.num_frames, 1), self.max_kpts
+        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)   # noqa: E731
+        self.stride = None if packed_stride is None else int(packed_stride)
+        if self.stride is None:
+            self.desc, self.pts = new((n, cap, 32), torch.uint8), new((n, cap, 3), torch.float32)
+        else:
+            self.blocks = new((n, self.stride), torch.uint8)
+        self.nkpts, self.view_count = new((n,), torch.int32), new((n,), torch.int32)
+        self.map_level, self.feat_idx, self.obs_idx = (new((n, cap), torch.int32) for _ in range(3))
+        self.pos_cam, self.uv, self.angle = new((n, cap, 3), torch.float64), new((n, cap, 2), torch.float64), new((n, cap), torch.float64)
+        torch.cuda.current_stream(self.device).synchronize()   # (the fills are done before a context's stream writes)
+
+    def view(self):
+        if self.stride is None:
+            return api.DeviceFrames(self.desc.data_ptr(), self.pts.data_ptr(), self.nkpts.data_ptr(), self.num_frames, self.max_kpts)
+        base = self.blocks.data_ptr()
+        return api.DeviceFrames(base, base + self.max_kpts * 32, self.nkpts.data_ptr(), self.num_frames, self.max_kpts,
+                                self.stride, self.stride)
+
+    def out_struct(self):
+        f = self.view()
+        return PsMapViewOut(api.PsFrameSet(f.desc_ptr, f.pts_ptr, f.nkpts_ptr, f.num_frames, f.max_kpts, f.desc_stride, f.pts_stride),
+                            self.map_level.data_ptr(), self.view_count.data_ptr(), self.feat_idx.data_ptr(), self.obs_idx.data_ptr(),
+                            self.pos_cam.data_ptr(), self.uv.data_ptr(), self.angle.data_ptr())
+
+    def download(self):
+        """Everything on the host (numpy); desc (V, cap, 32) and pts (V, cap, 3) whatever the layout."""
+        torch.cuda.synchronize(self.device)
+        V, cap = self.num_frames, self.max_kpts
+        if self.stride is None:
+            desc, pts = self.desc.cpu().numpy(), self.pts.cpu().numpy()
+        else:
+            b = self.blocks.cpu().numpy()
+            desc = b[:, :cap * 32].reshape(-1, cap, 32)
+            pts = np.ascontiguousarray(b[:, cap * 32:cap * 44]).view(np.float32).reshape(-1, cap, 3)
+        g = lambda t: t.cpu().numpy()[:V]   # noqa: E731
+        return dict(desc=desc[:V], pts=pts[:V], nkpts=g(self.nkpts), viewCount=g(self.view_count), mapLevel=g(self.map_level),
+                    featIdx=g(self.feat_idx), obsIdx=g(self.obs_idx), posCam=g(self.pos_cam), uv=g(self.uv), angle=g(self.angle))
+
+
+def build_map_views(ctx, store: MapStoreDevice, cam_inv, pose_angle, max_angle, K, image_size, max_kpts, cand=None,
+                    cand_counts=None, require_visible=False, out=None, packed_stride=None, use_torch_stream=True):
+    """ps_map_views_device: V map views from the resident store, asynchronous, ordered like `run_map_pairs`.
+    cam_inv (V, 4, 4): inverse camera poses (numpy, or a device tensor (V, 16) float64 column-major); pose_angle (V, num_poses):
+    api.view_angles of each view's pose (numpy or device tensor); K = (fx, fy, cx, cy); image_size = (width, height);
+    cand (V, cap) int32 + cand_counts (V,) (numpy or device tensors), or None = every feature of the store in index order.
+    Returns a MapViewsDevice (`out`, if given, is written again: a retry with the reported capacity allocates a new one)."""
+    dev = store.device
+
+    def dev_t(a, dt, shape=None):
+        if isinstance(a, torch.Tensor):
+            assert a.dtype == dt and a.is_contiguous() and a.device == dev
+            return a
+        a = np.ascontiguousarray(a, {torch.float64: np.float64, torch.int32: np.int32}[dt])
+        return torch.from_numpy(a if shape is None else a.reshape(shape)).to(dev)
+
+    if not isinstance(cam_inv, torch.Tensor):
+        cam_inv = np.ascontiguousarray(np.asarray(cam_inv, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1, 16)
+    cam_inv = dev_t(cam_inv, torch.float64)
+    V = int(cam_inv.shape[0])
+    pose_angle = dev_t(pose_angle, torch.float64, (V, store.num_poses))
+    assert tuple(pose_angle.shape) == (V, store.num_poses)
+    req = PsMapViewRequest()
+    req.camInv, req.poseAngle = cam_inv.data_ptr(), pose_angle.data_ptr()
+    keep = [cam_inv, pose_angle]
+    if cand is not None:
+        cand, cand_counts = dev_t(cand, torch.int32), dev_t(cand_counts, torch.int32)
+        assert cand.dim() == 2 and cand.shape[0] == V and tuple(cand_counts.shape) == (V,)
+        # (a list of capacity 0 is still a list -- every view empty --, not "every feature": an empty tensor has no address)
+        buf = cand if cand.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
+        req.cand, req.candCounts, req.candCapacity = buf.data_ptr(), cand_counts.data_ptr(), int(cand.shape[1])
+        keep += [buf, cand_counts]
+    req.maxAngle = float(max_angle)
+    req.fx, req.fy, req.cx, req.cy = (float(x) for x in K)
+    req.imageW, req.imageH = float(image_size[0]), float(image_size[1])
+    req.V, req.flags = V, PS_VIEW_REQUIRE_VISIBLE if require_visible else 0
+    if out is None:
+        out = MapViewsDevice(V, max_kpts, dev, packed_stride)
+    assert out.num_frames >= V and out.max_kpts == int(max_kpts)
+    torch.cuda.current_stream(dev).synchronize()   # (uploads above are complete before the context's stream reads them)
+    out.inputs = keep                              # the request's device arrays live as long as the result
+    st, os_ = store.view(), out.out_struct()
+    _on_torch_stream(ctx, dev, lambda: ctx.map_views_device(st, req, os_), use_torch_stream)
+    return out
+
+
+def frame_levels_device(ctx, frames, octave, det_dist, use_torch_stream=True):
+    """ps_frame_levels_device: predicted levels (F, cap) int32 of the keypoints of a device-resident frame set, for
+    MapBatchDevice's cur_level.  octave (F, cap) int32 / det_dist (F, cap) float64: numpy or device tensors.  An octave outside
+    the level table gives -1."""
+    dev = frames.device
+    up = lambda a, dt, nd: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, nd)).to(dev)   # noqa: E731
+    octave, det_dist = up(octave, torch.int32, np.int32), up(det_dist, torch.float64, np.float64)
+    shape = (frames.num_frames, frames.max_kpts)
+    assert octave.dtype == torch.int32 and det_dist.dtype == torch.float64 and tuple(octave.shape) == tuple(det_dist.shape) == shape
+    assert octave.is_contiguous() and det_dist.is_contiguous()
+    level = torch.zeros(shape, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    fv = frames.view()
+    _on_torch_stream(ctx, dev, lambda: ctx.frame_levels_device(fv, octave.data_ptr(), det_dist.data_ptr(), level.data_ptr()),
+                     use_torch_stream)
+    level.inputs = (octave, det_dist)
+    return level
