@@ -361,7 +361,8 @@ typedef struct PsFrameSet {
      * their descriptors and points together -- [maxKpts x 32 B][maxKpts x 12 B] per frame, what one transfer per frame or per
      * chunk of frames delivers (the prevDescriptors / prevFeatures3D pair of matcher.h:379-384 as one block) -- has
      * pts = desc + maxKpts x 32 and both strides = the frame's size.  descFrameStride: a multiple of 16, >= maxKpts x 32;
-     * ptsFrameStride: a multiple of 4, >= maxKpts x 12. */
+     * ptsFrameStride: a multiple of 4, >= maxKpts x 12; desc itself 16-byte aligned.  Every call that takes a frame set applies
+     * this one rule, and refuses a stride whose quarter does not fit an int (8 GiB and more between frames) with PS_ERR_BAD_ARG. */
     size_t descFrameStride;
     size_t ptsFrameStride;
 } PsFrameSet;

@@ -3,8 +3,9 @@ build-if-missing all come here).
 
 The library is ONE device translation unit -- csrc/ps_capi.hip and the kernel headers it includes, compiled by hipcc for
 gfx950 -- plus host-only translation units compiled as plain C++ against the HIP runtime API (no device code, no kernels):
-a change to those recompiles in a second, not with the 54 kernels.
+a change to those recompiles in a second, not with the kernels.
 """
+import glob
 import os
 import subprocess
 
@@ -24,9 +25,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
 
 DEVICE_TU = "ps_capi.hip"
-DEVICE_DEPS = ["ps_kernels.h", "ps_matcher_mfma.h", "ps_score_fast.h", "ps_score_euclid.h", "ps_device_math.h",
-               "ps_stream_async.h", "ps_stream_push.h", "ps_diag.h", "ps_internal.h", "ps_dbscan.h", "ps_map_match.h",
-               "ps_exclusion.h", "ps_map_view.h"]
+DEVICE_DEPS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.h")))  # every header directly under csrc/
 HOST_TUS = ["ps_context.cpp", "ps_env.cpp", "ps_batch_queue.cpp"]
 HOST_DEPS = ["ps_internal.h"]
 HEADER = os.path.join(ROOT, "include", "putslam_hip.h")

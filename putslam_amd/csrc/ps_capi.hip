@@ -3,12 +3,16 @@
 // timing record -- lives in ps_context.cpp / ps_internal.h, host-only; so do the batch queue and the environment default.
 // There is no CPU fallback anywhere in this file: every entry point launches the HIP kernels
 // of ps_kernels.h or fails with a negative PsStatus.
+//
+// Top to bottom: the VO path's kernel headers, the shared host glue (ps_glue.h), the plan of a call with its schedule and stages,
+// the VO and host-pointer entry points, then every further feature as ONE header (its kernels, then its host glue and entry
+// points) in dependency order, and psi_kernel_attributes last.
 #include "ps_kernels.h"
 #include "ps_matcher_mfma.h"
 #include "ps_score_fast.h"
 #include "ps_score_euclid.h"
-#include "ps_map_match.h"
 #include "ps_internal.h"
+#include "ps_glue.h"
 
 #include <cfloat>
 #include <chrono>
@@ -50,9 +54,6 @@ constexpr StagedFrom kStagedFromEuclidFixedSbs = {4.5e5, 75.0}, kStagedFromRepro
                      kStagedFromEuclidAdaptiveSbs = {2.4e4, 0.0}, kStagedFromReprojAdaptiveSbs = {2.4e4, 0.0};
 constexpr int kGenPlainFrom = 2; // complete scoring generates its models by a launch of their own from this many pairs on (Plan::genPlain)
 constexpr int kMfmaTT = 4;       // train tiles per wave of the MFMA matcher (ps_hamming_mfma<TT>, ps_matcher_mfma.h)
-} // namespace
-
-namespace {
 
 // The matcher forms that merge with atomicMin start from an all-ones keys block (see PsContext::keysCleanPtr).
 int keys_clean(PsContext *ctx, size_t bytes)
@@ -742,17 +743,12 @@ int run_match_stage(PsContext *ctx, const PsFrameSet &fs, const int32_t *dPairs,
                     int32_t *dNumMatches, int slot0)
 {
     const int cap = fs.maxKpts;
-    // frame strides (PsFrameSet, ABI 2): dense unless the frames keep descriptors and points together
-    const size_t descStride = fs.descFrameStride ? fs.descFrameStride : (size_t)cap * 32;
-    const size_t ptsStride = fs.ptsFrameStride ? fs.ptsFrameStride : (size_t)cap * 12;
-    if ((descStride & 15) != 0 || descStride < (size_t)cap * 32 || (ptsStride & 3) != 0 || (fs.pts && ptsStride < (size_t)cap * 12) ||
-        descStride / 4 > (size_t)INT_MAX || ptsStride / 4 > (size_t)INT_MAX || ((uintptr_t)fs.desc & 15) != 0)
-        return fail(ctx, PS_ERR_BAD_ARG, "frame set: descFrameStride must be a multiple of 16 and >= maxKpts x 32 (desc 16-byte aligned), "
-                                         "ptsFrameStride a multiple of 4 and >= maxKpts x 12");
-    const int fstrideDw = (int)(descStride / 4);
+    FrameStrides strides; // (PsFrameSet, ABI 2: dense unless the frames keep descriptors and points together; no points: ps_match_hamming256)
+    if (int rc = frame_strides(ctx, fs, true, fs.pts != nullptr, "frame set", strides)) return rc;
+    const int fstrideDw = strides.descDwords();
     PrepArgs pa = pl ? pl->pa : PrepArgs{};
     if (!pl) pa.cap = cap;
-    pa.ptsStride = (int)(ptsStride / 4);
+    pa.ptsStride = strides.ptsFloats();
     PS_ENSURE(ctx->keys, (size_t)P * cap * sizeof(uint32_t));
     PS_ENSURE(ctx->mvalid, (size_t)P * sizeof(int32_t));
     PS_ENSURE(ctx->cmax, (size_t)P * sizeof(float2));
@@ -826,7 +822,7 @@ int run_match_stage(PsContext *ctx, const PsFrameSet &fs, const int32_t *dPairs,
         }
         tick(ctx, slot0, false);
         hipLaunchKernelGGL(ps_hamming_nn<TPL>, dim3((unsigned)(tiles * qsplit) * (unsigned)P), dim3(kBlock), 0, ctx->stream,
-                           (const uint4 *)fs.desc, fs.nkpts, dPairs, cap, fstrideDw / 4, tiles, qsplit, (uint32_t *)ctx->keys.p);
+                           (const uint4 *)fs.desc, fs.nkpts, dPairs, cap, strides.descUint4(), tiles, qsplit, (uint32_t *)ctx->keys.p);
         tick(ctx, slot0, true);
         PS_HIP(hipGetLastError());
     }
@@ -846,36 +842,9 @@ void identity16(float *T)
     for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
 }
 
-// The host-pointer entry points are not part of the timed record.
-struct TimingOff {
-    PsContext *c;
-    bool saved;
-    explicit TimingOff(PsContext *ctx) : c(ctx), saved(ctx->timing) { c->timing = false; }
-    ~TimingOff() { c->timing = saved; }
-};
-
 } // namespace
 
-// (DBScan's launch attribute: defined with the rest of DBScan at the end of this file)
-static void dbscan_kernel_attributes();
-static void exclusion_kernel_attributes(); // (likewise: the exclusion filters)
-
 extern "C" {
-
-void psi_kernel_attributes(void)
-{
-    // the cross-check kernel keeps best[q] for up to PS_MAX_KPTS queries in LDS (64 KiB of the CU's 160 KiB)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_crosscheck_prep<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, PS_MAX_KPTS * 4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_crosscheck_prep<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, PS_MAX_KPTS * 4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_crosscheck_prep<true, 1024>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, PS_MAX_KPTS * 4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_crosscheck_prep<false, 1024>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, PS_MAX_KPTS * 4);
-    dbscan_kernel_attributes();
-    exclusion_kernel_attributes();
-}
 
 // ---------------------------------------------------------------------------------------------
 int ps_match_hamming256(PsContext *ctx, const uint8_t *query, int nq, size_t qstep, const uint8_t *train, int nt,
@@ -1028,7 +997,11 @@ int ps_ransac_rigid3d(PsContext *ctx, const PsRansacParams *params, const PsRans
                              nullptr);
 }
 
+} // extern "C"
+
 #include "ps_diag.h" // ps_debug_*: the parity tests' diagnostics (no reference counterpart)
+
+extern "C" {
 
 // ---------------------------------------------------------------------------------------------
 int ps_match_xyz(PsContext *ctx, const float *mapPos, const uint8_t *mapDesc, size_t mapDescStep, const int32_t *mapLevel,
@@ -1253,653 +1226,40 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
         return fail(ctx, PS_ERR_BAD_ARG, "ps_vo_pairs_device: bad frame set");
     if (!out->matches || !out->numMatches || !out->inlierMask || !out->pose || !out->stats)
         return fail(ctx, PS_ERR_BAD_ARG, "ps_vo_pairs_device: null output");
-    {
-        // (frame strides are checked here, before anything is planned or allocated; run_match_stage checks them again for its
-        // other callers)
-        const size_t ds = frames->descFrameStride ? frames->descFrameStride : (size_t)frames->maxKpts * 32;
-        const size_t ps = frames->ptsFrameStride ? frames->ptsFrameStride : (size_t)frames->maxKpts * 12;
-        if ((ds & 15) != 0 || ds < (size_t)frames->maxKpts * 32 || (ps & 3) != 0 || ps < (size_t)frames->maxKpts * 12 || ((uintptr_t)frames->desc & 15) != 0)
-            return fail(ctx, PS_ERR_BAD_ARG, "frame set: descFrameStride must be a multiple of 16 and >= maxKpts x 32 (desc 16-byte aligned), "
-                                             "ptsFrameStride a multiple of 4 and >= maxKpts x 12");
-    }
+    FrameStrides strides; // (checked here, before anything is planned or allocated; run_match_stage resolves them for its launches)
+    rc = frame_strides(ctx, *frames, true, true, "ps_vo_pairs_device", strides);
+    if (rc) return rc;
     if (cfg && cfg->sampleIdx) return fail(ctx, PS_ERR_BAD_ARG, "explicit sample streams are per call, not per batch");
     const int cap = frames->maxKpts;
     Plan pl;
     rc = make_plan(ctx, params, cfg, K, cap, cap, pl);
     if (rc) return rc;
-    if (ctx->timing) {
-        ctx->curCall = (int)(ctx->timedCalls % kTimingRing);
-        ctx->slotMask[ctx->curCall] = 0;
-        ctx->timedCalls++;
-    }
-    // This call returns with its work still queued.  Whatever happens after the first launch -- success or an error half
-    // way (an allocation failure for a later block, a launch failure) -- the end of what WAS queued is marked for a
-    // later ps_context_set_stream: the new stream must not touch the shared arena before that work has finished.
-    // (prepare_score below may already queue a clearing: the guard stands before it)
-    struct Handoff {
-        PsContext *c;
-        ~Handoff()
-        {
-            if (!c->handoff && hipEventCreateWithFlags(&c->handoff, hipEventDisableTiming) != hipSuccess) {
-                c->handoff = nullptr;
-                (void)hipStreamSynchronize(c->stream); // no event to wait on: drain instead
-                return;
-            }
-            if (hipEventRecord(c->handoff, c->stream) == hipSuccess)
-                c->handoffPending = true;
-            else
-                (void)hipStreamSynchronize(c->stream);
-        }
-    } handoffGuard{ctx};
+    begin_timed_call(ctx);
+    HandoffGuard handoffGuard{ctx}; // (prepare_score below may already queue a clearing: the guard stands before it)
     rc = prepare_score(ctx, pl, P, cap, false, true, frames->desc);
     if (rc) return rc;
     rc = run_match_stage(ctx, *frames, pairs, P, &pl, out->matches, out->numMatches, 0);
     if (rc) return rc;
-    rc = run_ransac_stage(ctx, pl, P, cap, out->matches, out->numMatches, cap, out->pose, out->inlierMask, out->stats, 2);
-    return rc;
-}
-
-#include "ps_stream_push.h" // ps_vo_stream_create / _push: the synchronous streaming form
-
-} // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// Map matching for a device-resident batch (ps_map_match.h): Matcher::matchXYZ, matcher.cpp:606-798
-namespace {
-
-// Map features per wave of the sweep: eight when that still gives every CU several work-groups, fewer for a handful of pairs
-// (ten pairs of 2000 features, one frame's retry ladder: four per wave, 1250 work-groups).
-int map_features_per_wave(int P, int mapCap)
-{
-    for (int f = 8; f > 1; f >>= 1)
-        if ((long long)P * ((mapCap + kMapWaves * f - 1) / (kMapWaves * f)) >= 1024) return f;
-    return 1;
-}
-
-int check_frame_set(PsContext *ctx, const PsFrameSet &fs, const char *what)
-{
-    if (!fs.desc || !fs.pts || !fs.nkpts || fs.maxKpts < 1 || fs.numFrames < 1) return fail(ctx, PS_ERR_BAD_ARG, what);
-    if (fs.maxKpts > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, "map batch: more than PS_MAX_KPTS keypoints per view / frame");
-    const size_t ds = fs.descFrameStride ? fs.descFrameStride : (size_t)fs.maxKpts * 32;
-    const size_t ps = fs.ptsFrameStride ? fs.ptsFrameStride : (size_t)fs.maxKpts * 12;
-    if ((ds & 15) != 0 || ds < (size_t)fs.maxKpts * 32 || (ps & 3) != 0 || ps < (size_t)fs.maxKpts * 12 || ds / 16 > (size_t)INT_MAX ||
-        ps / 4 > (size_t)INT_MAX || ((uintptr_t)fs.desc & 15) != 0)
-        return fail(ctx, PS_ERR_BAD_ARG, "frame set: descFrameStride must be a multiple of 16 and >= maxKpts x 32 (desc 16-byte aligned), "
-                                         "ptsFrameStride a multiple of 4 and >= maxKpts x 12");
-    return PS_OK;
-}
-
-int check_map_batch(PsContext *ctx, const PsMapBatch *b)
-{
-    if (!b || b->P < 0) return fail(ctx, PS_ERR_BAD_ARG, "map batch: null batch or P < 0");
-    if (b->P == 0) return PS_OK;
-    if (!b->pairs || !b->mapLevel || !b->curLevel) return fail(ctx, PS_ERR_BAD_ARG, "map batch: null pairs / mapLevel / curLevel");
-    int rc = check_frame_set(ctx, b->maps, "map batch: bad map views (null array, maxKpts or numFrames < 1)");
-    if (rc) return rc;
-    rc = check_frame_set(ctx, b->frames, "map batch: bad frames (null array, maxKpts or numFrames < 1)");
-    if (rc) return rc;
-    if (b->maxMatches < 1) return fail(ctx, PS_ERR_BAD_ARG, "map batch: maxMatches must lie in 1 .. 1 << 22");
-    if (b->maxMatches > (1 << 22)) return fail(ctx, PS_ERR_UNSUPPORTED, "map batch: maxMatches must lie in 1 .. 1 << 22");
-    return PS_OK;
-}
-
-// The two launches of ps_map_match.h for a checked batch; pl = null: matches only.  numClamped (device, P, or null) receives
-// max(numMatches[p], 0), what kernel 4 is given.
-int run_map_match(PsContext *ctx, const PsMapBatch &b, const Plan *pl, PsDMatch *dMatches, int32_t *dNumMatches, int32_t **numClamped,
-                  int slot0)
-{
-    const int P = b.P, F = map_features_per_wave(P, b.maps.maxKpts), CH = kMapWaves * F;
-    MapArgs a{};
-    a.mapPts = b.maps.pts; a.curPts = b.frames.pts;
-    a.mapDesc = (const uint4 *)b.maps.desc; a.curDesc = (const uint4 *)b.frames.desc;
-    a.mapN = b.maps.nkpts; a.curN = b.frames.nkpts;
-    a.mapLevel = b.mapLevel; a.curLevel = b.curLevel;
-    a.mapFrames = b.maps.numFrames; a.curFrames = b.frames.numFrames;
-    a.mapCap = b.maps.maxKpts; a.curCap = b.frames.maxKpts;
-    a.mapPtsStride = (int)((b.maps.ptsFrameStride ? b.maps.ptsFrameStride : (size_t)a.mapCap * 12) / 4);
-    a.curPtsStride = (int)((b.frames.ptsFrameStride ? b.frames.ptsFrameStride : (size_t)a.curCap * 12) / 4);
-    a.mapDescStride = (int)((b.maps.descFrameStride ? b.maps.descFrameStride : (size_t)a.mapCap * 32) / 16);
-    a.curDescStride = (int)((b.frames.descFrameStride ? b.frames.descFrameStride : (size_t)a.curCap * 32) / 16);
-    a.pairs = b.pairs;
-    a.radiusBound = b.radiusBound; a.acceptRatio = b.acceptRatio;
-    a.radiusPer = b.radiusBoundPerPair; a.ratioPer = b.acceptRatioPerPair;
-    a.maxMatches = b.maxMatches;
-    a.chunks = (a.mapCap + CH - 1) / CH;
-    a.chunkFeatures = CH;
-    // scratch: the staging rows, then [P] reserved | [P] clamped | [P][chunks] start | [P][chunks] count
-    PS_ENSURE(ctx->sMatches, (size_t)P * b.maxMatches * sizeof(PsDMatch));
-    PS_ENSURE(ctx->sMisc2, ((size_t)2 * P + (size_t)2 * P * a.chunks) * sizeof(int32_t));
-    if (pl) {
-        PS_ENSURE(ctx->mvalid, (size_t)P * sizeof(int32_t));
-        PS_ENSURE(ctx->cmax, (size_t)P * sizeof(float2));
-        int rc = ensure_records(ctx, (size_t)P, (size_t)b.maxMatches);
-        if (rc != PS_OK) return rc;
-    }
-    a.tmp = (PsDMatch *)ctx->sMatches.p;
-    a.tmpCount = (int32_t *)ctx->sMisc2.p;
-    int32_t *clamped = a.tmpCount + P;
-    a.chunkStart = clamped + P;
-    a.chunkCount = a.chunkStart + (size_t)P * a.chunks;
-    if (numClamped) *numClamped = clamped;
-    PS_HIP(hipMemsetAsync(a.tmpCount, 0, (size_t)P * sizeof(int32_t), ctx->stream));
-    tick(ctx, slot0, false);
-    const dim3 grid((unsigned)P * (unsigned)a.chunks), block(kMapBlock);
-    switch (F) {
-    case 8: hipLaunchKernelGGL(ps_map_sweep<8>, grid, block, 0, ctx->stream, a); break;
-    case 4: hipLaunchKernelGGL(ps_map_sweep<4>, grid, block, 0, ctx->stream, a); break;
-    case 2: hipLaunchKernelGGL(ps_map_sweep<2>, grid, block, 0, ctx->stream, a); break;
-    default: hipLaunchKernelGGL(ps_map_sweep<1>, grid, block, 0, ctx->stream, a); break;
-    }
-    tick(ctx, slot0, true);
-    PS_HIP(hipGetLastError());
-    tick(ctx, slot0 + 1, false);
-    const size_t lds = ((size_t)a.chunks + 1) * sizeof(int32_t);
-    const bool wide = P <= kWidePairs; // a handful of pairs: 1024-thread work-groups shorten the per-pair serial walk
-    const PrepArgs pa = pl ? pl->pa : PrepArgs{};
-    const RecPtrs rp = pl ? rec_ptrs(ctx, pl->score) : RecPtrs{};
-    int32_t *mv = (int32_t *)ctx->mvalid.p;
-    float2 *cmx = (float2 *)ctx->cmax.p;
-    if (pl) {
-        if (wide) hipLaunchKernelGGL((ps_map_emit<true, 1024>), dim3((unsigned)P), dim3(1024), lds, ctx->stream, a, pa, rp, dMatches, dNumMatches, clamped, mv, cmx);
-        else hipLaunchKernelGGL((ps_map_emit<true, kBlock>), dim3((unsigned)P), dim3(kBlock), lds, ctx->stream, a, pa, rp, dMatches, dNumMatches, clamped, mv, cmx);
-    } else {
-        if (wide) hipLaunchKernelGGL((ps_map_emit<false, 1024>), dim3((unsigned)P), dim3(1024), lds, ctx->stream, a, pa, rp, dMatches, dNumMatches, clamped, mv, cmx);
-        else hipLaunchKernelGGL((ps_map_emit<false, kBlock>), dim3((unsigned)P), dim3(kBlock), lds, ctx->stream, a, pa, rp, dMatches, dNumMatches, clamped, mv, cmx);
-    }
-    tick(ctx, slot0 + 1, true);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
-
-// Whatever an asynchronous call has queued is marked for a later ps_context_set_stream (see ps_vo_pairs_device).
-struct MapHandoff {
-    PsContext *c;
-    ~MapHandoff()
-    {
-        if (!c->handoff && hipEventCreateWithFlags(&c->handoff, hipEventDisableTiming) != hipSuccess) {
-            c->handoff = nullptr;
-            (void)hipStreamSynchronize(c->stream); // no event to wait on: drain instead
-            return;
-        }
-        if (hipEventRecord(c->handoff, c->stream) == hipSuccess)
-            c->handoffPending = true;
-        else
-            (void)hipStreamSynchronize(c->stream);
-    }
-};
-
-} // namespace
-
-extern "C" {
-
-float ps_map_sphere_bound(double sphereRadius) { return sq_bound_f32(sphereRadius); }
-
-size_t ps_abi_sizeof_map_batch(void) { return sizeof(PsMapBatch); }
-
-int ps_match_xyz_device(PsContext *ctx, const PsMapBatch *b, PsDMatch *matches, int32_t *numMatches)
-{
-    int rc = bind(ctx);
-    if (rc) return rc;
-    rc = check_map_batch(ctx, b);
-    if (rc) return rc;
-    if (b->P == 0) return PS_OK;
-    if (!matches || !numMatches) return fail(ctx, PS_ERR_BAD_ARG, "ps_match_xyz_device: null output");
-    TimingOff toff(ctx);
-    MapHandoff handoffGuard{ctx};
-    return run_map_match(ctx, *b, nullptr, matches, numMatches, nullptr, 0);
-}
-
-int ps_map_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
-                        const PsMapBatch *b, const PsPairResults *out)
-{
-    int rc = bind(ctx);
-    if (rc) return rc;
-    rc = check_map_batch(ctx, b);
-    if (rc) return rc;
-    if (!out) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_pairs_device: null output");
-    if (b->P == 0) return PS_OK;
-    if (!out->matches || !out->numMatches || !out->inlierMask || !out->pose || !out->stats)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_pairs_device: null output");
-    if (cfg && cfg->sampleIdx) return fail(ctx, PS_ERR_BAD_ARG, "explicit sample streams are per call, not per batch");
-    const int P = b->P, cap = b->maxMatches;
-    Plan pl;
-    rc = make_plan(ctx, params, cfg, K, cap, b->frames.maxKpts, pl);
-    if (rc) return rc;
-    if (ctx->timing) {
-        ctx->curCall = (int)(ctx->timedCalls % kTimingRing);
-        ctx->slotMask[ctx->curCall] = 0;
-        ctx->timedCalls++;
-    }
-    MapHandoff handoffGuard{ctx}; // (prepare_score below may already queue a clearing: the guard stands before it)
-    rc = prepare_score(ctx, pl, P, cap, false, true, b->maps.desc);
-    if (rc) return rc;
-    int32_t *clamped = nullptr;
-    rc = run_map_match(ctx, *b, &pl, out->matches, out->numMatches, &clamped, 0);
-    if (rc) return rc;
-    return run_ransac_stage(ctx, pl, P, cap, out->matches, clamped, cap, out->pose, out->inlierMask, out->stats, 2);
+    return run_ransac_stage(ctx, pl, P, cap, out->matches, out->numMatches, cap, out->pose, out->inlierMask, out->stats, 2);
 }
 
 } // extern "C"
 
-#include "ps_stream_async.h"
+// The further features, each header its kernels and then its host side, in dependency order
+#include "ps_stream_push.h"  // ps_vo_stream_create / _push: the synchronous streaming form
+#include "ps_stream_async.h" // ... and the pipelined one, on the PsVoStream of the former
+#include "ps_map_match.h"    // ps_match_xyz_device / ps_map_pairs_device (the plan and the stages above)
+#include "ps_dbscan.h"       // ps_dbscan_thin(_device)
+#include "ps_exclusion.h"    // ps_exclude(_device) and the three rules (DBScan's bound and union-find)
+#include "ps_map_view.h"     // ps_map_views_device / ps_frame_levels_device
 
-#include "ps_dbscan.h"
-
-// ---------------------------------------------------------------------------------------------
-// DBScan keypoint thinning (ps_dbscan.h): apart from the VO path, at the end of this translation unit
-namespace {
-// the least double s with (double)(float)sqrt(s) >= eps: bisection over the bit patterns of the non-negative doubles, whose
-// order is theirs; the rounded root is monotone in s
-double dbscan_bound(double eps)
+// Launch attributes of the kernels that need them (ps_internal.h; called once per context).
+extern "C" void psi_kernel_attributes(void)
 {
-    if (!(eps > 0.0)) return 0.0; // also NaN: nothing is a neighbour
-    uint64_t lo = 0, hi = 0x7FF0000000000000ull; // +inf: its root reaches every eps
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        double s;
-        std::memcpy(&s, &mid, 8);
-        if ((double)(float)std::sqrt(s) >= eps)
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    double s;
-    std::memcpy(&s, &lo, 8);
-    return s;
+    // the cross-check kernel keeps best[q] for up to PS_MAX_KPTS queries in LDS (64 KiB of the CU's 160 KiB)
+    for (const void *k : {reinterpret_cast<const void *>(&ps_crosscheck_prep<true>), reinterpret_cast<const void *>(&ps_crosscheck_prep<false>),
+                          reinterpret_cast<const void *>(&ps_crosscheck_prep<true, 1024>), reinterpret_cast<const void *>(&ps_crosscheck_prep<false, 1024>)})
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, PS_MAX_KPTS * 4);
+    dbscan_kernel_attributes();
+    exclusion_kernel_attributes();
 }
-
-int dbscan_launch(PsContext *ctx, const float *xy, const int32_t *octave, const int32_t *counts, int n0, int frames, int cap,
-                  double eps, int minPts, int ffc, int32_t *keptIdx, int32_t *nkept)
-{
-    hipLaunchKernelGGL(ps_dbscan_kernel, dim3((unsigned)frames), dim3(kDbBlock), dbscan_lds_bytes(cap), ctx->stream,
-                       reinterpret_cast<const float2 *>(xy), octave, counts, n0, cap, dbscan_bound(eps), minPts, ffc, keptIdx,
-                       nkept);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
-} // namespace
-
-static void dbscan_kernel_attributes()
-{
-    // 20 bytes of per-point state per keypoint
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_dbscan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)dbscan_lds_bytes(PS_DBSCAN_MAX_KPTS));
-}
-
-extern "C" {
-
-double ps_debug_dbscan_bound(double eps) { return dbscan_bound(eps); }
-
-int ps_dbscan_thin(PsContext *ctx, const float *xy, size_t xyStride, const int32_t *octave, size_t octaveStride, int n,
-                   double eps, int minPts, int featuresFromCluster, int32_t *keptIdx, int *nkept)
-{
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (nkept) *nkept = 0;
-    if (xyStride == 0) xyStride = 8;
-    if (octaveStride == 0) octaveStride = 4;
-    if (!nkept || n < 0 || n > PS_DBSCAN_MAX_KPTS || xyStride < 8 || octaveStride < 4 || (n > 0 && (!xy || !keptIdx)))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_dbscan_thin: bad argument (n must lie in 0 .. PS_DBSCAN_MAX_KPTS, strides >= 8 / 4 bytes)");
-    if (n == 0) return PS_OK;
-    std::vector<float> hxy((size_t)n * 2);
-    const char *pxy = reinterpret_cast<const char *>(xy);
-    for (int i = 0; i < n; ++i) std::memcpy(&hxy[(size_t)i * 2], pxy + (size_t)i * xyStride, 8);
-    std::vector<int32_t> hoct;
-    if (octave) {
-        hoct.resize((size_t)n);
-        const char *po = reinterpret_cast<const char *>(octave);
-        for (int i = 0; i < n; ++i) std::memcpy(&hoct[(size_t)i], po + (size_t)i * octaveStride, 4);
-    }
-    PS_ENSURE(ctx->sMisc0, (size_t)n * 8);
-    if (octave) PS_ENSURE(ctx->sMisc1, (size_t)n * 4);
-    PS_ENSURE(ctx->sMisc2, (size_t)n * 4);
-    PS_ENSURE(ctx->sNumM, sizeof(int32_t));
-    PS_HIP(hipMemcpyAsync(ctx->sMisc0.p, hxy.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (octave) PS_HIP(hipMemcpyAsync(ctx->sMisc1.p, hoct.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = dbscan_launch(ctx, (const float *)ctx->sMisc0.p, octave ? (const int32_t *)ctx->sMisc1.p : nullptr, nullptr, n, 1, n, eps,
-                       minPts, featuresFromCluster, (int32_t *)ctx->sMisc2.p, (int32_t *)ctx->sNumM.p);
-    if (rc) return rc;
-    int32_t nk = 0;
-    PS_HIP(hipMemcpyAsync(&nk, ctx->sNumM.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    PS_HIP(hipMemcpyAsync(keptIdx, ctx->sMisc2.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PS_HIP(hipStreamSynchronize(ctx->stream));
-    *nkept = nk;
-    return PS_OK;
-}
-
-int ps_dbscan_thin_device(PsContext *ctx, const float *xy, const int32_t *octave, const int32_t *counts, int frames, int capacity,
-                          double eps, int minPts, int featuresFromCluster, int32_t *keptIdx, int32_t *nkept)
-{
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (frames < 0 || (frames > 0 && (capacity < 1 || capacity > PS_DBSCAN_MAX_KPTS || !xy || !counts || !keptIdx || !nkept)))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_dbscan_thin_device: bad argument (capacity must lie in 1 .. PS_DBSCAN_MAX_KPTS)");
-    if (frames == 0) return PS_OK;
-    return dbscan_launch(ctx, xy, octave, counts, 0, frames, capacity, eps, minPts, featuresFromCluster, keptIdx, nkept);
-}
-
-} // extern "C"
-
-#include "ps_exclusion.h"
-
-// ---------------------------------------------------------------------------------------------
-// Spatial-exclusion filters (ps_exclusion.h): new map features, merge of tracked features, too-close removal
-namespace {
-// the least double s with sqrt(s) >= d: bisection over the bit patterns of the non-negative doubles (dbscan_bound without the
-// rounding to float)
-double sqrt_bound_f64(double d)
-{
-    if (!(d > 0.0)) return 0.0; // also NaN: nothing passes
-    uint64_t lo = 0, hi = 0x7FF0000000000000ull; // +inf: its root reaches every d
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        double s;
-        std::memcpy(&s, &mid, 8);
-        if (std::sqrt(s) >= d)
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    double s;
-    std::memcpy(&s, &lo, 8);
-    return s;
-}
-
-const char *exclusion_rule_error(const PsExclusionRule *r)
-{
-    if (!r) return "null rule";
-    if (r->form3 != PS_EXCL_NONE && r->form3 != PS_EXCL_F32 && r->form3 != PS_EXCL_F64) return "rule: unknown form3";
-    if (r->form2 != PS_EXCL_NONE && r->form2 != PS_EXCL_F64) return "rule: unknown form2";
-    if (r->mode != PS_EXCL_GREEDY && r->mode != PS_EXCL_ALL_EARLIER) return "rule: unknown mode";
-    return nullptr;
-}
-
-int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-// the three launches; flags / par: frames x capC scratch of the context.  n0 / m0 stand in for null counts.
-int exclusion_launch(PsContext *ctx, const PsExclusionRule &rule, const float *cand3, const float *cand2, const int32_t *candCounts,
-                     int n0, int capC, const float *ex3, const float *ex2, const int32_t *exCounts, int m0, int capE, int frames,
-                     int32_t *keptIdx, int32_t *nkept)
-{
-    const bool greedy = rule.mode == PS_EXCL_GREEDY;
-    PS_ENSURE(ctx->exFlag, (size_t)frames * capC);
-    if (greedy) PS_ENSURE(ctx->exPar, (size_t)frames * capC * sizeof(int32_t));
-    uint8_t *flags = (uint8_t *)ctx->exFlag.p;
-    int32_t *par = greedy ? (int32_t *)ctx->exPar.p : nullptr;
-    PS_HIP(hipMemsetAsync(flags, 0, (size_t)frames * capC, ctx->stream));
-    const int chunks = ceil_div(capC, kExTile);
-    const long long groups = (long long)frames * chunks;
-    // a small batch splits the other set's tiles over blockIdx.z until a thousand work-groups are in flight
-    const int want = groups >= 1024 ? 1 : (int)ceil_div(1024, (int)groups);
-    const int tilesE = ceil_div(capE > 0 ? capE : 1, kExTile);
-    const int zE = want < tilesE ? want : tilesE, zC = want < chunks ? want : chunks;
-    const dim3 block(kExTile);
-    hipLaunchKernelGGL(ps_excl_sweep<0>, dim3((unsigned)groups, 1, (unsigned)zE), block, 0, ctx->stream, rule, cand3, cand2,
-                       candCounts, n0, capC, ex3, ex2, exCounts, m0, capE, chunks, flags, par);
-    PS_HIP(hipGetLastError());
-    if (greedy)
-        hipLaunchKernelGGL(ps_excl_sweep<2>, dim3((unsigned)groups, 1, (unsigned)zC), block, 0, ctx->stream, rule, cand3, cand2,
-                           candCounts, n0, capC, ex3, ex2, exCounts, m0, capE, chunks, flags, par);
-    else
-        hipLaunchKernelGGL(ps_excl_sweep<1>, dim3((unsigned)groups, 1, (unsigned)zC), block, 0, ctx->stream, rule, cand3, cand2,
-                           candCounts, n0, capC, ex3, ex2, exCounts, m0, capE, chunks, flags, par);
-    PS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ps_excl_resolve, dim3((unsigned)frames), dim3(kExBlock), greedy ? excl_lds_bytes(capC) : 0, ctx->stream, rule,
-                       cand3, cand2, candCounts, n0, capC, exCounts, m0, capE, (const uint8_t *)flags, (const int32_t *)par, keptIdx,
-                       nkept);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
-} // namespace
-
-static void exclusion_kernel_attributes()
-{
-    // 11 bytes of per-candidate state
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_excl_resolve), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)excl_lds_bytes(PS_EXCL_MAX_CAND));
-}
-
-extern "C" {
-
-size_t ps_abi_sizeof_exclusion_rule(void) { return sizeof(PsExclusionRule); }
-
-double ps_sqrt_bound_f64(double d) { return sqrt_bound_f64(d); }
-
-int ps_exclusion_rule_new_map_features(double minEuclideanDistanceOfFeatures, double minImageDistanceOfFeatures,
-                                       int maxOnceFeatureAdd, PsExclusionRule *rule)
-{
-    if (!rule) return PS_ERR_BAD_ARG;
-    // the thresholds arrive through float parameters (PUTSLAM.cpp:101) and are compared as doubles (:62,68)
-    const double dE = (double)(float)minEuclideanDistanceOfFeatures, dI = (double)(float)minImageDistanceOfFeatures;
-    *rule = PsExclusionRule{};
-    rule->bound3 = (double)sq_bound_f32(dE);
-    rule->bound2 = dbscan_bound(dI);
-    rule->depthMin = 0.8;
-    rule->depthMax = 6.0;
-    rule->form3 = PS_EXCL_F32;
-    rule->form2 = PS_EXCL_F64;
-    rule->mode = PS_EXCL_GREEDY;
-    rule->maxKeep = maxOnceFeatureAdd > 0 ? maxOnceFeatureAdd : 0;
-    rule->depthGate = 1;
-    return PS_OK;
-}
-
-int ps_exclusion_rule_merge_tracked(double minimalReprojDistanceNewTrackingFeatures, PsExclusionRule *rule)
-{
-    if (!rule) return PS_ERR_BAD_ARG;
-    *rule = PsExclusionRule{};
-    rule->bound2 = sqrt_bound_f64(minimalReprojDistanceNewTrackingFeatures);
-    rule->form3 = PS_EXCL_NONE;
-    rule->form2 = PS_EXCL_F64;
-    rule->mode = PS_EXCL_GREEDY;
-    rule->maxKeep = -1;
-    return PS_OK;
-}
-
-int ps_exclusion_rule_too_close(double minimalEuclidDistanceNewTrackingFeatures, double minimalReprojDistanceNewTrackingFeatures,
-                                PsExclusionRule *rule)
-{
-    if (!rule) return PS_ERR_BAD_ARG;
-    *rule = PsExclusionRule{};
-    rule->bound3 = sqrt_bound_f64(minimalEuclidDistanceNewTrackingFeatures);
-    rule->bound2 = sqrt_bound_f64(minimalReprojDistanceNewTrackingFeatures);
-    rule->form3 = PS_EXCL_F64;
-    rule->form2 = PS_EXCL_F64;
-    rule->mode = PS_EXCL_ALL_EARLIER;
-    rule->maxKeep = -1;
-    return PS_OK;
-}
-
-int ps_exclude(PsContext *ctx, const PsExclusionRule *rule, const float *cand3, const float *cand2, int n, const float *exist3,
-               const float *exist2, int m, int32_t *keptIdx, int *nkept)
-{
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (const char *why = exclusion_rule_error(rule)) return fail(ctx, PS_ERR_BAD_ARG, why);
-    if (!nkept || n < 0 || m < 0) return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude: bad argument (null nkept or a negative count)");
-    if (n > PS_EXCL_MAX_CAND || m > PS_MAX_KPTS)
-        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_exclude: more than PS_EXCL_MAX_CAND candidates or PS_MAX_KPTS existing features");
-    const bool need3 = rule->form3 != PS_EXCL_NONE, need2 = rule->form2 != PS_EXCL_NONE;
-    if (n > 0 && (!keptIdx || ((need3 || rule->depthGate) && !cand3) || (need2 && !cand2)))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude: null candidate array or keptIdx");
-    if (n > 0 && m > 0 && ((need3 && !exist3) || (need2 && !exist2)))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude: null array of existing features");
-    if (n == 0) {
-        *nkept = 0;
-        return PS_OK;
-    }
-    TimingOff toff(ctx);
-    const bool up3 = cand3 && (need3 || rule->depthGate), e3 = m > 0 && need3, e2 = m > 0 && need2;
-    if (up3) PS_ENSURE(ctx->sMisc0, (size_t)n * 12);
-    if (need2) PS_ENSURE(ctx->sMisc1, (size_t)n * 8);
-    if (e3) PS_ENSURE(ctx->sDesc, (size_t)m * 12);
-    if (e2) PS_ENSURE(ctx->sMatches, (size_t)m * 8);
-    PS_ENSURE(ctx->sMisc2, (size_t)n * 4);
-    PS_ENSURE(ctx->sNumM, sizeof(int32_t));
-    if (up3) PS_HIP(hipMemcpyAsync(ctx->sMisc0.p, cand3, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
-    if (need2) PS_HIP(hipMemcpyAsync(ctx->sMisc1.p, cand2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (e3) PS_HIP(hipMemcpyAsync(ctx->sDesc.p, exist3, (size_t)m * 12, hipMemcpyHostToDevice, ctx->stream));
-    if (e2) PS_HIP(hipMemcpyAsync(ctx->sMatches.p, exist2, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
-    rc = exclusion_launch(ctx, *rule, up3 ? (const float *)ctx->sMisc0.p : nullptr, need2 ? (const float *)ctx->sMisc1.p : nullptr,
-                          nullptr, n, n, e3 ? (const float *)ctx->sDesc.p : nullptr, e2 ? (const float *)ctx->sMatches.p : nullptr,
-                          nullptr, m, m, 1, (int32_t *)ctx->sMisc2.p, (int32_t *)ctx->sNumM.p);
-    if (rc) return rc;
-    int32_t nk = 0;
-    std::vector<int32_t> kept((size_t)n);
-    PS_HIP(hipMemcpyAsync(&nk, ctx->sNumM.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    PS_HIP(hipMemcpyAsync(kept.data(), ctx->sMisc2.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PS_HIP(hipStreamSynchronize(ctx->stream));
-    if (nk < 0 || nk > n) return fail(ctx, PS_ERR_HIP, "ps_exclude: the device returned an impossible count");
-    std::memcpy(keptIdx, kept.data(), (size_t)nk * 4);
-    *nkept = nk;
-    return PS_OK;
-}
-
-int ps_exclude_device(PsContext *ctx, const PsExclusionRule *rule, const float *cand3, const float *cand2,
-                      const int32_t *candCounts, int candCapacity, const float *exist3, const float *exist2,
-                      const int32_t *existCounts, int existCapacity, int frames, int32_t *keptIdx, int32_t *nkept)
-{
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (const char *why = exclusion_rule_error(rule)) return fail(ctx, PS_ERR_BAD_ARG, why);
-    if (frames < 0 || candCapacity < 1 || existCapacity < 0)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude_device: bad argument (frames >= 0, candCapacity >= 1, existCapacity >= 0)");
-    if (candCapacity > PS_EXCL_MAX_CAND || existCapacity > PS_MAX_KPTS)
-        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_exclude_device: candCapacity above PS_EXCL_MAX_CAND or existCapacity above PS_MAX_KPTS");
-    if (frames == 0) return PS_OK;
-    const bool need3 = rule->form3 != PS_EXCL_NONE, need2 = rule->form2 != PS_EXCL_NONE;
-    if (!candCounts || !keptIdx || !nkept || ((need3 || rule->depthGate) && !cand3) || (need2 && !cand2))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude_device: null candidate array, counts or output");
-    if (existCapacity > 0 && (!existCounts || (need3 && !exist3) || (need2 && !exist2)))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude_device: null array of existing features");
-    TimingOff toff(ctx);
-    MapHandoff handoffGuard{ctx}; // (the context's scratch is in use until the launches have run)
-    return exclusion_launch(ctx, *rule, (need3 || rule->depthGate) ? cand3 : nullptr, need2 ? cand2 : nullptr, candCounts, 0,
-                            candCapacity, existCapacity > 0 && need3 ? exist3 : nullptr, existCapacity > 0 && need2 ? exist2 : nullptr,
-                            existCapacity > 0 ? existCounts : nullptr, 0, existCapacity, frames, keptIdx, nkept);
-}
-
-} // extern "C"
-
-#include "ps_map_view.h"
-
-// ---------------------------------------------------------------------------------------------
-// Map views from a resident feature map (ps_map_view.h): findNearestFrame, the angle filter, the move into the camera frame,
-// the predicted level and the descriptor gather, featuresMap.cpp:528-563 / PUTSLAM.cpp:28-51,932-950 / matcher.cpp:639-652,675-692
-namespace {
-
-// the level rule's constant block, uploaded once per context (the one synchronising step, like a scratch block's first growth)
-int ensure_level_block(PsContext *ctx)
-{
-    if (ctx->levelTab.p) return PS_OK;
-    static LevelBlock host; // (filled identically by every caller: psi_level_tables computes once per process)
-    if (psi_level_tables(host.t, host.pw) != PS_OK)
-        return fail(ctx, PS_ERR_UNSUPPORTED, "level thresholds: the host's log is not monotone around a switching point of ceil(log(x) / log(1.2))");
-    PS_ENSURE(ctx->levelTab, sizeof(LevelBlock));
-    hipError_t e = hipMemcpyAsync(ctx->levelTab.p, &host, sizeof(LevelBlock), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        release(ctx->levelTab);
-        return fail(ctx, PS_ERR_HIP, "level thresholds: upload", e);
-    }
-    return PS_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-size_t ps_abi_sizeof_map_store(void) { return sizeof(PsMapStore); }
-size_t ps_abi_sizeof_map_view_request(void) { return sizeof(PsMapViewRequest); }
-size_t ps_abi_sizeof_map_view_out(void) { return sizeof(PsMapViewOut); }
-
-int ps_map_views_device(PsContext *ctx, const PsMapStore *store, const PsMapViewRequest *req, const PsMapViewOut *out)
-{
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (!store || !req || !out) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null store, request or output block");
-    if (store->numFeatures < 0 || store->numObs < 0 || store->numPoses < 0 || req->V < 0)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: a negative count (numFeatures, numObs, numPoses, V)");
-    if (req->V == 0) return PS_OK;
-    if (!store->obsStart || (store->numFeatures > 0 && !store->pos) ||
-        (store->numObs > 0 && (!store->obsPose || !store->obsDesc || !store->obsOctave || !store->obsDetDist)))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null array in the store");
-    if (((uintptr_t)store->obsDesc & 15) != 0) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: obsDesc must be 16-byte aligned");
-    if (!req->camInv || (store->numPoses > 0 && !req->poseAngle))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null camInv or poseAngle");
-    if (req->cand && (!req->candCounts || req->candCapacity < 0))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: a candidate list needs candCounts and candCapacity >= 0");
-    if (!out->mapLevel || !out->viewCount) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null mapLevel or viewCount");
-    rc = check_frame_set(ctx, out->views, "ps_map_views_device: bad output views (null array, maxKpts or numFrames < 1)");
-    if (rc) return rc;
-    if (out->views.numFrames < req->V) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: the output set has fewer than V views");
-    const int V = req->V, slots = req->cand ? req->candCapacity : store->numFeatures;
-    const int chunks = slots > 0 ? (slots + kViewBlock - 1) / kViewBlock : 1;
-    if ((long long)V * chunks > (long long)INT_MAX)
-        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_map_views_device: V x candidate chunks exceeds the grid");
-    TimingOff toff(ctx);
-    rc = ensure_level_block(ctx);
-    if (rc) return rc;
-    const size_t groups = (size_t)V * chunks;
-    PS_ENSURE(ctx->viewChunks, groups * (kViewWaves * 8 + 4) + (size_t)V * 4);
-    MapHandoff handoffGuard{ctx}; // (the context's scratch is in use until the launches have run)
-    ViewArgs a{};
-    a.pos = store->pos; a.obsStart = store->obsStart; a.obsPose = store->obsPose;
-    a.obsDesc = (const uint4 *)store->obsDesc; a.obsOctave = store->obsOctave; a.obsDetDist = store->obsDetDist;
-    a.numFeatures = store->numFeatures; a.numObs = store->numObs; a.numPoses = store->numPoses;
-    a.camInv = req->camInv; a.poseAngle = req->poseAngle; a.cand = req->cand; a.candCounts = req->candCounts;
-    a.maxAngle = req->maxAngle; a.fx = req->fx; a.fy = req->fy; a.cx = req->cx; a.cy = req->cy;
-    a.imageW = req->imageW; a.imageH = req->imageH;
-    a.slots = slots; a.flags = req->flags;
-    const PsFrameSet &fs = out->views;
-    a.desc = (uint4 *)fs.desc; a.pts = (float *)fs.pts; a.nkpts = (int32_t *)fs.nkpts;
-    a.maxKpts = fs.maxKpts;
-    a.descStride = (int)((fs.descFrameStride ? fs.descFrameStride : (size_t)fs.maxKpts * 32) / 16);
-    a.ptsStride = (int)((fs.ptsFrameStride ? fs.ptsFrameStride : (size_t)fs.maxKpts * 12) / 4);
-    a.mapLevel = out->mapLevel; a.viewCount = out->viewCount; a.featIdx = out->featIdx; a.obsIdx = out->obsIdx;
-    a.posCam = out->posCam; a.uv = out->uv; a.angle = out->angle;
-    a.levels = (const LevelBlock *)ctx->levelTab.p;
-    a.keptMask = (unsigned long long *)ctx->viewChunks.p;
-    a.chunkCount = (int32_t *)(a.keptMask + groups * kViewWaves);
-    a.bad = a.chunkCount + groups;
-    a.chunks = chunks;
-    PS_HIP(hipMemsetAsync(a.bad, 0, (size_t)V * 4, ctx->stream));
-    const dim3 grid((unsigned)groups), block(kViewBlock);
-    const bool staged = store->numPoses <= kViewAngleLds;
-    if (staged) hipLaunchKernelGGL(ps_view_select<true>, grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL(ps_view_select<false>, grid, block, 0, ctx->stream, a);
-    PS_HIP(hipGetLastError());
-    if (staged) hipLaunchKernelGGL(ps_view_emit<true>, grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL(ps_view_emit<false>, grid, block, 0, ctx->stream, a);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
-
-int ps_frame_levels_device(PsContext *ctx, const PsFrameSet *frames, const int32_t *octave, const double *detDist, int32_t *curLevel)
-{
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (!frames || !octave || !detDist || !curLevel || frames->numFrames < 0)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_frame_levels_device: null argument or numFrames < 0");
-    if (frames->numFrames == 0) return PS_OK;
-    if (!frames->pts || !frames->nkpts || frames->maxKpts < 1)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_frame_levels_device: null pts / nkpts or maxKpts < 1");
-    if (frames->maxKpts > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, "ps_frame_levels_device: more than PS_MAX_KPTS keypoints per frame");
-    const size_t ps = frames->ptsFrameStride ? frames->ptsFrameStride : (size_t)frames->maxKpts * 12;
-    if ((ps & 3) != 0 || ps < (size_t)frames->maxKpts * 12 || ps / 4 > (size_t)INT_MAX)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_frame_levels_device: ptsFrameStride must be a multiple of 4 and >= maxKpts x 12");
-    const int chunks = (frames->maxKpts + kViewBlock - 1) / kViewBlock;
-    if ((long long)frames->numFrames * chunks > (long long)INT_MAX)
-        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_frame_levels_device: numFrames x chunks exceeds the grid");
-    TimingOff toff(ctx);
-    rc = ensure_level_block(ctx);
-    if (rc) return rc;
-    MapHandoff handoffGuard{ctx};
-    hipLaunchKernelGGL(ps_frame_levels, dim3((unsigned)frames->numFrames * (unsigned)chunks), dim3(kViewBlock), 0, ctx->stream,
-                       frames->pts, frames->nkpts, frames->maxKpts, (int)(ps / 4), chunks, octave, detDist,
-                       (const LevelBlock *)ctx->levelTab.p, curLevel);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
-
-} // extern "C"

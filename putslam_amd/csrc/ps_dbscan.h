@@ -4,7 +4,7 @@
 // What the reference computes, read closely:
 //  * neighbours: (double)(float)sqrt((double)dx*dx + (double)dy*dy) < eps with dx, dy float differences.  The float products
 //    are exact in double and the sum rounds once, so the predicate is  s < sstar  for the least double sstar whose rounded root
-//    reaches eps (dbscan_bound in ps_capi.hip, host side): no device sqrt.  A NaN makes every predicate false, itself included.
+//    reaches eps (dbscan_bound below, host side): no device sqrt.  A NaN makes every predicate false, itself included.
 //  * main loop in ascending index: an unvisited point counts ALL its neighbours (itself and visited ones included); below
 //    minPts it becomes noise, else it seeds a cluster whose list is expanded.
 //  * expansion: an unvisited x of the list is visited and collects its UNVISITED neighbours (x itself excluded); at least minPts
@@ -23,7 +23,7 @@
 #include <climits>
 #include <cstdint>
 
-#include "putslam_hip.h"
+#include "ps_glue.h"
 
 namespace psdev {
 
@@ -343,3 +343,85 @@ __global__ __launch_bounds__(kDbBlock) void ps_dbscan_kernel(const float2 *__res
 }
 
 } // namespace psdev
+
+// Host side (part of the device translation unit, ps_capi.hip): the bound, the launch and the entry points
+namespace {
+
+// the least double s with (double)(float)sqrt(s) >= eps; the rounded root is monotone in s
+double dbscan_bound(double eps)
+{
+    if (!(eps > 0.0)) return 0.0; // also NaN: nothing is a neighbour
+    return least_double_where([eps](double s) { return (double)(float)std::sqrt(s) >= eps; });
+}
+
+int dbscan_launch(PsContext *ctx, const float *xy, const int32_t *octave, const int32_t *counts, int n0, int frames, int cap,
+                  double eps, int minPts, int ffc, int32_t *keptIdx, int32_t *nkept)
+{
+    hipLaunchKernelGGL(ps_dbscan_kernel, dim3((unsigned)frames), dim3(kDbBlock), dbscan_lds_bytes(cap), ctx->stream,
+                       reinterpret_cast<const float2 *>(xy), octave, counts, n0, cap, dbscan_bound(eps), minPts, ffc, keptIdx,
+                       nkept);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+} // namespace
+
+static void dbscan_kernel_attributes()
+{
+    // 20 bytes of per-point state per keypoint
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_dbscan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)dbscan_lds_bytes(PS_DBSCAN_MAX_KPTS));
+}
+
+extern "C" {
+
+double ps_debug_dbscan_bound(double eps) { return dbscan_bound(eps); }
+
+int ps_dbscan_thin(PsContext *ctx, const float *xy, size_t xyStride, const int32_t *octave, size_t octaveStride, int n,
+                   double eps, int minPts, int featuresFromCluster, int32_t *keptIdx, int *nkept)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (nkept) *nkept = 0;
+    if (xyStride == 0) xyStride = 8;
+    if (octaveStride == 0) octaveStride = 4;
+    if (!nkept || n < 0 || n > PS_DBSCAN_MAX_KPTS || xyStride < 8 || octaveStride < 4 || (n > 0 && (!xy || !keptIdx)))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_dbscan_thin: bad argument (n must lie in 0 .. PS_DBSCAN_MAX_KPTS, strides >= 8 / 4 bytes)");
+    if (n == 0) return PS_OK;
+    std::vector<float> hxy((size_t)n * 2);
+    const char *pxy = reinterpret_cast<const char *>(xy);
+    for (int i = 0; i < n; ++i) std::memcpy(&hxy[(size_t)i * 2], pxy + (size_t)i * xyStride, 8);
+    std::vector<int32_t> hoct;
+    if (octave) {
+        hoct.resize((size_t)n);
+        const char *po = reinterpret_cast<const char *>(octave);
+        for (int i = 0; i < n; ++i) std::memcpy(&hoct[(size_t)i], po + (size_t)i * octaveStride, 4);
+    }
+    PS_ENSURE(ctx->sMisc0, (size_t)n * 8);
+    if (octave) PS_ENSURE(ctx->sMisc1, (size_t)n * 4);
+    PS_ENSURE(ctx->sMisc2, (size_t)n * 4);
+    PS_ENSURE(ctx->sNumM, sizeof(int32_t));
+    PS_HIP(hipMemcpyAsync(ctx->sMisc0.p, hxy.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (octave) PS_HIP(hipMemcpyAsync(ctx->sMisc1.p, hoct.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    rc = dbscan_launch(ctx, (const float *)ctx->sMisc0.p, octave ? (const int32_t *)ctx->sMisc1.p : nullptr, nullptr, n, 1, n, eps,
+                       minPts, featuresFromCluster, (int32_t *)ctx->sMisc2.p, (int32_t *)ctx->sNumM.p);
+    if (rc) return rc;
+    int32_t nk = 0;
+    PS_HIP(hipMemcpyAsync(&nk, ctx->sNumM.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PS_HIP(hipMemcpyAsync(keptIdx, ctx->sMisc2.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PS_HIP(hipStreamSynchronize(ctx->stream));
+    *nkept = nk;
+    return PS_OK;
+}
+
+int ps_dbscan_thin_device(PsContext *ctx, const float *xy, const int32_t *octave, const int32_t *counts, int frames, int capacity,
+                          double eps, int minPts, int featuresFromCluster, int32_t *keptIdx, int32_t *nkept)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (frames < 0 || (frames > 0 && (capacity < 1 || capacity > PS_DBSCAN_MAX_KPTS || !xy || !counts || !keptIdx || !nkept)))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_dbscan_thin_device: bad argument (capacity must lie in 1 .. PS_DBSCAN_MAX_KPTS)");
+    if (frames == 0) return PS_OK;
+    return dbscan_launch(ctx, xy, octave, counts, 0, frames, capacity, eps, minPts, featuresFromCluster, keptIdx, nkept);
+}
+
+} // extern "C"

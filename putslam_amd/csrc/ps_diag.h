@@ -1,9 +1,10 @@
 // ps_diag.h -- the diagnostics of the C ABI (ps_debug_*, include/putslam_hip.h): what the parity tests read beyond the outputs
 // -- per-hypothesis counts, stop tables, the exactness checks of the short division / root forms, staged-scoring survivors,
-// stamps.  No reference counterpart.  Included by ps_capi.hip inside its extern "C" block (the kernels and ransac_host_entry are
-// that file's).
+// stamps.  No reference counterpart.  Included by ps_capi.hip behind ransac_host_entry (the kernels and that function are that
+// file's).
 #pragma once
 
+extern "C" {
 // Diagnostic twin of ps_ransac_rigid3d that also returns the per-hypothesis inlier counts the
 // scoring kernel produced (length = hypotheses actually scored, returned through *numScored).
 int ps_debug_ransac_counts(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
@@ -204,3 +205,4 @@ int ps_debug_limits(PsContext *ctx, int estimator, double minRatio, int H, int M
     return PS_OK;
 }
 
+} // extern "C"

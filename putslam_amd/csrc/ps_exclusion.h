@@ -24,7 +24,8 @@
 #include <cstdint>
 
 #include "ps_dbscan.h"
-#include "putslam_hip.h"
+#include "ps_device_math.h"
+#include "ps_glue.h"
 
 namespace psdev {
 
@@ -339,3 +340,189 @@ __global__ __launch_bounds__(kExBlock) void ps_excl_resolve(PsExclusionRule rule
 }
 
 } // namespace psdev
+
+// Host side (part of the device translation unit, ps_capi.hip): the bounds, the rules, the launches and the entry points
+namespace {
+
+// the least double s with sqrt(s) >= d (dbscan_bound without the rounding to float)
+double sqrt_bound_f64(double d)
+{
+    if (!(d > 0.0)) return 0.0; // also NaN: nothing passes
+    return least_double_where([d](double s) { return std::sqrt(s) >= d; });
+}
+
+const char *exclusion_rule_error(const PsExclusionRule *r)
+{
+    if (!r) return "null rule";
+    if (r->form3 != PS_EXCL_NONE && r->form3 != PS_EXCL_F32 && r->form3 != PS_EXCL_F64) return "rule: unknown form3";
+    if (r->form2 != PS_EXCL_NONE && r->form2 != PS_EXCL_F64) return "rule: unknown form2";
+    if (r->mode != PS_EXCL_GREEDY && r->mode != PS_EXCL_ALL_EARLIER) return "rule: unknown mode";
+    return nullptr;
+}
+
+int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// the three launches; flags / par: frames x capC scratch of the context.  n0 / m0 stand in for null counts.
+int exclusion_launch(PsContext *ctx, const PsExclusionRule &rule, const float *cand3, const float *cand2, const int32_t *candCounts,
+                     int n0, int capC, const float *ex3, const float *ex2, const int32_t *exCounts, int m0, int capE, int frames,
+                     int32_t *keptIdx, int32_t *nkept)
+{
+    const bool greedy = rule.mode == PS_EXCL_GREEDY;
+    PS_ENSURE(ctx->exFlag, (size_t)frames * capC);
+    if (greedy) PS_ENSURE(ctx->exPar, (size_t)frames * capC * sizeof(int32_t));
+    uint8_t *flags = (uint8_t *)ctx->exFlag.p;
+    int32_t *par = greedy ? (int32_t *)ctx->exPar.p : nullptr;
+    PS_HIP(hipMemsetAsync(flags, 0, (size_t)frames * capC, ctx->stream));
+    const int chunks = ceil_div(capC, kExTile);
+    const long long groups = (long long)frames * chunks;
+    // a small batch splits the other set's tiles over blockIdx.z until a thousand work-groups are in flight
+    const int want = groups >= 1024 ? 1 : (int)ceil_div(1024, (int)groups);
+    const int tilesE = ceil_div(capE > 0 ? capE : 1, kExTile);
+    const int zE = want < tilesE ? want : tilesE, zC = want < chunks ? want : chunks;
+    const dim3 block(kExTile);
+    hipLaunchKernelGGL(ps_excl_sweep<0>, dim3((unsigned)groups, 1, (unsigned)zE), block, 0, ctx->stream, rule, cand3, cand2,
+                       candCounts, n0, capC, ex3, ex2, exCounts, m0, capE, chunks, flags, par);
+    PS_HIP(hipGetLastError());
+    if (greedy)
+        hipLaunchKernelGGL(ps_excl_sweep<2>, dim3((unsigned)groups, 1, (unsigned)zC), block, 0, ctx->stream, rule, cand3, cand2,
+                           candCounts, n0, capC, ex3, ex2, exCounts, m0, capE, chunks, flags, par);
+    else
+        hipLaunchKernelGGL(ps_excl_sweep<1>, dim3((unsigned)groups, 1, (unsigned)zC), block, 0, ctx->stream, rule, cand3, cand2,
+                           candCounts, n0, capC, ex3, ex2, exCounts, m0, capE, chunks, flags, par);
+    PS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ps_excl_resolve, dim3((unsigned)frames), dim3(kExBlock), greedy ? excl_lds_bytes(capC) : 0, ctx->stream, rule,
+                       cand3, cand2, candCounts, n0, capC, exCounts, m0, capE, (const uint8_t *)flags, (const int32_t *)par, keptIdx,
+                       nkept);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+} // namespace
+
+static void exclusion_kernel_attributes()
+{
+    // 11 bytes of per-candidate state
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_excl_resolve), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)excl_lds_bytes(PS_EXCL_MAX_CAND));
+}
+
+extern "C" {
+
+size_t ps_abi_sizeof_exclusion_rule(void) { return sizeof(PsExclusionRule); }
+
+double ps_sqrt_bound_f64(double d) { return sqrt_bound_f64(d); }
+
+int ps_exclusion_rule_new_map_features(double minEuclideanDistanceOfFeatures, double minImageDistanceOfFeatures,
+                                       int maxOnceFeatureAdd, PsExclusionRule *rule)
+{
+    if (!rule) return PS_ERR_BAD_ARG;
+    // the thresholds arrive through float parameters (PUTSLAM.cpp:101) and are compared as doubles (:62,68)
+    const double dE = (double)(float)minEuclideanDistanceOfFeatures, dI = (double)(float)minImageDistanceOfFeatures;
+    *rule = PsExclusionRule{};
+    rule->bound3 = (double)sq_bound_f32(dE);
+    rule->bound2 = dbscan_bound(dI);
+    rule->depthMin = 0.8;
+    rule->depthMax = 6.0;
+    rule->form3 = PS_EXCL_F32;
+    rule->form2 = PS_EXCL_F64;
+    rule->mode = PS_EXCL_GREEDY;
+    rule->maxKeep = maxOnceFeatureAdd > 0 ? maxOnceFeatureAdd : 0;
+    rule->depthGate = 1;
+    return PS_OK;
+}
+
+int ps_exclusion_rule_merge_tracked(double minimalReprojDistanceNewTrackingFeatures, PsExclusionRule *rule)
+{
+    if (!rule) return PS_ERR_BAD_ARG;
+    *rule = PsExclusionRule{};
+    rule->bound2 = sqrt_bound_f64(minimalReprojDistanceNewTrackingFeatures);
+    rule->form3 = PS_EXCL_NONE;
+    rule->form2 = PS_EXCL_F64;
+    rule->mode = PS_EXCL_GREEDY;
+    rule->maxKeep = -1;
+    return PS_OK;
+}
+
+int ps_exclusion_rule_too_close(double minimalEuclidDistanceNewTrackingFeatures, double minimalReprojDistanceNewTrackingFeatures,
+                                PsExclusionRule *rule)
+{
+    if (!rule) return PS_ERR_BAD_ARG;
+    *rule = PsExclusionRule{};
+    rule->bound3 = sqrt_bound_f64(minimalEuclidDistanceNewTrackingFeatures);
+    rule->bound2 = sqrt_bound_f64(minimalReprojDistanceNewTrackingFeatures);
+    rule->form3 = PS_EXCL_F64;
+    rule->form2 = PS_EXCL_F64;
+    rule->mode = PS_EXCL_ALL_EARLIER;
+    rule->maxKeep = -1;
+    return PS_OK;
+}
+
+int ps_exclude(PsContext *ctx, const PsExclusionRule *rule, const float *cand3, const float *cand2, int n, const float *exist3,
+               const float *exist2, int m, int32_t *keptIdx, int *nkept)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (const char *why = exclusion_rule_error(rule)) return fail(ctx, PS_ERR_BAD_ARG, why);
+    if (!nkept || n < 0 || m < 0) return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude: bad argument (null nkept or a negative count)");
+    if (n > PS_EXCL_MAX_CAND || m > PS_MAX_KPTS)
+        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_exclude: more than PS_EXCL_MAX_CAND candidates or PS_MAX_KPTS existing features");
+    const bool need3 = rule->form3 != PS_EXCL_NONE, need2 = rule->form2 != PS_EXCL_NONE;
+    if (n > 0 && (!keptIdx || ((need3 || rule->depthGate) && !cand3) || (need2 && !cand2)))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude: null candidate array or keptIdx");
+    if (n > 0 && m > 0 && ((need3 && !exist3) || (need2 && !exist2)))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude: null array of existing features");
+    if (n == 0) {
+        *nkept = 0;
+        return PS_OK;
+    }
+    TimingOff toff(ctx);
+    const bool up3 = cand3 && (need3 || rule->depthGate), e3 = m > 0 && need3, e2 = m > 0 && need2;
+    if (up3) PS_ENSURE(ctx->sMisc0, (size_t)n * 12);
+    if (need2) PS_ENSURE(ctx->sMisc1, (size_t)n * 8);
+    if (e3) PS_ENSURE(ctx->sDesc, (size_t)m * 12);
+    if (e2) PS_ENSURE(ctx->sMatches, (size_t)m * 8);
+    PS_ENSURE(ctx->sMisc2, (size_t)n * 4);
+    PS_ENSURE(ctx->sNumM, sizeof(int32_t));
+    if (up3) PS_HIP(hipMemcpyAsync(ctx->sMisc0.p, cand3, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
+    if (need2) PS_HIP(hipMemcpyAsync(ctx->sMisc1.p, cand2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (e3) PS_HIP(hipMemcpyAsync(ctx->sDesc.p, exist3, (size_t)m * 12, hipMemcpyHostToDevice, ctx->stream));
+    if (e2) PS_HIP(hipMemcpyAsync(ctx->sMatches.p, exist2, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
+    rc = exclusion_launch(ctx, *rule, up3 ? (const float *)ctx->sMisc0.p : nullptr, need2 ? (const float *)ctx->sMisc1.p : nullptr,
+                          nullptr, n, n, e3 ? (const float *)ctx->sDesc.p : nullptr, e2 ? (const float *)ctx->sMatches.p : nullptr,
+                          nullptr, m, m, 1, (int32_t *)ctx->sMisc2.p, (int32_t *)ctx->sNumM.p);
+    if (rc) return rc;
+    int32_t nk = 0;
+    std::vector<int32_t> kept((size_t)n);
+    PS_HIP(hipMemcpyAsync(&nk, ctx->sNumM.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PS_HIP(hipMemcpyAsync(kept.data(), ctx->sMisc2.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PS_HIP(hipStreamSynchronize(ctx->stream));
+    if (nk < 0 || nk > n) return fail(ctx, PS_ERR_HIP, "ps_exclude: the device returned an impossible count");
+    std::memcpy(keptIdx, kept.data(), (size_t)nk * 4);
+    *nkept = nk;
+    return PS_OK;
+}
+
+int ps_exclude_device(PsContext *ctx, const PsExclusionRule *rule, const float *cand3, const float *cand2,
+                      const int32_t *candCounts, int candCapacity, const float *exist3, const float *exist2,
+                      const int32_t *existCounts, int existCapacity, int frames, int32_t *keptIdx, int32_t *nkept)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (const char *why = exclusion_rule_error(rule)) return fail(ctx, PS_ERR_BAD_ARG, why);
+    if (frames < 0 || candCapacity < 1 || existCapacity < 0)
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude_device: bad argument (frames >= 0, candCapacity >= 1, existCapacity >= 0)");
+    if (candCapacity > PS_EXCL_MAX_CAND || existCapacity > PS_MAX_KPTS)
+        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_exclude_device: candCapacity above PS_EXCL_MAX_CAND or existCapacity above PS_MAX_KPTS");
+    if (frames == 0) return PS_OK;
+    const bool need3 = rule->form3 != PS_EXCL_NONE, need2 = rule->form2 != PS_EXCL_NONE;
+    if (!candCounts || !keptIdx || !nkept || ((need3 || rule->depthGate) && !cand3) || (need2 && !cand2))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude_device: null candidate array, counts or output");
+    if (existCapacity > 0 && (!existCounts || (need3 && !exist3) || (need2 && !exist2)))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_exclude_device: null array of existing features");
+    TimingOff toff(ctx);
+    HandoffGuard handoffGuard{ctx}; // (the context's scratch is in use until the launches have run)
+    return exclusion_launch(ctx, *rule, (need3 || rule->depthGate) ? cand3 : nullptr, need2 ? cand2 : nullptr, candCounts, 0,
+                            candCapacity, existCapacity > 0 && need3 ? exist3 : nullptr, existCapacity > 0 && need2 ? exist2 : nullptr,
+                            existCapacity > 0 ? existCounts : nullptr, 0, existCapacity, frames, keptIdx, nkept);
+}
+
+} // extern "C"

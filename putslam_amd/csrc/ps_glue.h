@@ -1,0 +1,101 @@
+// ps_glue.h -- what the entry points of the device translation unit share on the HOST side, each rule once: the guard that marks
+// queued work for a later ps_context_set_stream, the timing record's prologue and its switch, the PsFrameSet stride rule and the
+// bisection behind the host-found bounds.  Host code only; included by ps_capi.hip and by the feature headers' host parts.
+#pragma once
+#include <climits>
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "ps_internal.h"
+
+namespace {
+
+// An asynchronous call returns with its work still queued.  Whatever happens after the first launch -- success or an error half
+// way (an allocation failure for a later block, a launch failure) -- the end of what WAS queued is marked for a later
+// ps_context_set_stream: the new stream must not touch the shared arena before that work has finished.  The guard stands
+// before the first thing the call may queue (prepare_score may already queue a clearing).
+struct HandoffGuard {
+    PsContext *c;
+    ~HandoffGuard()
+    {
+        if (!c->handoff && hipEventCreateWithFlags(&c->handoff, hipEventDisableTiming) != hipSuccess) {
+            c->handoff = nullptr;
+            (void)hipStreamSynchronize(c->stream); // no event to wait on: drain instead
+            return;
+        }
+        if (hipEventRecord(c->handoff, c->stream) == hipSuccess)
+            c->handoffPending = true;
+        else
+            (void)hipStreamSynchronize(c->stream);
+    }
+};
+
+// The host-pointer entry points are not part of the timed record.
+struct TimingOff {
+    PsContext *c;
+    bool saved;
+    explicit TimingOff(PsContext *ctx) : c(ctx), saved(ctx->timing) { c->timing = false; }
+    ~TimingOff() { c->timing = saved; }
+};
+
+// A timed call (the VO and the map batch) takes the next slot of the timing ring; tick() records into it.
+inline void begin_timed_call(PsContext *ctx)
+{
+    if (!ctx->timing) return;
+    ctx->curCall = (int)(ctx->timedCalls++ % kTimingRing);
+    ctx->slotMask[ctx->curCall] = 0;
+}
+
+// Bytes between consecutive frames of a PsFrameSet, resolved, and the same in the units the kernels index with.
+struct FrameStrides {
+    size_t desc = 0, pts = 0;
+    int descDwords() const { return (int)(desc / 4); }
+    int descUint4() const { return (int)(desc / 16); }
+    int ptsFloats() const { return (int)(pts / 4); }
+};
+
+// THE STRIDE RULE of a PsFrameSet (include/putslam_hip.h), for a set whose maxKpts is at least 1: a stride of 0 means dense;
+// descFrameStride is a multiple of 16 and at least maxKpts x 32, desc itself 16-byte aligned; ptsFrameStride is a multiple of 4
+// and at least maxKpts x 12; either divided by 4 fits an int (the kernels' index type).  needDesc / needPts = false: the call
+// reads no descriptors / no points, and that half of the set is not looked at (its resolved stride is still returned).
+// Returns PS_ERR_BAD_ARG with `who` in the message.
+inline int frame_strides(PsContext *ctx, const PsFrameSet &fs, bool needDesc, bool needPts, const char *who, FrameStrides &out)
+{
+    const size_t denseDesc = (size_t)fs.maxKpts * 32, densePts = (size_t)fs.maxKpts * 12;
+    out.desc = fs.descFrameStride ? fs.descFrameStride : denseDesc;
+    out.pts = fs.ptsFrameStride ? fs.ptsFrameStride : densePts;
+    if (needDesc && ((out.desc & 15) != 0 || out.desc < denseDesc || out.desc / 4 > (size_t)INT_MAX || ((uintptr_t)fs.desc & 15) != 0))
+        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": descFrameStride must be a multiple of 16, >= maxKpts x 32 and below 8 GiB, "
+                                                             "desc 16-byte aligned").c_str());
+    if (needPts && ((out.pts & 3) != 0 || out.pts < densePts || out.pts / 4 > (size_t)INT_MAX))
+        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": ptsFrameStride must be a multiple of 4, >= maxKpts x 12 and below 8 GiB").c_str());
+    return PS_OK;
+}
+
+// A complete set as the map calls take it (views, frames, the views a call writes): every array, at least one frame, 1 ..
+// PS_MAX_KPTS keypoints a frame, and the stride rule.
+inline int check_frame_set(PsContext *ctx, const PsFrameSet &fs, const char *who, FrameStrides &out)
+{
+    if (!fs.desc || !fs.pts || !fs.nkpts || fs.maxKpts < 1 || fs.numFrames < 1)
+        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": bad frame set (null array, maxKpts or numFrames < 1)").c_str());
+    if (fs.maxKpts > PS_MAX_KPTS)
+        return fail(ctx, PS_ERR_UNSUPPORTED, (std::string(who) + ": more than PS_MAX_KPTS keypoints per view / frame").c_str());
+    return frame_strides(ctx, fs, true, true, who, out);
+}
+
+// The least non-negative double x, +inf included, with pred(x), for a predicate that is monotone in x and true at +inf:
+// bisection over the bit patterns of the non-negative doubles, whose order is theirs.
+template <class Pred> double least_double_where(Pred pred)
+{
+    const auto value = [](uint64_t bits) { double x; std::memcpy(&x, &bits, 8); return x; };
+    uint64_t lo = 0, hi = 0x7FF0000000000000ull; // +inf
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (pred(value(mid))) hi = mid;
+        else lo = mid + 1;
+    }
+    return value(lo);
+}
+
+} // namespace

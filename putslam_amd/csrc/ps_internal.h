@@ -1,9 +1,9 @@
 // ps_internal.h -- what the translation units of libputslam_hip.so share beyond the public C ABI (include/putslam_hip.h).
 // Not installed, not part of the ABI: the psi_ names may change between versions.
 //
-// The library is ONE device translation unit (ps_capi.hip: the kernels, the plan and every launch) and host-only ones compiled
+// The library is ONE device translation unit (ps_capi.hip and the headers it includes: the kernels, the plan and every launch) and host-only ones compiled
 // as plain C++ (ps_context.cpp: context, scratch arena, option table, stop-table builders, timing record; ps_batch_queue.cpp;
-// ps_env.cpp).  A change to the option table or to the queue recompiles in a second, not with the 54 kernels.
+// ps_env.cpp).  A change to the option table or to the queue recompiles in a second, not with the kernels.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -31,7 +31,7 @@ struct PsContext {
     int device = 0;
     hipStream_t own = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t handoff = nullptr; // recorded at every exit of the asynchronous call (ps_vo_pairs_device) once it has queued work:
+    hipEvent_t handoff = nullptr; // recorded at every exit of an asynchronous call (HandoffGuard, ps_glue.h) once it has queued work:
                                   // a newly selected stream waits for it
     bool handoffPending = false;
     std::string err;

@@ -16,7 +16,7 @@
 //                     scoring records, bounds, the scoring stage's counters cleared.
 // A pair whose count exceeds the row capacity reports -(count) and is handed to RANSAC with no matches.
 #pragma once
-
+#include "ps_glue.h"
 #include "ps_kernels.h"
 
 namespace psdev {
@@ -366,3 +366,147 @@ __global__ __launch_bounds__(BLOCK) void ps_map_emit(MapArgs a, PrepArgs pa, Rec
 }
 
 } // namespace psdev
+
+// Host side: Matcher::matchXYZ, matcher.cpp:606-798, for a device-resident batch.  Part of the device translation unit: included
+// by ps_capi.hip behind the plan and the stages (Plan, make_plan, prepare_score, ensure_records, rec_ptrs, tick, run_ransac_stage).
+namespace {
+
+// Map features per wave of the sweep: eight when that still gives every CU several work-groups, fewer for a handful of pairs
+// (ten pairs of 2000 features, one frame's retry ladder: four per wave, 1250 work-groups).
+int map_features_per_wave(int P, int mapCap)
+{
+    for (int f = 8; f > 1; f >>= 1)
+        if ((long long)P * ((mapCap + kMapWaves * f - 1) / (kMapWaves * f)) >= 1024) return f;
+    return 1;
+}
+
+struct MapStrides { FrameStrides maps, frames; };
+
+int check_map_batch(PsContext *ctx, const PsMapBatch *b, MapStrides &strides)
+{
+    if (!b || b->P < 0) return fail(ctx, PS_ERR_BAD_ARG, "map batch: null batch or P < 0");
+    if (b->P == 0) return PS_OK;
+    if (!b->pairs || !b->mapLevel || !b->curLevel) return fail(ctx, PS_ERR_BAD_ARG, "map batch: null pairs / mapLevel / curLevel");
+    if (int rc = check_frame_set(ctx, b->maps, "map batch: map views", strides.maps)) return rc;
+    if (int rc = check_frame_set(ctx, b->frames, "map batch: frames", strides.frames)) return rc;
+    if (b->maxMatches < 1) return fail(ctx, PS_ERR_BAD_ARG, "map batch: maxMatches must lie in 1 .. 1 << 22");
+    if (b->maxMatches > (1 << 22)) return fail(ctx, PS_ERR_UNSUPPORTED, "map batch: maxMatches must lie in 1 .. 1 << 22");
+    return PS_OK;
+}
+
+// The two launches of ps_map_match.h for a checked batch; pl = null: matches only.  numClamped (device, P, or null) receives
+// max(numMatches[p], 0), what kernel 4 is given.
+int run_map_match(PsContext *ctx, const PsMapBatch &b, const MapStrides &strides, const Plan *pl, PsDMatch *dMatches,
+                  int32_t *dNumMatches, int32_t **numClamped, int slot0)
+{
+    const int P = b.P, F = map_features_per_wave(P, b.maps.maxKpts), CH = kMapWaves * F;
+    MapArgs a{};
+    a.mapPts = b.maps.pts; a.curPts = b.frames.pts;
+    a.mapDesc = (const uint4 *)b.maps.desc; a.curDesc = (const uint4 *)b.frames.desc;
+    a.mapN = b.maps.nkpts; a.curN = b.frames.nkpts;
+    a.mapLevel = b.mapLevel; a.curLevel = b.curLevel;
+    a.mapFrames = b.maps.numFrames; a.curFrames = b.frames.numFrames;
+    a.mapCap = b.maps.maxKpts; a.curCap = b.frames.maxKpts;
+    a.mapPtsStride = strides.maps.ptsFloats(); a.curPtsStride = strides.frames.ptsFloats();
+    a.mapDescStride = strides.maps.descUint4(); a.curDescStride = strides.frames.descUint4();
+    a.pairs = b.pairs;
+    a.radiusBound = b.radiusBound; a.acceptRatio = b.acceptRatio;
+    a.radiusPer = b.radiusBoundPerPair; a.ratioPer = b.acceptRatioPerPair;
+    a.maxMatches = b.maxMatches;
+    a.chunks = (a.mapCap + CH - 1) / CH;
+    a.chunkFeatures = CH;
+    // scratch: the staging rows, then [P] reserved | [P] clamped | [P][chunks] start | [P][chunks] count
+    PS_ENSURE(ctx->sMatches, (size_t)P * b.maxMatches * sizeof(PsDMatch));
+    PS_ENSURE(ctx->sMisc2, ((size_t)2 * P + (size_t)2 * P * a.chunks) * sizeof(int32_t));
+    if (pl) {
+        PS_ENSURE(ctx->mvalid, (size_t)P * sizeof(int32_t));
+        PS_ENSURE(ctx->cmax, (size_t)P * sizeof(float2));
+        int rc = ensure_records(ctx, (size_t)P, (size_t)b.maxMatches);
+        if (rc != PS_OK) return rc;
+    }
+    a.tmp = (PsDMatch *)ctx->sMatches.p;
+    a.tmpCount = (int32_t *)ctx->sMisc2.p;
+    int32_t *clamped = a.tmpCount + P;
+    a.chunkStart = clamped + P;
+    a.chunkCount = a.chunkStart + (size_t)P * a.chunks;
+    if (numClamped) *numClamped = clamped;
+    PS_HIP(hipMemsetAsync(a.tmpCount, 0, (size_t)P * sizeof(int32_t), ctx->stream));
+    tick(ctx, slot0, false);
+    const dim3 grid((unsigned)P * (unsigned)a.chunks), block(kMapBlock);
+    switch (F) {
+    case 8: hipLaunchKernelGGL(ps_map_sweep<8>, grid, block, 0, ctx->stream, a); break;
+    case 4: hipLaunchKernelGGL(ps_map_sweep<4>, grid, block, 0, ctx->stream, a); break;
+    case 2: hipLaunchKernelGGL(ps_map_sweep<2>, grid, block, 0, ctx->stream, a); break;
+    default: hipLaunchKernelGGL(ps_map_sweep<1>, grid, block, 0, ctx->stream, a); break;
+    }
+    tick(ctx, slot0, true);
+    PS_HIP(hipGetLastError());
+    tick(ctx, slot0 + 1, false);
+    const size_t lds = ((size_t)a.chunks + 1) * sizeof(int32_t);
+    const bool wide = P <= kWidePairs; // a handful of pairs: 1024-thread work-groups shorten the per-pair serial walk
+    const PrepArgs pa = pl ? pl->pa : PrepArgs{};
+    const RecPtrs rp = pl ? rec_ptrs(ctx, pl->score) : RecPtrs{};
+    int32_t *mv = (int32_t *)ctx->mvalid.p;
+    float2 *cmx = (float2 *)ctx->cmax.p;
+    if (pl) {
+        if (wide) hipLaunchKernelGGL((ps_map_emit<true, 1024>), dim3((unsigned)P), dim3(1024), lds, ctx->stream, a, pa, rp, dMatches, dNumMatches, clamped, mv, cmx);
+        else hipLaunchKernelGGL((ps_map_emit<true, kBlock>), dim3((unsigned)P), dim3(kBlock), lds, ctx->stream, a, pa, rp, dMatches, dNumMatches, clamped, mv, cmx);
+    } else {
+        if (wide) hipLaunchKernelGGL((ps_map_emit<false, 1024>), dim3((unsigned)P), dim3(1024), lds, ctx->stream, a, pa, rp, dMatches, dNumMatches, clamped, mv, cmx);
+        else hipLaunchKernelGGL((ps_map_emit<false, kBlock>), dim3((unsigned)P), dim3(kBlock), lds, ctx->stream, a, pa, rp, dMatches, dNumMatches, clamped, mv, cmx);
+    }
+    tick(ctx, slot0 + 1, true);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+float ps_map_sphere_bound(double sphereRadius) { return sq_bound_f32(sphereRadius); }
+
+size_t ps_abi_sizeof_map_batch(void) { return sizeof(PsMapBatch); }
+
+int ps_match_xyz_device(PsContext *ctx, const PsMapBatch *b, PsDMatch *matches, int32_t *numMatches)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    MapStrides strides;
+    rc = check_map_batch(ctx, b, strides);
+    if (rc) return rc;
+    if (b->P == 0) return PS_OK;
+    if (!matches || !numMatches) return fail(ctx, PS_ERR_BAD_ARG, "ps_match_xyz_device: null output");
+    TimingOff toff(ctx);
+    HandoffGuard handoffGuard{ctx};
+    return run_map_match(ctx, *b, strides, nullptr, matches, numMatches, nullptr, 0);
+}
+
+int ps_map_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                        const PsMapBatch *b, const PsPairResults *out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    MapStrides strides;
+    rc = check_map_batch(ctx, b, strides);
+    if (rc) return rc;
+    if (!out) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_pairs_device: null output");
+    if (b->P == 0) return PS_OK;
+    if (!out->matches || !out->numMatches || !out->inlierMask || !out->pose || !out->stats)
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_pairs_device: null output");
+    if (cfg && cfg->sampleIdx) return fail(ctx, PS_ERR_BAD_ARG, "explicit sample streams are per call, not per batch");
+    const int P = b->P, cap = b->maxMatches;
+    Plan pl;
+    rc = make_plan(ctx, params, cfg, K, cap, b->frames.maxKpts, pl);
+    if (rc) return rc;
+    begin_timed_call(ctx);
+    HandoffGuard handoffGuard{ctx}; // (prepare_score below may already queue a clearing: the guard stands before it)
+    rc = prepare_score(ctx, pl, P, cap, false, true, b->maps.desc);
+    if (rc) return rc;
+    int32_t *clamped = nullptr;
+    rc = run_map_match(ctx, *b, strides, &pl, out->matches, out->numMatches, &clamped, 0);
+    if (rc) return rc;
+    return run_ransac_stage(ctx, pl, P, cap, out->matches, clamped, cap, out->pose, out->inlierMask, out->stats, 2);
+}
+
+} // extern "C"

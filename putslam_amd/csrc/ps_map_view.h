@@ -27,7 +27,7 @@
 #include <cstdint>
 
 #include "ps_device_math.h"
-#include "putslam_hip.h"
+#include "ps_glue.h"
 
 namespace psdev {
 
@@ -287,3 +287,123 @@ __global__ __launch_bounds__(kViewBlock) void ps_frame_levels(const float *__res
 }
 
 } // namespace psdev
+
+// Host side (part of the device translation unit, ps_capi.hip): the level block, the checks and the launches
+namespace {
+
+// the level rule's constant block, uploaded once per context (the one synchronising step, like a scratch block's first growth)
+int ensure_level_block(PsContext *ctx)
+{
+    if (ctx->levelTab.p) return PS_OK;
+    static LevelBlock host; // (filled identically by every caller: psi_level_tables computes once per process)
+    if (psi_level_tables(host.t, host.pw) != PS_OK)
+        return fail(ctx, PS_ERR_UNSUPPORTED, "level thresholds: the host's log is not monotone around a switching point of ceil(log(x) / log(1.2))");
+    PS_ENSURE(ctx->levelTab, sizeof(LevelBlock));
+    hipError_t e = hipMemcpyAsync(ctx->levelTab.p, &host, sizeof(LevelBlock), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        release(ctx->levelTab);
+        return fail(ctx, PS_ERR_HIP, "level thresholds: upload", e);
+    }
+    return PS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+size_t ps_abi_sizeof_map_store(void) { return sizeof(PsMapStore); }
+size_t ps_abi_sizeof_map_view_request(void) { return sizeof(PsMapViewRequest); }
+size_t ps_abi_sizeof_map_view_out(void) { return sizeof(PsMapViewOut); }
+
+int ps_map_views_device(PsContext *ctx, const PsMapStore *store, const PsMapViewRequest *req, const PsMapViewOut *out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!store || !req || !out) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null store, request or output block");
+    if (store->numFeatures < 0 || store->numObs < 0 || store->numPoses < 0 || req->V < 0)
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: a negative count (numFeatures, numObs, numPoses, V)");
+    if (req->V == 0) return PS_OK;
+    if (!store->obsStart || (store->numFeatures > 0 && !store->pos) ||
+        (store->numObs > 0 && (!store->obsPose || !store->obsDesc || !store->obsOctave || !store->obsDetDist)))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null array in the store");
+    if (((uintptr_t)store->obsDesc & 15) != 0) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: obsDesc must be 16-byte aligned");
+    if (!req->camInv || (store->numPoses > 0 && !req->poseAngle))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null camInv or poseAngle");
+    if (req->cand && (!req->candCounts || req->candCapacity < 0))
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: a candidate list needs candCounts and candCapacity >= 0");
+    if (!out->mapLevel || !out->viewCount) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null mapLevel or viewCount");
+    FrameStrides strides;
+    rc = check_frame_set(ctx, out->views, "ps_map_views_device: output views", strides);
+    if (rc) return rc;
+    if (out->views.numFrames < req->V) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: the output set has fewer than V views");
+    const int V = req->V, slots = req->cand ? req->candCapacity : store->numFeatures;
+    const int chunks = slots > 0 ? (slots + kViewBlock - 1) / kViewBlock : 1;
+    if ((long long)V * chunks > (long long)INT_MAX)
+        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_map_views_device: V x candidate chunks exceeds the grid");
+    TimingOff toff(ctx);
+    rc = ensure_level_block(ctx);
+    if (rc) return rc;
+    const size_t groups = (size_t)V * chunks;
+    PS_ENSURE(ctx->viewChunks, groups * (kViewWaves * 8 + 4) + (size_t)V * 4);
+    HandoffGuard handoffGuard{ctx}; // (the context's scratch is in use until the launches have run)
+    ViewArgs a{};
+    a.pos = store->pos; a.obsStart = store->obsStart; a.obsPose = store->obsPose;
+    a.obsDesc = (const uint4 *)store->obsDesc; a.obsOctave = store->obsOctave; a.obsDetDist = store->obsDetDist;
+    a.numFeatures = store->numFeatures; a.numObs = store->numObs; a.numPoses = store->numPoses;
+    a.camInv = req->camInv; a.poseAngle = req->poseAngle; a.cand = req->cand; a.candCounts = req->candCounts;
+    a.maxAngle = req->maxAngle; a.fx = req->fx; a.fy = req->fy; a.cx = req->cx; a.cy = req->cy;
+    a.imageW = req->imageW; a.imageH = req->imageH;
+    a.slots = slots; a.flags = req->flags;
+    const PsFrameSet &fs = out->views;
+    a.desc = (uint4 *)fs.desc; a.pts = (float *)fs.pts; a.nkpts = (int32_t *)fs.nkpts;
+    a.maxKpts = fs.maxKpts;
+    a.descStride = strides.descUint4();
+    a.ptsStride = strides.ptsFloats();
+    a.mapLevel = out->mapLevel; a.viewCount = out->viewCount; a.featIdx = out->featIdx; a.obsIdx = out->obsIdx;
+    a.posCam = out->posCam; a.uv = out->uv; a.angle = out->angle;
+    a.levels = (const LevelBlock *)ctx->levelTab.p;
+    a.keptMask = (unsigned long long *)ctx->viewChunks.p;
+    a.chunkCount = (int32_t *)(a.keptMask + groups * kViewWaves);
+    a.bad = a.chunkCount + groups;
+    a.chunks = chunks;
+    PS_HIP(hipMemsetAsync(a.bad, 0, (size_t)V * 4, ctx->stream));
+    const dim3 grid((unsigned)groups), block(kViewBlock);
+    const bool staged = store->numPoses <= kViewAngleLds;
+    if (staged) hipLaunchKernelGGL(ps_view_select<true>, grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL(ps_view_select<false>, grid, block, 0, ctx->stream, a);
+    PS_HIP(hipGetLastError());
+    if (staged) hipLaunchKernelGGL(ps_view_emit<true>, grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL(ps_view_emit<false>, grid, block, 0, ctx->stream, a);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+int ps_frame_levels_device(PsContext *ctx, const PsFrameSet *frames, const int32_t *octave, const double *detDist, int32_t *curLevel)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!frames || !octave || !detDist || !curLevel || frames->numFrames < 0)
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_frame_levels_device: null argument or numFrames < 0");
+    if (frames->numFrames == 0) return PS_OK;
+    if (!frames->pts || !frames->nkpts || frames->maxKpts < 1)
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_frame_levels_device: null pts / nkpts or maxKpts < 1");
+    if (frames->maxKpts > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, "ps_frame_levels_device: more than PS_MAX_KPTS keypoints per frame");
+    FrameStrides strides; // (no descriptors are read: desc may be null, and its stride is not looked at)
+    rc = frame_strides(ctx, *frames, false, true, "ps_frame_levels_device", strides);
+    if (rc) return rc;
+    const int chunks = (frames->maxKpts + kViewBlock - 1) / kViewBlock;
+    if ((long long)frames->numFrames * chunks > (long long)INT_MAX)
+        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_frame_levels_device: numFrames x chunks exceeds the grid");
+    TimingOff toff(ctx);
+    rc = ensure_level_block(ctx);
+    if (rc) return rc;
+    HandoffGuard handoffGuard{ctx};
+    hipLaunchKernelGGL(ps_frame_levels, dim3((unsigned)frames->numFrames * (unsigned)chunks), dim3(kViewBlock), 0, ctx->stream,
+                       frames->pts, frames->nkpts, frames->maxKpts, strides.ptsFloats(), chunks, octave, detDist,
+                       (const LevelBlock *)ctx->levelTab.p, curLevel);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+} // extern "C"

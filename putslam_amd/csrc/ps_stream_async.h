@@ -1,6 +1,6 @@
 // ps_stream_async.h -- the PIPELINED streaming form of Matcher::match (include/putslam_hip.h: ps_vo_stream_configure_async,
-// _push_async, _push_many, _flush, _pop_many, _pop).  Included at the end of ps_capi.hip (it uses that file's PsContext,
-// PsVoStream and PS_HIP / PS_ENSURE).
+// _push_async, _push_many, _flush, _pop_many, _pop).  Included by ps_capi.hip behind ps_stream_push.h (it uses that header's
+// PsVoStream and ps_capi.hip's plan and stages).
 //
 // Call shape served: reference src/Matcher/matcher.cpp:452-516 (one frame per call, the previous frame kept as state) in the
 // loop of src/PUTSLAM/PUTSLAM.cpp:677-740.  The synchronous ps_vo_stream_push pays a copy in, four kernels, a copy out and a

@@ -1,6 +1,6 @@
 // ps_stream_push.h -- the synchronous streaming form of Matcher::match (ps_vo_stream_create / _destroy / _reset / _push,
-// include/putslam_hip.h).  Included by ps_capi.hip inside its extern "C" block; the pipelined form (ps_stream_async.h) builds on
-// the PsVoStream defined here.
+// include/putslam_hip.h).  Included by ps_capi.hip after the stages (it uses that file's Plan, run_match_stage and run_ransac_stage);
+// the pipelined form (ps_stream_async.h) builds on the PsVoStream defined here.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
@@ -50,6 +50,8 @@ struct PsVoStream {
 };
 static void async_release(PsVoStream *s); // (ps_stream_async.h)
 static int async_reset(PsVoStream *s);
+
+extern "C" {
 
 int ps_vo_stream_create(PsContext *ctx, int maxKpts, PsVoStream **out)
 {
@@ -336,3 +338,4 @@ int ps_vo_stream_push(PsVoStream *s, const PsRansacParams *params, const PsRansa
     return PS_OK;
 }
 
+} // extern "C"
