@@ -541,6 +541,93 @@ int ps_map_views_device(PsContext *ctx, const PsMapStore *store, const PsMapView
 int ps_frame_levels_device(PsContext *ctx, const PsFrameSet *frames, const int32_t *octave, const double *detDist,
                            int32_t *curLevel);
 
+/* ---- Loop-closure candidates verified in one batch from the resident store: what the loop-closure thread does per candidate
+ * (poseA, poseB) of FABMAP's priority queue -- FeaturesMap::loopClosure (src/Map/featuresMap.cpp:733-873) around
+ * Matcher::matchFeatureLoopClosure (src/Matcher/matcher.cpp:802-861) -- for L candidates as two calls, no host step.
+ *
+ * ps_pose_sets_device inverts the store: for set s with q = poses[s], "the features observed from pose q, each with the
+ * descriptor and the local 3-D point of THAT observation" (camTrajectory[q].featuresIds, a std::set<int>, featuresMap.cpp:785;
+ * ExtendedDescriptor::descriptor / point3D, matcher.cpp:816-824).
+ *   membership  feature f is a member iff one of its observations has obsPose == q; if a malformed store holds several such
+ *               observations of one feature, the first (lowest observation index) is the one that is used;
+ *   order       members appear in ascending feature index (the std::set's order);
+ *   row         desc = that observation's 32 bytes, pts = the three (float) casts of its obsPoint3D, featIdx / obsIdx (when
+ *               given) = the feature and the observation;
+ *   counts      sets.nkpts[s] = setCount[s] = the count; sets.nkpts[S] = 0 is always written (the empty set: the verifier
+ *               below parks gated candidates there);
+ *   overflow    a count above maxKpts gives setCount[s] = -(count), nkpts[s] = 0, no row of that set is written, other sets
+ *               are unaffected (the rule of viewCount / numMatches; call again with that capacity);
+ *   bad pose    poses[s] outside 0 .. numPoses-1 gives setCount[s] = INT32_MIN, nkpts[s] = 0;
+ *   bad range   THE RULE: if ANY feature of the store has an obsStart range that is not ascending inside 0 .. numObs
+ *               (obsStart[f] < 0, obsStart[f+1] < obsStart[f] or obsStart[f+1] > numObs), every one of the S sets gets
+ *               setCount = INT32_MIN, nkpts = 0 and no row is written -- a store whose index is broken is not read in part;
+ *   other ids   an observation whose pose id lies outside 0 .. numPoses-1 belongs to no set (it is not an error);
+ *   rows beyond the count are not written; the same pose may be listed twice, both sets are written.
+ * The store's observation arrays are read twice (a count and an emit pass over the features, 256 a work-group) whatever S is:
+ * a pose -> set table of numPoses ints, filled from `poses`, names the sets of each observation's pose.  No atomic decides an
+ * order; the output does not depend on which work-group ran first.
+ * S > PS_LOOP_MAX_SETS, maxKpts > PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; a NULL array where one is needed, a negative count,
+ * numFrames < S + 1, maxKpts < 1, bad strides (the rule of PsFrameSet), obsDesc not 16-byte aligned -> PS_ERR_BAD_ARG; outputs
+ * untouched.  S == 0 writes nkpts[0] = 0 and returns PS_OK.  Asynchronous on the context's stream, copies nothing, does not
+ * synchronise (growing scratch aside: 4 bytes per set and 256 features of the store, 4 bytes per pose). */
+#define PS_LOOP_MAX_SETS 1024
+typedef struct PsPoseSetRequest {     /* pointers: DEVICE */
+    const double  *obsPoint3D;        /* O x 3: ExtendedDescriptor::point3D of each observation of the store (the feature in the
+                                         observing pose's camera frame) -- the one array PsMapStore lacks */
+    const int32_t *poses;             /* S pose ids */
+    int32_t S, reserved;
+} PsPoseSetRequest;
+typedef struct PsPoseSetOut {         /* pointers: DEVICE, written by the call */
+    PsFrameSet sets;                  /* numFrames >= S + 1, maxKpts <= PS_MAX_KPTS, dense or ABI-2 strides */
+    int32_t *setCount;                /* S */
+    int32_t *featIdx, *obsIdx;        /* numFrames x maxKpts each, or NULL */
+} PsPoseSetOut;
+int ps_pose_sets_device(PsContext *ctx, const PsMapStore *store, const PsPoseSetRequest *req, const PsPoseSetOut *out);
+
+/* ps_loop_pairs_device: L candidates (pairs of SET indices) as one launch chain.
+ *  1. gate: candidate l is RUN iff both set indices lie in 0 .. S-1, both setCount are >= 0, both are
+ *     > minNumberOfFeaturesLC (strict, featuresMap.cpp:776-779) and both are >= 10 (matcher.cpp:830); otherwise its effective
+ *     pair is (S, S), the empty set;
+ *  2. the body of ps_vo_pairs_device on the effective pairs: params->errorVersion as given (the caller sets errorVersionMap,
+ *     matcher.cpp:843-844), candidate l draws from cfg->seed + l, cfg->sampleIdx must be NULL;
+ *  3. verdict: ratio[l] = 0.0 if gated (both reference gates leave 0), -1.0 if run and numMatches == 0 (:838-839), otherwise
+ *     stats.pointInlierRatio (:859); closed[l] = ratio > matchingRatioThresholdLC (featuresMap.cpp:806; a NaN ratio is never
+ *     closed); pairedRows[l] = (queryIdx, trainIdx) of the final inliers in match order (pairedFeatures, :853-857),
+ *     numPaired[l] their count, pairedFeat[l] the two featIdx entries of each; empty lists for a gated or unmatched candidate.
+ *     A candidate that names a set index outside 0 .. S-1 or a set with a negative count: numPaired = INT32_MIN, ratio = 0.0,
+ *     closed = 0.
+ * pair.* of a run candidate is byte for byte ps_match_hamming256 on the two sets followed by ps_ransac_rigid3d with seed + l;
+ * of a gated one, what ps_vo_pairs_device gives for two empty frames.
+ * NOTE: pairedRows are ROW indices into the two sets.  The reference's merge (featuresMap.cpp:824-856) compares these row
+ * indices with feature IDS (featureB.id == pairFeat.second): it works only where rows and ids coincide.  Both forms are
+ * returned; the merge itself (addMeasurements / removeFeatures) stays with the host, the store is replaced whole.
+ * Argument rules are those of ps_vo_pairs_device: NULL where an array is needed (pairedFeat without featIdx included), L < 0,
+ * S < 0, sets.numFrames < S + 1, bad strides -> PS_ERR_BAD_ARG; maxKpts > PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; L == 0 is PS_OK. */
+typedef struct PsLoopBatch {          /* pointers: DEVICE */
+    PsFrameSet sets;                  /* as ps_pose_sets_device wrote them */
+    const int32_t *setCount;          /* S */
+    const int32_t *featIdx;           /* numFrames x maxKpts, or NULL */
+    const int32_t *pairs;             /* L x 2 set indices: [0] = frameIds[0] (query / prev side), [1] = frameIds[1] */
+    int32_t L, S;
+    int32_t minNumberOfFeaturesLC;    /* featuresMap.cpp:776-779; shipped 35 */
+    int32_t reserved;
+    double matchingRatioThresholdLC;  /* :806; shipped 0.4 */
+} PsLoopBatch;
+typedef struct PsLoopResults {        /* pointers: DEVICE */
+    PsPairResults pair;               /* L rows, row capacity sets.maxKpts */
+    double  *ratio;                   /* L: what loopClosure logs as matchingRatio */
+    int32_t *closed;                  /* L: ratio > matchingRatioThresholdLC */
+    int32_t *numPaired;               /* L */
+    int32_t *pairedRows;              /* L x maxKpts x 2: pairedFeatures (matcher.cpp:853-857) */
+    int32_t *pairedFeat;              /* L x maxKpts x 2 feature indices of those rows, or NULL (needs featIdx) */
+} PsLoopResults;
+int ps_loop_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                         const PsLoopBatch *batch, const PsLoopResults *out);
+size_t ps_abi_sizeof_pose_set_request(void);
+size_t ps_abi_sizeof_pose_set_out(void);
+size_t ps_abi_sizeof_loop_batch(void);
+size_t ps_abi_sizeof_loop_results(void);
+
 /* ---- A2, for a host that loops over batches (the loop of src/PUTSLAM/PUTSLAM.cpp:677-740 around Matcher::match,
  * src/Matcher/matcher.cpp:470-515): ps_vo_pairs_device through launch chains that are never joined.
  * One context is one launch chain: a batch's matrix-core Hamming sweep, then its vector scoring stages, dependent launches with

@@ -103,6 +103,31 @@ class PsMapViewOut(C.Structure):
                 ("obsIdx", C.c_void_p), ("posCam", C.c_void_p), ("uv", C.c_void_p), ("angle", C.c_void_p)]
 
 
+# ps_pose_sets_device / ps_loop_pairs_device (include/putslam_hip.h): loop-closure candidates from the resident store
+PS_LOOP_MAX_SETS = 1024
+PS_SET_INVALID = -2 ** 31       # setCount of a set with a bad pose id (or of every set of a store with a bad range); numPaired of
+                                # a candidate that names such a set
+
+
+class PsPoseSetRequest(C.Structure):
+    _fields_ = [("obsPoint3D", C.c_void_p), ("poses", C.c_void_p), ("S", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PsPoseSetOut(C.Structure):
+    _fields_ = [("sets", PsFrameSet), ("setCount", C.c_void_p), ("featIdx", C.c_void_p), ("obsIdx", C.c_void_p)]
+
+
+class PsLoopBatch(C.Structure):
+    _fields_ = [("sets", PsFrameSet), ("setCount", C.c_void_p), ("featIdx", C.c_void_p), ("pairs", C.c_void_p),
+                ("L", C.c_int32), ("S", C.c_int32), ("minNumberOfFeaturesLC", C.c_int32), ("reserved", C.c_int32),
+                ("matchingRatioThresholdLC", C.c_double)]
+
+
+class PsLoopResults(C.Structure):
+    _fields_ = [("pair", PsPairResults), ("ratio", C.c_void_p), ("closed", C.c_void_p), ("numPaired", C.c_void_p),
+                ("pairedRows", C.c_void_p), ("pairedFeat", C.c_void_p)]
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

@@ -6,8 +6,9 @@ object is missing the import fails loudly and tells the caller how to build it.
 import ctypes as C
 import os
 
-from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsHostPairResults, PsMapBatch, PsMapStore, PsMapViewOut, PsMapViewRequest,
-                   PsPairResults, PsRansacConfig, PsRansacParams, PsRansacStats)
+from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsMapStore,
+                   PsMapViewOut, PsMapViewRequest, PsPairResults, PsPoseSetOut, PsPoseSetRequest, PsRansacConfig, PsRansacParams,
+                   PsRansacStats)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -42,6 +43,8 @@ EXPORTED = [
     "ps_exclusion_rule_too_close", "ps_exclude", "ps_exclude_device",
     "ps_level_thresholds", "ps_view_angles", "ps_map_views_device", "ps_frame_levels_device",
     "ps_abi_sizeof_map_store", "ps_abi_sizeof_map_view_request", "ps_abi_sizeof_map_view_out",
+    "ps_pose_sets_device", "ps_loop_pairs_device",
+    "ps_abi_sizeof_pose_set_request", "ps_abi_sizeof_pose_set_out", "ps_abi_sizeof_loop_batch", "ps_abi_sizeof_loop_results",
 ]
 
 _lib = None
@@ -192,6 +195,9 @@ def load_path(path):
     L.ps_view_angles.argtypes = [vp, vp, i32, vp]
     L.ps_map_views_device.argtypes = [vp, C.POINTER(PsMapStore), C.POINTER(PsMapViewRequest), C.POINTER(PsMapViewOut)]
     L.ps_frame_levels_device.argtypes = [vp, C.POINTER(PsFrameSet), vp, vp, vp]
+    L.ps_pose_sets_device.argtypes = [vp, C.POINTER(PsMapStore), C.POINTER(PsPoseSetRequest), C.POINTER(PsPoseSetOut)]
+    L.ps_loop_pairs_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsLoopBatch),
+                                       C.POINTER(PsLoopResults)]
     L.ps_batch_queue_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.ps_batch_queue_destroy.argtypes = [vp]
     L.ps_batch_queue_destroy.restype = None
@@ -213,7 +219,7 @@ def load_path(path):
     L.ps_kernel_time_totals.argtypes = [vp, vp, vp]
     L.ps_context_enable_timing.argtypes = [vp, i32]
     for n in ("dmatch", "params", "config", "stats", "frameset", "results", "host_results", "map_batch", "exclusion_rule",
-              "map_store", "map_view_request", "map_view_out"):
+              "map_store", "map_view_request", "map_view_out", "pose_set_request", "pose_set_out", "loop_batch", "loop_results"):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -224,4 +230,6 @@ def struct_sizes():
                 stats=C.sizeof(PsRansacStats), frameset=C.sizeof(PsFrameSet), results=C.sizeof(PsPairResults),
                 host_results=C.sizeof(PsHostPairResults), map_batch=C.sizeof(PsMapBatch),
                 exclusion_rule=C.sizeof(PsExclusionRule), map_store=C.sizeof(PsMapStore),
-                map_view_request=C.sizeof(PsMapViewRequest), map_view_out=C.sizeof(PsMapViewOut))
+                map_view_request=C.sizeof(PsMapViewRequest), map_view_out=C.sizeof(PsMapViewOut),
+                pose_set_request=C.sizeof(PsPoseSetRequest), pose_set_out=C.sizeof(PsPoseSetOut),
+                loop_batch=C.sizeof(PsLoopBatch), loop_results=C.sizeof(PsLoopResults))

@@ -9,8 +9,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_OK, PsExclusionRule, PsFrameSet, PsHostPairResults, PsMapBatch, PsPairResults,  # noqa: F401
-                   PsMapStore, PsMapViewOut, PsMapViewRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
+from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, PS_SET_INVALID, PsExclusionRule, PsFrameSet,  # noqa: F401
+                   PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsPairResults, PsMapStore, PsMapViewOut, PsMapViewRequest,
+                   PsPoseSetOut, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
 
 
 class PsError(RuntimeError):
@@ -431,6 +432,52 @@ class Context:
                         frames.desc_stride, frames.pts_stride)
         v = lambda p: C.c_void_p(p or None)   # noqa: E731
         self._chk(self._L.ps_frame_levels_device(self._h, C.byref(fs), v(octave_ptr), v(det_dist_ptr), v(cur_level_ptr)))
+
+    # ---- loop-closure candidates from a resident feature map ----
+    def pose_sets_device(self, store: PsMapStore, request: PsPoseSetRequest, out: PsPoseSetOut):
+        """ps_pose_sets_device on filled structs of device pointers (asynchronous): device_batch.build_pose_sets."""
+        self._chk(self._L.ps_pose_sets_device(self._h, C.byref(store), C.byref(request), C.byref(out)))
+
+    def loop_pairs_device(self, params, cfg, K, batch: PsLoopBatch, out: PsLoopResults):
+        """ps_loop_pairs_device on filled structs of device pointers (asynchronous): device_batch.run_loop_pairs."""
+        K = None if K is None else np.ascontiguousarray(K, np.float32)
+        self._chk(self._L.ps_loop_pairs_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(batch), C.byref(out)))
+
+    def verify_loop_closures(self, store, obs_point3d, candidates, params, cfg, K, min_features=35, ratio_threshold=0.4,
+                             max_kpts=None):
+        """The loop of FeaturesMap::loopClosure (featuresMap.cpp:751-806) over a whole queue of candidates as two calls on the
+        resident store (a device_batch.MapStoreDevice; obs_point3d (O, 3) float64 beside it): candidates (L, 2) POSE ids
+        ([0] = frameIds[0], the query side); the poses are made unique, ps_pose_sets_device builds one set per pose and
+        ps_loop_pairs_device verifies every candidate, candidate l drawing from cfg.seed + l; params.errorVersion is used as
+        given (the caller sets errorVersionMap).  max_kpts (default 1024) is the sets' first capacity: if a set overflows it
+        the two calls are repeated once with the largest reported count (PS_MAX_KPTS at most), the ladder's rule.
+        Returns dict(poses (S,) the unique pose ids, pairs (L, 2) set indices, set_count (S,), ratio (L,) -- matchingRatio as
+        the reference logs it: 0.0 gated, -1.0 no matches --, closed (L,) bool, num_paired (L,), paired_rows / paired_feat:
+        lists of (n, 2) arrays (rows of the two sets / feature indices), pose (L, 4, 4), stats, num_matches)."""
+        from . import device_batch
+        cand = np.ascontiguousarray(candidates, np.int32).reshape(-1, 2)
+        poses, inv = np.unique(cand.reshape(-1), return_inverse=True)
+        poses, pairs = poses.astype(np.int32), inv.reshape(-1, 2).astype(np.int32)
+        if not isinstance(obs_point3d, device_batch.torch.Tensor):     # (uploaded once, whatever the number of attempts)
+            obs_point3d = device_batch.torch.from_numpy(np.ascontiguousarray(obs_point3d, np.float64).reshape(-1, 3)).to(store.device)
+        cap = int(max_kpts) if max_kpts is not None else 1024
+        for attempt in range(2):
+            sets = device_batch.build_pose_sets(self, store, obs_point3d, poses, cap)
+            batch = device_batch.LoopBatchDevice(sets, pairs, min_features, ratio_threshold)
+            device_batch.run_loop_pairs(self, params, cfg, K, batch)
+            r = batch.download()
+            count = sets.set_count.cpu().numpy()[:len(poses)]
+            over = count[(count < 0) & (count != PS_SET_INVALID)]
+            need = min(int(-over.min()), PS_MAX_KPTS) if len(over) else 0
+            if need <= cap:
+                break
+            cap = need      # a set overflowed its rows (-(count)): once more with room for the largest
+        n = [max(int(x), 0) for x in r["numPaired"]]
+        return dict(poses=poses, pairs=pairs, set_count=count, ratio=r["ratio"].copy(), closed=r["closed"].astype(bool),
+                    num_paired=r["numPaired"].copy(), paired_rows=[r["pairedRows"][l, :n[l]].copy() for l in range(len(n))],
+                    paired_feat=[r["pairedFeat"][l, :n[l]].copy() for l in range(len(n))],
+                    pose=r["pose"].reshape(-1, 4, 4).transpose(0, 2, 1).copy(), stats=r["stats"].copy(),
+                    num_matches=r["numMatches"].copy(), max_kpts=cap)
 
     # ---- A2 / A12: device-resident batch ----
     def vo_pairs_device(self, params, cfg, K, frames: "DeviceFrames", pairs_dev_ptr, P, out: "DeviceResults"):

@@ -54,6 +54,8 @@ struct PsContext {
     Buf exFlag, exPar; // exclusion filters (ps_exclusion.h): per frame and candidate slot, the sweep's flag and the union-find's parent
     Buf viewChunks;    // map views (ps_map_view.h): per view and chunk of 256 candidate slots the kept flags and their count, per view a flag
     Buf levelTab;      // the level rule's constant block (psdev::LevelBlock), filled at the first call that needs it
+    Buf poseSets;      // pose sets (ps_loop_closure.h): the pose -> set table, its chains, and per chunk of 256 features and set a count
+    Buf loopPairs;     // loop-closure verifier (ps_loop_closure.h): the effective pairs of the gate, [L][2]
     // cached stop tables
     int tabEstimator = -1, tabH = -1, tabRN = 0, tabUN = 0, tabIter0 = 0;
     double tabMinRatio = -1.0;

@@ -7,7 +7,8 @@ import numpy as np
 import torch
 
 from . import api
-from ._abi import DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsMapStore, PsMapViewOut, PsMapViewRequest
+from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopResults, PsMapStore, PsMapViewOut,
+                   PsMapViewRequest, PsPairResults, PsPoseSetOut, PsPoseSetRequest)
 
 
 class FrameSetDevice:
@@ -463,3 +464,127 @@ def frame_levels_device(ctx, frames, octave, det_dist, use_torch_stream=True):
                      use_torch_stream)
     level.inputs = (octave, det_dist)
     return level
+
+
+class PoseSetsDevice:
+    """What ps_pose_sets_device wrote: a frame set of S + 1 frames -- set s = the features observed from poses[s], frame S the
+    empty set --, set_count (S,) and the side arrays feat_idx / obs_idx (S + 1, cap) int32 (side_arrays=False: not kept, NULL is
+    passed).  packed_stride: bytes per set of ONE block [cap x 32 B descriptors][cap x 12 B points] instead of two dense arrays."""
+
+    def __init__(self, S, max_kpts, device, packed_stride=None, side_arrays=True):
+        self.device = torch.device(device)
+        self.S, self.num_frames, self.max_kpts = int(S), int(S) + 1, int(max_kpts)
+        n, cap = self.num_frames, self.max_kpts
+        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)   # noqa: E731
+        self.stride = None if packed_stride is None else int(packed_stride)
+        if self.stride is None:
+            self.desc, self.pts = new((n, cap, 32), torch.uint8), new((n, cap, 3), torch.float32)
+        else:
+            self.blocks = new((n, self.stride), torch.uint8)
+        self.nkpts, self.set_count = new((n,), torch.int32), new((max(self.S, 1),), torch.int32)
+        self.feat_idx, self.obs_idx = (new((n, cap), torch.int32), new((n, cap), torch.int32)) if side_arrays else (None, None)
+        torch.cuda.current_stream(self.device).synchronize()   # (the fills are done before a context's stream writes)
+
+    def view(self):
+        if self.stride is None:
+            return api.DeviceFrames(self.desc.data_ptr(), self.pts.data_ptr(), self.nkpts.data_ptr(), self.num_frames, self.max_kpts)
+        base = self.blocks.data_ptr()
+        return api.DeviceFrames(base, base + self.max_kpts * 32, self.nkpts.data_ptr(), self.num_frames, self.max_kpts,
+                                self.stride, self.stride)
+
+    def frame_set(self):
+        f = self.view()
+        return api.PsFrameSet(f.desc_ptr, f.pts_ptr, f.nkpts_ptr, f.num_frames, f.max_kpts, f.desc_stride, f.pts_stride)
+
+    def out_struct(self):
+        side = (None, None) if self.feat_idx is None else (self.feat_idx.data_ptr(), self.obs_idx.data_ptr())
+        return PsPoseSetOut(self.frame_set(), self.set_count.data_ptr(), *side)
+
+    def download(self):
+        """Everything on the host (numpy); desc (S + 1, cap, 32) and pts (S + 1, cap, 3) whatever the layout."""
+        torch.cuda.synchronize(self.device)
+        cap = self.max_kpts
+        if self.stride is None:
+            desc, pts = self.desc.cpu().numpy(), self.pts.cpu().numpy()
+        else:
+            b = self.blocks.cpu().numpy()
+            desc = b[:, :cap * 32].reshape(-1, cap, 32)
+            pts = np.ascontiguousarray(b[:, cap * 32:cap * 44]).view(np.float32).reshape(-1, cap, 3)
+        out = dict(desc=desc, pts=pts, nkpts=self.nkpts.cpu().numpy(), setCount=self.set_count.cpu().numpy()[:self.S])
+        if self.feat_idx is not None:
+            out.update(featIdx=self.feat_idx.cpu().numpy(), obsIdx=self.obs_idx.cpu().numpy())
+        return out
+
+
+def build_pose_sets(ctx, store: MapStoreDevice, obs_point3d, poses, max_kpts, packed_stride=None, out=None, side_arrays=True,
+                    use_torch_stream=True):
+    """ps_pose_sets_device: the feature sets of the poses `poses` (S pose ids; numpy or a device tensor) from the resident
+    store, asynchronous, ordered like `run_map_pairs`.  obs_point3d (O, 3) float64: ExtendedDescriptor::point3D of every
+    observation of the store, passed beside it (numpy, or a device tensor that stays resident with the store).
+    Returns a PoseSetsDevice (`out`, if given, is written again)."""
+    dev = store.device
+    if not isinstance(obs_point3d, torch.Tensor):
+        obs_point3d = torch.from_numpy(np.ascontiguousarray(obs_point3d, np.float64).reshape(-1, 3)).to(dev)
+    assert obs_point3d.dtype == torch.float64 and obs_point3d.is_contiguous() and tuple(obs_point3d.shape) == (store.num_obs, 3)
+    if not isinstance(poses, torch.Tensor):
+        poses = torch.from_numpy(np.ascontiguousarray(poses, np.int32).reshape(-1)).to(dev)
+    assert poses.dtype == torch.int32 and poses.is_contiguous() and poses.dim() == 1
+    S = int(poses.shape[0])
+    if out is None:
+        out = PoseSetsDevice(S, max_kpts, dev, packed_stride, side_arrays)
+    assert out.S == S and out.max_kpts == int(max_kpts)
+    req = PsPoseSetRequest(obs_point3d.data_ptr() if store.num_obs else None, poses.data_ptr() if S else None, S, 0)
+    torch.cuda.current_stream(dev).synchronize()   # (uploads above are complete before the context's stream reads them)
+    out.inputs = (obs_point3d, poses, store)       # the request's device arrays live as long as the result
+    st, os_ = store.view(), out.out_struct()
+    _on_torch_stream(ctx, dev, lambda: ctx.pose_sets_device(st, req, os_), use_torch_stream)
+    return out
+
+
+class LoopBatchDevice:
+    """A batch of loop-closure candidates in HBM (PsLoopBatch + PsLoopResults): `sets` as build_pose_sets wrote them, pairs (L, 2)
+    of SET indices ([0] the query / prev side), the two thresholds of FeaturesMap::loopClosure, and the output block."""
+
+    def __init__(self, sets: PoseSetsDevice, pairs, min_features=35, ratio_threshold=0.4, paired_feat=True):
+        self.device, self.sets = sets.device, sets
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        self.L, self.cap = pairs.shape[0], sets.max_kpts
+        self.min_features, self.ratio_threshold = int(min_features), float(ratio_threshold)
+        L, cap = max(self.L, 1), self.cap
+        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)   # noqa: E731
+        self.pairs = torch.from_numpy(pairs).to(self.device) if self.L else new((1, 2), torch.int32)
+        self.matches, self.num_matches = new((L, cap, 16), torch.uint8), new((L,), torch.int32)
+        self.mask, self.pose = new((L, cap), torch.uint8), new((L, 16), torch.float32)
+        self.stats = new((L, STATS_DTYPE.itemsize), torch.uint8)
+        self.ratio, self.closed, self.num_paired = new((L,), torch.float64), new((L,), torch.int32), new((L,), torch.int32)
+        self.paired_rows = new((L, cap, 2), torch.int32)
+        self.paired_feat = new((L, cap, 2), torch.int32) if paired_feat else None
+        torch.cuda.current_stream(self.device).synchronize()    # (the fills are done before a chain writes: PairBatchDevice)
+
+    def batch_struct(self):
+        s = self.sets
+        return PsLoopBatch(s.frame_set(), s.set_count.data_ptr(), s.feat_idx.data_ptr() if s.feat_idx is not None else None,
+                           self.pairs.data_ptr(), self.L, s.S, self.min_features, 0, self.ratio_threshold)
+
+    def results_struct(self):
+        pr = PsPairResults(self.matches.data_ptr(), self.num_matches.data_ptr(), self.mask.data_ptr(), self.pose.data_ptr(),
+                           self.stats.data_ptr())
+        return PsLoopResults(pr, self.ratio.data_ptr(), self.closed.data_ptr(), self.num_paired.data_ptr(),
+                             self.paired_rows.data_ptr(), self.paired_feat.data_ptr() if self.paired_feat is not None else None)
+
+    def download(self):
+        torch.cuda.synchronize(self.device)
+        L, g = self.L, (lambda t: t.cpu().numpy()[:self.L])
+        out = dict(matches=self.matches.cpu().numpy().view(DMATCH_DTYPE).reshape(max(L, 1), self.cap)[:L], numMatches=g(self.num_matches),
+                   inlierMask=g(self.mask), pose=g(self.pose), stats=self.stats.cpu().numpy().view(STATS_DTYPE).reshape(-1)[:L],
+                   ratio=g(self.ratio), closed=g(self.closed), numPaired=g(self.num_paired), pairedRows=g(self.paired_rows))
+        if self.paired_feat is not None:
+            out["pairedFeat"] = g(self.paired_feat)
+        return out
+
+
+def run_loop_pairs(ctx, params, cfg, K, batch: LoopBatchDevice, use_torch_stream=True):
+    """Asynchronous: gate -> match -> RANSAC -> refit -> verdict for every candidate of the batch (ps_loop_pairs_device), ordered
+    like `run_pairs`: after the work already queued on torch's current stream, which waits for the results."""
+    b, r = batch.batch_struct(), batch.results_struct()
+    _on_torch_stream(ctx, batch.device, lambda: ctx.loop_pairs_device(params, cfg, K, b, r), use_torch_stream)
