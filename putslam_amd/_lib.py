@@ -47,6 +47,12 @@ EXPORTED = [
     "ps_abi_sizeof_pose_set_request", "ps_abi_sizeof_pose_set_out", "ps_abi_sizeof_loop_batch", "ps_abi_sizeof_loop_results",
 ]
 
+# ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
+ABI_STRUCTS = dict(dmatch=PsDMatch, params=PsRansacParams, config=PsRansacConfig, stats=PsRansacStats, frameset=PsFrameSet,
+                   results=PsPairResults, host_results=PsHostPairResults, map_batch=PsMapBatch, exclusion_rule=PsExclusionRule,
+                   map_store=PsMapStore, map_view_request=PsMapViewRequest, map_view_out=PsMapViewOut,
+                   pose_set_request=PsPoseSetRequest, pose_set_out=PsPoseSetOut, loop_batch=PsLoopBatch, loop_results=PsLoopResults)
+
 _lib = None
 _by_path = {}
 
@@ -218,18 +224,11 @@ def load_path(path):
     L.ps_last_kernel_times_ms.argtypes = [vp, vp]
     L.ps_kernel_time_totals.argtypes = [vp, vp, vp]
     L.ps_context_enable_timing.argtypes = [vp, i32]
-    for n in ("dmatch", "params", "config", "stats", "frameset", "results", "host_results", "map_batch", "exclusion_rule",
-              "map_store", "map_view_request", "map_view_out", "pose_set_request", "pose_set_out", "loop_batch", "loop_results"):
+    for n in ABI_STRUCTS:
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
 
 
 def struct_sizes():
-    return dict(dmatch=C.sizeof(PsDMatch), params=C.sizeof(PsRansacParams), config=C.sizeof(PsRansacConfig),
-                stats=C.sizeof(PsRansacStats), frameset=C.sizeof(PsFrameSet), results=C.sizeof(PsPairResults),
-                host_results=C.sizeof(PsHostPairResults), map_batch=C.sizeof(PsMapBatch),
-                exclusion_rule=C.sizeof(PsExclusionRule), map_store=C.sizeof(PsMapStore),
-                map_view_request=C.sizeof(PsMapViewRequest), map_view_out=C.sizeof(PsMapViewOut),
-                pose_set_request=C.sizeof(PsPoseSetRequest), pose_set_out=C.sizeof(PsPoseSetOut),
-                loop_batch=C.sizeof(PsLoopBatch), loop_results=C.sizeof(PsLoopResults))
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS.items()}

@@ -24,6 +24,24 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _v(ptr):
+    """A raw address as c_void_p; 0 / None: NULL."""
+    return C.c_void_p(ptr or None)
+
+
+def retry_with_reported_capacity(run, cap, limit=None):
+    """run(cap) -> (result, rows needed): the convention of the device batches, whose negative counts report the rows an
+    overflowed output wanted.  If more were needed than `cap` (at most `limit`, if given), run is repeated ONCE with that
+    many.  Returns (the last result, the capacity it ran with)."""
+    result, need = run(cap)
+    if limit is not None:
+        need = min(need, limit)
+    if need > cap:
+        cap = need
+        result, _ = run(cap)
+    return result, cap
+
+
 def dbscan_bound(eps):
     """ps_debug_dbscan_bound: the least double s* with (double)(float)sqrt(s*) >= eps (DBScan's predicate is s < s*)."""
     return float(_lib.load().ps_debug_dbscan_bound(float(eps)))
@@ -382,10 +400,9 @@ class Context:
     def exclude_device(self, rule, cand3_ptr, cand2_ptr, cand_counts_ptr, cand_capacity, exist3_ptr, exist2_ptr, exist_counts_ptr,
                        exist_capacity, frames, kept_ptr, nkept_ptr):
         """ps_exclude_device on device pointers (asynchronous on the context's stream): device_batch.exclude_device."""
-        v = lambda p: C.c_void_p(p or None)   # noqa: E731
-        self._chk(self._L.ps_exclude_device(self._h, C.byref(rule), v(cand3_ptr), v(cand2_ptr), v(cand_counts_ptr), int(cand_capacity),
-                                            v(exist3_ptr), v(exist2_ptr), v(exist_counts_ptr), int(exist_capacity), int(frames),
-                                            v(kept_ptr), v(nkept_ptr)))
+        self._chk(self._L.ps_exclude_device(self._h, C.byref(rule), _v(cand3_ptr), _v(cand2_ptr), _v(cand_counts_ptr),
+                                            int(cand_capacity), _v(exist3_ptr), _v(exist2_ptr), _v(exist_counts_ptr),
+                                            int(exist_capacity), int(frames), _v(kept_ptr), _v(nkept_ptr)))
 
     def points3Dto2D(self, xyz, K):
         xyz = np.ascontiguousarray(xyz, np.float32)
@@ -428,10 +445,8 @@ class Context:
 
     def frame_levels_device(self, frames: "DeviceFrames", octave_ptr, det_dist_ptr, cur_level_ptr):
         """ps_frame_levels_device: predicted levels of the keypoints of a device-resident frame set (asynchronous)."""
-        fs = PsFrameSet(frames.desc_ptr, frames.pts_ptr, frames.nkpts_ptr, frames.num_frames, frames.max_kpts,
-                        frames.desc_stride, frames.pts_stride)
-        v = lambda p: C.c_void_p(p or None)   # noqa: E731
-        self._chk(self._L.ps_frame_levels_device(self._h, C.byref(fs), v(octave_ptr), v(det_dist_ptr), v(cur_level_ptr)))
+        fs = frames.struct()
+        self._chk(self._L.ps_frame_levels_device(self._h, C.byref(fs), _v(octave_ptr), _v(det_dist_ptr), _v(cur_level_ptr)))
 
     # ---- loop-closure candidates from a resident feature map ----
     def pose_sets_device(self, store: PsMapStore, request: PsPoseSetRequest, out: PsPoseSetOut):
@@ -458,20 +473,19 @@ class Context:
         cand = np.ascontiguousarray(candidates, np.int32).reshape(-1, 2)
         poses, inv = np.unique(cand.reshape(-1), return_inverse=True)
         poses, pairs = poses.astype(np.int32), inv.reshape(-1, 2).astype(np.int32)
-        if not isinstance(obs_point3d, device_batch.torch.Tensor):     # (uploaded once, whatever the number of attempts)
-            obs_point3d = device_batch.torch.from_numpy(np.ascontiguousarray(obs_point3d, np.float64).reshape(-1, 3)).to(store.device)
-        cap = int(max_kpts) if max_kpts is not None else 1024
-        for attempt in range(2):
+        # (uploaded once, whatever the number of attempts)
+        obs_point3d = device_batch.to_device_tensor(obs_point3d, device_batch.torch.float64, store.device, (-1, 3))
+
+        def run(cap):
             sets = device_batch.build_pose_sets(self, store, obs_point3d, poses, cap)
             batch = device_batch.LoopBatchDevice(sets, pairs, min_features, ratio_threshold)
             device_batch.run_loop_pairs(self, params, cfg, K, batch)
             r = batch.download()
             count = sets.set_count.cpu().numpy()[:len(poses)]
-            over = count[(count < 0) & (count != PS_SET_INVALID)]
-            need = min(int(-over.min()), PS_MAX_KPTS) if len(over) else 0
-            if need <= cap:
-                break
-            cap = need      # a set overflowed its rows (-(count)): once more with room for the largest
+            over = count[(count < 0) & (count != PS_SET_INVALID)]     # a set overflowed its rows: -(count)
+            return (r, count), int(-over.min()) if len(over) else 0
+
+        (r, count), cap = retry_with_reported_capacity(run, int(max_kpts) if max_kpts is not None else 1024, PS_MAX_KPTS)
         n = [max(int(x), 0) for x in r["numPaired"]]
         return dict(poses=poses, pairs=pairs, set_count=count, ratio=r["ratio"].copy(), closed=r["closed"].astype(bool),
                     num_paired=r["numPaired"].copy(), paired_rows=[r["pairedRows"][l, :n[l]].copy() for l in range(len(n))],
@@ -482,35 +496,20 @@ class Context:
     # ---- A2 / A12: device-resident batch ----
     def vo_pairs_device(self, params, cfg, K, frames: "DeviceFrames", pairs_dev_ptr, P, out: "DeviceResults"):
         K = np.ascontiguousarray(K, np.float32)
-        fs = PsFrameSet(frames.desc_ptr, frames.pts_ptr, frames.nkpts_ptr, frames.num_frames, frames.max_kpts,
-                        frames.desc_stride, frames.pts_stride)
-        res = PsPairResults(out.matches_ptr, out.num_matches_ptr, out.mask_ptr, out.pose_ptr, out.stats_ptr)
+        fs, res = frames.struct(), out.struct()
         self._chk(self._L.ps_vo_pairs_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(fs),
                                              C.c_void_p(pairs_dev_ptr), int(P), C.byref(res)))
 
     # ---- N2, device-resident batch ----
-    def _map_batch(self, b: "DeviceMapBatch"):
-        mb = PsMapBatch()
-        for dst, f in ((mb.maps, b.maps), (mb.frames, b.frames)):
-            dst.desc, dst.pts, dst.nkpts = f.desc_ptr, f.pts_ptr, f.nkpts_ptr
-            dst.numFrames, dst.maxKpts = f.num_frames, f.max_kpts
-            dst.descFrameStride, dst.ptsFrameStride = f.desc_stride, f.pts_stride
-        mb.mapLevel, mb.curLevel, mb.pairs = b.map_level_ptr, b.cur_level_ptr, b.pairs_ptr
-        mb.P, mb.maxMatches = b.P, b.max_matches
-        mb.radiusBound, mb.acceptRatio = b.radius_bound, b.accept_ratio
-        mb.radiusBoundPerPair, mb.acceptRatioPerPair = b.radius_bound_per_pair_ptr, b.accept_ratio_per_pair_ptr
-        return mb
-
     def match_xyz_device(self, batch: "DeviceMapBatch", matches_ptr, num_matches_ptr):
         """ps_match_xyz_device: the guided matching of every pair of the batch; asynchronous, device pointers."""
-        mb = self._map_batch(batch)
+        mb = batch.struct()
         self._chk(self._L.ps_match_xyz_device(self._h, C.byref(mb), C.c_void_p(matches_ptr), C.c_void_p(num_matches_ptr)))
 
     def map_pairs_device(self, params, cfg, K, batch: "DeviceMapBatch", out: "DeviceResults"):
         """ps_map_pairs_device: guided matching + the estimator for every pair; asynchronous, device pointers."""
         K = None if K is None else np.ascontiguousarray(K, np.float32)
-        mb = self._map_batch(batch)
-        res = PsPairResults(out.matches_ptr, out.num_matches_ptr, out.mask_ptr, out.pose_ptr, out.stats_ptr)
+        mb, res = batch.struct(), out.struct()
         self._chk(self._L.ps_map_pairs_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(mb), C.byref(res)))
 
     def match_xyz_ladder(self, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, params, cfg, K, radius=0.12,
@@ -542,16 +541,16 @@ class Context:
         views, mlv = side(map_desc, map_pos, map_level, nmap)
         frames, clv = side(cur_desc, cur_pos, cur_level, ncur)
         tries = [ladder_try(float(radius), float(ratio), k) for k in range(1, int(max_tries) + 1)]
-        cap = int(max_matches) if max_matches is not None else max(1, 4 * nmap)
-        for attempt in range(2):
+
+        def run(cap):
             batch = device_batch.MapBatchDevice(views, mlv, frames, clv, np.zeros((len(tries), 2), np.int32), cap,
                                                 radius=[t[0] for t in tries], ratio=[t[1] for t in tries])
             device_batch.run_map_pairs(self, params, cfg, K, batch)
             r = batch.download()
-            need = int(-r["numMatches"].min()) if len(tries) else 0
-            if need <= cap:
-                break
-            cap = need      # a try overflowed its rows (-(count)): once more with room for the largest, as the loop would see it
+            # (a try that overflowed its rows reports -(count): the repeat has room for the largest, as the loop would see it)
+            return r, int(-r["numMatches"].min()) if len(tries) else 0
+
+        r, _ = retry_with_reported_capacity(run, int(max_matches) if max_matches is not None else max(1, 4 * nmap))
         ratios = [float(x) for x in r["stats"]["pointInlierRatio"]]
         k = ladder_pick(ratios, min_ratio)
         n = max(int(r["numMatches"][k]), 0)
@@ -601,9 +600,7 @@ class BatchQueue:
     def submit(self, params, cfg, K, frames: "DeviceFrames", pairs_dev_ptr, P, out: "DeviceResults"):
         """Asynchronous; returns the batch's ticket."""
         K = np.ascontiguousarray(K, np.float32)
-        fs = PsFrameSet(frames.desc_ptr, frames.pts_ptr, frames.nkpts_ptr, frames.num_frames, frames.max_kpts,
-                        frames.desc_stride, frames.pts_stride)
-        res = PsPairResults(out.matches_ptr, out.num_matches_ptr, out.mask_ptr, out.pose_ptr, out.stats_ptr)
+        fs, res = frames.struct(), out.struct()
         t = C.c_int64(-1)
         self._ctx._chk(self._ctx._L.ps_batch_queue_submit(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(fs),
                                                           C.c_void_p(pairs_dev_ptr), int(P), C.byref(res), C.byref(t)))
@@ -812,6 +809,10 @@ class DeviceFrames:
         self.num_frames, self.max_kpts = int(num_frames), int(max_kpts)
         self.desc_stride, self.pts_stride = int(desc_stride), int(pts_stride)      # bytes between frames; 0 = dense
 
+    def struct(self):
+        return PsFrameSet(self.desc_ptr, self.pts_ptr, self.nkpts_ptr, self.num_frames, self.max_kpts, self.desc_stride,
+                          self.pts_stride)
+
 
 class DeviceResults:
     """Raw device pointers of per-pair outputs (PsPairResults)."""
@@ -819,6 +820,9 @@ class DeviceResults:
     def __init__(self, matches_ptr, num_matches_ptr, mask_ptr, pose_ptr, stats_ptr):
         self.matches_ptr, self.num_matches_ptr, self.mask_ptr = matches_ptr, num_matches_ptr, mask_ptr
         self.pose_ptr, self.stats_ptr = pose_ptr, stats_ptr
+
+    def struct(self):
+        return PsPairResults(self.matches_ptr, self.num_matches_ptr, self.mask_ptr, self.pose_ptr, self.stats_ptr)
 
 
 class DeviceMapBatch:
@@ -831,6 +835,11 @@ class DeviceMapBatch:
         self.P, self.max_matches = int(P), int(max_matches)
         self.radius_bound, self.accept_ratio = float(radius_bound), float(accept_ratio)
         self.radius_bound_per_pair_ptr, self.accept_ratio_per_pair_ptr = radius_bound_per_pair_ptr, accept_ratio_per_pair_ptr
+
+    def struct(self):
+        return PsMapBatch(self.maps.struct(), self.map_level_ptr, self.frames.struct(), self.cur_level_ptr, self.pairs_ptr,
+                          self.P, self.max_matches, self.radius_bound, self.accept_ratio, self.radius_bound_per_pair_ptr,
+                          self.accept_ratio_per_pair_ptr)
 
 
 def kernel_names():

@@ -8,26 +8,24 @@ import torch
 
 from . import api
 from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopResults, PsMapStore, PsMapViewOut,
-                   PsMapViewRequest, PsPairResults, PsPoseSetOut, PsPoseSetRequest)
+                   PsMapViewRequest, PsPoseSetOut, PsPoseSetRequest, make_config)
 
 
-class FrameSetDevice:
-    """desc (F,cap,32) u8, pts (F,cap,3) f32, nkpts (F,) i32 resident in HBM."""
+_NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
 
-    def __init__(self, desc, pts, nkpts, device="cuda:0"):
-        desc = np.ascontiguousarray(desc, np.uint8)
-        pts = np.ascontiguousarray(pts, np.float32)
-        nkpts = np.ascontiguousarray(nkpts, np.int32)
-        assert desc.ndim == 3 and desc.shape[2] == 32 and pts.shape == desc.shape[:2] + (3,)
-        self.device = torch.device(device)
-        self.desc = torch.from_numpy(desc).to(self.device)
-        self.pts = torch.from_numpy(pts).to(self.device)
-        self.nkpts = torch.from_numpy(nkpts).to(self.device)
-        self.num_frames, self.max_kpts = desc.shape[0], desc.shape[1]
 
-    def view(self):
-        return api.DeviceFrames(self.desc.data_ptr(), self.pts.data_ptr(), self.nkpts.data_ptr(), self.num_frames,
-                                self.max_kpts)
+def to_device_tensor(a, dtype, device, shape=None):
+    """A contiguous tensor of `dtype` on `device`: a numpy array (or sequence) is converted, reshaped to `shape` if given, and
+    uploaded; a device tensor is checked and used where it lies."""
+    if isinstance(a, torch.Tensor):
+        assert a.dtype == dtype and a.is_contiguous() and a.device == device
+        return a
+    a = np.ascontiguousarray(a, _NUMPY_OF[dtype])
+    return torch.from_numpy(a if shape is None else a.reshape(shape)).to(device)
+
+
+def _zeros(device, shape, dtype):
+    return torch.zeros(shape, dtype=dtype, device=device)
 
 
 def pack_frames(desc, pts, stride=None):
@@ -41,7 +39,63 @@ def pack_frames(desc, pts, stride=None):
     return out
 
 
-class PackedFrameSetDevice:
+def unpack_frames(blocks, cap):
+    """pack_frames' inverse: (F, stride) u8 -> desc (F, cap, 32) u8, pts (F, cap, 3) f32."""
+    desc = blocks[:, :cap * 32].reshape(-1, cap, 32)
+    return desc, np.ascontiguousarray(blocks[:, cap * 32:cap * 44]).view(np.float32).reshape(-1, cap, 3)
+
+
+class FrameSet:
+    """desc + pts + nkpts (num_frames,) i32 of num_frames frames of capacity max_kpts in HBM.  stride None: dense, desc
+    (F, cap, 32) u8 and pts (F, cap, 3) f32; else packed, blocks (F, stride) u8 as pack_frames lays them out (PsFrameSet strides).
+    The subclasses fill it: FrameSetDevice / PackedFrameSetDevice upload, MapViewsDevice / PoseSetsDevice are written by the library."""
+
+    stride = None
+
+    def _zero_frames(self, n, packed_stride):
+        """n zero-filled frames in the layout `packed_stride` asks for (None: dense)."""
+        cap, dev = self.max_kpts, self.device
+        self.stride = None if packed_stride is None else int(packed_stride)
+        if self.stride is None:
+            self.desc, self.pts = _zeros(dev, (n, cap, 32), torch.uint8), _zeros(dev, (n, cap, 3), torch.float32)
+        else:
+            self.blocks = _zeros(dev, (n, self.stride), torch.uint8)
+        self.nkpts = _zeros(dev, (n,), torch.int32)
+
+    def view(self):
+        if self.stride is None:
+            return api.DeviceFrames(self.desc.data_ptr(), self.pts.data_ptr(), self.nkpts.data_ptr(), self.num_frames,
+                                    self.max_kpts)
+        base = self.blocks.data_ptr()
+        return api.DeviceFrames(base, base + self.max_kpts * 32, self.nkpts.data_ptr(), self.num_frames, self.max_kpts,
+                                self.stride, self.stride)
+
+    def frame_set(self):
+        return self.view().struct()
+
+    def download_frames(self):
+        """(desc (F, cap, 32), pts (F, cap, 3)) on the host (numpy) whatever the layout."""
+        if self.stride is None:
+            return self.desc.cpu().numpy(), self.pts.cpu().numpy()
+        return unpack_frames(self.blocks.cpu().numpy(), self.max_kpts)
+
+
+class FrameSetDevice(FrameSet):
+    """desc (F,cap,32) u8, pts (F,cap,3) f32, nkpts (F,) i32 resident in HBM."""
+
+    def __init__(self, desc, pts, nkpts, device="cuda:0"):
+        desc = np.ascontiguousarray(desc, np.uint8)
+        pts = np.ascontiguousarray(pts, np.float32)
+        nkpts = np.ascontiguousarray(nkpts, np.int32)
+        assert desc.ndim == 3 and desc.shape[2] == 32 and pts.shape == desc.shape[:2] + (3,)
+        self.device = torch.device(device)
+        self.desc = torch.from_numpy(desc).to(self.device)
+        self.pts = torch.from_numpy(pts).to(self.device)
+        self.nkpts = torch.from_numpy(nkpts).to(self.device)
+        self.num_frames, self.max_kpts = desc.shape[0], desc.shape[1]
+
+
+class PackedFrameSetDevice(FrameSet):
     """The same frames as FrameSetDevice with every frame's descriptors and points in ONE block (PsFrameSet strides, ABI 2)."""
 
     def __init__(self, desc, pts, nkpts, device="cuda:0", stride=None):
@@ -52,21 +106,15 @@ class PackedFrameSetDevice:
         self.blocks = torch.from_numpy(packed).to(self.device)
         self.nkpts = torch.from_numpy(np.ascontiguousarray(nkpts, np.int32)).to(self.device)
 
-    def view(self):
-        base = self.blocks.data_ptr()
-        return api.DeviceFrames(base, base + self.max_kpts * 32, self.nkpts.data_ptr(), self.num_frames, self.max_kpts,
-                                self.stride, self.stride)
 
+class PairResultsDevice:
+    """The per-pair output block in HBM (PsPairResults) for P pairs of `cap` rows: matches (P, cap, 16) u8, num_matches (P,)
+    i32, mask (P, cap) u8, pose (P, 16) f32, stats (P, sizeof PsRansacStats) u8.  A subclass uploads and fills what else it
+    needs first and calls this constructor last: every block is ready when it returns."""
 
-class PairBatchDevice:
-    """Pairs (P,2) i32 and the per-pair outputs, all in HBM."""
-
-    def __init__(self, pairs, max_kpts, device="cuda:0"):
-        pairs = np.ascontiguousarray(pairs, np.int32)
+    def __init__(self, P, cap, device):
         self.device = torch.device(device)
-        self.P = pairs.shape[0]
-        self.cap = int(max_kpts)
-        self.pairs = torch.from_numpy(pairs).to(self.device)
+        self.P, self.cap = int(P), int(cap)
         P, cap = max(self.P, 1), self.cap
         self.matches = torch.zeros((P, cap, 16), dtype=torch.uint8, device=self.device)
         self.num_matches = torch.zeros(P, dtype=torch.int32, device=self.device)
@@ -78,9 +126,12 @@ class PairBatchDevice:
         # fuzz on batches of three pairs).  The blocks are ready when the constructor returns.
         torch.cuda.current_stream(self.device).synchronize()
 
-    def view(self):
-        return api.DeviceResults(self.matches.data_ptr(), self.num_matches.data_ptr(), self.mask.data_ptr(),
-                                 self.pose.data_ptr(), self.stats.data_ptr())
+    def view(self, lo=0):
+        """DeviceResults of the rows from pair `lo` on."""
+        m, n, k, p, s = self.matches, self.num_matches, self.mask, self.pose, self.stats
+        if lo:
+            m, n, k, p, s = m[lo:], n[lo:], k[lo:], p[lo:], s[lo:]
+        return api.DeviceResults(m.data_ptr(), n.data_ptr(), k.data_ptr(), p.data_ptr(), s.data_ptr())
 
     def download(self):
         torch.cuda.synchronize(self.device)
@@ -90,6 +141,15 @@ class PairBatchDevice:
                     inlierMask=self.mask.cpu().numpy()[:P],
                     pose=self.pose.cpu().numpy()[:P],
                     stats=self.stats.cpu().numpy().view(STATS_DTYPE).reshape(-1)[:P])
+
+
+class PairBatchDevice(PairResultsDevice):
+    """Pairs (P,2) i32 and the per-pair outputs, all in HBM."""
+
+    def __init__(self, pairs, max_kpts, device="cuda:0"):
+        pairs = np.ascontiguousarray(pairs, np.int32)
+        self.pairs = torch.from_numpy(pairs).to(torch.device(device))
+        super().__init__(pairs.shape[0], max_kpts, device)
 
 
 _SIDE_STREAMS = {}
@@ -105,22 +165,31 @@ def _work_stream(device):
     return _SIDE_STREAMS[key]
 
 
+def _on_torch_stream(ctx, device, call, use_torch_stream=True):
+    """call() -- one or more calls of `ctx` -- ordered after the work already queued on torch's current stream of `device`, which
+    waits for what they queue (`_work_stream`: the default stream hands over through the side stream).  use_torch_stream=False:
+    on whatever stream the context has."""
+    if not use_torch_stream:
+        call()
+        return
+    cur = torch.cuda.current_stream(device)
+    if cur.cuda_stream != 0:
+        ctx.set_stream(cur.cuda_stream)
+        call()
+        return
+    st = _work_stream(device)
+    st.wait_stream(cur)
+    ctx.set_stream(st.cuda_stream)
+    call()
+    cur.wait_stream(st)
+
+
 def run_pairs(ctx, params, cfg, K, frames: FrameSetDevice, batch: PairBatchDevice, use_torch_stream=True):
     """Asynchronous: match -> cross-check -> RANSAC -> refit for every pair of the batch, ordered after the work
     already queued on torch's current stream; the current stream waits for the results."""
-    if not use_torch_stream:
-        ctx.vo_pairs_device(params, cfg, K, frames.view(), batch.pairs.data_ptr(), batch.P, batch.view())
-        return
-    cur = torch.cuda.current_stream(frames.device)
-    if cur.cuda_stream != 0:
-        ctx.set_stream(cur.cuda_stream)
-        ctx.vo_pairs_device(params, cfg, K, frames.view(), batch.pairs.data_ptr(), batch.P, batch.view())
-        return
-    st = _work_stream(frames.device)
-    st.wait_stream(cur)
-    ctx.set_stream(st.cuda_stream)
-    ctx.vo_pairs_device(params, cfg, K, frames.view(), batch.pairs.data_ptr(), batch.P, batch.view())
-    cur.wait_stream(st)
+    _on_torch_stream(ctx, frames.device,
+                     lambda: ctx.vo_pairs_device(params, cfg, K, frames.view(), batch.pairs.data_ptr(), batch.P, batch.view()),
+                     use_torch_stream)
 
 
 def run_pairs_split(ctxs, streams, params, estimator, num_hypotheses, seed, K, frames: FrameSetDevice,
@@ -131,8 +200,6 @@ def run_pairs_split(ctxs, streams, params, estimator, num_hypotheses, seed, K, f
     join=True: every stream first waits for the current stream and the current stream waits for all of them at the
     end (the call is then ordered like `run_pairs`).  join=False: the sub-batch chains are only ordered within their
     own stream -- consecutive calls pipeline into each other and the caller synchronises before reading results."""
-    from . import api
-    from ._abi import make_config
     S = len(ctxs)
     assert len(streams) >= S and all(st.cuda_stream != 0 for st in streams[:S])
     P = batch.P
@@ -144,7 +211,7 @@ def run_pairs_split(ctxs, streams, params, estimator, num_hypotheses, seed, K, f
     if join:
         for st in streams[:S]:
             st.wait_stream(cur)
-    keep = []
+    fv, keep = frames.view(), []
     for i in range(S):
         lo, hi = bounds[i], bounds[i + 1]
         if hi <= lo:
@@ -152,9 +219,7 @@ def run_pairs_split(ctxs, streams, params, estimator, num_hypotheses, seed, K, f
         ctxs[i].set_stream(streams[i].cuda_stream)
         ci, k = make_config(estimator, num_hypotheses, seed=seed + lo)
         keep.append(k)
-        view = api.DeviceResults(batch.matches[lo:].data_ptr(), batch.num_matches[lo:].data_ptr(),
-                                 batch.mask[lo:].data_ptr(), batch.pose[lo:].data_ptr(), batch.stats[lo:].data_ptr())
-        ctxs[i].vo_pairs_device(params, ci, K, frames.view(), batch.pairs[lo:].data_ptr(), hi - lo, view)
+        ctxs[i].vo_pairs_device(params, ci, K, fv, batch.pairs[lo:].data_ptr(), hi - lo, batch.view(lo))
     if join:
         for st in streams[:S]:
             cur.wait_stream(st)
@@ -181,16 +246,7 @@ def dbscan_thin_device(ctx, xy, counts, octave=None, eps=10.0, min_pts=2, featur
     nkept = torch.empty((F,), dtype=torch.int32, device=xy.device)
     args = (xy.data_ptr(), octave.data_ptr() if octave is not None else 0, counts.data_ptr(), F, cap, kept.data_ptr(),
             nkept.data_ptr(), eps, min_pts, features_from_cluster)
-    cur = torch.cuda.current_stream(xy.device)   # ordered like run_pairs: after torch's queued work, before its later work
-    if cur.cuda_stream != 0:
-        ctx.set_stream(cur.cuda_stream)
-        ctx.dbscan_thin_device(*args)
-        return kept, nkept
-    st = _work_stream(xy.device)
-    st.wait_stream(cur)
-    ctx.set_stream(st.cuda_stream)
-    ctx.dbscan_thin_device(*args)
-    cur.wait_stream(st)
+    _on_torch_stream(ctx, xy.device, lambda: ctx.dbscan_thin_device(*args))   # ordered like run_pairs
     return kept, nkept
 
 
@@ -215,20 +271,11 @@ def exclude_device(ctx, rule, cand3, cand2, cand_counts, exist3=None, exist2=Non
     ptr = lambda t: t.data_ptr() if t is not None else 0   # noqa: E731
     args = (rule, ptr(cand3), ptr(cand2), cand_counts.data_ptr(), cap, ptr(exist3) if ecap else 0, ptr(exist2) if ecap else 0,
             exist_counts.data_ptr() if ecap else 0, ecap, F, kept.data_ptr(), nkept.data_ptr())
-    cur = torch.cuda.current_stream(lead.device)   # ordered like dbscan_thin_device
-    if cur.cuda_stream != 0:
-        ctx.set_stream(cur.cuda_stream)
-        ctx.exclude_device(*args)
-        return kept, nkept
-    st = _work_stream(lead.device)
-    st.wait_stream(cur)
-    ctx.set_stream(st.cuda_stream)
-    ctx.exclude_device(*args)
-    cur.wait_stream(st)
+    _on_torch_stream(ctx, lead.device, lambda: ctx.exclude_device(*args))   # ordered like run_pairs
     return kept, nkept
 
 
-class MapBatchDevice:
+class MapBatchDevice(PairResultsDevice):
     """A map-matching batch in HBM (PsMapBatch): the map views and frames (FrameSetDevice / PackedFrameSetDevice), their levels
     (views x maxKpts / frames x maxKpts int32), pairs (P, 2) of (map view, frame), the sphere radius and accept ratio -- scalars, or
     sequences of P for per-pair values -- and the output block with `max_matches` rows per pair."""
@@ -237,7 +284,7 @@ class MapBatchDevice:
         self.device = torch.device(device) if device is not None else maps.device
         self.maps, self.frames = maps, frames
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        self.P, self.cap = pairs.shape[0], int(max_matches)
+        self.P = pairs.shape[0]
         self.map_level = self._levels(map_level, maps)
         self.cur_level = self._levels(cur_level, frames)
         self.pairs = torch.from_numpy(pairs).to(self.device)
@@ -253,24 +300,14 @@ class MapBatchDevice:
         else:
             assert len(ratio) == self.P
             self.ratio_per = torch.from_numpy(np.array(ratio, np.float64)).to(self.device)
-        P, cap = max(self.P, 1), self.cap
-        self.matches = torch.zeros((P, cap, 16), dtype=torch.uint8, device=self.device)
-        self.num_matches = torch.zeros(P, dtype=torch.int32, device=self.device)
-        self.mask = torch.zeros((P, cap), dtype=torch.uint8, device=self.device)
-        self.pose = torch.zeros((P, 16), dtype=torch.float32, device=self.device)
-        self.stats = torch.zeros((P, STATS_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
-        torch.cuda.current_stream(self.device).synchronize()    # (the fills are done before a chain writes: PairBatchDevice)
+        super().__init__(self.P, max_matches, self.device)
 
     def _levels(self, level, fs):
         """Levels of a frame set: a numpy array is uploaded; a device tensor (build_map_views' / frame_levels_device's
         output) is used where it lies."""
-        if isinstance(level, torch.Tensor):
-            assert level.dtype == torch.int32 and level.is_contiguous() and level.device == self.device
-            assert tuple(level.shape) == (fs.num_frames, fs.max_kpts)
-            return level
-        level = np.ascontiguousarray(level, np.int32)
-        assert level.shape == (fs.num_frames, fs.max_kpts)
-        return torch.from_numpy(level).to(self.device)
+        level = to_device_tensor(level, torch.int32, self.device)
+        assert tuple(level.shape) == (fs.num_frames, fs.max_kpts)
+        return level
 
     def batch_view(self, lo=0, hi=None):
         """PsMapBatch of pairs [lo, hi)."""
@@ -280,35 +317,6 @@ class MapBatchDevice:
                                   self.radius_bound, self.accept_ratio,
                                   self.radius_per[lo:].data_ptr() if self.radius_per is not None else None,
                                   self.ratio_per[lo:].data_ptr() if self.ratio_per is not None else None)
-
-    def view(self, lo=0):
-        return api.DeviceResults(self.matches[lo:].data_ptr(), self.num_matches[lo:].data_ptr(), self.mask[lo:].data_ptr(),
-                                 self.pose[lo:].data_ptr(), self.stats[lo:].data_ptr())
-
-    def download(self):
-        torch.cuda.synchronize(self.device)
-        P = self.P
-        return dict(matches=self.matches.cpu().numpy().view(DMATCH_DTYPE).reshape(max(P, 1), self.cap)[:P],
-                    numMatches=self.num_matches.cpu().numpy()[:P],
-                    inlierMask=self.mask.cpu().numpy()[:P],
-                    pose=self.pose.cpu().numpy()[:P],
-                    stats=self.stats.cpu().numpy().view(STATS_DTYPE).reshape(-1)[:P])
-
-
-def _on_torch_stream(ctx, device, call, use_torch_stream):
-    if not use_torch_stream:
-        call()
-        return
-    cur = torch.cuda.current_stream(device)
-    if cur.cuda_stream != 0:
-        ctx.set_stream(cur.cuda_stream)
-        call()
-        return
-    st = _work_stream(device)
-    st.wait_stream(cur)
-    ctx.set_stream(st.cuda_stream)
-    call()
-    cur.wait_stream(st)
 
 
 def run_map_pairs(ctx, params, cfg, K, batch: MapBatchDevice, use_torch_stream=True):
@@ -352,7 +360,7 @@ class MapStoreDevice:
                           self.num_poses, 0)
 
 
-class MapViewsDevice:
+class MapViewsDevice(FrameSet):
     """What ps_map_views_device wrote: a frame set (desc / pts / nkpts; usable as MapBatchDevice.maps), map_level (V, cap) int32
     for MapBatchDevice's map_level, view_count (V,) and the side arrays feat_idx / obs_idx (V, cap) int32, pos_cam (V, cap, 3),
     uv (V, cap, 2), angle (V, cap) float64 -- device tensors.  packed_stride: bytes per view of ONE block
@@ -362,40 +370,22 @@ class MapViewsDevice:
         self.device = torch.device(device)
         self.num_frames, self.max_kpts = int(V), int(max_kpts)
         n, cap = max(self.num_frames, 1), self.max_kpts
-        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)   # noqa: E731
-        self.stride = None if packed_stride is None else int(packed_stride)
-        if self.stride is None:
-            self.desc, self.pts = new((n, cap, 32), torch.uint8), new((n, cap, 3), torch.float32)
-        else:
-            self.blocks = new((n, self.stride), torch.uint8)
-        self.nkpts, self.view_count = new((n,), torch.int32), new((n,), torch.int32)
+        new = lambda shape, dt: _zeros(self.device, shape, dt)   # noqa: E731
+        self._zero_frames(n, packed_stride)
+        self.view_count = new((n,), torch.int32)
         self.map_level, self.feat_idx, self.obs_idx = (new((n, cap), torch.int32) for _ in range(3))
         self.pos_cam, self.uv, self.angle = new((n, cap, 3), torch.float64), new((n, cap, 2), torch.float64), new((n, cap), torch.float64)
         torch.cuda.current_stream(self.device).synchronize()   # (the fills are done before a context's stream writes)
 
-    def view(self):
-        if self.stride is None:
-            return api.DeviceFrames(self.desc.data_ptr(), self.pts.data_ptr(), self.nkpts.data_ptr(), self.num_frames, self.max_kpts)
-        base = self.blocks.data_ptr()
-        return api.DeviceFrames(base, base + self.max_kpts * 32, self.nkpts.data_ptr(), self.num_frames, self.max_kpts,
-                                self.stride, self.stride)
-
     def out_struct(self):
-        f = self.view()
-        return PsMapViewOut(api.PsFrameSet(f.desc_ptr, f.pts_ptr, f.nkpts_ptr, f.num_frames, f.max_kpts, f.desc_stride, f.pts_stride),
-                            self.map_level.data_ptr(), self.view_count.data_ptr(), self.feat_idx.data_ptr(), self.obs_idx.data_ptr(),
-                            self.pos_cam.data_ptr(), self.uv.data_ptr(), self.angle.data_ptr())
+        return PsMapViewOut(self.frame_set(), self.map_level.data_ptr(), self.view_count.data_ptr(), self.feat_idx.data_ptr(),
+                            self.obs_idx.data_ptr(), self.pos_cam.data_ptr(), self.uv.data_ptr(), self.angle.data_ptr())
 
     def download(self):
         """Everything on the host (numpy); desc (V, cap, 32) and pts (V, cap, 3) whatever the layout."""
         torch.cuda.synchronize(self.device)
-        V, cap = self.num_frames, self.max_kpts
-        if self.stride is None:
-            desc, pts = self.desc.cpu().numpy(), self.pts.cpu().numpy()
-        else:
-            b = self.blocks.cpu().numpy()
-            desc = b[:, :cap * 32].reshape(-1, cap, 32)
-            pts = np.ascontiguousarray(b[:, cap * 32:cap * 44]).view(np.float32).reshape(-1, cap, 3)
+        V = self.num_frames
+        desc, pts = self.download_frames()
         g = lambda t: t.cpu().numpy()[:V]   # noqa: E731
         return dict(desc=desc[:V], pts=pts[:V], nkpts=g(self.nkpts), viewCount=g(self.view_count), mapLevel=g(self.map_level),
                     featIdx=g(self.feat_idx), obsIdx=g(self.obs_idx), posCam=g(self.pos_cam), uv=g(self.uv), angle=g(self.angle))
@@ -409,25 +399,17 @@ def build_map_views(ctx, store: MapStoreDevice, cam_inv, pose_angle, max_angle, 
     cand (V, cap) int32 + cand_counts (V,) (numpy or device tensors), or None = every feature of the store in index order.
     Returns a MapViewsDevice (`out`, if given, is written again: a retry with the reported capacity allocates a new one)."""
     dev = store.device
-
-    def dev_t(a, dt, shape=None):
-        if isinstance(a, torch.Tensor):
-            assert a.dtype == dt and a.is_contiguous() and a.device == dev
-            return a
-        a = np.ascontiguousarray(a, {torch.float64: np.float64, torch.int32: np.int32}[dt])
-        return torch.from_numpy(a if shape is None else a.reshape(shape)).to(dev)
-
     if not isinstance(cam_inv, torch.Tensor):
         cam_inv = np.ascontiguousarray(np.asarray(cam_inv, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1, 16)
-    cam_inv = dev_t(cam_inv, torch.float64)
+    cam_inv = to_device_tensor(cam_inv, torch.float64, dev)
     V = int(cam_inv.shape[0])
-    pose_angle = dev_t(pose_angle, torch.float64, (V, store.num_poses))
+    pose_angle = to_device_tensor(pose_angle, torch.float64, dev, (V, store.num_poses))
     assert tuple(pose_angle.shape) == (V, store.num_poses)
     req = PsMapViewRequest()
     req.camInv, req.poseAngle = cam_inv.data_ptr(), pose_angle.data_ptr()
     keep = [cam_inv, pose_angle]
     if cand is not None:
-        cand, cand_counts = dev_t(cand, torch.int32), dev_t(cand_counts, torch.int32)
+        cand, cand_counts = to_device_tensor(cand, torch.int32, dev), to_device_tensor(cand_counts, torch.int32, dev)
         assert cand.dim() == 2 and cand.shape[0] == V and tuple(cand_counts.shape) == (V,)
         # (a list of capacity 0 is still a list -- every view empty --, not "every feature": an empty tensor has no address)
         buf = cand if cand.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
@@ -452,11 +434,9 @@ def frame_levels_device(ctx, frames, octave, det_dist, use_torch_stream=True):
     MapBatchDevice's cur_level.  octave (F, cap) int32 / det_dist (F, cap) float64: numpy or device tensors.  An octave outside
     the level table gives -1."""
     dev = frames.device
-    up = lambda a, dt, nd: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, nd)).to(dev)   # noqa: E731
-    octave, det_dist = up(octave, torch.int32, np.int32), up(det_dist, torch.float64, np.float64)
+    octave, det_dist = to_device_tensor(octave, torch.int32, dev), to_device_tensor(det_dist, torch.float64, dev)
     shape = (frames.num_frames, frames.max_kpts)
-    assert octave.dtype == torch.int32 and det_dist.dtype == torch.float64 and tuple(octave.shape) == tuple(det_dist.shape) == shape
-    assert octave.is_contiguous() and det_dist.is_contiguous()
+    assert tuple(octave.shape) == tuple(det_dist.shape) == shape
     level = torch.zeros(shape, dtype=torch.int32, device=dev)
     torch.cuda.current_stream(dev).synchronize()
     fv = frames.view()
@@ -466,7 +446,7 @@ def frame_levels_device(ctx, frames, octave, det_dist, use_torch_stream=True):
     return level
 
 
-class PoseSetsDevice:
+class PoseSetsDevice(FrameSet):
     """What ps_pose_sets_device wrote: a frame set of S + 1 frames -- set s = the features observed from poses[s], frame S the
     empty set --, set_count (S,) and the side arrays feat_idx / obs_idx (S + 1, cap) int32 (side_arrays=False: not kept, NULL is
     passed).  packed_stride: bytes per set of ONE block [cap x 32 B descriptors][cap x 12 B points] instead of two dense arrays."""
@@ -475,26 +455,11 @@ class PoseSetsDevice:
         self.device = torch.device(device)
         self.S, self.num_frames, self.max_kpts = int(S), int(S) + 1, int(max_kpts)
         n, cap = self.num_frames, self.max_kpts
-        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)   # noqa: E731
-        self.stride = None if packed_stride is None else int(packed_stride)
-        if self.stride is None:
-            self.desc, self.pts = new((n, cap, 32), torch.uint8), new((n, cap, 3), torch.float32)
-        else:
-            self.blocks = new((n, self.stride), torch.uint8)
-        self.nkpts, self.set_count = new((n,), torch.int32), new((max(self.S, 1),), torch.int32)
+        new = lambda shape, dt: _zeros(self.device, shape, dt)   # noqa: E731
+        self._zero_frames(n, packed_stride)
+        self.set_count = new((max(self.S, 1),), torch.int32)
         self.feat_idx, self.obs_idx = (new((n, cap), torch.int32), new((n, cap), torch.int32)) if side_arrays else (None, None)
         torch.cuda.current_stream(self.device).synchronize()   # (the fills are done before a context's stream writes)
-
-    def view(self):
-        if self.stride is None:
-            return api.DeviceFrames(self.desc.data_ptr(), self.pts.data_ptr(), self.nkpts.data_ptr(), self.num_frames, self.max_kpts)
-        base = self.blocks.data_ptr()
-        return api.DeviceFrames(base, base + self.max_kpts * 32, self.nkpts.data_ptr(), self.num_frames, self.max_kpts,
-                                self.stride, self.stride)
-
-    def frame_set(self):
-        f = self.view()
-        return api.PsFrameSet(f.desc_ptr, f.pts_ptr, f.nkpts_ptr, f.num_frames, f.max_kpts, f.desc_stride, f.pts_stride)
 
     def out_struct(self):
         side = (None, None) if self.feat_idx is None else (self.feat_idx.data_ptr(), self.obs_idx.data_ptr())
@@ -503,13 +468,7 @@ class PoseSetsDevice:
     def download(self):
         """Everything on the host (numpy); desc (S + 1, cap, 32) and pts (S + 1, cap, 3) whatever the layout."""
         torch.cuda.synchronize(self.device)
-        cap = self.max_kpts
-        if self.stride is None:
-            desc, pts = self.desc.cpu().numpy(), self.pts.cpu().numpy()
-        else:
-            b = self.blocks.cpu().numpy()
-            desc = b[:, :cap * 32].reshape(-1, cap, 32)
-            pts = np.ascontiguousarray(b[:, cap * 32:cap * 44]).view(np.float32).reshape(-1, cap, 3)
+        desc, pts = self.download_frames()
         out = dict(desc=desc, pts=pts, nkpts=self.nkpts.cpu().numpy(), setCount=self.set_count.cpu().numpy()[:self.S])
         if self.feat_idx is not None:
             out.update(featIdx=self.feat_idx.cpu().numpy(), obsIdx=self.obs_idx.cpu().numpy())
@@ -523,12 +482,10 @@ def build_pose_sets(ctx, store: MapStoreDevice, obs_point3d, poses, max_kpts, pa
     observation of the store, passed beside it (numpy, or a device tensor that stays resident with the store).
     Returns a PoseSetsDevice (`out`, if given, is written again)."""
     dev = store.device
-    if not isinstance(obs_point3d, torch.Tensor):
-        obs_point3d = torch.from_numpy(np.ascontiguousarray(obs_point3d, np.float64).reshape(-1, 3)).to(dev)
-    assert obs_point3d.dtype == torch.float64 and obs_point3d.is_contiguous() and tuple(obs_point3d.shape) == (store.num_obs, 3)
-    if not isinstance(poses, torch.Tensor):
-        poses = torch.from_numpy(np.ascontiguousarray(poses, np.int32).reshape(-1)).to(dev)
-    assert poses.dtype == torch.int32 and poses.is_contiguous() and poses.dim() == 1
+    obs_point3d = to_device_tensor(obs_point3d, torch.float64, dev, (-1, 3))
+    assert tuple(obs_point3d.shape) == (store.num_obs, 3)
+    poses = to_device_tensor(poses, torch.int32, dev, (-1,))
+    assert poses.dim() == 1
     S = int(poses.shape[0])
     if out is None:
         out = PoseSetsDevice(S, max_kpts, dev, packed_stride, side_arrays)
@@ -541,25 +498,22 @@ def build_pose_sets(ctx, store: MapStoreDevice, obs_point3d, poses, max_kpts, pa
     return out
 
 
-class LoopBatchDevice:
+class LoopBatchDevice(PairResultsDevice):
     """A batch of loop-closure candidates in HBM (PsLoopBatch + PsLoopResults): `sets` as build_pose_sets wrote them, pairs (L, 2)
     of SET indices ([0] the query / prev side), the two thresholds of FeaturesMap::loopClosure, and the output block."""
 
     def __init__(self, sets: PoseSetsDevice, pairs, min_features=35, ratio_threshold=0.4, paired_feat=True):
-        self.device, self.sets = sets.device, sets
+        self.sets = sets
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        self.L, self.cap = pairs.shape[0], sets.max_kpts
+        self.L = pairs.shape[0]
         self.min_features, self.ratio_threshold = int(min_features), float(ratio_threshold)
-        L, cap = max(self.L, 1), self.cap
-        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)   # noqa: E731
-        self.pairs = torch.from_numpy(pairs).to(self.device) if self.L else new((1, 2), torch.int32)
-        self.matches, self.num_matches = new((L, cap, 16), torch.uint8), new((L,), torch.int32)
-        self.mask, self.pose = new((L, cap), torch.uint8), new((L, 16), torch.float32)
-        self.stats = new((L, STATS_DTYPE.itemsize), torch.uint8)
+        L, cap = max(self.L, 1), sets.max_kpts
+        new = lambda shape, dt: _zeros(sets.device, shape, dt)   # noqa: E731
+        self.pairs = torch.from_numpy(pairs).to(sets.device) if self.L else new((1, 2), torch.int32)
         self.ratio, self.closed, self.num_paired = new((L,), torch.float64), new((L,), torch.int32), new((L,), torch.int32)
         self.paired_rows = new((L, cap, 2), torch.int32)
         self.paired_feat = new((L, cap, 2), torch.int32) if paired_feat else None
-        torch.cuda.current_stream(self.device).synchronize()    # (the fills are done before a chain writes: PairBatchDevice)
+        super().__init__(self.L, cap, sets.device)
 
     def batch_struct(self):
         s = self.sets
@@ -567,17 +521,12 @@ class LoopBatchDevice:
                            self.pairs.data_ptr(), self.L, s.S, self.min_features, 0, self.ratio_threshold)
 
     def results_struct(self):
-        pr = PsPairResults(self.matches.data_ptr(), self.num_matches.data_ptr(), self.mask.data_ptr(), self.pose.data_ptr(),
-                           self.stats.data_ptr())
-        return PsLoopResults(pr, self.ratio.data_ptr(), self.closed.data_ptr(), self.num_paired.data_ptr(),
+        return PsLoopResults(self.view().struct(), self.ratio.data_ptr(), self.closed.data_ptr(), self.num_paired.data_ptr(),
                              self.paired_rows.data_ptr(), self.paired_feat.data_ptr() if self.paired_feat is not None else None)
 
     def download(self):
-        torch.cuda.synchronize(self.device)
-        L, g = self.L, (lambda t: t.cpu().numpy()[:self.L])
-        out = dict(matches=self.matches.cpu().numpy().view(DMATCH_DTYPE).reshape(max(L, 1), self.cap)[:L], numMatches=g(self.num_matches),
-                   inlierMask=g(self.mask), pose=g(self.pose), stats=self.stats.cpu().numpy().view(STATS_DTYPE).reshape(-1)[:L],
-                   ratio=g(self.ratio), closed=g(self.closed), numPaired=g(self.num_paired), pairedRows=g(self.paired_rows))
+        out, g = super().download(), (lambda t: t.cpu().numpy()[:self.L])
+        out.update(ratio=g(self.ratio), closed=g(self.closed), numPaired=g(self.num_paired), pairedRows=g(self.paired_rows))
         if self.paired_feat is not None:
             out["pairedFeat"] = g(self.paired_feat)
         return out
