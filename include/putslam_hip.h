@@ -225,15 +225,32 @@ int ps_umeyama_f32(PsContext *ctx, const float *src, const float *dst, int k, in
 /* ---- A10: KabschEst::computeTransformation, src/TransformEst/kabschEst.cpp:24-68
  * (interface include/putslam/TransformEst/transformEst.h:23).
  * A, B: n x 3 doubles, COLUMN-major with leading dimension ld (Eigen::MatrixXd storage).
- * T: column-major 4x4 double (Mat34 = Eigen::Transform<double,3,Affine>), maps A onto B. */
+ * T: column-major 4x4 double (Mat34 = Eigen::Transform<double,3,Affine>), maps A onto B.
+ * Only rows 0 .. n-1 of each column are read (ld > n: the rows between are padding).  The rotation is proper for every
+ * input: its handedness comes from the SVD's factors (det V det W), where kabschEst.cpp:53 takes the sign of the
+ * covariance's determinant -- the same for a covariance of full rank, rounding noise (a reflection for every second
+ * planar, collinear or three-point set) otherwise.  The summation order is a function of n alone: the same bytes for the
+ * same input, whatever ran before. */
 int ps_kabsch_f64(PsContext *ctx, const double *A, const double *B, int n, int ld, double *T);
 
 /* ---- A3: RGBD::keypoints2Dto3D / point2Dto3D / roundSize, src/RGBD/RGBD.cpp:10-16,30-65.
  * xy: n x 2 floats (cv::Point2f), depth: rows x cols uint16 with a pitch of depthStep BYTES,
- * K row-major 3x3 float, out: n x 3 floats. */
+ * K row-major 3x3 float, out: n x 3 floats.
+ * depth may be a region of a larger image (cv::Mat ROI, depthStep > cols * 2): the call reads
+ * ps_depth_view_bytes(rows, cols, depthStep) bytes from `depth` and no more.  A rounded pixel (v, u) is read by the
+ * reference's pointer arithmetic, so u == cols in a row that is not the last yields what follows that row's pixels (the
+ * parent image's next pixel; the next row's first pixel when dense); an address at or past the end of the last row's
+ * pixels (u == cols there, v == rows) yields depth 0 = missing, where the reference reads out of bounds.
+ * A NaN x or y has no pixel (the reference's (int)round(NaN) is undefined): depth 0 = missing, so Z = 0 (for a
+ * depthImageScale that is not 0) and X, Y are what (x - cx) / fx * Z gives: NaN for the NaN coordinate. */
 int ps_keypoints2Dto3D(PsContext *ctx, const float *xy, int n,
                        const uint16_t *depth, int rows, int cols, size_t depthStep,
                        const float *K, double depthImageScale, float *out);
+
+/* The addressable bytes of a rows x cols uint16 image with a pitch of depthStep bytes:
+ * (rows - 1) * depthStep + cols * 2 (the last row ends after its pixels, not after a whole pitch).
+ * 0 for a shape ps_keypoints2Dto3D rejects (rows or cols < 1, depthStep < cols * 2).  Needs no context and no device. */
+size_t ps_depth_view_bytes(int rows, int cols, size_t depthStep);
 
 /* ---- N4: RGBD::removeImageDistortion, src/RGBD/RGBD.cpp:254-314 = cv::undistortPoints(pts, K, dist) with
  * R = P = I (5 fixed-point iterations of the Brown model, double) followed by u = x_n*fx + cx in float.

@@ -267,13 +267,26 @@ def point_inlier_ratio(inliers, allm):
     return lib().po_point_inlier_ratio(_p(inliers), inliers.shape[0], _p(allm), allm.shape[0])
 
 
-def kabsch_f64(A, B):
-    """A, B: (n,3) arrays. Returns the 4x4 transform mapping A onto B."""
-    A = np.asfortranarray(A, np.float64)
-    B = np.asfortranarray(B, np.float64)
-    n = A.shape[0]
+def column_major_ld(A, B, ld):
+    """(A, B, n, ld) as a kabsch_f64 call hands them to C.  ld=None: (n,3) arrays, copied to dense column-major storage
+    (ld = max(n, 1)).  ld given: A and B already ARE views of column-major storage with that leading dimension -- (n,3)
+    float64 with strides (8, 8*ld), e.g. buf.reshape(3, ld)[:, :n].T -- and are passed without a copy."""
+    if ld is None:
+        A = np.asfortranarray(A, np.float64)
+        B = np.asfortranarray(B, np.float64)
+        return A, B, A.shape[0], max(A.shape[0], 1)
+    n, ld = A.shape[0], int(ld)
+    for M in (A, B):
+        assert M.dtype == np.float64 and M.shape == (n, 3) and ld >= max(n, 1)
+        assert M.strides[1] == 8 * ld and (n <= 1 or M.strides[0] == 8), "not a view of column-major storage with this ld"
+    return A, B, n, ld
+
+
+def kabsch_f64(A, B, ld=None):
+    """A, B: (n,3) arrays (ld: see column_major_ld). Returns the 4x4 transform mapping A onto B."""
+    A, B, n, ld = column_major_ld(A, B, ld)
     T = np.zeros(16, np.float64)
-    lib().po_kabsch_f64(_p(A), _p(B), n, max(n, 1), _p(T))
+    lib().po_kabsch_f64(_p(A), _p(B), n, ld, _p(T))
     return T.reshape(4, 4).T.copy()
 
 

@@ -166,13 +166,18 @@ void po_keypoints2Dto3D(const float *xy, int n, const uint16_t *depth, int rows,
 {
     for (int i = 0; i < n; ++i) { /* RGBD.cpp:47-65 */
         float fx = xy[2 * i], fy = xy[2 * i + 1];
-        int uR = po_round_size(fx, cols);
-        int vR = po_round_size(fy, rows);
-        /* cv::Mat::at(v,u) is plain pointer arithmetic: u == cols walks into the next row.
-         * Reads past the last row are undefined in the reference; they yield depth 0 here. */
-        size_t off = (size_t)vR * depthStep + (size_t)uR * 2;
         uint16_t dv = 0;
-        if (off + 2 <= (size_t)rows * depthStep) memcpy(&dv, (const uint8_t *)depth + off, 2);
+        /* A NaN coordinate has no pixel ((int)round(NaN) is undefined in the reference): depth 0 = missing. */
+        if (fx == fx && fy == fy) {
+            int uR = po_round_size(fx, cols);
+            int vR = po_round_size(fy, rows);
+            /* cv::Mat::at(v,u) is plain pointer arithmetic: u == cols in a row that is not the last reads what follows
+             * that row's pixels (the parent image's next pixel; the next row's first pixel when dense).  The image's
+             * addressable bytes end with the last row's pixels, (rows-1)*depthStep + cols*2: reads from there on are
+             * undefined in the reference; they yield depth 0 here. */
+            size_t off = (size_t)vR * depthStep + (size_t)uR * 2;
+            if (off + 2 <= (size_t)(rows - 1) * depthStep + (size_t)cols * 2) memcpy(&dv, (const uint8_t *)depth + off, 2);
+        }
         float Z = (float)(((double)dv) / depthImageScale);
         float u = (fx - K[2]) / K[0];
         float v = (fy - K[5]) / K[4];
@@ -798,35 +803,10 @@ int po_ransac_rigid3d(const PsRansacParams *params, const PsRansacConfig *cfg, c
 /* ------------------------------------------------------------------------------------------
  * A10  KabschEst::computeTransformation, src/TransformEst/kabschEst.cpp:24-68 (double)
  * ------------------------------------------------------------------------------------------ */
-static double det3_lu_f64(const double *Ain) /* Eigen dynamic-size determinant = PartialPivLU */
+static double det3_f64(const double *M) /* row-major; only its sign is used */
 {
-    double a[9];
-    memcpy(a, Ain, sizeof a);
-    double det = 1.0;
-    for (int k = 0; k < 3; ++k) {
-        int piv = k;
-        double big = fabs(a[3 * k + k]);
-        for (int r = k + 1; r < 3; ++r)
-            if (fabs(a[3 * r + k]) > big) {
-                big = fabs(a[3 * r + k]);
-                piv = r;
-            }
-        if (big == 0.0) return 0.0;
-        if (piv != k) {
-            for (int c = 0; c < 3; ++c) {
-                double t = a[3 * k + c];
-                a[3 * k + c] = a[3 * piv + c];
-                a[3 * piv + c] = t;
-            }
-            det = -det;
-        }
-        det *= a[3 * k + k];
-        for (int r = k + 1; r < 3; ++r) {
-            double f = a[3 * r + k] / a[3 * k + k];
-            for (int c = k + 1; c < 3; ++c) a[3 * r + c] -= f * a[3 * k + c];
-        }
-    }
-    return det;
+    return (M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6])) +
+           M[2] * (M[3] * M[7] - M[4] * M[6]);
 }
 
 void po_kabsch_f64(const double *A, const double *B, int n, int ld, double *T)
@@ -852,9 +832,10 @@ void po_kabsch_f64(const double *A, const double *B, int n, int ld, double *T)
         }
     double V[9], S[3], W[9]; /* :47-49  V = svd.matrixU(), W = svd.matrixV() */
     jacobi_svd3_f64(Am, V, S, W);
-    double det = det3_lu_f64(Am);
-    double dsg = (det != 0) ? det : 1; /* :53 */
-    double d = (double)((dsg > 0) - (dsg < 0));
+    /* :53 takes sign(A.determinant()) (1 for 0).  For a covariance of full rank that is the sign of det(V) det(W); for a
+     * rank-deficient one it is rounding noise and the reference returns a reflection for about every second planar,
+     * collinear or three-point set.  The handedness comes from the factors, as in Eigen::umeyama: det U = +1 always. */
+    double d = (det3_f64(V) * det3_f64(W) < 0) ? -1.0 : 1.0;
     double R[9]; /* :56 U = W * diag(1,1,d) * V^T */
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j)

@@ -39,7 +39,9 @@ int po_match_hamming256(const uint8_t *query, int nq, size_t qstep,
                         const uint8_t *train, int nt, size_t tstep,
                         PsDMatch *out, int *nout);
 
-/* RGBD::roundSize (RGBD.cpp:10-16), point2Dto3D (:47-65), keypoints2Dto3D (:30-45), point3Dto2D (:92-98). */
+/* RGBD::roundSize (RGBD.cpp:10-16), point2Dto3D (:47-65), keypoints2Dto3D (:30-45), point3Dto2D (:92-98).
+ * keypoints2Dto3D reads (rows-1)*depthStep + cols*2 bytes of `depth` at the most (a pitched image's last row ends after its
+ * pixels); an address from there on, or a NaN coordinate, is depth 0. */
 /* timed-baseline switch: SIMD popcount sweep (OpenCV's normHamming is vectorised) vs the scalar popcnt loop; identical results */
 void po_set_matcher_simd(int on);
 int po_get_matcher_simd(void);
@@ -101,7 +103,9 @@ int po_hypothesis_counts(const PsRansacParams *params, const PsRansacConfig *cfg
 /* RANSAC::pointInlierRatio (RANSAC.h:56-66). */
 double po_point_inlier_ratio(const PsDMatch *inliers, int ninl, const PsDMatch *all, int nall);
 
-/* KabschEst::computeTransformation (kabschEst.cpp:24-68). A,B n x 3 column-major (ld), T 4x4 column-major. */
+/* KabschEst::computeTransformation (kabschEst.cpp:24-68). A,B n x 3 column-major (ld), T 4x4 column-major.
+ * The handedness is taken from the SVD's factors (det V det W < 0 -> -1), not from the covariance's determinant (:53),
+ * whose sign is rounding noise for a rank-deficient covariance: det R = +1 for every input. */
 void po_kabsch_f64(const double *A, const double *B, int n, int ld, double *T);
 
 /* N2: guided map matching core of Matcher::matchXYZ, src/Matcher/matcher.cpp:606-746.

@@ -26,7 +26,7 @@ EXPORTED = [
     "ps_context_set_option", "ps_context_get_option",
     "ps_last_error", "ps_abi_version", "ps_device_arch",
     "ps_match_hamming256", "ps_ransac_rigid3d", "ps_umeyama_f32", "ps_kabsch_f64",
-    "ps_keypoints2Dto3D", "ps_points3Dto2D", "ps_vo_pairs_device", "ps_dbscan_thin", "ps_dbscan_thin_device", "ps_debug_dbscan_bound",
+    "ps_keypoints2Dto3D", "ps_depth_view_bytes", "ps_points3Dto2D", "ps_vo_pairs_device", "ps_dbscan_thin", "ps_dbscan_thin_device", "ps_debug_dbscan_bound",
     "ps_batch_queue_create", "ps_batch_queue_destroy", "ps_batch_queue_submit", "ps_batch_queue_wait", "ps_batch_queue_query",
     "ps_batch_queue_wait_on_stream", "ps_batch_queue_synchronize", "ps_batch_queue_chains", "ps_batch_queue_context",
     "ps_batch_queue_last_split", "ps_pack_records_device", "ps_match_xyz", "ps_predicted_level", "ps_remove_image_distortion",
@@ -150,6 +150,8 @@ def load_path(path):
     L.ps_umeyama_f32.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     L.ps_kabsch_f64.argtypes = [vp, vp, vp, i32, i32, vp]
     L.ps_keypoints2Dto3D.argtypes = [vp, vp, i32, vp, i32, i32, sz, vp, C.c_double, vp]
+    L.ps_depth_view_bytes.argtypes = [i32, i32, sz]
+    L.ps_depth_view_bytes.restype = sz
     L.ps_points3Dto2D.argtypes = [vp, vp, i32, vp, vp]
     L.ps_dbscan_thin.argtypes = [vp, vp, sz, vp, sz, i32, C.c_double, i32, i32, vp, C.POINTER(i32)]
     L.ps_dbscan_thin_device.argtypes = [vp, vp, vp, vp, i32, i32, C.c_double, i32, i32, vp, vp]

@@ -309,13 +309,24 @@ class Context:
         return (T[0], bool(valid[0])) if single else (T, valid.astype(bool))
 
     # ---- A10 ----
-    def kabsch_f64(self, A, B):
-        """KabschEst::computeTransformation (kabschEst.cpp:24-68). A, B (n,3). Returns 4x4 mapping A onto B."""
-        A = np.asfortranarray(A, np.float64)
-        B = np.asfortranarray(B, np.float64)
-        n = A.shape[0]
+    def kabsch_f64(self, A, B, ld=None):
+        """KabschEst::computeTransformation (kabschEst.cpp:24-68). A, B (n,3). Returns 4x4 mapping A onto B.
+        ld=None: the arrays are copied to dense column-major storage.  ld given: A and B already are views of column-major
+        storage with that leading dimension -- (n,3) float64 with strides (8, 8*ld), e.g. buf.reshape(3, ld)[:, :n].T -- and
+        are handed over as they lie."""
+        if ld is None:
+            A = np.asfortranarray(A, np.float64)
+            B = np.asfortranarray(B, np.float64)
+            n = A.shape[0]
+            ld = max(n, 1)
+        else:
+            n, ld = A.shape[0], int(ld)
+            for M in (A, B):
+                if not (M.dtype == np.float64 and M.shape == (n, 3) and ld >= max(n, 1) and M.strides[1] == 8 * ld
+                        and (n <= 1 or M.strides[0] == 8)):
+                    raise ValueError("kabsch_f64: A, B must be (n,3) float64 views of column-major storage with leading dimension ld")
         T = np.zeros(16, np.float64)
-        self._chk(self._L.ps_kabsch_f64(self._h, _p(A), _p(B), n, max(n, 1), _p(T)))
+        self._chk(self._L.ps_kabsch_f64(self._h, _p(A), _p(B), n, ld, _p(T)))
         return T.reshape(4, 4).T.copy()
 
     # ---- A3 ----

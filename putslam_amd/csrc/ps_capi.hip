@@ -1121,6 +1121,8 @@ int ps_kabsch_f64(PsContext *ctx, const double *A, const double *B, int n, int l
     return PS_OK;
 }
 
+size_t ps_depth_view_bytes(int rows, int cols, size_t depthStep) { return depth_view_bytes(rows, cols, depthStep); }
+
 int ps_keypoints2Dto3D(PsContext *ctx, const float *xy, int n, const uint16_t *depth, int rows, int cols,
                        size_t depthStep, const float *K, double depthImageScale, float *out)
 {
@@ -1129,13 +1131,14 @@ int ps_keypoints2Dto3D(PsContext *ctx, const float *xy, int n, const uint16_t *d
     if (n < 0 || rows <= 0 || cols <= 0 || !depth || !K || depthStep < (size_t)cols * 2 || (n > 0 && (!xy || !out)))
         return fail(ctx, PS_ERR_BAD_ARG, "ps_keypoints2Dto3D: bad argument");
     if (n == 0) return PS_OK;
+    const size_t bytes = depth_view_bytes(rows, cols, depthStep); // not rows x depthStep: the last row ends after its pixels
     PS_ENSURE(ctx->sMisc0, (size_t)n * 8);
-    PS_ENSURE(ctx->sMisc1, (size_t)rows * depthStep);
+    PS_ENSURE(ctx->sMisc1, bytes);
     PS_ENSURE(ctx->sMisc2, (size_t)n * 12);
     PS_HIP(hipMemcpyAsync(ctx->sMisc0.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PS_HIP(hipMemcpyAsync(ctx->sMisc1.p, depth, (size_t)rows * depthStep, hipMemcpyHostToDevice, ctx->stream));
+    PS_HIP(hipMemcpyAsync(ctx->sMisc1.p, depth, bytes, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(ps_backproject, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       (const float *)ctx->sMisc0.p, n, (const uint8_t *)ctx->sMisc1.p, rows, cols, depthStep, K[0],
+                       (const float *)ctx->sMisc0.p, n, (const uint8_t *)ctx->sMisc1.p, rows, cols, depthStep, bytes, K[0],
                        K[4], K[2], K[5], depthImageScale, (float *)ctx->sMisc2.p);
     PS_HIP(hipGetLastError());
     PS_HIP(hipMemcpyAsync(out, ctx->sMisc2.p, (size_t)n * 12, hipMemcpyDeviceToHost, ctx->stream));

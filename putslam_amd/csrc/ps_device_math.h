@@ -332,7 +332,7 @@ template <typename T> PS_HD void jacobi_svd3(const T (&A)[3][3], T (&U)[3][3], T
     }
 }
 
-PS_HD float det3(const float (&M)[3][3])
+template <typename T> PS_HD T det3(const T (&M)[3][3])
 {
     return (M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0])) +
            M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);

@@ -1613,46 +1613,14 @@ PS_D double wave_tree_sum_f64(double v)
     return __shfl(v, 0, 64);
 }
 
-PS_D double det3_lu(const double (&Ain)[3][3])
+// The handedness of the Kabsch rotation.  The reference takes sign(A.determinant()) of the covariance (kabschEst.cpp:53; 1 for
+// a determinant of 0): for a covariance of full rank that is the sign of det(V) det(W), and the only rule that differs is
+// meaningless -- for a planar, collinear or three-point set the determinant is rounding noise (or exactly 0) and says nothing
+// about the handedness of W V^T, so the reference returns a reflection for about every second such set.  Here the sign comes
+// from the factors themselves, as Eigen::umeyama takes it: det(W diag(1, 1, d) V^T) = +1 for every input.
+PS_D double kabsch_handedness(const double (&V)[3][3], const double (&W)[3][3])
 {
-    // Eigen's dynamic-size determinant goes through PartialPivLU (kabschEst.cpp:53).
-    double m[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) m[i][j] = Ain[i][j];
-    double det = 1.0;
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-        int piv = kx;
-        double big = fabs(m[kx][kx]);
-#pragma unroll
-        for (int r = kx + 1; r < 3; ++r)
-            if (fabs(m[r][kx]) > big) {
-                big = fabs(m[r][kx]);
-                piv = r;
-            }
-        if (big == 0.0) return 0.0;
-#pragma unroll
-        for (int r = kx + 1; r < 3; ++r)
-            if (r == piv) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    double t = m[kx][c];
-                    m[kx][c] = m[r][c];
-                    m[r][c] = t;
-                }
-                det = -det;
-            }
-        det *= m[kx][kx];
-#pragma unroll
-        for (int r = kx + 1; r < 3; ++r) {
-            double f = m[r][kx] / m[kx][kx];
-#pragma unroll
-            for (int c = kx + 1; c < 3; ++c) m[r][c] -= f * m[kx][c];
-        }
-    }
-    return det;
+    return (det3(V) * det3(W) < 0.0) ? -1.0 : 1.0;
 }
 
 // KabschEst::computeTransformation (reference src/TransformEst/kabschEst.cpp:24-68), double precision.
@@ -1699,9 +1667,7 @@ __global__ __launch_bounds__(64) void ps_kabsch_f64_kernel(const double *__restr
         for (int c = 0; c < 3; ++c) Am[r][c] = wave_tree_sum_f64(acc[r][c]);
     double V[3][3], W[3][3], S[3];
     jacobi_svd3<double>(Am, V, S, W); // V = svd.matrixU(), W = svd.matrixV()  (kabschEst.cpp:48-49)
-    double det = det3_lu(Am);
-    double dsg = (det != 0.0) ? det : 1.0;
-    double d = (double)((dsg > 0.0) - (dsg < 0.0));
+    double d = kabsch_handedness(V, W);
     double R[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -1724,8 +1690,10 @@ __global__ __launch_bounds__(64) void ps_kabsch_f64_kernel(const double *__restr
 
 // Large point sets: the same arithmetic spread over G wavefronts (one 64-lane work-group each, strided like the
 // single-wave kernel's lanes), partial sums combined in wave order by every wave / by the finishing wave.  The
-// summation tree is a function of (n, G) only, so results are reproducible; versus the oracle's sequential sums the
-// bound is the 1e-12 of the single-wave form.
+// summation tree is a function of (n, G) only: tests/kabsch_tree_ref.py restates it (lane-strided sequential partial sums,
+// the shuffle tree, per-wave partials added in wave order, each product rounded before it is added) and the pose equals that
+// restatement byte for byte, for this form and the single-wave one.  The oracle's sequential sums are another order: the two
+// poses agree only as far as the data's conditioning lets them (1e-15 on centred clouds, 1e-8 a million units from the origin).
 //   pass 1: part[g][0..5]  = column sums of A, B over the wave's points
 //   pass 2: part2[g][0..8] = sum (a - cA)(b - cB)^T over the wave's points, cA / cB from all part[] in order
 //   finish: one wave adds part2[] in order, SVD, pose
@@ -1814,9 +1782,7 @@ __global__ __launch_bounds__(64) void ps_kabsch_f64_finish(const double *__restr
         }
     double V[3][3], W[3][3], S[3];
     jacobi_svd3<double>(Am, V, S, W);
-    double det = det3_lu(Am);
-    double dsg = (det != 0.0) ? det : 1.0;
-    double d = (double)((dsg > 0.0) - (dsg < 0.0));
+    double d = kabsch_handedness(V, W);
     if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0 : 0.0;
@@ -1844,18 +1810,23 @@ PS_D int round_size(double x, int size)
 }
 __global__ __launch_bounds__(kBlock) void ps_backproject(const float *__restrict__ xy, int n,
                                                          const uint8_t *__restrict__ depth, int rows, int cols,
-                                                         size_t step, float fx, float fy, float cx, float cy,
-                                                         double scale, float *__restrict__ out)
+                                                         size_t step, size_t bytes, float fx, float fy, float cx,
+                                                         float cy, double scale, float *__restrict__ out)
 {
     int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     float x = xy[2 * i], y = xy[2 * i + 1];
-    int uR = round_size((double)x, cols), vR = round_size((double)y, rows);
-    size_t off = (size_t)vR * step + (size_t)uR * 2;
     unsigned dv = 0;
-    // cv::Mat::at is plain pointer arithmetic: u == cols reads the first pixel of the next row;
-    // past the last row the reference reads out of bounds, here that is depth 0 (= missing).
-    if (off + 2 <= (size_t)rows * step) dv = (unsigned)depth[off] | ((unsigned)depth[off + 1] << 8);
+    // A NaN coordinate has no pixel (the reference's (int)round(NaN) is undefined): depth 0 (= missing).
+    if (x == x && y == y) {
+        int uR = round_size((double)x, cols), vR = round_size((double)y, rows);
+        size_t off = (size_t)vR * step + (size_t)uR * 2;
+        // cv::Mat::at is plain pointer arithmetic: u == cols in a row that is not the last reads what follows that row's
+        // pixels (the parent image's next pixel for a region, the next row's first pixel for a dense image).  `bytes` =
+        // depth_view_bytes(rows, cols, step) is where the last row's pixels end: from there on the reference reads out of
+        // bounds, here that is depth 0 (= missing).
+        if (off + 2 <= bytes) dv = (unsigned)depth[off] | ((unsigned)depth[off + 1] << 8);
+    }
     float Z = (float)(((double)dv) / scale);
     float u = (x - cx) / fx;
     float v = (y - cy) / fy;

@@ -118,3 +118,26 @@ def test_pack_and_unpack_frames_are_inverses():
     assert pack_frames(desc, pts).shape == (F, 224)         # the default stride: cap x 44 rounded up to 16
     d, p = unpack_frames(pack_frames(desc, pts), cap)
     assert d.tobytes() == desc.tobytes() and p.tobytes() == pts.tobytes()
+
+
+def test_depth_view_bytes_is_where_the_last_row_ends():
+    """ps_depth_view_bytes (csrc/ps_glue.h: depth_view_bytes) -- what ps_keypoints2Dto3D copies from the host and what its
+    kernel may read: (rows - 1) x depthStep + cols x 2, not rows x depthStep.  Against numpy's own account of a view: the
+    distance from its first byte to the byte behind its last pixel."""
+    f = _lib.load().ps_depth_view_bytes
+    assert f(480, 640, 1280) == 480 * 1280                      # dense: the whole image
+    assert f(480, 560, 1280) == 479 * 1280 + 1120               # pitched: 160 bytes short of rows x depthStep
+    assert f(1, 1, 2) == 2 and f(1, 1, 4096) == 2               # 1 x 1, whatever the pitch
+    assert f(1, 40, 80) == 80 and f(1, 40, 1280) == 80          # rows = 1: the pitch does not matter
+    assert f(40, 1, 2) == 80 and f(40, 1, 1280) == 39 * 1280 + 2
+    full = np.zeros((480, 640), np.uint16)
+    for view in (full, full[:, 40:600], full[10:400, :], full[5:, 600:], full[7:8, 9:10], full[3:4, 10:50], full[20:60, 17:18]):
+        rows, cols = view.shape
+        first = view.__array_interface__["data"][0]
+        behind_last = view[rows - 1:, cols - 1:].__array_interface__["data"][0] + 2
+        assert f(rows, cols, view.strides[0]) == behind_last - first
+        assert first + f(rows, cols, view.strides[0]) <= full.__array_interface__["data"][0] + full.nbytes
+    assert full[5:, 600:].__array_interface__["data"][0] + 475 * 1280 > full.__array_interface__["data"][0] + full.nbytes  # rows x step was not
+    # shapes the call rejects
+    assert f(0, 640, 1280) == 0 and f(480, 0, 1280) == 0 and f(-1, 5, 10) == 0 and f(480, 640, 1279) == 0
+    assert f(2, 0x7fffffff, 2 * 0x7fffffff) == 2 * 2 * 0x7fffffff     # no 32-bit arithmetic

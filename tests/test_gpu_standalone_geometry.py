@@ -1,0 +1,370 @@
+"""The stand-alone entry points (ps_kabsch_f64, ps_keypoints2Dto3D, ps_remove_image_distortion, ps_points3Dto2D,
+ps_umeyama_f32) at their edges.
+
+Kabsch is held to the restated summation tree of tests/kabsch_tree_ref.py byte for byte: around every seam of the lane / wave
+decomposition, on every data family of tests/test_kabsch_tree_host.py, with non-finite and subnormal coordinates, with a
+leading dimension above n, and after a call that left other partial sums in the scratch block.  The helpers are held to the
+oracle byte for byte, back-projection in addition to a model written out in this file."""
+import ctypes
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kabsch_tree_ref as kt  # noqa: E402
+
+from putslam_amd import api  # noqa: E402
+from putslam_amd._abi import TUM_FR1_K  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+K_BLOCK = 256       # kBlock of ps_kernels.h: the work-group size of the per-point kernels
+
+
+def same_bits(got, want):
+    """Equal byte for byte; where `want` is NaN, `got` is NaN too (NaN payloads are not part of the contract)."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), (got, want)
+    assert got[~nan].tobytes() == want[~nan].tobytes(), (got, want, np.abs(got[~nan] - want[~nan]).max())
+
+
+# =================================================================================================== A10 Kabsch (double)
+SEAMS = [1, 2, 3, 4, 63, 64, 65, 127, 128, 129,         # one trip of the single wavefront, then two, then three
+         4095, 4096, 4097,
+         16383, 16384, 16385,                           # the switch to the three-kernel form (G = 5)
+         20480, 20481,                                  # G goes 5 -> 6
+         4194304, 4194305]                              # G at its cap of 1024: 64 trips a lane, then a 65th for one lane
+
+
+@pytest.mark.parametrize("n", SEAMS)
+def test_kabsch_equals_the_tree_around_every_seam(ctx, n):
+    A, B = kt.conditioned_cloud("centred", n, 7)
+    same_bits(ctx.kabsch_f64(A, B), kt.kabsch_tree(A, B))
+
+
+FAMILY_SIZES = (3, 65, 500, 16385, 20481)               # both kernels, one and several trips, two wave counts
+
+
+FAMILY_CASES = [(k, n) for k in kt.CONDITIONED + kt.DEGENERATE for n in FAMILY_SIZES if k != "three_points" or n == 3]
+
+
+@pytest.mark.parametrize("kind,n", FAMILY_CASES)
+def test_kabsch_equals_the_tree_on_every_family(ctx, kind, n):
+    make = kt.conditioned_cloud if kind in kt.CONDITIONED else kt.degenerate_cloud
+    for seed in (1, 2):
+        A, B = make(kind, n, seed)
+        T = ctx.kabsch_f64(A, B)
+        same_bits(T, kt.kabsch_tree(A, B))
+        if kind in kt.DEGENERATE:       # what the host suite asserts of the restatement holds for the device's bytes too
+            assert abs(np.linalg.det(T[:3, :3]) - 1.0) <= 64 * np.finfo(np.float64).eps
+
+
+@pytest.mark.parametrize("n", FAMILY_SIZES)
+@pytest.mark.parametrize("what", ["nan_in_A", "nan_in_B", "plus_inf", "minus_inf", "subnormal"])
+def test_kabsch_equals_the_tree_on_non_finite_and_subnormal_input(ctx, what, n):
+    """One NaN / one infinite coordinate: the SVD's sweep cap (PS_SVD_MAX_SWEEPS) bounds the run, and every comparison
+    the SVD and the handedness rule take on a NaN must fall the way the restatement's does.  Subnormal coordinates: the
+    covariance underflows to 0 and the pose is the coincident set's."""
+    A, B = kt.conditioned_cloud("centred", n, 3)
+    i = (2 * n) // 3
+    if what == "nan_in_A":
+        A[i, 0] = np.nan            # the covariance's first row, (0,0) included: the SVD's scale is NaN
+    elif what == "nan_in_B":
+        B[i, 1] = np.nan            # its middle column only: the scale stays finite
+    elif what == "plus_inf":
+        A[i, 2] = np.inf
+    elif what == "minus_inf":
+        B[i, 0] = -np.inf
+    else:
+        A, B = A * 1e-310, B * 1e-310
+    same_bits(ctx.kabsch_f64(A, B), kt.kabsch_tree(A, B))
+
+
+def _padded(M, ld):
+    """The (n,3) view of column-major storage with leading dimension ld whose padding rows hold NaN."""
+    n = M.shape[0]
+    store = np.full((3, ld), np.nan)
+    store[:, :n] = M.T
+    return store[:, :n].T
+
+
+@pytest.mark.parametrize("n", [3, 65, 16385, 20481])
+def test_kabsch_with_a_leading_dimension_above_n(ctx, oracle, n):
+    """ld in {n+1, n+7, 2n}: a padding row that is read shows in the pose as NaN."""
+    A, B = kt.conditioned_cloud("offset1e3", n, 11)
+    want = kt.kabsch_tree(A, B)
+    assert not np.isnan(want).any()
+    for ld in (n + 1, n + 7, 2 * n):
+        Av, Bv = _padded(A, ld), _padded(B, ld)
+        same_bits(kt.kabsch_tree(Av, Bv, ld), want)
+        same_bits(ctx.kabsch_f64(Av, Bv, ld), want)
+        same_bits(oracle.kabsch_f64(Av, Bv, ld), oracle.kabsch_f64(A, B))
+    with pytest.raises(ValueError):
+        ctx.kabsch_f64(A, B, n + 1)         # dense arrays are not a view of such storage
+
+
+def test_kabsch_is_reproducible_and_independent_of_the_scratch_contents(ctx):
+    """The same call twice gives the same bytes; a context whose first call was a 5 M-point one (1024 waves' partial sums in
+    the scratch block) gives the 3-point pose of a fresh one."""
+    A3, B3 = kt.conditioned_cloud("offset1e3", 3, 21)
+    want3 = kt.kabsch_tree(A3, B3)
+    A, B = kt.conditioned_cloud("centred", 20481, 22)
+    first = ctx.kabsch_f64(A, B)
+    assert first.tobytes() == ctx.kabsch_f64(A, B).tobytes()
+    c = api.Context(0)
+    try:
+        rng = np.random.default_rng(23)
+        big_a = rng.uniform(-1, 1, (5_000_000, 3))
+        big = c.kabsch_f64(big_a, big_a[::-1])
+        assert np.isfinite(big).all()
+        same_bits(c.kabsch_f64(A3, B3), want3)
+        same_bits(c.kabsch_f64(A, B), first)
+    finally:
+        c.close()
+    same_bits(ctx.kabsch_f64(A3, B3), want3)
+
+
+# =================================================================================================== A3 back-projection
+def _round_size(x, size):
+    """RGBD::roundSize on a non-NaN x: clamp below 0 to 0 and above size - 1 to SIZE (sic), round half away from zero."""
+    x = float(x)
+    if x < 0:
+        x = 0.0
+    elif x > size - 1:
+        x = float(size)
+    return int(math.floor(x + 0.5))         # (x >= 0 here)
+
+
+def backproject_model(xy, view, K, scale):
+    """ps_keypoints2Dto3D written out: the pixel by pointer arithmetic over the view's addressable bytes, NaN = missing."""
+    rows, cols = view.shape
+    step = view.strides[0]
+    nbytes = (rows - 1) * step + cols * 2
+    raw = np.frombuffer((ctypes.c_uint8 * nbytes).from_address(view.ctypes.data), np.uint8)
+    K = np.asarray(K, np.float32).reshape(3, 3)
+    out = np.zeros((len(xy), 3), np.float32)
+    with np.errstate(all="ignore"):
+        for i, (x, y) in enumerate(np.asarray(xy, np.float32)):
+            dv = 0
+            if not (np.isnan(x) or np.isnan(y)):
+                off = _round_size(y, rows) * step + _round_size(x, cols) * 2
+                if off + 2 <= nbytes:
+                    dv = int(raw[off]) | (int(raw[off + 1]) << 8)
+            Z = np.float32(np.float64(dv) / np.float64(scale))
+            u = (x - K[0, 2]) / K[0, 0]
+            v = (y - K[1, 2]) / K[1, 1]
+            out[i] = (u * Z, v * Z, Z)
+    return out
+
+
+def _edge_coordinates(size):
+    f = np.float32
+    last = f(size - 1)
+    return [f(0.5), f(1.5), f(2.5), f(7.5), f(size - 1.5),              # half away from zero
+            last, np.nextafter(last, f(np.inf)), f(size - 0.5), f(size), f(size + 3),
+            f(-0.0), f(-0.4), f(-1.0), f(0.49999997), f(np.inf), f(-np.inf), f(np.nan), f(size // 2)]
+
+
+def _edge_keypoints(rows, cols):
+    return np.array([(x, y) for x in _edge_coordinates(cols) for y in _edge_coordinates(rows)], np.float32)
+
+
+@pytest.fixture(scope="module")
+def parent_depth():
+    rng = np.random.default_rng(2026)
+    return rng.integers(1, 30000, (480, 640)).astype(np.uint16)         # no 0: a missing pixel cannot hide
+
+
+def _views(full):
+    return {"columns": full[:, 40:600], "rows": full[10:400, :], "corner": full[5:, 600:],     # corner ends with the buffer
+            "dense": full, "1x1": full[7:8, 9:10], "1xN": full[3:4, 10:50], "Nx1": full[20:60, 17:18],
+            "dense_Nx1": np.ascontiguousarray(full[:40, :1]), "dense_1x1": np.ascontiguousarray(full[:1, :1])}
+
+
+@pytest.mark.parametrize("name", ["columns", "rows", "corner", "dense", "1x1", "1xN", "Nx1", "dense_Nx1", "dense_1x1"])
+def test_backprojection_of_pitched_views(ctx, oracle, parent_depth, name):
+    view = _views(parent_depth)[name]
+    rows, cols = view.shape
+    xy = _edge_keypoints(rows, cols)
+    for scale in (5000.0, 1.0, 0.0):
+        g = ctx.keypoints2Dto3D(xy, view, TUM_FR1_K, scale)
+        same_bits(g, oracle.keypoints2Dto3D(xy, view, TUM_FR1_K, scale))
+        same_bits(g, backproject_model(xy, view, TUM_FR1_K, scale))
+
+
+def test_backprojection_literal_values(ctx, parent_depth):
+    """Expected values that depend on neither side: Z = depth / scale of the pixel the reference's arithmetic addresses."""
+    full = parent_depth
+    K = np.array([[1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32)     # X = x Z, Y = y Z
+
+    def Z(view, x, y, scale=1.0):
+        return ctx.keypoints2Dto3D(np.float32([[x, y]]), view, K, scale)[0, 2]
+
+    cols_view = full[:, 40:600]                                      # 480 x 560 inside 480 x 640
+    assert Z(cols_view, 560, 3) == full[3, 600]                      # u == cols, inner row: the parent's next pixel
+    assert Z(cols_view, 559.5, 3) == full[3, 600]                    # cols - 0.5 clamps to cols
+    assert Z(cols_view, np.nextafter(np.float32(559), np.float32(np.inf)), 3) == full[3, 600]
+    assert Z(cols_view, 559, 3) == full[3, 599]
+    assert Z(cols_view, 560, 479) == 0                               # u == cols in the last row: past the view's bytes
+    assert Z(cols_view, 559, 479) == full[479, 599]
+    assert Z(cols_view, 5, 480) == 0 and Z(cols_view, 5, 1e9) == 0   # v == rows
+    assert Z(cols_view, 2.5, 3.5) == full[4, 43] and Z(cols_view, 1.5, 0.5) == full[1, 42]      # half away from zero
+    assert Z(cols_view, -0.0, -0.4) == full[0, 40] and Z(cols_view, -np.inf, 2) == full[2, 40]
+    assert Z(cols_view, np.inf, 2) == full[2, 600] and Z(cols_view, 2, np.inf) == 0
+    assert Z(cols_view, np.nan, 2) == 0 and Z(cols_view, 2, np.nan) == 0                        # NaN: missing depth
+    rows_view = full[10:400, :]                                      # dense rows, the parent goes on behind them
+    assert Z(rows_view, 640, 5) == full[16, 0]                       # dense: the next row's first pixel
+    assert Z(rows_view, 640, 389) == 0 and Z(rows_view, 0, 390) == 0  # ... but never the parent's row behind the view
+    corner = full[5:, 600:]                                          # its last row ends where the buffer ends
+    assert Z(corner, 40, 2) == full[8, 0] and Z(corner, 39, 474) == full[479, 639] and Z(corner, 40, 474) == 0
+    # depth 0 and 65535, the scales, a camera matrix with fx = 0
+    img = np.array([[0, 65535], [5000, 1]], np.uint16)
+    got = ctx.keypoints2Dto3D(np.float32([[0, 0], [1, 0], [0, 1], [1, 1]]), img, K, 5000.0)
+    assert np.array_equal(got[:, 2], np.float32([0.0, np.float32(65535 / 5000.0), 1.0, np.float32(1 / 5000.0)]))
+    assert np.array_equal(got[2], np.float32([0, 1, 1]))
+    assert Z(img, 1, 0, 1.0) == 65535.0
+    with np.errstate(all="ignore"):
+        assert Z(img, 1, 0, 0.0) == np.inf and np.isnan(Z(img, 0, 0, 0.0))
+    K0 = np.array([[0, 0, 1], [0, 2, 0], [0, 0, 1]], np.float32)    # fx = 0: (x - cx) / 0
+    got = ctx.keypoints2Dto3D(np.float32([[1, 1], [0, 1], [1, 0]]), img, K0, 1.0)
+    assert np.isnan(got[0, 0]) and got[0, 1] == 0.5 and got[0, 2] == 1.0            # 0 / 0 * 1
+    assert got[1, 0] == -np.inf and got[1, 2] == 5000.0                              # -1 / 0 * 5000
+    assert np.isnan(got[2, 0]) and got[2, 2] == 65535.0                              # 0 / 0
+
+
+def test_backprojection_with_a_degenerate_camera_matrix(ctx, oracle, parent_depth):
+    view = parent_depth[100:140, 300:364]
+    xy = _edge_keypoints(*view.shape)
+    for K in (np.array([[0, 0, 31.5], [0, 525, 20], [0, 0, 1]], np.float32),
+              np.array([[1e-42, 0, 31.5], [0, -0.0, 20], [0, 0, 1]], np.float32)):      # fx subnormal, fy = -0
+        for scale in (5000.0, 0.0):
+            g = ctx.keypoints2Dto3D(xy, view, K, scale)
+            same_bits(g, oracle.keypoints2Dto3D(xy, view, K, scale))
+            same_bits(g, backproject_model(xy, view, K, scale))
+
+
+# =================================================================================================== N4 undistortion
+def _image_points(n, seed):
+    rng = np.random.default_rng([seed, n])
+    return np.stack([rng.uniform(-20, 660, n), rng.uniform(-20, 500, n)], 1).astype(np.float32)
+
+
+TUM_DIST = [0.2624, -0.9531, -0.0054, 0.0026, 1.1633]
+
+
+@pytest.mark.parametrize("n", [1, K_BLOCK - 1, K_BLOCK, K_BLOCK + 1])
+def test_remove_image_distortion_at_the_block_edges_and_on_hostile_values(ctx, oracle, n):
+    xy = _image_points(n, 1)
+    hostile = np.float32([[np.nan, 10], [10, np.nan], [np.inf, 10], [10, -np.inf], [1e30, 1e30], [-1e30, 5],
+                          [np.inf, np.nan], [0, 0], [-0.0, 3.4e38]])
+    xy[-min(n, len(hostile)):] = hostile[:min(n, len(hostile))]
+    for dist in (TUM_DIST, [0, 0, 0, 0, 0], [1e3, -1e6, 10, -10, 1e9]):
+        same_bits(ctx.remove_image_distortion(xy, TUM_FR1_K, dist), oracle.remove_image_distortion(xy, TUM_FR1_K, dist))
+
+
+def test_remove_image_distortion_through_a_zero_denominator(ctx, oracle):
+    """1 + ((k3 r^2 + k2) r^2 + k1) r^2 driven through 0: with K = I the point (1, 0) has r^2 = 1 in the first iteration and
+    k1 + k2 + k3 = -1 makes the radial factor a division by 0; the neighbours take the denominator through both signs."""
+    K = np.eye(3, dtype=np.float32)
+    t = np.linspace(-1e-3, 1e-3, 41, dtype=np.float32)
+    xy = np.concatenate([np.stack([1 + t, 0 * t], 1), np.stack([0 * t, 1 + t], 1),
+                         np.stack([np.sqrt(0.5, dtype=np.float32) + t, np.sqrt(0.5, dtype=np.float32) + 0 * t], 1)]).astype(np.float32)
+    for dist in ([-1, 0, 0, 0, 0], [0, -1, 0, 0, 0], [0, 0, 0, 0, -1], [-0.5, -0.25, 0, 0, -0.25], [-1, 0, 1e-3, -1e-3, 0]):
+        g = ctx.remove_image_distortion(xy, K, dist)
+        c = oracle.remove_image_distortion(xy, K, dist)
+        assert not np.isfinite(c).all()             # the case is what it claims to be
+        same_bits(g, c)
+
+
+def test_remove_image_distortion_with_a_subnormal_focal_length(ctx, oracle):
+    xy = _image_points(300, 2)
+    for fx, fy in ((1e-40, 525.0), (525.0, 1e-45), (1e-39, -1e-39), (0.0, 525.0)):
+        K = np.array([[fx, 0, 319.5], [0, fy, 239.5], [0, 0, 1]], np.float32)
+        for dist in (TUM_DIST, [0, 0, 0, 0, 0]):
+            same_bits(ctx.remove_image_distortion(xy, K, dist), oracle.remove_image_distortion(xy, K, dist))
+
+
+# =================================================================================================== A3 projection
+@pytest.mark.parametrize("n", [1, K_BLOCK - 1, K_BLOCK, K_BLOCK + 1])
+def test_points3Dto2D_over_every_kind_of_depth(ctx, oracle, n):
+    zs = np.float32([0.0, -0.0, -2.5, 1e-40, -1e-45, np.inf, -np.inf, np.nan, 1.0, 3.4e38, 1.2e-38])
+    xs = np.float32([0.0, -0.0, 1.0, -3.0, 1e-40, np.inf, np.nan, 3.4e38])
+    pts = np.array([(x, y, z) for z in zs for x in xs for y in xs[:4]], np.float32)          # 352 points
+    xyz = np.resize(pts[np.random.default_rng(n).permutation(len(pts))], (n, 3))
+    same_bits(ctx.points3Dto2D(xyz, TUM_FR1_K), oracle.points3Dto2D(xyz, TUM_FR1_K))
+    same_bits(ctx.points3Dto2D(pts, TUM_FR1_K), oracle.points3Dto2D(pts, TUM_FR1_K))
+    # literal: x fx / z + cx with z = -0 is -inf for positive x fx, +0 / -0 is NaN
+    lit = ctx.points3Dto2D(np.float32([[1, -1, -0.0], [0, 1, 0.0], [1, 1, np.inf], [2, 4, -2]]), np.eye(3, dtype=np.float32))
+    assert lit[0, 0] == -np.inf and lit[0, 1] == np.inf and np.isnan(lit[1, 0]) and lit[1, 1] == np.inf
+    assert np.array_equal(lit[2:], np.float32([[0, 0], [-1, -2]]))
+
+
+# =================================================================================================== A7 Umeyama sets
+def _umeyama_sets(nsets, k, seed):
+    rng = np.random.default_rng([seed, nsets, k])
+    src = (rng.uniform(-2, 2, (nsets, k, 3)) + [0, 0, 3]).astype(np.float32)
+    dst = np.empty_like(src)
+    for s in range(nsets):
+        dst[s] = (src[s] @ kt.rotation(rng, 30.0).T + rng.uniform(-0.5, 0.5, 3) + rng.normal(0, 0.004, (k, 3))).astype(np.float32)
+    return src, dst
+
+
+def _oracle_sets(oracle, src, dst):
+    T = np.empty((len(src), 4, 4), np.float32)
+    ok = np.empty(len(src), bool)
+    for s in range(len(src)):
+        T[s], ok[s] = oracle.umeyama_f32(src[s], dst[s])
+    return T, ok
+
+
+@pytest.mark.parametrize("nsets", [1, 4097])
+@pytest.mark.parametrize("k", [1, 2])
+def test_umeyama_with_fewer_than_three_points(ctx, oracle, k, nsets):
+    src, dst = _umeyama_sets(nsets, k, 5)
+    T, valid = ctx.umeyama_f32(src, dst)
+    To, oko = _oracle_sets(oracle, src, dst)
+    assert np.array_equal(valid, oko)
+    same_bits(T, To)
+
+
+@pytest.mark.parametrize("nsets", [1, 4097])
+@pytest.mark.parametrize("k", [3, 5, 65])
+def test_umeyama_batch_with_bad_sets_between_good_ones(ctx, oracle, k, nsets):
+    """Sets 0, the middle one and the last are NaN / coincident / collinear: their neighbours must equal their single-set
+    results, and `valid` must match the oracle's per set."""
+    src, dst = _umeyama_sets(nsets, k, 6)
+    bad = sorted({0, nsets // 2, nsets - 1})
+    line = np.outer(np.arange(k, dtype=np.float32), np.float32([1, 1, 1])) + np.float32([0, 0, 1])
+    kinds = ["nan", "coincident", "collinear"]
+    for s, kind in zip(bad, kinds):
+        if kind == "nan":
+            src[s, k // 2, 1] = np.nan
+        elif kind == "coincident":
+            src[s], dst[s] = np.float32(1.0), np.float32(2.0)
+        else:
+            src[s], dst[s] = line, line + np.float32(0.5)
+    T, valid = ctx.umeyama_f32(src, dst)
+    To, oko = _oracle_sets(oracle, src, dst)
+    assert np.array_equal(valid, oko) and not valid[0]              # (the NaN set is invalid: identity)
+    same_bits(T, To)
+    assert np.array_equal(T[0], np.eye(4, dtype=np.float32))
+    for s in sorted({min(b + d, nsets - 1) for b in bad for d in (-1, 0, 1) if b + d >= 0}):
+        Ts, oks = ctx.umeyama_f32(src[s], dst[s])                   # the same set alone
+        assert oks == bool(valid[s])
+        same_bits(Ts, T[s])
+
+
+def test_umeyama_with_no_points(ctx, oracle):
+    """k = 0: 1 / k = inf and inf * 0 = NaN in the means and the covariance; the SVD of an all-NaN matrix takes no rotation
+    (every comparison is false), so R = I with a NaN translation -- and T(0,0) is no NaN: `valid`, on both sides."""
+    empty = np.zeros((3, 0, 3), np.float32)
+    T, valid = ctx.umeyama_f32(empty, empty)
+    To, oko = _oracle_sets(oracle, empty, empty)
+    assert np.array_equal(valid, oko)
+    same_bits(T, To)
+    assert np.array_equal(T[:, :3, :3], np.tile(np.eye(3, dtype=np.float32), (3, 1, 1))) and np.isnan(T[:, :3, 3]).all()
