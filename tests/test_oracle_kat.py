@@ -123,6 +123,32 @@ def test_eval_errors_agree_with_is_inlier(oracle):
         assert not oracle.is_inlier(1, T, TUM_FR1_K, pp, cp, 1.0, big)
 
 
+def test_eval_errors_under_a_general_pose_equal_the_float64_model(oracle):
+    """The three error values (RANSAC.cpp:266-272,346-366) under a 30 degree / 0.5 m pose and a camera with fy = 0.8 fx and
+    cx != cy against tests/ransac_model_f64.py, which is written from the reference and shares nothing with the oracle.  At
+    T = I a swapped T / T^-1, a swapped image axis or the wrong focal length cannot show; here each moves a value by far more
+    than the margin: W (measured, see the model file) of the value or of the shipped threshold (0.04 m, 2 px), whichever is
+    larger -- what a decision next to a threshold can feel."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import ransac_model_f64 as rm
+    prev, cur, R, t = rm.make_input(rm.CLASSES[0])
+    T = np.eye(4, dtype=np.float32)
+    T[:3, :3], T[:3, 3] = R, t
+    keep = rm.depth_filter(prev, cur, np.arange(len(prev)), np.arange(len(prev)))
+    P, C = prev[keep].astype(np.float64), cur[keep].astype(np.float64)
+    T64 = T.astype(np.float64)                     # the pose as the oracle is handed it
+    want = np.stack(rm.errors(T64[None, :3, :3], T64[None, :3, 3], P, C, rm.K_SKEW.astype(np.float64)), -1)[0]
+    got = np.stack([oracle.eval_errors(T, rm.K_SKEW, prev[i], cur[i]) for i in keep])
+    tol = rm.W * np.maximum(want, [0.04, 2.0, 2.0])
+    assert (np.abs(got - want) <= tol).all(), np.abs((got - want) / tol).max()
+    assert (want[:, 0] < 0.04).sum() > 50 and (want[:, 0] > 0.04).sum() > 50      # both sides of the threshold
+    for mutation in ("no_inverse", "real_new_from_prev", "fx_for_v"):           # ... and a wrong formula is far outside
+        other = np.stack(rm.errors(T64[None, :3, :3], T64[None, :3, 3], P, C, rm.K_SKEW.astype(np.float64), mutation), -1)[0]
+        assert (np.abs(got - other) > tol).sum() > 100, mutation
+
+
 def test_ransac_iteration_table(oracle):
     table = {0.15: 1157, 0.2: 487, 0.25: 248, 0.3: 142, 0.4: 59, 0.5: 29, 0.6: 16, 0.7: 9, 0.8: 5, 0.9: 2}
     for r, it in table.items():
