@@ -405,6 +405,61 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
                        const float *K, const PsFrameSet *frames,
                        const int32_t *pairs, int P, const PsPairResults *out);
 
+/* ---- A1 for FLOAT descriptors (SURF / SIFT): MatcherOpenCV::performMatching, src/Matcher/matcherOpenCV.cpp:198-206, with the
+ * matcher the plugin builds for those two settings, cv::BFMatcher(cv::NORM_L2, crossCheck = true) (matcherOpenCV.cpp:100-102).
+ * The semantics are RESTATED, not compiled against an OpenCV:
+ *   L2sqr(a, b) in float, every operation rounded separately, no FMA, in the order of OpenCV 3.0 - 3.3's SSE2 normL2Sqr_: eight
+ *     lane accumulators over the blocks of eight elements, d = ((s0 + s1) + s2) + s3 over s[i] = acc0[i] + acc1[i], then
+ *     d += ((t0^2 + t1^2) + t2^2) + t3^2 over blocks of four differences, then d += t^2 per element;
+ *   dist = sqrtf(L2sqr), correctly rounded; every comparison is made on dist (two different sums may share a square root);
+ *   step 1: each train row takes the query row with the least dist < FLT_MAX, ties to the lowest index (NaN, +inf and values
+ *     >= FLT_MAX are never taken; a train row without an admissible query takes nobody);
+ *   step 2: each query row keeps the train row with the least dist among those that took it, ties to the lowest index;
+ *   step 3: DMatch(q, t, 0, dist) in ascending q.
+ * Every distance is computed value-exactly by HIP kernels (no CPU path): outputs are byte for byte the restatement's.
+ * Host pointers, synchronous; rows are dim floats wide, 1 <= dim <= PS_MAX_L2_DIM, with a row pitch of qstep / tstep BYTES
+ * (cv::Mat::step, >= dim x 4).  out must hold nq entries; *nout receives the number written.
+ * Option "matcher_l2" (environment PUTSLAM_HIP_MATCHER_L2, read at context creation): 1 (default) = for dim 64 / 128 a
+ * matrix-core prefilter (v_mfma_f32_32x32x2_f32) lists, per train row, the queries a proven error band cannot exclude, and only
+ * those are evaluated value-exactly; 0 = every (t, q) is.  The bytes are the same; "matcher_l2_used" (read only) reports the form
+ * the last call took.
+ * dim < 1, a pitch below a row, NULL where an array is needed -> PS_ERR_BAD_ARG; dim > PS_MAX_L2_DIM or more than PS_MAX_KPTS
+ * rows -> PS_ERR_UNSUPPORTED; *nout = 0 on error. */
+#define PS_MAX_L2_DIM 512
+int ps_match_l2_f32(PsContext *ctx, const float *query, int nq, size_t qstepBytes, const float *train, int nt, size_t tstepBytes,
+                    int dim, PsDMatch *out, int *nout);
+
+/* A frame set with float descriptors; all pointers are DEVICE pointers.  THE RULES: desc is 4-byte aligned; descRowStride is a
+ * multiple of 4 and >= dim x 4 (0 = dense, dim x 4); descFrameStride is a multiple of 4 and >= maxKpts x the row stride (0 =
+ * dense); ptsFrameStride is a multiple of 4 and >= maxKpts x 12 (0 = dense), its quarter fits an int.  What lies between the
+ * rows is never read. */
+typedef struct PsFrameSetF32 {
+    const float *desc;        /* numFrames x maxKpts rows of dim floats */
+    const float *pts;         /* numFrames x maxKpts x 3 floats, back-projected 3-D points (may be NULL for ps_match_l2_device) */
+    const int32_t *nkpts;     /* numFrames keypoint counts (<= maxKpts) */
+    int32_t numFrames;
+    int32_t maxKpts;          /* row capacity per frame; also the capacity of per-pair outputs */
+    int32_t dim;              /* floats per descriptor: 64 (SURF), 128 (SIFT / extended SURF), any 1 .. PS_MAX_L2_DIM */
+    size_t descRowStride;     /* bytes between rows, 0 = dense */
+    size_t descFrameStride;   /* bytes between frames' descriptor blocks, 0 = dense */
+    size_t ptsFrameStride;    /* bytes between frames' point blocks, 0 = dense */
+} PsFrameSetF32;
+size_t ps_abi_sizeof_frameset_f32(void);
+
+/* matcherOpenCV.cpp:100-102,198-206 for P (prevFrame, curFrame) pairs of a device-resident set: matches (P x maxKpts) and
+ * numMatches (P) are DEVICE arrays; asynchronous on the context's stream, nothing is copied to or from the host.  Pair p's list
+ * is byte for byte ps_match_l2_f32's on the two frames.  A pair that names a frame outside the set has no matches.
+ * NULL where an array is needed, P < 0, dim < 1, a bad stride -> PS_ERR_BAD_ARG; dim > PS_MAX_L2_DIM or maxKpts > PS_MAX_KPTS ->
+ * PS_ERR_UNSUPPORTED; the outputs are not touched.  P == 0 is PS_OK. */
+int ps_match_l2_device(PsContext *ctx, const PsFrameSetF32 *frames, const int32_t *pairs, int P, PsDMatch *matches,
+                       int32_t *numMatches);
+
+/* The body of ps_vo_pairs_device with the float matcher (matcherOpenCV.cpp:100-102,198-206) in front: pair p draws from
+ * cfg->seed + p, and every output is byte for byte what ps_match_l2_f32 followed by ps_ransac_rigid3d with seed + p gives.
+ * Argument rules as ps_match_l2_device (frames->pts is needed here). */
+int ps_vo_pairs_l2_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                          const PsFrameSetF32 *frames, const int32_t *pairs, int P, const PsPairResults *out);
+
 /* ---- N2 for a device-resident batch: Matcher::matchXYZ (src/Matcher/matcher.cpp:606-798) for P (map view, frame) pairs --
  * guided matching, then the estimator -- as ONE launch chain.  PUTSLAM calls matchXYZ once per frame and retries it up to ten
  * times with a wider sphere and a looser ratio while the inlier ratio stays under 0.1 (src/PUTSLAM/PUTSLAM.cpp:788-798): the
@@ -904,6 +959,15 @@ int ps_debug_stage_order(PsContext *ctx, int P, int cap, int32_t *perm, int32_t 
  * wrote into a private buffer: out16[0..3] = ps_crosscheck_prep (start, best[q] built, matches compacted + records written,
  * end), out16[4..9] = ps_select_refit (start, selection replayed, winner's inlier pass, refit, re-selection, end). */
 int ps_debug_stamps(PsContext *ctx, uint64_t *out16);
+/* Diagnostic of the float matcher's matrix-core prefilter (option "matcher_l2" = 1, dim 64 / 128): for
+ * one pair of host arrays as ps_match_l2_f32 takes them, the prefilter's estimate s~(t, q) of the squared distance and its band
+ * E(t, q), as two nt x nq row-major float arrays (train row major).  The band's claim: |s~ - S| <= E and |L2sqr - S| <= E for
+ * the real-number S.  dim other than 64 / 128 -> PS_ERR_UNSUPPORTED. */
+int ps_debug_l2_band(PsContext *ctx, const float *query, int nq, size_t qstepBytes, const float *train, int nt, size_t tstepBytes,
+                     int dim, float *stilde, float *band);
+/* Diagnostic counters of the last float matching call that ran the prefilter while option "l2_stats" was 1: out3 = {train rows
+ * swept exactly, candidate (t, q) evaluations of the other rows, rows whose candidate list overflowed}. */
+int ps_debug_l2_stats(PsContext *ctx, uint64_t *out3);
 /* DBScan's neighbour predicate in the square domain: the least double s* with (double)(float)sqrt(s*) >= eps (0 for eps <= 0
  * or NaN), so that (float)sqrt(s) < eps  <=>  s < s*.  Pure host arithmetic. */
 double ps_debug_dbscan_bound(double eps);

@@ -10,6 +10,7 @@ import numpy as np
 PS_OK = 0
 PS_DESC_BYTES = 32
 PS_MAX_KPTS = 16384
+PS_MAX_L2_DIM = 512
 
 # RANSAC::ERROR_VERSION (reference include/putslam/TransformEst/RANSAC.h:22)
 EUCLIDEAN_ERROR = 0
@@ -54,6 +55,12 @@ class PsFrameSet(C.Structure):
     _fields_ = [("desc", C.c_void_p), ("pts", C.c_void_p), ("nkpts", C.c_void_p),
                 ("numFrames", C.c_int32), ("maxKpts", C.c_int32),
                 ("descFrameStride", C.c_size_t), ("ptsFrameStride", C.c_size_t)]     # ABI 2: 0 = dense frames
+
+
+class PsFrameSetF32(C.Structure):
+    _fields_ = [("desc", C.c_void_p), ("pts", C.c_void_p), ("nkpts", C.c_void_p),
+                ("numFrames", C.c_int32), ("maxKpts", C.c_int32), ("dim", C.c_int32),
+                ("descRowStride", C.c_size_t), ("descFrameStride", C.c_size_t), ("ptsFrameStride", C.c_size_t)]   # 0 = dense
 
 
 class PsPairResults(C.Structure):

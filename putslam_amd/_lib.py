@@ -6,7 +6,7 @@ object is missing the import fails loudly and tells the caller how to build it.
 import ctypes as C
 import os
 
-from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsMapStore,
+from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsMapStore,
                    PsMapViewOut, PsMapViewRequest, PsPairResults, PsPoseSetOut, PsPoseSetRequest, PsRansacConfig, PsRansacParams,
                    PsRansacStats)
 
@@ -44,7 +44,8 @@ EXPORTED = [
     "ps_level_thresholds", "ps_view_angles", "ps_map_views_device", "ps_frame_levels_device",
     "ps_abi_sizeof_map_store", "ps_abi_sizeof_map_view_request", "ps_abi_sizeof_map_view_out",
     "ps_pose_sets_device", "ps_loop_pairs_device",
-    "ps_abi_sizeof_pose_set_request", "ps_abi_sizeof_pose_set_out", "ps_abi_sizeof_loop_batch", "ps_abi_sizeof_loop_results",
+    "ps_abi_sizeof_pose_set_request", "ps_abi_sizeof_pose_set_out", "ps_abi_sizeof_loop_batch", "ps_abi_sizeof_loop_results",    "ps_match_l2_f32", "ps_match_l2_device", "ps_vo_pairs_l2_device", "ps_abi_sizeof_frameset_f32", "ps_debug_l2_band",
+    "ps_debug_l2_stats",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -52,6 +53,8 @@ ABI_STRUCTS = dict(dmatch=PsDMatch, params=PsRansacParams, config=PsRansacConfig
                    results=PsPairResults, host_results=PsHostPairResults, map_batch=PsMapBatch, exclusion_rule=PsExclusionRule,
                    map_store=PsMapStore, map_view_request=PsMapViewRequest, map_view_out=PsMapViewOut,
                    pose_set_request=PsPoseSetRequest, pose_set_out=PsPoseSetOut, loop_batch=PsLoopBatch, loop_results=PsLoopResults)
+# ... and of the float-descriptor matcher's frame set (a table of its own: ABI_STRUCTS is the ABI-2 set the layout tests count)
+ABI_STRUCTS_F32 = dict(frameset_f32=PsFrameSetF32)
 
 _lib = None
 _by_path = {}
@@ -206,6 +209,12 @@ def load_path(path):
     L.ps_pose_sets_device.argtypes = [vp, C.POINTER(PsMapStore), C.POINTER(PsPoseSetRequest), C.POINTER(PsPoseSetOut)]
     L.ps_loop_pairs_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsLoopBatch),
                                        C.POINTER(PsLoopResults)]
+    L.ps_match_l2_f32.argtypes = [vp, vp, i32, sz, vp, i32, sz, i32, vp, C.POINTER(i32)]
+    L.ps_debug_l2_band.argtypes = [vp, vp, i32, sz, vp, i32, sz, i32, vp, vp]
+    L.ps_debug_l2_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.ps_match_l2_device.argtypes = [vp, C.POINTER(PsFrameSetF32), vp, i32, vp, vp]
+    L.ps_vo_pairs_l2_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsFrameSetF32), vp, i32,
+                                        C.POINTER(PsPairResults)]
     L.ps_batch_queue_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.ps_batch_queue_destroy.argtypes = [vp]
     L.ps_batch_queue_destroy.restype = None
@@ -226,7 +235,7 @@ def load_path(path):
     L.ps_last_kernel_times_ms.argtypes = [vp, vp]
     L.ps_kernel_time_totals.argtypes = [vp, vp, vp]
     L.ps_context_enable_timing.argtypes = [vp, i32]
-    for n in ABI_STRUCTS:
+    for n in list(ABI_STRUCTS) + list(ABI_STRUCTS_F32):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -234,3 +243,7 @@ def load_path(path):
 
 def struct_sizes():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS.items()}
+
+
+def struct_sizes_f32():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_F32.items()}

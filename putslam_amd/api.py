@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, PS_SET_INVALID, PsExclusionRule, PsFrameSet,  # noqa: F401
-                   PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsPairResults, PsMapStore, PsMapViewOut, PsMapViewRequest,
+                   PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsPairResults, PsMapStore, PsMapViewOut, PsMapViewRequest,
                    PsPoseSetOut, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
 
 
@@ -239,6 +239,35 @@ class Context:
         ts = train.strides[0] if nt else 32
         self._chk(self._L.ps_match_hamming256(self._h, _p(query), nq, qs, _p(train), nt, ts, _p(out), C.byref(n)))
         return out[: n.value].copy()
+
+    def match_l2(self, query, train):
+        """MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) with the SURF / SIFT matcher, BFMatcher(NORM_L2, crossCheck)
+        (matcherOpenCV.cpp:100-102): query = prev rows, train = cur rows (float32, the same number of columns, 1 .. 512)."""
+        assert query.dtype == np.float32 and train.dtype == np.float32 and query.ndim == 2 and train.ndim == 2
+        nq, nt, dim = query.shape[0], train.shape[0], query.shape[1]
+        assert train.shape[1] == dim and (nq == 0 or query.strides[1] == 4) and (nt == 0 or train.strides[1] == 4)
+        out = np.zeros(max(nq, 1), DMATCH_DTYPE)
+        n = C.c_int(0)
+        qs = query.strides[0] if nq else dim * 4
+        ts = train.strides[0] if nt else dim * 4
+        self._chk(self._L.ps_match_l2_f32(self._h, _p(query), nq, qs, _p(train), nt, ts, dim, _p(out), C.byref(n)))
+        return out[: n.value].copy()
+
+    def l2_stats(self):
+        """(train rows swept exactly, candidate evaluations, rows whose candidate list overflowed) of the last float matching call
+        that ran the prefilter with option "l2_stats" on."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self._L.ps_debug_l2_stats(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def debug_l2_band(self, query, train):
+        """The prefilter's s~ and E for every (train row, query row) of one pair: two (nt, nq) float32 arrays (dim 64 / 128)."""
+        query = np.ascontiguousarray(query, np.float32)
+        train = np.ascontiguousarray(train, np.float32)
+        nq, nt, dim = query.shape[0], train.shape[0], query.shape[1]
+        s, e = np.zeros((nt, nq), np.float32), np.zeros((nt, nq), np.float32)
+        self._chk(self._L.ps_debug_l2_band(self._h, _p(query), nq, dim * 4, _p(train), nt, dim * 4, dim, _p(s), _p(e)))
+        return s, e
 
     # ---- A4..A9, A11 ----
     def ransac_rigid3d(self, params, cfg, K, prev, cur, matches):
@@ -510,6 +539,19 @@ class Context:
         fs, res = frames.struct(), out.struct()
         self._chk(self._L.ps_vo_pairs_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(fs),
                                              C.c_void_p(pairs_dev_ptr), int(P), C.byref(res)))
+
+    def match_l2_device(self, frames: "DeviceFramesF32", pairs_dev_ptr, P, matches_ptr, num_matches_ptr):
+        """ps_match_l2_device: the float-descriptor cross-check matching of every pair; asynchronous, device pointers."""
+        fs = frames.struct()
+        self._chk(self._L.ps_match_l2_device(self._h, C.byref(fs), C.c_void_p(pairs_dev_ptr), int(P), C.c_void_p(matches_ptr),
+                                             C.c_void_p(num_matches_ptr)))
+
+    def vo_pairs_l2_device(self, params, cfg, K, frames: "DeviceFramesF32", pairs_dev_ptr, P, out: "DeviceResults"):
+        """ps_vo_pairs_l2_device: ps_vo_pairs_device with the float-descriptor matcher in front."""
+        K = None if K is None else np.ascontiguousarray(K, np.float32)
+        fs, res = frames.struct(), out.struct()
+        self._chk(self._L.ps_vo_pairs_l2_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(fs),
+                                                C.c_void_p(pairs_dev_ptr), int(P), C.byref(res)))
 
     # ---- N2, device-resident batch ----
     def match_xyz_device(self, batch: "DeviceMapBatch", matches_ptr, num_matches_ptr):
@@ -823,6 +865,19 @@ class DeviceFrames:
     def struct(self):
         return PsFrameSet(self.desc_ptr, self.pts_ptr, self.nkpts_ptr, self.num_frames, self.max_kpts, self.desc_stride,
                           self.pts_stride)
+
+
+class DeviceFramesF32:
+    """Raw device pointers of a frame set with float descriptors (PsFrameSetF32); strides in bytes, 0 = dense."""
+
+    def __init__(self, desc_ptr, pts_ptr, nkpts_ptr, num_frames, max_kpts, dim, row_stride=0, desc_stride=0, pts_stride=0):
+        self.desc_ptr, self.pts_ptr, self.nkpts_ptr = desc_ptr, pts_ptr, nkpts_ptr
+        self.num_frames, self.max_kpts, self.dim = int(num_frames), int(max_kpts), int(dim)
+        self.row_stride, self.desc_stride, self.pts_stride = int(row_stride), int(desc_stride), int(pts_stride)
+
+    def struct(self):
+        return PsFrameSetF32(self.desc_ptr, self.pts_ptr, self.nkpts_ptr, self.num_frames, self.max_kpts, self.dim,
+                             self.row_stride, self.desc_stride, self.pts_stride)
 
 
 class DeviceResults:

@@ -1096,9 +1096,38 @@ FrameMatcherHIP::FrameMatcherHIP(const std::string, const std::string) : FrameMa
 FrameMatcherHIP::~FrameMatcherHIP(void) {}
 const std::string &FrameMatcherHIP::getName() const { return name; }
 
+// matcherOpenCV.cpp:97-105 builds BFMatcher(NORM_L2, true) for the float descriptors (SURF / SIFT) and the Hamming matcher for the
+// binary ones; :198-206 is the same call on either.  Here the Mats' type decides.
 std::vector<cv::DMatch> FrameMatcherHIP::performMatching(cv::Mat prevDescriptors, cv::Mat descriptors)
 {
+    if (prevDescriptors.type() == CV_32F && descriptors.type() == CV_32F) return l2CrossCheckMatch(prevDescriptors, descriptors);
     return hammingCrossCheckMatch(prevDescriptors, descriptors);
+}
+
+// MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) with the matcher of matcherOpenCV.cpp:100-102, cv::BFMatcher(cv::NORM_L2,
+// true), on CV_32F descriptor Mats of 1 .. PS_MAX_L2_DIM columns (ps_match_l2_f32).
+std::vector<cv::DMatch> l2CrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors)
+{
+    std::vector<cv::DMatch> matches;
+    if (prevDescriptors.empty() || descriptors.empty()) return matches;
+    if (prevDescriptors.type() != CV_32F || descriptors.type() != CV_32F || prevDescriptors.cols != descriptors.cols) {
+        std::cerr << "putslam_hip: l2CrossCheckMatch takes two CV_32F descriptor Mats of the same width" << std::endl;
+        return matches;
+    }
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return matches;
+    matches.resize((size_t)prevDescriptors.rows);
+    int n = 0;
+    status = ps_match_l2_f32(ctx, reinterpret_cast<const float *>(prevDescriptors.data), prevDescriptors.rows, (size_t)prevDescriptors.step,
+                             reinterpret_cast<const float *>(descriptors.data), descriptors.rows, (size_t)descriptors.step,
+                             prevDescriptors.cols, reinterpret_cast<PsDMatch *>(matches.data()), &n);
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        n = 0;
+    }
+    matches.resize((size_t)n);
+    return matches;
 }
 
 // MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) as a free function: the body the reference's own class

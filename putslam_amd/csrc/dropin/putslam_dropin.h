@@ -344,6 +344,8 @@ int chooseFeaturesToAddToMap(const std::vector<Eigen::Vector3f> &feature3D, cons
 
 // MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) as a free function over the calling thread's context.
 std::vector<cv::DMatch> hammingCrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors);
+// ... and with the float descriptors' matcher, cv::BFMatcher(cv::NORM_L2, true) (matcherOpenCV.cpp:100-102): CV_32F Mats.
+std::vector<cv::DMatch> l2CrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors);
 
 // Library-owned singletons with the reference factories' ownership rules (raw pointer returned, a second call
 // replaces the instance: matcherOpenCV.cpp:20-47): one for the VO thread, one for the loop-closure thread.
@@ -361,8 +363,9 @@ struct VOTrajectory {
 };
 
 // The concrete matcher: performMatching = cv::BFMatcher(NORM_HAMMING, crossCheck = true).match(prev, cur) on the GPU
-// (the body MatcherOpenCV::performMatching gets in a PUTSLAM build, matcherOpenCV.cpp:198-206), match() fused with the
-// RANSAC against the frame resident in HBM.
+// (the body MatcherOpenCV::performMatching gets in a PUTSLAM build, matcherOpenCV.cpp:198-206) for CV_8U descriptor Mats and
+// cv::BFMatcher(NORM_L2, true) for CV_32F ones (matcherOpenCV.cpp:100-102); match() fused with the RANSAC against the frame
+// resident in HBM (binary descriptors only).
 class FrameMatcherHIP : public FrameMatcher {
   public:
     typedef std::unique_ptr<FrameMatcherHIP> Ptr;

@@ -1256,6 +1256,7 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
 #include "ps_exclusion.h"    // ps_exclude(_device) and the three rules (DBScan's bound and union-find)
 #include "ps_map_view.h"     // ps_map_views_device / ps_frame_levels_device
 #include "ps_loop_closure.h" // ps_pose_sets_device / ps_loop_pairs_device (the plan and the stages above)
+#include "ps_match_l2.h"     // ps_match_l2_f32 / ps_match_l2_device / ps_vo_pairs_l2_device (the plan and the stages above)
 
 // Launch attributes of the kernels that need them (ps_internal.h; called once per context).
 extern "C" void psi_kernel_attributes(void)
@@ -1266,4 +1267,5 @@ extern "C" void psi_kernel_attributes(void)
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, PS_MAX_KPTS * 4);
     dbscan_kernel_attributes();
     exclusion_kernel_attributes();
+    l2_kernel_attributes();
 }

@@ -141,6 +141,8 @@ struct OptDesc {
 const OptDesc kOptions[] = {
     {"matcher", "MATCHER", &PsContext::matcher, 0, 2, "matcher: 0 (VALU), 1 (MFMA) or 2 (by batch size)"},
     {"matcher_fused", "MATCHER_FUSED", &PsContext::matcherFused, 0, 1, "matcher_fused: 0 or 1"},
+    {"matcher_l2", "MATCHER_L2", &PsContext::matcherL2, 0, 1, "matcher_l2: 0 (value-exact sweep) or 1 (matrix-core prefilter + value-exact evaluation)"},
+    {"l2_stats", nullptr, &PsContext::l2Stats, 0, 1, "l2_stats: 0 or 1"},
     {"score", "SCORE", &PsContext::scoreFast, 0, 1, "score: 0 (value-exact kernels) or 1 (decision-exact kernels)"},
     {"score_stats", nullptr, &PsContext::scoreStats, 0, 1, "score_stats: 0 or 1"},
     {"prune", "PRUNE", &PsContext::prune, 0, 2, "prune: 0 (complete scoring), 1 (staged from the cost model's batch size on) or 2 (staged whenever possible)"},
@@ -259,7 +261,7 @@ void ps_context_destroy(PsContext *ctx)
     Buf *all[] = {&ctx->keys, &ctx->recA, &ctx->recB, &ctx->recC, &ctx->recD, &ctx->recE, &ctx->recF, &ctx->recShadow, &ctx->models, &ctx->survA, &ctx->survB, &ctx->survN, &ctx->recF2, &ctx->permBuf, &ctx->prefInfo, &ctx->frontRec, &ctx->validMask, &ctx->stamps, &ctx->dbgCnt, &ctx->bailCnt, &ctx->counts, &ctx->mvalid,
                   &ctx->cmax, &ctx->idxList, &ctx->raw, &ctx->xq, &ctx->tabR, &ctx->tabU, &ctx->sDesc, &ctx->sNk,
                   &ctx->sMatches, &ctx->sNumM, &ctx->sMask, &ctx->sPose, &ctx->sStats,
-                  &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab, &ctx->poseSets, &ctx->loopPairs};
+                  &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab, &ctx->poseSets, &ctx->loopPairs, &ctx->l2Keys, &ctx->l2Img, &ctx->l2Norms, &ctx->l2List, &ctx->l2ListLo, &ctx->l2Count, &ctx->l2Stat};
     for (Buf *b : all) release(*b);
     for (hipEvent_t e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
@@ -318,6 +320,7 @@ int ps_context_get_option(const PsContext *ctx, const char *name)
 {
     if (!ctx || !name) return PS_ERR_BAD_ARG;
     if (strcmp(name, "matcher_used") == 0) return ctx->matcherUsed;
+    if (strcmp(name, "matcher_l2_used") == 0) return ctx->matcherL2Used; // the form the last float matching call took
     if (strcmp(name, "stamps") == 0) return ctx->stampsOn;
     if (strcmp(name, "last_staged_pairs") == 0) return ctx->stagedP;       // pairs of the last scoring step if it was staged, else 0
     if (strcmp(name, "hopeless") == 0) return ctx->hopeless;               // the "nothing to gain" policy's current state
@@ -326,7 +329,7 @@ int ps_context_get_option(const PsContext *ctx, const char *name)
                             &ctx->survA, &ctx->survB, &ctx->survN, &ctx->recF2, &ctx->permBuf, &ctx->prefInfo, &ctx->frontRec,
                             &ctx->validMask, &ctx->stamps, &ctx->dbgCnt, &ctx->bailCnt, &ctx->counts, &ctx->mvalid, &ctx->cmax,
                             &ctx->idxList, &ctx->raw, &ctx->xq, &ctx->tabR, &ctx->tabU, &ctx->sDesc, &ctx->sNk, &ctx->sMatches,
-                            &ctx->sNumM, &ctx->sMask, &ctx->sPose, &ctx->sStats, &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab, &ctx->poseSets, &ctx->loopPairs};
+                            &ctx->sNumM, &ctx->sMask, &ctx->sPose, &ctx->sStats, &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab, &ctx->poseSets, &ctx->loopPairs, &ctx->l2Keys, &ctx->l2Img, &ctx->l2Norms, &ctx->l2List, &ctx->l2ListLo, &ctx->l2Count, &ctx->l2Stat};
         size_t sum = 0;
         for (const Buf *b : all) sum += b->cap;
         return (int)((sum + (((size_t)1 << 20) - 1)) >> 20);

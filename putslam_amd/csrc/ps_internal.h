@@ -56,6 +56,9 @@ struct PsContext {
     Buf levelTab;      // the level rule's constant block (psdev::LevelBlock), filled at the first call that needs it
     Buf poseSets;      // pose sets (ps_loop_closure.h): the pose -> set table, its chains, and per chunk of 256 features and set a count
     Buf loopPairs;     // loop-closure verifier (ps_loop_closure.h): the effective pairs of the gate, [L][2]
+    Buf l2Keys;        // float-descriptor matcher (ps_match_l2.h): per pair, query split and train row the nearest query, (distance bits, index)
+    Buf l2Img, l2Norms, l2List, l2ListLo, l2Count, l2Stat; // ... its matrix-core prefilter: operand image and squared norms per frame, candidate lists
+                                                 // and their counts per pair, train row and slot, the diagnostic counters
     // cached stop tables
     int tabEstimator = -1, tabH = -1, tabRN = 0, tabUN = 0, tabIter0 = 0;
     double tabMinRatio = -1.0;
@@ -80,6 +83,11 @@ struct PsContext {
     // 1 = the decision-exact kernels (ps_score_fast.h / ps_score_euclid.h, default), 0 = the value-exact ps_ransac_score<MODE>
     // (the matrix-core scoring experiment of round 2 -- split-f16 transforms on v_mfma_f32_32x32x16_f16, correct, no gain on
     // the headline -- left the tree in round 4: profiles/variants/ps_score_mfma.h.txt)
+    // float-descriptor matcher (ps_match_l2.h, option "matcher_l2"): 1 = matrix-core prefilter + value-exact evaluation of what it
+    // lists (dim 64 / 128; other dims take the sweep), 0 = the value-exact sweep ps_l2_nn.  Identical bytes either way.
+    int matcherL2 = 1;
+    int matcherL2Used = 0; // what the last float matching call ran (option "matcher_l2_used", read only)
+    int l2Stats = 0;       // option "l2_stats": the prefilter counts what it hands on (ps_debug_l2_stats)
     int scoreFast = 1;
     int scoreStats = 0;
     // pruned scoring (ps_score_euclid.h): 1 = large batches score the first 256 hypotheses of every pair completely and

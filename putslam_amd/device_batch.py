@@ -107,6 +107,37 @@ class PackedFrameSetDevice(FrameSet):
         self.nkpts = torch.from_numpy(np.ascontiguousarray(nkpts, np.int32)).to(self.device)
 
 
+class FrameSetF32Device:
+    """Float descriptors (F, cap, dim) f32, pts (F, cap, 3) f32 (or None: matching only) and nkpts (F,) i32 resident in HBM
+    (PsFrameSetF32).  row_floats > dim: the rows lie row_floats floats apart and what lies between them is filled with `pad`
+    (never read by the library)."""
+
+    def __init__(self, desc, pts, nkpts, device="cuda:0", row_floats=None, pad=np.nan):
+        desc = np.ascontiguousarray(desc, np.float32)
+        assert desc.ndim == 3
+        self.device = torch.device(device)
+        self.num_frames, self.max_kpts, self.dim = desc.shape
+        self.row_floats = self.dim if row_floats is None else int(row_floats)
+        assert self.row_floats >= self.dim
+        if self.row_floats != self.dim:
+            wide = np.full((self.num_frames, self.max_kpts, self.row_floats), pad, np.float32)
+            wide[:, :, :self.dim] = desc
+            desc = wide
+        self.desc = torch.from_numpy(desc).to(self.device)
+        self.pts = None
+        if pts is not None:
+            pts = np.ascontiguousarray(pts, np.float32)
+            assert pts.shape == (self.num_frames, self.max_kpts, 3)
+            self.pts = torch.from_numpy(pts).to(self.device)
+        self.nkpts = torch.from_numpy(np.ascontiguousarray(nkpts, np.int32)).to(self.device)
+
+    def view(self):
+        dense = self.row_floats == self.dim
+        return api.DeviceFramesF32(self.desc.data_ptr(), 0 if self.pts is None else self.pts.data_ptr(), self.nkpts.data_ptr(),
+                                   self.num_frames, self.max_kpts, self.dim, 0 if dense else self.row_floats * 4,
+                                   0 if dense else self.max_kpts * self.row_floats * 4, 0)
+
+
 class PairResultsDevice:
     """The per-pair output block in HBM (PsPairResults) for P pairs of `cap` rows: matches (P, cap, 16) u8, num_matches (P,)
     i32, mask (P, cap) u8, pose (P, 16) f32, stats (P, sizeof PsRansacStats) u8.  A subclass uploads and fills what else it
@@ -189,6 +220,21 @@ def run_pairs(ctx, params, cfg, K, frames: FrameSetDevice, batch: PairBatchDevic
     already queued on torch's current stream; the current stream waits for the results."""
     _on_torch_stream(ctx, frames.device,
                      lambda: ctx.vo_pairs_device(params, cfg, K, frames.view(), batch.pairs.data_ptr(), batch.P, batch.view()),
+                     use_torch_stream)
+
+
+def run_vo_pairs_l2(ctx, params, cfg, K, frames: FrameSetF32Device, batch: PairBatchDevice, use_torch_stream=True):
+    """run_pairs for frames with float descriptors (ps_vo_pairs_l2_device)."""
+    _on_torch_stream(ctx, frames.device,
+                     lambda: ctx.vo_pairs_l2_device(params, cfg, K, frames.view(), batch.pairs.data_ptr(), batch.P, batch.view()),
+                     use_torch_stream)
+
+
+def run_match_l2(ctx, frames: FrameSetF32Device, batch: PairBatchDevice, use_torch_stream=True):
+    """The matches alone (ps_match_l2_device) into batch.matches / batch.num_matches."""
+    _on_torch_stream(ctx, frames.device,
+                     lambda: ctx.match_l2_device(frames.view(), batch.pairs.data_ptr(), batch.P, batch.matches.data_ptr(),
+                                                 batch.num_matches.data_ptr()),
                      use_torch_stream)
 
 

@@ -118,3 +118,54 @@ def make_sequence(num_frames, n, config=3, index=0, **kw):
     pairs = np.stack([np.arange(num_frames - 1), np.arange(1, num_frames)], axis=1).astype(np.int32)
     gt = np.stack([f["T_prev_from_cur"] for f in frames[1:]]) if num_frames > 1 else np.zeros((0, 4, 4))
     return dict(desc=desc, pts=pts, nkpts=nk, pairs=pairs, gt=gt, frames=frames)
+
+
+# ---- float descriptors (SURF / SIFT), for the NORM_L2 matcher -------------------------------------------------------------
+FLOAT_DIM = {"surf": 64, "sift": 128}
+
+
+def float_rows(rng, n, kind):
+    """n fresh descriptors: "surf" -- standard normal rows scaled to unit length, 64 wide; "sift" -- |N(0, 1)| scaled to norm 512,
+    floored and clipped to 0 .. 255, 128 wide."""
+    x = rng.standard_normal((n, FLOAT_DIM[kind]))
+    if kind == "surf":
+        return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+    x = np.abs(x)
+    return np.clip(np.floor(x * (512.0 / np.linalg.norm(x, axis=1, keepdims=True))), 0, 255).astype(np.float32)
+
+
+def float_rows_linked(rng, prev, truth, kind):
+    """One row per entry of `truth`: the noisy copy of prev[truth[i]] (surf: + 0.08 N(0, 1), renormalised; sift: + round(6 N(0, 1)),
+    clipped to 0 .. 255) where truth[i] >= 0, a fresh row elsewhere."""
+    truth = np.asarray(truth)
+    out = float_rows(rng, truth.size, kind)
+    k = np.nonzero(truth >= 0)[0]
+    src = prev[truth[k]].astype(np.float64)
+    if kind == "surf":
+        y = src + 0.08 * rng.standard_normal(src.shape)
+        out[k] = (y / np.linalg.norm(y, axis=1, keepdims=True)).astype(np.float32)
+    else:
+        out[k] = np.clip(src + np.round(6.0 * rng.standard_normal(src.shape)), 0, 255).astype(np.float32)
+    return out
+
+
+def float_scene(kind, nq, nt, index=0, replaced=0.30):
+    """(query (nq, D), train (nt, D), truth (nt,)): train rows are noisy copies of query rows, `replaced` of them fresh rows
+    (truth -1), in a random order."""
+    rng = _rng(7 if kind == "surf" else 8, index)
+    query = float_rows(rng, nq, kind)
+    truth = rng.permutation(nq)[:nt] if nt <= nq else rng.integers(0, max(nq, 1), nt)
+    truth = np.where(rng.random(nt) < replaced, -1, truth) if nq > 0 else np.full(nt, -1)
+    truth = truth[rng.permutation(nt)]
+    return query, float_rows_linked(rng, query, truth, kind), truth
+
+
+def make_float_sequence(num_frames, n, kind="surf", config=3, index=0, **kw):
+    """make_sequence with float descriptors (F, n, D) f32 linked along the same true correspondences."""
+    seq = make_sequence(num_frames, n, config=config, index=index, **kw)
+    rng = _rng(9, index)
+    rows = [float_rows(rng, n, kind)]
+    for f in seq["frames"][1:]:
+        rows.append(float_rows_linked(rng, rows[-1], f["truth"], kind))
+    seq["fdesc"] = np.stack(rows)
+    return seq
