@@ -511,6 +511,53 @@ int ps_match_xyz_device(PsContext *ctx, const PsMapBatch *b, PsDMatch *matches, 
 int ps_map_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
                         const PsMapBatch *b, const PsPairResults *out);
 
+/* ---- N2 for FLOAT descriptors (SURF / SIFT): Matcher::matchXYZ with normType = cv::NORM_L2 on CV_32F rows
+ * (matcher.cpp:625-628, :719-721, :737-739).  Candidates (sphere, level, ascending i), the emit rule, the record and its order
+ * are ps_match_xyz's; only the VALUE of a candidate differs.  It is RESTATED from OpenCV 3.x's continuous path norm() ->
+ * normL2_32f -> normL2Sqr<float, double>, not compiled against an OpenCV (tests/map_l2_ref.py):
+ *   x[k] = (float)(map[k] - cur[k]) (cv::subtract on CV_32F); v[k] = (double)x[k]; s = 0.0;
+ *   s = s + (((v0 v0 + v1 v1) + v2 v2) + v3 v3) over the blocks of four, then s = s + v v per remaining element;
+ *   value = (float)sqrt(s), a correctly rounded double square root narrowed once.
+ * Best value (:714-727): the first candidate is taken whatever its value, a later one if value < bestVal.  So a NaN value at the
+ * first candidate leaves bestVal NaN and the feature emits nothing; a NaN at a later candidate is ignored; +inf is an ordinary
+ * value.  Every candidate with acceptRatio * (double)value <= (double)bestVal is emitted as DMatch(j, i, -1, value), ordered by
+ * (j, i) (acceptRatio 0 with a +inf candidate: 0 * inf = NaN, not emitted).
+ * Host pointers, synchronous.  Rows are dim floats wide, 1 <= dim <= PS_MAX_L2_DIM, with pitches in BYTES (>= dim x 4); limits
+ * and errors as ps_match_l2_f32.  Returns PS_ERR_BAD_ARG with *nout = required capacity if cap is too small. */
+int ps_match_xyz_l2_f32(PsContext *ctx, const float *mapPos, const float *mapDesc, size_t mapDescStepBytes, const int32_t *mapLevel,
+                        int nmap, const float *curPos, const float *curDesc, size_t curDescStepBytes, const int32_t *curLevel,
+                        int ncur, int dim, double sphereRadius, double acceptRatio, PsDMatch *out, int cap, int *nout);
+
+/* PsMapBatch with float-descriptor sets (THE RULES of PsFrameSetF32 for either; pts is needed); maps.dim must equal frames.dim.
+ * A host with float descriptors fills `maps` itself: PsMapStore / ps_map_views_device hold binary rows only. */
+typedef struct PsMapBatchF32 {
+    PsFrameSetF32 maps;           /* "map views": desc = the descriptor chosen for each visible feature, pts = (float) casts of
+                                     MapFeature::position in the camera frame, nkpts = features per view */
+    const int32_t *mapLevel;      /* maps.numFrames x maps.maxKpts predicted levels */
+    PsFrameSetF32 frames;         /* current frames: descriptors + back-projected points */
+    const int32_t *curLevel;      /* frames.numFrames x frames.maxKpts */
+    const int32_t *pairs;         /* P x 2 (map view, frame), device */
+    int32_t P;
+    int32_t maxMatches;           /* row capacity of out->matches / out->inlierMask for every pair */
+    float radiusBound;            /* ps_map_sphere_bound(radius), used when radiusBoundPerPair is NULL */
+    double acceptRatio;           /* used when acceptRatioPerPair is NULL */
+    const float *radiusBoundPerPair;   /* device, P, or NULL */
+    const double *acceptRatioPerPair;  /* device, P, or NULL */
+} PsMapBatchF32;
+size_t ps_abi_sizeof_map_batch_f32(void);
+
+/* ps_match_xyz_device / ps_map_pairs_device for a PsMapBatchF32: the same contract -- device pointers, asynchronous on the
+ * context's stream, nothing copied, no synchronisation; numMatches[p] = -(count) for a pair over maxMatches, which the estimator
+ * sees without matches; a pair naming a view or a frame outside its set has no matches -- with the value above.  Pair p's list
+ * is byte for byte ps_match_xyz_l2_f32's, and mask, pose and stats of ps_map_pairs_l2_device are byte for byte those of
+ * ps_match_xyz_l2_f32 followed by ps_ransac_rigid3d with cfg->seed + p.
+ * maxKpts above PS_MAX_KPTS, dim above PS_MAX_L2_DIM, maxMatches above 1 << 22 -> PS_ERR_UNSUPPORTED; dim < 1, maps.dim !=
+ * frames.dim, maxMatches < 1, a bad stride, NULL where an array is needed, P < 0 -> PS_ERR_BAD_ARG; outputs are not touched.
+ * P == 0 is PS_OK.  Scratch as the binary calls (16 B a match of staging, about 150 B a match of records), shared with them. */
+int ps_match_xyz_l2_device(PsContext *ctx, const PsMapBatchF32 *b, PsDMatch *matches, int32_t *numMatches);
+int ps_map_pairs_l2_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                           const PsMapBatchF32 *b, const PsPairResults *out);
+
 /* ---- Map views built on the device from a RESIDENT feature map: what a host does per frame and per visible map feature before
  * matchXYZ -- FeaturesMap::findNearestFrame (src/Map/featuresMap.cpp:528-563), PUTSLAM::removeMapFeaturesWithoutGoodObservationAngle
  * (src/PUTSLAM/PUTSLAM.cpp:932-950), moveMapFeaturesToLocalCordinateSystem (PUTSLAM.cpp:28-51), the predicted level of

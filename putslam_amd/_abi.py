@@ -74,6 +74,12 @@ class PsMapBatch(C.Structure):
                 ("acceptRatio", C.c_double), ("radiusBoundPerPair", C.c_void_p), ("acceptRatioPerPair", C.c_void_p)]
 
 
+class PsMapBatchF32(C.Structure):
+    _fields_ = [("maps", PsFrameSetF32), ("mapLevel", C.c_void_p), ("frames", PsFrameSetF32), ("curLevel", C.c_void_p),
+                ("pairs", C.c_void_p), ("P", C.c_int32), ("maxMatches", C.c_int32), ("radiusBound", C.c_float),
+                ("acceptRatio", C.c_double), ("radiusBoundPerPair", C.c_void_p), ("acceptRatioPerPair", C.c_void_p)]
+
+
 # PsExclusionRule forms and modes (include/putslam_hip.h)
 PS_EXCL_NONE, PS_EXCL_F32, PS_EXCL_F64 = 0, 1, 2
 PS_EXCL_GREEDY, PS_EXCL_ALL_EARLIER = 0, 1

@@ -6,7 +6,7 @@ object is missing the import fails loudly and tells the caller how to build it.
 import ctypes as C
 import os
 
-from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsMapStore,
+from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsMapBatchF32, PsMapStore,
                    PsMapViewOut, PsMapViewRequest, PsPairResults, PsPoseSetOut, PsPoseSetRequest, PsRansacConfig, PsRansacParams,
                    PsRansacStats)
 
@@ -215,6 +215,11 @@ def load_path(path):
     L.ps_match_l2_device.argtypes = [vp, C.POINTER(PsFrameSetF32), vp, i32, vp, vp]
     L.ps_vo_pairs_l2_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsFrameSetF32), vp, i32,
                                         C.POINTER(PsPairResults)]
+    L.ps_match_xyz_l2_f32.argtypes = [vp, vp, vp, sz, vp, i32, vp, vp, sz, vp, i32, i32, C.c_double, C.c_double, vp, i32, C.POINTER(i32)]
+    L.ps_match_xyz_l2_device.argtypes = [vp, C.POINTER(PsMapBatchF32), vp, vp]
+    L.ps_map_pairs_l2_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsMapBatchF32),
+                                         C.POINTER(PsPairResults)]
+    L.ps_abi_sizeof_map_batch_f32.restype = sz   # (ABI_STRUCTS_F32 stays the float matcher's one struct)
     L.ps_batch_queue_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.ps_batch_queue_destroy.argtypes = [vp]
     L.ps_batch_queue_destroy.restype = None

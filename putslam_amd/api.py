@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, PS_SET_INVALID, PsExclusionRule, PsFrameSet,  # noqa: F401
-                   PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsPairResults, PsMapStore, PsMapViewOut, PsMapViewRequest,
+                   PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsMapBatchF32, PsPairResults, PsMapStore, PsMapViewOut, PsMapViewRequest,
                    PsPoseSetOut, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
 
 
@@ -475,6 +475,31 @@ class Context:
                 continue
             self._chk(rc)
 
+    def match_xyz_l2(self, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, radius=0.12, ratio=0.55):
+        """match_xyz for float descriptors (ps_match_xyz_l2_f32): (n, dim) float32 rows, the value is the L2 norm of the float
+        difference accumulated in double (tests/map_l2_ref.py)."""
+        map_pos = np.ascontiguousarray(map_pos, np.float32)
+        cur_pos = np.ascontiguousarray(cur_pos, np.float32)
+        map_desc = np.ascontiguousarray(map_desc, np.float32)
+        cur_desc = np.ascontiguousarray(cur_desc, np.float32)
+        map_level = np.ascontiguousarray(map_level, np.int32)
+        cur_level = np.ascontiguousarray(cur_level, np.int32)
+        assert map_desc.ndim == 2 and cur_desc.ndim == 2 and map_desc.shape[1] == cur_desc.shape[1]
+        nmap, ncur, dim = map_pos.shape[0], cur_pos.shape[0], map_desc.shape[1]
+        cap = max(1, 4 * nmap)
+        while True:
+            out = np.zeros(cap, DMATCH_DTYPE)
+            n = C.c_int(0)
+            rc = self._L.ps_match_xyz_l2_f32(self._h, _p(map_pos), _p(map_desc), dim * 4, _p(map_level), nmap, _p(cur_pos),
+                                             _p(cur_desc), dim * 4, _p(cur_level), ncur, dim, float(radius), float(ratio), _p(out),
+                                             cap, C.byref(n))
+            if rc == PS_OK:
+                return out[: n.value].copy()
+            if n.value > cap:
+                cap = n.value
+                continue
+            self._chk(rc)
+
     def predicted_level(self, octave, det_dist, cur_dist):
         return self._L.ps_predicted_level(int(octave), float(det_dist), float(cur_dist))
 
@@ -564,6 +589,57 @@ class Context:
         K = None if K is None else np.ascontiguousarray(K, np.float32)
         mb, res = batch.struct(), out.struct()
         self._chk(self._L.ps_map_pairs_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(mb), C.byref(res)))
+
+    def match_xyz_l2_device(self, batch: "DeviceMapBatchF32", matches_ptr, num_matches_ptr):
+        """ps_match_xyz_l2_device: match_xyz_device for float descriptors; asynchronous, device pointers."""
+        mb = batch.struct()
+        self._chk(self._L.ps_match_xyz_l2_device(self._h, C.byref(mb), C.c_void_p(matches_ptr), C.c_void_p(num_matches_ptr)))
+
+    def map_pairs_l2_device(self, params, cfg, K, batch: "DeviceMapBatchF32", out: "DeviceResults"):
+        """ps_map_pairs_l2_device: map_pairs_device for float descriptors; asynchronous, device pointers."""
+        K = None if K is None else np.ascontiguousarray(K, np.float32)
+        mb, res = batch.struct(), out.struct()
+        self._chk(self._L.ps_map_pairs_l2_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(mb), C.byref(res)))
+
+    def match_xyz_ladder_l2(self, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, params, cfg, K, radius=0.12,
+                            ratio=0.55, max_tries=10, min_ratio=0.1, max_matches=None, device=None):
+        """match_xyz_ladder for float descriptors ((n, dim) float32 rows): the tries of matcher.cpp:617-622 as ONE
+        ps_map_pairs_l2_device call; the same selection, the same result dict, the same capacity rule."""
+        from . import device_batch
+        map_pos = np.ascontiguousarray(map_pos, np.float32)
+        cur_pos = np.ascontiguousarray(cur_pos, np.float32)
+        map_desc = np.ascontiguousarray(map_desc, np.float32)
+        cur_desc = np.ascontiguousarray(cur_desc, np.float32)
+        assert map_desc.ndim == 2 and cur_desc.ndim == 2 and map_desc.shape[1] == cur_desc.shape[1]
+        nmap, ncur, dim = map_pos.shape[0], cur_pos.shape[0], map_desc.shape[1]
+        dev = device if device is not None else "cuda:%d" % self._L.ps_context_device(self._h)
+
+        def side(desc, pos, level, n):       # one view / frame as a frame set of its own (capacity >= 1)
+            cap = max(n, 1)
+            d, q, lv = np.zeros((1, cap, dim), np.float32), np.zeros((1, cap, 3), np.float32), np.zeros((1, cap), np.int32)
+            if n:
+                d[0], q[0], lv[0] = desc, pos, np.asarray(level, np.int32).reshape(n)
+            return device_batch.FrameSetF32Device(d, q, [n], dev), lv
+
+        views, mlv = side(map_desc, map_pos, map_level, nmap)
+        frames, clv = side(cur_desc, cur_pos, cur_level, ncur)
+        tries = [ladder_try(float(radius), float(ratio), k) for k in range(1, int(max_tries) + 1)]
+
+        def run(cap):
+            batch = device_batch.MapBatchF32Device(views, mlv, frames, clv, np.zeros((len(tries), 2), np.int32), cap,
+                                                   radius=[t[0] for t in tries], ratio=[t[1] for t in tries])
+            device_batch.run_map_pairs_l2(self, params, cfg, K, batch)
+            r = batch.download()
+            return r, int(-r["numMatches"].min()) if len(tries) else 0
+
+        r, _ = retry_with_reported_capacity(run, int(max_matches) if max_matches is not None else max(1, 4 * nmap))
+        ratios = [float(x) for x in r["stats"]["pointInlierRatio"]]
+        k = ladder_pick(ratios, min_ratio)
+        n = max(int(r["numMatches"][k]), 0)
+        ir = ratios[k]
+        return dict(matches=r["matches"][k, :n].copy(), mask=r["inlierMask"][k, :n].copy(), pose=r["pose"][k].reshape(4, 4).T.copy(),
+                    stats=r["stats"][k].copy(), inlier_ratio=-1.0 if ir != ir else ir, try_used=k + 1,
+                    num_matches=int(r["numMatches"][k]))
 
     def match_xyz_ladder(self, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, params, cfg, K, radius=0.12,
                          ratio=0.55, max_tries=10, min_ratio=0.1, max_matches=None, device=None):
@@ -906,6 +982,15 @@ class DeviceMapBatch:
         return PsMapBatch(self.maps.struct(), self.map_level_ptr, self.frames.struct(), self.cur_level_ptr, self.pairs_ptr,
                           self.P, self.max_matches, self.radius_bound, self.accept_ratio, self.radius_bound_per_pair_ptr,
                           self.accept_ratio_per_pair_ptr)
+
+
+class DeviceMapBatchF32(DeviceMapBatch):
+    """Raw device pointers of a float-descriptor map-matching batch (PsMapBatchF32): maps / frames are DeviceFramesF32."""
+
+    def struct(self):
+        return PsMapBatchF32(self.maps.struct(), self.map_level_ptr, self.frames.struct(), self.cur_level_ptr, self.pairs_ptr,
+                             self.P, self.max_matches, self.radius_bound, self.accept_ratio, self.radius_bound_per_pair_ptr,
+                             self.accept_ratio_per_pair_ptr)
 
 
 def kernel_names():

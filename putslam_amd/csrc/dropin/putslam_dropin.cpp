@@ -775,11 +775,34 @@ double FrameMatcher::matchFeatureLoopClosure(cv::Mat desc0, std::vector<Eigen::V
     return RANSAC::pointInlierRatio(inlierMatches, matches);
 }
 
+namespace {
+// What matchXYZ / matchXYZLadder are given: CV_32F frame descriptors take the float calls (matcher.cpp:625-628 picks NORM_L2 for
+// SURF / SIFT) with rows of `dim` floats, anything else today's 32-byte path.  False -- after one line on std::cerr -- for mixed
+// types or a float map row whose width differs from the frame's (a feature without a descriptor keeps its zero row).
+bool mapDescriptorKind(const std::vector<FrameMatcher::MapFeatureXYZ> &mapFeatures, const cv::Mat &cur, bool &isFloat, int &dim, const char *who)
+{
+    isFloat = cur.type() == CV_32F;
+    dim = isFloat ? cur.cols : 32;
+    for (const FrameMatcher::MapFeatureXYZ &f : mapFeatures) {
+        if (f.descriptor.empty()) continue;
+        if ((f.descriptor.type() == CV_32F) != isFloat || (isFloat && f.descriptor.cols != dim)) {
+            std::cerr << "putslam_hip: " << who << ": map and frame descriptors differ in type or width" << std::endl;
+            return false;
+        }
+    }
+    return true;
+}
+} // namespace
+
 double FrameMatcher::matchXYZ(const std::vector<MapFeatureXYZ> &mapFeatures, cv::Mat currentPoseDescriptors,
                          std::vector<Eigen::Vector3f> &currentPoseFeatures3D, const std::vector<int> &currentPoseOctaves,
                          const std::vector<double> &currentPoseDetDists, Eigen::Matrix4f &estimatedTransformation,
                          std::vector<cv::DMatch> &inlierMatches, int computationNumber)
 {
+    bool isFloat;
+    int dim;
+    if (!mapDescriptorKind(mapFeatures, currentPoseDescriptors, isFloat, dim, "matchXYZ")) return -1.0;
+    const size_t rowBytes = isFloat ? (size_t)dim * 4 : 32; // 1 x 32 CV_8U, or 1 x D CV_32F
     double matchingXYZSphereRadius = matcherParameters.OpenCVParams.matchingXYZSphereRadius; // matcher.cpp:616-622
     double matchingXYZacceptRatioOfBestMatch = matcherParameters.OpenCVParams.matchingXYZacceptRatioOfBestMatch;
     if (computationNumber > 1) {
@@ -794,13 +817,13 @@ double FrameMatcher::matchXYZ(const std::vector<MapFeatureXYZ> &mapFeatures, cv:
         curLevels[i] = ps_predicted_level(currentPoseOctaves[i], currentPoseDetDists[i], (double)nrm);
     }
     std::vector<Eigen::Vector3f> mapFeaturePositions3D(nmap);
-    std::vector<unsigned char> mapDesc(nmap * 32);
+    std::vector<unsigned char> mapDesc(nmap * rowBytes);
     for (size_t j = 0; j < nmap; ++j) { // :681-692,701-702
         const MapFeatureXYZ &f = mapFeatures[j];
         double curDist = std::sqrt(f.position[0] * f.position[0] + f.position[1] * f.position[1] + f.position[2] * f.position[2]);
         mapLevels[j] = ps_predicted_level(f.octave, f.detDist, curDist);
         mapFeaturePositions3D[j] = Eigen::Vector3f((float)f.position[0], (float)f.position[1], (float)f.position[2]);
-        if (!f.descriptor.empty()) std::memcpy(&mapDesc[j * 32], f.descriptor.data, 32);
+        if (!f.descriptor.empty()) std::memcpy(&mapDesc[j * rowBytes], f.descriptor.data, rowBytes);
     }
     std::vector<cv::DMatch> matches;
     int status;
@@ -809,11 +832,19 @@ double FrameMatcher::matchXYZ(const std::vector<MapFeatureXYZ> &mapFeatures, cv:
     int cap = (int)(4 * nmap + 16), n = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         matches.resize((size_t)cap);
-        status = ps_match_xyz(ctx, reinterpret_cast<const float *>(mapFeaturePositions3D.data()), mapDesc.data(), 32,
-                              mapLevels.data(), (int)nmap, reinterpret_cast<const float *>(currentPoseFeatures3D.data()),
-                              currentPoseDescriptors.data, (size_t)currentPoseDescriptors.step, curLevels.data(), (int)ncur,
-                              matchingXYZSphereRadius, matchingXYZacceptRatioOfBestMatch,
-                              reinterpret_cast<PsDMatch *>(matches.data()), cap, &n);
+        if (isFloat) // norm(mapDescriptor - curDescriptor, NORM_L2) on CV_32F rows (:625-628, :719-721)
+            status = ps_match_xyz_l2_f32(ctx, reinterpret_cast<const float *>(mapFeaturePositions3D.data()),
+                                         reinterpret_cast<const float *>(mapDesc.data()), rowBytes, mapLevels.data(), (int)nmap,
+                                         reinterpret_cast<const float *>(currentPoseFeatures3D.data()),
+                                         reinterpret_cast<const float *>(currentPoseDescriptors.data), (size_t)currentPoseDescriptors.step,
+                                         curLevels.data(), (int)ncur, dim, matchingXYZSphereRadius, matchingXYZacceptRatioOfBestMatch,
+                                         reinterpret_cast<PsDMatch *>(matches.data()), cap, &n);
+        else
+            status = ps_match_xyz(ctx, reinterpret_cast<const float *>(mapFeaturePositions3D.data()), mapDesc.data(), 32,
+                                  mapLevels.data(), (int)nmap, reinterpret_cast<const float *>(currentPoseFeatures3D.data()),
+                                  currentPoseDescriptors.data, (size_t)currentPoseDescriptors.step, curLevels.data(), (int)ncur,
+                                  matchingXYZSphereRadius, matchingXYZacceptRatioOfBestMatch,
+                                  reinterpret_cast<PsDMatch *>(matches.data()), cap, &n);
         if (status == PS_OK || n <= cap) break;
         cap = n;
     }
@@ -870,6 +901,10 @@ double FrameMatcher::matchXYZLadder(const std::vector<MapFeatureXYZ> &mapFeature
 {
     if (maxTries < 1) maxTries = 1;
     if (tryUsed) *tryUsed = maxTries; // (no try reaches minRatio: the last one is returned)
+    bool isFloat;
+    int dim;
+    if (!mapDescriptorKind(mapFeatures, currentPoseDescriptors, isFloat, dim, "matchXYZLadder")) return -1.0;
+    const size_t rowBytes = isFloat ? (size_t)dim * 4 : 32; // 1 x 32 CV_8U, or 1 x D CV_32F
     const size_t nmap = mapFeatures.size(), ncur = currentPoseFeatures3D.size();
     int status;
     PsContext *ctx = threadContext(&status);
@@ -877,7 +912,7 @@ double FrameMatcher::matchXYZLadder(const std::vector<MapFeatureXYZ> &mapFeature
     const int T = maxTries;
     int cap = (int)(4 * nmap + 16);
     // inputs, in one host block that mirrors the device block: descriptors | points | levels | counts | pairs | bounds | ratios
-    const size_t oMapDesc = 0, oCurDesc = oMapDesc + nmap * 32, oMapPts = oCurDesc + ncur * 32, oCurPts = up16(oMapPts + nmap * 12),
+    const size_t oMapDesc = 0, oCurDesc = oMapDesc + nmap * rowBytes, oMapPts = oCurDesc + ncur * rowBytes, oCurPts = up16(oMapPts + nmap * 12),
                  oMapLvl = up16(oCurPts + ncur * 12), oCurLvl = up16(oMapLvl + nmap * 4), oCounts = up16(oCurLvl + ncur * 4),
                  oPairs = oCounts + 16, oBound = up16(oPairs + (size_t)T * 8), oRatio = up16(oBound + (size_t)T * 4),
                  inBytes = up16(oRatio + (size_t)T * 8);
@@ -889,14 +924,14 @@ double FrameMatcher::matchXYZLadder(const std::vector<MapFeatureXYZ> &mapFeature
         const float pos[3] = {(float)f.position[0], (float)f.position[1], (float)f.position[2]};
         std::memcpy(&in[oMapLvl + j * 4], &lvl, 4);
         std::memcpy(&in[oMapPts + j * 12], pos, 12);
-        if (!f.descriptor.empty()) std::memcpy(&in[oMapDesc + j * 32], f.descriptor.data, 32);
+        if (!f.descriptor.empty()) std::memcpy(&in[oMapDesc + j * rowBytes], f.descriptor.data, rowBytes);
     }
     for (size_t i = 0; i < ncur; ++i) { // :639-652; curDist = Eigen float norm()
         const Eigen::Vector3f &p = currentPoseFeatures3D[i];
         const float nrm = std::sqrt(p[0] * p[0] + (p[1] * p[1] + p[2] * p[2]));
         const int32_t lvl = ps_predicted_level(currentPoseOctaves[i], currentPoseDetDists[i], (double)nrm);
         std::memcpy(&in[oCurLvl + i * 4], &lvl, 4);
-        std::memcpy(&in[oCurDesc + i * 32], currentPoseDescriptors.data + i * (size_t)currentPoseDescriptors.step, 32);
+        std::memcpy(&in[oCurDesc + i * rowBytes], currentPoseDescriptors.data + i * (size_t)currentPoseDescriptors.step, rowBytes);
     }
     std::memcpy(&in[oCurPts], currentPoseFeatures3D.data(), ncur * 12);
     const int32_t counts[2] = {(int32_t)nmap, (int32_t)ncur};
@@ -948,32 +983,44 @@ double FrameMatcher::matchXYZLadder(const std::vector<MapFeatureXYZ> &mapFeature
             return -1.0;
         }
         unsigned char *d = static_cast<unsigned char *>(block.p), *o = d + inBytes;
-        PsMapBatch mb;
-        std::memset(&mb, 0, sizeof mb);
-        mb.maps.desc = d + oMapDesc;
-        mb.maps.pts = reinterpret_cast<const float *>(d + oMapPts);
-        mb.maps.nkpts = reinterpret_cast<const int32_t *>(d + oCounts);
-        mb.maps.numFrames = 1;
-        mb.maps.maxKpts = (int32_t)nmap;
-        mb.mapLevel = reinterpret_cast<const int32_t *>(d + oMapLvl);
-        mb.frames.desc = d + oCurDesc;
-        mb.frames.pts = reinterpret_cast<const float *>(d + oCurPts);
-        mb.frames.nkpts = reinterpret_cast<const int32_t *>(d + oCounts) + 1;
-        mb.frames.numFrames = 1;
-        mb.frames.maxKpts = (int32_t)ncur;
-        mb.curLevel = reinterpret_cast<const int32_t *>(d + oCurLvl);
-        mb.pairs = reinterpret_cast<const int32_t *>(d + oPairs);
-        mb.P = T;
-        mb.maxMatches = cap;
-        mb.radiusBoundPerPair = reinterpret_cast<const float *>(d + oBound);
-        mb.acceptRatioPerPair = reinterpret_cast<const double *>(d + oRatio);
+        const auto fill = [&](auto &mb) { // what PsMapBatch and PsMapBatchF32 share
+            std::memset(&mb, 0, sizeof mb);
+            mb.maps.pts = reinterpret_cast<const float *>(d + oMapPts);
+            mb.maps.nkpts = reinterpret_cast<const int32_t *>(d + oCounts);
+            mb.maps.numFrames = 1;
+            mb.maps.maxKpts = (int32_t)nmap;
+            mb.mapLevel = reinterpret_cast<const int32_t *>(d + oMapLvl);
+            mb.frames.pts = reinterpret_cast<const float *>(d + oCurPts);
+            mb.frames.nkpts = reinterpret_cast<const int32_t *>(d + oCounts) + 1;
+            mb.frames.numFrames = 1;
+            mb.frames.maxKpts = (int32_t)ncur;
+            mb.curLevel = reinterpret_cast<const int32_t *>(d + oCurLvl);
+            mb.pairs = reinterpret_cast<const int32_t *>(d + oPairs);
+            mb.P = T;
+            mb.maxMatches = cap;
+            mb.radiusBoundPerPair = reinterpret_cast<const float *>(d + oBound);
+            mb.acceptRatioPerPair = reinterpret_cast<const double *>(d + oRatio);
+        };
         PsPairResults res;
         res.matches = reinterpret_cast<PsDMatch *>(o + oMatches);
         res.numMatches = reinterpret_cast<int32_t *>(o + oNum);
         res.inlierMask = o + oMask;
         res.pose = reinterpret_cast<float *>(o + oPose);
         res.stats = reinterpret_cast<PsRansacStats *>(o + oStats);
-        status = ps_map_pairs_device(ctx, &prm, &cfg, haveK ? K : nullptr, &mb, &res);
+        if (isFloat) {
+            PsMapBatchF32 mb;
+            fill(mb);
+            mb.maps.desc = reinterpret_cast<const float *>(d + oMapDesc);
+            mb.frames.desc = reinterpret_cast<const float *>(d + oCurDesc);
+            mb.maps.dim = mb.frames.dim = dim;
+            status = ps_map_pairs_l2_device(ctx, &prm, &cfg, haveK ? K : nullptr, &mb, &res);
+        } else {
+            PsMapBatch mb;
+            fill(mb);
+            mb.maps.desc = d + oMapDesc;
+            mb.frames.desc = d + oCurDesc;
+            status = ps_map_pairs_device(ctx, &prm, &cfg, haveK ? K : nullptr, &mb, &res);
+        }
         out.resize(outBytes);
         const bool copied = status == PS_OK && hipMemcpyAsync(out.data(), o, outBytes, hipMemcpyDeviceToHost, stream) == hipSuccess;
         const int sync = ps_context_synchronize(ctx); // (also after a failed call: the upload may still be reading `in`)

@@ -203,7 +203,7 @@ class FrameMatcher {
     struct MapFeatureXYZ {
         unsigned int id = 0;
         double position[3] = {0, 0, 0};
-        cv::Mat descriptor; // 1 x 32 CV_8U
+        cv::Mat descriptor; // 1 x 32 CV_8U, or 1 x D CV_32F
         int octave = 0;
         double detDist = 1.0;
     };
@@ -242,7 +242,10 @@ class FrameMatcher {
                                    std::vector<Eigen::Vector3f> pts1, Eigen::Matrix4f &estimatedTransformation,
                                    std::vector<cv::DMatch> &inlierMatches);
     // Guided matching of map features against the current pose's keypoints + RANSAC with errorVersionMap
-    // (matchXYZ, matcher.cpp:606-798): returns RANSAC::pointInlierRatio, or -1 when nothing matched.
+    // (matchXYZ, matcher.cpp:606-798): returns RANSAC::pointInlierRatio, or -1 when nothing matched.  The type of
+    // currentPoseDescriptors decides the value (:625-628): CV_32F Mats (SURF / SIFT, rows of D floats) take NORM_L2
+    // (ps_match_xyz_l2_f32; matchXYZLadder: ps_map_pairs_l2_device), CV_8U Mats the Hamming path.  Mixed types, or a float map
+    // row whose width differs from the frame's, print one line to std::cerr and return -1.
     double matchXYZ(const std::vector<MapFeatureXYZ> &mapFeatures, cv::Mat currentPoseDescriptors,
                     std::vector<Eigen::Vector3f> &currentPoseFeatures3D, const std::vector<int> &currentPoseOctaves,
                     const std::vector<double> &currentPoseDetDists, Eigen::Matrix4f &estimatedTransformation,

@@ -326,6 +326,8 @@ class MapBatchDevice(PairResultsDevice):
     (views x maxKpts / frames x maxKpts int32), pairs (P, 2) of (map view, frame), the sphere radius and accept ratio -- scalars, or
     sequences of P for per-pair values -- and the output block with `max_matches` rows per pair."""
 
+    _batch_view_type = api.DeviceMapBatch   # (MapBatchF32Device: the float sets' struct)
+
     def __init__(self, maps, map_level, frames, cur_level, pairs, max_matches, radius=0.12, ratio=0.55, device=None):
         self.device = torch.device(device) if device is not None else maps.device
         self.maps, self.frames = maps, frames
@@ -358,7 +360,7 @@ class MapBatchDevice(PairResultsDevice):
     def batch_view(self, lo=0, hi=None):
         """PsMapBatch of pairs [lo, hi)."""
         hi = self.P if hi is None else hi
-        return api.DeviceMapBatch(self.maps.view(), self.map_level.data_ptr(), self.frames.view(), self.cur_level.data_ptr(),
+        return self._batch_view_type(self.maps.view(), self.map_level.data_ptr(), self.frames.view(), self.cur_level.data_ptr(),
                                   self.pairs[lo:].data_ptr() if lo < self.P else self.pairs.data_ptr(), hi - lo, self.cap,
                                   self.radius_bound, self.accept_ratio,
                                   self.radius_per[lo:].data_ptr() if self.radius_per is not None else None,
@@ -376,6 +378,29 @@ def run_match_xyz(ctx, batch: MapBatchDevice, use_torch_stream=True):
     """Asynchronous: the guided matching alone (ps_match_xyz_device) into the batch's matches / num_matches."""
     _on_torch_stream(ctx, batch.device,
                      lambda: ctx.match_xyz_device(batch.batch_view(), batch.matches.data_ptr(), batch.num_matches.data_ptr()),
+                     use_torch_stream)
+
+
+class MapBatchF32Device(MapBatchDevice):
+    """MapBatchDevice for float descriptors (PsMapBatchF32): maps / frames are FrameSetF32Device of one dim, with points."""
+
+    def __init__(self, maps, map_level, frames, cur_level, pairs, max_matches, radius=0.12, ratio=0.55, device=None):
+        assert maps.pts is not None and frames.pts is not None
+        super().__init__(maps, map_level, frames, cur_level, pairs, max_matches, radius, ratio, device)
+
+    _batch_view_type = api.DeviceMapBatchF32
+
+
+def run_map_pairs_l2(ctx, params, cfg, K, batch: MapBatchF32Device, use_torch_stream=True):
+    """run_map_pairs for float descriptors (ps_map_pairs_l2_device)."""
+    _on_torch_stream(ctx, batch.device, lambda: ctx.map_pairs_l2_device(params, cfg, K, batch.batch_view(), batch.view()),
+                     use_torch_stream)
+
+
+def run_match_xyz_l2(ctx, batch: MapBatchF32Device, use_torch_stream=True):
+    """run_match_xyz for float descriptors (ps_match_xyz_l2_device)."""
+    _on_torch_stream(ctx, batch.device,
+                     lambda: ctx.match_xyz_l2_device(batch.batch_view(), batch.matches.data_ptr(), batch.num_matches.data_ptr()),
                      use_torch_stream)
 
 
