@@ -6,6 +6,7 @@ error modes, estimators, thresholds, seeds).  tests/test_gpu_fuzz_slice.py colle
     python tests/fuzz_gpu.py --iters 3000 --seed 1
     python tests/fuzz_gpu.py --iters 100000 --procs 8 --modes 0,2,4 --counts     (round 3: the new scoring kernels)
     python tests/fuzz_gpu.py --batch --iters 400 --procs 4                       (staged scoring: random batches)
+    python tests/fuzz_gpu.py --map --iters 2000 --procs 4                        (guided map matching: random device batches)
 """
 import argparse
 import os
@@ -175,6 +176,152 @@ def run_batch(iters, seed, verbose=True, modes=(0, 1, 2, 4), oracle_pairs=3):
     return bad
 
 
+MAP_WIDTHS = (20, 64, 65, 128)
+
+
+def draw_map(rng):
+    """One configuration of run_map (no GPU): ragged views and frames of capacity <= 600 (tests/match_xyz_model_f64.py's
+    generators), binary rows or float rows of a width of MAP_WIDTHS, dense or pitched, P pairs in 1 .. 80 (a few of them naming a
+    view or a frame outside its set), radius from the retry ladder or log-uniform in [0.03, 1], ratio in [0.1, 0.9], both scalar or
+    per pair."""
+    import match_xyz_model_f64 as model
+    kind = "binary" if rng.random() < 0.4 else int(rng.choice(MAP_WIDTHS))
+
+    def ragged(n, cap):
+        out = []
+        for _ in range(n):
+            x = rng.random()
+            out.append(0 if x < 0.12 else 1 if x < 0.2 else cap if x < 0.35 else int(rng.integers(0, cap + 1)))
+        return out
+
+    vcap, fcap = (int(round(10 ** rng.uniform(0.5, np.log10(600)))) for _ in range(2))
+    V, F = int(rng.integers(1, 5)), int(rng.integers(1, 5))
+    source = rng.integers(0, F, V)
+    views, frames = model.sets(rng, ragged(V, vcap), ragged(F, fcap), vcap, fcap, source, kind)
+    P = int(rng.integers(1, 81))
+    pairs = np.zeros((P, 2), np.int32)
+    for p in range(P):
+        v = int(rng.integers(0, V))
+        pairs[p] = (v, source[v] if rng.random() < 0.7 else rng.integers(0, F))
+        if rng.random() < 0.03:
+            col = int(rng.integers(0, 2))
+            pairs[p, col] = [-1, (V, F)[col], 1000][int(rng.integers(0, 3))]
+    n = P if rng.random() < 0.5 else 1
+    radius = [model.ladder(0.12, 0.55, int(rng.integers(1, 11)))[0] if rng.random() < 0.5 else float(10 ** rng.uniform(np.log10(0.03), 0))
+              for _ in range(n)]
+    ratio = [float(rng.uniform(0.1, 0.9)) for _ in range(n)]
+    return dict(kind=kind, views=views, frames=frames, pairs=pairs, radius=radius if n > 1 else radius[0],
+                ratio=ratio if n > 1 else ratio[0], pitched=bool(rng.random() < 0.5), short=bool(rng.random() < 0.35),
+                cut=float(rng.uniform(0.2, 0.95)), pad=int(rng.choice([1, 4, 12])))
+
+
+def map_answers(cfg):
+    """Per pair of a draw_map configuration: (the match list of oracle.match_xyz / map_l2_ref.match_xyz_l2, the model's
+    Answer), each computed once per distinct (view, frame, radius, ratio)."""
+    import map_l2_ref
+    import match_xyz_model_f64 as model
+    from putslam_amd._abi import DMATCH_DTYPE
+    views, frames = cfg["views"], cfg["frames"]
+    done, out = {}, []
+    for p, (v, f) in enumerate(cfg["pairs"]):
+        r = cfg["radius"][p] if np.ndim(cfg["radius"]) else cfg["radius"]
+        a = cfg["ratio"][p] if np.ndim(cfg["ratio"]) else cfg["ratio"]
+        key = (int(v), int(f), r, a)
+        if key not in done:
+            if not (0 <= v < len(views["nkpts"]) and 0 <= f < len(frames["nkpts"])):
+                done[key] = (np.zeros(0, DMATCH_DTYPE), model.Answer(0, cfg["kind"] != "binary"))
+            else:
+                sides = model.side(views, v) + model.side(frames, f)
+                if len(sides[0]) == 0 or len(sides[3]) == 0:
+                    m = np.zeros(0, DMATCH_DTYPE)
+                else:
+                    m = (po.match_xyz if cfg["kind"] == "binary" else map_l2_ref.match_xyz_l2)(*sides, r, a)
+                done[key] = (m, model.match_xyz(*sides, r, a))
+        out.append(done[key])
+    return out
+
+
+def map_max_matches(cfg, answers):
+    """The rows per pair: the largest count, or (cfg short) a part of it, so that some pairs report -(count)."""
+    top = max([len(m) for m, _ in answers] + [1])
+    return max(1, int(top * cfg["cut"])) if cfg["short"] else top
+
+
+def map_model_failures(answers, lists=None):
+    """The shared check of every pair's list (default: the CPU answer's own) against the model, the cap on ambiguous features
+    taken over the whole configuration (one scene).  Returns the failures."""
+    import match_xyz_model_f64 as model
+    fails, amb, cand = [], 0, 0
+    seen = set()
+    for p, (m, ans) in enumerate(answers):
+        got = m if lists is None else lists[p]
+        if got is None:
+            continue
+        r = model.compare(got, ans)
+        if id(ans) not in seen:
+            seen.add(id(ans))
+            amb, cand = amb + r.ambiguous, cand + r.with_candidates
+        r.ambiguous = r.with_candidates = 0
+        fails += [(p, x) for x in r.failures()]
+    if amb > model.AMBIGUOUS_CAP * cand:
+        fails.append(("cap", amb, cand))
+    return fails
+
+
+def run_map(iters, seed, ctx=None, verbose=True):
+    """Random device batches of the guided map matching (ps_match_xyz_device / ps_match_xyz_l2_device): every pair's count and
+    rows against oracle.match_xyz / map_l2_ref.match_xyz_l2 as bytes -- a pair whose count exceeds maxMatches reports -(count) --
+    and through the shared check against the float64 model of tests/match_xyz_model_f64.py.  Returns the number of
+    configurations with a difference."""
+    from putslam_amd.device_batch import (FrameSetDevice, FrameSetF32Device, MapBatchDevice, MapBatchF32Device, PackedFrameSetDevice,
+                                          run_match_xyz, run_match_xyz_l2)
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    rng = np.random.default_rng(seed)
+    ctx = ctx or api.Context(0)
+    t0 = time.time()
+    bad = 0
+    for it in range(iters):
+        cfg = draw_map(rng)
+        views, frames, pairs = cfg["views"], cfg["frames"], cfg["pairs"]
+        answers = map_answers(cfg)
+        cap = map_max_matches(cfg, answers)
+        if cfg["kind"] == "binary":
+            if cfg["pitched"]:
+                vs = PackedFrameSetDevice(views["desc"], views["pos"], views["nkpts"], stride=(views["cap"] * 44 + 15) // 16 * 16 + 16 * cfg["pad"])
+                fs = PackedFrameSetDevice(frames["desc"], frames["pos"], frames["nkpts"])
+            else:
+                vs = FrameSetDevice(views["desc"], views["pos"], views["nkpts"])
+                fs = FrameSetDevice(frames["desc"], frames["pos"], frames["nkpts"])
+            b = MapBatchDevice(vs, views["level"], fs, frames["level"], pairs, cap, radius=cfg["radius"], ratio=cfg["ratio"])
+            run_match_xyz(ctx, b)
+        else:
+            rf = cfg["kind"] + cfg["pad"] if cfg["pitched"] else None
+            vs = FrameSetF32Device(views["desc"], views["pos"], views["nkpts"], row_floats=rf)
+            fs = FrameSetF32Device(frames["desc"], frames["pos"], frames["nkpts"], row_floats=rf)
+            b = MapBatchF32Device(vs, views["level"], fs, frames["level"], pairs, cap, radius=cfg["radius"], ratio=cfg["ratio"])
+            run_match_xyz_l2(ctx, b)
+        g = b.download()
+        why, lists = [], []
+        for p, (m, _) in enumerate(answers):
+            n = int(g["numMatches"][p])
+            if len(m) > cap:
+                lists.append(None)
+                if n != -len(m):
+                    why.append((p, "count over capacity", n, -len(m)))
+                continue
+            lists.append(g["matches"][p, :max(n, 0)])
+            if n != len(m) or lists[-1].tobytes() != m.tobytes():
+                why.append((p, "bytes", n, len(m)))
+        why += map_model_failures(answers, lists)
+        if why:
+            bad += 1
+            print("MISMATCH", dict(it=it, seed=seed, kind=cfg["kind"], P=len(pairs), views=views["nkpts"].tolist(),
+                                   frames=frames["nkpts"].tolist(), pitched=cfg["pitched"], cap=cap), "differences:", why[:12], flush=True)
+        if verbose and (it + 1) % 20 == 0:
+            print(f"{it + 1} map configurations, {bad} mismatches, {time.time() - t0:.0f} s", flush=True)
+    return bad
+
+
 def main():
     import faulthandler
     faulthandler.enable()   # a worker that dies on a signal leaves its Python stack in its log
@@ -186,6 +333,7 @@ def main():
     ap.add_argument("--counts", action="store_true", help="also compare every hypothesis's inlier count")
     ap.add_argument("--procs", type=int, default=1, help="worker processes (seeds seed, seed+1, ...), iterations split evenly")
     ap.add_argument("--batch", action="store_true", help="random batches: staged scoring vs complete scoring vs oracle")
+    ap.add_argument("--map", action="store_true", help="random device batches of the guided map matching vs oracle and float64 model")
     ap.add_argument("--log-dir", default=None,
                     help="where every worker's FULL output is kept (default: gpurun_out/fuzz_logs under the repository)")
     ap.add_argument("--tag", default="", help="label for the log files of this run")
@@ -197,7 +345,7 @@ def main():
         per = (a.iters + a.procs - 1) // a.procs
         log_dir = a.log_dir or os.path.join(ROOT, "gpurun_out", "fuzz_logs")
         os.makedirs(log_dir, exist_ok=True)
-        stamp = f"{a.tag or 'run'}_{'batch' if a.batch else 'single'}_{int(time.time())}_{os.getpid()}"
+        stamp = f"{a.tag or 'run'}_{'map' if a.map else 'batch' if a.batch else 'single'}_{int(time.time())}_{os.getpid()}"
         ps, logs = [], []
         for i in range(a.procs):
             # every worker's complete output goes to a file of its own (round 3 lost the only failing worker's output to a
@@ -208,7 +356,7 @@ def main():
             logs.append((path, f))
             ps.append(subprocess.Popen([sys.executable, "-u", os.path.abspath(__file__), "--iters", str(per), "--seed", str(a.seed + i),
                                         "--max-kpts", str(a.max_kpts), "--modes", a.modes] + (["--counts"] if a.counts else [])
-                                       + (["--batch"] if a.batch else []), stdout=f, stderr=subprocess.STDOUT, text=True))
+                                       + (["--batch"] if a.batch else []) + (["--map"] if a.map else []), stdout=f, stderr=subprocess.STDOUT, text=True))
         failed = 0
         for i, p in enumerate(ps):
             p.wait()
@@ -230,7 +378,9 @@ def main():
         print(f"fuzz done: {per * a.procs} iterations over {a.procs} workers, modes {a.modes}, "
               f"{'no mismatches' if failed == 0 else f'{failed} WORKER(S) FAILED (MISMATCHES or crashes, see above)'}")
         return 1 if failed else 0
-    if a.batch:
+    if a.map:
+        bad = run_map(a.iters, a.seed)
+    elif a.batch:
         bad = run_batch(a.iters, a.seed, modes=tuple(m for m in modes if m != 3))
     else:
         bad = run(a.iters, a.seed, a.max_kpts, modes=modes, counts=a.counts)

@@ -20,3 +20,12 @@ def test_fuzz_batch_slice(oracle):
     """Random batches through the staged scoring: staged == complete on every pair, == oracle on sampled pairs."""
     import fuzz_gpu
     assert fuzz_gpu.run_batch(12, 77, verbose=False) == 0
+
+
+@pytest.mark.parametrize("seed", [5, 1905])
+def test_fuzz_map_slice(ctx, oracle, seed):
+    """Random device batches of the guided map matching, binary and float rows: bytes against the oracle / the restatement, and the
+    shared check against the float64 model (tests/match_xyz_model_f64.py).  The same draws pass on the CPU in
+    tests/test_match_xyz_model_host.py::test_fuzz_map_draws_on_the_host."""
+    import fuzz_gpu
+    assert fuzz_gpu.run_map(20, seed, ctx=ctx, verbose=False) == 0
