@@ -529,7 +529,7 @@ int ps_match_xyz_l2_f32(PsContext *ctx, const float *mapPos, const float *mapDes
                         int ncur, int dim, double sphereRadius, double acceptRatio, PsDMatch *out, int cap, int *nout);
 
 /* PsMapBatch with float-descriptor sets (THE RULES of PsFrameSetF32 for either; pts is needed); maps.dim must equal frames.dim.
- * A host with float descriptors fills `maps` itself: PsMapStore / ps_map_views_device hold binary rows only. */
+ * ps_map_views_l2_device writes `maps` and mapLevel from a resident PsMapStoreF32 (further down); a host may also fill them. */
 typedef struct PsMapBatchF32 {
     PsFrameSetF32 maps;           /* "map views": desc = the descriptor chosen for each visible feature, pts = (float) casts of
                                      MapFeature::position in the camera frame, nkpts = features per view */
@@ -746,6 +746,81 @@ size_t ps_abi_sizeof_pose_set_request(void);
 size_t ps_abi_sizeof_pose_set_out(void);
 size_t ps_abi_sizeof_loop_batch(void);
 size_t ps_abi_sizeof_loop_results(void);
+
+/* ---- The resident store, its two inversions and the verifier for FLOAT descriptors (SURF / SIFT).  The reference runs the same
+ * code for both descriptor kinds: matcher.cpp:675-679 copies whatever cv::Mat row the chosen observation holds,
+ * matchFeatureLoopClosure (:802-861) pushes ext.descriptor rows into a Mat and calls performMatching, which for SURF / SIFT is
+ * cv::BFMatcher(NORM_L2, true) (matcherOpenCV.cpp:100-102).  Everything that depends on the store's index arrays alone -- the
+ * observation choice, steps 2 - 4, membership, order, counts -- is the binary calls' (the same kernels); what differs is the row.
+ * A ROW IS COPIED AS 32-BIT WORDS, never through float arithmetic: NaN payloads, -0.0 and subnormals arrive bit for bit.  What
+ * lies between the rows of a pitched output is never written.   */
+typedef struct PsMapStoreF32 {    /* PsMapStore with float rows; DEVICE pointers */
+    const double  *pos;           /* F x 3 */
+    const int32_t *obsStart;      /* F + 1 */
+    const int32_t *obsPose;       /* O */
+    const float   *obsDesc;       /* O rows of dim floats, 4-byte aligned */
+    const int32_t *obsOctave;     /* O */
+    const double  *obsDetDist;    /* O */
+    int32_t numFeatures, numObs, numPoses;
+    int32_t dim;                  /* floats per row, 1 .. PS_MAX_L2_DIM */
+    size_t obsDescRowStride;      /* bytes between rows: 0 = dense (dim x 4), else a multiple of 4 and >= dim x 4 */
+} PsMapStoreF32;
+
+typedef struct PsMapViewOutF32 {  /* PsMapViewOut with a float-descriptor set: drops into PsMapBatchF32::maps / mapLevel */
+    PsFrameSetF32 views;          /* numFrames >= V, THE RULES of PsFrameSetF32 (pts is needed); views.dim == store.dim */
+    int32_t *mapLevel;            /* numFrames x maxKpts */
+    int32_t *viewCount;           /* V */
+    int32_t *featIdx;             /* side arrays as in PsMapViewOut, each V x maxKpts rows or NULL */
+    int32_t *obsIdx;
+    double *posCam;
+    double *uv;
+    double *angle;
+} PsMapViewOutF32;
+
+/* ps_map_views_device for a PsMapStoreF32: the five steps, the count / overflow / INT32_MIN rules and the argument rules are that
+ * call's, word for word, with PsMapViewRequest as it is; step 5's desc = the chosen observation's dim floats (matcher.cpp:675-679).
+ * The rows are copied by a pass of their own after the emit kernel (ps_gather_rows_f32: one wavefront per row, consecutive
+ * words), from the observation index of every row -- obsIdx, or a scratch block of 4 x V x maxKpts bytes when obsIdx is NULL.
+ * No row of an overflowed or invalid view is written.
+ * Beyond ps_map_views_device's errors: store.dim < 1, views.dim != store.dim, a row stride that is not a multiple of 4 or lies
+ * below dim x 4, obsDesc not 4-byte aligned -> PS_ERR_BAD_ARG; dim > PS_MAX_L2_DIM -> PS_ERR_UNSUPPORTED; the output set follows
+ * THE RULES of PsFrameSetF32.  Outputs untouched on any error; V == 0 is PS_OK. */
+int ps_map_views_l2_device(PsContext *ctx, const PsMapStoreF32 *store, const PsMapViewRequest *req, const PsMapViewOutF32 *out);
+
+typedef struct PsPoseSetOutF32 {      /* PsPoseSetOut with a float-descriptor set */
+    PsFrameSetF32 sets;               /* numFrames >= S + 1, THE RULES of PsFrameSetF32 (pts is needed); sets.dim == store.dim */
+    int32_t *setCount;                /* S */
+    int32_t *featIdx, *obsIdx;        /* numFrames x maxKpts each, or NULL */
+} PsPoseSetOutF32;
+
+/* ps_pose_sets_device for a PsMapStoreF32: membership, order, counts, overflow, bad pose, bad range, "rows beyond the count are
+ * not written", nkpts[S] = 0 and PS_LOOP_MAX_SETS are that call's, unchanged; a row's desc = that observation's dim floats
+ * (matcher.cpp:816-818), copied by ps_gather_rows_f32 as above.  Errors as ps_pose_sets_device, with the store / set rules of
+ * ps_map_views_l2_device in place of the 16-byte alignment of a binary store.  S == 0 writes nkpts[0] = 0. */
+int ps_pose_sets_l2_device(PsContext *ctx, const PsMapStoreF32 *store, const PsPoseSetRequest *req, const PsPoseSetOutF32 *out);
+
+typedef struct PsLoopBatchF32 {       /* PsLoopBatch with float-descriptor sets; pointers: DEVICE */
+    PsFrameSetF32 sets;               /* as ps_pose_sets_l2_device wrote them */
+    const int32_t *setCount;          /* S */
+    const int32_t *featIdx;           /* numFrames x maxKpts, or NULL */
+    const int32_t *pairs;             /* L x 2 set indices */
+    int32_t L, S;
+    int32_t minNumberOfFeaturesLC;
+    int32_t reserved;
+    double matchingRatioThresholdLC;
+} PsLoopBatchF32;
+
+/* ps_loop_pairs_device with the float matcher (matcherOpenCV.cpp:100-102,198-206) in place of the Hamming one: the same gate,
+ * verdict, pairedRows / pairedFeat and invalid-candidate rules, PsLoopResults as it is.  pair.* of a run candidate is byte for
+ * byte ps_match_l2_f32 on the two sets followed by ps_ransac_rigid3d with seed + l; of a gated one, what ps_vo_pairs_l2_device
+ * gives for two empty frames.  The option "matcher_l2" changes no byte.  Argument rules as ps_loop_pairs_device, the sets under
+ * THE RULES of PsFrameSetF32. */
+int ps_loop_pairs_l2_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                            const PsLoopBatchF32 *batch, const PsLoopResults *out);
+size_t ps_abi_sizeof_map_store_f32(void);
+size_t ps_abi_sizeof_map_view_out_f32(void);
+size_t ps_abi_sizeof_pose_set_out_f32(void);
+size_t ps_abi_sizeof_loop_batch_f32(void);
 
 /* ---- A2, for a host that loops over batches (the loop of src/PUTSLAM/PUTSLAM.cpp:677-740 around Matcher::match,
  * src/Matcher/matcher.cpp:470-515): ps_vo_pairs_device through launch chains that are never joined.

@@ -141,6 +141,29 @@ class PsLoopResults(C.Structure):
                 ("pairedRows", C.c_void_p), ("pairedFeat", C.c_void_p)]
 
 
+# The resident store with float descriptor rows (include/putslam_hip.h)
+class PsMapStoreF32(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("obsStart", C.c_void_p), ("obsPose", C.c_void_p), ("obsDesc", C.c_void_p),
+                ("obsOctave", C.c_void_p), ("obsDetDist", C.c_void_p),
+                ("numFeatures", C.c_int32), ("numObs", C.c_int32), ("numPoses", C.c_int32), ("dim", C.c_int32),
+                ("obsDescRowStride", C.c_size_t)]
+
+
+class PsMapViewOutF32(C.Structure):
+    _fields_ = [("views", PsFrameSetF32), ("mapLevel", C.c_void_p), ("viewCount", C.c_void_p), ("featIdx", C.c_void_p),
+                ("obsIdx", C.c_void_p), ("posCam", C.c_void_p), ("uv", C.c_void_p), ("angle", C.c_void_p)]
+
+
+class PsPoseSetOutF32(C.Structure):
+    _fields_ = [("sets", PsFrameSetF32), ("setCount", C.c_void_p), ("featIdx", C.c_void_p), ("obsIdx", C.c_void_p)]
+
+
+class PsLoopBatchF32(C.Structure):
+    _fields_ = [("sets", PsFrameSetF32), ("setCount", C.c_void_p), ("featIdx", C.c_void_p), ("pairs", C.c_void_p),
+                ("L", C.c_int32), ("S", C.c_int32), ("minNumberOfFeaturesLC", C.c_int32), ("reserved", C.c_int32),
+                ("matchingRatioThresholdLC", C.c_double)]
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

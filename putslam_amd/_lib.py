@@ -6,9 +6,9 @@ object is missing the import fails loudly and tells the caller how to build it.
 import ctypes as C
 import os
 
-from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsMapBatchF32, PsMapStore,
-                   PsMapViewOut, PsMapViewRequest, PsPairResults, PsPoseSetOut, PsPoseSetRequest, PsRansacConfig, PsRansacParams,
-                   PsRansacStats)
+from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch,
+                   PsMapBatchF32, PsMapStore, PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPairResults, PsPoseSetOut,
+                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -46,6 +46,8 @@ EXPORTED = [
     "ps_pose_sets_device", "ps_loop_pairs_device",
     "ps_abi_sizeof_pose_set_request", "ps_abi_sizeof_pose_set_out", "ps_abi_sizeof_loop_batch", "ps_abi_sizeof_loop_results",    "ps_match_l2_f32", "ps_match_l2_device", "ps_vo_pairs_l2_device", "ps_abi_sizeof_frameset_f32", "ps_debug_l2_band",
     "ps_debug_l2_stats",
+    "ps_map_views_l2_device", "ps_pose_sets_l2_device", "ps_loop_pairs_l2_device",
+    "ps_abi_sizeof_map_store_f32", "ps_abi_sizeof_map_view_out_f32", "ps_abi_sizeof_pose_set_out_f32", "ps_abi_sizeof_loop_batch_f32",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -55,6 +57,9 @@ ABI_STRUCTS = dict(dmatch=PsDMatch, params=PsRansacParams, config=PsRansacConfig
                    pose_set_request=PsPoseSetRequest, pose_set_out=PsPoseSetOut, loop_batch=PsLoopBatch, loop_results=PsLoopResults)
 # ... and of the float-descriptor matcher's frame set (a table of its own: ABI_STRUCTS is the ABI-2 set the layout tests count)
 ABI_STRUCTS_F32 = dict(frameset_f32=PsFrameSetF32)
+# ... and of the resident store with float rows (ps_map_views_l2_device / ps_pose_sets_l2_device / ps_loop_pairs_l2_device)
+ABI_STRUCTS_STORE_F32 = dict(map_store_f32=PsMapStoreF32, map_view_out_f32=PsMapViewOutF32, pose_set_out_f32=PsPoseSetOutF32,
+                             loop_batch_f32=PsLoopBatchF32)
 
 _lib = None
 _by_path = {}
@@ -220,6 +225,10 @@ def load_path(path):
     L.ps_map_pairs_l2_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsMapBatchF32),
                                          C.POINTER(PsPairResults)]
     L.ps_abi_sizeof_map_batch_f32.restype = sz   # (ABI_STRUCTS_F32 stays the float matcher's one struct)
+    L.ps_map_views_l2_device.argtypes = [vp, C.POINTER(PsMapStoreF32), C.POINTER(PsMapViewRequest), C.POINTER(PsMapViewOutF32)]
+    L.ps_pose_sets_l2_device.argtypes = [vp, C.POINTER(PsMapStoreF32), C.POINTER(PsPoseSetRequest), C.POINTER(PsPoseSetOutF32)]
+    L.ps_loop_pairs_l2_device.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsLoopBatchF32),
+                                          C.POINTER(PsLoopResults)]
     L.ps_batch_queue_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.ps_batch_queue_destroy.argtypes = [vp]
     L.ps_batch_queue_destroy.restype = None
@@ -240,7 +249,7 @@ def load_path(path):
     L.ps_last_kernel_times_ms.argtypes = [vp, vp]
     L.ps_kernel_time_totals.argtypes = [vp, vp, vp]
     L.ps_context_enable_timing.argtypes = [vp, i32]
-    for n in list(ABI_STRUCTS) + list(ABI_STRUCTS_F32):
+    for n in list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -252,3 +261,7 @@ def struct_sizes():
 
 def struct_sizes_f32():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_F32.items()}
+
+
+def struct_sizes_store_f32():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_STORE_F32.items()}

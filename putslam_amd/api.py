@@ -10,8 +10,8 @@ import numpy as np
 
 from . import _lib
 from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, PS_SET_INVALID, PsExclusionRule, PsFrameSet,  # noqa: F401
-                   PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopResults, PsMapBatch, PsMapBatchF32, PsPairResults, PsMapStore, PsMapViewOut, PsMapViewRequest,
-                   PsPoseSetOut, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
+                   PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch, PsMapBatchF32, PsPairResults, PsMapStore,
+                   PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
 
 
 class PsError(RuntimeError):
@@ -518,6 +518,19 @@ class Context:
         """ps_pose_sets_device on filled structs of device pointers (asynchronous): device_batch.build_pose_sets."""
         self._chk(self._L.ps_pose_sets_device(self._h, C.byref(store), C.byref(request), C.byref(out)))
 
+    def map_views_l2_device(self, store: PsMapStoreF32, request: PsMapViewRequest, out: PsMapViewOutF32):
+        """ps_map_views_l2_device on filled structs of device pointers (asynchronous): device_batch.build_map_views_l2."""
+        self._chk(self._L.ps_map_views_l2_device(self._h, C.byref(store), C.byref(request), C.byref(out)))
+
+    def pose_sets_l2_device(self, store: PsMapStoreF32, request: PsPoseSetRequest, out: PsPoseSetOutF32):
+        """ps_pose_sets_l2_device on filled structs of device pointers (asynchronous): device_batch.build_pose_sets_l2."""
+        self._chk(self._L.ps_pose_sets_l2_device(self._h, C.byref(store), C.byref(request), C.byref(out)))
+
+    def loop_pairs_l2_device(self, params, cfg, K, batch: PsLoopBatchF32, out: PsLoopResults):
+        """ps_loop_pairs_l2_device on filled structs of device pointers (asynchronous): device_batch.run_loop_pairs_l2."""
+        K = None if K is None else np.ascontiguousarray(K, np.float32)
+        self._chk(self._L.ps_loop_pairs_l2_device(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(batch), C.byref(out)))
+
     def loop_pairs_device(self, params, cfg, K, batch: PsLoopBatch, out: PsLoopResults):
         """ps_loop_pairs_device on filled structs of device pointers (asynchronous): device_batch.run_loop_pairs."""
         K = None if K is None else np.ascontiguousarray(K, np.float32)
@@ -534,6 +547,20 @@ class Context:
         Returns dict(poses (S,) the unique pose ids, pairs (L, 2) set indices, set_count (S,), ratio (L,) -- matchingRatio as
         the reference logs it: 0.0 gated, -1.0 no matches --, closed (L,) bool, num_paired (L,), paired_rows / paired_feat:
         lists of (n, 2) arrays (rows of the two sets / feature indices), pose (L, 4, 4), stats, num_matches)."""
+        from . import device_batch as db
+        return self._verify_loop_closures(db.build_pose_sets, db.LoopBatchDevice, db.run_loop_pairs, store, obs_point3d, candidates,
+                                          params, cfg, K, min_features, ratio_threshold, max_kpts)
+
+    def verify_loop_closures_l2(self, store, obs_point3d, candidates, params, cfg, K, min_features=35, ratio_threshold=0.4,
+                                max_kpts=None):
+        """verify_loop_closures for a store of float descriptor rows (a device_batch.MapStoreF32Device): ps_pose_sets_l2_device
+        and ps_loop_pairs_l2_device; the same contract, the same result dict, the same single retry at the reported capacity."""
+        from . import device_batch as db
+        return self._verify_loop_closures(db.build_pose_sets_l2, db.LoopBatchF32Device, db.run_loop_pairs_l2, store, obs_point3d,
+                                          candidates, params, cfg, K, min_features, ratio_threshold, max_kpts)
+
+    def _verify_loop_closures(self, build_sets, batch_type, run_pairs, store, obs_point3d, candidates, params, cfg, K, min_features,
+                              ratio_threshold, max_kpts):
         from . import device_batch
         cand = np.ascontiguousarray(candidates, np.int32).reshape(-1, 2)
         poses, inv = np.unique(cand.reshape(-1), return_inverse=True)
@@ -542,9 +569,9 @@ class Context:
         obs_point3d = device_batch.to_device_tensor(obs_point3d, device_batch.torch.float64, store.device, (-1, 3))
 
         def run(cap):
-            sets = device_batch.build_pose_sets(self, store, obs_point3d, poses, cap)
-            batch = device_batch.LoopBatchDevice(sets, pairs, min_features, ratio_threshold)
-            device_batch.run_loop_pairs(self, params, cfg, K, batch)
+            sets = build_sets(self, store, obs_point3d, poses, cap)
+            batch = batch_type(sets, pairs, min_features, ratio_threshold)
+            run_pairs(self, params, cfg, K, batch)
             r = batch.download()
             count = sets.set_count.cpu().numpy()[:len(poses)]
             over = count[(count < 0) & (count != PS_SET_INVALID)]     # a set overflowed its rows: -(count)

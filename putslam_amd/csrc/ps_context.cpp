@@ -261,7 +261,7 @@ void ps_context_destroy(PsContext *ctx)
     Buf *all[] = {&ctx->keys, &ctx->recA, &ctx->recB, &ctx->recC, &ctx->recD, &ctx->recE, &ctx->recF, &ctx->recShadow, &ctx->models, &ctx->survA, &ctx->survB, &ctx->survN, &ctx->recF2, &ctx->permBuf, &ctx->prefInfo, &ctx->frontRec, &ctx->validMask, &ctx->stamps, &ctx->dbgCnt, &ctx->bailCnt, &ctx->counts, &ctx->mvalid,
                   &ctx->cmax, &ctx->idxList, &ctx->raw, &ctx->xq, &ctx->tabR, &ctx->tabU, &ctx->sDesc, &ctx->sNk,
                   &ctx->sMatches, &ctx->sNumM, &ctx->sMask, &ctx->sPose, &ctx->sStats,
-                  &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab, &ctx->poseSets, &ctx->loopPairs, &ctx->l2Keys, &ctx->l2Img, &ctx->l2Norms, &ctx->l2List, &ctx->l2ListLo, &ctx->l2Count, &ctx->l2Stat};
+                  &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab, &ctx->poseSets, &ctx->loopPairs, &ctx->l2Keys, &ctx->l2Img, &ctx->l2Norms, &ctx->l2List, &ctx->l2ListLo, &ctx->l2Count, &ctx->l2Stat, &ctx->gatherObs};
     for (Buf *b : all) release(*b);
     for (hipEvent_t e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
@@ -329,7 +329,7 @@ int ps_context_get_option(const PsContext *ctx, const char *name)
                             &ctx->survA, &ctx->survB, &ctx->survN, &ctx->recF2, &ctx->permBuf, &ctx->prefInfo, &ctx->frontRec,
                             &ctx->validMask, &ctx->stamps, &ctx->dbgCnt, &ctx->bailCnt, &ctx->counts, &ctx->mvalid, &ctx->cmax,
                             &ctx->idxList, &ctx->raw, &ctx->xq, &ctx->tabR, &ctx->tabU, &ctx->sDesc, &ctx->sNk, &ctx->sMatches,
-                            &ctx->sNumM, &ctx->sMask, &ctx->sPose, &ctx->sStats, &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab, &ctx->poseSets, &ctx->loopPairs, &ctx->l2Keys, &ctx->l2Img, &ctx->l2Norms, &ctx->l2List, &ctx->l2ListLo, &ctx->l2Count, &ctx->l2Stat};
+                            &ctx->sNumM, &ctx->sMask, &ctx->sPose, &ctx->sStats, &ctx->sMisc0, &ctx->sMisc1, &ctx->sMisc2, &ctx->exFlag, &ctx->exPar, &ctx->viewChunks, &ctx->levelTab, &ctx->poseSets, &ctx->loopPairs, &ctx->l2Keys, &ctx->l2Img, &ctx->l2Norms, &ctx->l2List, &ctx->l2ListLo, &ctx->l2Count, &ctx->l2Stat, &ctx->gatherObs};
         size_t sum = 0;
         for (const Buf *b : all) sum += b->cap;
         return (int)((sum + (((size_t)1 << 20) - 1)) >> 20);

@@ -59,6 +59,7 @@ struct PsContext {
     Buf l2Keys;        // float-descriptor matcher (ps_match_l2.h): per pair, query split and train row the nearest query, (distance bits, index)
     Buf l2Img, l2Norms, l2List, l2ListLo, l2Count, l2Stat; // ... its matrix-core prefilter: operand image and squared norms per frame, candidate lists
                                                  // and their counts per pair, train row and slot, the diagnostic counters
+    Buf gatherObs;     // float-row store (ps_map_store_f32.h): the observation of every output row when the caller keeps no obsIdx
     // cached stop tables
     int tabEstimator = -1, tabH = -1, tabRN = 0, tabUN = 0, tabIter0 = 0;
     double tabMinRatio = -1.0;

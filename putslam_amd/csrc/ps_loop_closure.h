@@ -143,7 +143,8 @@ __global__ __launch_bounds__(kPoseBlock) void ps_pose_scan(PoseSetArgs a)
     }
 }
 
-__global__ __launch_bounds__(kPoseBlock) void ps_pose_emit(PoseSetArgs a)
+// DESC = false (the float-row store, ps_map_store_f32.h): the 32 descriptor bytes are left out; obsIdx is then always given
+template <bool DESC = true> __global__ __launch_bounds__(kPoseBlock) void ps_pose_emit(PoseSetArgs a)
 {
     extern __shared__ __align__(16) unsigned s_bm[];
     if (a.bad[0] != 0) return; // (the whole grid)
@@ -172,9 +173,11 @@ __global__ __launch_bounds__(kPoseBlock) void ps_pose_emit(PoseSetArgs a)
 #pragma unroll
             for (int j = 0; j < kPoseWords; ++j) row += j < w ? __popc(bm[j]) : (j == w ? __popc(bm[j] & below) : 0);
             if (row < 0 || row >= n) continue;
-            uint4 *__restrict__ d = a.desc + (size_t)k * a.descStride + 2 * (size_t)row;
-            d[0] = a.obsDesc[2 * (size_t)o];
-            d[1] = a.obsDesc[2 * (size_t)o + 1];
+            if (DESC) {
+                uint4 *__restrict__ d = a.desc + (size_t)k * a.descStride + 2 * (size_t)row;
+                d[0] = a.obsDesc[2 * (size_t)o];
+                d[1] = a.obsDesc[2 * (size_t)o + 1];
+            }
             float *__restrict__ p = a.pts + (size_t)k * a.ptsStride + 3 * (size_t)row;
             p[0] = (float)a.obsPoint3D[3 * (size_t)o]; // matcher.cpp:819-821
             p[1] = (float)a.obsPoint3D[3 * (size_t)o + 1];
@@ -261,58 +264,49 @@ __global__ __launch_bounds__(kBlock) void ps_loop_verdict(LoopArgs a)
 
 } // namespace psdev
 
-// Host side (part of the device translation unit, ps_capi.hip): the checks and the launches
-extern "C" {
+// Host side (part of the device translation unit, ps_capi.hip): the checks and the launches.  ps_map_store_f32.h runs the same
+// chains for a store of float rows: the two store structs differ in obsDesc alone, the two batches in `sets` alone.
+namespace {
 
-size_t ps_abi_sizeof_pose_set_request(void) { return sizeof(PsPoseSetRequest); }
-size_t ps_abi_sizeof_pose_set_out(void) { return sizeof(PsPoseSetOut); }
-size_t ps_abi_sizeof_loop_batch(void) { return sizeof(PsLoopBatch); }
-size_t ps_abi_sizeof_loop_results(void) { return sizeof(PsLoopResults); }
-
-int ps_pose_sets_device(PsContext *ctx, const PsMapStore *store, const PsPoseSetRequest *req, const PsPoseSetOut *out)
+// The argument rules of a pose-set call that do not concern the descriptor rows or the output set
+template <class Store, class Out>
+int check_pose_call(PsContext *ctx, const char *who, const Store *store, const PsPoseSetRequest *req, const Out *out)
 {
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (!store || !req || !out) return fail(ctx, PS_ERR_BAD_ARG, "ps_pose_sets_device: null store, request or output block");
-    if (store->numFeatures < 0 || store->numObs < 0 || store->numPoses < 0 || req->S < 0)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_pose_sets_device: a negative count (numFeatures, numObs, numPoses, S)");
-    if (req->S > PS_LOOP_MAX_SETS) return fail(ctx, PS_ERR_UNSUPPORTED, "ps_pose_sets_device: more than PS_LOOP_MAX_SETS sets");
-    FrameStrides strides;
-    rc = check_frame_set(ctx, out->sets, "ps_pose_sets_device: output sets", strides);
-    if (rc) return rc;
+    const std::string w(who);
     const int S = req->S;
-    if (out->sets.numFrames < S + 1) return fail(ctx, PS_ERR_BAD_ARG, "ps_pose_sets_device: the output set has fewer than S + 1 frames");
-    if (S > 0 && (!req->poses || !out->setCount)) return fail(ctx, PS_ERR_BAD_ARG, "ps_pose_sets_device: null poses or setCount");
+    if (out->sets.numFrames < S + 1) return fail(ctx, PS_ERR_BAD_ARG, (w + ": the output set has fewer than S + 1 frames").c_str());
+    if (S > 0 && (!req->poses || !out->setCount)) return fail(ctx, PS_ERR_BAD_ARG, (w + ": null poses or setCount").c_str());
     if (S > 0 && (!store->obsStart || (store->numObs > 0 && (!store->obsPose || !store->obsDesc || !req->obsPoint3D))))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_pose_sets_device: null array in the store, or null obsPoint3D");
-    if (((uintptr_t)store->obsDesc & 15) != 0) return fail(ctx, PS_ERR_BAD_ARG, "ps_pose_sets_device: obsDesc must be 16-byte aligned");
-    TimingOff toff(ctx);
-    if (S == 0) { // nothing but the empty set
-        PS_HIP(hipMemsetAsync((void *)out->sets.nkpts, 0, sizeof(int32_t), ctx->stream));
-        return PS_OK;
-    }
-    const int chunks = (store->numFeatures + kPoseBlock - 1) / kPoseBlock;
-    const size_t fixedInts = 4 + (size_t)S + (size_t)store->numPoses; // bad (padded) | next | head
-    PS_ENSURE(ctx->poseSets, (fixedInts + (size_t)chunks * S) * sizeof(int32_t));
-    HandoffGuard handoffGuard{ctx}; // (the context's scratch is in use until the launches have run)
-    PoseSetArgs a{};
-    a.obsStart = store->obsStart; a.obsPose = store->obsPose; a.obsDesc = (const uint4 *)store->obsDesc;
+        return fail(ctx, PS_ERR_BAD_ARG, (w + ": null array in the store, or null obsPoint3D").c_str());
+    return PS_OK;
+}
+
+template <class Store, class Out> void fill_pose_args(PoseSetArgs &a, const Store *store, const PsPoseSetRequest *req, const Out *out)
+{
+    a.obsStart = store->obsStart; a.obsPose = store->obsPose;
     a.obsPoint3D = req->obsPoint3D;
     a.numFeatures = store->numFeatures; a.numObs = store->numObs; a.numPoses = store->numPoses;
-    a.poses = req->poses; a.S = S;
-    const PsFrameSet &fs = out->sets;
-    a.desc = (uint4 *)fs.desc; a.pts = (float *)fs.pts; a.nkpts = (int32_t *)fs.nkpts;
-    a.maxKpts = fs.maxKpts;
-    a.descStride = strides.descUint4();
-    a.ptsStride = strides.ptsFloats();
+    a.poses = req->poses; a.S = req->S;
+    a.pts = (float *)out->sets.pts; a.nkpts = (int32_t *)out->sets.nkpts;
+    a.maxKpts = out->sets.maxKpts;
     a.setCount = out->setCount; a.featIdx = out->featIdx; a.obsIdx = out->obsIdx;
+}
+
+// The scratch and the four launches for S >= 1 sets.  DESC = false: ps_pose_emit leaves the descriptor rows out.
+template <bool DESC> int run_pose_chain(PsContext *ctx, PoseSetArgs &a)
+{
+    const int S = a.S;
+    const int chunks = (a.numFeatures + kPoseBlock - 1) / kPoseBlock;
+    const size_t fixedInts = 4 + (size_t)S + (size_t)a.numPoses; // bad (padded) | next | head
+    PS_ENSURE(ctx->poseSets, (fixedInts + (size_t)chunks * S) * sizeof(int32_t));
+    HandoffGuard handoffGuard{ctx}; // (the context's scratch is in use until the launches have run)
     a.bad = (int32_t *)ctx->poseSets.p;
     a.next = a.bad + 4;
     a.head = a.next + S;
-    a.chunkCount = a.head + store->numPoses;
+    a.chunkCount = a.head + a.numPoses;
     a.chunks = chunks;
     PS_HIP(hipMemsetAsync(a.bad, 0, 4 * sizeof(int32_t), ctx->stream));
-    if (store->numPoses > 0) PS_HIP(hipMemsetAsync(a.head, 0xFF, (size_t)store->numPoses * sizeof(int32_t), ctx->stream));
+    if (a.numPoses > 0) PS_HIP(hipMemsetAsync(a.head, 0xFF, (size_t)a.numPoses * sizeof(int32_t), ctx->stream));
     hipLaunchKernelGGL(ps_pose_table, dim3(1), dim3(kPoseTableBlock), 0, ctx->stream, a.poses, S, a.numPoses, a.head, a.next);
     PS_HIP(hipGetLastError());
     const size_t lds = (size_t)S * kPoseWords * sizeof(unsigned); // 32 KiB at PS_LOOP_MAX_SETS
@@ -323,30 +317,31 @@ int ps_pose_sets_device(PsContext *ctx, const PsMapStore *store, const PsPoseSet
     hipLaunchKernelGGL(ps_pose_scan, dim3((unsigned)S), dim3(kPoseBlock), 0, ctx->stream, a);
     PS_HIP(hipGetLastError());
     if (chunks > 0) {
-        hipLaunchKernelGGL(ps_pose_emit, dim3((unsigned)chunks), dim3(kPoseBlock), lds, ctx->stream, a);
+        hipLaunchKernelGGL(ps_pose_emit<DESC>, dim3((unsigned)chunks), dim3(kPoseBlock), lds, ctx->stream, a);
         PS_HIP(hipGetLastError());
     }
     return PS_OK;
 }
 
-int ps_loop_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
-                         const PsLoopBatch *b, const PsLoopResults *out)
+// ps_loop_pairs_device / ps_loop_pairs_l2_device: checkSets(b->sets) holds the rule of the batch's frame set, match(eff, L, pl)
+// runs the matcher of its descriptor kind on the effective pairs.
+template <class Batch, class Check, class Match>
+int loop_pairs_body(PsContext *ctx, const char *who, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                    const Batch *b, const PsLoopResults *out, Check checkSets, Match match)
 {
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (!b || !out || b->L < 0) return fail(ctx, PS_ERR_BAD_ARG, "ps_loop_pairs_device: null batch or results, or L < 0");
+    const std::string w(who);
+    if (!b || !out || b->L < 0) return fail(ctx, PS_ERR_BAD_ARG, (w + ": null batch or results, or L < 0").c_str());
     if (b->L == 0) return PS_OK;
-    if (b->S < 0 || !b->pairs || !b->setCount) return fail(ctx, PS_ERR_BAD_ARG, "ps_loop_pairs_device: S < 0, null pairs or setCount");
-    FrameStrides strides; // (checked here, before anything is planned or allocated; run_match_stage resolves them for its launches)
-    rc = check_frame_set(ctx, b->sets, "ps_loop_pairs_device: sets", strides);
+    if (b->S < 0 || !b->pairs || !b->setCount) return fail(ctx, PS_ERR_BAD_ARG, (w + ": S < 0, null pairs or setCount").c_str());
+    int rc = checkSets(b->sets); // (checked here, before anything is planned or allocated)
     if (rc) return rc;
     if ((long long)b->sets.numFrames < (long long)b->S + 1)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_loop_pairs_device: the frame set has fewer than S + 1 frames (the empty set is frame S)");
+        return fail(ctx, PS_ERR_BAD_ARG, (w + ": the frame set has fewer than S + 1 frames (the empty set is frame S)").c_str());
     const PsPairResults &pr = out->pair;
     if (!pr.matches || !pr.numMatches || !pr.inlierMask || !pr.pose || !pr.stats || !out->ratio || !out->closed || !out->numPaired ||
         !out->pairedRows)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_loop_pairs_device: null output");
-    if (out->pairedFeat && !b->featIdx) return fail(ctx, PS_ERR_BAD_ARG, "ps_loop_pairs_device: pairedFeat needs featIdx");
+        return fail(ctx, PS_ERR_BAD_ARG, (w + ": null output").c_str());
+    if (out->pairedFeat && !b->featIdx) return fail(ctx, PS_ERR_BAD_ARG, (w + ": pairedFeat needs featIdx").c_str());
     if (cfg && cfg->sampleIdx) return fail(ctx, PS_ERR_BAD_ARG, "explicit sample streams are per call, not per batch");
     const int L = b->L, cap = b->sets.maxKpts;
     Plan pl;
@@ -367,13 +362,67 @@ int ps_loop_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsR
     PS_HIP(hipGetLastError());
     rc = prepare_score(ctx, pl, L, cap, false, true, b->sets.desc);
     if (rc) return rc;
-    rc = run_match_stage(ctx, b->sets, a.eff, L, &pl, pr.matches, pr.numMatches, 0);
+    rc = match(a.eff, L, pl);
     if (rc) return rc;
     rc = run_ransac_stage(ctx, pl, L, cap, pr.matches, pr.numMatches, cap, pr.pose, pr.inlierMask, pr.stats, 2);
     if (rc) return rc;
     hipLaunchKernelGGL(ps_loop_verdict, dim3((unsigned)L), dim3(kBlock), 0, ctx->stream, a);
     PS_HIP(hipGetLastError());
     return PS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+size_t ps_abi_sizeof_pose_set_request(void) { return sizeof(PsPoseSetRequest); }
+size_t ps_abi_sizeof_pose_set_out(void) { return sizeof(PsPoseSetOut); }
+size_t ps_abi_sizeof_loop_batch(void) { return sizeof(PsLoopBatch); }
+size_t ps_abi_sizeof_loop_results(void) { return sizeof(PsLoopResults); }
+
+int ps_pose_sets_device(PsContext *ctx, const PsMapStore *store, const PsPoseSetRequest *req, const PsPoseSetOut *out)
+{
+    const char *who = "ps_pose_sets_device";
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!store || !req || !out) return fail(ctx, PS_ERR_BAD_ARG, "ps_pose_sets_device: null store, request or output block");
+    if (store->numFeatures < 0 || store->numObs < 0 || store->numPoses < 0 || req->S < 0)
+        return fail(ctx, PS_ERR_BAD_ARG, "ps_pose_sets_device: a negative count (numFeatures, numObs, numPoses, S)");
+    if (req->S > PS_LOOP_MAX_SETS) return fail(ctx, PS_ERR_UNSUPPORTED, "ps_pose_sets_device: more than PS_LOOP_MAX_SETS sets");
+    FrameStrides strides;
+    rc = check_frame_set(ctx, out->sets, "ps_pose_sets_device: output sets", strides);
+    if (rc) return rc;
+    rc = check_pose_call(ctx, who, store, req, out);
+    if (rc) return rc;
+    if (((uintptr_t)store->obsDesc & 15) != 0) return fail(ctx, PS_ERR_BAD_ARG, "ps_pose_sets_device: obsDesc must be 16-byte aligned");
+    TimingOff toff(ctx);
+    if (req->S == 0) { // nothing but the empty set
+        PS_HIP(hipMemsetAsync((void *)out->sets.nkpts, 0, sizeof(int32_t), ctx->stream));
+        return PS_OK;
+    }
+    PoseSetArgs a{};
+    fill_pose_args(a, store, req, out);
+    a.obsDesc = (const uint4 *)store->obsDesc;
+    a.desc = (uint4 *)out->sets.desc;
+    a.descStride = strides.descUint4();
+    a.ptsStride = strides.ptsFloats();
+    return run_pose_chain<true>(ctx, a);
+}
+
+int ps_loop_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                         const PsLoopBatch *b, const PsLoopResults *out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    return loop_pairs_body(
+        ctx, "ps_loop_pairs_device", params, cfg, K, b, out,
+        [&](const PsFrameSet &fs) {
+            FrameStrides strides; // (run_match_stage resolves them again for its launches)
+            return check_frame_set(ctx, fs, "ps_loop_pairs_device: sets", strides);
+        },
+        [&](const int32_t *eff, int L, const Plan &pl) {
+            return run_match_stage(ctx, b->sets, eff, L, &pl, out->pair.matches, out->pair.numMatches, 0);
+        });
 }
 
 } // extern "C"

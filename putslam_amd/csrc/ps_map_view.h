@@ -193,7 +193,9 @@ template <bool STAGED> __global__ __launch_bounds__(kViewBlock) void ps_view_sel
     if (tid == 0) a.chunkCount[blk] = (sCnt[0] + sCnt[1]) + (sCnt[2] + sCnt[3]);
 }
 
-template <bool STAGED> __global__ __launch_bounds__(kViewBlock) void ps_view_emit(ViewArgs a)
+// DESC = false (the float-row store, ps_map_store_f32.h): the row's 32 descriptor bytes are left out -- obsIdx, which is then
+// always given, names the observation and ps_gather_rows_f32 copies its row afterwards.
+template <bool STAGED, bool DESC = true> __global__ __launch_bounds__(kViewBlock) void ps_view_emit(ViewArgs a)
 {
     __shared__ double sAng[STAGED ? kViewAngleLds : 1];
     __shared__ int sPre[kViewWaves], sTot[kViewWaves];
@@ -246,9 +248,11 @@ template <bool STAGED> __global__ __launch_bounds__(kViewBlock) void ps_view_emi
     bool bad = false;
     if (!view_eval<true>(a, M, ang, f, r, bad) || bad || row >= a.maxKpts) return; // (what the select pass kept is kept again)
     const size_t o = (size_t)v * a.maxKpts + row;
-    uint4 *__restrict__ d = a.desc + (size_t)v * a.descStride + 2 * (size_t)row;
-    d[0] = a.obsDesc[2 * (size_t)r.obs];
-    d[1] = a.obsDesc[2 * (size_t)r.obs + 1];
+    if (DESC) {
+        uint4 *__restrict__ d = a.desc + (size_t)v * a.descStride + 2 * (size_t)row;
+        d[0] = a.obsDesc[2 * (size_t)r.obs];
+        d[1] = a.obsDesc[2 * (size_t)r.obs + 1];
+    }
     float *__restrict__ p = a.pts + (size_t)v * a.ptsStride + 3 * (size_t)row;
     p[0] = (float)r.p0; // matcher.cpp:700-701
     p[1] = (float)r.p1;
@@ -308,6 +312,76 @@ int ensure_level_block(PsContext *ctx)
     return PS_OK;
 }
 
+// What ps_map_views_device and ps_map_views_l2_device (ps_map_store_f32.h) share on the host side: the two store structs differ
+// in obsDesc alone, the two output blocks in `views` alone.
+// The argument rules that do not concern the descriptor rows or the output set; PS_OK with V == 0 left to the caller.
+template <class Store> int check_view_call(PsContext *ctx, const char *who, const Store *store, const PsMapViewRequest *req)
+{
+    const std::string w(who);
+    if (store->numFeatures < 0 || store->numObs < 0 || store->numPoses < 0 || req->V < 0)
+        return fail(ctx, PS_ERR_BAD_ARG, (w + ": a negative count (numFeatures, numObs, numPoses, V)").c_str());
+    if (req->V == 0) return PS_OK;
+    if (!store->obsStart || (store->numFeatures > 0 && !store->pos) ||
+        (store->numObs > 0 && (!store->obsPose || !store->obsDesc || !store->obsOctave || !store->obsDetDist)))
+        return fail(ctx, PS_ERR_BAD_ARG, (w + ": null array in the store").c_str());
+    return PS_OK;
+}
+
+template <class Out> int check_view_request(PsContext *ctx, const char *who, int numPoses, const PsMapViewRequest *req, const Out *out)
+{
+    const std::string w(who);
+    if (!req->camInv || (numPoses > 0 && !req->poseAngle)) return fail(ctx, PS_ERR_BAD_ARG, (w + ": null camInv or poseAngle").c_str());
+    if (req->cand && (!req->candCounts || req->candCapacity < 0))
+        return fail(ctx, PS_ERR_BAD_ARG, (w + ": a candidate list needs candCounts and candCapacity >= 0").c_str());
+    if (!out->mapLevel || !out->viewCount) return fail(ctx, PS_ERR_BAD_ARG, (w + ": null mapLevel or viewCount").c_str());
+    return PS_OK;
+}
+
+// The store's index arrays, the request and the side arrays of a checked call (descriptor rows and the output set: the caller's)
+template <class Store, class Out> void fill_view_args(ViewArgs &a, const Store *store, const PsMapViewRequest *req, const Out *out)
+{
+    a.pos = store->pos; a.obsStart = store->obsStart; a.obsPose = store->obsPose;
+    a.obsOctave = store->obsOctave; a.obsDetDist = store->obsDetDist;
+    a.numFeatures = store->numFeatures; a.numObs = store->numObs; a.numPoses = store->numPoses;
+    a.camInv = req->camInv; a.poseAngle = req->poseAngle; a.cand = req->cand; a.candCounts = req->candCounts;
+    a.maxAngle = req->maxAngle; a.fx = req->fx; a.fy = req->fy; a.cx = req->cx; a.cy = req->cy;
+    a.imageW = req->imageW; a.imageH = req->imageH;
+    a.slots = req->cand ? req->candCapacity : store->numFeatures;
+    a.flags = req->flags;
+    a.nkpts = (int32_t *)out->views.nkpts; a.pts = (float *)out->views.pts;
+    a.maxKpts = out->views.maxKpts;
+    a.mapLevel = out->mapLevel; a.viewCount = out->viewCount; a.featIdx = out->featIdx; a.obsIdx = out->obsIdx;
+    a.posCam = out->posCam; a.uv = out->uv; a.angle = out->angle;
+}
+
+// The level block, the scratch and the two launches for V views.  DESC = false: ps_view_emit leaves the descriptor rows out.
+template <bool DESC> int run_view_chain(PsContext *ctx, const char *who, ViewArgs &a, int V)
+{
+    const int chunks = a.slots > 0 ? (a.slots + kViewBlock - 1) / kViewBlock : 1;
+    if ((long long)V * chunks > (long long)INT_MAX)
+        return fail(ctx, PS_ERR_UNSUPPORTED, (std::string(who) + ": V x candidate chunks exceeds the grid").c_str());
+    int rc = ensure_level_block(ctx);
+    if (rc) return rc;
+    const size_t groups = (size_t)V * chunks;
+    PS_ENSURE(ctx->viewChunks, groups * (kViewWaves * 8 + 4) + (size_t)V * 4);
+    HandoffGuard handoffGuard{ctx}; // (the context's scratch is in use until the launches have run)
+    a.levels = (const LevelBlock *)ctx->levelTab.p;
+    a.keptMask = (unsigned long long *)ctx->viewChunks.p;
+    a.chunkCount = (int32_t *)(a.keptMask + groups * kViewWaves);
+    a.bad = a.chunkCount + groups;
+    a.chunks = chunks;
+    PS_HIP(hipMemsetAsync(a.bad, 0, (size_t)V * 4, ctx->stream));
+    const dim3 grid((unsigned)groups), block(kViewBlock);
+    const bool staged = a.numPoses <= kViewAngleLds;
+    if (staged) hipLaunchKernelGGL(ps_view_select<true>, grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL(ps_view_select<false>, grid, block, 0, ctx->stream, a);
+    PS_HIP(hipGetLastError());
+    if (staged) hipLaunchKernelGGL((ps_view_emit<true, DESC>), grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL((ps_view_emit<false, DESC>), grid, block, 0, ctx->stream, a);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -318,65 +392,27 @@ size_t ps_abi_sizeof_map_view_out(void) { return sizeof(PsMapViewOut); }
 
 int ps_map_views_device(PsContext *ctx, const PsMapStore *store, const PsMapViewRequest *req, const PsMapViewOut *out)
 {
+    const char *who = "ps_map_views_device";
     int rc = bind(ctx);
     if (rc) return rc;
     if (!store || !req || !out) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null store, request or output block");
-    if (store->numFeatures < 0 || store->numObs < 0 || store->numPoses < 0 || req->V < 0)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: a negative count (numFeatures, numObs, numPoses, V)");
-    if (req->V == 0) return PS_OK;
-    if (!store->obsStart || (store->numFeatures > 0 && !store->pos) ||
-        (store->numObs > 0 && (!store->obsPose || !store->obsDesc || !store->obsOctave || !store->obsDetDist)))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null array in the store");
+    rc = check_view_call(ctx, who, store, req);
+    if (rc || req->V == 0) return rc;
     if (((uintptr_t)store->obsDesc & 15) != 0) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: obsDesc must be 16-byte aligned");
-    if (!req->camInv || (store->numPoses > 0 && !req->poseAngle))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null camInv or poseAngle");
-    if (req->cand && (!req->candCounts || req->candCapacity < 0))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: a candidate list needs candCounts and candCapacity >= 0");
-    if (!out->mapLevel || !out->viewCount) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: null mapLevel or viewCount");
+    rc = check_view_request(ctx, who, store->numPoses, req, out);
+    if (rc) return rc;
     FrameStrides strides;
     rc = check_frame_set(ctx, out->views, "ps_map_views_device: output views", strides);
     if (rc) return rc;
     if (out->views.numFrames < req->V) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_views_device: the output set has fewer than V views");
-    const int V = req->V, slots = req->cand ? req->candCapacity : store->numFeatures;
-    const int chunks = slots > 0 ? (slots + kViewBlock - 1) / kViewBlock : 1;
-    if ((long long)V * chunks > (long long)INT_MAX)
-        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_map_views_device: V x candidate chunks exceeds the grid");
     TimingOff toff(ctx);
-    rc = ensure_level_block(ctx);
-    if (rc) return rc;
-    const size_t groups = (size_t)V * chunks;
-    PS_ENSURE(ctx->viewChunks, groups * (kViewWaves * 8 + 4) + (size_t)V * 4);
-    HandoffGuard handoffGuard{ctx}; // (the context's scratch is in use until the launches have run)
     ViewArgs a{};
-    a.pos = store->pos; a.obsStart = store->obsStart; a.obsPose = store->obsPose;
-    a.obsDesc = (const uint4 *)store->obsDesc; a.obsOctave = store->obsOctave; a.obsDetDist = store->obsDetDist;
-    a.numFeatures = store->numFeatures; a.numObs = store->numObs; a.numPoses = store->numPoses;
-    a.camInv = req->camInv; a.poseAngle = req->poseAngle; a.cand = req->cand; a.candCounts = req->candCounts;
-    a.maxAngle = req->maxAngle; a.fx = req->fx; a.fy = req->fy; a.cx = req->cx; a.cy = req->cy;
-    a.imageW = req->imageW; a.imageH = req->imageH;
-    a.slots = slots; a.flags = req->flags;
-    const PsFrameSet &fs = out->views;
-    a.desc = (uint4 *)fs.desc; a.pts = (float *)fs.pts; a.nkpts = (int32_t *)fs.nkpts;
-    a.maxKpts = fs.maxKpts;
+    fill_view_args(a, store, req, out);
+    a.obsDesc = (const uint4 *)store->obsDesc;
+    a.desc = (uint4 *)out->views.desc;
     a.descStride = strides.descUint4();
     a.ptsStride = strides.ptsFloats();
-    a.mapLevel = out->mapLevel; a.viewCount = out->viewCount; a.featIdx = out->featIdx; a.obsIdx = out->obsIdx;
-    a.posCam = out->posCam; a.uv = out->uv; a.angle = out->angle;
-    a.levels = (const LevelBlock *)ctx->levelTab.p;
-    a.keptMask = (unsigned long long *)ctx->viewChunks.p;
-    a.chunkCount = (int32_t *)(a.keptMask + groups * kViewWaves);
-    a.bad = a.chunkCount + groups;
-    a.chunks = chunks;
-    PS_HIP(hipMemsetAsync(a.bad, 0, (size_t)V * 4, ctx->stream));
-    const dim3 grid((unsigned)groups), block(kViewBlock);
-    const bool staged = store->numPoses <= kViewAngleLds;
-    if (staged) hipLaunchKernelGGL(ps_view_select<true>, grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL(ps_view_select<false>, grid, block, 0, ctx->stream, a);
-    PS_HIP(hipGetLastError());
-    if (staged) hipLaunchKernelGGL(ps_view_emit<true>, grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL(ps_view_emit<false>, grid, block, 0, ctx->stream, a);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
+    return run_view_chain<true>(ctx, who, a, req->V);
 }
 
 int ps_frame_levels_device(PsContext *ctx, const PsFrameSet *frames, const int32_t *octave, const double *detDist, int32_t *curLevel)

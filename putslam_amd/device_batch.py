@@ -7,8 +7,9 @@ import numpy as np
 import torch
 
 from . import api
-from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopResults, PsMapStore, PsMapViewOut,
-                   PsMapViewRequest, PsPoseSetOut, PsPoseSetRequest, make_config)
+from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapStore,
+                   PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
+                   make_config)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -462,13 +463,8 @@ class MapViewsDevice(FrameSet):
                     featIdx=g(self.feat_idx), obsIdx=g(self.obs_idx), posCam=g(self.pos_cam), uv=g(self.uv), angle=g(self.angle))
 
 
-def build_map_views(ctx, store: MapStoreDevice, cam_inv, pose_angle, max_angle, K, image_size, max_kpts, cand=None,
-                    cand_counts=None, require_visible=False, out=None, packed_stride=None, use_torch_stream=True):
-    """ps_map_views_device: V map views from the resident store, asynchronous, ordered like `run_map_pairs`.
-    cam_inv (V, 4, 4): inverse camera poses (numpy, or a device tensor (V, 16) float64 column-major); pose_angle (V, num_poses):
-    api.view_angles of each view's pose (numpy or device tensor); K = (fx, fy, cx, cy); image_size = (width, height);
-    cand (V, cap) int32 + cand_counts (V,) (numpy or device tensors), or None = every feature of the store in index order.
-    Returns a MapViewsDevice (`out`, if given, is written again: a retry with the reported capacity allocates a new one)."""
+def _map_view_request(store, cam_inv, pose_angle, max_angle, K, image_size, cand, cand_counts, require_visible):
+    """(PsMapViewRequest, the device tensors it points to, V) for a store (MapStoreDevice / MapStoreF32Device)."""
     dev = store.device
     if not isinstance(cam_inv, torch.Tensor):
         cam_inv = np.ascontiguousarray(np.asarray(cam_inv, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1, 16)
@@ -490,6 +486,18 @@ def build_map_views(ctx, store: MapStoreDevice, cam_inv, pose_angle, max_angle, 
     req.fx, req.fy, req.cx, req.cy = (float(x) for x in K)
     req.imageW, req.imageH = float(image_size[0]), float(image_size[1])
     req.V, req.flags = V, PS_VIEW_REQUIRE_VISIBLE if require_visible else 0
+    return req, keep, V
+
+
+def build_map_views(ctx, store: MapStoreDevice, cam_inv, pose_angle, max_angle, K, image_size, max_kpts, cand=None,
+                    cand_counts=None, require_visible=False, out=None, packed_stride=None, use_torch_stream=True):
+    """ps_map_views_device: V map views from the resident store, asynchronous, ordered like `run_map_pairs`.
+    cam_inv (V, 4, 4): inverse camera poses (numpy, or a device tensor (V, 16) float64 column-major); pose_angle (V, num_poses):
+    api.view_angles of each view's pose (numpy or device tensor); K = (fx, fy, cx, cy); image_size = (width, height);
+    cand (V, cap) int32 + cand_counts (V,) (numpy or device tensors), or None = every feature of the store in index order.
+    Returns a MapViewsDevice (`out`, if given, is written again: a retry with the reported capacity allocates a new one)."""
+    dev = store.device
+    req, keep, V = _map_view_request(store, cam_inv, pose_angle, max_angle, K, image_size, cand, cand_counts, require_visible)
     if out is None:
         out = MapViewsDevice(V, max_kpts, dev, packed_stride)
     assert out.num_frames >= V and out.max_kpts == int(max_kpts)
@@ -608,3 +616,188 @@ def run_loop_pairs(ctx, params, cfg, K, batch: LoopBatchDevice, use_torch_stream
     like `run_pairs`: after the work already queued on torch's current stream, which waits for the results."""
     b, r = batch.batch_struct(), batch.results_struct()
     _on_torch_stream(ctx, batch.device, lambda: ctx.loop_pairs_device(params, cfg, K, b, r), use_torch_stream)
+
+
+# ---- the resident store with float descriptor rows (SURF / SIFT): ps_map_views_l2_device / ps_pose_sets_l2_device /
+# ps_loop_pairs_l2_device (DESIGN.md section 8.8)
+def _rows_f32(device, rows, dim, row_floats, offset_floats):
+    """(flat, rows view): zero-filled float32 storage for `rows` rows of `dim` floats lying row_floats floats apart, the first
+    one offset_floats floats behind the allocation's (256-byte aligned) base."""
+    row_floats = dim if row_floats is None else int(row_floats)
+    assert row_floats >= dim and offset_floats >= 0
+    flat = _zeros(device, (int(offset_floats) + max(rows, 1) * row_floats,), torch.float32)
+    return flat, flat[int(offset_floats):].view(max(rows, 1), row_floats), row_floats
+
+
+class MapStoreF32Device:
+    """MapStoreDevice with float descriptor rows (PsMapStoreF32): obs_desc (O, dim) float32.  row_floats > dim: the rows lie
+    row_floats floats apart, what lies between them holds `pad` (never read by the library); offset_floats: the first row lies
+    that many floats behind the allocation's base (a store that is not 16-byte aligned).  Rows are uploaded as they are: NaN
+    payloads, -0.0 and subnormals included."""
+
+    def __init__(self, pos, obs_start, obs_pose, obs_desc, obs_octave, obs_det_dist, num_poses, device="cuda:0", row_floats=None,
+                 pad=np.nan, offset_floats=0):
+        self.device = torch.device(device)
+        pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+        obs_start = np.ascontiguousarray(obs_start, np.int32)
+        obs_pose = np.ascontiguousarray(obs_pose, np.int32)
+        obs_desc = np.ascontiguousarray(obs_desc, np.float32)
+        assert obs_desc.ndim == 2
+        obs_octave = np.ascontiguousarray(obs_octave, np.int32)
+        obs_det_dist = np.ascontiguousarray(obs_det_dist, np.float64)
+        self.num_features, self.num_obs, self.num_poses = pos.shape[0], obs_pose.shape[0], int(num_poses)
+        self.dim = int(obs_desc.shape[1])
+        assert obs_start.shape == (self.num_features + 1,)
+        assert obs_desc.shape[0] == obs_octave.shape[0] == obs_det_dist.shape[0] == self.num_obs
+        self.desc_flat, self.obs_desc, self.row_floats = _rows_f32(self.device, self.num_obs, self.dim, row_floats, offset_floats)
+        if self.num_obs:
+            wide = np.full((self.num_obs, self.row_floats), pad, np.float32)
+            wide.view(np.uint32)[:, :self.dim] = obs_desc.view(np.uint32)   # (bit for bit)
+            self.obs_desc.view(torch.int32).copy_(torch.from_numpy(wide.view(np.int32)))
+        up = lambda a: torch.from_numpy(a).to(self.device)   # noqa: E731
+        self.pos, self.obs_start, self.obs_pose = up(pos), up(obs_start), up(obs_pose)
+        self.obs_octave, self.obs_det_dist = up(obs_octave), up(obs_det_dist)
+        torch.cuda.current_stream(self.device).synchronize()   # (resident before a context's own stream reads it)
+
+    def view(self):
+        return PsMapStoreF32(self.pos.data_ptr(), self.obs_start.data_ptr(), self.obs_pose.data_ptr(), self.obs_desc.data_ptr(),
+                             self.obs_octave.data_ptr(), self.obs_det_dist.data_ptr(), self.num_features, self.num_obs,
+                             self.num_poses, self.dim, 0 if self.row_floats == self.dim else self.row_floats * 4)
+
+
+class FrameSetF32Out:
+    """A float-descriptor frame set the library writes (PsFrameSetF32): desc (n, cap, row_floats) float32 -- a view of desc_flat
+    that starts offset_floats floats behind its base --, pts (n, cap, 3) float32, nkpts (n,) int32.  Usable wherever a
+    FrameSetF32Device is (MapBatchF32Device.maps, run_match_l2)."""
+
+    def _zero_frames(self, n, dim, row_floats, offset_floats):
+        cap, dev = self.max_kpts, self.device
+        self.dim, self.offset_floats = int(dim), int(offset_floats)
+        self.desc_flat, rows, self.row_floats = _rows_f32(dev, n * cap, self.dim, row_floats, offset_floats)
+        self.desc = rows.view(n, cap, self.row_floats)
+        self.pts = _zeros(dev, (n, cap, 3), torch.float32)
+        self.nkpts = _zeros(dev, (n,), torch.int32)
+
+    def view(self):
+        dense = self.row_floats == self.dim
+        return api.DeviceFramesF32(self.desc.data_ptr(), self.pts.data_ptr(), self.nkpts.data_ptr(), self.num_frames, self.max_kpts,
+                                   self.dim, 0 if dense else self.row_floats * 4, 0 if dense else self.max_kpts * self.row_floats * 4, 0)
+
+    def frame_set(self):
+        return self.view().struct()
+
+    def download_frames(self):
+        """(desc (n, cap, dim) float32, pts (n, cap, 3)) on the host; the rows bit for bit (copied as 32-bit words)."""
+        d = self.desc.view(torch.int32).cpu().numpy().view(np.float32)
+        return np.ascontiguousarray(d[:, :, :self.dim]), self.pts.cpu().numpy()
+
+
+class MapViewsF32Device(FrameSetF32Out):
+    """What ps_map_views_l2_device wrote: MapViewsDevice with float rows of `dim` floats; feeds MapBatchF32Device (maps =
+    this object, map_level = .map_level).  obs_idx=False: no obsIdx array is kept (NULL is passed: the library records the rows'
+    observations in its own scratch)."""
+
+    def __init__(self, V, max_kpts, dim, device, row_floats=None, offset_floats=0, obs_idx=True):
+        self.device = torch.device(device)
+        self.num_frames, self.max_kpts = int(V), int(max_kpts)
+        n, cap = max(self.num_frames, 1), self.max_kpts
+        new = lambda shape, dt: _zeros(self.device, shape, dt)   # noqa: E731
+        self._zero_frames(n, dim, row_floats, offset_floats)
+        self.view_count = new((n,), torch.int32)
+        self.map_level, self.feat_idx = new((n, cap), torch.int32), new((n, cap), torch.int32)
+        self.obs_idx = new((n, cap), torch.int32) if obs_idx else None
+        self.pos_cam, self.uv, self.angle = new((n, cap, 3), torch.float64), new((n, cap, 2), torch.float64), new((n, cap), torch.float64)
+        torch.cuda.current_stream(self.device).synchronize()   # (the fills are done before a context's stream writes)
+
+    def out_struct(self):
+        return PsMapViewOutF32(self.frame_set(), self.map_level.data_ptr(), self.view_count.data_ptr(), self.feat_idx.data_ptr(),
+                               self.obs_idx.data_ptr() if self.obs_idx is not None else None, self.pos_cam.data_ptr(),
+                               self.uv.data_ptr(), self.angle.data_ptr())
+
+    def download(self):
+        torch.cuda.synchronize(self.device)
+        V = self.num_frames
+        desc, pts = self.download_frames()
+        g = lambda t: t.cpu().numpy()[:V]   # noqa: E731
+        out = dict(desc=desc[:V], pts=pts[:V], nkpts=g(self.nkpts), viewCount=g(self.view_count), mapLevel=g(self.map_level),
+                   featIdx=g(self.feat_idx), posCam=g(self.pos_cam), uv=g(self.uv), angle=g(self.angle))
+        if self.obs_idx is not None:
+            out["obsIdx"] = g(self.obs_idx)
+        return out
+
+
+def build_map_views_l2(ctx, store: MapStoreF32Device, cam_inv, pose_angle, max_angle, K, image_size, max_kpts, cand=None,
+                       cand_counts=None, require_visible=False, out=None, row_floats=None, obs_idx=True, use_torch_stream=True):
+    """build_map_views for a store of float rows (ps_map_views_l2_device): the same arguments; returns a MapViewsF32Device
+    (`out`, if given, is written again)."""
+    dev = store.device
+    req, keep, V = _map_view_request(store, cam_inv, pose_angle, max_angle, K, image_size, cand, cand_counts, require_visible)
+    if out is None:
+        out = MapViewsF32Device(V, max_kpts, store.dim, dev, row_floats, 0, obs_idx)
+    assert out.num_frames >= V and out.max_kpts == int(max_kpts)
+    torch.cuda.current_stream(dev).synchronize()   # (uploads above are complete before the context's stream reads them)
+    out.inputs = keep + [store]
+    st, os_ = store.view(), out.out_struct()
+    _on_torch_stream(ctx, dev, lambda: ctx.map_views_l2_device(st, req, os_), use_torch_stream)
+    return out
+
+
+class PoseSetsF32Device(FrameSetF32Out):
+    """What ps_pose_sets_l2_device wrote: PoseSetsDevice with float rows of `dim` floats (S + 1 frames, frame S the empty set)."""
+
+    def __init__(self, S, max_kpts, dim, device, row_floats=None, offset_floats=0, side_arrays=True):
+        self.device = torch.device(device)
+        self.S, self.num_frames, self.max_kpts = int(S), int(S) + 1, int(max_kpts)
+        n, cap = self.num_frames, self.max_kpts
+        new = lambda shape, dt: _zeros(self.device, shape, dt)   # noqa: E731
+        self._zero_frames(n, dim, row_floats, offset_floats)
+        self.set_count = new((max(self.S, 1),), torch.int32)
+        self.feat_idx, self.obs_idx = (new((n, cap), torch.int32), new((n, cap), torch.int32)) if side_arrays else (None, None)
+        torch.cuda.current_stream(self.device).synchronize()   # (the fills are done before a context's stream writes)
+
+    def out_struct(self):
+        side = (None, None) if self.feat_idx is None else (self.feat_idx.data_ptr(), self.obs_idx.data_ptr())
+        return PsPoseSetOutF32(self.frame_set(), self.set_count.data_ptr(), *side)
+
+    def download(self):
+        torch.cuda.synchronize(self.device)
+        desc, pts = self.download_frames()
+        out = dict(desc=desc, pts=pts, nkpts=self.nkpts.cpu().numpy(), setCount=self.set_count.cpu().numpy()[:self.S])
+        if self.feat_idx is not None:
+            out.update(featIdx=self.feat_idx.cpu().numpy(), obsIdx=self.obs_idx.cpu().numpy())
+        return out
+
+
+def build_pose_sets_l2(ctx, store: MapStoreF32Device, obs_point3d, poses, max_kpts, row_floats=None, out=None, side_arrays=True,
+                       use_torch_stream=True):
+    """build_pose_sets for a store of float rows (ps_pose_sets_l2_device); returns a PoseSetsF32Device."""
+    dev = store.device
+    obs_point3d = to_device_tensor(obs_point3d, torch.float64, dev, (-1, 3))
+    assert tuple(obs_point3d.shape) == (store.num_obs, 3)
+    poses = to_device_tensor(poses, torch.int32, dev, (-1,))
+    assert poses.dim() == 1
+    S = int(poses.shape[0])
+    if out is None:
+        out = PoseSetsF32Device(S, max_kpts, store.dim, dev, row_floats, 0, side_arrays)
+    assert out.S == S and out.max_kpts == int(max_kpts)
+    req = PsPoseSetRequest(obs_point3d.data_ptr() if store.num_obs else None, poses.data_ptr() if S else None, S, 0)
+    torch.cuda.current_stream(dev).synchronize()   # (uploads above are complete before the context's stream reads them)
+    out.inputs = (obs_point3d, poses, store)
+    st, os_ = store.view(), out.out_struct()
+    _on_torch_stream(ctx, dev, lambda: ctx.pose_sets_l2_device(st, req, os_), use_torch_stream)
+    return out
+
+
+class LoopBatchF32Device(LoopBatchDevice):
+    """LoopBatchDevice for float-descriptor sets (PsLoopBatchF32): `sets` as build_pose_sets_l2 wrote them."""
+
+    def batch_struct(self):
+        s = self.sets
+        return PsLoopBatchF32(s.frame_set(), s.set_count.data_ptr(), s.feat_idx.data_ptr() if s.feat_idx is not None else None,
+                              self.pairs.data_ptr(), self.L, s.S, self.min_features, 0, self.ratio_threshold)
+
+
+def run_loop_pairs_l2(ctx, params, cfg, K, batch: LoopBatchF32Device, use_torch_stream=True):
+    """run_loop_pairs for float descriptors (ps_loop_pairs_l2_device)."""
+    b, r = batch.batch_struct(), batch.results_struct()
+    _on_torch_stream(ctx, batch.device, lambda: ctx.loop_pairs_l2_device(params, cfg, K, b, r), use_torch_stream)
