@@ -660,6 +660,79 @@ int ps_map_views_device(PsContext *ctx, const PsMapStore *store, const PsMapView
 int ps_frame_levels_device(PsContext *ctx, const PsFrameSet *frames, const int32_t *octave, const double *detDist,
                            int32_t *curLevel);
 
+/* ---- Pyramidal Lucas-Kanade feature tracking: MatcherOpenCV::performTracking, src/Matcher/matcherOpenCV.cpp:209-300, the first
+ * step of Matcher::trackKLT (src/Matcher/matcher.cpp:133-449) -- cv::calcOpticalFlowPyrLK on the image pair (:232-238), the error
+ * gate (:247-252), the too-close-by-error removal (:254-265) and the compaction into cv::DMatch(i, j, 0) (:267-290).
+ * The arithmetic is the project's reading of OpenCV 3.x's lkpyramid.cpp, scalar path with float accumulators (DESIGN.md section
+ * 8.9, restated in tests/klt_ref.py): integer pyramid and Scharr passes, 14-bit bilinear weights rounded half to even, the 2x2
+ * matrix and the mismatch vector as float sums in window order.  SIMD builds of OpenCV sum in another order and may differ in
+ * the last bits of those sums.  status starts at 1 and err at 0; err of a failed point that OpenCV leaves undefined is 0. */
+enum { PS_KLT_USE_INITIAL_FLOW = 4, PS_KLT_GET_MIN_EIGENVALS = 8 }; /* cv::OPTFLOW_USE_INITIAL_FLOW / OPTFLOW_LK_GET_MIN_EIGENVALS */
+typedef struct PsKltParams {
+    double eps;              /* TermCriteria epsilon: clamped to 0 .. 10, then squared (OpenCVParams.eps, :222) */
+    double minEigThreshold;  /* OpenCVParams.trackingMinEigThreshold (:238) */
+    int32_t winSize;         /* square window, 3 .. 31 (OpenCVParams.winSize, :234-235) */
+    int32_t maxLevels;       /* 0 .. 7 (OpenCVParams.maxLevels, :236) */
+    int32_t maxCount;        /* TermCriteria maxCount: clamped to 0 .. 100 (OpenCVParams.maxIter, :221) */
+    int32_t flags;           /* PS_KLT_USE_INITIAL_FLOW | PS_KLT_GET_MIN_EIGENVALS (:225-229) */
+} PsKltParams;
+typedef struct PsImageSet {  /* numFrames interleaved 8-bit images of one shape; pixels: DEVICE */
+    const uint8_t *pixels;
+    size_t rowStride;        /* bytes between rows, 0 = dense (cols x channels) */
+    size_t frameStride;      /* bytes between frames, 0 = dense (rows x rowStride) */
+    int32_t numFrames, rows, cols, channels; /* channels 1 or 3 (the reference passes rgbImage) */
+} PsImageSet;
+typedef struct PsKltPyramids PsKltPyramids; /* a set of `slots` image pyramids with their derivatives, device resident */
+size_t ps_abi_sizeof_klt_params(void);
+size_t ps_abi_sizeof_image_set(void);
+
+/* cv::buildOpticalFlowPyramid's storage for `slots` images of rows x cols x channels (what calcOpticalFlowPyrLK builds for its two
+ * images, :232): level 0 and up to maxLevels reduced levels -- building stops before a level whose width or height would be
+ * <= winSize -- each stored with its winSize-wide border (REFLECT_101 for the image, 0 for the derivative).
+ * winSize 3 .. 31, maxLevels 0 .. 7, channels 1 or 3, slots 1 .. 65535, rows and cols above winSize, else PS_ERR_BAD_ARG; rows or
+ * cols above 8192: PS_ERR_UNSUPPORTED.  Synchronous (allocates).  destroy waits for the device; NULL is harmless. */
+int ps_klt_pyramids_create(PsContext *ctx, int rows, int cols, int channels, int winSize, int maxLevels, int slots, PsKltPyramids **out);
+void ps_klt_pyramids_destroy(PsKltPyramids *pyr);
+int ps_klt_pyramids_num_levels(const PsKltPyramids *pyr); /* levels stored, level 0 included; -1 for NULL */
+/* Fills the levels and derivatives of slots firstSlot .. firstSlot + images->numFrames - 1 from device-resident images of the
+ * set's shape: one launch per level and pass over all frames.  A shape other than the set's, a stride below its row / frame or
+ * slots outside the set: PS_ERR_BAD_ARG.  Asynchronous on the context's stream; uses no scratch of the context. */
+int ps_klt_pyramids_build_device(PsContext *ctx, PsKltPyramids *pyr, const PsImageSet *images, int firstSlot);
+/* cv::calcOpticalFlowPyrLK (:232-238) for P pairs of slots: pairs P x 2 int32 (previous slot, next slot; a pair may name one slot
+ * twice), prevPts / nextPts P x capacity x 2 floats, counts P int32, status P x capacity bytes, err P x capacity floats -- all
+ * DEVICE.  nextPts is read only under PS_KLT_USE_INITIAL_FLOW.  params->winSize must be the set's; the level count is the
+ * set's.  Nothing beyond a pair's count is written; a pair whose count lies outside 0 .. capacity is left alone altogether (the
+ * count -1 of ps_dbscan_thin_device: ps_klt_select_device reports it); a pair that names a slot outside the set has its points
+ * failed (status 0, err 0, nextPts untouched).  One wavefront per point.  Asynchronous; uses no scratch of the context. */
+int ps_klt_track_device(PsContext *ctx, const PsKltPyramids *pyr, const PsKltParams *params, const int32_t *pairs, const float *prevPts,
+                        const int32_t *counts, int P, int capacity, float *nextPts, uint8_t *status, float *err);
+/* The selection (:247-290) for P pairs: a point survives iff status != 0, not (double)err > trackingErrorThreshold, and no i < j
+ * sweep marked it -- for every pair of points, failed ones included, with sqrt((double)dx*dx + (double)dy*dy) <
+ * minimalReprojDistance (float differences; decided as sum < ps_sqrt_bound_f64(distance)) i is marked if err[i] > err[j], else j;
+ * a comparison that involves a NaN is false.  Survivor j (index order) of pair p: matches[p][j] = (i, j, 0, 0.f), keptPts[p][j]
+ * its point, keptIdx[p][j] = i (what the caller compacts keyPoints / detDists with); numMatches[p] their number, -1 for a count
+ * outside 0 .. capacity.  All arrays DEVICE, P x capacity; the inputs are not changed.  capacity <= PS_MAX_KPTS.  Asynchronous. */
+int ps_klt_select_device(PsContext *ctx, const float *nextPts, const uint8_t *status, const float *err, const int32_t *counts, int P,
+                         int capacity, double trackingErrorThreshold, double minimalReprojDistance, PsDMatch *matches,
+                         int32_t *numMatches, float *keptPts, int32_t *keptIdx);
+/* cv::calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, status, err, Size(winSize, winSize), maxLevels, criteria, flags,
+ * minEigThreshold) (:232-238) for one pair: HOST pointers, uploads included, synchronous.  Images rows x cols x channels bytes,
+ * rowStride bytes apart (0 = dense); nextPts is read under PS_KLT_USE_INITIAL_FLOW and written for all n points. */
+int ps_calc_optical_flow_pyr_lk(PsContext *ctx, const uint8_t *prevImg, const uint8_t *nextImg, int rows, int cols, int channels,
+                                size_t rowStride, const float *prevPts, float *nextPts, int n, uint8_t *status, float *err,
+                                const PsKltParams *params);
+/* MatcherOpenCV::performTracking (:209-300) for one pair, track + select: HOST pointers, synchronous.  nextPts (all n tracked
+ * positions), status and err (either may be NULL) as above; matches / keptPts / keptIdx have room for n entries, *numMatches
+ * receives the survivors' number.  n <= PS_MAX_KPTS. */
+int ps_perform_tracking(PsContext *ctx, const uint8_t *prevImg, const uint8_t *nextImg, int rows, int cols, int channels, size_t rowStride,
+                        const float *prevPts, float *nextPts, int n, const PsKltParams *params, double trackingErrorThreshold,
+                        double minimalReprojDistance, uint8_t *status, float *err, PsDMatch *matches, int *numMatches, float *keptPts,
+                        int32_t *keptIdx);
+/* Diagnostic (no reference counterpart): one stored level of one slot read back to the HOST.  dims4 = {rows, cols, stored rows,
+ * stored cols} (stored = with the border); img stored rows x stored cols x channels bytes; der the same elements as int16 pairs
+ * (Ix, Iy).  Any of the three may be NULL.  Waits for the context's stream. */
+int ps_debug_klt_level(PsContext *ctx, const PsKltPyramids *pyr, int slot, int level, int32_t *dims4, uint8_t *img, int16_t *der);
+
 /* ---- Loop-closure candidates verified in one batch from the resident store: what the loop-closure thread does per candidate
  * (poseA, poseB) of FABMAP's priority queue -- FeaturesMap::loopClosure (src/Map/featuresMap.cpp:733-873) around
  * Matcher::matchFeatureLoopClosure (src/Matcher/matcher.cpp:802-861) -- for L candidates as two calls, no host step.

@@ -164,6 +164,26 @@ class PsLoopBatchF32(C.Structure):
                 ("matchingRatioThresholdLC", C.c_double)]
 
 
+# Pyramidal Lucas-Kanade tracking (include/putslam_hip.h)
+PS_KLT_USE_INITIAL_FLOW = 4
+PS_KLT_GET_MIN_EIGENVALS = 8
+
+
+class PsKltParams(C.Structure):
+    _fields_ = [("eps", C.c_double), ("minEigThreshold", C.c_double), ("winSize", C.c_int32), ("maxLevels", C.c_int32),
+                ("maxCount", C.c_int32), ("flags", C.c_int32)]
+
+
+class PsImageSet(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("rowStride", C.c_size_t), ("frameStride", C.c_size_t), ("numFrames", C.c_int32),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("channels", C.c_int32)]
+
+
+def klt_params(win_size=7, max_levels=3, max_count=30, eps=0.01, flags=0, min_eig_threshold=1e-4):
+    """PsKltParams; the defaults are the shipped OpenCVParams (winSize 7, maxLevels 3, maxIter 30, eps 0.01)."""
+    return PsKltParams(float(eps), float(min_eig_threshold), int(win_size), int(max_levels), int(max_count), int(flags))
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

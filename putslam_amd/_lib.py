@@ -8,7 +8,7 @@ import os
 
 from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch,
                    PsMapBatchF32, PsMapStore, PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPairResults, PsPoseSetOut,
-                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats)
+                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -48,6 +48,9 @@ EXPORTED = [
     "ps_debug_l2_stats",
     "ps_map_views_l2_device", "ps_pose_sets_l2_device", "ps_loop_pairs_l2_device",
     "ps_abi_sizeof_map_store_f32", "ps_abi_sizeof_map_view_out_f32", "ps_abi_sizeof_pose_set_out_f32", "ps_abi_sizeof_loop_batch_f32",
+    "ps_klt_pyramids_create", "ps_klt_pyramids_destroy", "ps_klt_pyramids_num_levels", "ps_klt_pyramids_build_device",
+    "ps_klt_track_device", "ps_klt_select_device", "ps_calc_optical_flow_pyr_lk", "ps_perform_tracking", "ps_debug_klt_level",
+    "ps_abi_sizeof_klt_params", "ps_abi_sizeof_image_set",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -60,6 +63,8 @@ ABI_STRUCTS_F32 = dict(frameset_f32=PsFrameSetF32)
 # ... and of the resident store with float rows (ps_map_views_l2_device / ps_pose_sets_l2_device / ps_loop_pairs_l2_device)
 ABI_STRUCTS_STORE_F32 = dict(map_store_f32=PsMapStoreF32, map_view_out_f32=PsMapViewOutF32, pose_set_out_f32=PsPoseSetOutF32,
                              loop_batch_f32=PsLoopBatchF32)
+# ... and of the Lucas-Kanade tracker (ps_klt_* / ps_perform_tracking)
+ABI_STRUCTS_KLT = dict(klt_params=PsKltParams, image_set=PsImageSet)
 
 _lib = None
 _by_path = {}
@@ -249,7 +254,18 @@ def load_path(path):
     L.ps_last_kernel_times_ms.argtypes = [vp, vp]
     L.ps_kernel_time_totals.argtypes = [vp, vp, vp]
     L.ps_context_enable_timing.argtypes = [vp, i32]
-    for n in list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32):
+    L.ps_klt_pyramids_create.argtypes = [vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+    L.ps_klt_pyramids_destroy.argtypes = [vp]
+    L.ps_klt_pyramids_destroy.restype = None
+    L.ps_klt_pyramids_num_levels.argtypes = [vp]
+    L.ps_klt_pyramids_build_device.argtypes = [vp, vp, C.POINTER(PsImageSet), i32]
+    L.ps_klt_track_device.argtypes = [vp, vp, C.POINTER(PsKltParams), vp, vp, vp, i32, i32, vp, vp, vp]
+    L.ps_klt_select_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp]
+    L.ps_calc_optical_flow_pyr_lk.argtypes = [vp, vp, vp, i32, i32, i32, sz, vp, vp, i32, vp, vp, C.POINTER(PsKltParams)]
+    L.ps_perform_tracking.argtypes = [vp, vp, vp, i32, i32, i32, sz, vp, vp, i32, C.POINTER(PsKltParams), C.c_double, C.c_double,
+                                      vp, vp, vp, C.POINTER(i32), vp, vp]
+    L.ps_debug_klt_level.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    for n in list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -265,3 +281,7 @@ def struct_sizes_f32():
 
 def struct_sizes_store_f32():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_STORE_F32.items()}
+
+
+def struct_sizes_klt():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_KLT.items()}

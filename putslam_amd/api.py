@@ -11,7 +11,8 @@ import numpy as np
 from . import _lib
 from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, PS_SET_INVALID, PsExclusionRule, PsFrameSet,  # noqa: F401
                    PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch, PsMapBatchF32, PsPairResults, PsMapStore,
-                   PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config)
+                   PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config,
+                   PsImageSet, PsKltParams, klt_params)
 
 
 class PsError(RuntimeError):
@@ -443,6 +444,98 @@ class Context:
         self._chk(self._L.ps_exclude_device(self._h, C.byref(rule), _v(cand3_ptr), _v(cand2_ptr), _v(cand_counts_ptr),
                                             int(cand_capacity), _v(exist3_ptr), _v(exist2_ptr), _v(exist_counts_ptr),
                                             int(exist_capacity), int(frames), _v(kept_ptr), _v(nkept_ptr)))
+
+    # ---- pyramidal Lucas-Kanade tracking (ps_klt.h) ----
+    @staticmethod
+    def _klt_images(prev_img, next_img):
+        prev_img, next_img = np.asarray(prev_img, np.uint8), np.asarray(next_img, np.uint8)
+        assert prev_img.shape == next_img.shape and prev_img.ndim in (2, 3)
+        cn = 1 if prev_img.ndim == 2 else prev_img.shape[2]
+
+        def rows_of(a):   # rows may lie any stride apart (a region of a larger image); a row itself is dense
+            dense = a.shape[1] * cn
+            ok = a.strides[0] >= dense and (a.ndim == 2 and a.strides[1] == 1 or a.ndim == 3 and a.strides[1:] == (cn, 1))
+            return a if ok else np.ascontiguousarray(a)
+        prev_img, next_img = rows_of(prev_img), rows_of(next_img)
+        if next_img.strides[0] != prev_img.strides[0]:
+            prev_img, next_img = np.ascontiguousarray(prev_img), np.ascontiguousarray(next_img)
+        return prev_img, next_img, cn
+
+    def calc_optical_flow_pyr_lk(self, prev_img, next_img, prev_pts, params: PsKltParams = None, next_pts=None):
+        """cv::calcOpticalFlowPyrLK (ps_calc_optical_flow_pyr_lk) on numpy arrays: images (rows, cols) or (rows, cols, 3) uint8,
+        prev_pts (n, 2) float32, next_pts the initial flow under PS_KLT_USE_INITIAL_FLOW.  params: _abi.klt_params(...), default
+        the shipped OpenCVParams.  Returns (nextPts (n, 2) float32, status (n,) uint8, err (n,) float32)."""
+        params = params or klt_params()
+        prev_img, next_img, cn = self._klt_images(prev_img, next_img)
+        prev_pts = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
+        n = prev_pts.shape[0]
+        nxt = np.zeros((max(n, 1), 2), np.float32)
+        if next_pts is not None:
+            nxt[:n] = np.asarray(next_pts, np.float32).reshape(n, 2)
+        status, err = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32)
+        self._chk(self._L.ps_calc_optical_flow_pyr_lk(self._h, _p(prev_img), _p(next_img), prev_img.shape[0], prev_img.shape[1], cn,
+                                                      prev_img.strides[0], _p(prev_pts), _p(nxt), n, _p(status), _p(err),
+                                                      C.byref(params)))
+        return nxt[:n], status[:n], err[:n]
+
+    def perform_tracking(self, prev_img, next_img, prev_pts, tracking_error_threshold, min_reproj_distance,
+                         params: PsKltParams = None, next_pts=None):
+        """MatcherOpenCV::performTracking (ps_perform_tracking) on numpy arrays: track, gate by error, drop the worse of two
+        features that end closer than min_reproj_distance, compact.  Returns a dict: matches (k,) DMATCH_DTYPE = (i, j, 0, 0),
+        kept_pts (k, 2), kept_idx (k,) -- what the caller compacts keyPoints / detDists with --, and next_pts / status / err of
+        all n points."""
+        params = params or klt_params()
+        prev_img, next_img, cn = self._klt_images(prev_img, next_img)
+        prev_pts = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
+        n = prev_pts.shape[0]
+        m = max(n, 1)
+        nxt = np.zeros((m, 2), np.float32)
+        if next_pts is not None:
+            nxt[:n] = np.asarray(next_pts, np.float32).reshape(n, 2)
+        status, err = np.zeros(m, np.uint8), np.zeros(m, np.float32)
+        matches, kept_pts, kept_idx = np.zeros(m, DMATCH_DTYPE), np.zeros((m, 2), np.float32), np.zeros(m, np.int32)
+        nk = C.c_int(0)
+        self._chk(self._L.ps_perform_tracking(self._h, _p(prev_img), _p(next_img), prev_img.shape[0], prev_img.shape[1], cn,
+                                              prev_img.strides[0], _p(prev_pts), _p(nxt), n, C.byref(params),
+                                              float(tracking_error_threshold), float(min_reproj_distance), _p(status), _p(err),
+                                              _p(matches), C.byref(nk), _p(kept_pts), _p(kept_idx)))
+        k = nk.value
+        return dict(matches=matches[:k].copy(), kept_pts=kept_pts[:k].copy(), kept_idx=kept_idx[:k].copy(), next_pts=nxt[:n],
+                    status=status[:n], err=err[:n])
+
+    def klt_pyramids_create(self, rows, cols, channels, win_size, max_levels, slots):
+        """ps_klt_pyramids_create: the handle of a device-resident pyramid set (device_batch.KltPyramids owns one)."""
+        h = C.c_void_p()
+        self._chk(self._L.ps_klt_pyramids_create(self._h, int(rows), int(cols), int(channels), int(win_size), int(max_levels),
+                                                 int(slots), C.byref(h)))
+        return h
+
+    def klt_pyramids_build_device(self, pyr, images: PsImageSet, first_slot=0):
+        self._chk(self._L.ps_klt_pyramids_build_device(self._h, pyr, C.byref(images), int(first_slot)))
+
+    def klt_track_device(self, pyr, params: PsKltParams, pairs_ptr, prev_pts_ptr, counts_ptr, P, capacity, next_pts_ptr, status_ptr,
+                         err_ptr):
+        """ps_klt_track_device on device pointers (asynchronous on the context's stream): device_batch.track_klt_pairs."""
+        self._chk(self._L.ps_klt_track_device(self._h, pyr, C.byref(params), _v(pairs_ptr), _v(prev_pts_ptr), _v(counts_ptr), int(P),
+                                              int(capacity), _v(next_pts_ptr), _v(status_ptr), _v(err_ptr)))
+
+    def klt_select_device(self, next_pts_ptr, status_ptr, err_ptr, counts_ptr, P, capacity, tracking_error_threshold,
+                          min_reproj_distance, matches_ptr, num_matches_ptr, kept_pts_ptr, kept_idx_ptr):
+        """ps_klt_select_device on device pointers (asynchronous on the context's stream): device_batch.select_tracked."""
+        self._chk(self._L.ps_klt_select_device(self._h, _v(next_pts_ptr), _v(status_ptr), _v(err_ptr), _v(counts_ptr), int(P),
+                                               int(capacity), float(tracking_error_threshold), float(min_reproj_distance),
+                                               _v(matches_ptr), _v(num_matches_ptr), _v(kept_pts_ptr), _v(kept_idx_ptr)))
+
+    def debug_klt_level(self, pyr, slot, level, channels):
+        """ps_debug_klt_level: (image (rows + 2W, cols + 2W, cn) uint8, derivative (.., cn, 2) int16, (rows, cols)) of one stored
+        level, border included."""
+        dims = np.zeros(4, np.int32)
+        self._chk(self._L.ps_debug_klt_level(self._h, pyr, int(slot), int(level), _p(dims), None, None))
+        cn = int(channels)
+        img = np.zeros((dims[2], dims[3], cn), np.uint8)
+        der = np.zeros((dims[2], dims[3], cn, 2), np.int16)
+        self._chk(self._L.ps_debug_klt_level(self._h, pyr, int(slot), int(level), _p(dims), _p(img), _p(der)))
+        return img, der, (int(dims[0]), int(dims[1]))
 
     def points3Dto2D(self, xyz, K):
         xyz = np.ascontiguousarray(xyz, np.float32)

@@ -28,6 +28,7 @@ typedef Eigen::Transform<double, 3, Eigen::Affine> Mat34; // reference include/p
 #define CV_16U 2
 #define CV_32F 5
 #define CV_8UC1 CV_8U
+#define CV_8UC3 16 // CV_MAKETYPE(CV_8U, 3): the rgbImage of performTracking
 #define CV_32FC1 CV_32F
 #endif
 
@@ -75,7 +76,9 @@ class Mat {
     }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
     int type() const { return type_; }
-    size_t elemSize() const { return type_ == CV_8U ? 1 : (type_ == CV_16U ? 2 : 4); }
+    int depth() const { return type_ & 7; }
+    int channels() const { return (type_ >> 3) + 1; }
+    size_t elemSize() const { return (size_t)channels() * (depth() == CV_8U ? 1 : (depth() == CV_16U ? 2 : 4)); }
     template <typename T> T &at(int r, int c) { return *reinterpret_cast<T *>(data + (size_t)r * step + (size_t)c * sizeof(T)); }
     template <typename T> const T &at(int r, int c) const
     {

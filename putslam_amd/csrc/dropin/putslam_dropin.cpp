@@ -1151,6 +1151,77 @@ std::vector<cv::DMatch> FrameMatcherHIP::performMatching(cv::Mat prevDescriptors
     return hammingCrossCheckMatch(prevDescriptors, descriptors);
 }
 
+std::vector<cv::DMatch> FrameMatcherHIP::performTracking(cv::Mat prevImg, cv::Mat img, std::vector<cv::Point2f> &prevFeatures,
+                                                         std::vector<cv::Point2f> &features, std::vector<cv::KeyPoint> &prevKeyPoints,
+                                                         std::vector<cv::KeyPoint> &keyPoints, std::vector<double> &prevDetDists,
+                                                         std::vector<double> &detDists)
+{
+    return trackFeaturesLK(matcherParameters, prevImg, img, prevFeatures, features, prevKeyPoints, keyPoints, prevDetDists, detDists);
+}
+
+// MatcherOpenCV::performTracking, matcherOpenCV.cpp:209-300
+std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat prevImg, cv::Mat img,
+                                        std::vector<cv::Point2f> &prevFeatures, std::vector<cv::Point2f> &features,
+                                        std::vector<cv::KeyPoint> &prevKeyPoints, std::vector<cv::KeyPoint> &keyPoints,
+                                        std::vector<double> &prevDetDists, std::vector<double> &detDists)
+{
+    std::vector<cv::DMatch> matches;
+    const auto &cvp = matcherParameters.OpenCVParams;
+    const size_t n = prevFeatures.size();
+    const bool initialFlow = cvp.useInitialFlow > 0 && features.size() == n; // (calcOpticalFlowPyrLK asserts the sizes agree)
+    std::vector<cv::Point2f> tracked = initialFlow ? features : std::vector<cv::Point2f>(n);
+    features.clear();
+    keyPoints.clear();
+    detDists.clear();
+    const auto is8u = [](const cv::Mat &m) { return m.depth() == CV_8U && (m.channels() == 1 || m.channels() == 3); };
+    if (prevImg.empty() || img.empty() || !is8u(prevImg) || prevImg.type() != img.type() || prevImg.rows != img.rows ||
+        prevImg.cols != img.cols || prevImg.step != img.step || prevKeyPoints.size() != n || prevDetDists.size() != n ||
+        (cvp.useInitialFlow > 0 && !initialFlow)) {
+        std::cerr << "putslam_hip: performTracking takes two CV_8UC1 / CV_8UC3 images of one size and step, and one key point and "
+                     "detection distance per previous feature" << std::endl;
+        return matches;
+    }
+    if (n == 0) return matches;
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return matches;
+    PsKltParams prm;
+    prm.eps = cvp.eps;                                   // :220-222, TermCriteria(ITER | EPS, maxIter, eps)
+    prm.minEigThreshold = cvp.trackingMinEigThreshold;   // :238
+    prm.winSize = cvp.winSize;                           // :234-235
+    prm.maxLevels = cvp.maxLevels;                       // :236
+    prm.maxCount = cvp.maxIter;
+    prm.flags = (cvp.useInitialFlow > 0 ? PS_KLT_USE_INITIAL_FLOW : 0) | (cvp.trackingErrorType > 0 ? PS_KLT_GET_MIN_EIGENVALS : 0); // :225-229
+    matches.resize(n);
+    std::vector<cv::Point2f> keptPts(n);
+    std::vector<int32_t> keptIdx(n);
+    int k = 0;
+    status = ps_perform_tracking(ctx, prevImg.data, img.data, prevImg.rows, prevImg.cols, prevImg.channels(), prevImg.step,
+                                 reinterpret_cast<const float *>(prevFeatures.data()), reinterpret_cast<float *>(tracked.data()), (int)n,
+                                 &prm, cvp.trackingErrorThreshold, cvp.minimalReprojDistanceNewTrackingFeatures, nullptr, nullptr,
+                                 reinterpret_cast<PsDMatch *>(matches.data()), &k, reinterpret_cast<float *>(keptPts.data()), keptIdx.data());
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        matches.clear();
+        return matches;
+    }
+    matches.resize((size_t)k);
+    // :240-245 then :267-290: the survivors keep the previous frame's key point (its pt moved) and detection distance
+    features.assign(keptPts.begin(), keptPts.begin() + k);
+    keyPoints.reserve((size_t)k);
+    detDists.reserve((size_t)k);
+    for (int j = 0; j < k; ++j) {
+        cv::KeyPoint kp = prevKeyPoints[(size_t)keptIdx[(size_t)j]];
+        kp.pt = keptPts[(size_t)j];
+        keyPoints.push_back(kp);
+        detDists.push_back(prevDetDists[(size_t)keptIdx[(size_t)j]]);
+    }
+    if (matcherParameters.verbose > 0)
+        std::cout << "MatcherOpenCV::performTracking -- features tracked " << matches.size() << " ("
+                  << (float)matches.size() * 100.0 / (float)prevFeatures.size() << "%)" << std::endl;
+    return matches;
+}
+
 // MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) with the matcher of matcherOpenCV.cpp:100-102, cv::BFMatcher(cv::NORM_L2,
 // true), on CV_32F descriptor Mats of 1 .. PS_MAX_L2_DIM columns (ps_match_l2_f32).
 std::vector<cv::DMatch> l2CrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors)

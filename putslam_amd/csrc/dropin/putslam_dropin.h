@@ -8,8 +8,8 @@
 //   putslam::KabschEst + factory   include/putslam/TransformEst/kabschEst.h, src/TransformEst/kabschEst.cpp
 //
 // The Matcher plugin itself (putslam::Matcher / ::MatcherOpenCV, include/putslam/Matcher/matcher.h:24,100-151,405-422)
-// keeps ITS OWN class in a PUTSLAM build: detection, description and tracking are image-domain OpenCV stages outside the
-// path.  This library therefore defines no symbol of that name.  What it provides for the plugin is
+// keeps ITS OWN class in a PUTSLAM build: detection and description are image-domain OpenCV stages outside the
+// path (performTracking has a body here: trackFeaturesLK below).  This library therefore defines no symbol of that name.  What it provides for the plugin is
 //   putslam_hip::FrameMatcher / FrameMatcherHIP   the hot-path state machine behind Matcher::match / runVO /
 //                                  matchXYZ / matchFeatureLoopClosure (matcher.cpp:452-516,606-861) on descriptors and
 //                                  3-D points, which the reference's methods call after their detect / describe part;
@@ -178,7 +178,7 @@ TransformEst *createKabschEstimator(void);
 namespace putslam_hip {
 
 // ---------------------------------------------------------------------------------------------
-// Hot-path part of the Matcher plugin.  Detection / description / tracking are image-domain OpenCV
+// Hot-path part of the Matcher plugin.  Detection / description are image-domain OpenCV
 // stages outside the path: their pure virtuals are not part of this class; the
 // frame enters at the point where Matcher::match has descriptors and 3-D points (matcher.cpp:467-480).
 // Deliberately NOT named putslam::Matcher: the reference's class of that name stays in a PUTSLAM build and
@@ -194,6 +194,11 @@ class FrameMatcher {
             double matchingXYZacceptRatioOfBestMatch = 0.55;  // :72
             double minimalReprojDistanceNewTrackingFeatures = 3;     // :68
             double minimalEuclidDistanceNewTrackingFeatures = 0.01;  // :69
+            // the tracker's block (matcher.h:45-49,59-60; putslammatcherOpenCVParameters.xml:64,73-75)
+            int useInitialFlow = 0, winSize = 7, maxLevels = 3, maxIter = 30;
+            float eps = 0.01f;
+            double trackingErrorThreshold = 25.0, trackingMinEigThreshold = 0.0;
+            int trackingErrorType = 0;
         } OpenCVParams;
         MatcherParameters();
     };
@@ -350,6 +355,16 @@ std::vector<cv::DMatch> hammingCrossCheckMatch(cv::Mat prevDescriptors, cv::Mat 
 // ... and with the float descriptors' matcher, cv::BFMatcher(cv::NORM_L2, true) (matcherOpenCV.cpp:100-102): CV_32F Mats.
 std::vector<cv::DMatch> l2CrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors);
 
+// MatcherOpenCV::performTracking (matcherOpenCV.cpp:209-300) as a free function over the calling thread's context
+// (ps_perform_tracking): cv::calcOpticalFlowPyrLK on the image pair (CV_8UC1 or CV_8UC3 Mats of one size), keyPoints / detDists
+// copied from the previous frame's with the tracked positions, the error gate, the too-close-by-error removal, and the erase of
+// every feature that did not survive from features, keyPoints and detDists; returns DMatch(i, j, 0) per survivor.  On an error
+// the three vectors come back empty with no matches (the text goes to stderr).
+std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat prevImg, cv::Mat img,
+                                        std::vector<cv::Point2f> &prevFeatures, std::vector<cv::Point2f> &features,
+                                        std::vector<cv::KeyPoint> &prevKeyPoints, std::vector<cv::KeyPoint> &keyPoints,
+                                        std::vector<double> &prevDetDists, std::vector<double> &detDists);
+
 // Library-owned singletons with the reference factories' ownership rules (raw pointer returned, a second call
 // replaces the instance: matcherOpenCV.cpp:20-47): one for the VO thread, one for the loop-closure thread.
 FrameMatcher *createFrameMatcher(void);
@@ -377,6 +392,11 @@ class FrameMatcherHIP : public FrameMatcher {
     ~FrameMatcherHIP(void);
     virtual const std::string &getName() const;
     virtual std::vector<cv::DMatch> performMatching(cv::Mat prevDescriptors, cv::Mat descriptors);
+    // MatcherOpenCV::performTracking, matcherOpenCV.cpp:209-300 (the reference's signature; trackFeaturesLK above)
+    virtual std::vector<cv::DMatch> performTracking(cv::Mat prevImg, cv::Mat img, std::vector<cv::Point2f> &prevFeatures,
+                                                    std::vector<cv::Point2f> &features, std::vector<cv::KeyPoint> &prevKeyPoints,
+                                                    std::vector<cv::KeyPoint> &keyPoints, std::vector<double> &prevDetDists,
+                                                    std::vector<double> &detDists);
 };
 
 } // namespace putslam_hip

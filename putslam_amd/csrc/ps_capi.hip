@@ -1259,6 +1259,7 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
 #include "ps_match_l2.h"     // ps_match_l2_f32 / ps_match_l2_device / ps_vo_pairs_l2_device (the plan and the stages above)
 #include "ps_map_match_l2.h" // ps_match_xyz_l2_f32 / ps_match_xyz_l2_device / ps_map_pairs_l2_device (the two headers above)
 #include "ps_map_store_f32.h" // ps_map_views_l2_device / ps_pose_sets_l2_device / ps_loop_pairs_l2_device (ps_map_view.h, ps_loop_closure.h, ps_match_l2.h)
+#include "ps_klt.h"          // ps_klt_pyramids_* / ps_klt_track_device / ps_klt_select_device / ps_perform_tracking (ps_exclusion.h's bound)
 
 // Launch attributes of the kernels that need them (ps_internal.h; called once per context).
 extern "C" void psi_kernel_attributes(void)
@@ -1270,4 +1271,5 @@ extern "C" void psi_kernel_attributes(void)
     dbscan_kernel_attributes();
     exclusion_kernel_attributes();
     l2_kernel_attributes();
+    klt_kernel_attributes();
 }

@@ -34,6 +34,9 @@ PS_HD float ps_sqrt(float x) { return sqrtf(x); }
 PS_HD double ps_sqrt(double x) { return sqrt(x); }
 PS_HD float ps_abs(float x) { return fabsf(x); }
 PS_HD double ps_abs(double x) { return fabs(x); }
+// a / b correctly rounded (the HIP default for float) and rint, ties to even (cvRound on an SSE2 build): ps_klt.h
+PS_HD float ps_div(float a, float b) { return a / b; }
+PS_HD float ps_rint(float x) { return rintf(x); }
 
 
 // ---- exact float sqrt / reciprocal / quotients with the range fix-ups removed (device, float only) ----------------

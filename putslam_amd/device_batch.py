@@ -9,7 +9,7 @@ import torch
 from . import api
 from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
-                   make_config)
+                   make_config, PsImageSet, klt_params)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -320,6 +320,86 @@ def exclude_device(ctx, rule, cand3, cand2, cand_counts, exist3=None, exist2=Non
             exist_counts.data_ptr() if ecap else 0, ecap, F, kept.data_ptr(), nkept.data_ptr())
     _on_torch_stream(ctx, lead.device, lambda: ctx.exclude_device(*args))   # ordered like run_pairs
     return kept, nkept
+
+
+class KltPyramids:
+    """A device-resident set of `slots` image pyramids with their derivatives (ps_klt_pyramids_create): the images of a sequence,
+    built once, tracked pair by pair.  rows x cols x channels 8-bit images; win_size / max_levels as in _abi.klt_params."""
+
+    def __init__(self, ctx, rows, cols, channels, slots, win_size=7, max_levels=3):
+        self.ctx, self.rows, self.cols, self.channels, self.slots = ctx, int(rows), int(cols), int(channels), int(slots)
+        self.win_size, self.max_levels = int(win_size), int(max_levels)
+        self.handle = ctx.klt_pyramids_create(rows, cols, channels, win_size, max_levels, slots)
+        self.num_levels = int(ctx._L.ps_klt_pyramids_num_levels(self.handle))
+
+    def close(self):
+        if self.handle is not None:
+            self.ctx._L.ps_klt_pyramids_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def build(self, images, first_slot=0, use_torch_stream=True):
+        """Fills slots first_slot .. from `images`: a uint8 device tensor (F, rows, cols[, channels]) whose rows and frames may
+        lie any stride apart (a view of a padded block); a row itself is dense.  Asynchronous, ordered like run_pairs."""
+        assert images.dtype == torch.uint8 and images.dim() in (3, 4) and tuple(images.shape[1:3]) == (self.rows, self.cols)
+        cn = 1 if images.dim() == 3 else images.shape[3]
+        assert cn == self.channels and (images.dim() == 3 and images.stride(2) == 1 or images.dim() == 4 and images.stride()[2:] == (cn, 1))
+        s = PsImageSet(images.data_ptr(), images.stride(1), images.stride(0) if images.shape[0] > 1 else 0, images.shape[0],
+                       self.rows, self.cols, cn)
+        _on_torch_stream(self.ctx, images.device, lambda: self.ctx.klt_pyramids_build_device(self.handle, s, first_slot),
+                         use_torch_stream)
+
+    def level(self, slot, level):
+        """(image, derivative, (rows, cols)) of one stored level, border included, on the host (api.Context.debug_klt_level)."""
+        return self.ctx.debug_klt_level(self.handle, slot, level, self.channels)
+
+
+def track_klt_pairs(ctx, pyr: KltPyramids, pairs, prev_pts, counts, params=None, next_pts=None, status=None, err=None,
+                    use_torch_stream=True):
+    """cv::calcOpticalFlowPyrLK for P pairs of slots of `pyr` (ps_klt_track_device): pairs (P, 2) int32 (previous, next),
+    prev_pts (P, cap, 2) float32, counts (P,) int32 -- torch tensors on the context's device.  next_pts: the initial flow under
+    PS_KLT_USE_INITIAL_FLOW, written in place; status (P, cap) uint8 / err (P, cap) float32: blocks to write into (default: new
+    ones).  Returns (next_pts, status, err), written asynchronously: nothing beyond a pair's count."""
+    params = params or klt_params(pyr.win_size, pyr.max_levels)
+    P, cap = prev_pts.shape[0], prev_pts.shape[1]
+    dev = prev_pts.device
+    assert prev_pts.dtype == torch.float32 and prev_pts.shape == (P, cap, 2) and prev_pts.is_contiguous()
+    assert pairs.dtype == torch.int32 and pairs.shape == (P, 2) and pairs.is_contiguous()
+    assert counts.dtype == torch.int32 and counts.shape == (P,) and counts.is_contiguous()
+    next_pts = _zeros(dev, (P, cap, 2), torch.float32) if next_pts is None else next_pts
+    status = _zeros(dev, (P, cap), torch.uint8) if status is None else status
+    err = _zeros(dev, (P, cap), torch.float32) if err is None else err
+    assert next_pts.dtype == torch.float32 and next_pts.shape == (P, cap, 2) and next_pts.is_contiguous()
+    assert status.dtype == torch.uint8 and status.shape == (P, cap) and status.is_contiguous()
+    assert err.dtype == torch.float32 and err.shape == (P, cap) and err.is_contiguous()
+    args = (pyr.handle, params, pairs.data_ptr(), prev_pts.data_ptr(), counts.data_ptr(), P, cap, next_pts.data_ptr(),
+            status.data_ptr(), err.data_ptr())
+    _on_torch_stream(ctx, dev, lambda: ctx.klt_track_device(*args), use_torch_stream)
+    return next_pts, status, err
+
+
+def select_tracked(ctx, next_pts, status, err, counts, tracking_error_threshold, min_reproj_distance, use_torch_stream=True):
+    """performTracking's selection for P pairs (ps_klt_select_device) on what track_klt_pairs returned.  Returns (matches (P, cap, 4)
+    int32 words of PsDMatch, num_matches (P,) int32, kept_pts (P, cap, 2) float32, kept_idx (P, cap) int32), written
+    asynchronously: pair p keeps its first num_matches[p] rows (-1: a count outside 0 .. cap)."""
+    P, cap = status.shape
+    dev = status.device
+    assert next_pts.dtype == torch.float32 and next_pts.shape == (P, cap, 2) and next_pts.is_contiguous()
+    assert status.dtype == torch.uint8 and status.is_contiguous() and err.dtype == torch.float32 and err.shape == (P, cap) and err.is_contiguous()
+    assert counts.dtype == torch.int32 and counts.shape == (P,) and counts.is_contiguous()
+    matches = torch.empty((P, cap, 4), dtype=torch.int32, device=dev)
+    num = torch.empty((P,), dtype=torch.int32, device=dev)
+    kept_pts = torch.empty((P, cap, 2), dtype=torch.float32, device=dev)
+    kept_idx = torch.empty((P, cap), dtype=torch.int32, device=dev)
+    args = (next_pts.data_ptr(), status.data_ptr(), err.data_ptr(), counts.data_ptr(), P, cap, tracking_error_threshold,
+            min_reproj_distance, matches.data_ptr(), num.data_ptr(), kept_pts.data_ptr(), kept_idx.data_ptr())
+    _on_torch_stream(ctx, dev, lambda: ctx.klt_select_device(*args), use_torch_stream)
+    return matches, num, kept_pts, kept_idx
 
 
 class MapBatchDevice(PairResultsDevice):
