@@ -733,6 +733,76 @@ int ps_perform_tracking(PsContext *ctx, const uint8_t *prevImg, const uint8_t *n
  * (Ix, Iy).  Any of the three may be NULL.  Waits for the context's stream. */
 int ps_debug_klt_level(PsContext *ctx, const PsKltPyramids *pyr, int slot, int level, int32_t *dims4, uint8_t *img, int16_t *der);
 
+/* ---- FAST-9/16 key point detection: MatcherOpenCV::detectFeatures, src/Matcher/matcherOpenCV.cpp:118-180, for detector = "FAST"
+ * (cv::FastFeatureDetector::create(), :64-65) -- the first step of the refill chain of Matcher::trackKLT (matcher.cpp:213-260):
+ * cvtColor(RGB2GRAY) (:122), the grid of ROIs (:127-146), the detector in every ROI (:148), the per-ROI ordering by response and
+ * cut to maximalTrackedFeatures * 3 / (gridCols * gridRows) (:155-165), the joined ordering and cut (:169-177).
+ * The arithmetic is the project's reading of OpenCV 3.x's fast.cpp / fast_score.cpp (FAST_t<16>, cornerScore<16>) and of the 8-bit
+ * cvtColor (restated twice in tests/fast_ref.py); no OpenCV build was at hand to pin it against.  All of
+ * it is integer arithmetic, on which OpenCV's SIMD and scalar builds agree:
+ *   grey      (c0 * 4899 + c1 * 9617 + c2 * 1868 + 8192) >> 14 -- channel 0 takes the red weight whatever the host stored there
+ *             (the reference hands its BGR-loaded image to CV_RGB2GRAY as it is); channels == 1: the image is grey already (an
+ *             extension for hosts that convert themselves, OpenCV would throw);
+ *   ROIs      for k in 0 .. gridCols-1 (outer), i in 0 .. gridRows-1 (inner): origin (k * cols / gridCols, i * rows / gridRows),
+ *             size cols / gridCols x rows / gridRows, integer divisions: a remainder strip is never looked at.  The detector sees
+ *             an ROI as an image of its own: candidates are its rows 3 .. R-4 and columns 3 .. C-4 (R or C < 7: none);
+ *   corner    with d[k] = v - ring[k] over the ring (0,3) (1,3) (2,2) (3,1) (3,0) (3,-1) (2,-2) (1,-3) (0,-3) (-1,-3) (-2,-2) (-3,-1)
+ *             (-3,0) (-3,1) (-2,2) (-1,3): nine cyclically consecutive d all > t or all < -t, t = threshold clamped to 0 .. 255;
+ *   score     max(t, D, B) - 1 as a byte, D = the largest over the 16 arcs of nine of the least d, B the same for -d; 0 for a
+ *             non-corner;
+ *   emission  with suppression: a corner whose score is strictly above its eight neighbours' (two equal neighbours suppress
+ *             each other, a corner of score 0 -- t = 0 only -- never comes out), response = score; without: every corner,
+ *             response 0 (OpenCV computes no score in that mode);
+ *   order     THE ONE PLACE this library decides what the reference leaves open: both orderings by response are std::sort with
+ *             p1.response > p2.response (matcherOpenCV.h:84-87), which is not stable, so among equal responses the reference's
+ *             order -- and who survives a cut that falls inside a tie -- is whatever its libstdc++ does.  Here both are STABLE:
+ *             ties keep raster order (y, then x) inside an ROI and the order of the ROI loop across ROIs.
+ * A key point is (pt = (x, y) in image coordinates, size 7, angle -1, response, octave 0, class_id -1); the calls return pt and
+ * response. */
+typedef struct PsDetectParams {
+    int32_t threshold;               /* clamped to 0 .. 255; FastFeatureDetector::create(): 10 */
+    int32_t nonmaxSuppression;       /* 0 = off; create(): on */
+    int32_t gridRows, gridCols;      /* OpenCVParams.gridRows / gridCols, at least 1 */
+    int32_t maximalTrackedFeatures;  /* OpenCVParams.maximalTrackedFeatures, 0 .. PS_MAX_KPTS */
+    int32_t reserved;                /* must be 0 */
+} PsDetectParams;
+typedef struct PsFastDetector PsFastDetector; /* grey, score and corner maps for up to maxFrames images of one shape, device resident */
+size_t ps_abi_sizeof_detect_params(void);
+
+/* A detector for images of rows x cols x channels bytes, up to maxFrames (1 .. 65535) a call: three byte planes per frame.
+ * rows or cols < 1, channels other than 1 or 3, maxFrames outside its range -> PS_ERR_BAD_ARG; rows or cols above 8192 ->
+ * PS_ERR_UNSUPPORTED.  Synchronous (allocates).  destroy waits for the device; NULL is harmless. */
+int ps_fast_detector_create(PsContext *ctx, int rows, int cols, int channels, int maxFrames, PsFastDetector **out);
+void ps_fast_detector_destroy(PsFastDetector *det);
+/* detectFeatures for every frame of a device-resident set (the PsImageSet the KLT pyramids are built from).  xy numFrames x
+ * capacity x 2 floats, response numFrames x capacity floats, counts numFrames int32 -- all DEVICE; frame f's counts[f] key points
+ * fill its first rows in the final order, nothing beyond them is written.  The layout is the one ps_dbscan_thin_device takes
+ * (octave = NULL) and whose kept indices ps_klt_track_device's callers gather with: no repacking step in between.
+ * Three launches whatever the frame count: the score pass over all frames, one work-group per (frame, ROI) that orders and cuts
+ * the ROI, one per frame that joins them.  Asynchronous on the context's stream, except that a call which needs more room for
+ * its ROI lists than any call before (4 bytes per kept key point of every ROI) allocates first, which waits for the device.
+ * NULL where an array is needed, gridRows / gridCols < 1, maximalTrackedFeatures < 0, reserved != 0, a shape or stride that does
+ * not fit the detector, numFrames < 0 or above maxFrames, capacity < min(maximalTrackedFeatures, candidate pixels of all ROIs)
+ * -> PS_ERR_BAD_ARG (text: ps_last_error); maximalTrackedFeatures or capacity above PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; outputs
+ * untouched.  numFrames == 0 is PS_OK. */
+int ps_detect_features_device(PsContext *ctx, PsFastDetector *det, const PsImageSet *images, const PsDetectParams *params, int capacity,
+                              float *xy, float *response, int32_t *counts);
+/* detectFeatures for one image: HOST pointers, upload included, synchronous.  img rows x cols x channels bytes, rowStride bytes
+ * between rows (0 = dense; a region of a larger image keeps its parent's).  xy cap x 2 floats, response cap floats, *nout the
+ * number found.  Returns PS_ERR_BAD_ARG with *nout = required capacity if cap is too small (nothing else is written); other
+ * errors as above, *nout untouched. */
+int ps_detect_features(PsContext *ctx, const uint8_t *img, int rows, int cols, int channels, size_t rowStride, const PsDetectParams *params,
+                       float *xy, float *response, int cap, int *nout);
+/* Diagnostic (no reference counterpart): the grey image, the score map and the corner map (1 = corner) of one frame of the
+ * detector's LAST call read back to the HOST, rows x cols bytes each; any of the three may be NULL.  Waits for the context's
+ * stream. */
+int ps_debug_fast_maps(PsContext *ctx, const PsFastDetector *det, int frame, uint8_t *gray, uint8_t *score, uint8_t *corner);
+/* Diagnostic (no reference counterpart; profiles/scripts/fast_times.py times each pass alone with it): ps_detect_features_device
+ * with only the passes of the mask queued -- 1 the score pass, 2 the per-ROI selection, 4 the join.  A pass reads what the passes
+ * before it left in the detector: call with 7 (= ps_detect_features_device) and the same arguments first. */
+int ps_debug_fast_passes(PsContext *ctx, PsFastDetector *det, const PsImageSet *images, const PsDetectParams *params, int capacity,
+                         float *xy, float *response, int32_t *counts, int passes);
+
 /* ---- Loop-closure candidates verified in one batch from the resident store: what the loop-closure thread does per candidate
  * (poseA, poseB) of FABMAP's priority queue -- FeaturesMap::loopClosure (src/Map/featuresMap.cpp:733-873) around
  * Matcher::matchFeatureLoopClosure (src/Matcher/matcher.cpp:802-861) -- for L candidates as two calls, no host step.

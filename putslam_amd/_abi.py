@@ -184,6 +184,19 @@ def klt_params(win_size=7, max_levels=3, max_count=30, eps=0.01, flags=0, min_ei
     return PsKltParams(float(eps), float(min_eig_threshold), int(win_size), int(max_levels), int(max_count), int(flags))
 
 
+# FAST-9/16 key point detection (include/putslam_hip.h)
+class PsDetectParams(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("nonmaxSuppression", C.c_int32), ("gridRows", C.c_int32), ("gridCols", C.c_int32),
+                ("maximalTrackedFeatures", C.c_int32), ("reserved", C.c_int32)]
+
+
+def detect_params(threshold=10, nonmax_suppression=True, grid_rows=1, grid_cols=1, maximal_tracked_features=500):
+    """PsDetectParams; the defaults are cv::FastFeatureDetector::create()'s (threshold 10, suppression on) and the shipped
+    OpenCVParams (gridRows = gridCols = 1, maximalTrackedFeatures 500)."""
+    return PsDetectParams(int(threshold), 1 if nonmax_suppression else 0, int(grid_rows), int(grid_cols),
+                          int(maximal_tracked_features), 0)
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

@@ -8,7 +8,7 @@ import os
 
 from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch,
                    PsMapBatchF32, PsMapStore, PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPairResults, PsPoseSetOut,
-                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams)
+                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -51,6 +51,8 @@ EXPORTED = [
     "ps_klt_pyramids_create", "ps_klt_pyramids_destroy", "ps_klt_pyramids_num_levels", "ps_klt_pyramids_build_device",
     "ps_klt_track_device", "ps_klt_select_device", "ps_calc_optical_flow_pyr_lk", "ps_perform_tracking", "ps_debug_klt_level",
     "ps_abi_sizeof_klt_params", "ps_abi_sizeof_image_set",
+    "ps_fast_detector_create", "ps_fast_detector_destroy", "ps_detect_features_device", "ps_detect_features", "ps_debug_fast_maps", "ps_debug_fast_passes",
+    "ps_abi_sizeof_detect_params",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -65,6 +67,8 @@ ABI_STRUCTS_STORE_F32 = dict(map_store_f32=PsMapStoreF32, map_view_out_f32=PsMap
                              loop_batch_f32=PsLoopBatchF32)
 # ... and of the Lucas-Kanade tracker (ps_klt_* / ps_perform_tracking)
 ABI_STRUCTS_KLT = dict(klt_params=PsKltParams, image_set=PsImageSet)
+# ... and of the FAST detector (ps_fast_detector_* / ps_detect_features)
+ABI_STRUCTS_DETECT = dict(detect_params=PsDetectParams)
 
 _lib = None
 _by_path = {}
@@ -265,7 +269,14 @@ def load_path(path):
     L.ps_perform_tracking.argtypes = [vp, vp, vp, i32, i32, i32, sz, vp, vp, i32, C.POINTER(PsKltParams), C.c_double, C.c_double,
                                       vp, vp, vp, C.POINTER(i32), vp, vp]
     L.ps_debug_klt_level.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-    for n in list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT):
+    L.ps_fast_detector_create.argtypes = [vp, i32, i32, i32, i32, C.POINTER(vp)]
+    L.ps_fast_detector_destroy.argtypes = [vp]
+    L.ps_fast_detector_destroy.restype = None
+    L.ps_detect_features_device.argtypes = [vp, vp, C.POINTER(PsImageSet), C.POINTER(PsDetectParams), i32, vp, vp, vp]
+    L.ps_detect_features.argtypes = [vp, vp, i32, i32, i32, sz, C.POINTER(PsDetectParams), vp, vp, i32, C.POINTER(i32)]
+    L.ps_debug_fast_maps.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.ps_debug_fast_passes.argtypes = [vp, vp, C.POINTER(PsImageSet), C.POINTER(PsDetectParams), i32, vp, vp, vp, i32]
+    for n in list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT) + list(ABI_STRUCTS_DETECT):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -285,3 +296,7 @@ def struct_sizes_store_f32():
 
 def struct_sizes_klt():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_KLT.items()}
+
+
+def struct_sizes_detect():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_DETECT.items()}

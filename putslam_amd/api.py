@@ -12,7 +12,7 @@ from . import _lib
 from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, PS_SET_INVALID, PsExclusionRule, PsFrameSet,  # noqa: F401
                    PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch, PsMapBatchF32, PsPairResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config,
-                   PsImageSet, PsKltParams, klt_params)
+                   PsImageSet, PsKltParams, klt_params, PsDetectParams, detect_params)
 
 
 class PsError(RuntimeError):
@@ -536,6 +536,45 @@ class Context:
         der = np.zeros((dims[2], dims[3], cn, 2), np.int16)
         self._chk(self._L.ps_debug_klt_level(self._h, pyr, int(slot), int(level), _p(dims), _p(img), _p(der)))
         return img, der, (int(dims[0]), int(dims[1]))
+
+    # ---- FAST-9/16 key point detection (ps_fast.h) ----
+    def detect_features(self, image, params: PsDetectParams = None):
+        """MatcherOpenCV::detectFeatures for detector = "FAST" (ps_detect_features) on a numpy image (rows, cols) or (rows, cols, 3)
+        uint8, whose rows may lie any stride apart (a region of a larger image).  params: _abi.detect_params(...), default the
+        shipped ones.  Returns (xy (n, 2) float32, response (n,) float32) in the final order: response descending, ties in
+        raster order inside an ROI and in the order of the ROI loop across ROIs."""
+        params = params or detect_params()
+        image = np.asarray(image, np.uint8)
+        assert image.ndim in (2, 3)
+        cn = 1 if image.ndim == 2 else image.shape[2]
+        dense = image.shape[1] * cn
+        if not (image.strides[0] >= dense and (image.ndim == 2 and image.strides[1] == 1 or image.ndim == 3 and image.strides[1:] == (cn, 1))):
+            image = np.ascontiguousarray(image)
+        cap = max(0, min(int(params.maximalTrackedFeatures), PS_MAX_KPTS))
+        xy, response = np.zeros((max(cap, 1), 2), np.float32), np.zeros(max(cap, 1), np.float32)
+        n = C.c_int(0)
+        self._chk(self._L.ps_detect_features(self._h, _p(image), image.shape[0], image.shape[1], cn, image.strides[0], C.byref(params),
+                                             _p(xy), _p(response), cap, C.byref(n)))
+        return xy[:n.value].copy(), response[:n.value].copy()
+
+    def fast_detector_create(self, rows, cols, channels, max_frames):
+        """ps_fast_detector_create: the handle of a device-resident detector (device_batch.FastDetector owns one)."""
+        h = C.c_void_p()
+        self._chk(self._L.ps_fast_detector_create(self._h, int(rows), int(cols), int(channels), int(max_frames), C.byref(h)))
+        return h
+
+    def detect_features_device(self, det, images: PsImageSet, params: PsDetectParams, capacity, xy_ptr, response_ptr, counts_ptr,
+                               passes=7):
+        """ps_detect_features_device on device pointers (asynchronous on the context's stream): device_batch.detect_features_batch.
+        passes other than 7: ps_debug_fast_passes, only the passes of the mask (1 score, 2 select, 4 join), for timing."""
+        self._chk(self._L.ps_debug_fast_passes(self._h, det, C.byref(images), C.byref(params), int(capacity), _v(xy_ptr),
+                                               _v(response_ptr), _v(counts_ptr), int(passes)))
+
+    def debug_fast_maps(self, det, frame, rows, cols):
+        """ps_debug_fast_maps: (grey, score, corner) of one frame of the detector's last call, (rows, cols) uint8 each."""
+        maps = [np.zeros((int(rows), int(cols)), np.uint8) for _ in range(3)]
+        self._chk(self._L.ps_debug_fast_maps(self._h, det, int(frame), _p(maps[0]), _p(maps[1]), _p(maps[2])))
+        return tuple(maps)
 
     def points3Dto2D(self, xyz, K):
         xyz = np.ascontiguousarray(xyz, np.float32)

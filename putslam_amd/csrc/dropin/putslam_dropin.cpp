@@ -1222,6 +1222,56 @@ std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &m
     return matches;
 }
 
+std::vector<cv::KeyPoint> FrameMatcherHIP::detectFeatures(cv::Mat rgbImage) { return detectFeaturesFAST(matcherParameters, rgbImage); }
+
+// MatcherOpenCV::detectFeatures, matcherOpenCV.cpp:118-180, for the detector of :64-65
+std::vector<cv::KeyPoint> detectFeaturesFAST(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat rgbImage)
+{
+    std::vector<cv::KeyPoint> keypoints;
+    const auto &cvp = matcherParameters.OpenCVParams;
+    if (cvp.detector != "FAST") {
+        std::cerr << "putslam_hip: detectFeatures runs detector \"FAST\" only (asked for \"" << cvp.detector
+                  << "\"): no key points; ORB / SURF / SIFT detection stays with OpenCV on the host" << std::endl;
+        return keypoints;
+    }
+    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3)) {
+        std::cerr << "putslam_hip: detectFeatures takes a CV_8UC1 or CV_8UC3 image" << std::endl;
+        return keypoints;
+    }
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return keypoints;
+    PsDetectParams prm;
+    prm.threshold = 10;          // cv::FastFeatureDetector::create()'s defaults (:65)
+    prm.nonmaxSuppression = 1;
+    prm.gridRows = cvp.gridRows;
+    prm.gridCols = cvp.gridCols;
+    prm.maximalTrackedFeatures = cvp.maximalTrackedFeatures;
+    prm.reserved = 0;
+    const int cap = cvp.maximalTrackedFeatures > 0 ? cvp.maximalTrackedFeatures : 0;
+    std::vector<cv::Point2f> xy((size_t)cap);
+    std::vector<float> response((size_t)cap);
+    int n = 0;
+    status = ps_detect_features(ctx, rgbImage.data, rgbImage.rows, rgbImage.cols, rgbImage.channels(), (size_t)rgbImage.step, &prm,
+                                reinterpret_cast<float *>(xy.data()), response.data(), cap, &n);
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        return keypoints;
+    }
+    keypoints.resize((size_t)n);
+    for (int j = 0; j < n; ++j) { // cv::KeyPoint(pt, 7.f, -1, score): octave 0, class_id -1
+        cv::KeyPoint &kp = keypoints[(size_t)j];
+        kp.pt = xy[(size_t)j];
+        kp.size = 7.f;
+        kp.angle = -1.f;
+        kp.response = response[(size_t)j];
+        kp.octave = 0;
+        kp.class_id = -1;
+    }
+    if (matcherParameters.verbose > 1) std::cout << "MatcherOpenCV: After joining we have " << keypoints.size() << " keypoints" << std::endl;
+    return keypoints;
+}
+
 // MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) with the matcher of matcherOpenCV.cpp:100-102, cv::BFMatcher(cv::NORM_L2,
 // true), on CV_32F descriptor Mats of 1 .. PS_MAX_L2_DIM columns (ps_match_l2_f32).
 std::vector<cv::DMatch> l2CrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors)

@@ -199,6 +199,10 @@ class FrameMatcher {
             float eps = 0.01f;
             double trackingErrorThreshold = 25.0, trackingMinEigThreshold = 0.0;
             int trackingErrorType = 0;
+            // the detector's block (matcher.h:40,43,51; putslammatcherOpenCVParameters.xml:64,67): detectFeatures below runs "FAST"
+            std::string detector = "ORB";
+            int gridRows = 1, gridCols = 1;
+            int maximalTrackedFeatures = 500;
         } OpenCVParams;
         MatcherParameters();
     };
@@ -365,6 +369,18 @@ std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &m
                                         std::vector<cv::KeyPoint> &prevKeyPoints, std::vector<cv::KeyPoint> &keyPoints,
                                         std::vector<double> &prevDetDists, std::vector<double> &detDists);
 
+// MatcherOpenCV::detectFeatures (matcherOpenCV.cpp:118-180) for OpenCVParams.detector == "FAST" (cv::FastFeatureDetector::create(),
+// :64-65: threshold 10, non-maximum suppression on, pattern 9/16) as a free function over the calling thread's context
+// (ps_detect_features): cvtColor(RGB2GRAY) -- channel 0 takes the red weight; a CV_8UC1 Mat is taken as grey already --, the
+// gridCols x gridRows ROIs, the detector in each, the per-ROI ordering by response cut to maximalTrackedFeatures * 3 / (gridCols *
+// gridRows), the joined ordering cut to maximalTrackedFeatures.  rgbImage: CV_8UC1 or CV_8UC3, any step (a region of a parent).
+// Each key point is (pt, size 7, angle -1, response = score, octave 0, class_id -1).
+// BOTH orderings are STABLE here: the reference's std::sort (compare_response, matcherOpenCV.h:84-87) leaves the order of equal
+// responses, and who survives a cut inside a tie, to its libstdc++; this library keeps raster order inside an ROI and the order
+// of the ROI loop across ROIs (include/putslam_hip.h).
+// Any other detector (ORB, SURF, SIFT) is NOT run on the CPU instead: one line goes to std::cerr and the list comes back empty.
+std::vector<cv::KeyPoint> detectFeaturesFAST(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat rgbImage);
+
 // Library-owned singletons with the reference factories' ownership rules (raw pointer returned, a second call
 // replaces the instance: matcherOpenCV.cpp:20-47): one for the VO thread, one for the loop-closure thread.
 FrameMatcher *createFrameMatcher(void);
@@ -397,6 +413,8 @@ class FrameMatcherHIP : public FrameMatcher {
                                                     std::vector<cv::Point2f> &features, std::vector<cv::KeyPoint> &prevKeyPoints,
                                                     std::vector<cv::KeyPoint> &keyPoints, std::vector<double> &prevDetDists,
                                                     std::vector<double> &detDists);
+    // MatcherOpenCV::detectFeatures, matcherOpenCV.cpp:118-180 (the reference's signature; detectFeaturesFAST above)
+    virtual std::vector<cv::KeyPoint> detectFeatures(cv::Mat rgbImage);
 };
 
 } // namespace putslam_hip

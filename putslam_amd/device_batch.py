@@ -9,7 +9,7 @@ import torch
 from . import api
 from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
-                   make_config, PsImageSet, klt_params)
+                   make_config, PsImageSet, klt_params, detect_params)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -322,6 +322,14 @@ def exclude_device(ctx, rule, cand3, cand2, cand_counts, exist3=None, exist2=Non
     return kept, nkept
 
 
+def _image_set(images, rows, cols, channels):
+    """PsImageSet of a uint8 device tensor (F, rows, cols[, channels]) whose rows and frames may lie any stride apart."""
+    assert images.dtype == torch.uint8 and images.dim() in (3, 4) and tuple(images.shape[1:3]) == (rows, cols)
+    cn = 1 if images.dim() == 3 else images.shape[3]
+    assert cn == channels and (images.dim() == 3 and images.stride(2) == 1 or images.dim() == 4 and images.stride()[2:] == (cn, 1))
+    return PsImageSet(images.data_ptr(), images.stride(1), images.stride(0) if images.shape[0] > 1 else 0, images.shape[0], rows, cols, cn)
+
+
 class KltPyramids:
     """A device-resident set of `slots` image pyramids with their derivatives (ps_klt_pyramids_create): the images of a sequence,
     built once, tracked pair by pair.  rows x cols x channels 8-bit images; win_size / max_levels as in _abi.klt_params."""
@@ -346,11 +354,7 @@ class KltPyramids:
     def build(self, images, first_slot=0, use_torch_stream=True):
         """Fills slots first_slot .. from `images`: a uint8 device tensor (F, rows, cols[, channels]) whose rows and frames may
         lie any stride apart (a view of a padded block); a row itself is dense.  Asynchronous, ordered like run_pairs."""
-        assert images.dtype == torch.uint8 and images.dim() in (3, 4) and tuple(images.shape[1:3]) == (self.rows, self.cols)
-        cn = 1 if images.dim() == 3 else images.shape[3]
-        assert cn == self.channels and (images.dim() == 3 and images.stride(2) == 1 or images.dim() == 4 and images.stride()[2:] == (cn, 1))
-        s = PsImageSet(images.data_ptr(), images.stride(1), images.stride(0) if images.shape[0] > 1 else 0, images.shape[0],
-                       self.rows, self.cols, cn)
+        s = _image_set(images, self.rows, self.cols, self.channels)
         _on_torch_stream(self.ctx, images.device, lambda: self.ctx.klt_pyramids_build_device(self.handle, s, first_slot),
                          use_torch_stream)
 
@@ -400,6 +404,53 @@ def select_tracked(ctx, next_pts, status, err, counts, tracking_error_threshold,
             min_reproj_distance, matches.data_ptr(), num.data_ptr(), kept_pts.data_ptr(), kept_idx.data_ptr())
     _on_torch_stream(ctx, dev, lambda: ctx.klt_select_device(*args), use_torch_stream)
     return matches, num, kept_pts, kept_idx
+
+
+class FastDetector:
+    """A device-resident FAST-9/16 detector for up to `max_frames` images of rows x cols x channels bytes a call
+    (ps_fast_detector_create): the grey, score and corner maps of its last call stay readable through maps()."""
+
+    def __init__(self, ctx, rows, cols, channels, max_frames):
+        self.ctx, self.rows, self.cols, self.channels, self.max_frames = ctx, int(rows), int(cols), int(channels), int(max_frames)
+        self.handle = ctx.fast_detector_create(rows, cols, channels, max_frames)
+
+    def close(self):
+        if self.handle is not None:
+            self.ctx._L.ps_fast_detector_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def maps(self, frame):
+        """(grey, score, corner) of one frame of the last call, on the host (api.Context.debug_fast_maps)."""
+        return self.ctx.debug_fast_maps(self.handle, frame, self.rows, self.cols)
+
+
+def detect_features_batch(ctx, det: FastDetector, images, params=None, capacity=None, xy=None, response=None, counts=None,
+                          use_torch_stream=True, passes=7):
+    """MatcherOpenCV::detectFeatures (detector = "FAST") for every frame of `images` (ps_detect_features_device): a uint8 device
+    tensor (F, rows, cols[, channels]) of the detector's shape, the tensor KltPyramids.build takes.  params: _abi.detect_params(...),
+    default the shipped ones; capacity: rows per frame (default maximalTrackedFeatures).  xy (F, cap, 2) float32 / response (F, cap)
+    float32 / counts (F,) int32: blocks to write into (default: new ones).  Returns (xy, response, counts), written asynchronously:
+    nothing beyond a frame's count.  xy and counts drop into dbscan_thin_device, the rows it keeps into track_klt_pairs.
+    passes: 7, or the mask of ps_debug_fast_passes (timing scripts)."""
+    params = params or detect_params()
+    s = _image_set(images, det.rows, det.cols, det.channels)
+    F, dev = images.shape[0], images.device
+    cap = int(params.maximalTrackedFeatures) if capacity is None else int(capacity)
+    xy = _zeros(dev, (F, cap, 2), torch.float32) if xy is None else xy
+    response = _zeros(dev, (F, cap), torch.float32) if response is None else response
+    counts = _zeros(dev, (F,), torch.int32) if counts is None else counts
+    assert xy.dtype == torch.float32 and xy.shape == (F, cap, 2) and xy.is_contiguous()
+    assert response.dtype == torch.float32 and response.shape == (F, cap) and response.is_contiguous()
+    assert counts.dtype == torch.int32 and counts.shape == (F,) and counts.is_contiguous()
+    args = (det.handle, s, params, cap, xy.data_ptr(), response.data_ptr(), counts.data_ptr(), passes)
+    _on_torch_stream(ctx, dev, lambda: ctx.detect_features_device(*args), use_torch_stream)
+    return xy, response, counts
 
 
 class MapBatchDevice(PairResultsDevice):
