@@ -586,10 +586,26 @@ class Context:
     # ---- N2 ----
     def match_xyz(self, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, radius=0.12, ratio=0.55):
         """Guided map matching core of Matcher::matchXYZ (matcher.cpp:694-746)."""
+        return self._match_xyz(self._L.ps_match_xyz, np.uint8, 32, (), map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level,
+                               radius, ratio)
+
+    def match_xyz_l2(self, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, radius=0.12, ratio=0.55):
+        """match_xyz for float descriptors (ps_match_xyz_l2_f32): (n, dim) float32 rows, the value is the L2 norm of the float
+        difference accumulated in double (tests/map_l2_ref.py)."""
+        map_desc = np.ascontiguousarray(map_desc, np.float32)
+        cur_desc = np.ascontiguousarray(cur_desc, np.float32)
+        assert map_desc.ndim == 2 and cur_desc.ndim == 2 and map_desc.shape[1] == cur_desc.shape[1]
+        dim = map_desc.shape[1]
+        return self._match_xyz(self._L.ps_match_xyz_l2_f32, np.float32, dim * 4, (dim,), map_pos, map_desc, map_level, cur_pos,
+                               cur_desc, cur_level, radius, ratio)
+
+    def _match_xyz(self, entry, dtype, row_bytes, dim_arg, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, radius, ratio):
+        """match_xyz / match_xyz_l2: `entry` on rows of `dtype`, `row_bytes` apart (dim_arg: what the entry takes after ncur);
+        repeated with the reported count while the output rows are too few."""
         map_pos = np.ascontiguousarray(map_pos, np.float32)
         cur_pos = np.ascontiguousarray(cur_pos, np.float32)
-        map_desc = np.ascontiguousarray(map_desc, np.uint8)
-        cur_desc = np.ascontiguousarray(cur_desc, np.uint8)
+        map_desc = np.ascontiguousarray(map_desc, dtype)
+        cur_desc = np.ascontiguousarray(cur_desc, dtype)
         map_level = np.ascontiguousarray(map_level, np.int32)
         cur_level = np.ascontiguousarray(cur_level, np.int32)
         nmap, ncur = map_pos.shape[0], cur_pos.shape[0]
@@ -597,34 +613,8 @@ class Context:
         while True:
             out = np.zeros(cap, DMATCH_DTYPE)
             n = C.c_int(0)
-            rc = self._L.ps_match_xyz(self._h, _p(map_pos), _p(map_desc), 32, _p(map_level), nmap, _p(cur_pos),
-                                      _p(cur_desc), 32, _p(cur_level), ncur, float(radius), float(ratio), _p(out), cap,
-                                      C.byref(n))
-            if rc == PS_OK:
-                return out[: n.value].copy()
-            if n.value > cap:
-                cap = n.value
-                continue
-            self._chk(rc)
-
-    def match_xyz_l2(self, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, radius=0.12, ratio=0.55):
-        """match_xyz for float descriptors (ps_match_xyz_l2_f32): (n, dim) float32 rows, the value is the L2 norm of the float
-        difference accumulated in double (tests/map_l2_ref.py)."""
-        map_pos = np.ascontiguousarray(map_pos, np.float32)
-        cur_pos = np.ascontiguousarray(cur_pos, np.float32)
-        map_desc = np.ascontiguousarray(map_desc, np.float32)
-        cur_desc = np.ascontiguousarray(cur_desc, np.float32)
-        map_level = np.ascontiguousarray(map_level, np.int32)
-        cur_level = np.ascontiguousarray(cur_level, np.int32)
-        assert map_desc.ndim == 2 and cur_desc.ndim == 2 and map_desc.shape[1] == cur_desc.shape[1]
-        nmap, ncur, dim = map_pos.shape[0], cur_pos.shape[0], map_desc.shape[1]
-        cap = max(1, 4 * nmap)
-        while True:
-            out = np.zeros(cap, DMATCH_DTYPE)
-            n = C.c_int(0)
-            rc = self._L.ps_match_xyz_l2_f32(self._h, _p(map_pos), _p(map_desc), dim * 4, _p(map_level), nmap, _p(cur_pos),
-                                             _p(cur_desc), dim * 4, _p(cur_level), ncur, dim, float(radius), float(ratio), _p(out),
-                                             cap, C.byref(n))
+            rc = entry(self._h, _p(map_pos), _p(map_desc), row_bytes, _p(map_level), nmap, _p(cur_pos), _p(cur_desc), row_bytes,
+                       _p(cur_level), ncur, *dim_arg, float(radius), float(ratio), _p(out), cap, C.byref(n))
             if rc == PS_OK:
                 return out[: n.value].copy()
             if n.value > cap:
@@ -764,41 +754,13 @@ class Context:
                             ratio=0.55, max_tries=10, min_ratio=0.1, max_matches=None, device=None):
         """match_xyz_ladder for float descriptors ((n, dim) float32 rows): the tries of matcher.cpp:617-622 as ONE
         ps_map_pairs_l2_device call; the same selection, the same result dict, the same capacity rule."""
-        from . import device_batch
-        map_pos = np.ascontiguousarray(map_pos, np.float32)
-        cur_pos = np.ascontiguousarray(cur_pos, np.float32)
+        from . import device_batch as db
         map_desc = np.ascontiguousarray(map_desc, np.float32)
         cur_desc = np.ascontiguousarray(cur_desc, np.float32)
         assert map_desc.ndim == 2 and cur_desc.ndim == 2 and map_desc.shape[1] == cur_desc.shape[1]
-        nmap, ncur, dim = map_pos.shape[0], cur_pos.shape[0], map_desc.shape[1]
-        dev = device if device is not None else "cuda:%d" % self._L.ps_context_device(self._h)
-
-        def side(desc, pos, level, n):       # one view / frame as a frame set of its own (capacity >= 1)
-            cap = max(n, 1)
-            d, q, lv = np.zeros((1, cap, dim), np.float32), np.zeros((1, cap, 3), np.float32), np.zeros((1, cap), np.int32)
-            if n:
-                d[0], q[0], lv[0] = desc, pos, np.asarray(level, np.int32).reshape(n)
-            return device_batch.FrameSetF32Device(d, q, [n], dev), lv
-
-        views, mlv = side(map_desc, map_pos, map_level, nmap)
-        frames, clv = side(cur_desc, cur_pos, cur_level, ncur)
-        tries = [ladder_try(float(radius), float(ratio), k) for k in range(1, int(max_tries) + 1)]
-
-        def run(cap):
-            batch = device_batch.MapBatchF32Device(views, mlv, frames, clv, np.zeros((len(tries), 2), np.int32), cap,
-                                                   radius=[t[0] for t in tries], ratio=[t[1] for t in tries])
-            device_batch.run_map_pairs_l2(self, params, cfg, K, batch)
-            r = batch.download()
-            return r, int(-r["numMatches"].min()) if len(tries) else 0
-
-        r, _ = retry_with_reported_capacity(run, int(max_matches) if max_matches is not None else max(1, 4 * nmap))
-        ratios = [float(x) for x in r["stats"]["pointInlierRatio"]]
-        k = ladder_pick(ratios, min_ratio)
-        n = max(int(r["numMatches"][k]), 0)
-        ir = ratios[k]
-        return dict(matches=r["matches"][k, :n].copy(), mask=r["inlierMask"][k, :n].copy(), pose=r["pose"][k].reshape(4, 4).T.copy(),
-                    stats=r["stats"][k].copy(), inlier_ratio=-1.0 if ir != ir else ir, try_used=k + 1,
-                    num_matches=int(r["numMatches"][k]))
+        return self._match_xyz_ladder(db.FrameSetF32Device, db.MapBatchF32Device, db.run_map_pairs_l2, np.float32, map_desc.shape[1],
+                                      map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, params, cfg, K, radius, ratio,
+                                      max_tries, min_ratio, max_matches, device)
 
     def match_xyz_ladder(self, map_pos, map_desc, map_level, cur_pos, cur_desc, cur_level, params, cfg, K, radius=0.12,
                          ratio=0.55, max_tries=10, min_ratio=0.1, max_matches=None, device=None):
@@ -813,7 +775,13 @@ class Context:
         match_xyz + ransac_rigid3d and retries.  Measured (profiles/r08a/map_pairs.txt): 0.55 ms at 500 x 500 and 0.85 ms at
         2000 x 2000 against 0.23 / 0.68 / 2.3 ms and 0.30 / 0.89 / 3.2 ms for one / three / ten sequential tries -- the ladder
         wins from the third try on."""
-        from . import device_batch
+        from . import device_batch as db
+        return self._match_xyz_ladder(db.FrameSetDevice, db.MapBatchDevice, db.run_map_pairs, np.uint8, 32, map_pos, map_desc,
+                                      map_level, cur_pos, cur_desc, cur_level, params, cfg, K, radius, ratio, max_tries, min_ratio,
+                                      max_matches, device)
+
+    def _match_xyz_ladder(self, frame_set_type, batch_type, run_pairs, dtype, width, map_pos, map_desc, map_level, cur_pos, cur_desc,
+                          cur_level, params, cfg, K, radius, ratio, max_tries, min_ratio, max_matches, device):
         map_pos = np.ascontiguousarray(map_pos, np.float32)
         cur_pos = np.ascontiguousarray(cur_pos, np.float32)
         nmap, ncur = map_pos.shape[0], cur_pos.shape[0]
@@ -821,19 +789,19 @@ class Context:
 
         def side(desc, pos, level, n):       # one view / frame as a frame set of its own (capacity >= 1)
             cap = max(n, 1)
-            d, q, lv = np.zeros((1, cap, 32), np.uint8), np.zeros((1, cap, 3), np.float32), np.zeros((1, cap), np.int32)
+            d, q, lv = np.zeros((1, cap, width), dtype), np.zeros((1, cap, 3), np.float32), np.zeros((1, cap), np.int32)
             if n:
-                d[0], q[0], lv[0] = np.asarray(desc, np.uint8).reshape(n, 32), pos, np.asarray(level, np.int32).reshape(n)
-            return device_batch.FrameSetDevice(d, q, [n], dev), lv
+                d[0], q[0], lv[0] = np.asarray(desc, dtype).reshape(n, width), pos, np.asarray(level, np.int32).reshape(n)
+            return frame_set_type(d, q, [n], dev), lv
 
         views, mlv = side(map_desc, map_pos, map_level, nmap)
         frames, clv = side(cur_desc, cur_pos, cur_level, ncur)
         tries = [ladder_try(float(radius), float(ratio), k) for k in range(1, int(max_tries) + 1)]
 
         def run(cap):
-            batch = device_batch.MapBatchDevice(views, mlv, frames, clv, np.zeros((len(tries), 2), np.int32), cap,
-                                                radius=[t[0] for t in tries], ratio=[t[1] for t in tries])
-            device_batch.run_map_pairs(self, params, cfg, K, batch)
+            batch = batch_type(views, mlv, frames, clv, np.zeros((len(tries), 2), np.int32), cap,
+                               radius=[t[0] for t in tries], ratio=[t[1] for t in tries])
+            run_pairs(self, params, cfg, K, batch)
             r = batch.download()
             # (a try that overflowed its rows reports -(count): the repeat has room for the largest, as the loop would see it)
             return r, int(-r["numMatches"].min()) if len(tries) else 0

@@ -1251,13 +1251,13 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
 // The further features, each header its kernels and then its host side, in dependency order
 #include "ps_stream_push.h"  // ps_vo_stream_create / _push: the synchronous streaming form
 #include "ps_stream_async.h" // ... and the pipelined one, on the PsVoStream of the former
-#include "ps_map_match.h"    // ps_match_xyz_device / ps_map_pairs_device (the plan and the stages above)
+#include "ps_map_match.h"    // map_sweep<F, D>, its launcher and entry bodies; ps_match_xyz_device / ps_map_pairs_device (the plan and the stages above)
 #include "ps_dbscan.h"       // ps_dbscan_thin(_device)
 #include "ps_exclusion.h"    // ps_exclude(_device) and the three rules (DBScan's bound and union-find)
 #include "ps_map_view.h"     // ps_map_views_device / ps_frame_levels_device
 #include "ps_loop_closure.h" // ps_pose_sets_device / ps_loop_pairs_device (the plan and the stages above)
 #include "ps_match_l2.h"     // ps_match_l2_f32 / ps_match_l2_device / ps_vo_pairs_l2_device (the plan and the stages above)
-#include "ps_map_match_l2.h" // ps_match_xyz_l2_f32 / ps_match_xyz_l2_device / ps_map_pairs_l2_device (the two headers above)
+#include "ps_map_match_l2.h" // the float policy of ps_map_match.h: ps_match_xyz_l2_f32 / ps_match_xyz_l2_device / ps_map_pairs_l2_device (ps_match_l2.h too)
 #include "ps_map_store_f32.h" // ps_map_views_l2_device / ps_pose_sets_l2_device / ps_loop_pairs_l2_device (ps_map_view.h, ps_loop_closure.h, ps_match_l2.h)
 #include "ps_klt.h"          // ps_klt_pyramids_* / ps_klt_track_device / ps_klt_select_device / ps_perform_tracking (ps_exclusion.h's bound)
 #include "ps_fast.h"         // ps_fast_detector_* / ps_detect_features(_device) (ps_klt.h's PsImageSet stride rule)

@@ -1,20 +1,33 @@
 // ps_map_match.h -- batched, device-resident guided map matching: Matcher::matchXYZ (reference src/Matcher/matcher.cpp:694-746)
-// for P (map view, frame) pairs in two launches, no host step (ps_match_xyz_device / ps_map_pairs_device, include/putslam_hip.h).
+// for P (map view, frame) pairs in two launches, no host step, for 32-byte binary rows (ps_match_xyz_device /
+// ps_map_pairs_device, include/putslam_hip.h) and, through ps_map_match_l2.h, for SURF / SIFT float rows.
 // The rule is ps_match_xyz_kernel's (ps_kernels.h), which sweeps a frame twice between a count, a scan and a write launch:
 //
-//   ps_map_sweep<F>   grid P x chunks, a chunk = 4 waves x F map features.  The frame's positions and levels pass through LDS
+//   map_sweep<F, D>   THE sweep, once, for a descriptor policy D; the kernels ps_map_sweep<F> (MapBinRows, below) and
+//                     ps_map_sweep_l2<F> (MapL2Rows, ps_map_match_l2.h) are its two instantiations.
+//                     Grid P x chunks, a chunk = 4 waves x F map features.  The frame's positions and levels pass through LDS
 //                     once per work-group, 1024 keypoints at a time; a wave holds its F features in scalar registers, so one LDS
 //                     read serves F sphere tests.  Candidates are rare (0 - 3 per feature at the first try of the retry ladder,
-//                     up to 14 at the tenth): a feature's candidates (i, value) are appended in ballot order -- ascending i -- to
-//                     a stash of kMapStash entries in LDS, and best / ratio / emit work on that list.  A feature with more
-//                     candidates than the stash holds is swept again from global memory (map_resweep, the old kernel's second
-//                     sweep).  The chunk's accepted matches, ordered by (j, i), go to a place in the pair's row of a staging
-//                     block that the chunk reserves with ONE atomic add; (start, count) are kept per chunk.
+//                     up to 14 at the tenth): a feature's candidates (i, value bits) are appended in ballot order -- ascending
+//                     i -- to a stash of kMapStash entries in LDS, and best / ratio / emit work on that list.  A feature with
+//                     more candidates than the stash holds is swept again from global memory (map_resweep, the old kernel's
+//                     second sweep).  The chunk's accepted matches, ordered by (j, i), go to a place in the pair's row of a
+//                     staging block that the chunk reserves with ONE atomic add; (start, count) are kept per chunk.
 //   ps_map_emit       grid P.  Scans the pair's chunk counts and moves the chunks to the output row in chunk order -- the
 //                     (j, i) order of the reference's push_back loop whatever order the chunks ran in -- and, in the same pass
 //                     over the matches, does what ps_prep_from_matches does for one pair: depth filter, ordered compaction,
 //                     scoring records, bounds, the scoring stage's counters cleared.
 // A pair whose count exceeds the row capacity reports -(count) and is handed to RANSAC with no matches.
+//
+// A descriptor policy D holds what a candidate's VALUE is, and nothing of the decomposition:
+//   D::Args                      the kernel's argument block: MapArgs m, then the descriptor pointers and strides
+//   D(args, view, frame)         the rows of the pair's map view and frame
+//   D::Best, D::none()           what a lane keeps per feature across the tile loop
+//   hit(j, i, best)              inside the rare hit branch: the value bits stashed beside i (binary: the value, evaluated
+//                                there; float: nothing yet -- a row is 256 - 2048 B and is not touched there)
+//   values<F>(lists, cnt, jw)    the value phase of the wave's F lists between the tile loop and best / ratio (binary: none)
+//   best_value(best, list, cnt, s)  bestVal of a feature with cnt > 0 candidates
+//   value(j, i)                  one lane, one candidate, from global memory: map_resweep's value
 #pragma once
 #include "ps_glue.h"
 #include "ps_kernels.h"
@@ -26,14 +39,13 @@ constexpr int kMapWaves = kMapBlock / 64;
 constexpr int kMapTile = 1024;  // keypoints staged per trip: 16 KiB of LDS
 constexpr int kMapStash = 16;   // candidates kept per map feature
 
+// What the decomposition and ps_map_emit read (the descriptors are the policies')
 struct MapArgs {
     const float *mapPts, *curPts;     // frame sets' points
-    const uint4 *mapDesc, *curDesc;   // ... descriptors
     const int32_t *mapN, *curN;       // ... keypoint counts
     const int32_t *mapLevel, *curLevel; // [numFrames][maxKpts]
     int mapFrames, curFrames, mapCap, curCap;
     int mapPtsStride, curPtsStride;   // floats between frames
-    int mapDescStride, curDescStride; // uint4 between frames
     const int32_t *pairs;             // P x (map view, frame)
     float radiusBound;
     double acceptRatio;
@@ -65,48 +77,76 @@ PS_D unsigned long long wave_min_u64(unsigned long long v)
     return __shfl(v, 0, 64);
 }
 
-// One wave, one map feature, the whole frame from global memory: every candidate within the accept ratio of bestVal,
-// ascending i.  Returns their number; WRITE emits them from out[0] on.
-template <bool WRITE>
-PS_D int map_resweep(float mx, float my, float mz, int lj, const uint4 &a0, const uint4 &a1, const float *__restrict__ curPos,
-                     const uint4 *__restrict__ curDesc, const int32_t *__restrict__ curLevel, int ncur, float radiusBound,
-                     double acceptRatio, float bestVal, int j, PsDMatch *__restrict__ out)
+PS_D uint32_t wave_min_u32(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_down((int)v, o, 64);
+        v = other < v ? other : v;
+    }
+    return (uint32_t)__shfl((int)v, 0, 64);
+}
+
+// One map feature against the pair's frame: what a sweep from global memory needs
+struct MapSphere {
+    float mx, my, mz;
+    int lj, j;
+    const float *__restrict__ curPos;
+    const int32_t *__restrict__ curLevel;
+    int ncur;
+    float radiusBound;
+    double acceptRatio;
+};
+
+enum MapResweep { kMapLeast, kMapCount, kMapWrite };
+
+// One wave, one map feature, the whole frame from global memory, a lane evaluating d.value(j, i) per candidate.
+//   kMapLeast: returns the bits of the least non-NaN value among the candidates (+inf's bits if there is none);
+//   kMapCount / kMapWrite: the number of candidates within the accept ratio of bestVal, ascending i; kMapWrite emits them from
+//   out[0] on.
+template <MapResweep MODE, class D> PS_D uint32_t map_resweep(const D &d, const MapSphere &s, float bestVal, PsDMatch *__restrict__ out)
 {
     const int lane = threadIdx.x & 63;
-    int n = 0;
-    for (int i0 = 0; i0 < ncur; i0 += 64) {
+    uint32_t n = 0, least = 0x7F800000u;
+    for (int i0 = 0; i0 < s.ncur; i0 += 64) {
         const int i = i0 + lane;
         bool acc = false;
         float value = 0.f;
-        if (i < ncur) {
-            const float d0 = mx - curPos[3 * i], d1 = my - curPos[3 * i + 1], d2 = mz - curPos[3 * i + 2];
-            const float s = d0 * d0 + (d1 * d1 + d2 * d2);
-            const int li = curLevel[i];
-            if (s < radiusBound && li - 1 <= lj && lj <= li + 1) {
-                value = (float)satdiff_popc256(a0, a1, curDesc[2 * i], curDesc[2 * i + 1]);
-                acc = acceptRatio * (double)value <= (double)bestVal;
+        if (i < s.ncur) {
+            const float d0 = s.mx - s.curPos[3 * i], d1 = s.my - s.curPos[3 * i + 1], d2 = s.mz - s.curPos[3 * i + 2];
+            const float sum = d0 * d0 + (d1 * d1 + d2 * d2);
+            const int li = s.curLevel[i];
+            if (sum < s.radiusBound && li - 1 <= s.lj && s.lj <= li + 1) {
+                value = d.value(s.j, i);
+                if (MODE == kMapLeast) {
+                    if (value == value && __float_as_uint(value) < least) least = __float_as_uint(value);
+                } else {
+                    acc = s.acceptRatio * (double)value <= (double)bestVal;
+                }
             }
         }
-        const unsigned long long bal = __ballot(acc);
-        if (WRITE && acc) {
-            PsDMatch m;
-            m.queryIdx = j;
-            m.trainIdx = i;
-            m.imgIdx = -1; // default-constructed cv::DMatch (matcher.cpp:741)
-            m.distance = value;
-            out[n + __popcll(bal & ((1ull << lane) - 1ull))] = m;
+        if (MODE != kMapLeast) {
+            const unsigned long long bal = __ballot(acc);
+            if (MODE == kMapWrite && acc) {
+                PsDMatch m;
+                m.queryIdx = s.j;
+                m.trainIdx = i;
+                m.imgIdx = -1; // default-constructed cv::DMatch (matcher.cpp:741)
+                m.distance = value;
+                out[n + __popcll(bal & ((1ull << lane) - 1ull))] = m;
+            }
+            n += __popcll(bal);
         }
-        n += __popcll(bal);
     }
-    return n;
+    return MODE == kMapLeast ? wave_min_u32(least) : n;
 }
 
-template <int F>
-__global__ __launch_bounds__(kMapBlock) void ps_map_sweep(MapArgs a)
+template <int F, class D> PS_D void map_sweep(const typename D::Args &b)
 {
     constexpr int CH = kMapWaves * F;
+    const MapArgs &a = b.m;
     __shared__ uint4 s_tile[kMapTile];
-    __shared__ uint2 s_stash[CH * kMapStash];
+    __shared__ uint2 s_stash[CH * kMapStash]; // (i, the value's float bits)
     __shared__ int s_n[CH];
     __shared__ int s_start;
     const int p = blockIdx.x / a.chunks, c = blockIdx.x - p * a.chunks;
@@ -124,22 +164,23 @@ __global__ __launch_bounds__(kMapBlock) void ps_map_sweep(MapArgs a)
     const float radiusBound = a.radiusPer ? a.radiusPer[p] : a.radiusBound;
     const double acceptRatio = a.ratioPer ? a.ratioPer[p] : a.acceptRatio;
     const float *__restrict__ mapPos = a.mapPts + (size_t)view * a.mapPtsStride;
-    const uint4 *__restrict__ mapDesc = a.mapDesc + (size_t)view * a.mapDescStride;
     const int32_t *__restrict__ mapLevel = a.mapLevel + (size_t)view * a.mapCap;
     const float *__restrict__ curPos = a.curPts + (size_t)frame * a.curPtsStride;
-    const uint4 *__restrict__ curDesc = a.curDesc + (size_t)frame * a.curDescStride;
     const int32_t *__restrict__ curLevel = a.curLevel + (size_t)frame * a.curCap;
+    const D d(b, view, frame);
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const unsigned long long below = (1ull << lane) - 1ull;
+    const int jw = j0 + w * F;                          // the wave's first feature
+    uint2 *const lists = s_stash + w * F * kMapStash; // ... and its F lists
 
     // the wave's F map features: wave-uniform (a feature beyond the view gets a NaN position: no test passes)
     float mx[F], my[F], mz[F];
     int lj[F], cnt[F];
-    unsigned long long best[F]; // per lane: least (value, i) among the candidates it has seen
+    typename D::Best best[F];
 #pragma unroll
     for (int f = 0; f < F; ++f) {
-        const int j = j0 + w * F + f;
+        const int j = jw + f;
         const bool has = j < nmap;
         const int jc = has ? j : nmap - 1;
         mx[f] = has ? mapPos[3 * jc] : __builtin_nanf("");
@@ -147,7 +188,7 @@ __global__ __launch_bounds__(kMapBlock) void ps_map_sweep(MapArgs a)
         mz[f] = mapPos[3 * jc + 2];
         lj[f] = mapLevel[jc];
         cnt[f] = 0;
-        best[f] = ~0ull;
+        best[f] = D::none();
     }
 
     for (int t0 = 0; t0 < ncur; t0 += kMapTile) {
@@ -172,13 +213,11 @@ __global__ __launch_bounds__(kMapBlock) void ps_map_sweep(MapArgs a)
                 const bool hit = inb && s < radiusBound && li - 1 <= lj[f] && lj[f] <= li + 1;
                 const unsigned long long bal = __ballot(hit);
                 if (bal != 0ull) { // (rare; wave-uniform)
-                    const int j = j0 + w * F + f, g = t0 + i;
                     if (hit) {
-                        const uint32_t v = satdiff_popc256(mapDesc[2 * j], mapDesc[2 * j + 1], curDesc[2 * g], curDesc[2 * g + 1]);
-                        const unsigned long long key = ((unsigned long long)v << 32) | (unsigned)g;
-                        best[f] = key < best[f] ? key : best[f];
+                        const int g = t0 + i;
+                        const uint32_t bits = d.hit(jw + f, g, best[f]);
                         const int pos = cnt[f] + __popcll(bal & below);
-                        if (pos < kMapStash) s_stash[(w * F + f) * kMapStash + pos] = make_uint2((uint32_t)g, v);
+                        if (pos < kMapStash) lists[f * kMapStash + pos] = make_uint2((uint32_t)g, bits);
                     }
                     cnt[f] += __popcll(bal);
                 }
@@ -186,26 +225,26 @@ __global__ __launch_bounds__(kMapBlock) void ps_map_sweep(MapArgs a)
         }
     }
     __syncthreads(); // the stash is complete
+    d.template values<F>(lists, cnt, jw);
 
-    // best / ratio over the short list (or a second sweep), the feature's accepted count
+    // best / ratio over the short list (or further sweeps), the feature's accepted count
+    const auto sphere = [&](int f) { return MapSphere{mx[f], my[f], mz[f], lj[f], jw + f, curPos, curLevel, ncur, radiusBound, acceptRatio}; };
     unsigned long long accMask[F];
     float bestVal[F];
 #pragma unroll
     for (int f = 0; f < F; ++f) {
-        const int j = j0 + w * F + f;
         accMask[f] = 0ull;
         bestVal[f] = 0.f;
         int n = 0;
         if (cnt[f] > 0) {
-            bestVal[f] = (float)(uint32_t)(wave_min_u64(best[f]) >> 32);
+            bestVal[f] = d.best_value(best[f], lists + f * kMapStash, cnt[f], sphere(f));
             if (cnt[f] <= kMapStash) {
                 bool acc = false;
-                if (lane < cnt[f]) acc = acceptRatio * (double)(float)s_stash[(w * F + f) * kMapStash + lane].y <= (double)bestVal[f];
+                if (lane < cnt[f]) acc = acceptRatio * (double)__uint_as_float(lists[f * kMapStash + lane].y) <= (double)bestVal[f];
                 accMask[f] = __ballot(acc);
                 n = __popcll(accMask[f]);
             } else {
-                n = map_resweep<false>(mx[f], my[f], mz[f], lj[f], mapDesc[2 * j], mapDesc[2 * j + 1], curPos, curDesc, curLevel, ncur,
-                                       radiusBound, acceptRatio, bestVal[f], j, nullptr);
+                n = (int)map_resweep<kMapCount>(d, sphere(f), bestVal[f], nullptr);
             }
         }
         if (lane == 0) s_n[w * F + f] = n;
@@ -230,25 +269,56 @@ __global__ __launch_bounds__(kMapBlock) void ps_map_sweep(MapArgs a)
     PsDMatch *__restrict__ out = a.tmp + (size_t)p * a.maxMatches + start + before;
 #pragma unroll
     for (int f = 0; f < F; ++f) {
-        const int j = j0 + w * F + f;
         if (cnt[f] == 0) continue;
         if (cnt[f] <= kMapStash) {
             if ((accMask[f] >> lane) & 1ull) {
-                const uint2 e = s_stash[(w * F + f) * kMapStash + lane];
+                const uint2 e = lists[f * kMapStash + lane];
                 PsDMatch m;
-                m.queryIdx = j;
+                m.queryIdx = jw + f;
                 m.trainIdx = (int)e.x;
                 m.imgIdx = -1; // default-constructed cv::DMatch (matcher.cpp:741)
-                m.distance = (float)e.y;
+                m.distance = __uint_as_float(e.y);
                 out[__popcll(accMask[f] & below)] = m;
             }
             out += __popcll(accMask[f]);
         } else {
-            out += map_resweep<true>(mx[f], my[f], mz[f], lj[f], mapDesc[2 * j], mapDesc[2 * j + 1], curPos, curDesc, curLevel, ncur,
-                                     radiusBound, acceptRatio, bestVal[f], j, out);
+            out += map_resweep<kMapWrite>(d, sphere(f), bestVal[f], out);
         }
     }
 }
+
+// The binary policy: 32-byte rows, the value is the popcount of the difference -- cheap enough to evaluate inside the hit branch,
+// where each lane also keeps its least (value << 32 | i), so that bestVal is one wave minimum.
+struct MapBinArgs {
+    MapArgs m;
+    const uint4 *mapDesc, *curDesc;   // frame sets' descriptors
+    int mapDescStride, curDescStride; // uint4 between frames
+};
+
+struct MapBinRows {
+    using Args = MapBinArgs;
+    using Best = unsigned long long; // per lane: least (value, i) among the candidates it has seen
+    const uint4 *__restrict__ mapDesc, *__restrict__ curDesc;
+
+    PS_D MapBinRows(const Args &b, int view, int frame)
+        : mapDesc(b.mapDesc + (size_t)view * b.mapDescStride), curDesc(b.curDesc + (size_t)frame * b.curDescStride)
+    {
+    }
+    PS_D static Best none() { return ~0ull; }
+    PS_D uint32_t popc(int j, int i) const { return satdiff_popc256(mapDesc[2 * j], mapDesc[2 * j + 1], curDesc[2 * i], curDesc[2 * i + 1]); }
+    PS_D uint32_t hit(int j, int i, Best &best) const
+    {
+        const uint32_t v = popc(j, i);
+        const Best key = ((Best)v << 32) | (unsigned)i;
+        best = key < best ? key : best;
+        return __float_as_uint((float)v);
+    }
+    template <int F> PS_D void values(uint2 *, const int (&)[F], int) const {}
+    PS_D float best_value(Best best, const uint2 *, int, const MapSphere &) const { return (float)(uint32_t)(wave_min_u64(best) >> 32); }
+    PS_D float value(int j, int i) const { return (float)popc(j, i); }
+};
+
+template <int F> __global__ __launch_bounds__(kMapBlock) void ps_map_sweep(MapBinArgs b) { map_sweep<F, MapBinRows>(b); }
 
 // exclusive prefix of v over the work-group, in thread order; total = the sum
 template <int BLOCK> PS_D int block_scan_int(int v, int &total, int *wsum)
@@ -369,6 +439,9 @@ __global__ __launch_bounds__(BLOCK) void ps_map_emit(MapArgs a, PrepArgs pa, Rec
 
 // Host side: Matcher::matchXYZ, matcher.cpp:606-798, for a device-resident batch.  Part of the device translation unit: included
 // by ps_capi.hip behind the plan and the stages (Plan, make_plan, prepare_score, ensure_records, rec_ptrs, tick, run_ransac_stage).
+// A batch KIND names what differs between PsMapBatch and PsMapBatchF32 -- Batch, Args (the policy's argument block), what (the
+// prefix of the messages), sweeps() (the kernel per F) and sets(ctx, b, l): the rule of the two frame sets, which leaves the
+// descriptor arguments and the point strides of a batch that passed in l.  MapBinKind is below, MapL2Kind in ps_map_match_l2.h.
 namespace {
 
 // Map features per wave of the sweep: eight when that still gives every CU several work-groups, fewer for a handful of pairs
@@ -380,35 +453,33 @@ int map_features_per_wave(int P, int mapCap)
     return 1;
 }
 
-struct MapStrides { FrameStrides maps, frames; };
+template <class Args> struct MapSweeps { void (*f1)(Args), (*f2)(Args), (*f4)(Args), (*f8)(Args); };
 
-int check_map_batch(PsContext *ctx, const PsMapBatch *b, MapStrides &strides)
+template <class Kind> int check_map_batch(PsContext *ctx, const typename Kind::Batch *b, typename Kind::Args &l)
 {
-    if (!b || b->P < 0) return fail(ctx, PS_ERR_BAD_ARG, "map batch: null batch or P < 0");
+    const std::string w(Kind::what);
+    if (!b || b->P < 0) return fail(ctx, PS_ERR_BAD_ARG, (w + ": null batch or P < 0").c_str());
     if (b->P == 0) return PS_OK;
-    if (!b->pairs || !b->mapLevel || !b->curLevel) return fail(ctx, PS_ERR_BAD_ARG, "map batch: null pairs / mapLevel / curLevel");
-    if (int rc = check_frame_set(ctx, b->maps, "map batch: map views", strides.maps)) return rc;
-    if (int rc = check_frame_set(ctx, b->frames, "map batch: frames", strides.frames)) return rc;
-    if (b->maxMatches < 1) return fail(ctx, PS_ERR_BAD_ARG, "map batch: maxMatches must lie in 1 .. 1 << 22");
-    if (b->maxMatches > (1 << 22)) return fail(ctx, PS_ERR_UNSUPPORTED, "map batch: maxMatches must lie in 1 .. 1 << 22");
+    if (!b->pairs || !b->mapLevel || !b->curLevel) return fail(ctx, PS_ERR_BAD_ARG, (w + ": null pairs / mapLevel / curLevel").c_str());
+    if (int rc = Kind::sets(ctx, *b, l)) return rc;
+    if (b->maxMatches < 1) return fail(ctx, PS_ERR_BAD_ARG, (w + ": maxMatches must lie in 1 .. 1 << 22").c_str());
+    if (b->maxMatches > (1 << 22)) return fail(ctx, PS_ERR_UNSUPPORTED, (w + ": maxMatches must lie in 1 .. 1 << 22").c_str());
     return PS_OK;
 }
 
-// The two launches of ps_map_match.h for a checked batch; pl = null: matches only.  numClamped (device, P, or null) receives
-// max(numMatches[p], 0), what kernel 4 is given.
-int run_map_match(PsContext *ctx, const PsMapBatch &b, const MapStrides &strides, const Plan *pl, PsDMatch *dMatches,
+// The two launches for a checked batch (l as check_map_batch left it); pl = null: matches only.  numClamped (device, P, or
+// null) receives max(numMatches[p], 0), what kernel 4 is given.
+template <class Kind>
+int run_map_match(PsContext *ctx, const typename Kind::Batch &b, typename Kind::Args l, const Plan *pl, PsDMatch *dMatches,
                   int32_t *dNumMatches, int32_t **numClamped, int slot0)
 {
     const int P = b.P, F = map_features_per_wave(P, b.maps.maxKpts), CH = kMapWaves * F;
-    MapArgs a{};
+    MapArgs &a = l.m;
     a.mapPts = b.maps.pts; a.curPts = b.frames.pts;
-    a.mapDesc = (const uint4 *)b.maps.desc; a.curDesc = (const uint4 *)b.frames.desc;
     a.mapN = b.maps.nkpts; a.curN = b.frames.nkpts;
     a.mapLevel = b.mapLevel; a.curLevel = b.curLevel;
     a.mapFrames = b.maps.numFrames; a.curFrames = b.frames.numFrames;
     a.mapCap = b.maps.maxKpts; a.curCap = b.frames.maxKpts;
-    a.mapPtsStride = strides.maps.ptsFloats(); a.curPtsStride = strides.frames.ptsFloats();
-    a.mapDescStride = strides.maps.descUint4(); a.curDescStride = strides.frames.descUint4();
     a.pairs = b.pairs;
     a.radiusBound = b.radiusBound; a.acceptRatio = b.acceptRatio;
     a.radiusPer = b.radiusBoundPerPair; a.ratioPer = b.acceptRatioPerPair;
@@ -433,11 +504,12 @@ int run_map_match(PsContext *ctx, const PsMapBatch &b, const MapStrides &strides
     PS_HIP(hipMemsetAsync(a.tmpCount, 0, (size_t)P * sizeof(int32_t), ctx->stream));
     tick(ctx, slot0, false);
     const dim3 grid((unsigned)P * (unsigned)a.chunks), block(kMapBlock);
+    const MapSweeps<typename Kind::Args> sweeps = Kind::sweeps();
     switch (F) {
-    case 8: hipLaunchKernelGGL(ps_map_sweep<8>, grid, block, 0, ctx->stream, a); break;
-    case 4: hipLaunchKernelGGL(ps_map_sweep<4>, grid, block, 0, ctx->stream, a); break;
-    case 2: hipLaunchKernelGGL(ps_map_sweep<2>, grid, block, 0, ctx->stream, a); break;
-    default: hipLaunchKernelGGL(ps_map_sweep<1>, grid, block, 0, ctx->stream, a); break;
+    case 8: hipLaunchKernelGGL(sweeps.f8, grid, block, 0, ctx->stream, l); break;
+    case 4: hipLaunchKernelGGL(sweeps.f4, grid, block, 0, ctx->stream, l); break;
+    case 2: hipLaunchKernelGGL(sweeps.f2, grid, block, 0, ctx->stream, l); break;
+    default: hipLaunchKernelGGL(sweeps.f1, grid, block, 0, ctx->stream, l); break;
     }
     tick(ctx, slot0, true);
     PS_HIP(hipGetLastError());
@@ -460,40 +532,36 @@ int run_map_match(PsContext *ctx, const PsMapBatch &b, const MapStrides &strides
     return PS_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-float ps_map_sphere_bound(double sphereRadius) { return sq_bound_f32(sphereRadius); }
-
-size_t ps_abi_sizeof_map_batch(void) { return sizeof(PsMapBatch); }
-
-int ps_match_xyz_device(PsContext *ctx, const PsMapBatch *b, PsDMatch *matches, int32_t *numMatches)
+// ps_match_xyz_device / ps_match_xyz_l2_device
+template <class Kind>
+int match_xyz_body(PsContext *ctx, const char *who, const typename Kind::Batch *b, PsDMatch *matches, int32_t *numMatches)
 {
     int rc = bind(ctx);
     if (rc) return rc;
-    MapStrides strides;
-    rc = check_map_batch(ctx, b, strides);
+    typename Kind::Args l{};
+    rc = check_map_batch<Kind>(ctx, b, l);
     if (rc) return rc;
     if (b->P == 0) return PS_OK;
-    if (!matches || !numMatches) return fail(ctx, PS_ERR_BAD_ARG, "ps_match_xyz_device: null output");
+    if (!matches || !numMatches) return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null output").c_str());
     TimingOff toff(ctx);
     HandoffGuard handoffGuard{ctx};
-    return run_map_match(ctx, *b, strides, nullptr, matches, numMatches, nullptr, 0);
+    return run_map_match<Kind>(ctx, *b, l, nullptr, matches, numMatches, nullptr, 0);
 }
 
-int ps_map_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
-                        const PsMapBatch *b, const PsPairResults *out)
+// ps_map_pairs_device / ps_map_pairs_l2_device
+template <class Kind>
+int map_pairs_body(PsContext *ctx, const char *who, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                   const typename Kind::Batch *b, const PsPairResults *out)
 {
     int rc = bind(ctx);
     if (rc) return rc;
-    MapStrides strides;
-    rc = check_map_batch(ctx, b, strides);
+    typename Kind::Args l{};
+    rc = check_map_batch<Kind>(ctx, b, l);
     if (rc) return rc;
-    if (!out) return fail(ctx, PS_ERR_BAD_ARG, "ps_map_pairs_device: null output");
+    if (!out) return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null output").c_str());
     if (b->P == 0) return PS_OK;
     if (!out->matches || !out->numMatches || !out->inlierMask || !out->pose || !out->stats)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_map_pairs_device: null output");
+        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null output").c_str());
     if (cfg && cfg->sampleIdx) return fail(ctx, PS_ERR_BAD_ARG, "explicit sample streams are per call, not per batch");
     const int P = b->P, cap = b->maxMatches;
     Plan pl;
@@ -504,9 +572,45 @@ int ps_map_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRa
     rc = prepare_score(ctx, pl, P, cap, false, true, b->maps.desc);
     if (rc) return rc;
     int32_t *clamped = nullptr;
-    rc = run_map_match(ctx, *b, strides, &pl, out->matches, out->numMatches, &clamped, 0);
+    rc = run_map_match<Kind>(ctx, *b, l, &pl, out->matches, out->numMatches, &clamped, 0);
     if (rc) return rc;
     return run_ransac_stage(ctx, pl, P, cap, out->matches, clamped, cap, out->pose, out->inlierMask, out->stats, 2);
+}
+
+struct MapBinKind {
+    using Batch = PsMapBatch;
+    using Args = MapBinArgs;
+    static constexpr const char *what = "map batch";
+    static MapSweeps<Args> sweeps() { return {ps_map_sweep<1>, ps_map_sweep<2>, ps_map_sweep<4>, ps_map_sweep<8>}; }
+    static int sets(PsContext *ctx, const Batch &b, Args &l)
+    {
+        FrameStrides maps, frames;
+        if (int rc = check_frame_set(ctx, b.maps, "map batch: map views", maps)) return rc;
+        if (int rc = check_frame_set(ctx, b.frames, "map batch: frames", frames)) return rc;
+        l.m.mapPtsStride = maps.ptsFloats(); l.m.curPtsStride = frames.ptsFloats();
+        l.mapDesc = (const uint4 *)b.maps.desc; l.curDesc = (const uint4 *)b.frames.desc;
+        l.mapDescStride = maps.descUint4(); l.curDescStride = frames.descUint4();
+        return PS_OK;
+    }
+};
+
+} // namespace
+
+extern "C" {
+
+float ps_map_sphere_bound(double sphereRadius) { return sq_bound_f32(sphereRadius); }
+
+size_t ps_abi_sizeof_map_batch(void) { return sizeof(PsMapBatch); }
+
+int ps_match_xyz_device(PsContext *ctx, const PsMapBatch *b, PsDMatch *matches, int32_t *numMatches)
+{
+    return match_xyz_body<MapBinKind>(ctx, "ps_match_xyz_device", b, matches, numMatches);
+}
+
+int ps_map_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                        const PsMapBatch *b, const PsPairResults *out)
+{
+    return map_pairs_body<MapBinKind>(ctx, "ps_map_pairs_device", params, cfg, K, b, out);
 }
 
 } // extern "C"

@@ -3,6 +3,7 @@ matcher.cpp alone; the oracle and tests/map_l2_ref.py are not consulted here) th
 (ps_match_xyz, ps_match_xyz_l2_f32), the device batches (ps_match_xyz_device, ps_match_xyz_l2_device) at every number of map
 features per wave, and the match rows of ps_map_pairs_device / ps_map_pairs_l2_device."""
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -172,6 +173,57 @@ def test_device_batches_against_the_model(ctx, view_cap, kind):
     total, amb, cand = _check_batch(b, dev.download(), (kind, view_cap))
     print("%s capacity %d (F = %d): %d matches over 64 pairs, %d / %d features ambiguous" % (kind, view_cap, F, total, amb, cand))
     assert total > 5 * view_cap          # (a check of empty rows would say nothing)
+
+
+STASH_ORDERS = ((0, 1, 2), (2, 0, 1))          # 15, 16, 17 candidates (model.scene_stash); 17, 15, 16
+
+
+@functools.lru_cache(maxsize=None)
+def _stash_scene(kind):
+    """model.scene_stash and, per (order, ratio), the model's answer for its three features in that order."""
+    s = model.scene_stash(np.random.default_rng(77), kind)
+    answers = {}
+    for v, order in enumerate(STASH_ORDERS):
+        o = list(order)
+        for ratio in (model.RATIO, 0.1):
+            answers[v, ratio] = model.match_xyz(s["map_pos"][o], s["map_desc"][o], s["map_level"][o], s["cur_pos"], s["cur_desc"],
+                                                s["cur_level"], model.RADIUS, ratio)
+    return s, answers
+
+
+@pytest.mark.parametrize("ratio", [model.RATIO, 0.1])
+@pytest.mark.parametrize("kind", ["binary", 64, 20])
+@pytest.mark.parametrize("view_cap", [130, 260, 520])
+def test_device_batches_sweep_again_beside_stashed_features(ctx, view_cap, kind, ratio):
+    """A feature with more candidates than the stash holds (17: swept again from global memory) beside stashed ones (15, 16) in
+    ONE wave's chain of output offsets and in the offset of the wave behind it, at 2, 4 and 8 map features per wave: 64 identical
+    pairs over one frame of 84 keypoints, the three features in the order 15, 16, 17 and in the order 17, 15, 16."""
+    from putslam_amd.device_batch import run_match_xyz, run_match_xyz_l2
+    s, answers = _stash_scene(kind)
+    ncur = len(s["cur_pos"])
+    assert ncur == 84
+    views = dict(pos=np.zeros((2, view_cap, 3), np.float32), desc=np.zeros((2, view_cap) + s["map_desc"].shape[1:], s["map_desc"].dtype),
+                 level=np.zeros((2, view_cap), np.int32), nkpts=np.array([3, 3], np.int32))
+    for v, order in enumerate(STASH_ORDERS):
+        o = list(order)
+        views["pos"][v, :3], views["desc"][v, :3], views["level"][v, :3] = s["map_pos"][o], s["map_desc"][o], s["map_level"][o]
+    frames = dict(pos=s["cur_pos"][None], desc=s["cur_desc"][None], level=s["cur_level"][None], nkpts=np.array([ncur], np.int32))
+    for v in range(2):
+        ans = answers[v, ratio]
+        assert ans.exact and not ans.ambiguous
+        want = ans.pairs()
+        assert len(want) == (47 if kind == 20 and ratio == model.RATIO else 48)
+        b = dict(views=views, frames=frames, pairs=np.tile(np.array([v, 0], np.int32), (P, 1)), radius=[model.RADIUS] * P,
+                 ratio=[ratio] * P)
+        dev = _device_batch(b, kind, 64)
+        (run_match_xyz if kind == "binary" else run_match_xyz_l2)(ctx, dev)
+        g = dev.download()
+        for p in range(P):
+            n = int(g["numMatches"][p])
+            assert n == len(want), (kind, view_cap, v, p, n)
+            rows = g["matches"][p, :n]
+            model.check(rows, ans, (kind, view_cap, v, p))
+            assert [(int(q), int(t)) for q, t in zip(rows["queryIdx"], rows["trainIdx"])] == want, (kind, view_cap, v, p)
 
 
 @pytest.mark.parametrize("kind", ["binary", 64])
