@@ -803,6 +803,99 @@ int ps_debug_fast_maps(PsContext *ctx, const PsFastDetector *det, int frame, uin
 int ps_debug_fast_passes(PsContext *ctx, PsFastDetector *det, const PsImageSet *images, const PsDetectParams *params, int capacity,
                          float *xy, float *response, int32_t *counts, int passes);
 
+/* ---- ORB descriptor extraction: MatcherOpenCV::describeFeatures, src/Matcher/matcherOpenCV.cpp:183-195, for descriptor = "ORB"
+ * (descriptorExtractor->compute(rgbImage, features, descriptors) with cv::ORB::create()) -- the last per-frame step of
+ * Matcher::detectInitFeatures (matcher.cpp:36), Matcher::match (:467) and Matcher::trackKLT (:338).  The rows are the 32-byte rows
+ * ps_match_hamming256, ps_match_xyz* and the resident map store take.
+ * The arithmetic is the project's reading of OpenCV 3.0 - 3.3's ORB_Impl::detectAndCompute with useProvidedKeypoints = true: orb.cpp,
+ * the 8-bit resize(INTER_LINEAR), the 8-bit separable GaussianBlur and cvtColor (restated twice in
+ * tests/orb_ref.py); no OpenCV build was at hand to pin it against -- the reading is UNPINNED.  ORB's sampling pattern is DATA
+ * here: a host that wants OpenCV's rows passes OpenCV's 256 x 4 table, NULL selects the documented default below.  Everything but
+ * the rotation is integer arithmetic; cvRound rounds half to even; float operations are single IEEE operations:
+ *   grey      1 channel: the image as it is.  3 channels: COLOR_BGR2GRAY, (c0 * 1868 + c1 * 9617 + c2 * 4899 + 8192) >> 14 -- not
+ *             the detector's RGB2GRAY weights: in the reference the same buffer goes through both conversions;
+ *   levels    for l in 0 .. nLevels-1: scale_l = (float)pow((double)scaleFactor, l), rows_l = cvRound((float)rows / scale_l), cols_l
+ *             alike; level 0 is the grey image, level l is resized from level l - 1 (480 x 640, 1.2: 400 x 533, 333 x 444, ...);
+ *   resize    per destination index d of an axis with sn source and dn destination pixels: scale = 1.0 / ((double)dn / sn),
+ *             f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s; columns: s < 0 -> s = 0, f = 0; s >= sn-1 -> s = sn-1,
+ *             f = 0; rows keep f and clamp the indices s, s + 1 to 0 .. sn-1; a0 = cvRound((1.f - f) * 2048.f), a1 =
+ *             cvRound(f * 2048.f).  h = S[s] * a0 + S[min(s+1, sn-1)] * a1 (int), out = (((b0 * (h0 >> 4)) >> 16) +
+ *             ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+ *   blur      7 x 7, sigma 2, integer taps {18, 34, 49, 55, 49, 34, 18} = cvRound(256 g): they sum to 257, which is part of the
+ *             reading (a constant 128 blurs to 129).  Rows first, then columns, in int; out = min(255, (v + 32768) >> 16);
+ *             BORDER_REFLECT_101 of the unblurred level as cv::borderInterpolate does it: a length of 1 gives index 0, else
+ *             p < 0 -> -p, p >= n -> 2n - 2 - p, repeated until inside.  Every level is kept raw and blurred;
+ *   kept      a key point is described iff 31 <= x < cols-31, 31 <= y < rows-31 (float compares, NaN fails; rows or cols <= 62:
+ *             none) and 0 <= octave < nLevels (an extension: OpenCV would index out of bounds).  The kept ones are grouped by
+ *             octave ascending and keep their input order inside an octave (OpenCV's !sortedByLevel branch; what trackKLT
+ *             :302-331 does by hand); keptIdx[j] is the input index of output row j;
+ *   row       s = 1.f / scale_octave; centre (cvRound(x * s), cvRound(y * s)) in that level; (a, b) = (cos, sin) of angle degrees;
+ *             for a pattern point (px, py): ix = cvRound(px * a - py * b), iy = cvRound(px * b + py * a); bit p of the row -- byte
+ *             p >> 3, bit p & 7 -- is v(point 0) < v(point 1) of pair p.  v reads the blurred level where the pixel lies inside the
+ *             level and the RAW level at the REFLECT_101 index where it lies outside (OpenCV blurs a region of an atlas in place:
+ *             the border around the region holds unblurred reflected copies);
+ *   rotation  one fixed float sequence of this library's own (cosf differs between libraries), no fused operation: an angle that is
+ *             not finite or beyond 2^20 in magnitude counts as 0; q = rint(angle * (float)(1 / 90.)), r = angle - q * 90.f (exact),
+ *             k = (int)q & 3, t = r * (float)(pi / 180), u = t * t; S = ((((S9 u + S7) u + S5) u + S3) (t u)) + t and
+ *             C = (((((C10 u + C8) u + C6) u + C4) u + C2) u) + 1.f with Sn, Cn = (float)(+-1 / n!), every product and sum rounded
+ *             on its own; (a, b) = (C, S), (-S, C), (-C, -S), (S, -C) for k = 0 .. 3.  Against float64 cos / sin the absolute
+ *             error stays below 2^-20 (measured: 7.2e-8), so a sample differs from the exact rotation's only where its exact
+ *             coordinate lies within 2^-15 px of a half-integer;
+ *   pattern   256 pairs x (x0, y0, x1, y1) int8, every coordinate in -15 .. 15.  The default: SplitMix64 from state
+ *             0x5055545F4F5242 (add 0x9E3779B97F4A7C15; z ^= z >> 30, z *= 0xBF58476D1CE4E5B9; z ^= z >> 27, z *=
+ *             0x94D049BB133111EB; z ^= z >> 31); per draw u, coordinate i is ((u >> 8i) & 15) + ((u >> (8i + 4)) & 15) - 15; a
+ *             draw whose two points are equal is drawn again.  It starts (11,-7,-5,-7) (-7,0,-2,-1) (-8,-3,5,-8) (-8,0,-12,-6). */
+typedef struct PsOrbParams {
+    float scaleFactor;    /* 1 < scaleFactor <= 2; cv::ORB::create(): 1.2f */
+    int32_t nLevels;      /* 1 .. 8; create(): 8 */
+    int32_t reserved[2];  /* must be 0 */
+} PsOrbParams;
+typedef struct PsOrbPyramids PsOrbPyramids; /* `slots` image pyramids, every level raw and blurred, with the pattern; device resident */
+size_t ps_abi_sizeof_orb_params(void);
+/* The default pattern, 1024 int8 (pure host arithmetic, no context); PS_ERR_BAD_ARG for NULL. */
+int ps_orb_pattern_default(int8_t *out1024);
+
+/* Storage for `slots` (1 .. 65535) pyramids of rows x cols x channels images, the resize coefficients (built once, here) and the
+ * pattern: pattern1024 is a HOST array of 256 x 4 int8, NULL = the default.  A NULL argument, a parameter outside its range, an
+ * empty level, channels other than 1 or 3, a pattern coordinate outside -15 .. 15 -> PS_ERR_BAD_ARG; rows or cols above 8192 ->
+ * PS_ERR_UNSUPPORTED.  Synchronous (allocates).  destroy waits for the device; NULL is harmless. */
+int ps_orb_pyramids_create(PsContext *ctx, int rows, int cols, int channels, const PsOrbParams *params, const int8_t *pattern1024, int slots,
+                           PsOrbPyramids **out);
+void ps_orb_pyramids_destroy(PsOrbPyramids *pyr);
+/* dims2 = {rows, cols} and the scale of one level (either may be NULL); PS_ERR_BAD_ARG for NULL or no such level.  No context. */
+int ps_orb_pyramids_level(const PsOrbPyramids *pyr, int level, int32_t *dims2, float *scale);
+/* Fills slots firstSlot .. firstSlot + images->numFrames - 1 from device-resident images of the set's shape (the PsImageSet the
+ * KLT pyramids and the detector take): one launch per level and pass over all frames.  A shape other than the set's, a stride
+ * below its row / frame or slots outside the set: PS_ERR_BAD_ARG.  Asynchronous on the context's stream. */
+int ps_orb_pyramids_build_device(PsContext *ctx, PsOrbPyramids *pyr, const PsImageSet *images, int firstSlot);
+/* describeFeatures for F frames: frame f's key points are rows 0 .. counts[f]-1 of xy (F x capacity x 2 floats), angle (F x capacity
+ * floats, degrees), octave (F x capacity int32) -- the layout of ps_detect_features_device and ps_klt_select_device -- and are
+ * described in the pyramid of slot slots[f] (two frames may name one slot).  desc F x capacity x 32 bytes, keptIdx F x capacity
+ * int32, numKept F int32; all arrays DEVICE.  Frame f's numKept[f] rows come out in the order above; nothing is written beyond
+ * them.  A frame whose count lies outside 0 .. capacity gets numKept[f] = -1 and nothing else; one that names a slot outside the
+ * set gets numKept[f] = 0 and nothing else.  Two launches: a work-group per frame places the key points, a wavefront per kept key
+ * point writes its row.  NULL where an array is needed, capacity < 1, F outside 0 .. 65535 -> PS_ERR_BAD_ARG; capacity above
+ * PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; F == 0 is PS_OK.  Asynchronous; uses no scratch of the context. */
+int ps_describe_features_device(PsContext *ctx, const PsOrbPyramids *pyr, const int32_t *slots, const float *xy, const float *angle,
+                                const int32_t *octave, const int32_t *counts, int F, int capacity, uint8_t *desc, int32_t *keptIdx,
+                                int32_t *numKept);
+/* describeFeatures for one image: HOST pointers, uploads included, synchronous.  img rows x cols x channels bytes, rowStride bytes
+ * between rows (0 = dense); n key points (n <= PS_MAX_KPTS, else PS_ERR_UNSUPPORTED); desc n x 32 bytes and keptIdx n int32 receive
+ * the *nout kept rows.  Errors as above, outputs untouched. */
+int ps_describe_features(PsContext *ctx, const uint8_t *img, int rows, int cols, int channels, size_t rowStride, const PsOrbParams *params,
+                         const int8_t *pattern1024, const float *xy, const float *angle, const int32_t *octave, int n, uint8_t *desc,
+                         int32_t *keptIdx, int *nout);
+/* Diagnostic (no reference counterpart): the raw and the blurred plane of one level of one slot read back to the HOST, rows_l x
+ * cols_l bytes each (ps_orb_pyramids_level); either may be NULL.  Waits for the context's stream. */
+int ps_debug_orb_level(PsContext *ctx, const PsOrbPyramids *pyr, int slot, int level, uint8_t *raw, uint8_t *blurred);
+/* Diagnostic (no reference counterpart; profiles/scripts/orb_times.py times each pass alone with it): the arguments of
+ * ps_orb_pyramids_build_device and ps_describe_features_device with only the passes of the mask queued -- 1 level 0, 2 the
+ * resizes, 4 the blurs, 8 the placement, 16 the rows.  A pass reads what the passes before it left: call with 31 first.  The
+ * build arguments are checked only if the mask names a build pass, the describe arguments only if it names one of theirs. */
+int ps_debug_orb_passes(PsContext *ctx, PsOrbPyramids *pyr, const PsImageSet *images, int firstSlot, const int32_t *slots, const float *xy,
+                        const float *angle, const int32_t *octave, const int32_t *counts, int F, int capacity, uint8_t *desc, int32_t *keptIdx,
+                        int32_t *numKept, int passes);
+
 /* ---- Loop-closure candidates verified in one batch from the resident store: what the loop-closure thread does per candidate
  * (poseA, poseB) of FABMAP's priority queue -- FeaturesMap::loopClosure (src/Map/featuresMap.cpp:733-873) around
  * Matcher::matchFeatureLoopClosure (src/Matcher/matcher.cpp:802-861) -- for L candidates as two calls, no host step.

@@ -197,6 +197,16 @@ def detect_params(threshold=10, nonmax_suppression=True, grid_rows=1, grid_cols=
                           int(maximal_tracked_features), 0)
 
 
+# ORB descriptor extraction (include/putslam_hip.h)
+class PsOrbParams(C.Structure):
+    _fields_ = [("scaleFactor", C.c_float), ("nLevels", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def orb_params(scale_factor=1.2, n_levels=8):
+    """PsOrbParams; the defaults are cv::ORB::create()'s (scaleFactor 1.2f, 8 levels)."""
+    return PsOrbParams(float(scale_factor), int(n_levels), (C.c_int32 * 2)(0, 0))
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

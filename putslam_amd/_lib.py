@@ -8,7 +8,7 @@ import os
 
 from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch,
                    PsMapBatchF32, PsMapStore, PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPairResults, PsPoseSetOut,
-                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams)
+                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams, PsOrbParams)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -53,6 +53,8 @@ EXPORTED = [
     "ps_abi_sizeof_klt_params", "ps_abi_sizeof_image_set",
     "ps_fast_detector_create", "ps_fast_detector_destroy", "ps_detect_features_device", "ps_detect_features", "ps_debug_fast_maps", "ps_debug_fast_passes",
     "ps_abi_sizeof_detect_params",
+    "ps_orb_pattern_default", "ps_orb_pyramids_create", "ps_orb_pyramids_destroy", "ps_orb_pyramids_level", "ps_orb_pyramids_build_device",
+    "ps_describe_features_device", "ps_describe_features", "ps_debug_orb_level", "ps_debug_orb_passes", "ps_abi_sizeof_orb_params",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -69,6 +71,7 @@ ABI_STRUCTS_STORE_F32 = dict(map_store_f32=PsMapStoreF32, map_view_out_f32=PsMap
 ABI_STRUCTS_KLT = dict(klt_params=PsKltParams, image_set=PsImageSet)
 # ... and of the FAST detector (ps_fast_detector_* / ps_detect_features)
 ABI_STRUCTS_DETECT = dict(detect_params=PsDetectParams)
+ABI_STRUCTS_ORB = dict(orb_params=PsOrbParams)
 
 _lib = None
 _by_path = {}
@@ -276,7 +279,18 @@ def load_path(path):
     L.ps_detect_features.argtypes = [vp, vp, i32, i32, i32, sz, C.POINTER(PsDetectParams), vp, vp, i32, C.POINTER(i32)]
     L.ps_debug_fast_maps.argtypes = [vp, vp, i32, vp, vp, vp]
     L.ps_debug_fast_passes.argtypes = [vp, vp, C.POINTER(PsImageSet), C.POINTER(PsDetectParams), i32, vp, vp, vp, i32]
-    for n in list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT) + list(ABI_STRUCTS_DETECT):
+    L.ps_orb_pattern_default.argtypes = [vp]
+    L.ps_orb_pyramids_create.argtypes = [vp, i32, i32, i32, C.POINTER(PsOrbParams), vp, i32, C.POINTER(vp)]
+    L.ps_orb_pyramids_destroy.argtypes = [vp]
+    L.ps_orb_pyramids_destroy.restype = None
+    L.ps_orb_pyramids_level.argtypes = [vp, i32, vp, C.POINTER(C.c_float)]
+    L.ps_orb_pyramids_build_device.argtypes = [vp, vp, C.POINTER(PsImageSet), i32]
+    L.ps_describe_features_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    L.ps_describe_features.argtypes = [vp, vp, i32, i32, i32, sz, C.POINTER(PsOrbParams), vp, vp, vp, vp, i32, vp, vp, C.POINTER(i32)]
+    L.ps_debug_orb_level.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.ps_debug_orb_passes.argtypes = [vp, vp, C.POINTER(PsImageSet), i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32]
+    for n in (list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT) + list(ABI_STRUCTS_DETECT)
+              + list(ABI_STRUCTS_ORB)):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -300,3 +314,7 @@ def struct_sizes_klt():
 
 def struct_sizes_detect():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_DETECT.items()}
+
+
+def struct_sizes_orb():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_ORB.items()}

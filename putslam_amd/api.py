@@ -12,7 +12,7 @@ from . import _lib
 from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, PS_SET_INVALID, PsExclusionRule, PsFrameSet,  # noqa: F401
                    PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch, PsMapBatchF32, PsPairResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config,
-                   PsImageSet, PsKltParams, klt_params, PsDetectParams, detect_params)
+                   PsImageSet, PsKltParams, klt_params, PsDetectParams, detect_params, PsOrbParams, orb_params)
 
 
 class PsError(RuntimeError):
@@ -575,6 +575,76 @@ class Context:
         maps = [np.zeros((int(rows), int(cols)), np.uint8) for _ in range(3)]
         self._chk(self._L.ps_debug_fast_maps(self._h, det, int(frame), _p(maps[0]), _p(maps[1]), _p(maps[2])))
         return tuple(maps)
+
+    # ---- ORB descriptor extraction (ps_orb.h) ----
+    def describe_features(self, image, xy, angle=None, octave=None, params: PsOrbParams = None, pattern=None):
+        """MatcherOpenCV::describeFeatures for descriptor = "ORB" (ps_describe_features) on a numpy image (rows, cols) or
+        (rows, cols, 3) uint8 whose rows may lie any stride apart.  xy (n, 2) float32; angle (n,) degrees, default -1 (what the FAST
+        detector leaves); octave (n,) int32, default 0.  params: _abi.orb_params(...), default cv::ORB::create()'s; pattern (256, 4)
+        int8 in -15 .. 15, default the library's.  Returns (desc (k, 32) uint8, kept_idx (k,) int32): the described key points
+        grouped by octave, input order inside an octave; kept_idx[j] is the input index of row j."""
+        params = params or orb_params()
+        image = np.asarray(image, np.uint8)
+        assert image.ndim in (2, 3)
+        cn = 1 if image.ndim == 2 else image.shape[2]
+        dense = image.shape[1] * cn
+        if not (image.strides[0] >= dense and (image.ndim == 2 and image.strides[1] == 1 or image.ndim == 3 and image.strides[1:] == (cn, 1))):
+            image = np.ascontiguousarray(image)
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        n = xy.shape[0]
+        angle = np.full(n, -1.0, np.float32) if angle is None else np.ascontiguousarray(angle, np.float32).reshape(n)
+        octave = np.zeros(n, np.int32) if octave is None else np.ascontiguousarray(octave, np.int32).reshape(n)
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8).reshape(1024)
+        desc, kept = np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.int32)
+        k = C.c_int(0)
+        self._chk(self._L.ps_describe_features(self._h, _p(image), image.shape[0], image.shape[1], cn, image.strides[0], C.byref(params),
+                                               None if pat is None else _p(pat), _p(xy), _p(angle), _p(octave), n, _p(desc), _p(kept),
+                                               C.byref(k)))
+        return desc[:k.value].copy(), kept[:k.value].copy()
+
+    def orb_pyramids_create(self, rows, cols, channels, params: PsOrbParams, pattern, slots):
+        """ps_orb_pyramids_create: the handle of a device-resident pyramid set (device_batch.OrbPyramids owns one)."""
+        h = C.c_void_p()
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8).reshape(1024)
+        self._chk(self._L.ps_orb_pyramids_create(self._h, int(rows), int(cols), int(channels), C.byref(params),
+                                                 None if pat is None else _p(pat), int(slots), C.byref(h)))
+        return h
+
+    def orb_pyramids_build_device(self, pyr, images: PsImageSet, first_slot=0):
+        self._chk(self._L.ps_orb_pyramids_build_device(self._h, pyr, C.byref(images), int(first_slot)))
+
+    def describe_features_device(self, pyr, slots_ptr, xy_ptr, angle_ptr, octave_ptr, counts_ptr, F, capacity, desc_ptr, kept_idx_ptr,
+                                 num_kept_ptr, passes=31):
+        """ps_describe_features_device on device pointers (asynchronous on the context's stream): device_batch.describe_features_batch.
+        passes other than 31: ps_debug_orb_passes, only the placement (8) or the rows (16), for timing."""
+        if passes == 31:
+            self._chk(self._L.ps_describe_features_device(self._h, pyr, _v(slots_ptr), _v(xy_ptr), _v(angle_ptr), _v(octave_ptr),
+                                                          _v(counts_ptr), int(F), int(capacity), _v(desc_ptr), _v(kept_idx_ptr),
+                                                          _v(num_kept_ptr)))
+        else:
+            self._chk(self._L.ps_debug_orb_passes(self._h, pyr, None, 0, _v(slots_ptr), _v(xy_ptr), _v(angle_ptr), _v(octave_ptr),
+                                                  _v(counts_ptr), int(F), int(capacity), _v(desc_ptr), _v(kept_idx_ptr), _v(num_kept_ptr),
+                                                  int(passes) & 24))
+
+    def debug_orb_passes_build(self, pyr, images: PsImageSet, first_slot, passes):
+        """ps_debug_orb_passes with a build mask alone: 1 level 0, 2 the resizes, 4 the blurs (timing scripts)."""
+        self._chk(self._L.ps_debug_orb_passes(self._h, pyr, C.byref(images), int(first_slot), None, None, None, None, None, 0, 0, None, None,
+                                              None, int(passes) & 7))
+
+    def orb_pyramids_level(self, pyr, level):
+        """ps_orb_pyramids_level: ((rows, cols), scale float32) of one level."""
+        dims, scale = np.zeros(2, np.int32), C.c_float(0)
+        rc = self._L.ps_orb_pyramids_level(pyr, int(level), _p(dims), C.byref(scale))
+        if rc != PS_OK:
+            raise ValueError("ps_orb_pyramids_level: no such level")
+        return (int(dims[0]), int(dims[1])), np.float32(scale.value)
+
+    def debug_orb_level(self, pyr, slot, level):
+        """ps_debug_orb_level: (raw, blurred) of one level of one slot, (rows_l, cols_l) uint8 each."""
+        (r, c), _ = self.orb_pyramids_level(pyr, level)
+        raw, blr = np.zeros((r, c), np.uint8), np.zeros((r, c), np.uint8)
+        self._chk(self._L.ps_debug_orb_level(self._h, pyr, int(slot), int(level), _p(raw), _p(blr)))
+        return raw, blr
 
     def points3Dto2D(self, xyz, K):
         xyz = np.ascontiguousarray(xyz, np.float32)

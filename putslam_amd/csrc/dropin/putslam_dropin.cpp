@@ -1272,6 +1272,60 @@ std::vector<cv::KeyPoint> detectFeaturesFAST(const FrameMatcher::MatcherParamete
     return keypoints;
 }
 
+cv::Mat FrameMatcherHIP::describeFeatures(cv::Mat rgbImage, std::vector<cv::KeyPoint> &features)
+{
+    return describeFeaturesORB(matcherParameters, rgbImage, features);
+}
+
+// MatcherOpenCV::describeFeatures, matcherOpenCV.cpp:183-195, for the extractor cv::ORB::create()
+cv::Mat describeFeaturesORB(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat rgbImage, std::vector<cv::KeyPoint> &features)
+{
+    const std::vector<cv::KeyPoint> in = features;
+    features.clear();
+    const auto &cvp = matcherParameters.OpenCVParams;
+    if (cvp.descriptor != "ORB") {
+        std::cerr << "putslam_hip: describeFeatures runs descriptor \"ORB\" only (asked for \"" << cvp.descriptor
+                  << "\"): no descriptors; SURF / SIFT description stays with OpenCV on the host" << std::endl;
+        return cv::Mat();
+    }
+    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3)) {
+        std::cerr << "putslam_hip: describeFeatures takes a CV_8UC1 or CV_8UC3 image" << std::endl;
+        return cv::Mat();
+    }
+    if (in.empty()) return cv::Mat();
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return cv::Mat();
+    PsOrbParams prm;
+    prm.scaleFactor = 1.2f; // cv::ORB::create()'s defaults
+    prm.nLevels = 8;
+    prm.reserved[0] = prm.reserved[1] = 0;
+    const size_t n = in.size();
+    std::vector<cv::Point2f> xy(n);
+    std::vector<float> angle(n);
+    std::vector<int32_t> octave(n), keptIdx(n);
+    for (size_t i = 0; i < n; ++i) {
+        xy[i] = in[i].pt;
+        angle[i] = in[i].angle;
+        octave[i] = in[i].octave;
+    }
+    std::vector<unsigned char> rows(n * 32);
+    int k = 0;
+    status = ps_describe_features(ctx, rgbImage.data, rgbImage.rows, rgbImage.cols, rgbImage.channels(), (size_t)rgbImage.step, &prm, nullptr,
+                                  reinterpret_cast<const float *>(xy.data()), angle.data(), octave.data(), (int)n, rows.data(), keptIdx.data(),
+                                  &k);
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        return cv::Mat();
+    }
+    if (k == 0) return cv::Mat();
+    cv::Mat descriptors(k, 32, CV_8U);
+    std::memcpy(descriptors.data, rows.data(), (size_t)k * 32);
+    features.resize((size_t)k);
+    for (int j = 0; j < k; ++j) features[(size_t)j] = in[(size_t)keptIdx[(size_t)j]];
+    return descriptors;
+}
+
 // MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) with the matcher of matcherOpenCV.cpp:100-102, cv::BFMatcher(cv::NORM_L2,
 // true), on CV_32F descriptor Mats of 1 .. PS_MAX_L2_DIM columns (ps_match_l2_f32).
 std::vector<cv::DMatch> l2CrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors)

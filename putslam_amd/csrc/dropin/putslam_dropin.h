@@ -203,6 +203,8 @@ class FrameMatcher {
             std::string detector = "ORB";
             int gridRows = 1, gridCols = 1;
             int maximalTrackedFeatures = 500;
+            // the descriptor's name (matcher.h:40; putslammatcherOpenCVParameters.xml:64): describeFeatures below runs "ORB"
+            std::string descriptor = "ORB";
         } OpenCVParams;
         MatcherParameters();
     };
@@ -381,6 +383,16 @@ std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &m
 // Any other detector (ORB, SURF, SIFT) is NOT run on the CPU instead: one line goes to std::cerr and the list comes back empty.
 std::vector<cv::KeyPoint> detectFeaturesFAST(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat rgbImage);
 
+// MatcherOpenCV::describeFeatures (matcherOpenCV.cpp:183-195) for OpenCVParams.descriptor == "ORB" (cv::ORB::create(): scaleFactor
+// 1.2f, 8 levels) as a free function over the calling thread's context (ps_describe_features): descriptorExtractor->compute(rgbImage,
+// features, descriptors) in the project's reading of OpenCV 3.0 - 3.3 (include/putslam_hip.h) with the library's default sampling
+// pattern -- a host that needs OpenCV's own rows calls ps_describe_features with OpenCV's table.  rgbImage: CV_8UC1 or CV_8UC3, any
+// step.  Returns an n x 32 CV_8U Mat and REPLACES `features` by the described key points in the rows' order, as OpenCV does: those
+// 31 pixels inside the image, grouped by octave, input order inside an octave.
+// Any other descriptor (SURF, SIFT) is NOT run on the CPU instead: one line goes to std::cerr, the Mat comes back empty and
+// `features` is cleared.
+cv::Mat describeFeaturesORB(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat rgbImage, std::vector<cv::KeyPoint> &features);
+
 // Library-owned singletons with the reference factories' ownership rules (raw pointer returned, a second call
 // replaces the instance: matcherOpenCV.cpp:20-47): one for the VO thread, one for the loop-closure thread.
 FrameMatcher *createFrameMatcher(void);
@@ -415,6 +427,8 @@ class FrameMatcherHIP : public FrameMatcher {
                                                     std::vector<double> &detDists);
     // MatcherOpenCV::detectFeatures, matcherOpenCV.cpp:118-180 (the reference's signature; detectFeaturesFAST above)
     virtual std::vector<cv::KeyPoint> detectFeatures(cv::Mat rgbImage);
+    // MatcherOpenCV::describeFeatures, matcherOpenCV.cpp:183-195 (the reference's signature; describeFeaturesORB above)
+    virtual cv::Mat describeFeatures(cv::Mat rgbImage, std::vector<cv::KeyPoint> &features);
 };
 
 } // namespace putslam_hip

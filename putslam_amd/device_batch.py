@@ -9,7 +9,7 @@ import torch
 from . import api
 from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
-                   make_config, PsImageSet, klt_params, detect_params)
+                   make_config, PsImageSet, klt_params, detect_params, orb_params)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -451,6 +451,72 @@ def detect_features_batch(ctx, det: FastDetector, images, params=None, capacity=
     args = (det.handle, s, params, cap, xy.data_ptr(), response.data_ptr(), counts.data_ptr(), passes)
     _on_torch_stream(ctx, dev, lambda: ctx.detect_features_device(*args), use_torch_stream)
     return xy, response, counts
+
+
+class OrbPyramids:
+    """A device-resident set of `slots` ORB pyramids (ps_orb_pyramids_create): every level raw and blurred, with the sampling
+    pattern -- (256, 4) int8 in -15 .. 15, default the library's.  params: _abi.orb_params(...), default cv::ORB::create()'s."""
+
+    def __init__(self, ctx, rows, cols, channels, slots, params=None, pattern=None):
+        self.ctx, self.rows, self.cols, self.channels, self.slots = ctx, int(rows), int(cols), int(channels), int(slots)
+        self.params = params or orb_params()
+        self.num_levels = int(self.params.nLevels)
+        self.handle = ctx.orb_pyramids_create(rows, cols, channels, self.params, pattern, slots)
+
+    def close(self):
+        if self.handle is not None:
+            self.ctx._L.ps_orb_pyramids_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def build(self, images, first_slot=0, use_torch_stream=True, passes=7):
+        """Fills slots first_slot .. from `images`: a uint8 device tensor (F, rows, cols[, channels]), the tensor KltPyramids.build
+        and detect_features_batch take.  Asynchronous, ordered like run_pairs.  passes: 7, or the build mask of
+        ps_debug_orb_passes (timing scripts)."""
+        s = _image_set(images, self.rows, self.cols, self.channels)
+        call = ((lambda: self.ctx.orb_pyramids_build_device(self.handle, s, first_slot)) if passes == 7 else
+                (lambda: self.ctx.debug_orb_passes_build(self.handle, s, first_slot, passes)))
+        _on_torch_stream(self.ctx, images.device, call, use_torch_stream)
+
+    def level(self, level):
+        """((rows, cols), scale float32) of one level (ps_orb_pyramids_level)."""
+        return self.ctx.orb_pyramids_level(self.handle, level)
+
+    def planes(self, slot, level):
+        """(raw, blurred) of one level of one slot, on the host (api.Context.debug_orb_level)."""
+        return self.ctx.debug_orb_level(self.handle, slot, level)
+
+
+def describe_features_batch(ctx, pyr: OrbPyramids, slots, xy, angle, octave, counts, desc=None, kept_idx=None, num_kept=None,
+                            use_torch_stream=True, passes=31):
+    """MatcherOpenCV::describeFeatures (descriptor = "ORB") for F frames (ps_describe_features_device): slots (F,) int32 -- the
+    slot of `pyr` each frame is described in --, xy (F, cap, 2) float32, angle (F, cap) float32 degrees, octave (F, cap) int32,
+    counts (F,) int32: torch tensors on the context's device, the layout detect_features_batch returns.  desc (F, cap, 32) uint8 /
+    kept_idx (F, cap) int32 / num_kept (F,) int32: blocks to write into (default: new ones).  Returns (desc, kept_idx, num_kept),
+    written asynchronously: frame f's first num_kept[f] rows, grouped by octave, nothing beyond them (-1: a count outside
+    0 .. cap).  desc drops into the binary frame sets."""
+    F, cap = xy.shape[0], xy.shape[1]
+    dev = xy.device
+    assert xy.dtype == torch.float32 and xy.shape == (F, cap, 2) and xy.is_contiguous()
+    assert angle.dtype == torch.float32 and angle.shape == (F, cap) and angle.is_contiguous()
+    assert octave.dtype == torch.int32 and octave.shape == (F, cap) and octave.is_contiguous()
+    for t in (slots, counts):
+        assert t.dtype == torch.int32 and t.shape == (F,) and t.is_contiguous()
+    desc = _zeros(dev, (F, cap, 32), torch.uint8) if desc is None else desc
+    kept_idx = _zeros(dev, (F, cap), torch.int32) if kept_idx is None else kept_idx
+    num_kept = _zeros(dev, (F,), torch.int32) if num_kept is None else num_kept
+    assert desc.dtype == torch.uint8 and desc.shape == (F, cap, 32) and desc.is_contiguous()
+    assert kept_idx.dtype == torch.int32 and kept_idx.shape == (F, cap) and kept_idx.is_contiguous()
+    assert num_kept.dtype == torch.int32 and num_kept.shape == (F,) and num_kept.is_contiguous()
+    args = (pyr.handle, slots.data_ptr(), xy.data_ptr(), angle.data_ptr(), octave.data_ptr(), counts.data_ptr(), F, cap, desc.data_ptr(),
+            kept_idx.data_ptr(), num_kept.data_ptr(), passes)
+    _on_torch_stream(ctx, dev, lambda: ctx.describe_features_device(*args), use_torch_stream)
+    return desc, kept_idx, num_kept
 
 
 class MapBatchDevice(PairResultsDevice):
