@@ -45,7 +45,7 @@ EXPORTED = [
     "ps_abi_sizeof_map_store", "ps_abi_sizeof_map_view_request", "ps_abi_sizeof_map_view_out",
     "ps_pose_sets_device", "ps_loop_pairs_device",
     "ps_abi_sizeof_pose_set_request", "ps_abi_sizeof_pose_set_out", "ps_abi_sizeof_loop_batch", "ps_abi_sizeof_loop_results",    "ps_match_l2_f32", "ps_match_l2_device", "ps_vo_pairs_l2_device", "ps_abi_sizeof_frameset_f32", "ps_debug_l2_band",
-    "ps_debug_l2_stats",
+    "ps_debug_l2_stats", "ps_match_xyz_l2_f32", "ps_match_xyz_l2_device", "ps_map_pairs_l2_device", "ps_abi_sizeof_map_batch_f32",
     "ps_map_views_l2_device", "ps_pose_sets_l2_device", "ps_loop_pairs_l2_device",
     "ps_abi_sizeof_map_store_f32", "ps_abi_sizeof_map_view_out_f32", "ps_abi_sizeof_pose_set_out_f32", "ps_abi_sizeof_loop_batch_f32",
     "ps_klt_pyramids_create", "ps_klt_pyramids_destroy", "ps_klt_pyramids_num_levels", "ps_klt_pyramids_build_device",

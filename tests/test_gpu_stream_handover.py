@@ -1,38 +1,98 @@
 """The hand-over of a library call onto torch's current stream (device_batch._on_torch_stream) keeps torch's ORDER, not only
 the results: a torch op queued just before the call writes the inputs' final values, a torch copy queued just after it reads the
 outputs, nothing synchronises the host in between, and the copy must hold what a fully synchronised run computes -- from torch's
-default stream (handle 0: forked to and joined from the side stream) and from an explicit stream (handed over as it is)."""
+default stream (handle 0: forked to and joined from the side stream) and from an explicit stream (handed over as it is).
+
+Four entry points have tests of their own below; then every asynchronous entry point runs its case of tests/stream_order_cases.py
+the same way, pairs of calls run across a ps_context_set_stream while the first stream is still busy, and the front-end chain
+detect -> thin -> gather -> describe -> track -> select is queued without a host step."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
-from putslam_amd import synth
-from putslam_amd._abi import EST_FIXED, EUCLIDEAN_ERROR, TUM_FR1_K, default_ransac_params, make_config
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import stream_order_cases as S  # noqa: E402
+
+from putslam_amd import synth  # noqa: E402
+from putslam_amd._abi import EST_FIXED, EUCLIDEAN_ERROR, TUM_FR1_K, default_ransac_params, make_config  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 CAP, NK = 64, [40, 64]
 
 
+BALLAST_BYTES, BALLAST_FILLS = 1 << 30, 64
+
+
+@pytest.fixture(scope="module")
+def ballast():
+    import torch
+    return torch.empty(BALLAST_BYTES, dtype=torch.uint8, device="cuda:0")
+
+
+def _busy(ballast, times=1):
+    """times x BALLAST_FILLS fills of the ballast on torch's current stream and an event behind them: while event.query() is False
+    the stream is still busy with them, so whatever was queued behind is pending.  Returns (event, event in front of the fills).
+
+    Measured on the MI355X (every run prints both figures, _report): 64 fills of 1 GiB take 9.9 - 10.0 ms between the two events.
+    Queuing on the host (perf_counter around the call) takes 0.02 - 0.11 ms for a single entry point -- the slowest is the case of
+    ps_orb_pyramids_build_device, a build and a describe --, up to 0.29 ms for the two calls and two ps_context_set_stream of a
+    switch pair, and 0.52 - 0.70 ms for the whole front-end chain, the slowest thing queued here.  The ballast is 14 times that,
+    where 4 times is asked for as the margin for a busy host; the four fills of 256 MiB this file used before come to about
+    0.16 ms at that rate (not measured), no more than two single calls and a quarter of the chain."""
+    import torch
+    first, last = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    first.record()
+    for _ in range(times * BALLAST_FILLS):
+        ballast.fill_(1)
+    last.record()
+    return last, first
+
+
+def _report(what, first, last, host_seconds):
+    print("%s: queued in %.3f ms on the host, ballast %.3f ms" % (what, host_seconds * 1e3, first.elapsed_time(last)))
+
+
 @pytest.fixture(params=["default", "side"])
-def ordered(request, ctx):
-    """ordered(inputs, finals, call, outputs) -> clones of outputs(), taken on the stream under test behind call(), which runs
-    behind the copies finals -> inputs; the stream is busy before them, so that they are still pending when call() is made."""
+def ordered(request, ctx, ballast):
+    """ordered(inputs, finals, call, outputs, drains=False) -> clones of outputs(), taken on the stream under test behind call(),
+    which runs behind the copies finals -> inputs; the stream is busy before them (_busy), so that they are still pending when
+    call() is made -- and that is checked: the event behind the ballast, read on the host right after call() returns, must not
+    have happened ("ballast too short": the run proved nothing).  drains=True, a wrapper that synchronises the host before it
+    queues: the event must have happened, so a host synchronisation is where the table says and nowhere else."""
+    import time
     import torch
     stream = torch.cuda.Stream() if request.param == "side" else torch.cuda.default_stream()
-    ballast = torch.empty(256 << 20, dtype=torch.uint8, device="cuda:0")
 
-    def run(inputs, finals, call, outputs):
+    def run(inputs, finals, call, outputs, drains=False):
         torch.cuda.synchronize()
+        if drains and request.param == "default":
+            # the wrapper's synchronisation drains the default stream and leaves the side stream the call runs on idle, so a
+            # missing join would go unnoticed: that stream is kept busy by a ballast of its own, three times as long (the two
+            # run side by side and share the memory's bandwidth)
+            from putslam_amd.device_batch import _work_stream
+            with torch.cuda.stream(_work_stream(torch.device("cuda:0"))):
+                _busy(ballast, 3)
         with torch.cuda.stream(stream):
-            for _ in range(4):
-                ballast.fill_(1)
+            busy, first = _busy(ballast)
             for t, f in zip(inputs, finals):
                 t.copy_(f)
+            t0 = time.perf_counter()
             call()
+            t1 = time.perf_counter()
+            drained = busy.query()
             got = [t.clone() for t in outputs()]
         torch.cuda.synchronize()
+        _report(request.node.name, first, busy, t1 - t0)
+        if drains:
+            assert drained, "the wrapper no longer synchronises the host before it queues: correct the table's `drains`"
+        else:
+            assert not drained, "ballast too short (or the wrapper synchronised the host): the stream was idle when the call was queued"
         return got
 
+    run.stream = stream
     yield run
     ctx.set_stream(0)
 
@@ -137,3 +197,184 @@ def test_run_match_xyz(ctx, ordered):
     got = ordered([t for s in late for t in (s.desc, s.pts, s.nkpts)], [t for s in (views, frames) for t in (s.desc, s.pts, s.nkpts)],
                   lambda: run_match_xyz(ctx, out), lambda: [out.matches, out.num_matches])
     _check(got, [ref.matches, ref.num_matches])
+
+
+# ---------------------------------------------------------------- every asynchronous entry point, from the table
+def _want(ctx, name, k):
+    """What case k of an entry point computes with everything synchronised before and after the call.  Made anew in front of every
+    run under test, not kept: the call also leaves the context as the run under test must find it -- the scratch arena grown to
+    the case's size and the RANSAC stop table that of the case's parameters, for a call that has to grow the one or rebuild the
+    other drains its stream first, as it should, and would read here as a host synchronisation in the wrapper."""
+    import torch
+    case = S.TABLE[name].prep(k, ctx)
+    for t, f in zip(case.inputs, case.finals):
+        t.copy_(f)
+    torch.cuda.synchronize()
+    case.call(ctx)
+    torch.cuda.synchronize()
+    assert bool((case.counts() > 0).all()), (name, k, case.counts())          # the expected run did something
+    want = case.norm([t.clone() for t in case.outputs()])
+    torch.cuda.synchronize()
+    ctx.set_stream(0)
+    return want
+
+
+def _differ(a, b):
+    import torch
+    return any(not torch.equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("name", sorted(S.TABLE))
+def test_entry_point_keeps_the_order_of_torchs_stream(ctx, ordered, name):
+    import torch
+    entry = S.TABLE[name]
+    want = _want(ctx, name, 0)
+    case = entry.prep(0, ctx)
+    torch.cuda.synchronize()
+    got = ordered(case.inputs, case.finals, lambda: case.call(ctx), case.outputs, entry.drains)
+    _check(case.norm(got), want)
+
+
+# ---------------------------------------------------------------- across a stream switch, the first stream busy
+def _switch(ctx, ballast, first, second):
+    """first() on stream A behind the ballast, ps_context_set_stream to stream B with no synchronisation, second(); A must still
+    be busy when second() has been queued.  The contexts' calls are made directly (direct=True): no wrapper chooses a stream."""
+    import time
+    import torch
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(a):
+        busy, start = _busy(ballast)
+    t0 = time.perf_counter()
+    ctx.set_stream(a.cuda_stream)
+    first()
+    ctx.set_stream(b.cuda_stream)
+    second()
+    t1 = time.perf_counter()
+    drained = busy.query()
+    torch.cuda.synchronize()
+    ctx.set_stream(0)
+    _report("switch", start, busy, t1 - t0)
+    assert not drained, "ballast too short: stream A was idle at the switch"
+
+
+def _filled(case):
+    import torch
+    for t, f in zip(case.inputs, case.finals):
+        t.copy_(f)
+    torch.cuda.synchronize()
+    return case
+
+
+def _outputs(case):
+    return case.norm([t.clone() for t in case.outputs()])
+
+
+SAME_CALL = ["ps_match_l2_device", "ps_vo_pairs_l2_device", "ps_match_xyz_l2_device", "ps_map_pairs_l2_device", "ps_map_views_l2_device",
+             "ps_pose_sets_device", "ps_pose_sets_l2_device", "ps_loop_pairs_device", "ps_loop_pairs_l2_device", "ps_klt_select_device",
+             "ps_detect_features_device"]
+
+
+@pytest.mark.parametrize("name", SAME_CALL)
+def test_same_call_on_two_streams_with_the_first_busy(ctx, ballast, name):
+    """Inputs 0 on stream A, inputs 1 on stream B: both results are those of two separate synchronised calls.  The two
+    ps_detect_features_device calls share ONE detector (its maps and ROI lists): the first call's outputs must not hold the second
+    image's key points."""
+    want = [_want(ctx, name, 0), _want(ctx, name, 1)]
+    assert _differ(want[0], want[1])
+    prep = S.TABLE[name].prep
+    one = _filled(prep(0, ctx))
+    two = _filled(prep(1, ctx, share=one) if name == "ps_detect_features_device" else prep(1, ctx))
+    _switch(ctx, ballast, lambda: one.call(ctx, direct=True), lambda: two.call(ctx, direct=True))
+    _check(_outputs(one), want[0])
+    _check(_outputs(two), want[1])
+
+
+@pytest.mark.parametrize("name", ["ps_klt_pyramids_build_device", "ps_orb_pyramids_build_device"])
+def test_build_on_one_stream_then_its_reader_on_another(ctx, ballast, name):
+    """Read after write on the slots of a pyramid set, which belong to the set and not to a stream."""
+    want = _want(ctx, name, 0)
+    case = _filled(S.TABLE[name].prep(0, ctx))
+    _switch(ctx, ballast, lambda: case.build(ctx, direct=True), lambda: case.read(ctx, direct=True))
+    _check(_outputs(case), want)
+
+
+@pytest.mark.parametrize("name", ["ps_klt_track_device", "ps_describe_features_device"])
+def test_rebuild_on_another_stream_while_a_reader_is_queued(ctx, ballast, name):
+    """Write after read: a track / describe of the slots' content queued on stream A, the same slots built again from other images
+    on stream B.  The reader's result is the old content's; the same reader afterwards sees the new content."""
+    import torch
+    want = _want(ctx, name, 0)
+    case = _filled(S.TABLE[name].prep(0, ctx))
+    _switch(ctx, ballast, lambda: case.call(ctx, direct=True), lambda: case.rebuild(ctx, direct=True))
+    _check(_outputs(case), want)
+    case.call(ctx)
+    torch.cuda.synchronize()
+    ctx.set_stream(0)
+    assert _differ(_outputs(case), want)
+
+
+# ---------------------------------------------------------------- the front-end chain, queued without a host step
+@pytest.fixture(scope="module")
+def chain(ctx):
+    c = S.ChainDevice(ctx)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def chain_stepwise(ctx, chain):
+    """The chain with torch.cuda.synchronize() after every step, on the real images."""
+    import torch
+    images = torch.from_numpy(np.stack(S.chain_images())).to("cuda:0")
+    torch.cuda.synchronize()
+    out = chain.run(images, torch.cuda.synchronize)
+    torch.cuda.synchronize()
+    ctx.set_stream(0)
+    return {k: t.cpu().numpy() for k, t in out.items()}
+
+
+def test_chain_stepwise_equals_the_restatements_chained(chain_stepwise):
+    g, ref, want = chain_stepwise, S.chain_reference(), S.CHAIN_COUNTS
+    assert g["counts"].tolist() == want["detected"] and g["nkept"].tolist() == want["thinned"] and g["dnum"].tolist() == want["described"]
+    for f, r in enumerate(ref["frames"]):
+        n, m, d = len(r["xy"]), len(r["keep"]), len(r["kept"])
+        assert g["xy"][f, :n].tobytes() == r["xy"].tobytes() and g["response"][f, :n].tobytes() == r["response"].tobytes(), f
+        assert g["kept"][f, :m].tolist() == r["keep"].tolist() and g["kxy"][f, :m].tobytes() == r["kxy"].tobytes(), f
+        assert g["dkept"][f, :d].tolist() == r["kept"].tolist() and g["desc"][f, :d].tobytes() == r["desc"].tobytes(), f
+    m = want["thinned"][0]
+    assert g["next"][0, :m].tobytes() == np.ascontiguousarray(ref["next"], np.float32).tobytes()
+    assert g["status"][0, :m].tolist() == ref["status"].tolist() and int(g["status"].sum()) == want["tracked"]
+    assert g["err"][0, :m].tobytes() == np.ascontiguousarray(ref["err"], np.float32).tobytes()
+    s = want["selected"]
+    assert int(g["num"][0]) == s and g["sidx"][0, :s].tolist() == ref["selected"].tolist()
+    assert g["matches"][0, :s, :3].tolist() == ref["matches"].tolist()
+    assert g["spts"][0, :s].tobytes() == np.ascontiguousarray(ref["next"], np.float32)[ref["selected"]].tobytes()
+
+
+@pytest.mark.parametrize("where", ["default", "side"])
+def test_chain_queued_without_a_host_step(ctx, ballast, chain, chain_stepwise, where):
+    """The images arrive by a copy queued behind the ballast (stale: zero images, nothing detected); every link is queued while
+    the stream is still busy with the ballast, a torch gather stands between two library calls, and the clones equal the stepwise
+    run's, byte for byte."""
+    import time
+    import torch
+    stream = torch.cuda.Stream() if where == "side" else torch.cuda.default_stream()
+    final = torch.from_numpy(np.stack(S.chain_images())).to("cuda:0")
+    images = torch.zeros_like(final)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(stream):
+        busy, start = _busy(ballast)
+        images.copy_(final)
+        t0 = time.perf_counter()
+        out = chain.run(images)
+        t1 = time.perf_counter()
+        drained = busy.query()
+    torch.cuda.synchronize()
+    ctx.set_stream(0)
+    _report("chain/" + where, start, busy, t1 - t0)
+    assert not drained, "ballast too short: the stream was idle before the chain was queued"
+    got = {k: t.cpu().numpy() for k, t in out.items()}
+    assert got["counts"].tolist() == S.CHAIN_COUNTS["detected"] and int(got["num"][0]) == S.CHAIN_COUNTS["selected"]
+    for k, w in chain_stepwise.items():
+        assert got[k].tobytes() == w.tobytes(), k
