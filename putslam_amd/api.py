@@ -30,6 +30,19 @@ def _v(ptr):
     return C.c_void_p(ptr or None)
 
 
+def _host_image(a):
+    """(image, channels) as the host forms of the image front end take one: (rows, cols) or (rows, cols, channels) uint8 whose rows
+    may lie any stride apart (a region of a larger image) while a row itself is dense -- used where it lies; anything else is
+    copied into a dense uint8 array."""
+    a = np.asarray(a, np.uint8)
+    assert a.ndim in (2, 3)
+    cn = 1 if a.ndim == 2 else a.shape[2]
+    dense = a.shape[1] * cn
+    if not (a.strides[0] >= dense and (a.ndim == 2 and a.strides[1] == 1 or a.ndim == 3 and a.strides[1:] == (cn, 1))):
+        a = np.ascontiguousarray(a)
+    return a, cn
+
+
 def retry_with_reported_capacity(run, cap, limit=None):
     """run(cap) -> (result, rows needed): the convention of the device batches, whose negative counts report the rows an
     overflowed output wanted.  If more were needed than `cap` (at most `limit`, if given), run is repeated ONCE with that
@@ -446,36 +459,29 @@ class Context:
                                             int(exist_capacity), int(frames), _v(kept_ptr), _v(nkept_ptr)))
 
     # ---- pyramidal Lucas-Kanade tracking (ps_klt.h) ----
-    @staticmethod
-    def _klt_images(prev_img, next_img):
-        prev_img, next_img = np.asarray(prev_img, np.uint8), np.asarray(next_img, np.uint8)
-        assert prev_img.shape == next_img.shape and prev_img.ndim in (2, 3)
-        cn = 1 if prev_img.ndim == 2 else prev_img.shape[2]
-
-        def rows_of(a):   # rows may lie any stride apart (a region of a larger image); a row itself is dense
-            dense = a.shape[1] * cn
-            ok = a.strides[0] >= dense and (a.ndim == 2 and a.strides[1] == 1 or a.ndim == 3 and a.strides[1:] == (cn, 1))
-            return a if ok else np.ascontiguousarray(a)
-        prev_img, next_img = rows_of(prev_img), rows_of(next_img)
-        if next_img.strides[0] != prev_img.strides[0]:
+    def _klt_pair(self, prev_img, next_img, prev_pts, params, next_pts):
+        """The shared opening of the two host forms: (params, the ten leading arguments of either call, n, and next_pts / status /
+        err of max(n, 1) rows, next_pts holding the initial flow if one was given)."""
+        params = params or klt_params()
+        (prev_img, cn), (next_img, _) = _host_image(prev_img), _host_image(next_img)
+        assert prev_img.shape == next_img.shape
+        if next_img.strides[0] != prev_img.strides[0]:   # (the call takes one row stride for both)
             prev_img, next_img = np.ascontiguousarray(prev_img), np.ascontiguousarray(next_img)
-        return prev_img, next_img, cn
+        prev_pts = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
+        n = prev_pts.shape[0]
+        m = max(n, 1)
+        nxt = np.zeros((m, 2), np.float32)
+        if next_pts is not None:
+            nxt[:n] = np.asarray(next_pts, np.float32).reshape(n, 2)
+        head = (self._h, _p(prev_img), _p(next_img), prev_img.shape[0], prev_img.shape[1], cn, prev_img.strides[0], _p(prev_pts), _p(nxt), n)
+        return params, head, n, nxt, np.zeros(m, np.uint8), np.zeros(m, np.float32)
 
     def calc_optical_flow_pyr_lk(self, prev_img, next_img, prev_pts, params: PsKltParams = None, next_pts=None):
         """cv::calcOpticalFlowPyrLK (ps_calc_optical_flow_pyr_lk) on numpy arrays: images (rows, cols) or (rows, cols, 3) uint8,
         prev_pts (n, 2) float32, next_pts the initial flow under PS_KLT_USE_INITIAL_FLOW.  params: _abi.klt_params(...), default
         the shipped OpenCVParams.  Returns (nextPts (n, 2) float32, status (n,) uint8, err (n,) float32)."""
-        params = params or klt_params()
-        prev_img, next_img, cn = self._klt_images(prev_img, next_img)
-        prev_pts = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
-        n = prev_pts.shape[0]
-        nxt = np.zeros((max(n, 1), 2), np.float32)
-        if next_pts is not None:
-            nxt[:n] = np.asarray(next_pts, np.float32).reshape(n, 2)
-        status, err = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32)
-        self._chk(self._L.ps_calc_optical_flow_pyr_lk(self._h, _p(prev_img), _p(next_img), prev_img.shape[0], prev_img.shape[1], cn,
-                                                      prev_img.strides[0], _p(prev_pts), _p(nxt), n, _p(status), _p(err),
-                                                      C.byref(params)))
+        params, head, n, nxt, status, err = self._klt_pair(prev_img, next_img, prev_pts, params, next_pts)
+        self._chk(self._L.ps_calc_optical_flow_pyr_lk(*head, _p(status), _p(err), C.byref(params)))
         return nxt[:n], status[:n], err[:n]
 
     def perform_tracking(self, prev_img, next_img, prev_pts, tracking_error_threshold, min_reproj_distance,
@@ -484,21 +490,12 @@ class Context:
         features that end closer than min_reproj_distance, compact.  Returns a dict: matches (k,) DMATCH_DTYPE = (i, j, 0, 0),
         kept_pts (k, 2), kept_idx (k,) -- what the caller compacts keyPoints / detDists with --, and next_pts / status / err of
         all n points."""
-        params = params or klt_params()
-        prev_img, next_img, cn = self._klt_images(prev_img, next_img)
-        prev_pts = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
-        n = prev_pts.shape[0]
+        params, head, n, nxt, status, err = self._klt_pair(prev_img, next_img, prev_pts, params, next_pts)
         m = max(n, 1)
-        nxt = np.zeros((m, 2), np.float32)
-        if next_pts is not None:
-            nxt[:n] = np.asarray(next_pts, np.float32).reshape(n, 2)
-        status, err = np.zeros(m, np.uint8), np.zeros(m, np.float32)
         matches, kept_pts, kept_idx = np.zeros(m, DMATCH_DTYPE), np.zeros((m, 2), np.float32), np.zeros(m, np.int32)
         nk = C.c_int(0)
-        self._chk(self._L.ps_perform_tracking(self._h, _p(prev_img), _p(next_img), prev_img.shape[0], prev_img.shape[1], cn,
-                                              prev_img.strides[0], _p(prev_pts), _p(nxt), n, C.byref(params),
-                                              float(tracking_error_threshold), float(min_reproj_distance), _p(status), _p(err),
-                                              _p(matches), C.byref(nk), _p(kept_pts), _p(kept_idx)))
+        self._chk(self._L.ps_perform_tracking(*head, C.byref(params), float(tracking_error_threshold), float(min_reproj_distance),
+                                              _p(status), _p(err), _p(matches), C.byref(nk), _p(kept_pts), _p(kept_idx)))
         k = nk.value
         return dict(matches=matches[:k].copy(), kept_pts=kept_pts[:k].copy(), kept_idx=kept_idx[:k].copy(), next_pts=nxt[:n],
                     status=status[:n], err=err[:n])
@@ -544,12 +541,7 @@ class Context:
         shipped ones.  Returns (xy (n, 2) float32, response (n,) float32) in the final order: response descending, ties in
         raster order inside an ROI and in the order of the ROI loop across ROIs."""
         params = params or detect_params()
-        image = np.asarray(image, np.uint8)
-        assert image.ndim in (2, 3)
-        cn = 1 if image.ndim == 2 else image.shape[2]
-        dense = image.shape[1] * cn
-        if not (image.strides[0] >= dense and (image.ndim == 2 and image.strides[1] == 1 or image.ndim == 3 and image.strides[1:] == (cn, 1))):
-            image = np.ascontiguousarray(image)
+        image, cn = _host_image(image)
         cap = max(0, min(int(params.maximalTrackedFeatures), PS_MAX_KPTS))
         xy, response = np.zeros((max(cap, 1), 2), np.float32), np.zeros(max(cap, 1), np.float32)
         n = C.c_int(0)
@@ -584,12 +576,7 @@ class Context:
         int8 in -15 .. 15, default the library's.  Returns (desc (k, 32) uint8, kept_idx (k,) int32): the described key points
         grouped by octave, input order inside an octave; kept_idx[j] is the input index of row j."""
         params = params or orb_params()
-        image = np.asarray(image, np.uint8)
-        assert image.ndim in (2, 3)
-        cn = 1 if image.ndim == 2 else image.shape[2]
-        dense = image.shape[1] * cn
-        if not (image.strides[0] >= dense and (image.ndim == 2 and image.strides[1] == 1 or image.ndim == 3 and image.strides[1:] == (cn, 1))):
-            image = np.ascontiguousarray(image)
+        image, cn = _host_image(image)
         xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
         n = xy.shape[0]
         angle = np.full(n, -1.0, np.float32) if angle is None else np.ascontiguousarray(angle, np.float32).reshape(n)

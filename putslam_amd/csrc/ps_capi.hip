@@ -1260,7 +1260,7 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
 #include "ps_map_match_l2.h" // the float policy of ps_map_match.h: ps_match_xyz_l2_f32 / ps_match_xyz_l2_device / ps_map_pairs_l2_device (ps_match_l2.h too)
 #include "ps_map_store_f32.h" // ps_map_views_l2_device / ps_pose_sets_l2_device / ps_loop_pairs_l2_device (ps_map_view.h, ps_loop_closure.h, ps_match_l2.h)
 #include "ps_klt.h"          // ps_klt_pyramids_* / ps_klt_track_device / ps_klt_select_device / ps_perform_tracking (ps_exclusion.h's bound)
-#include "ps_fast.h"         // ps_fast_detector_* / ps_detect_features(_device) (ps_klt.h's PsImageSet stride rule)
+#include "ps_fast.h"         // ps_fast_detector_* / ps_detect_features(_device) (the PsImageSet rule of all three: ps_glue.h, ps_image_rule.h)
 #include "ps_orb.h"          // ps_orb_pyramids_* / ps_describe_features(_device) (ps_fast.h's stable counting sort)
 
 // Launch attributes of the kernels that need them (ps_internal.h; called once per context).

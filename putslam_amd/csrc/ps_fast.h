@@ -29,7 +29,6 @@
 
 #include "ps_device_math.h"
 #include "ps_glue.h"
-#include "ps_klt.h"
 
 namespace psdev {
 
@@ -38,8 +37,6 @@ constexpr int kFastBlock = 256;              // threads of the score pass: a col
 constexpr int kFastLds = kFastTile + 6;      // the tile with its three-pixel ring
 constexpr int kFastSelBlock = 1024;          // threads of the selecting / merging work-group = elements of a chunk
 constexpr int kFastSelWaves = kFastSelBlock / 64;
-constexpr int kFastMaxDim = 8192;            // rows / cols: a packed (y << 16 | x) holds both, a plane's index stays inside an int
-constexpr int kFastMaxFrames = 65535;        // frames of a detector: the third grid dimension
 
 // The grid of ROIs (matcherOpenCV.cpp:133-146): ROI (k, i) starts at (k * cols / gridCols, i * rows / gridRows) and is
 // cols / gridCols x rows / gridRows pixels, all integer divisions.  roiW = roiH = 0: no ROI holds a candidate.
@@ -135,6 +132,7 @@ __global__ __launch_bounds__(kFastBlock) void ps_fast_score(const uint8_t *__res
         int v = 0;
         if (x >= 0 && x < g.cols && y >= 0 && y < g.rows) {
             const uint8_t *p = img + (size_t)y * rowStride + (size_t)x * cn;
+            // (CV_RGB2GRAY: channel 0 weighs 4899 here, 1868 in ps_orb.h's orb_gray -- intended)
             v = cn == 1 ? (int)p[0] : ((int)p[0] * 4899 + (int)p[1] * 9617 + (int)p[2] * 1868 + 8192) >> 14;
         }
         tile[ly][lx] = (uint8_t)v;
@@ -420,14 +418,6 @@ FastPlan fast_plan(int rows, int cols, const PsDetectParams &p)
     return pl;
 }
 
-int fast_shape_error(PsContext *ctx, int rows, int cols, int channels, const char *who)
-{
-    if (rows < 1 || cols < 1 || (channels != 1 && channels != 3))
-        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": rows and cols at least 1, channels 1 or 3").c_str());
-    if (rows > kFastMaxDim || cols > kFastMaxDim) return fail(ctx, PS_ERR_UNSUPPORTED, (std::string(who) + ": image above 8192 rows or columns").c_str());
-    return PS_OK;
-}
-
 // room for the ROI lists of `frames` frames under `pl` (synchronous when it has to grow: hipFree waits for the device)
 int fast_reserve(PsContext *ctx, PsFastDetector *det, const FastPlan &pl, int frames)
 {
@@ -484,17 +474,32 @@ int fast_detect_launch(PsContext *ctx, PsFastDetector *det, const uint8_t *pixel
     return PS_OK;
 }
 
-struct FastDeviceBlock {
-    void *p = nullptr;
-    ~FastDeviceBlock()
-    {
-        if (p) (void)hipFree(p);
+// ps_detect_features_device (passes = 7) and ps_debug_fast_passes, each reporting under its own name
+int fast_detect_device(PsContext *ctx, PsFastDetector *det, const PsImageSet *images, const PsDetectParams *params, int capacity, float *xy,
+                       float *response, int32_t *counts, int passes, const char *who)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const auto msg = [who](const char *what) { return std::string(who) + what; };
+    if (const char *why = fast_params_error(params)) return fail(ctx, PS_ERR_BAD_ARG, why);
+    if (params->maximalTrackedFeatures > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, msg(": maximalTrackedFeatures above PS_MAX_KPTS").c_str());
+    size_t row = 0, frame = 0;
+    rc = check_image_set(ctx, det, &PsFastDetector::maxFrames, images, 0, who, row, frame, false); // (the pixels: below, with the other arrays)
+    if (rc) return rc;
+    if (images->numFrames == 0) return PS_OK;
+    const FastPlan pl = fast_plan(det->rows, det->cols, *params);
+    if (capacity > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, msg(": capacity above PS_MAX_KPTS").c_str());
+    if (capacity < 0 || capacity < pl.need())
+        return fail(ctx, PS_ERR_BAD_ARG, msg(": capacity below min(maximalTrackedFeatures, candidate pixels)").c_str());
+    if (!images->pixels || !counts || (capacity > 0 && (!xy || !response))) return fail(ctx, PS_ERR_BAD_ARG, msg(": null array").c_str());
+    TimingOff toff(ctx);
+    if (pl.any()) {
+        rc = fast_reserve(ctx, det, pl, images->numFrames);
+        if (rc) return rc;
     }
-};
-struct FastDetectorOwner {
-    PsFastDetector *p = nullptr;
-    ~FastDetectorOwner() { ps_fast_detector_destroy(p); }
-};
+    HandoffGuard handoffGuard{ctx};
+    return fast_detect_launch(ctx, det, images->pixels, row, frame, images->numFrames, pl, capacity, xy, response, counts, passes & 7);
+}
 
 } // namespace
 
@@ -508,10 +513,11 @@ int ps_fast_detector_create(PsContext *ctx, int rows, int cols, int channels, in
     if (rc) return rc;
     if (!out) return fail(ctx, PS_ERR_BAD_ARG, "ps_fast_detector_create: null out");
     *out = nullptr;
-    rc = fast_shape_error(ctx, rows, cols, channels, "ps_fast_detector_create");
+    rc = image_shape_error(ctx, rows, cols, channels, "ps_fast_detector_create");
     if (rc) return rc;
-    if (maxFrames < 1 || maxFrames > kFastMaxFrames) return fail(ctx, PS_ERR_BAD_ARG, "ps_fast_detector_create: maxFrames must lie in 1 .. 65535");
-    PsFastDetector *d = new PsFastDetector;
+    if (maxFrames < 1 || maxFrames > kImageMaxFrames) return fail(ctx, PS_ERR_BAD_ARG, "ps_fast_detector_create: maxFrames must lie in 1 .. 65535");
+    HandleOwner<PsFastDetector> own(new PsFastDetector, ps_fast_detector_destroy);
+    PsFastDetector *d = own.get();
     d->device = ctx->device;
     d->rows = rows;
     d->cols = cols;
@@ -519,11 +525,8 @@ int ps_fast_detector_create(PsContext *ctx, int rows, int cols, int channels, in
     d->maxFrames = maxFrames;
     d->plane = (size_t)rows * cols;
     const hipError_t e = hipMalloc((void **)&d->maps, 3 * d->plane * (size_t)maxFrames);
-    if (e != hipSuccess) {
-        ps_fast_detector_destroy(d);
-        return fail(ctx, PS_ERR_ALLOC, "ps_fast_detector_create: hipMalloc", e);
-    }
-    *out = d;
+    if (e != hipSuccess) return fail(ctx, PS_ERR_ALLOC, "ps_fast_detector_create: hipMalloc", e);
+    *out = own.release();
     return PS_OK;
 }
 
@@ -540,36 +543,13 @@ void ps_fast_detector_destroy(PsFastDetector *det)
 int ps_detect_features_device(PsContext *ctx, PsFastDetector *det, const PsImageSet *images, const PsDetectParams *params, int capacity,
                               float *xy, float *response, int32_t *counts)
 {
-    return ps_debug_fast_passes(ctx, det, images, params, capacity, xy, response, counts, 7);
+    return fast_detect_device(ctx, det, images, params, capacity, xy, response, counts, 7, "ps_detect_features_device");
 }
 
 int ps_debug_fast_passes(PsContext *ctx, PsFastDetector *det, const PsImageSet *images, const PsDetectParams *params, int capacity,
                          float *xy, float *response, int32_t *counts, int passes)
 {
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (const char *why = fast_params_error(params)) return fail(ctx, PS_ERR_BAD_ARG, why);
-    if (params->maximalTrackedFeatures > PS_MAX_KPTS)
-        return fail(ctx, PS_ERR_UNSUPPORTED, "ps_detect_features_device: maximalTrackedFeatures above PS_MAX_KPTS");
-    size_t row = 0, frame = 0;
-    if (!det || !images || det->device != ctx->device || images->numFrames < 0 || images->numFrames > det->maxFrames)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_detect_features_device: null argument, another device's detector, or more frames than the detector holds");
-    if (images->rows != det->rows || images->cols != det->cols || images->channels != det->cn || !klt_image_strides(*images, row, frame))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_detect_features_device: the images' shape differs from the detector's, or a stride is below its row / frame");
-    if (images->numFrames == 0) return PS_OK;
-    const FastPlan pl = fast_plan(det->rows, det->cols, *params);
-    if (capacity > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, "ps_detect_features_device: capacity above PS_MAX_KPTS");
-    if (capacity < 0 || capacity < pl.need())
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_detect_features_device: capacity below min(maximalTrackedFeatures, candidate pixels)");
-    if (!images->pixels || !counts || (capacity > 0 && (!xy || !response)))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_detect_features_device: null array");
-    TimingOff toff(ctx);
-    if (pl.any()) {
-        rc = fast_reserve(ctx, det, pl, images->numFrames);
-        if (rc) return rc;
-    }
-    HandoffGuard handoffGuard{ctx};
-    return fast_detect_launch(ctx, det, images->pixels, row, frame, images->numFrames, pl, capacity, xy, response, counts, passes & 7);
+    return fast_detect_device(ctx, det, images, params, capacity, xy, response, counts, passes, "ps_debug_fast_passes");
 }
 
 int ps_detect_features(PsContext *ctx, const uint8_t *img, int rows, int cols, int channels, size_t rowStride, const PsDetectParams *params,
@@ -580,11 +560,10 @@ int ps_detect_features(PsContext *ctx, const uint8_t *img, int rows, int cols, i
     if (const char *why = fast_params_error(params)) return fail(ctx, PS_ERR_BAD_ARG, why);
     if (params->maximalTrackedFeatures > PS_MAX_KPTS)
         return fail(ctx, PS_ERR_UNSUPPORTED, "ps_detect_features: maximalTrackedFeatures above PS_MAX_KPTS");
-    rc = fast_shape_error(ctx, rows, cols, channels, "ps_detect_features");
+    rc = image_shape_error(ctx, rows, cols, channels, "ps_detect_features");
     if (rc) return rc;
-    const size_t dense = (size_t)cols * channels;
-    if (rowStride == 0) rowStride = dense;
-    if (!img || !nout || rowStride < dense || cap < 0 || (cap > 0 && (!xy || !response)))
+    rowStride = image_row_stride(cols, channels, rowStride);
+    if (!img || !nout || rowStride == 0 || cap < 0 || (cap > 0 && (!xy || !response)))
         return fail(ctx, PS_ERR_BAD_ARG, "ps_detect_features: null array, negative cap or a row stride below a row");
     const FastPlan pl = fast_plan(rows, cols, *params);
     const int room = (int)pl.need(); // (at most maximalTrackedFeatures <= PS_MAX_KPTS)
@@ -593,23 +572,25 @@ int ps_detect_features(PsContext *ctx, const uint8_t *img, int rows, int cols, i
         return PS_OK;
     }
     TimingOff toff(ctx);
-    FastDetectorOwner det;
-    rc = ps_fast_detector_create(ctx, rows, cols, channels, 1, &det.p);
+    PsFastDetector *det = nullptr;
+    rc = ps_fast_detector_create(ctx, rows, cols, channels, 1, &det);
     if (rc) return rc;
+    const HandleOwner<PsFastDetector> own(det, ps_fast_detector_destroy);
     if (pl.any()) {
-        rc = fast_reserve(ctx, det.p, pl, 1);
+        rc = fast_reserve(ctx, det, pl, 1);
         if (rc) return rc;
     }
-    const size_t imgBytes = (size_t)(rows - 1) * rowStride + dense;
+    const size_t imgBytes = image_bytes(rows, cols, channels, rowStride);
     // one block: the image | count | xy | response
-    const size_t oCount = (imgBytes + 15) & ~(size_t)15, oXy = oCount + 16, oResp = oXy + (size_t)room * 8, total = oResp + (size_t)room * 4;
-    FastDeviceBlock blk;
-    const hipError_t e = hipMalloc(&blk.p, total);
-    if (e != hipSuccess) return fail(ctx, PS_ERR_ALLOC, "hipMalloc", e);
-    char *d = (char *)blk.p;
+    BlockLayout lay;
+    lay.take<uint8_t>(imgBytes);
+    const size_t oCount = lay.take<int32_t>(1, 16), oXy = lay.take<float2>((size_t)room), oResp = lay.take<float>((size_t)room), total = lay.total;
+    const DeviceBlock blk(total);
+    if (blk.err != hipSuccess) return fail(ctx, PS_ERR_ALLOC, "hipMalloc", blk.err);
+    char *d = blk.p;
     PS_HIP(hipMemcpyAsync(d, img, imgBytes, hipMemcpyHostToDevice, ctx->stream));
     PS_HIP(hipStreamSynchronize(ctx->stream)); // (a pageable source may change)
-    rc = fast_detect_launch(ctx, det.p, (const uint8_t *)d, rowStride, 0, 1, pl, room, (float *)(d + oXy), (float *)(d + oResp),
+    rc = fast_detect_launch(ctx, det, (const uint8_t *)d, rowStride, 0, 1, pl, room, (float *)(d + oXy), (float *)(d + oResp),
                             (int32_t *)(d + oCount));
     if (rc) return rc;
     std::vector<char> back(total - oCount);

@@ -1,12 +1,14 @@
 // ps_glue.h -- what the entry points of the device translation unit share on the HOST side, each rule once: the guard that marks
-// queued work for a later ps_context_set_stream, the timing record's prologue and its switch, the PsFrameSet stride rule and the
-// bisection behind the host-found bounds.  Host code only; included by ps_capi.hip and by the feature headers' host parts.
+// queued work for a later ps_context_set_stream, the timing record's prologue and its switch, the PsFrameSet stride rule, the
+// bisection behind the host-found bounds, and the image front end's guards and checks.  Host code only; included by ps_capi.hip and by the feature headers' host parts.
 #pragma once
 #include <climits>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 
+#include "ps_image_rule.h"
 #include "ps_internal.h"
 
 namespace {
@@ -92,6 +94,46 @@ inline size_t depth_view_bytes(int rows, int cols, size_t step)
 {
     if (rows < 1 || cols < 1 || step < (size_t)cols * 2) return 0;
     return (size_t)(rows - 1) * step + (size_t)cols * 2;
+}
+
+// ---- the image front end (ps_klt.h, ps_fast.h, ps_orb.h); the arithmetic is ps_image_rule.h's ----
+
+// The device block of a host form: allocated here (err says how that went), freed at every exit.
+struct DeviceBlock {
+    char *p = nullptr;
+    const hipError_t err;
+    explicit DeviceBlock(size_t bytes) : err(hipMalloc((void **)&p, bytes)) {}
+    ~DeviceBlock() { if (p) (void)hipFree(p); }
+};
+
+// A handle (a pyramid set, a detector) with its destroy function: destroyed at every exit unless it was released.
+template <class T> using HandleOwner = std::unique_ptr<T, void (*)(T *)>;
+
+// The shape of an image as every front-end call takes it (KLT has its window rules in front of this one).
+inline int image_shape_error(PsContext *ctx, int rows, int cols, int channels, const char *who)
+{
+    if (rows < 1 || cols < 1 || (channels != 1 && channels != 3))
+        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": rows and cols at least 1, channels 1 or 3").c_str());
+    if (rows > kImageMaxDim || cols > kImageMaxDim)
+        return fail(ctx, PS_ERR_UNSUPPORTED, (std::string(who) + ": image above 8192 rows or columns").c_str());
+    return PS_OK;
+}
+
+// THE IMAGE-SET RULE, for an owner (device, rows, cols, cn; `slots` names its slot count) that takes the set's frames into slots
+// firstSlot ..: owner and set are there, the owner is this device's, the frames are not negative and fit into the slots, the
+// shape is the owner's, the strides resolve (image_set_strides; returned) and, with frames, there are pixels.  pixels = false
+// leaves the last to the caller (ps_detect_features_device looks at it after its capacity rules).
+template <class Owner>
+int check_image_set(PsContext *ctx, const Owner *own, int Owner::*slots, const PsImageSet *images, int firstSlot, const char *who, size_t &row,
+                    size_t &frame, bool pixels = true)
+{
+    if (!own || !images || own->device != ctx->device || images->numFrames < 0 || firstSlot < 0 ||
+        (long long)firstSlot + images->numFrames > own->*slots)
+        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null argument, another device's handle, or slots outside the set").c_str());
+    if (images->rows != own->rows || images->cols != own->cols || images->channels != own->cn || !image_set_strides(*images, row, frame))
+        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": the images' shape differs from the handle's, or a stride is below its row / frame").c_str());
+    if (pixels && images->numFrames > 0 && !images->pixels) return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null pixels").c_str());
+    return PS_OK;
 }
 
 // The least non-negative double x, +inf included, with pred(x), for a predicate that is monotone in x and true at +inf:

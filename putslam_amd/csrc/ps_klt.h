@@ -34,7 +34,6 @@ constexpr int kKltLevels = 8;      // level 0 and up to seven reduced ones
 constexpr int kKltBlock = 256;     // threads of a pyramid-pass work-group; the tracker's at most
 constexpr int kKltSelBlock = 1024; // threads of the selecting work-group = points of an LDS tile
 constexpr int kKltSelWaves = kKltSelBlock / 64;
-constexpr int kKltMaxDim = 8192;   // rows / cols: a padded level's element count stays far inside an int
 
 // One stored level: the image as (rows + 2W) x (cols + 2W) x cn bytes, the derivative with the same element index as packed
 // int16 pairs (Ix low, Iy high).  Offsets are counted from the slot's start, in elements of either array.
@@ -472,20 +471,7 @@ int klt_shape_error(PsContext *ctx, int rows, int cols, int channels, int winSiz
         return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": winSize 3 .. 31, maxLevels 0 .. 7, channels 1 or 3").c_str());
     if (rows <= winSize || cols <= winSize)
         return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": the image must be larger than the window in both directions").c_str());
-    if (rows > kKltMaxDim || cols > kKltMaxDim) return fail(ctx, PS_ERR_UNSUPPORTED, (std::string(who) + ": image above 8192 rows or columns").c_str());
-    return PS_OK;
-}
-
-// resolved strides of a PsImageSet; 0 for a set the call rejects
-bool klt_image_strides(const PsImageSet &s, size_t &row, size_t &frame)
-{
-    if (s.rows < 1 || s.cols < 1 || s.channels < 1) return false;
-    const size_t dense = (size_t)s.cols * s.channels;
-    row = s.rowStride ? s.rowStride : dense;
-    if (row < dense) return false;
-    const size_t need = (size_t)(s.rows - 1) * row + dense;
-    frame = s.frameStride ? s.frameStride : (size_t)s.rows * row;
-    return frame >= need;
+    return image_shape_error(ctx, rows, cols, channels, who); // (after the window rules: only its size limit is left to break)
 }
 
 int klt_build_launch(PsContext *ctx, PsKltPyramids *pyr, const uint8_t *pixels, size_t rowStride, size_t frameStride, int frames,
@@ -556,19 +542,6 @@ int klt_select_launch(PsContext *ctx, const float *pts, const uint8_t *status, c
     return PS_OK;
 }
 
-// device blocks of the host forms: freed at every exit
-struct KltDeviceBlock {
-    void *p = nullptr;
-    ~KltDeviceBlock()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
-struct KltPyramidsOwner {
-    PsKltPyramids *p = nullptr;
-    ~KltPyramidsOwner() { ps_klt_pyramids_destroy(p); }
-};
-
 // The host forms: one pair, uploads included, synchronous.  select = false: calcOpticalFlowPyrLK alone.
 int klt_host_pair(PsContext *ctx, const char *who, const uint8_t *prevImg, const uint8_t *nextImg, int rows, int cols, int channels,
                   size_t rowStride, const float *prevPts, float *nextPts, int n, uint8_t *status, float *err, const PsKltParams *prm,
@@ -579,28 +552,29 @@ int klt_host_pair(PsContext *ctx, const char *who, const uint8_t *prevImg, const
     if (const char *why = klt_params_error(prm)) return fail(ctx, PS_ERR_BAD_ARG, why);
     rc = klt_shape_error(ctx, rows, cols, channels, prm->winSize, prm->maxLevels, who);
     if (rc) return rc;
-    const size_t dense = (size_t)cols * channels;
-    if (rowStride == 0) rowStride = dense;
-    if (!prevImg || !nextImg || rowStride < dense || n < 0 || (select && !numMatches) ||
+    rowStride = image_row_stride(cols, channels, rowStride);
+    if (!prevImg || !nextImg || rowStride == 0 || n < 0 || (select && !numMatches) ||
         (n > 0 && (!prevPts || !nextPts || (!select && (!status || !err)) || (select && (!matches || !keptPts || !keptIdx)))))
         return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null array, negative count or a row stride below a row").c_str());
     if (select && n > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, (std::string(who) + ": more than PS_MAX_KPTS points").c_str());
     if (select) *numMatches = 0;
     if (n == 0) return PS_OK;
     TimingOff toff(ctx);
-    KltPyramidsOwner pyr;
-    rc = ps_klt_pyramids_create(ctx, rows, cols, channels, prm->winSize, prm->maxLevels, 2, &pyr.p);
+    PsKltPyramids *pyr = nullptr;
+    rc = ps_klt_pyramids_create(ctx, rows, cols, channels, prm->winSize, prm->maxLevels, 2, &pyr);
     if (rc) return rc;
-    const size_t imgBytes = (size_t)(rows - 1) * rowStride + dense;
-    // one block: two images | pairs[2] | count | prevPts | nextPts | err | numMatches | matches | keptPts | keptIdx | status
-    const size_t oImg1 = (imgBytes + 15) & ~(size_t)15, oPairs = 2 * oImg1, oCount = oPairs + 8, oPrev = oCount + 8,
-                 oNext = oPrev + (size_t)n * 8, oErr = oNext + (size_t)n * 8, oNum = oErr + (size_t)n * 4 + (((size_t)n & 1) ? 4 : 0),
-                 oMatches = oNum + 8, oKeptPts = oMatches + (size_t)n * 16, oKeptIdx = oKeptPts + (size_t)n * 8,
-                 oStatus = oKeptIdx + (size_t)n * 4, total = oStatus + (size_t)n;
-    KltDeviceBlock blk;
-    hipError_t e = hipMalloc(&blk.p, total);
-    if (e != hipSuccess) return fail(ctx, PS_ERR_ALLOC, "hipMalloc", e);
-    char *d = (char *)blk.p;
+    const HandleOwner<PsKltPyramids> own(pyr, ps_klt_pyramids_destroy);
+    const size_t imgBytes = image_bytes(rows, cols, channels, rowStride), N = (size_t)n;
+    // one block: two images | pairs[2], count, 0 | prevPts | nextPts | err | numMatches | matches | keptPts | keptIdx | status
+    static_assert(alignof(float2) == 8 && alignof(PsDMatch) == 4, "the layout aligns every array to its element type");
+    BlockLayout lay;
+    lay.take<uint8_t>(imgBytes, 16); // (the previous image, at 0)
+    const size_t oImg1 = lay.take<uint8_t>(imgBytes, 16), oPairs = lay.take<int32_t>(4, 16), oCount = oPairs + 8, oPrev = lay.take<float2>(N),
+                 oNext = lay.take<float2>(N), oErr = lay.take<float>(N), oNum = lay.take<int32_t>(1), oMatches = lay.take<PsDMatch>(N, 8),
+                 oKeptPts = lay.take<float2>(N), oKeptIdx = lay.take<int32_t>(N), oStatus = lay.take<uint8_t>(N), total = lay.total;
+    const DeviceBlock blk(total);
+    if (blk.err != hipSuccess) return fail(ctx, PS_ERR_ALLOC, "hipMalloc", blk.err);
+    char *d = blk.p;
     const int32_t head[4] = {0, 1, n, 0};
     PS_HIP(hipMemcpyAsync(d, prevImg, imgBytes, hipMemcpyHostToDevice, ctx->stream));
     PS_HIP(hipMemcpyAsync(d + oImg1, nextImg, imgBytes, hipMemcpyHostToDevice, ctx->stream));
@@ -608,9 +582,9 @@ int klt_host_pair(PsContext *ctx, const char *who, const uint8_t *prevImg, const
     PS_HIP(hipMemcpyAsync(d + oPrev, prevPts, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     if (prm->flags & PS_KLT_USE_INITIAL_FLOW) PS_HIP(hipMemcpyAsync(d + oNext, nextPts, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     PS_HIP(hipStreamSynchronize(ctx->stream)); // (head[] and pageable sources leave scope / may change)
-    rc = klt_build_launch(ctx, pyr.p, (const uint8_t *)d, rowStride, oImg1, 2, 0);
+    rc = klt_build_launch(ctx, pyr, (const uint8_t *)d, rowStride, oImg1, 2, 0);
     if (rc) return rc;
-    rc = klt_track_launch(ctx, pyr.p, *prm, (const int32_t *)(d + oPairs), (const float *)(d + oPrev), (const int32_t *)(d + oCount), 1, n,
+    rc = klt_track_launch(ctx, pyr, *prm, (const int32_t *)(d + oPairs), (const float *)(d + oPrev), (const int32_t *)(d + oCount), 1, n,
                           (float *)(d + oNext), (uint8_t *)(d + oStatus), (float *)(d + oErr));
     if (rc) return rc;
     if (select) {
@@ -658,8 +632,9 @@ int ps_klt_pyramids_create(PsContext *ctx, int rows, int cols, int channels, int
     *out = nullptr;
     rc = klt_shape_error(ctx, rows, cols, channels, winSize, maxLevels, "ps_klt_pyramids_create");
     if (rc) return rc;
-    if (slots < 1 || slots > 65535) return fail(ctx, PS_ERR_BAD_ARG, "ps_klt_pyramids_create: slots must lie in 1 .. 65535");
-    PsKltPyramids *p = new PsKltPyramids;
+    if (slots < 1 || slots > kImageMaxFrames) return fail(ctx, PS_ERR_BAD_ARG, "ps_klt_pyramids_create: slots must lie in 1 .. 65535");
+    HandleOwner<PsKltPyramids> own(new PsKltPyramids, ps_klt_pyramids_destroy);
+    PsKltPyramids *p = own.get();
     p->device = ctx->device;
     p->rows = rows;
     p->cols = cols;
@@ -686,11 +661,8 @@ int ps_klt_pyramids_create(PsContext *ctx, int rows, int cols, int channels, int
     if (e == hipSuccess) e = hipMalloc((void **)&p->der, p->slotElems * (size_t)slots * 4);
     if (e == hipSuccess) e = hipMalloc((void **)&p->dLevels, sizeof(p->lv));
     if (e == hipSuccess) e = hipMemcpy(p->dLevels, p->lv, sizeof(KltLevel) * (size_t)(p->L + 1), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        ps_klt_pyramids_destroy(p);
-        return fail(ctx, PS_ERR_ALLOC, "ps_klt_pyramids_create: hipMalloc", e);
-    }
-    *out = p;
+    if (e != hipSuccess) return fail(ctx, PS_ERR_ALLOC, "ps_klt_pyramids_create: hipMalloc", e);
+    *out = own.release();
     return PS_OK;
 }
 
@@ -711,13 +683,9 @@ int ps_klt_pyramids_build_device(PsContext *ctx, PsKltPyramids *pyr, const PsIma
     int rc = bind(ctx);
     if (rc) return rc;
     size_t row = 0, frame = 0;
-    if (!pyr || !images || pyr->device != ctx->device || images->numFrames < 0 || firstSlot < 0 ||
-        (long long)firstSlot + images->numFrames > pyr->slots)
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_klt_pyramids_build_device: null argument, another device's set, or slots outside the set");
-    if (images->rows != pyr->rows || images->cols != pyr->cols || images->channels != pyr->cn || !klt_image_strides(*images, row, frame))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_klt_pyramids_build_device: the images' shape differs from the set's, or a stride is below its row / frame");
+    rc = check_image_set(ctx, pyr, &PsKltPyramids::slots, images, firstSlot, "ps_klt_pyramids_build_device", row, frame);
+    if (rc) return rc;
     if (images->numFrames == 0) return PS_OK;
-    if (!images->pixels) return fail(ctx, PS_ERR_BAD_ARG, "ps_klt_pyramids_build_device: null pixels");
     TimingOff toff(ctx);
     HandoffGuard handoffGuard{ctx};
     return klt_build_launch(ctx, pyr, images->pixels, row, frame, images->numFrames, firstSlot);

@@ -37,9 +37,8 @@
 #include <vector>
 
 #include "ps_device_math.h"
-#include "ps_fast.h"
+#include "ps_fast.h" // fast_stable_take, its FastSortLds and kFastSelBlock: ps_orb_place orders the key points with them
 #include "ps_glue.h"
-#include "ps_klt.h"
 
 namespace psdev {
 
@@ -92,6 +91,7 @@ PS_D void orb_rotation(float deg, float &a, float &b)
     b = k == 0 ? s : (k == 1 ? c : (k == 2 ? -s : -c));
 }
 
+// (COLOR_BGR2GRAY: channel 0 weighs 1868 here, 4899 in ps_fast.h's ps_fast_score -- intended)
 PS_D int orb_gray(const uint8_t *p, int cn)
 {
     return cn == 1 ? (int)p[0] : ((int)p[0] * 1868 + (int)p[1] * 9617 + (int)p[2] * 4899 + 8192) >> 14;
@@ -370,14 +370,6 @@ const char *orb_params_error(const PsOrbParams *p)
     return nullptr;
 }
 
-int orb_shape_error(PsContext *ctx, int rows, int cols, int channels, const char *who)
-{
-    if (rows < 1 || cols < 1 || (channels != 1 && channels != 3))
-        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": rows and cols at least 1, channels 1 or 3").c_str());
-    if (rows > kFastMaxDim || cols > kFastMaxDim) return fail(ctx, PS_ERR_UNSUPPORTED, (std::string(who) + ": image above 8192 rows or columns").c_str());
-    return PS_OK;
-}
-
 bool orb_pattern_ok(const int8_t *p)
 {
     for (int i = 0; i < 1024; ++i)
@@ -431,39 +423,16 @@ int orb_describe_launch(PsContext *ctx, const PsOrbPyramids *pyr, const int32_t 
     return PS_OK;
 }
 
-int orb_build_check(PsContext *ctx, PsOrbPyramids *pyr, const PsImageSet *images, int firstSlot, size_t &row, size_t &frame, const char *who)
-{
-    if (!pyr || !images || pyr->device != ctx->device || images->numFrames < 0 || firstSlot < 0 ||
-        (long long)firstSlot + images->numFrames > pyr->slots)
-        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null argument, another device's set, or slots outside the set").c_str());
-    if (images->rows != pyr->rows || images->cols != pyr->cols || images->channels != pyr->cn || !klt_image_strides(*images, row, frame))
-        return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": the images' shape differs from the set's, or a stride is below its row / frame").c_str());
-    if (images->numFrames > 0 && !images->pixels) return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null pixels").c_str());
-    return PS_OK;
-}
-
 int orb_describe_check(PsContext *ctx, const PsOrbPyramids *pyr, const int32_t *slots, const float *xy, const float *angle, const int32_t *octave,
                        const int32_t *counts, int F, int capacity, uint8_t *desc, int32_t *keptIdx, int32_t *numKept, const char *who)
 {
-    if (!pyr || pyr->device != ctx->device || F < 0 || F > kFastMaxFrames)
+    if (!pyr || pyr->device != ctx->device || F < 0 || F > kImageMaxFrames)
         return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null or foreign pyramid set, or F outside 0 .. 65535").c_str());
     if (capacity > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, (std::string(who) + ": capacity above PS_MAX_KPTS").c_str());
     if (F > 0 && (capacity < 1 || !slots || !xy || !angle || !octave || !counts || !desc || !keptIdx || !numKept))
         return fail(ctx, PS_ERR_BAD_ARG, (std::string(who) + ": null array or capacity < 1").c_str());
     return PS_OK;
 }
-
-struct OrbDeviceBlock {
-    void *p = nullptr;
-    ~OrbDeviceBlock()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
-struct OrbPyramidsOwner {
-    PsOrbPyramids *p = nullptr;
-    ~OrbPyramidsOwner() { ps_orb_pyramids_destroy(p); }
-};
 
 } // namespace
 
@@ -486,13 +455,13 @@ int ps_orb_pyramids_create(PsContext *ctx, int rows, int cols, int channels, con
     if (!out) return fail(ctx, PS_ERR_BAD_ARG, "ps_orb_pyramids_create: null out");
     *out = nullptr;
     if (const char *why = orb_params_error(params)) return fail(ctx, PS_ERR_BAD_ARG, why);
-    rc = orb_shape_error(ctx, rows, cols, channels, "ps_orb_pyramids_create");
+    rc = image_shape_error(ctx, rows, cols, channels, "ps_orb_pyramids_create");
     if (rc) return rc;
-    if (slots < 1 || slots > kFastMaxFrames) return fail(ctx, PS_ERR_BAD_ARG, "ps_orb_pyramids_create: slots must lie in 1 .. 65535");
+    if (slots < 1 || slots > kImageMaxFrames) return fail(ctx, PS_ERR_BAD_ARG, "ps_orb_pyramids_create: slots must lie in 1 .. 65535");
     if (pattern1024 && !orb_pattern_ok(pattern1024))
         return fail(ctx, PS_ERR_BAD_ARG, "ps_orb_pyramids_create: a pattern coordinate outside -15 .. 15");
-    OrbPyramidsOwner own;
-    PsOrbPyramids *p = own.p = new PsOrbPyramids;
+    HandleOwner<PsOrbPyramids> own(new PsOrbPyramids, ps_orb_pyramids_destroy);
+    PsOrbPyramids *p = own.get();
     p->device = ctx->device;
     p->rows = rows;
     p->cols = cols;
@@ -534,8 +503,7 @@ int ps_orb_pyramids_create(PsContext *ctx, int rows, int cols, int channels, con
     if (e == hipSuccess) e = hipMemcpy(p->dLevels, p->lv, sizeof(OrbLevel) * (size_t)p->nLevels, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->dPattern, pat, sizeof(pat), hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(ctx, PS_ERR_ALLOC, "ps_orb_pyramids_create: hipMalloc", e);
-    *out = p;
-    own.p = nullptr;
+    *out = own.release();
     return PS_OK;
 }
 
@@ -566,7 +534,7 @@ int ps_orb_pyramids_build_device(PsContext *ctx, PsOrbPyramids *pyr, const PsIma
     int rc = bind(ctx);
     if (rc) return rc;
     size_t row = 0, frame = 0;
-    rc = orb_build_check(ctx, pyr, images, firstSlot, row, frame, "ps_orb_pyramids_build_device");
+    rc = check_image_set(ctx, pyr, &PsOrbPyramids::slots, images, firstSlot, "ps_orb_pyramids_build_device", row, frame);
     if (rc) return rc;
     if (images->numFrames == 0) return PS_OK;
     TimingOff toff(ctx);
@@ -597,7 +565,7 @@ int ps_debug_orb_passes(PsContext *ctx, PsOrbPyramids *pyr, const PsImageSet *im
     size_t row = 0, frame = 0;
     const bool builds = (passes & (kOrbPassLevel0 | kOrbPassResize | kOrbPassBlur)) != 0, describes = (passes & (kOrbPassPlace | kOrbPassDescribe)) != 0;
     if (builds) {
-        rc = orb_build_check(ctx, pyr, images, firstSlot, row, frame, "ps_debug_orb_passes");
+        rc = check_image_set(ctx, pyr, &PsOrbPyramids::slots, images, firstSlot, "ps_debug_orb_passes", row, frame);
         if (rc) return rc;
     }
     if (describes) {
@@ -621,29 +589,30 @@ int ps_describe_features(PsContext *ctx, const uint8_t *img, int rows, int cols,
     int rc = bind(ctx);
     if (rc) return rc;
     if (const char *why = orb_params_error(params)) return fail(ctx, PS_ERR_BAD_ARG, why);
-    rc = orb_shape_error(ctx, rows, cols, channels, "ps_describe_features");
+    rc = image_shape_error(ctx, rows, cols, channels, "ps_describe_features");
     if (rc) return rc;
     if (n > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, "ps_describe_features: more than PS_MAX_KPTS key points");
-    const size_t dense = (size_t)cols * channels;
-    if (rowStride == 0) rowStride = dense;
-    if (!img || !nout || rowStride < dense || n < 0 || (n > 0 && (!xy || !angle || !octave || !desc || !keptIdx)))
+    rowStride = image_row_stride(cols, channels, rowStride);
+    if (!img || !nout || rowStride == 0 || n < 0 || (n > 0 && (!xy || !angle || !octave || !desc || !keptIdx)))
         return fail(ctx, PS_ERR_BAD_ARG, "ps_describe_features: null array, negative n or a row stride below a row");
     TimingOff toff(ctx);
-    OrbPyramidsOwner pyr;
-    rc = ps_orb_pyramids_create(ctx, rows, cols, channels, params, pattern1024, 1, &pyr.p); // (refuses a bad pattern or an empty level)
+    PsOrbPyramids *pyr = nullptr;
+    rc = ps_orb_pyramids_create(ctx, rows, cols, channels, params, pattern1024, 1, &pyr); // (refuses a bad pattern or an empty level)
     if (rc) return rc;
+    const HandleOwner<PsOrbPyramids> own(pyr, ps_orb_pyramids_destroy);
     if (n == 0) {
         *nout = 0;
         return PS_OK;
     }
-    const size_t imgBytes = (size_t)(rows - 1) * rowStride + dense, N = (size_t)n;
-    // one block: the image | slot, count, numKept | xy | angle | octave | keptIdx | desc
-    const size_t oHead = (imgBytes + 15) & ~(size_t)15, oXy = oHead + 16, oAngle = oXy + N * 8, oOct = oAngle + N * 4, oKept = oOct + N * 4,
-                 oDesc = oKept + N * 4, total = oDesc + N * 32;
-    OrbDeviceBlock blk;
-    const hipError_t e = hipMalloc(&blk.p, total);
-    if (e != hipSuccess) return fail(ctx, PS_ERR_ALLOC, "hipMalloc", e);
-    char *d = (char *)blk.p;
+    const size_t imgBytes = image_bytes(rows, cols, channels, rowStride), N = (size_t)n;
+    // one block: the image | slot, count, numKept, 0 | xy | angle | octave | keptIdx | desc
+    BlockLayout lay;
+    lay.take<uint8_t>(imgBytes);
+    const size_t oHead = lay.take<int32_t>(4, 16), oXy = lay.take<float2>(N), oAngle = lay.take<float>(N), oOct = lay.take<int32_t>(N),
+                 oKept = lay.take<int32_t>(N), oDesc = lay.take<uint8_t>(N * 32), total = lay.total;
+    const DeviceBlock blk(total);
+    if (blk.err != hipSuccess) return fail(ctx, PS_ERR_ALLOC, "hipMalloc", blk.err);
+    char *d = blk.p;
     const int32_t head[4] = {0, n, 0, 0};
     PS_HIP(hipMemcpyAsync(d, img, imgBytes, hipMemcpyHostToDevice, ctx->stream));
     PS_HIP(hipMemcpyAsync(d + oHead, head, sizeof(head), hipMemcpyHostToDevice, ctx->stream));
@@ -651,10 +620,10 @@ int ps_describe_features(PsContext *ctx, const uint8_t *img, int rows, int cols,
     PS_HIP(hipMemcpyAsync(d + oAngle, angle, N * 4, hipMemcpyHostToDevice, ctx->stream));
     PS_HIP(hipMemcpyAsync(d + oOct, octave, N * 4, hipMemcpyHostToDevice, ctx->stream));
     PS_HIP(hipStreamSynchronize(ctx->stream)); // (head[] and pageable sources leave scope / may change)
-    rc = orb_build_launch(ctx, pyr.p, (const uint8_t *)d, rowStride, 0, 1, 0, kOrbPassAll);
+    rc = orb_build_launch(ctx, pyr, (const uint8_t *)d, rowStride, 0, 1, 0, kOrbPassAll);
     if (rc) return rc;
     int32_t *h = (int32_t *)(d + oHead);
-    rc = orb_describe_launch(ctx, pyr.p, h, (const float *)(d + oXy), (const float *)(d + oAngle), (const int32_t *)(d + oOct), h + 1, 1, n,
+    rc = orb_describe_launch(ctx, pyr, h, (const float *)(d + oXy), (const float *)(d + oAngle), (const int32_t *)(d + oOct), h + 1, 1, n,
                              (uint8_t *)(d + oDesc), (int32_t *)(d + oKept), h + 2, kOrbPassAll);
     if (rc) return rc;
     int32_t k = 0;

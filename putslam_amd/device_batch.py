@@ -29,6 +29,18 @@ def _zeros(device, shape, dtype):
     return torch.zeros(shape, dtype=dtype, device=device)
 
 
+def _expect(t, dtype, shape):
+    """`t` is a contiguous tensor of this dtype and shape."""
+    assert t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous(), (t.dtype, tuple(t.shape), dtype, tuple(shape))
+
+
+def _block(t, device, shape, dtype):
+    """The caller's block `t`, checked, or a new zeroed one of this shape."""
+    t = _zeros(device, shape, dtype) if t is None else t
+    _expect(t, dtype, shape)
+    return t
+
+
 def pack_frames(desc, pts, stride=None):
     """(F, cap, 32) u8 + (F, cap, 3) f32 -> (F, stride) u8: every frame one block [cap x 32 B descriptors][cap x 12 B points]
     padded to `stride` bytes (default: cap x 44 rounded up to 16 -- PS_FRAMES_PACKED / ps_vo_stream_packed_stride)."""
@@ -284,11 +296,11 @@ def dbscan_thin_device(ctx, xy, counts, octave=None, eps=10.0, min_pts=2, featur
     """DBScan keypoint thinning of a device-resident batch (ps_dbscan_thin_device): xy (F, cap, 2) float32, counts (F,) int32,
     octave (F, cap) int32 or None -- torch tensors on the context's device.  Returns (kept (F, cap) int32, nkept (F,) int32),
     device tensors written asynchronously on the context's stream: frame f keeps kept[f, :nkept[f]] (ascending)."""
-    assert xy.dtype == torch.float32 and xy.dim() == 3 and xy.shape[2] == 2 and xy.is_contiguous()
-    assert counts.dtype == torch.int32 and counts.shape == (xy.shape[0],) and counts.is_contiguous()
-    if octave is not None:
-        assert octave.dtype == torch.int32 and octave.shape == xy.shape[:2] and octave.is_contiguous()
     F, cap = xy.shape[0], xy.shape[1]
+    _expect(xy, torch.float32, (F, cap, 2))
+    _expect(counts, torch.int32, (F,))
+    if octave is not None:
+        _expect(octave, torch.int32, (F, cap))
     kept = torch.empty((F, cap), dtype=torch.int32, device=xy.device)
     nkept = torch.empty((F,), dtype=torch.int32, device=xy.device)
     args = (xy.data_ptr(), octave.data_ptr() if octave is not None else 0, counts.data_ptr(), F, cap, kept.data_ptr(),
@@ -305,14 +317,16 @@ def exclude_device(ctx, rule, cand3, cand2, cand_counts, exist3=None, exist2=Non
     lead = cand2 if cand2 is not None else cand3
     F, cap = lead.shape[0], lead.shape[1]
     for t, w in ((cand3, 3), (cand2, 2)):
-        assert t is None or (t.dtype == torch.float32 and t.shape == (F, cap, w) and t.is_contiguous())
-    assert cand_counts.dtype == torch.int32 and cand_counts.shape == (F,) and cand_counts.is_contiguous()
+        if t is not None:
+            _expect(t, torch.float32, (F, cap, w))
+    _expect(cand_counts, torch.int32, (F,))
     elead = exist2 if exist2 is not None else exist3
     ecap = 0 if elead is None else elead.shape[1]
     if ecap:
         for t, w in ((exist3, 3), (exist2, 2)):
-            assert t is None or (t.dtype == torch.float32 and t.shape == (F, ecap, w) and t.is_contiguous())
-        assert exist_counts.dtype == torch.int32 and exist_counts.shape == (F,) and exist_counts.is_contiguous()
+            if t is not None:
+                _expect(t, torch.float32, (F, ecap, w))
+        _expect(exist_counts, torch.int32, (F,))
     kept = torch.empty((F, cap), dtype=torch.int32, device=lead.device)
     nkept = torch.empty((F,), dtype=torch.int32, device=lead.device)
     ptr = lambda t: t.data_ptr() if t is not None else 0   # noqa: E731
@@ -330,19 +344,13 @@ def _image_set(images, rows, cols, channels):
     return PsImageSet(images.data_ptr(), images.stride(1), images.stride(0) if images.shape[0] > 1 else 0, images.shape[0], rows, cols, cn)
 
 
-class KltPyramids:
-    """A device-resident set of `slots` image pyramids with their derivatives (ps_klt_pyramids_create): the images of a sequence,
-    built once, tracked pair by pair.  rows x cols x channels 8-bit images; win_size / max_levels as in _abi.klt_params."""
-
-    def __init__(self, ctx, rows, cols, channels, slots, win_size=7, max_levels=3):
-        self.ctx, self.rows, self.cols, self.channels, self.slots = ctx, int(rows), int(cols), int(channels), int(slots)
-        self.win_size, self.max_levels = int(win_size), int(max_levels)
-        self.handle = ctx.klt_pyramids_create(rows, cols, channels, win_size, max_levels, slots)
-        self.num_levels = int(ctx._L.ps_klt_pyramids_num_levels(self.handle))
+class _Handle:
+    """The owner of one handle of the library (`ctx`, `handle`): close() destroys it once, through the symbol the subclass's
+    `_destroy` names, and so does the collector."""
 
     def close(self):
         if self.handle is not None:
-            self.ctx._L.ps_klt_pyramids_destroy(self.handle)
+            getattr(self.ctx._L, self._destroy)(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -350,6 +358,19 @@ class KltPyramids:
             self.close()
         except Exception:
             pass
+
+
+class KltPyramids(_Handle):
+    """A device-resident set of `slots` image pyramids with their derivatives (ps_klt_pyramids_create): the images of a sequence,
+    built once, tracked pair by pair.  rows x cols x channels 8-bit images; win_size / max_levels as in _abi.klt_params."""
+
+    _destroy = "ps_klt_pyramids_destroy"
+
+    def __init__(self, ctx, rows, cols, channels, slots, win_size=7, max_levels=3):
+        self.ctx, self.rows, self.cols, self.channels, self.slots = ctx, int(rows), int(cols), int(channels), int(slots)
+        self.win_size, self.max_levels = int(win_size), int(max_levels)
+        self.handle = ctx.klt_pyramids_create(rows, cols, channels, win_size, max_levels, slots)
+        self.num_levels = int(ctx._L.ps_klt_pyramids_num_levels(self.handle))
 
     def build(self, images, first_slot=0, use_torch_stream=True):
         """Fills slots first_slot .. from `images`: a uint8 device tensor (F, rows, cols[, channels]) whose rows and frames may
@@ -372,15 +393,12 @@ def track_klt_pairs(ctx, pyr: KltPyramids, pairs, prev_pts, counts, params=None,
     params = params or klt_params(pyr.win_size, pyr.max_levels)
     P, cap = prev_pts.shape[0], prev_pts.shape[1]
     dev = prev_pts.device
-    assert prev_pts.dtype == torch.float32 and prev_pts.shape == (P, cap, 2) and prev_pts.is_contiguous()
-    assert pairs.dtype == torch.int32 and pairs.shape == (P, 2) and pairs.is_contiguous()
-    assert counts.dtype == torch.int32 and counts.shape == (P,) and counts.is_contiguous()
-    next_pts = _zeros(dev, (P, cap, 2), torch.float32) if next_pts is None else next_pts
-    status = _zeros(dev, (P, cap), torch.uint8) if status is None else status
-    err = _zeros(dev, (P, cap), torch.float32) if err is None else err
-    assert next_pts.dtype == torch.float32 and next_pts.shape == (P, cap, 2) and next_pts.is_contiguous()
-    assert status.dtype == torch.uint8 and status.shape == (P, cap) and status.is_contiguous()
-    assert err.dtype == torch.float32 and err.shape == (P, cap) and err.is_contiguous()
+    _expect(prev_pts, torch.float32, (P, cap, 2))
+    _expect(pairs, torch.int32, (P, 2))
+    _expect(counts, torch.int32, (P,))
+    next_pts = _block(next_pts, dev, (P, cap, 2), torch.float32)
+    status = _block(status, dev, (P, cap), torch.uint8)
+    err = _block(err, dev, (P, cap), torch.float32)
     args = (pyr.handle, params, pairs.data_ptr(), prev_pts.data_ptr(), counts.data_ptr(), P, cap, next_pts.data_ptr(),
             status.data_ptr(), err.data_ptr())
     _on_torch_stream(ctx, dev, lambda: ctx.klt_track_device(*args), use_torch_stream)
@@ -393,9 +411,10 @@ def select_tracked(ctx, next_pts, status, err, counts, tracking_error_threshold,
     asynchronously: pair p keeps its first num_matches[p] rows (-1: a count outside 0 .. cap)."""
     P, cap = status.shape
     dev = status.device
-    assert next_pts.dtype == torch.float32 and next_pts.shape == (P, cap, 2) and next_pts.is_contiguous()
-    assert status.dtype == torch.uint8 and status.is_contiguous() and err.dtype == torch.float32 and err.shape == (P, cap) and err.is_contiguous()
-    assert counts.dtype == torch.int32 and counts.shape == (P,) and counts.is_contiguous()
+    _expect(next_pts, torch.float32, (P, cap, 2))
+    _expect(status, torch.uint8, (P, cap))
+    _expect(err, torch.float32, (P, cap))
+    _expect(counts, torch.int32, (P,))
     matches = torch.empty((P, cap, 4), dtype=torch.int32, device=dev)
     num = torch.empty((P,), dtype=torch.int32, device=dev)
     kept_pts = torch.empty((P, cap, 2), dtype=torch.float32, device=dev)
@@ -406,24 +425,15 @@ def select_tracked(ctx, next_pts, status, err, counts, tracking_error_threshold,
     return matches, num, kept_pts, kept_idx
 
 
-class FastDetector:
+class FastDetector(_Handle):
     """A device-resident FAST-9/16 detector for up to `max_frames` images of rows x cols x channels bytes a call
     (ps_fast_detector_create): the grey, score and corner maps of its last call stay readable through maps()."""
+
+    _destroy = "ps_fast_detector_destroy"
 
     def __init__(self, ctx, rows, cols, channels, max_frames):
         self.ctx, self.rows, self.cols, self.channels, self.max_frames = ctx, int(rows), int(cols), int(channels), int(max_frames)
         self.handle = ctx.fast_detector_create(rows, cols, channels, max_frames)
-
-    def close(self):
-        if self.handle is not None:
-            self.ctx._L.ps_fast_detector_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def maps(self, frame):
         """(grey, score, corner) of one frame of the last call, on the host (api.Context.debug_fast_maps)."""
@@ -442,37 +452,25 @@ def detect_features_batch(ctx, det: FastDetector, images, params=None, capacity=
     s = _image_set(images, det.rows, det.cols, det.channels)
     F, dev = images.shape[0], images.device
     cap = int(params.maximalTrackedFeatures) if capacity is None else int(capacity)
-    xy = _zeros(dev, (F, cap, 2), torch.float32) if xy is None else xy
-    response = _zeros(dev, (F, cap), torch.float32) if response is None else response
-    counts = _zeros(dev, (F,), torch.int32) if counts is None else counts
-    assert xy.dtype == torch.float32 and xy.shape == (F, cap, 2) and xy.is_contiguous()
-    assert response.dtype == torch.float32 and response.shape == (F, cap) and response.is_contiguous()
-    assert counts.dtype == torch.int32 and counts.shape == (F,) and counts.is_contiguous()
+    xy = _block(xy, dev, (F, cap, 2), torch.float32)
+    response = _block(response, dev, (F, cap), torch.float32)
+    counts = _block(counts, dev, (F,), torch.int32)
     args = (det.handle, s, params, cap, xy.data_ptr(), response.data_ptr(), counts.data_ptr(), passes)
     _on_torch_stream(ctx, dev, lambda: ctx.detect_features_device(*args), use_torch_stream)
     return xy, response, counts
 
 
-class OrbPyramids:
+class OrbPyramids(_Handle):
     """A device-resident set of `slots` ORB pyramids (ps_orb_pyramids_create): every level raw and blurred, with the sampling
     pattern -- (256, 4) int8 in -15 .. 15, default the library's.  params: _abi.orb_params(...), default cv::ORB::create()'s."""
+
+    _destroy = "ps_orb_pyramids_destroy"
 
     def __init__(self, ctx, rows, cols, channels, slots, params=None, pattern=None):
         self.ctx, self.rows, self.cols, self.channels, self.slots = ctx, int(rows), int(cols), int(channels), int(slots)
         self.params = params or orb_params()
         self.num_levels = int(self.params.nLevels)
         self.handle = ctx.orb_pyramids_create(rows, cols, channels, self.params, pattern, slots)
-
-    def close(self):
-        if self.handle is not None:
-            self.ctx._L.ps_orb_pyramids_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def build(self, images, first_slot=0, use_torch_stream=True, passes=7):
         """Fills slots first_slot .. from `images`: a uint8 device tensor (F, rows, cols[, channels]), the tensor KltPyramids.build
@@ -502,17 +500,14 @@ def describe_features_batch(ctx, pyr: OrbPyramids, slots, xy, angle, octave, cou
     0 .. cap).  desc drops into the binary frame sets."""
     F, cap = xy.shape[0], xy.shape[1]
     dev = xy.device
-    assert xy.dtype == torch.float32 and xy.shape == (F, cap, 2) and xy.is_contiguous()
-    assert angle.dtype == torch.float32 and angle.shape == (F, cap) and angle.is_contiguous()
-    assert octave.dtype == torch.int32 and octave.shape == (F, cap) and octave.is_contiguous()
+    _expect(xy, torch.float32, (F, cap, 2))
+    _expect(angle, torch.float32, (F, cap))
+    _expect(octave, torch.int32, (F, cap))
     for t in (slots, counts):
-        assert t.dtype == torch.int32 and t.shape == (F,) and t.is_contiguous()
-    desc = _zeros(dev, (F, cap, 32), torch.uint8) if desc is None else desc
-    kept_idx = _zeros(dev, (F, cap), torch.int32) if kept_idx is None else kept_idx
-    num_kept = _zeros(dev, (F,), torch.int32) if num_kept is None else num_kept
-    assert desc.dtype == torch.uint8 and desc.shape == (F, cap, 32) and desc.is_contiguous()
-    assert kept_idx.dtype == torch.int32 and kept_idx.shape == (F, cap) and kept_idx.is_contiguous()
-    assert num_kept.dtype == torch.int32 and num_kept.shape == (F,) and num_kept.is_contiguous()
+        _expect(t, torch.int32, (F,))
+    desc = _block(desc, dev, (F, cap, 32), torch.uint8)
+    kept_idx = _block(kept_idx, dev, (F, cap), torch.int32)
+    num_kept = _block(num_kept, dev, (F,), torch.int32)
     args = (pyr.handle, slots.data_ptr(), xy.data_ptr(), angle.data_ptr(), octave.data_ptr(), counts.data_ptr(), F, cap, desc.data_ptr(),
             kept_idx.data_ptr(), num_kept.data_ptr(), passes)
     _on_torch_stream(ctx, dev, lambda: ctx.describe_features_device(*args), use_torch_stream)

@@ -141,3 +141,25 @@ def test_depth_view_bytes_is_where_the_last_row_ends():
     # shapes the call rejects
     assert f(0, 640, 1280) == 0 and f(480, 0, 1280) == 0 and f(-1, 5, 10) == 0 and f(480, 640, 1279) == 0
     assert f(2, 0x7fffffff, 2 * 0x7fffffff) == 2 * 2 * 0x7fffffff     # no 32-bit arithmetic
+
+
+def test_host_image_keeps_a_usable_image_and_copies_the_rest():
+    """api._host_image, the one conversion of a numpy image for the host forms of the image front end: uint8 with dense rows any
+    stride apart is used where it lies, anything else comes back as a dense uint8 copy of equal values."""
+    rng = np.random.default_rng(9)
+    grey = rng.integers(0, 256, (60, 80), dtype=np.uint8)
+    colour = rng.integers(0, 256, (60, 80, 3), dtype=np.uint8)
+    for a, cn in ((grey, 1), (colour, 3)):
+        got, n = api._host_image(a)
+        assert n == cn and got is a and np.shares_memory(got, a) and got.strides == a.strides
+    for parent, cn in ((grey, 1), (colour, 3)):     # a region of a larger image: no copy, the parent's row stride
+        region = parent[2:50, 5:69]
+        got, n = api._host_image(region)
+        assert n == cn and np.shares_memory(got, parent) and got.shape == region.shape and got.strides[0] == parent.strides[0] == 80 * cn
+        assert got.__array_interface__["data"][0] == region.__array_interface__["data"][0]
+    flt = rng.uniform(0.0, 255.0, (60, 80)).astype(np.float32)
+    for what, a in (("column-strided", grey[:, ::2]), ("transposed", grey.T), ("row-reversed", grey[::-1]), ("float", flt),
+                    ("column-strided colour", colour[:, ::2]), ("row-reversed colour", colour[::-1])):
+        got, n = api._host_image(a)
+        assert n == (1 if a.ndim == 2 else 3) and got.dtype == np.uint8 and got.flags["C_CONTIGUOUS"] and got.shape == a.shape, what
+        assert not np.shares_memory(got, a) and np.array_equal(got, a.astype(np.uint8)), what

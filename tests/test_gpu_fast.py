@@ -11,6 +11,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import fast_ref as F  # noqa: E402
+from image_frontend_util import as_hwc, u32, upload_images  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,26 +28,6 @@ def ctx():
 def prm(threshold=10, nms=True, grid_rows=1, grid_cols=1, max_features=500):
     from putslam_amd._abi import detect_params
     return detect_params(threshold, nms, grid_rows, grid_cols, max_features)
-
-
-def as_hwc(img):
-    img = np.asarray(img, np.uint8)
-    return img[..., None] if img.ndim == 2 else img
-
-
-def upload_images(imgs, padded):
-    """(F, rows, cols[, 3]) uint8 on the device: dense, or a view into a block with padded rows and frames."""
-    import torch
-    dev = torch.device("cuda:0")
-    a = np.stack([as_hwc(i) for i in imgs])
-    n, rows, cols, cn = a.shape
-    if not padded:
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    else:
-        block = torch.full((n, rows + 3, cols + 5, cn), 0xEE, dtype=torch.uint8, device=dev)
-        block[:, :rows, :cols] = torch.from_numpy(a).to(dev)
-        t = block[:, :rows, :cols]
-    return t[..., 0] if cn == 1 else t
 
 
 def sentinels(frames, cap):
@@ -74,10 +55,6 @@ def run_device(ctx, imgs, p, cap=None, padded=False, det=None, want_maps=False):
     if own:
         det.close()
     return out
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def assert_frame(got, f, want, what=""):

@@ -10,6 +10,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import klt_ref as K  # noqa: E402
+from image_frontend_util import u32, upload_images  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -31,21 +32,6 @@ def prm(win=7, max_levels=3, max_count=30, eps=0.01, flags=0, min_eig=1e-4):
 def images(rows, cols, cn, shifts, seed=11):
     """One texture sampled at several shifts: frame k carries the flow shifts[k] relative to frame 0."""
     return [K.smooth_texture(rows, cols, cn, seed=seed, shift=(-s[0], -s[1])) for s in shifts]
-
-
-def upload_images(imgs, padded):
-    """(F, rows, cols[, 3]) uint8 on the device: dense, or a view into a block with padded rows and frames."""
-    import torch
-    dev = torch.device("cuda:0")
-    a = np.stack([K.as_hwc(i) for i in imgs])
-    F, rows, cols, cn = a.shape
-    if not padded:
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    else:
-        block = torch.full((F, rows + 3, cols + 5, cn), 0xEE, dtype=torch.uint8, device=dev)
-        block[:, :rows, :cols] = torch.from_numpy(a).to(dev)
-        t = block[:, :rows, :cols]
-    return t[..., 0] if cn == 1 else t
 
 
 def sentinel(shape, dtype):
@@ -88,10 +74,6 @@ def run_device(ctx, imgs, pairs, pts_lists, params, padded=False, init=None, cou
 def ref_track(prev, nxt, pts, params, init=None):
     return K.track(prev, nxt, pts, params.winSize, params.maxLevels, params.maxCount, params.eps, params.flags,
                    params.minEigThreshold, next_pts=init)
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def assert_pair_equal(got, want, n, what=""):

@@ -12,6 +12,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import orb_ref as R  # noqa: E402
+from image_frontend_util import upload_images  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -24,26 +25,6 @@ ROWS, COLS, NL, CAP = 80, 96, 8, 257
 def ctx():
     from putslam_amd import api
     return api.Context(0)
-
-
-def as_hwc(img):
-    img = np.asarray(img, np.uint8)
-    return img[..., None] if img.ndim == 2 else img
-
-
-def upload_images(imgs, padded):
-    """(F, rows, cols[, 3]) uint8 on the device: dense, or a view into a block whose rows and frames are padded with 0xEE."""
-    import torch
-    dev = torch.device("cuda:0")
-    a = np.stack([as_hwc(i) for i in imgs])
-    n, rows, cols, cn = a.shape
-    if not padded:
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    else:
-        block = torch.full((n, rows + 3, cols + 5, cn), 0xEE, dtype=torch.uint8, device=dev)
-        block[:, :rows, :cols] = torch.from_numpy(a).to(dev)
-        t = block[:, :rows, :cols]
-    return t[..., 0] if cn == 1 else t
 
 
 @pytest.mark.parametrize("rows,cols", [(9, 13), (37, 53), (63, 64), (80, 96)])
