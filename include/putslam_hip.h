@@ -896,6 +896,101 @@ int ps_debug_orb_passes(PsContext *ctx, PsOrbPyramids *pyr, const PsImageSet *im
                         const float *angle, const int32_t *octave, const int32_t *counts, int F, int capacity, uint8_t *desc, int32_t *keptIdx,
                         int32_t *numKept, int passes);
 
+/* ---- ORB key point detection: MatcherOpenCV::detectFeatures, src/Matcher/matcherOpenCV.cpp:118-180, for detector = "ORB"
+ * (cv::ORB::create(), :66-67) -- the SHIPPED detector (resources/putslammatcherOpenCVParameters.xml:64) and the first per-frame step
+ * of Matcher::match: cvtColor(RGB2GRAY) (:122), the grid of ROIs (:127-146), the detector in every ROI (:148), the per-ROI ordering
+ * and cut (:155-165), the joined ordering and cut (:169-177).  The arrays it writes are the ones ps_dbscan_thin_device (with
+ * octave) and ps_describe_features_device take.
+ * The arithmetic is the project's reading of OpenCV 3.0 - 3.3's ORB_Impl::detectAndCompute (key points only), computeKeyPoints,
+ * HarrisResponses, ICAngles, KeyPointsFilter and scalar fastAtan2 (restated twice in
+ * tests/orb_detect_ref.py); no OpenCV build was at hand to pin it against -- the reading is UNPINNED.  Integer arithmetic except
+ * where stated; float operations are single IEEE operations without contraction; cvRound rounds half to even:
+ *   grey      the WHOLE image with CV_RGB2GRAY, (c0 * 4899 + c1 * 9617 + c2 * 1868 + 8192) >> 14 -- the FAST detector's weights, not
+ *             the descriptor's; channels == 1: grey already;
+ *   ROIs      the grid of the FAST section above; the detector sees an ROI as an image of its own, so every ROI has ITS OWN pyramid
+ *             of rows / gridRows x cols / gridCols pixels.  Levels, scales and the resize are the ORB descriptor section's; only
+ *             the raw levels are read, nothing is blurred;
+ *   constants edgeThreshold 31, firstLevel 0, HARRIS_SCORE, patchSize 31 (cv::ORB::create()'s);
+ *   quotas    factor = (float)(1.0 / scaleFactor); nd = nFeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)nLevels)) in
+ *             float; for l = 0 .. nLevels-2: q_l = cvRound(nd), nd *= factor; q_last = max(nFeatures - sum q_l, 0)
+ *             (500 / 1.2 / 8: 109 90 75 63 52 44 36 31);
+ *   level l   FAST-9/16 with threshold fastThreshold (clamped to 0 .. 255) and suppression on the level as an image of its own,
+ *             response = score; kept 31 <= x < cols_l - 31, 31 <= y < rows_l - 31 (rows_l or cols_l <= 62: nothing); retainBest(2 q_l)
+ *             by the score: no more than n remain -> all stay, n = 0 -> none, else every key point whose response is >= the n-th
+ *             largest stays: TIES AT THE CUT ARE ALL KEPT, so the surviving set is defined although nth_element's order is not;
+ *   Harris    at the survivor's (x0, y0) in the raw level, block 7, k = 0.04f: over the 49 pixels p with row pitch s,
+ *             Ix = (p[1] - p[-1]) * 2 + (p[-s+1] - p[-s-1]) + (p[s+1] - p[s-1]), Iy = (p[s] - p[-s]) * 2 + (p[s-1] - p[-s-1]) +
+ *             (p[s+1] - p[-s+1]); int a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy; scale = 1.f / (4 * 7 * 255.f), s4 = scale * scale *
+ *             scale * scale (left to right); response = ((fa * fb - fc * fc) - (k * (fa + fb)) * (fa + fb)) * s4 with fa = (float)a
+ *             ..., every operation rounded on its own; then retainBest(q_l) by this response, ties kept;
+ *   angle     the intensity centroid over the disc of half patch 15: umax[0 .. 15] = 15 15 15 15 14 14 14 13 13 12 11 10 9 8 6 3,
+ *             m10 = sum u I(u, v), m01 = sum v I(u, v) over |v| <= 15, |u| <= umax[|v|]; angle = fastAtan2((float)m01, (float)m10);
+ *   fastAtan2 one fixed float sequence, degrees: ax = |x|, ay = |y|, c = min(ax, ay) / (max(ax, ay) + (float)DBL_EPSILON), c2 = c * c,
+ *             a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c with p1, p3, p5, p7 = (float)0.9997878412794807, (float)-0.3258083974640975,
+ *             (float)0.1555786518463281, (float)-0.04432655554792128, each times (float)(180 / pi); a = 90 - a if ax < ay; a = 180 - a
+ *             if x < 0; a = 360 - a if y < 0; (0, 0) gives 0.  Within 0.0096 degrees of atan2 (measured; OpenCV documents 0.3);
+ *   ROI list  levels ascending, raster order (y, then x) inside a level -- THIS ORDER IS THE LIBRARY'S DECISION, the reference's
+ *             nth_element / partition leave it open; pt = (x0 * scale_l, y0 * scale_l) as float products, size 31 * scale_l,
+ *             octave l, class_id -1, angle and the Harris response;
+ *   order     the grid loop of the FAST section: both orderings STABLE by response > (descending floats, negative responses are
+ *             ordinary), the cut to maximalTrackedFeatures * 3 / (gridCols * gridRows) per ROI, the ROI origin added as floats, the
+ *             joined ordering, the cut to maximalTrackedFeatures. */
+typedef struct PsOrbDetectParams {
+    int32_t nFeatures;               /* 0 .. PS_MAX_KPTS; cv::ORB::create(): 500 */
+    float scaleFactor;               /* 1 < scaleFactor <= 2; create(): 1.2f */
+    int32_t nLevels;                 /* 1 .. 8; create(): 8 */
+    int32_t fastThreshold;           /* clamped to 0 .. 255; create(): 20 */
+    int32_t gridRows, gridCols;      /* OpenCVParams.gridRows / gridCols, at least 1 */
+    int32_t maximalTrackedFeatures;  /* OpenCVParams.maximalTrackedFeatures, 0 .. PS_MAX_KPTS */
+    int32_t reserved;                /* must be 0 */
+} PsOrbDetectParams;
+typedef struct PsOrbDetector PsOrbDetector; /* the pyramids (raw and FAST score planes) of every ROI of up to maxFrames images, and the lists */
+size_t ps_abi_sizeof_orb_detect_params(void);
+/* The per-level quotas of `params` (nFeatures, scaleFactor, nLevels), eight int32, 0 beyond nLevels.  Pure host arithmetic, no
+ * context; PS_ERR_BAD_ARG for NULL or parameters outside their ranges. */
+int ps_orb_detect_quotas(const PsOrbDetectParams *params, int32_t *quotas8);
+
+/* A detector for images of rows x cols x channels bytes, up to maxFrames a call.  The grid, scaleFactor and nLevels of `params`
+ * are fixed here: they shape the pyramids, one per (frame, ROI).  A NULL argument, a parameter outside its range, channels other
+ * than 1 or 3, an empty ROI or level, maxFrames x gridRows x gridCols outside 1 .. 65535 -> PS_ERR_BAD_ARG; rows or cols above
+ * 8192, nFeatures or maximalTrackedFeatures above PS_MAX_KPTS -> PS_ERR_UNSUPPORTED.  Synchronous (allocates).  destroy waits for
+ * the device; NULL is harmless. */
+int ps_orb_detector_create(PsContext *ctx, int rows, int cols, int channels, const PsOrbDetectParams *params, int maxFrames,
+                           PsOrbDetector **out);
+void ps_orb_detector_destroy(PsOrbDetector *det);
+/* dims2 = {rows, cols} and the scale of one level of an ROI's pyramid (either may be NULL); PS_ERR_BAD_ARG for NULL or no such
+ * level.  No context. */
+int ps_orb_detector_level(const PsOrbDetector *det, int level, int32_t *dims2, float *scale);
+/* detectFeatures for every frame of a device-resident set.  xy numFrames x capacity x 2 floats, response and angle numFrames x
+ * capacity floats, octave numFrames x capacity int32, counts numFrames int32 -- all DEVICE; frame f's counts[f] key points fill its
+ * first rows in the final order, nothing beyond them is written.  The layout is the one ps_dbscan_thin_device and
+ * ps_describe_features_device take: no repacking step in between.  params: nFeatures, fastThreshold and maximalTrackedFeatures are
+ * this call's; scaleFactor, nLevels, gridRows and gridCols must be the detector's.  Asynchronous on the context's stream, except
+ * that a call which needs more room for its ROI lists than any call before allocates first, which waits for the device.
+ * NULL where an array is needed, a parameter outside its range or other than the detector's, a shape or stride that does not fit
+ * the detector, numFrames < 0 or above maxFrames, capacity < min(maximalTrackedFeatures, what the ROIs can emit) -> PS_ERR_BAD_ARG
+ * (text: ps_last_error); nFeatures, maximalTrackedFeatures or capacity above PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; outputs untouched.
+ * numFrames == 0 is PS_OK. */
+int ps_orb_detect_frames(PsContext *ctx, PsOrbDetector *det, const PsImageSet *images, const PsOrbDetectParams *params, int capacity,
+                         float *xy, float *response, float *angle, int32_t *octave, int32_t *counts);
+/* detectFeatures for one image: HOST pointers, upload included, synchronous.  img rows x cols x channels bytes, rowStride bytes
+ * between rows (0 = dense; a region of a larger image keeps its parent's).  xy cap x 2 floats, response / angle cap floats, octave
+ * cap int32, *nout the number found.  Returns PS_ERR_BAD_ARG with *nout = required capacity if cap is too small (nothing else is
+ * written); other errors as above, *nout untouched. */
+int ps_detect_features_orb(PsContext *ctx, const uint8_t *img, int rows, int cols, int channels, size_t rowStride,
+                           const PsOrbDetectParams *params, float *xy, float *response, float *angle, int32_t *octave, int cap, int *nout);
+/* Diagnostic (no reference counterpart): one level of one slot (slot = frame * gridRows * gridCols + ROI in loop order) of the
+ * detector's LAST call read back to the HOST: the raw level and its FAST score plane, rows_l x cols_l bytes each; *numFirst the
+ * survivors of the first cut, and the first min(*numFirst, cap) of them in raster order: yx = y << 16 | x, their Harris response and
+ * angle, and kept = 1 where the second cut keeps them.  Any pointer may be NULL.  Waits for the context's stream. */
+int ps_debug_orb_detect_level(PsContext *ctx, const PsOrbDetector *det, int slot, int level, uint8_t *raw, uint8_t *score, int32_t *numFirst,
+                              uint32_t *yx, float *response, float *angle, uint8_t *kept, int cap);
+/* Diagnostic (no reference counterpart; profiles/scripts/orb_detect_times.py times each pass alone with it): ps_orb_detect_frames
+ * with only the passes of the mask queued -- 1 the pyramids, 2 the FAST scores, 4 the first cut, 8 Harris and angle, 16 the second
+ * cut and the ROI ordering, 32 the join.  A pass reads what the passes before it left: call with 63 first. */
+int ps_debug_orb_detect_passes(PsContext *ctx, PsOrbDetector *det, const PsImageSet *images, const PsOrbDetectParams *params, int capacity,
+                               float *xy, float *response, float *angle, int32_t *octave, int32_t *counts, int passes);
+
 /* ---- Loop-closure candidates verified in one batch from the resident store: what the loop-closure thread does per candidate
  * (poseA, poseB) of FABMAP's priority queue -- FeaturesMap::loopClosure (src/Map/featuresMap.cpp:733-873) around
  * Matcher::matchFeatureLoopClosure (src/Matcher/matcher.cpp:802-861) -- for L candidates as two calls, no host step.

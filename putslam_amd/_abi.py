@@ -207,6 +207,20 @@ def orb_params(scale_factor=1.2, n_levels=8):
     return PsOrbParams(float(scale_factor), int(n_levels), (C.c_int32 * 2)(0, 0))
 
 
+# ORB key point detection (include/putslam_hip.h)
+class PsOrbDetectParams(C.Structure):
+    _fields_ = [("nFeatures", C.c_int32), ("scaleFactor", C.c_float), ("nLevels", C.c_int32), ("fastThreshold", C.c_int32),
+                ("gridRows", C.c_int32), ("gridCols", C.c_int32), ("maximalTrackedFeatures", C.c_int32), ("reserved", C.c_int32)]
+
+
+def orb_detect_params(n_features=500, scale_factor=1.2, n_levels=8, fast_threshold=20, grid_rows=1, grid_cols=1,
+                      maximal_tracked_features=500):
+    """PsOrbDetectParams; the defaults are cv::ORB::create()'s (500 features, scaleFactor 1.2f, 8 levels, fastThreshold 20) and the
+    shipped OpenCVParams (gridRows = gridCols = 1, maximalTrackedFeatures 500)."""
+    return PsOrbDetectParams(int(n_features), float(scale_factor), int(n_levels), int(fast_threshold), int(grid_rows), int(grid_cols),
+                             int(maximal_tracked_features), 0)
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

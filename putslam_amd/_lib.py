@@ -8,7 +8,7 @@ import os
 
 from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch,
                    PsMapBatchF32, PsMapStore, PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPairResults, PsPoseSetOut,
-                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams, PsOrbParams)
+                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams, PsOrbParams, PsOrbDetectParams)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -55,6 +55,8 @@ EXPORTED = [
     "ps_abi_sizeof_detect_params",
     "ps_orb_pattern_default", "ps_orb_pyramids_create", "ps_orb_pyramids_destroy", "ps_orb_pyramids_level", "ps_orb_pyramids_build_device",
     "ps_describe_features_device", "ps_describe_features", "ps_debug_orb_level", "ps_debug_orb_passes", "ps_abi_sizeof_orb_params",
+    "ps_orb_detector_create", "ps_orb_detector_destroy", "ps_orb_detector_level", "ps_orb_detect_quotas", "ps_orb_detect_frames",
+    "ps_detect_features_orb", "ps_debug_orb_detect_level", "ps_debug_orb_detect_passes", "ps_abi_sizeof_orb_detect_params",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -72,6 +74,7 @@ ABI_STRUCTS_KLT = dict(klt_params=PsKltParams, image_set=PsImageSet)
 # ... and of the FAST detector (ps_fast_detector_* / ps_detect_features)
 ABI_STRUCTS_DETECT = dict(detect_params=PsDetectParams)
 ABI_STRUCTS_ORB = dict(orb_params=PsOrbParams)
+ABI_STRUCTS_ORB_DETECT = dict(orb_detect_params=PsOrbDetectParams)
 
 _lib = None
 _by_path = {}
@@ -289,8 +292,17 @@ def load_path(path):
     L.ps_describe_features.argtypes = [vp, vp, i32, i32, i32, sz, C.POINTER(PsOrbParams), vp, vp, vp, vp, i32, vp, vp, C.POINTER(i32)]
     L.ps_debug_orb_level.argtypes = [vp, vp, i32, i32, vp, vp]
     L.ps_debug_orb_passes.argtypes = [vp, vp, C.POINTER(PsImageSet), i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32]
+    L.ps_orb_detector_create.argtypes = [vp, i32, i32, i32, C.POINTER(PsOrbDetectParams), i32, C.POINTER(vp)]
+    L.ps_orb_detector_destroy.argtypes = [vp]
+    L.ps_orb_detector_destroy.restype = None
+    L.ps_orb_detector_level.argtypes = [vp, i32, vp, C.POINTER(C.c_float)]
+    L.ps_orb_detect_quotas.argtypes = [C.POINTER(PsOrbDetectParams), vp]
+    L.ps_orb_detect_frames.argtypes = [vp, vp, C.POINTER(PsImageSet), C.POINTER(PsOrbDetectParams), i32, vp, vp, vp, vp, vp]
+    L.ps_detect_features_orb.argtypes = [vp, vp, i32, i32, i32, sz, C.POINTER(PsOrbDetectParams), vp, vp, vp, vp, i32, C.POINTER(i32)]
+    L.ps_debug_orb_detect_level.argtypes = [vp, vp, i32, i32, vp, vp, C.POINTER(i32), vp, vp, vp, vp, i32]
+    L.ps_debug_orb_detect_passes.argtypes = [vp, vp, C.POINTER(PsImageSet), C.POINTER(PsOrbDetectParams), i32, vp, vp, vp, vp, vp, i32]
     for n in (list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT) + list(ABI_STRUCTS_DETECT)
-              + list(ABI_STRUCTS_ORB)):
+              + list(ABI_STRUCTS_ORB) + list(ABI_STRUCTS_ORB_DETECT)):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -318,3 +330,7 @@ def struct_sizes_detect():
 
 def struct_sizes_orb():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_ORB.items()}
+
+
+def struct_sizes_orb_detect():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_ORB_DETECT.items()}

@@ -12,7 +12,8 @@ from . import _lib
 from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, PS_SET_INVALID, PsExclusionRule, PsFrameSet,  # noqa: F401
                    PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch, PsMapBatchF32, PsPairResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config,
-                   PsImageSet, PsKltParams, klt_params, PsDetectParams, detect_params, PsOrbParams, orb_params)
+                   PsImageSet, PsKltParams, klt_params, PsDetectParams, detect_params, PsOrbParams, orb_params,
+                   PsOrbDetectParams, orb_detect_params)
 
 
 class PsError(RuntimeError):
@@ -567,6 +568,63 @@ class Context:
         maps = [np.zeros((int(rows), int(cols)), np.uint8) for _ in range(3)]
         self._chk(self._L.ps_debug_fast_maps(self._h, det, int(frame), _p(maps[0]), _p(maps[1]), _p(maps[2])))
         return tuple(maps)
+
+    # ---- ORB key point detection (ps_orb_detect.h) ----
+    def detect_features_orb(self, image, params: PsOrbDetectParams = None):
+        """MatcherOpenCV::detectFeatures for detector = "ORB" (ps_detect_features_orb) on a numpy image (rows, cols) or (rows, cols, 3)
+        uint8, whose rows may lie any stride apart (a region of a larger image).  params: _abi.orb_detect_params(...), default the
+        shipped ones.  Returns (xy (n, 2) float32, response (n,) float32 -- Harris --, angle (n,) float32 degrees, octave (n,) int32)
+        in the final order: response descending, ties in the order (level, raster position) inside an ROI and in the order of the
+        ROI loop across ROIs."""
+        params = params or orb_detect_params()
+        image, cn = _host_image(image)
+        cap = max(0, min(int(params.maximalTrackedFeatures), PS_MAX_KPTS))
+        m = max(cap, 1)
+        xy, response, angle, octave = np.zeros((m, 2), np.float32), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.int32)
+        n = C.c_int(0)
+        self._chk(self._L.ps_detect_features_orb(self._h, _p(image), image.shape[0], image.shape[1], cn, image.strides[0], C.byref(params),
+                                                 _p(xy), _p(response), _p(angle), _p(octave), cap, C.byref(n)))
+        k = n.value
+        return xy[:k].copy(), response[:k].copy(), angle[:k].copy(), octave[:k].copy()
+
+    def orb_detector_create(self, rows, cols, channels, params: PsOrbDetectParams, max_frames):
+        """ps_orb_detector_create: the handle of a device-resident detector (device_batch.OrbDetector owns one)."""
+        h = C.c_void_p()
+        self._chk(self._L.ps_orb_detector_create(self._h, int(rows), int(cols), int(channels), C.byref(params), int(max_frames), C.byref(h)))
+        return h
+
+    def orb_detector_level(self, det, level):
+        """ps_orb_detector_level: ((rows, cols), scale float32) of one level of an ROI's pyramid."""
+        dims, scale = np.zeros(2, np.int32), C.c_float(0)
+        if self._L.ps_orb_detector_level(det, int(level), _p(dims), C.byref(scale)) != PS_OK:
+            raise PsError(-1, "ps_orb_detector_level: no such level")
+        return (int(dims[0]), int(dims[1])), np.float32(scale.value)
+
+    def orb_detect_frames(self, det, images: PsImageSet, params: PsOrbDetectParams, capacity, xy_ptr, response_ptr, angle_ptr, octave_ptr,
+                          counts_ptr, passes=63):
+        """ps_orb_detect_frames on device pointers (asynchronous on the context's stream): device_batch.detect_features_orb_batch.
+        passes other than 63: ps_debug_orb_detect_passes, only the passes of the mask, for timing."""
+        args = (self._h, det, C.byref(images), C.byref(params), int(capacity), _v(xy_ptr), _v(response_ptr), _v(angle_ptr), _v(octave_ptr),
+                _v(counts_ptr))
+        if passes == 63:
+            self._chk(self._L.ps_orb_detect_frames(*args))
+        else:
+            self._chk(self._L.ps_debug_orb_detect_passes(*args, int(passes)))
+
+    def debug_orb_detect_level(self, det, slot, level):
+        """ps_debug_orb_detect_level: dict(raw, score (rows_l, cols_l) uint8; yx (n,) uint32 = y << 16 | x, response, angle (n,)
+        float32, kept (n,) uint8) of one level of one slot of the detector's last call: the survivors of the first cut in raster
+        order, kept = 1 where the second cut keeps them."""
+        (rows, cols), _ = self.orb_detector_level(det, level)
+        raw, score = np.zeros((rows, cols), np.uint8), np.zeros((rows, cols), np.uint8)
+        n = C.c_int32(0)
+        self._chk(self._L.ps_debug_orb_detect_level(self._h, det, int(slot), int(level), _p(raw), _p(score), C.byref(n), None, None, None, None, 0))
+        m = max(n.value, 1)
+        yx, resp, ang, kept = np.zeros(m, np.uint32), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.uint8)
+        self._chk(self._L.ps_debug_orb_detect_level(self._h, det, int(slot), int(level), None, None, C.byref(n), _p(yx), _p(resp), _p(ang),
+                                                    _p(kept), m))
+        k = n.value
+        return dict(raw=raw, score=score, yx=yx[:k], response=resp[:k], angle=ang[:k], kept=kept[:k])
 
     # ---- ORB descriptor extraction (ps_orb.h) ----
     def describe_features(self, image, xy, angle=None, octave=None, params: PsOrbParams = None, pattern=None):

@@ -1222,7 +1222,62 @@ std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &m
     return matches;
 }
 
-std::vector<cv::KeyPoint> FrameMatcherHIP::detectFeatures(cv::Mat rgbImage) { return detectFeaturesFAST(matcherParameters, rgbImage); }
+// the detector of matcherOpenCV.cpp:64-67 by its name: "ORB" (the shipped one) and "FAST" run on the device, anything else is refused
+std::vector<cv::KeyPoint> FrameMatcherHIP::detectFeatures(cv::Mat rgbImage)
+{
+    const std::string &detector = matcherParameters.OpenCVParams.detector;
+    if (detector == "ORB") return detectFeaturesORB(matcherParameters, rgbImage);
+    if (detector == "FAST") return detectFeaturesFAST(matcherParameters, rgbImage);
+    std::cerr << "putslam_hip: detectFeatures runs detector \"ORB\" and detector \"FAST\" only (asked for \"" << detector
+              << "\"): no key points; SURF / SIFT detection stays with OpenCV on the host" << std::endl;
+    return std::vector<cv::KeyPoint>();
+}
+
+// MatcherOpenCV::detectFeatures, matcherOpenCV.cpp:118-180, for the detector of :66-67, cv::ORB::create()
+std::vector<cv::KeyPoint> detectFeaturesORB(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat rgbImage)
+{
+    std::vector<cv::KeyPoint> keypoints;
+    const auto &cvp = matcherParameters.OpenCVParams;
+    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3)) {
+        std::cerr << "putslam_hip: detectFeatures takes a CV_8UC1 or CV_8UC3 image" << std::endl;
+        return keypoints;
+    }
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return keypoints;
+    PsOrbDetectParams prm;
+    prm.nFeatures = 500; // cv::ORB::create()'s defaults (:67)
+    prm.scaleFactor = 1.2f;
+    prm.nLevels = 8;
+    prm.fastThreshold = 20;
+    prm.gridRows = cvp.gridRows;
+    prm.gridCols = cvp.gridCols;
+    prm.maximalTrackedFeatures = cvp.maximalTrackedFeatures;
+    prm.reserved = 0;
+    const int cap = cvp.maximalTrackedFeatures > 0 ? cvp.maximalTrackedFeatures : 0;
+    std::vector<cv::Point2f> xy((size_t)cap);
+    std::vector<float> response((size_t)cap), angle((size_t)cap);
+    std::vector<int32_t> octave((size_t)cap);
+    int n = 0;
+    status = ps_detect_features_orb(ctx, rgbImage.data, rgbImage.rows, rgbImage.cols, rgbImage.channels(), (size_t)rgbImage.step, &prm,
+                                    reinterpret_cast<float *>(xy.data()), response.data(), angle.data(), octave.data(), cap, &n);
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        return keypoints;
+    }
+    keypoints.resize((size_t)n);
+    for (int j = 0; j < n; ++j) { // size = patchSize * scale of the level, class_id -1
+        cv::KeyPoint &kp = keypoints[(size_t)j];
+        kp.pt = xy[(size_t)j];
+        kp.size = 31.f * (float)std::pow((double)prm.scaleFactor, (double)octave[(size_t)j]);
+        kp.angle = angle[(size_t)j];
+        kp.response = response[(size_t)j];
+        kp.octave = octave[(size_t)j];
+        kp.class_id = -1;
+    }
+    if (matcherParameters.verbose > 1) std::cout << "MatcherOpenCV: After joining we have " << keypoints.size() << " keypoints" << std::endl;
+    return keypoints;
+}
 
 // MatcherOpenCV::detectFeatures, matcherOpenCV.cpp:118-180, for the detector of :64-65
 std::vector<cv::KeyPoint> detectFeaturesFAST(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat rgbImage)
@@ -1230,8 +1285,8 @@ std::vector<cv::KeyPoint> detectFeaturesFAST(const FrameMatcher::MatcherParamete
     std::vector<cv::KeyPoint> keypoints;
     const auto &cvp = matcherParameters.OpenCVParams;
     if (cvp.detector != "FAST") {
-        std::cerr << "putslam_hip: detectFeatures runs detector \"FAST\" only (asked for \"" << cvp.detector
-                  << "\"): no key points; ORB / SURF / SIFT detection stays with OpenCV on the host" << std::endl;
+        std::cerr << "putslam_hip: detectFeaturesFAST runs detector \"FAST\" only (asked for \"" << cvp.detector << "\"): no key points"
+                  << std::endl;
         return keypoints;
     }
     if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3)) {

@@ -199,7 +199,7 @@ class FrameMatcher {
             float eps = 0.01f;
             double trackingErrorThreshold = 25.0, trackingMinEigThreshold = 0.0;
             int trackingErrorType = 0;
-            // the detector's block (matcher.h:40,43,51; putslammatcherOpenCVParameters.xml:64,67): detectFeatures below runs "FAST"
+            // the detector's block (matcher.h:40,43,51; putslammatcherOpenCVParameters.xml:64,67): detectFeatures below runs "ORB" and "FAST"
             std::string detector = "ORB";
             int gridRows = 1, gridCols = 1;
             int maximalTrackedFeatures = 500;
@@ -380,8 +380,14 @@ std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &m
 // BOTH orderings are STABLE here: the reference's std::sort (compare_response, matcherOpenCV.h:84-87) leaves the order of equal
 // responses, and who survives a cut inside a tie, to its libstdc++; this library keeps raster order inside an ROI and the order
 // of the ROI loop across ROIs (include/putslam_hip.h).
-// Any other detector (ORB, SURF, SIFT) is NOT run on the CPU instead: one line goes to std::cerr and the list comes back empty.
+// Any other detector is NOT run here: one line goes to std::cerr and the list comes back empty.
 std::vector<cv::KeyPoint> detectFeaturesFAST(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat rgbImage);
+// MatcherOpenCV::detectFeatures for OpenCVParams.detector == "ORB" (cv::ORB::create(), :66-67), the SHIPPED detector: the same grid
+// loop around ORB detection with create()'s defaults (500 features, scaleFactor 1.2f, 8 levels, fastThreshold 20) through
+// ps_detect_features_orb (include/putslam_hip.h).  Every ROI has its own pyramid.  A key point is (pt in
+// image coordinates, size 31 * scale of its level, angle in degrees, the Harris response, octave = level, class_id -1): what
+// describeFeaturesORB below and DBScan take.  The detector's name is not looked at (FrameMatcherHIP::detectFeatures dispatches on it).
+std::vector<cv::KeyPoint> detectFeaturesORB(const FrameMatcher::MatcherParameters &matcherParameters, cv::Mat rgbImage);
 
 // MatcherOpenCV::describeFeatures (matcherOpenCV.cpp:183-195) for OpenCVParams.descriptor == "ORB" (cv::ORB::create(): scaleFactor
 // 1.2f, 8 levels) as a free function over the calling thread's context (ps_describe_features): descriptorExtractor->compute(rgbImage,
@@ -425,7 +431,7 @@ class FrameMatcherHIP : public FrameMatcher {
                                                     std::vector<cv::Point2f> &features, std::vector<cv::KeyPoint> &prevKeyPoints,
                                                     std::vector<cv::KeyPoint> &keyPoints, std::vector<double> &prevDetDists,
                                                     std::vector<double> &detDists);
-    // MatcherOpenCV::detectFeatures, matcherOpenCV.cpp:118-180 (the reference's signature; detectFeaturesFAST above)
+    // MatcherOpenCV::detectFeatures, matcherOpenCV.cpp:118-180 (the reference's signature; detectFeaturesORB / detectFeaturesFAST above by OpenCVParams.detector)
     virtual std::vector<cv::KeyPoint> detectFeatures(cv::Mat rgbImage);
     // MatcherOpenCV::describeFeatures, matcherOpenCV.cpp:183-195 (the reference's signature; describeFeaturesORB above)
     virtual cv::Mat describeFeatures(cv::Mat rgbImage, std::vector<cv::KeyPoint> &features);

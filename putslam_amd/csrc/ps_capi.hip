@@ -1262,6 +1262,7 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
 #include "ps_klt.h"          // ps_klt_pyramids_* / ps_klt_track_device / ps_klt_select_device / ps_perform_tracking (ps_exclusion.h's bound)
 #include "ps_fast.h"         // ps_fast_detector_* / ps_detect_features(_device) (the PsImageSet rule of all three: ps_glue.h, ps_image_rule.h)
 #include "ps_orb.h"          // ps_orb_pyramids_* / ps_describe_features(_device) (ps_fast.h's stable counting sort)
+#include "ps_orb_detect.h"   // ps_orb_detector_* / ps_orb_detect_frames / ps_detect_features_orb (ps_fast.h's tile body, ps_orb.h's levels)
 
 // Launch attributes of the kernels that need them (ps_internal.h; called once per context).
 extern "C" void psi_kernel_attributes(void)

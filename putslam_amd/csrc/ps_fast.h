@@ -117,15 +117,19 @@ PS_D void fast_pixel(const uint8_t (*tile)[kFastLds + 2], int cy, int cx, int t,
     }
 }
 
-// Grey, score and corner planes of every frame f of the set: one work-group per 32 x 32 tile.
-__global__ __launch_bounds__(kFastBlock) void ps_fast_score(const uint8_t *__restrict__ src, size_t rowStride, size_t frameStride, int cn,
-                                                            FastGeom g, int t, uint8_t *__restrict__ gray, uint8_t *__restrict__ score,
-                                                            uint8_t *__restrict__ corner, size_t plane)
+// LDS of one tile of the score pass
+struct FastTileLds {
+    uint8_t tile[kFastLds][kFastLds + 2];
+    uint8_t colOk[kFastTile], rowOk[kFastTile];
+};
+
+// The 32 x 32 tile at (tx0, ty0) of ONE image `img` (rows rowStride bytes apart, cn channels) of g.rows x g.cols pixels: its grey,
+// score and corner bytes go to dense planes of g.cols bytes a row.  gray / corner may be null (ps_orb_detect.h scores a pyramid
+// level, which is grey already and needs no corner plane).
+PS_D void fast_score_tile(FastTileLds &s, const uint8_t *__restrict__ img, size_t rowStride, int cn, const FastGeom &g, int t, int tx0,
+                          int ty0, uint8_t *__restrict__ gray, uint8_t *__restrict__ score, uint8_t *__restrict__ corner)
 {
-    __shared__ uint8_t tile[kFastLds][kFastLds + 2];
-    __shared__ uint8_t colOk[kFastTile], rowOk[kFastTile];
-    const int tid = (int)threadIdx.x, tx0 = (int)blockIdx.x * kFastTile, ty0 = (int)blockIdx.y * kFastTile, f = (int)blockIdx.z;
-    const uint8_t *img = src + (size_t)f * frameStride;
+    const int tid = (int)threadIdx.x;
     for (int e = tid; e < kFastLds * kFastLds; e += kFastBlock) {
         const int ly = e / kFastLds, lx = e % kFastLds;
         const int x = tx0 + lx - 3, y = ty0 + ly - 3;
@@ -135,7 +139,7 @@ __global__ __launch_bounds__(kFastBlock) void ps_fast_score(const uint8_t *__res
             // (CV_RGB2GRAY: channel 0 weighs 4899 here, 1868 in ps_orb.h's orb_gray -- intended)
             v = cn == 1 ? (int)p[0] : ((int)p[0] * 4899 + (int)p[1] * 9617 + (int)p[2] * 1868 + 8192) >> 14;
         }
-        tile[ly][lx] = (uint8_t)v;
+        s.tile[ly][lx] = (uint8_t)v;
     }
     if (tid < 2 * kFastTile) { // which columns / rows of the tile are candidates of their ROI
         const bool row = tid >= kFastTile;
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(kFastBlock) void ps_fast_score(const uint8_t *__res
             const int o = fast_axis_offset(p, n, row ? g.gridRows : g.gridCols);
             ok = o >= 3 && o <= roi - 4;
         }
-        (row ? rowOk : colOk)[i] = ok;
+        (row ? s.rowOk : s.colOk)[i] = ok;
     }
     __syncthreads();
     const int lx = tid & (kFastTile - 1), x = tx0 + lx;
@@ -154,12 +158,23 @@ __global__ __launch_bounds__(kFastBlock) void ps_fast_score(const uint8_t *__res
         const int y = ty0 + ly;
         if (y >= g.rows) break;
         int sc = 0, cr = 0;
-        if (colOk[lx] && rowOk[ly]) fast_pixel(tile, ly + 3, lx + 3, t, sc, cr);
-        const size_t o = (size_t)f * plane + (size_t)y * g.cols + x;
-        gray[o] = tile[ly + 3][lx + 3];
+        if (s.colOk[lx] && s.rowOk[ly]) fast_pixel(s.tile, ly + 3, lx + 3, t, sc, cr);
+        const size_t o = (size_t)y * g.cols + x;
+        if (gray) gray[o] = s.tile[ly + 3][lx + 3];
         score[o] = (uint8_t)sc;
-        corner[o] = (uint8_t)cr;
+        if (corner) corner[o] = (uint8_t)cr;
     }
+}
+
+// Grey, score and corner planes of every frame f of the set: one work-group per 32 x 32 tile.
+__global__ __launch_bounds__(kFastBlock) void ps_fast_score(const uint8_t *__restrict__ src, size_t rowStride, size_t frameStride, int cn,
+                                                            FastGeom g, int t, uint8_t *__restrict__ gray, uint8_t *__restrict__ score,
+                                                            uint8_t *__restrict__ corner, size_t plane)
+{
+    __shared__ FastTileLds s;
+    const size_t f = blockIdx.z;
+    fast_score_tile(s, src + f * frameStride, rowStride, cn, g, t, (int)blockIdx.x * kFastTile, (int)blockIdx.y * kFastTile, gray + f * plane,
+                    score + f * plane, corner + f * plane);
 }
 
 // LDS of the counting sort one work-group runs

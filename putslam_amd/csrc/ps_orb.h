@@ -91,10 +91,22 @@ PS_D void orb_rotation(float deg, float &a, float &b)
     b = k == 0 ? s : (k == 1 ? c : (k == 2 ? -s : -c));
 }
 
-// (COLOR_BGR2GRAY: channel 0 weighs 1868 here, 4899 in ps_fast.h's ps_fast_score -- intended)
-PS_D int orb_gray(const uint8_t *p, int cn)
+// Where level 0 of a slot comes from: window q = slot % (gridRows * gridCols) of the grid of matcherOpenCV.cpp:133-146 over frame
+// slot / (gridRows * gridCols) -- columns outer, rows inner, origin (k * cols / gridCols, i * rows / gridRows) -- and the weights
+// of channels 0 and 2.  Description takes the whole image with COLOR_BGR2GRAY (channel 0 weighs 1868 here, 4899 in ps_fast.h's
+// ps_fast_score -- intended); detection (ps_orb_detect.h) takes every ROI with CV_RGB2GRAY.
+struct OrbWindow {
+    int gridRows, gridCols, rows, cols; // the grid and the PARENT image's shape
+    int w0, w2;
+};
+inline OrbWindow orb_whole_bgr(int rows, int cols) // (host)
 {
-    return cn == 1 ? (int)p[0] : ((int)p[0] * 1868 + (int)p[1] * 9617 + (int)p[2] * 4899 + 8192) >> 14;
+    return OrbWindow{1, 1, rows, cols, 1868, 4899};
+}
+
+PS_D int orb_gray(const uint8_t *p, int cn, int w0, int w2)
+{
+    return cn == 1 ? (int)p[0] : ((int)p[0] * w0 + (int)p[1] * 9617 + (int)p[2] * w2 + 8192) >> 14;
 }
 
 // four pixels e .. e + 3 of a dense plane of n bytes: one word where all four exist (planes start 16-byte aligned)
@@ -111,17 +123,20 @@ PS_D void orb_store4(uint8_t *plane, unsigned e, unsigned n, const int v[4])
 
 // Level 0 of slots firstSlot .. of the set: the grey image, four pixels a thread
 __global__ __launch_bounds__(kOrbBlock) void ps_orb_level0(const uint8_t *__restrict__ src, size_t rowStride, size_t frameStride, int cn,
-                                                           OrbLevel lv, uint8_t *__restrict__ planes, size_t slotBytes, int firstSlot)
+                                                           OrbWindow win, OrbLevel lv, uint8_t *__restrict__ planes, size_t slotBytes,
+                                                           int firstSlot)
 {
     const unsigned n = (unsigned)lv.rows * (unsigned)lv.cols, e = ((unsigned)blockIdx.x * kOrbBlock + threadIdx.x) * 4u;
     if (e >= n) return;
-    const int f = (int)blockIdx.y;
-    const uint8_t *img = src + (size_t)f * frameStride;
+    const int f = (int)blockIdx.y; // the slot, counted from firstSlot
+    const int cells = win.gridRows * win.gridCols, q = f % cells, wk = q / win.gridRows, wi = q - wk * win.gridRows;
+    const uint8_t *img = src + (size_t)(f / cells) * frameStride + (size_t)(wi * win.rows / win.gridRows) * rowStride +
+                         (size_t)(wk * win.cols / win.gridCols) * cn;
     int y = (int)(e / (unsigned)lv.cols), x = (int)(e - (unsigned)y * (unsigned)lv.cols);
     int v[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        if (e + k < n) v[k] = orb_gray(img + (size_t)y * rowStride + (size_t)x * cn, cn);
+        if (e + k < n) v[k] = orb_gray(img + (size_t)y * rowStride + (size_t)x * cn, cn, win.w0, win.w2);
         if (++x == lv.cols) {
             x = 0;
             ++y;
@@ -387,8 +402,8 @@ int orb_build_launch(PsContext *ctx, PsOrbPyramids *pyr, const uint8_t *pixels, 
     for (int l = 0; l < pyr->nLevels; ++l) {
         const OrbLevel &lv = pyr->lv[l];
         if (l == 0 && (passes & kOrbPassLevel0)) {
-            hipLaunchKernelGGL(ps_orb_level0, grid(lv), dim3(kOrbBlock), 0, ctx->stream, pixels, rowStride, frameStride, pyr->cn, lv, pyr->planes,
-                               pyr->slotBytes, firstSlot);
+            hipLaunchKernelGGL(ps_orb_level0, grid(lv), dim3(kOrbBlock), 0, ctx->stream, pixels, rowStride, frameStride, pyr->cn,
+                               orb_whole_bgr(pyr->rows, pyr->cols), lv, pyr->planes, pyr->slotBytes, firstSlot);
             PS_HIP(hipGetLastError());
         }
         if (l > 0 && (passes & kOrbPassResize)) {

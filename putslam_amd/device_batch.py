@@ -9,7 +9,7 @@ import torch
 from . import api
 from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
-                   make_config, PsImageSet, klt_params, detect_params, orb_params)
+                   make_config, PsImageSet, klt_params, detect_params, orb_params, orb_detect_params)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -458,6 +458,54 @@ def detect_features_batch(ctx, det: FastDetector, images, params=None, capacity=
     args = (det.handle, s, params, cap, xy.data_ptr(), response.data_ptr(), counts.data_ptr(), passes)
     _on_torch_stream(ctx, dev, lambda: ctx.detect_features_device(*args), use_torch_stream)
     return xy, response, counts
+
+
+class OrbDetector(_Handle):
+    """A device-resident ORB detector for up to `max_frames` images of rows x cols x channels bytes a call (ps_orb_detector_create):
+    one pyramid per (frame, ROI) of the grid of `params` (_abi.orb_detect_params(...), default the shipped ones), whose
+    scaleFactor, nLevels, gridRows and gridCols are fixed here.  The planes and survivor lists of its last call stay readable
+    through level()."""
+
+    _destroy = "ps_orb_detector_destroy"
+
+    def __init__(self, ctx, rows, cols, channels, max_frames, params=None):
+        self.ctx, self.rows, self.cols, self.channels, self.max_frames = ctx, int(rows), int(cols), int(channels), int(max_frames)
+        self.params = params or orb_detect_params()
+        self.num_levels = int(self.params.nLevels)
+        self.num_rois = int(self.params.gridRows) * int(self.params.gridCols)
+        self.handle = ctx.orb_detector_create(rows, cols, channels, self.params, max_frames)
+
+    def level_shape(self, level):
+        """((rows, cols), scale float32) of one level of an ROI's pyramid (ps_orb_detector_level)."""
+        return self.ctx.orb_detector_level(self.handle, level)
+
+    def level(self, frame, roi, level):
+        """The planes and lists of one level of ROI `roi` (loop order) of frame `frame` of the last call, on the host
+        (api.Context.debug_orb_detect_level)."""
+        return self.ctx.debug_orb_detect_level(self.handle, int(frame) * self.num_rois + int(roi), level)
+
+
+def detect_features_orb_batch(ctx, det: OrbDetector, images, params=None, capacity=None, xy=None, response=None, angle=None, octave=None,
+                              counts=None, use_torch_stream=True, passes=63):
+    """MatcherOpenCV::detectFeatures (detector = "ORB") for every frame of `images` (ps_orb_detect_frames): a uint8 device tensor
+    (F, rows, cols[, channels]) of the detector's shape.  params: _abi.orb_detect_params(...) with the detector's scaleFactor,
+    nLevels and grid, default the detector's own; capacity: rows per frame (default maximalTrackedFeatures).  xy (F, cap, 2) float32 /
+    response, angle (F, cap) float32 / octave (F, cap) int32 / counts (F,) int32: blocks to write into (default: new ones).  Returns
+    (xy, response, angle, octave, counts), written asynchronously: nothing beyond a frame's count.  xy, octave and counts drop into
+    dbscan_thin_device; xy, angle, octave and counts into describe_features_batch.  passes: 63, or the mask of
+    ps_debug_orb_detect_passes (timing scripts)."""
+    params = params or det.params
+    s = _image_set(images, det.rows, det.cols, det.channels)
+    F, dev = images.shape[0], images.device
+    cap = int(params.maximalTrackedFeatures) if capacity is None else int(capacity)
+    xy = _block(xy, dev, (F, cap, 2), torch.float32)
+    response = _block(response, dev, (F, cap), torch.float32)
+    angle = _block(angle, dev, (F, cap), torch.float32)
+    octave = _block(octave, dev, (F, cap), torch.int32)
+    counts = _block(counts, dev, (F,), torch.int32)
+    args = (det.handle, s, params, cap, xy.data_ptr(), response.data_ptr(), angle.data_ptr(), octave.data_ptr(), counts.data_ptr(), passes)
+    _on_torch_stream(ctx, dev, lambda: ctx.orb_detect_frames(*args), use_torch_stream)
+    return xy, response, angle, octave, counts
 
 
 class OrbPyramids(_Handle):
