@@ -991,6 +991,102 @@ int ps_debug_orb_detect_level(PsContext *ctx, const PsOrbDetector *det, int slot
 int ps_debug_orb_detect_passes(PsContext *ctx, PsOrbDetector *det, const PsImageSet *images, const PsOrbDetectParams *params, int capacity,
                                float *xy, float *response, float *angle, int32_t *octave, int32_t *counts, int passes);
 
+/* ---- Frame assembly: what Matcher::detectInitFeatures (src/Matcher/matcher.cpp:17-64) and Matcher::match (:452-516) do between
+ * "key points" and "descriptors with 3-D points": the DBScan survivors compacted (dbscan.run erases from the vector, :24-26), the
+ * described key points undistorted and back-projected IN THE DESCRIBED ORDER (descriptorExtractor->compute replaces the vector,
+ * :36-49) and the detection distances (:51-58) -- and the whole per-frame front end as one call on one stream, from a batch of
+ * RGB-D images to a dense PsFrameSet. */
+typedef struct PsDepthSet {  /* numFrames 16-bit depth images of one shape (PsImageSet's 16-bit twin); pixels: DEVICE */
+    const uint16_t *pixels;
+    size_t rowStride;        /* BYTES between rows, 0 = dense (cols x 2) */
+    size_t frameStride;      /* BYTES between frames, 0 = dense (rows x rowStride); at least one view, also for a single frame */
+    int32_t numFrames, rows, cols;
+} PsDepthSet;
+typedef struct PsFrameGeometry {
+    float K[9];              /* camera matrix, row-major (cameraMatrixMat) */
+    double dist5[5];         /* k1 k2 p1 p2 k3 (distortionCoeffsMat) */
+    double depthImageScale;  /* sensorData.depthImageScale */
+} PsFrameGeometry;
+typedef struct PsFrameRowsOut {  /* DEVICE pointers, each F x capacity rows (nkpts: F); NULL = not wanted, except pts and nkpts */
+    float *pts;              /* x 3: features3D -- with nkpts and the descriptors a dense PsFrameSet */
+    int32_t *nkpts;
+    float *xy;               /* x 2: the distorted position (prevFeaturesDistorted) */
+    float *xyUndist;         /* x 2: prevFeaturesUndistorted */
+    float *angle, *response; /* the key point's, from angleIn / responseIn */
+    int32_t *octave;         /* ... from octaveIn */
+    int32_t *srcIdx;         /* the input row this output row was taken from */
+    double *detDist;         /* prevDetDists: what ps_frame_levels_device and the map store take */
+    const float *angleIn, *responseIn; /* F x capacity, the layout of xy; needed where the output beside it is wanted */
+    const int32_t *octaveIn;
+} PsFrameRowsOut;
+size_t ps_abi_sizeof_depth_set(void);
+size_t ps_abi_sizeof_frame_geometry(void);
+size_t ps_abi_sizeof_frame_rows_out(void);
+
+/* Compacts F frames of key points by index lists (ps_dbscan_thin_device's keptIdx / nkept): output row j of frame f is input row
+ * idx[f][j] for j < nidx[f], countsOut[f] = nidx[f].  All arrays DEVICE, F x capacity rows in the detector's layout (xy x 2 floats).
+ * A frame whose nidx[f] lies outside 0 .. capacity gets countsOut[f] = -1 and nothing else (the convention of DBScan and of
+ * describe: a bad frame propagates); an index outside 0 .. capacity-1 is not followed: that row is written as zeros.  Nothing is
+ * written beyond a frame's count.  response / angle / octave are optional as In / Out PAIRS: both NULL = not wanted, one NULL ->
+ * PS_ERR_BAD_ARG.  The outputs must not overlap the inputs.  NULL where an array is needed, capacity < 1, F outside 0 .. 65535 ->
+ * PS_ERR_BAD_ARG; capacity above PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; F == 0 is PS_OK.  One launch, asynchronous on the context's
+ * stream; uses no scratch of the context. */
+int ps_gather_keypoints(PsContext *ctx, const int32_t *idx, const int32_t *nidx, int F, int capacity, const float *xyIn,
+                        const float *responseIn, const float *angleIn, const int32_t *octaveIn, float *xyOut, float *responseOut,
+                        float *angleOut, int32_t *octaveOut, int32_t *countsOut);
+
+/* For output row j < numKept[f] of frame f: i = keptIdx[f][j] (ps_describe_features_device's), p = xy[f][i]; undist = the
+ * arithmetic of ps_remove_image_distortion on p; out->pts[f][j] = the arithmetic of ps_keypoints2Dto3D on undist in depth frame
+ * firstDepthFrame + f -- frame g spans ps_depth_view_bytes(rows, cols, rowStride) bytes from pixels + g x frameStride, and the rule
+ * of ps_keypoints2Dto3D holds for that frame alone AS THE DENSE IMAGE the reference holds: u == cols in a row that is not the last
+ * reads the next row's first pixel whatever the row stride, u == cols in the last row and v == rows read depth 0.  A set's padding
+ * is alignment, not a parent image: neither it nor the next frame is ever read.
+ * out->nkpts[f] = numKept[f], or 0 where that lies outside 0 .. capacity (a frame set carries no negative count).  An index
+ * outside 0 .. capacity-1 is not followed: every wanted array of that row is written as zeros.  detDist is matcher.cpp:52-57 as
+ * the compiler sees it: float products, float sums left to right, no fused operation, the correctly rounded float square root,
+ * then widened to double.  Nothing is written beyond a frame's count.  A NULL among geometry, depth, xy, keptIdx, numKept, out,
+ * out->pts, out->nkpts or an input beside a wanted output, a depth set whose strides do not resolve, firstDepthFrame < 0 or firstDepthFrame + F above its numFrames, capacity < 1, F outside 0 .. 65535 ->
+ * PS_ERR_BAD_ARG; capacity above PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; F == 0 is PS_OK.  One launch, asynchronous; no scratch. */
+int ps_assemble_frames(PsContext *ctx, const PsFrameGeometry *geometry, const PsDepthSet *depth, int firstDepthFrame, const float *xy,
+                       const int32_t *keptIdx, const int32_t *numKept, int F, int capacity, const PsFrameRowsOut *out);
+
+/* The per-frame front end for images of one shape, detector and descriptor "ORB": ps_orb_detect_frames, ps_dbscan_thin_device
+ * (minPts 2, featuresFromCluster 1: dbscan.h:19), ps_gather_keypoints, ps_orb_pyramids_build_device, ps_describe_features_device
+ * and ps_assemble_frames on the context's stream, with no host step in between. */
+typedef struct PsFrontEndParams {
+    PsOrbDetectParams detect;
+    PsOrbParams describe;
+    double DBScanEps;        /* OpenCVParams.DBScanEps */
+} PsFrontEndParams;
+typedef struct PsFrontEnd PsFrontEnd; /* a PsOrbDetector, a PsOrbPyramids of maxFrames slots and every intermediate array */
+size_t ps_abi_sizeof_front_end_params(void);
+/* Everything a frames call needs is allocated here -- maxFrames x max(1, maximalTrackedFeatures) rows of every intermediate
+ * array and the detector's ROI lists -- so that call neither allocates nor waits.  pattern1024: HOST, NULL = the default.
+ * Errors are those of ps_orb_detector_create and ps_orb_pyramids_create; maximalTrackedFeatures above PS_DBSCAN_MAX_KPTS ->
+ * PS_ERR_UNSUPPORTED.  detect and describe are two cv::ORB objects in the reference (matcherOpenCV.cpp:66-67, :90) and may differ
+ * here too: a descriptor with fewer levels drops the key points of the octaves it lacks.  Synchronous.  destroy waits for the
+ * device; NULL is harmless. */
+int ps_front_end_create(PsContext *ctx, int rows, int cols, int channels, const PsFrontEndParams *params, const int8_t *pattern1024,
+                        int maxFrames, PsFrontEnd **out);
+void ps_front_end_destroy(PsFrontEnd *fe);
+/* Images and depth (DEVICE sets of the handle's shape, the same numFrames, at most maxFrames) in; desc F x capacity x 32 bytes,
+ * out->pts and out->nkpts out: with maxKpts = capacity and strides 0 these three ARE a dense PsFrameSet for ps_vo_pairs_device.
+ * The side arrays of `out` are those of ps_assemble_frames; its angleIn / responseIn / octaveIn are ignored (the handle's own key
+ * points stand there).  capacity: at least what the detector can emit (as for ps_orb_detect_frames), at most max(1,
+ * maximalTrackedFeatures) -- the rows the handle holds.  capacity above PS_DBSCAN_MAX_KPTS -> PS_ERR_UNSUPPORTED; a NULL, a shape
+ * or stride that does not fit, numFrames that differ or exceed maxFrames, a capacity outside the range above -> PS_ERR_BAD_ARG
+ * with a text in ps_last_error; outputs untouched.
+ * numFrames == 0 is PS_OK.  Asynchronous on the context's stream. */
+int ps_front_end_frames(PsContext *ctx, PsFrontEnd *fe, const PsImageSet *images, const PsDepthSet *depth, const PsFrameGeometry *geometry,
+                        int capacity, uint8_t *desc, const PsFrameRowsOut *out);
+/* The same for one frame: HOST pointers, uploads and downloads included, synchronous.  img rows x cols x channels bytes with
+ * rowStride bytes between rows, depth rows x cols uint16 with depthStep bytes between rows (0 = dense either; a region keeps its
+ * parent's -- the depth rule is the set's: what lies between the rows is not read).  desc cap x 32 bytes, out: HOST arrays of cap rows (pts required; nkpts ignored), *nout the rows.  Returns
+ * PS_ERR_BAD_ARG with *nout = required capacity if cap is too small (nothing else is written); other errors as above. */
+int ps_front_end_frame(PsContext *ctx, const uint8_t *img, const uint16_t *depth, int rows, int cols, int channels, size_t rowStride,
+                       size_t depthStep, const PsFrontEndParams *params, const int8_t *pattern1024, const PsFrameGeometry *geometry,
+                       uint8_t *desc, const PsFrameRowsOut *out, int cap, int *nout);
+
 /* ---- Loop-closure candidates verified in one batch from the resident store: what the loop-closure thread does per candidate
  * (poseA, poseB) of FABMAP's priority queue -- FeaturesMap::loopClosure (src/Map/featuresMap.cpp:733-873) around
  * Matcher::matchFeatureLoopClosure (src/Matcher/matcher.cpp:802-861) -- for L candidates as two calls, no host step.

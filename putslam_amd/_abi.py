@@ -221,6 +221,41 @@ def orb_detect_params(n_features=500, scale_factor=1.2, n_levels=8, fast_thresho
                              int(maximal_tracked_features), 0)
 
 
+# Frame assembly and the front end (include/putslam_hip.h)
+class PsDepthSet(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("rowStride", C.c_size_t), ("frameStride", C.c_size_t), ("numFrames", C.c_int32),
+                ("rows", C.c_int32), ("cols", C.c_int32)]
+
+
+class PsFrameGeometry(C.Structure):
+    _fields_ = [("K", C.c_float * 9), ("dist5", C.c_double * 5), ("depthImageScale", C.c_double)]
+
+
+class PsFrameRowsOut(C.Structure):
+    _fields_ = [("pts", C.c_void_p), ("nkpts", C.c_void_p), ("xy", C.c_void_p), ("xyUndist", C.c_void_p), ("angle", C.c_void_p),
+                ("response", C.c_void_p), ("octave", C.c_void_p), ("srcIdx", C.c_void_p), ("detDist", C.c_void_p),
+                ("angleIn", C.c_void_p), ("responseIn", C.c_void_p), ("octaveIn", C.c_void_p)]
+
+
+class PsFrontEndParams(C.Structure):
+    _fields_ = [("detect", PsOrbDetectParams), ("describe", PsOrbParams), ("DBScanEps", C.c_double)]
+
+
+def frame_geometry(K, dist5=(0.0,) * 5, depth_image_scale=5000.0):
+    """PsFrameGeometry: K nine floats row-major, dist5 (k1, k2, p1, p2, k3), depthImageScale."""
+    K = np.asarray(K, np.float32).reshape(9)
+    d = np.asarray(dist5, np.float64).reshape(5)
+    return PsFrameGeometry((C.c_float * 9)(*K.tolist()), (C.c_double * 5)(*d.tolist()), float(depth_image_scale))
+
+
+def front_end_params(detect=None, describe=None, dbscan_eps=10.0):
+    """PsFrontEndParams: detect _abi.orb_detect_params(...) and describe _abi.orb_params(...), default the shipped ones (which
+    share scaleFactor and nLevels, as the front end requires); dbscan_eps OpenCVParams.DBScanEps."""
+    detect = detect or orb_detect_params()
+    describe = describe or orb_params(detect.scaleFactor, detect.nLevels)
+    return PsFrontEndParams(detect, describe, float(dbscan_eps))
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

@@ -8,7 +8,8 @@ import os
 
 from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch,
                    PsMapBatchF32, PsMapStore, PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPairResults, PsPoseSetOut,
-                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams, PsOrbParams, PsOrbDetectParams)
+                   PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams, PsOrbParams, PsOrbDetectParams,
+                   PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -57,6 +58,8 @@ EXPORTED = [
     "ps_describe_features_device", "ps_describe_features", "ps_debug_orb_level", "ps_debug_orb_passes", "ps_abi_sizeof_orb_params",
     "ps_orb_detector_create", "ps_orb_detector_destroy", "ps_orb_detector_level", "ps_orb_detect_quotas", "ps_orb_detect_frames",
     "ps_detect_features_orb", "ps_debug_orb_detect_level", "ps_debug_orb_detect_passes", "ps_abi_sizeof_orb_detect_params",
+    "ps_gather_keypoints", "ps_assemble_frames", "ps_front_end_create", "ps_front_end_destroy", "ps_front_end_frames", "ps_front_end_frame",
+    "ps_abi_sizeof_depth_set", "ps_abi_sizeof_frame_geometry", "ps_abi_sizeof_frame_rows_out", "ps_abi_sizeof_front_end_params",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -75,6 +78,9 @@ ABI_STRUCTS_KLT = dict(klt_params=PsKltParams, image_set=PsImageSet)
 ABI_STRUCTS_DETECT = dict(detect_params=PsDetectParams)
 ABI_STRUCTS_ORB = dict(orb_params=PsOrbParams)
 ABI_STRUCTS_ORB_DETECT = dict(orb_detect_params=PsOrbDetectParams)
+# ... and of frame assembly and the front end (ps_gather_keypoints / ps_assemble_frames / ps_front_end_*)
+ABI_STRUCTS_FRAME_ASSEMBLY = dict(depth_set=PsDepthSet, frame_geometry=PsFrameGeometry, frame_rows_out=PsFrameRowsOut,
+                                  front_end_params=PsFrontEndParams)
 
 _lib = None
 _by_path = {}
@@ -301,8 +307,17 @@ def load_path(path):
     L.ps_detect_features_orb.argtypes = [vp, vp, i32, i32, i32, sz, C.POINTER(PsOrbDetectParams), vp, vp, vp, vp, i32, C.POINTER(i32)]
     L.ps_debug_orb_detect_level.argtypes = [vp, vp, i32, i32, vp, vp, C.POINTER(i32), vp, vp, vp, vp, i32]
     L.ps_debug_orb_detect_passes.argtypes = [vp, vp, C.POINTER(PsImageSet), C.POINTER(PsOrbDetectParams), i32, vp, vp, vp, vp, vp, i32]
+    L.ps_gather_keypoints.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ps_assemble_frames.argtypes = [vp, C.POINTER(PsFrameGeometry), C.POINTER(PsDepthSet), i32, vp, vp, vp, i32, i32, C.POINTER(PsFrameRowsOut)]
+    L.ps_front_end_create.argtypes = [vp, i32, i32, i32, C.POINTER(PsFrontEndParams), vp, i32, C.POINTER(vp)]
+    L.ps_front_end_destroy.argtypes = [vp]
+    L.ps_front_end_destroy.restype = None
+    L.ps_front_end_frames.argtypes = [vp, vp, C.POINTER(PsImageSet), C.POINTER(PsDepthSet), C.POINTER(PsFrameGeometry), i32, vp,
+                                      C.POINTER(PsFrameRowsOut)]
+    L.ps_front_end_frame.argtypes = [vp, vp, vp, i32, i32, i32, sz, sz, C.POINTER(PsFrontEndParams), vp, C.POINTER(PsFrameGeometry), vp,
+                                     C.POINTER(PsFrameRowsOut), i32, C.POINTER(i32)]
     for n in (list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT) + list(ABI_STRUCTS_DETECT)
-              + list(ABI_STRUCTS_ORB) + list(ABI_STRUCTS_ORB_DETECT)):
+              + list(ABI_STRUCTS_ORB) + list(ABI_STRUCTS_ORB_DETECT) + list(ABI_STRUCTS_FRAME_ASSEMBLY)):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -334,3 +349,7 @@ def struct_sizes_orb():
 
 def struct_sizes_orb_detect():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_ORB_DETECT.items()}
+
+
+def struct_sizes_frame_assembly():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_FRAME_ASSEMBLY.items()}

@@ -13,7 +13,7 @@ from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, P
                    PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch, PsMapBatchF32, PsPairResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config,
                    PsImageSet, PsKltParams, klt_params, PsDetectParams, detect_params, PsOrbParams, orb_params,
-                   PsOrbDetectParams, orb_detect_params)
+                   PsOrbDetectParams, orb_detect_params, PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, front_end_params)
 
 
 class PsError(RuntimeError):
@@ -690,6 +690,60 @@ class Context:
         raw, blr = np.zeros((r, c), np.uint8), np.zeros((r, c), np.uint8)
         self._chk(self._L.ps_debug_orb_level(self._h, pyr, int(slot), int(level), _p(raw), _p(blr)))
         return raw, blr
+
+    # ---- frame assembly and the front end (ps_frame_assembly.h) ----
+    def gather_keypoints(self, idx_ptr, nidx_ptr, F, capacity, xy_in, response_in, angle_in, octave_in, xy_out, response_out, angle_out,
+                         octave_out, counts_out):
+        """ps_gather_keypoints on device pointers (asynchronous on the context's stream): device_batch.gather_keypoints."""
+        self._chk(self._L.ps_gather_keypoints(self._h, _v(idx_ptr), _v(nidx_ptr), int(F), int(capacity), _v(xy_in), _v(response_in),
+                                              _v(angle_in), _v(octave_in), _v(xy_out), _v(response_out), _v(angle_out), _v(octave_out),
+                                              _v(counts_out)))
+
+    def assemble_frames(self, geometry: PsFrameGeometry, depth: PsDepthSet, first_depth_frame, xy_ptr, kept_idx_ptr, num_kept_ptr, F,
+                        capacity, out: PsFrameRowsOut):
+        """ps_assemble_frames on device pointers (asynchronous on the context's stream): device_batch.assemble_frames."""
+        self._chk(self._L.ps_assemble_frames(self._h, C.byref(geometry), C.byref(depth), int(first_depth_frame), _v(xy_ptr),
+                                             _v(kept_idx_ptr), _v(num_kept_ptr), int(F), int(capacity), C.byref(out)))
+
+    def front_end_create(self, rows, cols, channels, params: PsFrontEndParams, pattern, max_frames):
+        """ps_front_end_create: the handle of a device-resident front end (device_batch.FrontEnd owns one)."""
+        h = C.c_void_p()
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8).reshape(1024)
+        self._chk(self._L.ps_front_end_create(self._h, int(rows), int(cols), int(channels), C.byref(params),
+                                              None if pat is None else _p(pat), int(max_frames), C.byref(h)))
+        return h
+
+    def front_end_frames(self, fe, images: PsImageSet, depth: PsDepthSet, geometry: PsFrameGeometry, capacity, desc_ptr,
+                         out: PsFrameRowsOut):
+        """ps_front_end_frames on device pointers (asynchronous on the context's stream): device_batch.front_end_frames_batch."""
+        self._chk(self._L.ps_front_end_frames(self._h, fe, C.byref(images), C.byref(depth), C.byref(geometry), int(capacity),
+                                              _v(desc_ptr), C.byref(out)))
+
+    def front_end_frame(self, image, depth, geometry: PsFrameGeometry, params: PsFrontEndParams = None, pattern=None):
+        """The whole per-frame front end of Matcher::detectInitFeatures / Matcher::match for detector and descriptor "ORB"
+        (ps_front_end_frame) on a numpy image (rows, cols) or (rows, cols, 3) uint8 and its depth image (rows, cols) uint16, whose
+        rows may lie any stride apart.  Returns a dict of the k described key points in the described order: desc (k, 32) uint8,
+        pts (k, 3) float32, xy / xy_undist (k, 2) float32, angle / response (k,) float32, octave (k,) int32, src_idx (k,) int32 (the
+        row among DBScan's survivors), det_dist (k,) float64."""
+        params = params or front_end_params()
+        image, cn = _host_image(image)
+        depth = np.asarray(depth)
+        assert depth.dtype == np.uint16 and depth.ndim == 2 and depth.shape == image.shape[:2]
+        if depth.strides[1] != 2 or depth.strides[0] < depth.shape[1] * 2:
+            depth = np.ascontiguousarray(depth)
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8).reshape(1024)
+        cap = max(1, min(int(params.detect.maximalTrackedFeatures), PS_MAX_KPTS))
+        a = dict(desc=np.zeros((cap, 32), np.uint8), pts=np.zeros((cap, 3), np.float32), xy=np.zeros((cap, 2), np.float32),
+                 xy_undist=np.zeros((cap, 2), np.float32), angle=np.zeros(cap, np.float32), response=np.zeros(cap, np.float32),
+                 octave=np.zeros(cap, np.int32), src_idx=np.zeros(cap, np.int32), det_dist=np.zeros(cap, np.float64))
+        ptr = lambda k: a[k].ctypes.data   # noqa: E731
+        out = PsFrameRowsOut(ptr("pts"), None, ptr("xy"), ptr("xy_undist"), ptr("angle"), ptr("response"), ptr("octave"), ptr("src_idx"),
+                             ptr("det_dist"), None, None, None)
+        n = C.c_int(0)
+        self._chk(self._L.ps_front_end_frame(self._h, _p(image), _p(depth), image.shape[0], image.shape[1], cn, image.strides[0],
+                                             depth.strides[0], C.byref(params), None if pat is None else _p(pat), C.byref(geometry),
+                                             _p(a["desc"]), C.byref(out), cap, C.byref(n)))
+        return {k: v[:n.value].copy() for k, v in a.items()}
 
     def points3Dto2D(self, xyz, K):
         xyz = np.ascontiguousarray(xyz, np.float32)

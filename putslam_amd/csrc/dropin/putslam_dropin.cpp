@@ -461,6 +461,9 @@ FrameMatcher::MatcherParameters::MatcherParameters()
     cameraMatrixMat = cv::Mat(3, 3, CV_32FC1);
     const float K[9] = {517.3f, 0.0f, 318.6f, 0.0f, 516.5f, 255.3f, 0.0f, 0.0f, 1.0f};
     for (int i = 0; i < 9; ++i) cameraMatrixMat.at<float>(i / 3, i % 3) = K[i];
+    distortionCoeffsMat = cv::Mat(1, 5, CV_32FC1); // :7, rgbDistortion
+    const float dist[5] = {-0.0410f, 0.3286f, 0.0087f, 0.0051f, -0.5643f};
+    for (int i = 0; i < 5; ++i) distortionCoeffsMat.at<float>(0, i) = dist[i];
 }
 
 void FrameMatcher::detectInitFeatures(cv::Mat descriptors, std::vector<Eigen::Vector3f> features3D)
@@ -1379,6 +1382,91 @@ cv::Mat describeFeaturesORB(const FrameMatcher::MatcherParameters &matcherParame
     features.resize((size_t)k);
     for (int j = 0; j < k; ++j) features[(size_t)j] = in[(size_t)keptIdx[(size_t)j]];
     return descriptors;
+}
+
+// Matcher::detectInitFeatures, matcher.cpp:19-49 / Matcher::match, :457-482: the frame from its images to descriptors and 3-D points
+void FrameMatcherHIP::frontEnd(cv::Mat rgbImage, cv::Mat depthImage, double depthImageScale, cv::Mat &descriptors,
+                               std::vector<Eigen::Vector3f> &features3D, std::vector<cv::KeyPoint> *keyPoints, std::vector<cv::Point2f> *undistorted)
+{
+    descriptors = cv::Mat();
+    features3D.clear();
+    if (keyPoints) keyPoints->clear();
+    if (undistorted) undistorted->clear();
+    const auto &cvp = matcherParameters.OpenCVParams;
+    if (cvp.detector != "ORB" || cvp.descriptor != "ORB") {
+        std::cerr << "putslam_hip: frontEnd runs detector \"ORB\" with descriptor \"ORB\" only (asked for \"" << cvp.detector << "\" and \""
+                  << cvp.descriptor << "\"): nothing detected; the separate calls or OpenCV on the host serve the others" << std::endl;
+        return;
+    }
+    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3) || depthImage.empty() ||
+        depthImage.type() != CV_16U || depthImage.rows != rgbImage.rows || depthImage.cols != rgbImage.cols) {
+        std::cerr << "putslam_hip: frontEnd takes a CV_8UC1 or CV_8UC3 image and a CV_16U depth image of the same size" << std::endl;
+        return;
+    }
+    const int cap = cvp.maximalTrackedFeatures > 0 ? cvp.maximalTrackedFeatures : 0;
+    if (cap == 0) return;
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return;
+    PsFrontEndParams prm;
+    prm.detect.nFeatures = 500; // cv::ORB::create()'s defaults (matcherOpenCV.cpp:67, :90)
+    prm.detect.scaleFactor = 1.2f;
+    prm.detect.nLevels = 8;
+    prm.detect.fastThreshold = 20;
+    prm.detect.gridRows = cvp.gridRows;
+    prm.detect.gridCols = cvp.gridCols;
+    prm.detect.maximalTrackedFeatures = cvp.maximalTrackedFeatures;
+    prm.detect.reserved = 0;
+    prm.describe.scaleFactor = 1.2f;
+    prm.describe.nLevels = 8;
+    prm.describe.reserved[0] = prm.describe.reserved[1] = 0;
+    prm.DBScanEps = cvp.DBScanEps;
+    PsFrameGeometry geo;
+    bool haveK;
+    cameraToK(matcherParameters.cameraMatrixMat, geo.K, haveK);
+    const cv::Mat &dc = matcherParameters.distortionCoeffsMat;
+    const int nd = dc.empty() ? 0 : dc.rows * dc.cols;
+    for (int i = 0; i < 5; ++i) geo.dist5[i] = i < nd ? (double)dc.at<float>(dc.rows == 1 ? 0 : i, dc.rows == 1 ? i : 0) : 0.0;
+    geo.depthImageScale = depthImageScale;
+    const size_t room = (size_t)cap;
+    std::vector<unsigned char> rows(room * 32);
+    std::vector<cv::Point2f> xy(room), und(room);
+    std::vector<float> angle(room), response(room);
+    std::vector<int32_t> octave(room);
+    features3D.resize(room);
+    PsFrameRowsOut out;
+    std::memset(&out, 0, sizeof out);
+    out.pts = reinterpret_cast<float *>(features3D.data());
+    out.xy = reinterpret_cast<float *>(xy.data());
+    out.xyUndist = reinterpret_cast<float *>(und.data());
+    out.angle = angle.data();
+    out.response = response.data();
+    out.octave = octave.data();
+    int n = 0;
+    status = ps_front_end_frame(ctx, rgbImage.data, reinterpret_cast<const uint16_t *>(depthImage.data), rgbImage.rows, rgbImage.cols,
+                                rgbImage.channels(), (size_t)rgbImage.step, (size_t)depthImage.step, &prm, nullptr, &geo, rows.data(), &out, cap, &n);
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        features3D.clear();
+        return;
+    }
+    features3D.resize((size_t)n);
+    if (n == 0) return;
+    descriptors = cv::Mat(n, 32, CV_8U);
+    std::memcpy(descriptors.data, rows.data(), (size_t)n * 32);
+    if (undistorted) undistorted->assign(und.begin(), und.begin() + n);
+    if (keyPoints) {
+        keyPoints->resize((size_t)n);
+        for (int j = 0; j < n; ++j) { // the key point detectFeaturesORB makes
+            cv::KeyPoint &kp = (*keyPoints)[(size_t)j];
+            kp.pt = xy[(size_t)j];
+            kp.size = 31.f * (float)std::pow((double)prm.detect.scaleFactor, (double)octave[(size_t)j]);
+            kp.angle = angle[(size_t)j];
+            kp.response = response[(size_t)j];
+            kp.octave = octave[(size_t)j];
+            kp.class_id = -1;
+        }
+    }
 }
 
 // MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) with the matcher of matcherOpenCV.cpp:100-102, cv::BFMatcher(cv::NORM_L2,

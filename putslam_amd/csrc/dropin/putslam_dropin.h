@@ -189,6 +189,7 @@ class FrameMatcher {
         int verbose = 0;
         RANSAC::parameters RANSACParams;
         cv::Mat cameraMatrixMat; // 3x3 CV_32FC1
+        cv::Mat distortionCoeffsMat; // 1x5 CV_32FC1: k1 k2 p1 p2 k3 (datasetConfig rgbDistortion; what frontEnd undistorts with)
         struct {
             double matchingXYZSphereRadius = 0.12;            // putslammatcherOpenCVParameters.xml:71
             double matchingXYZacceptRatioOfBestMatch = 0.55;  // :72
@@ -205,6 +206,7 @@ class FrameMatcher {
             int maximalTrackedFeatures = 500;
             // the descriptor's name (matcher.h:40; putslammatcherOpenCVParameters.xml:64): describeFeatures below runs "ORB"
             std::string descriptor = "ORB";
+            double DBScanEps = 1; // matcher.h:54; putslammatcherOpenCVParameters.xml:70 (frontEnd's thinning)
         } OpenCVParams;
         MatcherParameters();
     };
@@ -435,6 +437,17 @@ class FrameMatcherHIP : public FrameMatcher {
     virtual std::vector<cv::KeyPoint> detectFeatures(cv::Mat rgbImage);
     // MatcherOpenCV::describeFeatures, matcherOpenCV.cpp:183-195 (the reference's signature; describeFeaturesORB above)
     virtual cv::Mat describeFeatures(cv::Mat rgbImage, std::vector<cv::KeyPoint> &features);
+    // The whole per-frame front end of Matcher::detectInitFeatures (matcher.cpp:19-49) / Matcher::match (:457-482) for detector and
+    // descriptor "ORB" as ONE call (ps_front_end_frame): detectFeatures, DBScan(OpenCVParams.DBScanEps).run, describeFeatures,
+    // removeImageDistortion with cameraMatrixMat / distortionCoeffsMat and keypoints2Dto3D with depthImageScale, the last two on the
+    // DESCRIBED key points in the described order.  rgbImage CV_8UC1 / CV_8UC3, depthImage CV_16U of the same size, any steps.
+    // descriptors: n x 32 CV_8U; features3D: n points; keyPoints (the described ones, all six fields) and undistorted
+    // (prevFeaturesUndistorted) where asked for.  With
+    //     auto fe = [&](const SensorFrame &s, cv::Mat &d, std::vector<Eigen::Vector3f> &p) { m.frontEnd(s.rgbImage, s.depthImage, s.depthImageScale, d, p); };
+    // it is the frontEnd callable of putslam_matcher_glue.h.  Any other detector or descriptor is NOT run on the CPU instead: one line
+    // goes to std::cerr and every output comes back empty.
+    void frontEnd(cv::Mat rgbImage, cv::Mat depthImage, double depthImageScale, cv::Mat &descriptors, std::vector<Eigen::Vector3f> &features3D,
+                  std::vector<cv::KeyPoint> *keyPoints = nullptr, std::vector<cv::Point2f> *undistorted = nullptr);
 };
 
 } // namespace putslam_hip

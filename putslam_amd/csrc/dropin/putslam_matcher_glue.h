@@ -25,8 +25,9 @@ namespace putslam_hip {
 
 // Matcher::detectInitFeatures (matcher.cpp:17-64) / Matcher::match = runVO (matcher.cpp:452-516) from the point where
 // the frame has been detected, described, undistorted and back-projected.  `frontEnd(sensorData, descriptors,
-// features3D)` is the reference's own detect / describe / removeImageDistortion / keypoints2Dto3D sequence
-// (matcher.cpp:457-467,474-480), injected by the caller; everything after it runs on the GPU.
+// features3D)` is the detect / DBScan / describe / removeImageDistortion / keypoints2Dto3D sequence (matcher.cpp:457-467,474-480):
+// for detector and descriptor "ORB" a lambda around FrameMatcherHIP::frontEnd, which runs it on the GPU as one call
+// (putslam_dropin.h), else the reference's own, injected by the caller; everything after it runs on the GPU.
 template <class SensorFrameT, class FrontEnd>
 void detectInitFeatures(FrameMatcher &hot, const SensorFrameT &sensorData, FrontEnd &&frontEnd)
 {

@@ -86,15 +86,7 @@ inline int check_frame_set(PsContext *ctx, const PsFrameSet &fs, const char *who
     return frame_strides(ctx, fs, true, true, who, out);
 }
 
-// THE ADDRESSABLE BYTES of a rows x cols image of 16-bit pixels whose rows lie `step` bytes apart (a cv::Mat, possibly a
-// region of a larger one): the last row ends after its cols pixels, not after a whole pitch -- what follows them belongs to
-// the parent image or to nobody.  The upload of ps_keypoints2Dto3D copies this many bytes and its kernel reads no further.
-// 0 for a shape the call rejects (rows or cols < 1, step below a row).
-inline size_t depth_view_bytes(int rows, int cols, size_t step)
-{
-    if (rows < 1 || cols < 1 || step < (size_t)cols * 2) return 0;
-    return (size_t)(rows - 1) * step + (size_t)cols * 2;
-}
+// (depth_view_bytes, the addressable bytes of a 16-bit depth image, stands in ps_image_rule.h with the PsDepthSet rule)
 
 // ---- the image front end (ps_klt.h, ps_fast.h, ps_orb.h); the arithmetic is ps_image_rule.h's ----
 

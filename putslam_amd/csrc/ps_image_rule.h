@@ -1,5 +1,6 @@
 // ps_image_rule.h -- the arithmetic of the image front end's host side (ps_klt.h, ps_fast.h, ps_orb.h), each rule once: the limits,
-// the row stride and the addressable bytes of a host image, the strides of a PsImageSet, the layout of a host form's device block.
+// the row stride and the addressable bytes of a host image, the strides of a PsImageSet and of a PsDepthSet (ps_frame_assembly.h), the
+// layout of a host form's device block.
 // Pure -- no HIP header, no runtime call: tests/cpp/test_image_rule.cpp includes it into a plain C++ program.
 #pragma once
 #include <cstddef>
@@ -21,7 +22,7 @@ inline size_t image_row_stride(int cols, int channels, size_t rowStride)
     return rowStride < dense ? 0 : rowStride;
 }
 
-// THE ADDRESSABLE BYTES of one host image (ps_glue.h's depth_view_bytes for 8-bit channels): the last row ends after its pixels,
+// THE ADDRESSABLE BYTES of one host image (depth_view_bytes below for 8-bit channels): the last row ends after its pixels,
 // not after a whole stride.  The uploads copy this many bytes and the kernels read no further.  0 for a shape the calls reject.
 inline size_t image_bytes(int rows, int cols, int channels, size_t rowStride)
 {
@@ -39,6 +40,30 @@ inline bool image_set_strides(const PsImageSet &s, size_t &row, size_t &frame)
     if (s.rows < 1 || row == 0) return false;
     frame = s.frameStride ? s.frameStride : (size_t)s.rows * row;
     return frame >= image_bytes(s.rows, s.cols, s.channels, row);
+}
+
+// THE ADDRESSABLE BYTES of a rows x cols image of 16-bit pixels whose rows lie `step` bytes apart (a cv::Mat, possibly a
+// region of a larger one): the last row ends after its cols pixels, not after a whole pitch -- what follows them belongs to
+// the parent image or to nobody.  The upload of ps_keypoints2Dto3D copies this many bytes and its kernel reads no further.
+// 0 for a shape the call rejects (rows or cols < 1, step below a row).
+inline size_t depth_view_bytes(int rows, int cols, size_t step)
+{
+    if (rows < 1 || cols < 1 || step < (size_t)cols * 2) return 0;
+    return (size_t)(rows - 1) * step + (size_t)cols * 2;
+}
+
+// THE STRIDE RULE of a PsDepthSet (image_set_strides for 16-bit pixels), resolved: a rowStride of 0 is a dense row, a frameStride
+// of 0 is rows x rowStride; both even (the pixels are uint16), rowStride at least a dense row, frameStride at least one view --
+// depth_view_bytes, `view` -- of a single frame too.  false for a set the calls reject.
+inline bool depth_set_strides(const PsDepthSet &s, size_t &row, size_t &frame, size_t &view)
+{
+    row = frame = view = 0;
+    if (s.rows < 1 || s.cols < 1 || s.rows > kImageMaxDim || s.cols > kImageMaxDim) return false;
+    row = s.rowStride ? s.rowStride : (size_t)s.cols * 2;
+    view = depth_view_bytes(s.rows, s.cols, row);
+    if (view == 0 || (row & 1) != 0) return false;
+    frame = s.frameStride ? s.frameStride : (size_t)s.rows * row;
+    return (frame & 1) == 0 && frame >= view;
 }
 
 // Consecutive regions of ONE allocation: take<T>(count) is the offset of `count` elements of T, aligned to what T needs (or to

@@ -1808,6 +1808,30 @@ PS_D int round_size(double x, int size)
         x = size; // sic: the reference clamps to size, not size-1
     return (int)round(x);
 }
+// ONE statement of the depth read's rule and ONE of point2Dto3D's arithmetic, shared by ps_backproject and ps_assemble_rows
+// (ps_frame_assembly.h).  depth_rule_offset: the byte offset of the rounded pixel in an image whose rows lie `step` bytes apart and
+// whose addressable bytes end at `bytes`; false where there is no pixel to read (depth 0 = missing).
+PS_D bool depth_rule_offset(float x, float y, int rows, int cols, size_t step, size_t bytes, size_t &off)
+{
+    // A NaN coordinate has no pixel (the reference's (int)round(NaN) is undefined): depth 0 (= missing).
+    if (!(x == x && y == y)) return false;
+    int uR = round_size((double)x, cols), vR = round_size((double)y, rows);
+    off = (size_t)vR * step + (size_t)uR * 2;
+    // cv::Mat::at is plain pointer arithmetic: u == cols in a row that is not the last reads what follows that row's
+    // pixels (the parent image's next pixel for a region, the next row's first pixel for a dense image).  `bytes` =
+    // depth_view_bytes(rows, cols, step) is where the last row's pixels end: from there on the reference reads out of
+    // bounds, here that is depth 0 (= missing).
+    return off + 2 <= bytes;
+}
+PS_D unsigned depth_pixel(const uint8_t *__restrict__ at) { return (unsigned)at[0] | ((unsigned)at[1] << 8); }
+PS_D void point_from_depth(float x, float y, unsigned dv, float fx, float fy, float cx, float cy, double scale, float &X, float &Y, float &Z)
+{
+    Z = (float)(((double)dv) / scale);
+    float u = (x - cx) / fx;
+    float v = (y - cy) / fy;
+    X = u * Z;
+    Y = v * Z;
+}
 __global__ __launch_bounds__(kBlock) void ps_backproject(const float *__restrict__ xy, int n,
                                                          const uint8_t *__restrict__ depth, int rows, int cols,
                                                          size_t step, size_t bytes, float fx, float fy, float cx,
@@ -1815,23 +1839,13 @@ __global__ __launch_bounds__(kBlock) void ps_backproject(const float *__restrict
 {
     int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    float x = xy[2 * i], y = xy[2 * i + 1];
-    unsigned dv = 0;
-    // A NaN coordinate has no pixel (the reference's (int)round(NaN) is undefined): depth 0 (= missing).
-    if (x == x && y == y) {
-        int uR = round_size((double)x, cols), vR = round_size((double)y, rows);
-        size_t off = (size_t)vR * step + (size_t)uR * 2;
-        // cv::Mat::at is plain pointer arithmetic: u == cols in a row that is not the last reads what follows that row's
-        // pixels (the parent image's next pixel for a region, the next row's first pixel for a dense image).  `bytes` =
-        // depth_view_bytes(rows, cols, step) is where the last row's pixels end: from there on the reference reads out of
-        // bounds, here that is depth 0 (= missing).
-        if (off + 2 <= bytes) dv = (unsigned)depth[off] | ((unsigned)depth[off + 1] << 8);
-    }
-    float Z = (float)(((double)dv) / scale);
-    float u = (x - cx) / fx;
-    float v = (y - cy) / fy;
-    out[3 * i] = u * Z;
-    out[3 * i + 1] = v * Z;
+    const float x = xy[2 * i], y = xy[2 * i + 1];
+    size_t off = 0;
+    const unsigned dv = depth_rule_offset(x, y, rows, cols, step, bytes, off) ? depth_pixel(depth + off) : 0u;
+    float X, Y, Z;
+    point_from_depth(x, y, dv, fx, fy, cx, cy, scale, X, Y, Z);
+    out[3 * i] = X;
+    out[3 * i + 1] = Y;
     out[3 * i + 2] = Z;
 }
 
@@ -1842,16 +1856,14 @@ struct DistArgs {
     double k[5]; // k1 k2 p1 p2 k3
     float fx, fy, cx, cy;
 };
-__global__ __launch_bounds__(kBlock) void ps_undistort_kernel(const float *__restrict__ xy, int n, DistArgs a,
-                                                              float *__restrict__ out)
+// ONE statement of the iteration, shared by ps_undistort_kernel and ps_assemble_rows (ps_frame_assembly.h)
+PS_D void undistort_point(float px, float py, const DistArgs &a, float &u, float &v)
 {
-    int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
     const double fx = (double)a.fx, fy = (double)a.fy, cx = (double)a.cx, cy = (double)a.cy;
     const double ifx = 1. / fx, ify = 1. / fy;
     const double k0 = a.k[0], k1 = a.k[1], k2 = a.k[2], k3 = a.k[3], k4 = a.k[4];
     const double z = 0.0; // k[5..11] of OpenCV's 12-coefficient form: absent in the reference's configs
-    double x = (double)xy[2 * i], y = (double)xy[2 * i + 1];
+    double x = (double)px, y = (double)py;
     double x0 = x = (x - cx) * ifx;
     double y0 = y = (y - cy) * ify;
     for (int j = 0; j < 5; ++j) {
@@ -1863,8 +1875,18 @@ __global__ __launch_bounds__(kBlock) void ps_undistort_kernel(const float *__res
         y = (y0 - deltaY) * icdist;
     }
     float xn = (float)x, yn = (float)y;
-    out[2 * i] = xn * a.fx + a.cx;
-    out[2 * i + 1] = yn * a.fy + a.cy;
+    u = xn * a.fx + a.cx;
+    v = yn * a.fy + a.cy;
+}
+__global__ __launch_bounds__(kBlock) void ps_undistort_kernel(const float *__restrict__ xy, int n, DistArgs a,
+                                                              float *__restrict__ out)
+{
+    int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float u, v;
+    undistort_point(xy[2 * i], xy[2 * i + 1], a, u, v);
+    out[2 * i] = u;
+    out[2 * i + 1] = v;
 }
 
 __global__ __launch_bounds__(kBlock) void ps_project_kernel(const float *__restrict__ xyz, int n, float fx, float fy,

@@ -9,7 +9,8 @@ import torch
 from . import api
 from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
-                   make_config, PsImageSet, klt_params, detect_params, orb_params, orb_detect_params)
+                   make_config, PsImageSet, klt_params, detect_params, orb_params, orb_detect_params, PsDepthSet, PsFrameRowsOut,
+                   front_end_params)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -560,6 +561,129 @@ def describe_features_batch(ctx, pyr: OrbPyramids, slots, xy, angle, octave, cou
             kept_idx.data_ptr(), num_kept.data_ptr(), passes)
     _on_torch_stream(ctx, dev, lambda: ctx.describe_features_device(*args), use_torch_stream)
     return desc, kept_idx, num_kept
+
+
+def DepthSet(depth, rows, cols):
+    """PsDepthSet of a uint16 (torch.int16 / torch.uint16) device tensor (F, rows, cols) whose rows and frames may lie any stride
+    apart (a view of a padded block); a row itself is dense."""
+    assert depth.element_size() == 2 and not depth.is_floating_point() and depth.dim() == 3 and tuple(depth.shape[1:]) == (rows, cols)
+    assert depth.stride(2) == 1
+    return PsDepthSet(depth.data_ptr(), depth.stride(1) * 2, depth.stride(0) * 2 if depth.shape[0] > 1 else 0, depth.shape[0], rows, cols)
+
+
+def gather_keypoints(ctx, idx, nidx, xy, response=None, angle=None, octave=None, use_torch_stream=True):
+    """Compacts F frames of key points by index lists (ps_gather_keypoints): idx (F, cap) int32 / nidx (F,) int32 -- what
+    dbscan_thin_device returns --, xy (F, cap, 2) float32, response / angle (F, cap) float32, octave (F, cap) int32 or None.
+    Returns (xy, response, angle, octave, counts) -- None where the input was None --, new device tensors written asynchronously:
+    frame f's first counts[f] rows (-1: nidx[f] outside 0 .. cap), nothing beyond them.  They drop into describe_features_batch."""
+    F, cap = xy.shape[0], xy.shape[1]
+    dev = xy.device
+    _expect(idx, torch.int32, (F, cap))
+    _expect(nidx, torch.int32, (F,))
+    _expect(xy, torch.float32, (F, cap, 2))
+    for t, dt in ((response, torch.float32), (angle, torch.float32), (octave, torch.int32)):
+        if t is not None:
+            _expect(t, dt, (F, cap))
+    like = lambda t: None if t is None else torch.zeros_like(t)   # noqa: E731
+    ptr = lambda t: 0 if t is None else t.data_ptr()              # noqa: E731
+    xy_o, resp_o, ang_o, oct_o = torch.zeros_like(xy), like(response), like(angle), like(octave)
+    counts = _zeros(dev, (F,), torch.int32)
+    args = (idx.data_ptr(), nidx.data_ptr(), F, cap, xy.data_ptr(), ptr(response), ptr(angle), ptr(octave), xy_o.data_ptr(), ptr(resp_o),
+            ptr(ang_o), ptr(oct_o), counts.data_ptr())
+    _on_torch_stream(ctx, dev, lambda: ctx.gather_keypoints(*args), use_torch_stream)
+    return xy_o, resp_o, ang_o, oct_o, counts
+
+
+_SIDE_ARRAYS = (("xy", torch.float32, (2,)), ("xy_undist", torch.float32, (2,)), ("angle", torch.float32, ()),
+                ("response", torch.float32, ()), ("octave", torch.int32, ()), ("src_idx", torch.int32, ()), ("det_dist", torch.float64, ()))
+
+
+class FrameRowsDevice(FrameSet):
+    """What ps_assemble_frames / ps_front_end_frames write: a dense frame set -- desc (F, cap, 32) uint8 (assemble_frames leaves it
+    zero: it writes no descriptors), pts (F, cap, 3) float32, nkpts (F,) int32: everything a FrameSetDevice is to run_pairs -- and
+    the side arrays named in `side` (default all): xy, xy_undist (F, cap, 2) float32, angle, response (F, cap) float32, octave,
+    src_idx (F, cap) int32, det_dist (F, cap) float64; the others are None."""
+
+    def __init__(self, F, cap, device, side=None):
+        self.device, self.num_frames, self.max_kpts = torch.device(device), int(F), int(cap)
+        self._zero_frames(self.num_frames, None)
+        names = [n for n, _, _ in _SIDE_ARRAYS] if side is None else list(side)
+        for n, dt, tail in _SIDE_ARRAYS:
+            setattr(self, n, _zeros(self.device, (self.num_frames, self.max_kpts) + tail, dt) if n in names else None)
+
+    def out_struct(self, angle_in=None, response_in=None, octave_in=None):
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        return PsFrameRowsOut(ptr(self.pts), ptr(self.nkpts), ptr(self.xy), ptr(self.xy_undist), ptr(self.angle), ptr(self.response),
+                              ptr(self.octave), ptr(self.src_idx), ptr(self.det_dist), ptr(angle_in), ptr(response_in), ptr(octave_in))
+
+    def download(self):
+        """dict of numpy arrays: desc, pts, nkpts and every side array that is there."""
+        names = ["desc", "pts", "nkpts"] + [n for n, _, _ in _SIDE_ARRAYS if getattr(self, n) is not None]
+        return {n: getattr(self, n).cpu().numpy() for n in names}
+
+
+def assemble_frames(ctx, geometry, depth, xy, kept_idx, num_kept, angle=None, response=None, octave=None, first_depth_frame=0, side=None,
+                    out=None, use_torch_stream=True):
+    """Undistortion, back-projection and detection distance of the described key points in the described order
+    (ps_assemble_frames): geometry _abi.frame_geometry(...); depth a uint16 device tensor (D, rows, cols), frame f reads depth frame
+    first_depth_frame + f; xy (F, cap, 2) float32 and kept_idx (F, cap) int32 / num_kept (F,) int32 -- what describe_features_batch
+    took and returned; angle / response / octave (F, cap): the key points' columns, needed where `side` names them.  side: the side
+    arrays wanted (default: all whose input is there).  Returns a FrameRowsDevice, written asynchronously."""
+    F, cap = xy.shape[0], xy.shape[1]
+    dev = xy.device
+    _expect(xy, torch.float32, (F, cap, 2))
+    _expect(kept_idx, torch.int32, (F, cap))
+    _expect(num_kept, torch.int32, (F,))
+    if side is None:
+        have = dict(angle=angle, response=response, octave=octave)
+        side = [n for n, _, _ in _SIDE_ARRAYS if have.get(n, True) is not None]
+    out = out or FrameRowsDevice(F, cap, dev, side)
+    ds = DepthSet(depth, depth.shape[1], depth.shape[2])
+    o = out.out_struct(angle, response, octave)
+    _on_torch_stream(ctx, dev, lambda: ctx.assemble_frames(geometry, ds, first_depth_frame, xy.data_ptr(), kept_idx.data_ptr(),
+                                                           num_kept.data_ptr(), F, cap, o), use_torch_stream)
+    return out
+
+
+class FrontEnd(_Handle):
+    """The device-resident per-frame front end for up to `max_frames` images of rows x cols x channels bytes a call
+    (ps_front_end_create): an ORB detector, an ORB pyramid set and every intermediate array.  params: _abi.front_end_params(...),
+    default the shipped ones; pattern as OrbPyramids takes it."""
+
+    _destroy = "ps_front_end_destroy"
+
+    def __init__(self, ctx, rows, cols, channels, max_frames, params=None, pattern=None):
+        self.ctx, self.rows, self.cols, self.channels, self.max_frames = ctx, int(rows), int(cols), int(channels), int(max_frames)
+        self.params = params or front_end_params()
+        self.handle = ctx.front_end_create(rows, cols, channels, self.params, pattern, max_frames)
+
+
+def front_end_frames_batch(ctx, fe: FrontEnd, images, depth, geometry, capacity=None, side=None, out=None, use_torch_stream=True):
+    """A batch of RGB-D images to a frame set (ps_front_end_frames): images a uint8 device tensor (F, rows, cols[, channels]) of the
+    front end's shape, depth a uint16 device tensor (F, rows, cols), geometry _abi.frame_geometry(...); capacity: rows per frame
+    (default max(1, maximalTrackedFeatures)).  Returns a FrameRowsDevice -- a frame set for run_pairs with the side arrays of
+    `side` (default all) --, written asynchronously, ordered like run_pairs."""
+    s = _image_set(images, fe.rows, fe.cols, fe.channels)
+    ds = DepthSet(depth, fe.rows, fe.cols)
+    F, dev = images.shape[0], images.device
+    cap = max(1, int(fe.params.detect.maximalTrackedFeatures)) if capacity is None else int(capacity)
+    out = out or FrameRowsDevice(F, cap, dev, side)
+    o = out.out_struct()
+    _on_torch_stream(ctx, dev, lambda: ctx.front_end_frames(fe.handle, s, ds, geometry, cap, out.desc.data_ptr(), o), use_torch_stream)
+    return out
+
+
+def run_image_sequence(ctx, fe: FrontEnd, images, depth, geometry, params, cfg, capacity=None, side=None, use_torch_stream=True):
+    """Visual odometry over a sequence of RGB-D images with no host step: front_end_frames_batch, then run_pairs on the consecutive
+    pairs (f, f + 1).  params / cfg: the RANSAC parameters and configuration of run_pairs; K is the geometry's.  Returns
+    (frames: FrameRowsDevice, batch: PairBatchDevice), both written asynchronously."""
+    frames = front_end_frames_batch(ctx, fe, images, depth, geometry, capacity, side, use_torch_stream=use_torch_stream)
+    F = frames.num_frames
+    pairs = np.stack([np.arange(0, max(F - 1, 0)), np.arange(1, max(F, 1))], axis=1).astype(np.int32)
+    batch = PairBatchDevice(pairs, frames.max_kpts, frames.device)
+    if batch.P:
+        run_pairs(ctx, params, cfg, np.array(list(geometry.K), np.float32), frames, batch, use_torch_stream)
+    return frames, batch
 
 
 class MapBatchDevice(PairResultsDevice):
