@@ -386,6 +386,8 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
     __shared__ int s_cnt[kBlock];
     __shared__ int s_tot[kBlock]; // kind 2, split match range: the counts of the range's parts meet here
     __shared__ int s_pref[2];
+    __shared__ int s_qn[kBlock / 64]; // what each wave leaves to the work-group's final drain
+    static_assert(kBlock / 64 == 4, "the final drain finds an entry's wave among four");
 
     int tid = threadIdx.x;
     // (kind 2 calls this in a loop: without the empty asm the compiler computes everything that hangs on the thread index --
@@ -451,13 +453,30 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
         if (!LIST && st.hBase + (int)bx * kBlock >= hEnd) return true;
     }
 
-    // (a wavefront without a hypothesis of its own has nothing to do -- the 64-hypothesis prefix of the adaptive
-    // schedules fills one of the four; a pass with a split match range has no such wavefront, and a barrier to come)
-    if (cover == kBlock && hFirstOfWave(h, lane) >= hEnd) return false;
+    // (a wavefront without a hypothesis of its own has nothing to sweep -- the 64-hypothesis prefix of the adaptive
+    // schedules fills one of the four; a pass with a split match range has no such wavefront -- but it goes to the barriers
+    // of the work-group's final drain and takes its share of the entries; the models-only launch has neither)
+    const bool idle = cover == kBlock && hFirstOfWave(h, lane) >= hEnd; // (wave-uniform)
+    if (KIND == 0 && st.genOnly && idle) return false;
 
+    const float4 *__restrict__ pa = recA + rbase;
+    const float4 *__restrict__ pb = recB + rbase;
+    const float4 *__restrict__ pc = recC + rbase;
+    const float4 *__restrict__ pe = recE + rbase;
+    const float2 *__restrict__ pf = recF + rbase * 5;
+    // position of the hot record -> match of the original record arrays (stages after ps_stage_reorder; the cold paths)
+    const int32_t *__restrict__ pperm = (pruned && st.perm != nullptr) ? st.perm + rbase : nullptr;
+    auto orig = [&](int m) { return pperm != nullptr ? pperm[m] : m; };
+
+    bool valid = false;
+    int cnt = 0;
+    int qn = 0;                      // parked evaluations of this wave (wave-uniform)
+    unsigned long long parked = 0;
+    bool swept = false;              // the decision-exact sweep ran (wave-uniform): its counts are in s_cnt, its statistics due
+    int mFrontS = 0, mPairsS = 0, frontParkTripsS = 0; // (statistics of the sweep, reported after the final drain)
+    if (!idle) { // (not indented: down to the final drain)
     Rigid mdl;
     set_identity(mdl);
-    bool valid = false;
     if (LIST) {
         if (h < hEnd) {
             load_model(ma, (size_t)p * ma.modelH + h, mdl); // parked by stage 1 (only valid samples survive it; h < modelH: a
@@ -491,14 +510,6 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
     }
     s_cnt[tid] = 0;
 
-    const float4 *__restrict__ pa = recA + rbase;
-    const float4 *__restrict__ pb = recB + rbase;
-    const float4 *__restrict__ pc = recC + rbase;
-    const float4 *__restrict__ pe = recE + rbase;
-    const float2 *__restrict__ pf = recF + rbase * 5;
-    // position of the hot record -> match of the original record arrays (stages after ps_stage_reorder; the cold paths)
-    const int32_t *__restrict__ pperm = (pruned && st.perm != nullptr) ? st.perm + rbase : nullptr;
-    auto orig = [&](int m) { return pperm != nullptr ? pperm[m] : m; };
     const float2 pbnd = pairBound[p];
     const float cmax = pbnd.x, umax = pbnd.y;
 
@@ -508,7 +519,6 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
     // none of it has to stay alive across the drain's register-hungry code (kept alive it was spilled to scratch on
     // every launch: 40 dwords per lane, 349 MB of writes per 499 pairs, profiles/r02d).  The size S the bounds hang on
     // comes out of the same pass (one general inverse per hypothesis, not two).
-    int cnt = 0;
     {
         FastModel F;
         // per-hypothesis coefficients of the two limits (see rebuild), held as TWO register pairs whose halves the packed FMAs
@@ -589,10 +599,8 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
                 score_accumulate<MODE, false>(md, iv, k, A, B, C, cnt);
             }
         } else {
-        int qn = 0;                      // parked evaluations of this wave (wave-uniform)
-        unsigned long long parked = 0;
-
-        // value-exact evaluation of the parked (match, lane) pairs, one lane each
+        // value-exact evaluation of the parked (match, lane) pairs, one lane each: the wave's own drain, when its queue is full
+        // in the middle of the sweep (what is left at the end goes to the work-group's final drain, below)
         auto drain = [&]() {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             for (int e = lane; e < qn; e += 64) {
@@ -750,17 +758,59 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
             s_q[wv][qn + lanes_below(execAll)] = ((uint32_t)mPairs << 6) | (uint32_t)lane;
             qn += n;
         }
-        drain();
+        parked += (unsigned long long)qn; // (the statistics count entries parked, whoever evaluates them)
+        swept = true;
+        mFrontS = mFront, mPairsS = mPairs, frontParkTripsS = frontParkTrips;
+        }
+    }
+    } // (!idle)
+
+    // The final drain, ONE for the work-group.  A wave ends its sweep with a handful of entries (0.07 % of the evaluations and
+    // 0.9 % of the pre-test trips are parked): drained by the wave itself they cost a whole value-exact pass -- twelve LDS
+    // reads, the general inverse, three record loads, inlier_test -- with 5 ... 7 of 64 lanes busy, in every wave of every
+    // launch.  Instead the waves leave their entries in s_q[wave][0 .. qn), publish qn, and after a barrier the work-group
+    // takes the four queues as one list, entry e to thread e (in strides of 256): a wave whose stride holds no entry skips
+    // the value-exact code.  An entry names its thread (wave * 64 + lane) and its match; the model is that thread's in
+    // s_mdl, the verdict goes to that thread's s_cnt -- nothing else travels.  EVERY wave of the work-group comes here:
+    // the ones without a hypothesis and the ones that took the value-exact loop publish 0 (the exits above this point are
+    // uniform over the work-group).  The looping forms separate their passes by a barrier of their own, so the next pass
+    // writes s_q / s_qn / s_mdl / s_cnt only after every wave has left this one's second barrier.
+    if (lane == 0) s_qn[wv] = qn;
+    __syncthreads();
+    {
+        const int n1 = __builtin_amdgcn_readfirstlane(s_qn[0]);
+        const int n2 = n1 + __builtin_amdgcn_readfirstlane(s_qn[1]);
+        const int n3 = n2 + __builtin_amdgcn_readfirstlane(s_qn[2]);
+        const int n4 = n3 + __builtin_amdgcn_readfirstlane(s_qn[3]);
+        for (int e = tid; e < n4; e += kBlock) {
+            const int w = (e >= n1) + (e >= n2) + (e >= n3);                 // the wave that parked entry e ...
+            const int i = e - (w == 0 ? 0 : (w == 1 ? n1 : (w == 2 ? n2 : n3))); // ... as its i-th (i < its qn <= kQueueCap)
+            const uint32_t ent = s_q[w][i];
+            const int t = w * 64 + (int)(ent & 63u), m = orig((int)(ent >> 6));
+            Rigid md, iv;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+#pragma unroll
+                for (int b = 0; b < 3; ++b) md.R[a][b] = s_mdl[3 * a + b][t];
+                md.t[a] = s_mdl[9 + a][t];
+            }
+            inverse_rigid_general(md, iv);
+            const float4 A = pa[m], B = pb[m], C = pc[m];
+            if (inlier_test<MODE>(md, iv, k, A, B, C)) atomicAdd(&s_cnt[t], 1);
+        }
+    }
+    __syncthreads();
+    if (idle) return false;
+    if (swept) {
         cnt += s_cnt[tid];
         if (dbg != nullptr && lane == 0) {
             atomicAdd(&dbg[0], parked);
             atomicAdd(&dbg[1], (unsigned long long)(m1 - m0) * 64ull);
-            if (PRE) { // (ps_debug_score_stats_ex: [2] / [3] = pre-test trips without / with a lane left to the value-exact test)
-                const int frontTrips = mFront > m0 ? ((mFront < mPairs ? mFront : mPairs) - m0) >> 1 : 0;
-                atomicAdd(&dbg[3], (unsigned long long)frontParkTrips);
-                atomicAdd(&dbg[2], (unsigned long long)(frontTrips - frontParkTrips));
+            if (KIND == 1) { // (ps_debug_score_stats_ex: [2] / [3] = pre-test trips without / with a lane left to the value-exact test)
+                const int frontTrips = mFrontS > m0 ? ((mFrontS < mPairsS ? mFrontS : mPairsS) - m0) >> 1 : 0;
+                atomicAdd(&dbg[3], (unsigned long long)frontParkTripsS);
+                atomicAdd(&dbg[2], (unsigned long long)(frontTrips - frontParkTripsS));
             }
-        }
         }
     }
     int tidE = tid; // (a fresh copy for the epilogue's LDS addresses: kept alive across the loops they went to scratch memory)
