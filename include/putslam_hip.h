@@ -1260,13 +1260,26 @@ size_t ps_abi_sizeof_loop_batch_f32(void);
  * from 16 to 1000 pairs, two read 601 k / 406 k / 183 k, six are worse than four: profiles/r06u/small_batch_chains.txt).  The chains'
  * contexts carry option "side_by_side" = chains: with other chains filling the gaps between its dependent launches the staged
  * scoring pays from 2 - 5 times smaller batches on than it does for a lone context (profiles/r06u/bench_data_crossover.txt).
- * The chains are ordered only within themselves; nothing ever makes one wait for another.
+ * The chains are ordered only within themselves; for a host that gives batches in flight output blocks of their own, nothing ever
+ * makes one wait for another (the one exception is under submit: a block shared by batches in flight on several chains).
  *   submit: arguments of ps_vo_pairs_device (device pointers); pair p draws from cfg->seed + p: the outputs are byte for byte
  *           those of ONE ps_vo_pairs_device call.  Returns at once; *ticket (may be NULL) names the batch.  Inputs and outputs
  *           must stay valid until the batch is complete.  Batches in flight run CONCURRENTLY: give consecutive batches output
  *           blocks of their own (`chains` blocks used in turn are enough: batch n + chains runs on batch n's chain, behind it).
- *           A batch that is handed the block (out->pose) of a batch still in flight on another chain is queued behind that one on
- *           its chain instead -- correct, and as fast as one context.  Reading a batch's results needs its ticket waited for.  At most 64 batches are in flight: the 65th submit waits for
+ *           A batch that is handed the block of batches still in flight is ordered behind them -- the block holds the results
+ *           of the batch submitted last, row by row -- instead of racing them (csrc/ps_queue_hazard.h; every batch still in
+ *           the ring is looked at, whatever else its chain has been given since):
+ *             - the writers in flight all sit on one chain: the batch follows them on that chain, whole, whatever chain its
+ *               number names and whether or not it would have been split -- correct, and as fast as one context; no chain waits;
+ *             - they sit on several chains (a whole batch after a split one, PUTSLAM_HIP_QUEUE_SPLIT_FROM; split batches with
+ *               different bounds): a whole batch runs on one of those chains, which waits (device-side, hipStreamWaitEvent) for the
+ *               others' events; a split batch keeps its bounds and every share waits for the shares in flight on other chains
+ *               whose rows it writes.  Split after split with the same bounds needs nothing: chain by chain they are in order.
+ *             Only rows count: a shorter batch is not ordered behind shares that write rows it does not have.
+ *           The block is identified by out->pose ALONE (a batch without a pose array: by NULL, all such batches as one block).
+ *           Blocks with different pose arrays that share any other array (matches, numMatches, inlierMask, stats), and arrays
+ *           that overlap without being equal, are not seen: keeping those apart stays the host's responsibility.
+ *           Reading a batch's results needs its ticket waited for.  At most 64 batches are in flight: the 65th submit waits for
  *           the first.  If the chain's call fails the error is returned (text: ps_last_error of ctx); the ticket still stands
  *           for whatever part of the batch was queued.
  *   wait / query: the host blocks until / asks whether that batch is complete (query: 1 complete, 0 not yet).

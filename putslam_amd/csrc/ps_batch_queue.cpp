@@ -19,11 +19,14 @@
 // 499 pairs: 610 k on the bench sequence, 125: 490 k, 64: 416 k with the chains' side_by_side option, which moves the staged
 // scoring's crossover to where it lies when other chains fill the gaps between its launches: profiles/r06u, profiles/r06v.)
 //
-//   * chains are ordered only within themselves: submit never makes one chain wait for another, and a batch's completion is an
-//     event per chain it ran on, recorded behind its last launch -- waited for by the host (ps_batch_queue_wait) or by a stream of
-//     the host's (ps_batch_queue_wait_on_stream), never by another chain;
+//   * chains are ordered only within themselves: a batch's completion is an event per chain it ran on, recorded behind its last
+//     launch -- waited for by the host (ps_batch_queue_wait) or by a stream of the host's (ps_batch_queue_wait_on_stream), and by
+//     another chain in one case only: a batch handed an output block that batches still in flight on SEVERAL chains write (whole
+//     after split, ps_queue_hazard.h).  A host that gives batches in flight blocks of their own never makes a chain wait;
 //   * pair p of a batch keeps its hypothesis stream cfg->seed + p: results are byte for byte those of one ps_vo_pairs_device call;
-//   * consecutive batches run side by side: they need output blocks of their own (two blocks used in turn do for two chains).
+//   * consecutive batches run side by side: they need output blocks of their own (two blocks used in turn do for two chains);
+//     a batch handed the block of batches still in flight runs behind them (ps_queue_hazard.h: the rule, and every ticket's
+//     block and bounds are what it reads).
 // Host-only translation unit: everything here is queue bookkeeping around ps_vo_pairs_device.
 #include <hip/hip_runtime_api.h>
 
@@ -34,17 +37,19 @@
 #include <vector>
 
 #include "ps_internal.h"
+#include "ps_queue_hazard.h"
 
 namespace {
 
-constexpr int kMaxChains = PS_BATCH_QUEUE_MAX_CHAINS;
+constexpr int kMaxChains = kQueueMaxChains;
 constexpr int kDefaultChains = 4; // (profiles/r06u/small_batch_chains.txt: the best count at every batch size tried)
 constexpr int kTickets = 64;      // batches that can be in flight; submit waits for the oldest when the ring is full
 constexpr int kSplitFromPairs = 0x7fffffff; // (never: whole batches, the chains in turn; PUTSLAM_HIP_QUEUE_SPLIT_FROM overrides)
 
 struct Ticket {
     long long seq = -1;              // batch number this slot holds (-1: never used)
-    bool used[kMaxChains] = {};
+    QueueBatchRecord rec;            // its output block, its bounds and the chains it ran on: what the hazard rule reads
+    bool done[kMaxChains] = {};      // the chain's event was seen complete (completion is for good: not asked again)
     hipEvent_t ev[kMaxChains] = {};
 };
 
@@ -60,14 +65,6 @@ struct PsBatchQueue {
     Ticket ring[kTickets];
     long long next = 0;              // number of the next batch
     int32_t lastBounds[kMaxChains + 1] = {};
-    // the output block (its pose array) and the number of the last whole batch every chain was given: a batch that writes the block
-    // of a batch still in flight on ANOTHER chain follows it on that chain instead of racing it
-    const void *lastOut[kMaxChains] = {};
-    long long lastSeq[kMaxChains];
-    PsBatchQueue()
-    {
-        for (long long &x : lastSeq) x = -1;
-    }
 };
 
 namespace {
@@ -81,34 +78,12 @@ int qfail(PsBatchQueue *q, int code, const std::string &what)
 int wait_slot(PsBatchQueue *q, Ticket &t)
 {
     for (int i = 0; i < q->chains; ++i)
-        if (t.used[i]) {
+        if (t.rec.used[i] && !t.done[i]) {
             hipError_t e = hipEventSynchronize(t.ev[i]);
             if (e != hipSuccess) return qfail(q, PS_ERR_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
+            t.done[i] = true;
         }
     return PS_OK;
-}
-
-// which pairs of a batch of P go to which chain: bounds[0 .. chains]
-void split(const PsBatchQueue *q, int P, long long seq, int32_t *bounds)
-{
-    const int C = q->chains;
-    if (C == 1) {
-        bounds[0] = 0;
-        bounds[1] = P;
-        return;
-    }
-    if (P < q->splitFrom) { // the whole batch on one chain, the chains in turn
-        const int c = (int)(seq % C);
-        for (int i = 0; i <= C; ++i) bounds[i] = i <= c ? 0 : P;
-        return;
-    }
-    if (C == 2) {
-        bounds[0] = 0;
-        bounds[1] = (int32_t)((long long)P * q->splitPermille / 1000);
-        bounds[2] = P;
-        return;
-    }
-    for (int i = 0; i <= C; ++i) bounds[i] = (int32_t)((long long)P * i / C);
 }
 
 } // namespace
@@ -212,30 +187,37 @@ int ps_batch_queue_submit(PsBatchQueue *q, const PsRansacParams *params, const P
         int rc = wait_slot(q, t);
         if (rc != PS_OK) return rc;
     }
-    int32_t bounds[kMaxChains + 1];
-    split(q, P, seq, bounds);
-    if (q->chains > 1 && P > 0 && P < q->splitFrom) {
-        // Whole batches run side by side on different chains, so two of them must not write the same output block.  A host that
-        // hands over the block of a batch that is still in flight on another chain gets stream order instead of a race: the new
-        // batch follows that one on ITS chain (and the pair run one after the other: blocks of their own, in turn, is how a
-        // host gets the queue's rate).
-        int mine = 0;
-        for (int i = 0; i < q->chains; ++i)
-            if (bounds[i + 1] > bounds[i]) mine = i;
-        for (int j = 0; j < q->chains; ++j) {
-            if (j == mine || q->lastOut[j] != (const void *)out->pose || q->lastSeq[j] < 0) continue;
-            Ticket &tj = q->ring[q->lastSeq[j] % kTickets];
-            if (tj.seq != q->lastSeq[j] || !tj.used[j]) continue; // (older than the ring: complete)
-            const hipError_t e = hipEventQuery(tj.ev[j]);
-            if (e == hipErrorNotReady) {
+    // Batches run side by side on different chains, so two of them must not write the same output block at once.  A host that
+    // hands over the block (out->pose names it) of batches still in flight gets stream order instead of a race: ps_queue_hazard.h
+    // reads every ticket of the ring -- a chain can hold batches on several blocks -- and moves the batch behind them, or, where
+    // they sit on several chains, makes its chain wait for theirs.
+    int32_t nominal[kMaxChains + 1];
+    queue_nominal_bounds(q->chains, P, seq, q->splitFrom, q->splitPermille, nominal);
+    QueuePlan plan;
+    const int older = (int)(seq < kTickets - 1 ? seq : kTickets - 1); // (the slot this batch takes is complete: wait_slot)
+    queue_hazard_plan(
+        q->chains, nominal, (const void *)out->pose, older,
+        [&](int age) -> const QueueBatchRecord * {
+            const Ticket &o = q->ring[(seq - age) % kTickets];
+            return o.seq == seq - age ? &o.rec : nullptr;
+        },
+        [&](int age, int chain) {
+            Ticket &o = q->ring[(seq - age) % kTickets];
+            if (o.done[chain]) return true;
+            if (hipEventQuery(o.ev[chain]) == hipErrorNotReady) {
                 (void)hipGetLastError();
-                for (int i = 0; i <= q->chains; ++i) bounds[i] = i <= j ? 0 : P;
-                mine = j;
-                break;
+                return false;
             }
-        }
-        q->lastOut[mine] = (const void *)out->pose;
-        q->lastSeq[mine] = seq;
+            o.done[chain] = true;
+            return true;
+        },
+        plan);
+    const int32_t *bounds = plan.bounds;
+    for (int w = 0; w < plan.nwaits; ++w) {
+        const QueueWait &qw = plan.waits[w];
+        const hipError_t e = hipStreamWaitEvent((hipStream_t)ps_context_stream(q->ctx[qw.waiter]), q->ring[(seq - qw.age) % kTickets].ev[qw.chain], 0);
+        if (e != hipSuccess) // (nothing of the batch is queued yet: no ticket)
+            return qfail(q, PS_ERR_HIP, std::string("ps_batch_queue_submit: hipStreamWaitEvent: ") + hipGetErrorString(e));
     }
     const size_t cap = (size_t)frames->maxKpts;
     bool used[kMaxChains] = {};
@@ -265,7 +247,12 @@ int ps_batch_queue_submit(PsBatchQueue *q, const PsRansacParams *params, const P
     }
     // (the ticket exists even for a failed batch: waiting for it waits for whatever part of it was queued)
     t.seq = seq;
-    for (int i = 0; i < kMaxChains; ++i) t.used[i] = used[i];
+    t.rec.block = (const void *)out->pose;
+    for (int i = 0; i <= q->chains; ++i) t.rec.bounds[i] = bounds[i];
+    for (int i = 0; i < kMaxChains; ++i) {
+        t.rec.used[i] = used[i];
+        t.done[i] = false;
+    }
     for (int i = 0; i <= q->chains; ++i) q->lastBounds[i] = bounds[i];
     q->next = seq + 1;
     if (ticket) *ticket = seq;
@@ -307,7 +294,7 @@ int ps_batch_queue_query(PsBatchQueue *q, int64_t ticket)
     Ticket *t = find_ticket(q, ticket, &rc);
     if (!t) return rc == PS_OK ? 1 : rc;
     for (int i = 0; i < q->chains; ++i)
-        if (t->used[i]) {
+        if (t->rec.used[i]) {
             hipError_t e = hipEventQuery(t->ev[i]);
             if (e == hipErrorNotReady) {
                 (void)hipGetLastError();
@@ -326,7 +313,7 @@ int ps_batch_queue_wait_on_stream(PsBatchQueue *q, int64_t ticket, void *hipStre
     if (!t) return rc;
     if (hipSetDevice(q->device) != hipSuccess) return qfail(q, PS_ERR_HIP, "ps_batch_queue_wait_on_stream: hipSetDevice");
     for (int i = 0; i < q->chains; ++i)
-        if (t->used[i]) {
+        if (t->rec.used[i]) {
             hipError_t e = hipStreamWaitEvent((hipStream_t)hipStream, t->ev[i], 0);
             if (e != hipSuccess) return qfail(q, PS_ERR_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e));
         }
