@@ -1543,6 +1543,136 @@ size_t ps_abi_sizeof_results(void);
 size_t ps_abi_sizeof_host_results(void);
 size_t ps_abi_sizeof_map_batch(void);
 
+/* ---- The tracking VO step (VOVersion = 1): Matcher::trackKLT, src/Matcher/matcher.cpp:147-211, for P pairs with no host step
+ * -- track, select, undistort and back-project the tracked positions, carry the key points' columns along, and run the estimator
+ * on the DMatch(i, j, 0) lists the selection wrote.  Three calls: the estimator over caller-supplied device-resident match lists,
+ * the tracked rows, and the whole step.  DESIGN.md section 8.14. */
+typedef struct PsPointSets {  /* numSets blocks of 3-D points, DEVICE */
+    const float *pts;        /* set s: capacity x 3 floats from pts + s x setStride bytes */
+    const int32_t *counts;   /* numSets: the rows of every set that are points */
+    int32_t numSets, capacity;
+    size_t setStride;        /* BYTES between sets, 0 = dense (capacity x 12); a multiple of 4, at least capacity x 12 */
+} PsPointSets;
+size_t ps_abi_sizeof_point_sets(void);
+
+/* RANSAC::estimateTransformation (RANSAC.cpp:50-174) / RANSAC_USAC (USAC_wrapper.cpp:104-151) for P pairs with the caller's match
+ * lists.  Pair p matches set pairs[2p] of `prev` (queryIdx) with set pairs[2p + 1] of `cur` (trainIdx); pairs = NULL: set p of
+ * both.  matches P x cap, numMatches P, pairs P x 2 int32: DEVICE, as is everything `prev`, `cur` and `out` point to.  out:
+ * inlierMask P x cap, pose P x 16, stats P; its matches / numMatches are ignored and may be NULL.  cfg->sampleIdx must be NULL;
+ * pair p draws from cfg->seed + p.  Asynchronous on the context's stream; only the context's scratch may grow.
+ * For every pair the mask, the pose and the statistics are, byte for byte, those of ps_ransac_rigid3d on (prev set, cur set,
+ * matches[p], numMatches[p]) with seed cfg->seed + p.  What that host form refuses, and device data may still hold, is decided
+ * here:
+ *  - a match whose queryIdx / trainIdx lies outside 0 .. count-1 of its set is never followed: it is dropped like a match that
+ *    fails the depth gate (RANSAC.cpp:65-74), its mask byte is 0, and pointInlierRatio does not count its trainIdx.  The results
+ *    are those of the list without it, except that stats.numMatchesIn stays numMatches[p] and the mask keeps the list's positions;
+ *  - numMatches[p] outside 0 .. cap, a pair index outside its group of sets, or a set count outside 0 .. capacity: the list counts
+ *    as empty -- identity pose, NO mask byte written, the statistics of a list below minimalNumberOfMatches (RANSAC.cpp:77-80)
+ *    with numMatchesIn = 0.
+ * NULL params / cfg / prev / cur / out or (P > 0) a NULL array, P < 0, cap < 1, cap above 1 << 22, a set stride that breaks the rule
+ * above, a sampleIdx -> PS_ERR_BAD_ARG; capacity of `cur` above PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; text in ps_last_error.  P == 0 is PS_OK. */
+int ps_ransac_match_lists(PsContext *ctx, const PsRansacParams *params, const PsRansacConfig *cfg, const float *K,
+                          const PsPointSets *prev, const PsPointSets *cur, const int32_t *pairs, const PsDMatch *matches,
+                          const int32_t *numMatches, int P, int cap, const PsPairResults *out);
+
+typedef struct PsTrackedCarry {  /* the previous rows' key point columns, DEVICE, P x capacity each; NULL = not carried */
+    const float *angle, *response;
+    const int32_t *octave;
+    const double *detDist;   /* prevDetDists: carried, not recomputed (matcher.cpp:183-186) */
+} PsTrackedCarry;
+typedef struct PsTrackedRows {   /* the rows a tracked frame leaves, DEVICE, P x capacity rows each (counts: P) */
+    float *xy;               /* x 2: the tracked (distorted) position -- prevFeaturesDistorted of the next frame; required */
+    float *xyUndist;         /* x 2; NULL = not wanted */
+    float *pts;              /* x 3: features3D; required */
+    int32_t *counts;         /* required */
+    float *angle, *response; /* each wanted exactly where its PsTrackedCarry column is given: both or neither */
+    int32_t *octave;
+    double *detDist;
+} PsTrackedRows;
+size_t ps_abi_sizeof_tracked_carry(void);
+size_t ps_abi_sizeof_tracked_rows(void);
+
+/* The tracked rows, matcher.cpp:159-186, for P pairs.  For output row j < numKept[p] with i = keptIdx[p][j]: out->xy[p][j] =
+ * nextPts[p][i]; xyUndist = the arithmetic of ps_remove_image_distortion on it; pts = the arithmetic of ps_keypoints2Dto3D on
+ * xyUndist in depth frame depthFrame[p] under ps_assemble_frames' rule (the frame alone, as the DENSE image the reference holds);
+ * angle / response / octave / detDist [p][j] = carry's [p][i].  out->counts[p] = numKept[p]; where that lies outside 0 ..
+ * capacity (the -1 of ps_klt_select_device) counts[p] = -1 and nothing else is written for the pair.  An index outside 0 ..
+ * capacity-1 is not followed: the row is written as zeros.  A depthFrame[p] outside 0 .. numFrames-1 gives points of depth 0, the
+ * keypoints2Dto3D result for no depth.  Nothing is written beyond a pair's count.  nextPts P x capacity x 2 floats, keptIdx P x
+ * capacity, numKept and depthFrame P int32: DEVICE.  carry may be NULL (nothing carried).  THE ROWS OF ONE FRAME ARE THE PREVIOUS
+ * ROWS OF THE NEXT: xy / pts / counts / the carried columns, unchanged, are what ps_track_vo_pairs takes as prevXY / prevPts /
+ * prevCounts / prev.  A NULL among geometry, depth, depthFrame, nextPts, keptIdx, numKept, out, out->xy, out->pts, out->counts, a
+ * carried column without its output or the reverse, a depth set whose strides do not resolve or (P > 0) without pixels, capacity
+ * < 1, P outside 0 .. 65535 -> PS_ERR_BAD_ARG; capacity above PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; P == 0 is PS_OK.  One launch,
+ * asynchronous; no scratch.
+ * THE OUTPUT BLOCKS MUST NOT OVERLAP THE INPUTS: a row is read at keptIdx[p][j] while other rows are written at j, so rows cannot be
+ * assembled in place -- a chain alternates between two sets of blocks (device_batch.run_tracked_sequences allocates one per step). */
+int ps_assemble_tracked(PsContext *ctx, const PsFrameGeometry *geometry, const PsDepthSet *depth, const int32_t *depthFrame,
+                        const float *nextPts, const int32_t *keptIdx, const int32_t *numKept, int P, int capacity,
+                        const PsTrackedCarry *carry, const PsTrackedRows *out);
+
+typedef struct PsTrackVoParams {
+    double trackingErrorThreshold;                   /* OpenCVParams.trackingErrorThreshold */
+    double minimalReprojDistanceNewTrackingFeatures; /* OpenCVParams.minimalReprojDistanceNewTrackingFeatures */
+    int32_t removeTooCloseFeatures;                  /* must be 0 (below) */
+    int32_t reserved;
+} PsTrackVoParams;
+typedef struct PsTrackVoIn {     /* DEVICE pointers */
+    const int32_t *pairs;        /* P x 2: (previous, current) slots of the pyramid set */
+    const int32_t *depthFrame;   /* P: the depth frame of every pair; NULL = the pair's current slot */
+    const float *prevXY;         /* P x capacity x 2: prevFeaturesDistorted */
+    const float *prevPts;        /* P x capacity x 3: prevFeatures3D */
+    const int32_t *prevCounts;   /* P */
+    PsTrackedCarry prev;         /* prevKeyPoints' columns and prevDetDists */
+} PsTrackVoIn;
+typedef struct PsTrackVoOut {    /* DEVICE pointers, P x capacity rows each unless noted */
+    float *nextPts;              /* x 2; the tracker's: caller-owned intermediates, all three required; nextPts is READ under */
+    uint8_t *status;             /*      PS_KLT_USE_INITIAL_FLOW, as for ps_klt_track_device */
+    float *err;
+    PsDMatch *matches;           /* DMatch(i, j, 0): ps_klt_select_device's; required with numMatches and keptIdx */
+    int32_t *numMatches;         /* P */
+    int32_t *keptIdx;
+    PsTrackedRows rows;          /* the frame's rows: ps_assemble_tracked's; rows.xy is also the selection's keptPts */
+    uint8_t *inlierMask;         /* over matches; required with pose and stats */
+    float *pose;                 /* P x 16 column-major */
+    PsRansacStats *stats;        /* P */
+} PsTrackVoOut;
+size_t ps_abi_sizeof_track_vo_params(void);
+size_t ps_abi_sizeof_track_vo_in(void);
+size_t ps_abi_sizeof_track_vo_out(void);
+
+/* matcher.cpp:147-211 for P pairs of slots of a pyramid set, as one queue of launches on the context's stream: the launch of
+ * ps_klt_track_device on (in->pairs, in->prevXY, in->prevCounts), the launch of ps_klt_select_device with tp's two thresholds,
+ * the launch of ps_assemble_tracked, and the chain of ps_ransac_match_lists on (in->prevPts with prevCounts, out->rows.pts with
+ * rows.counts, out->matches) with pair p = (set p, set p) and params->errorVersion as given (the caller puts errorVersionVO
+ * there).  It neither waits nor downloads; only the context's RANSAC scratch may grow.  A pair with prevCounts[p] == 0 gives the
+ * identity and no matches (:147-148); a pair whose count the selection refuses (-1) gives rows.counts[p] = -1 and the results of
+ * an empty list.  The rows of a call, unchanged, are the previous rows of the next (ps_assemble_tracked): a tracked sequence
+ * chains on one stream until a refill is due.
+ * tp->removeTooCloseFeatures != 0 -> PS_ERR_UNSUPPORTED: the reference erases the removed features from features3D and leaves the
+ * surviving matches' trainIdx un-renumbered (matcher.cpp:960-963), so that RANSAC reads features3D at stale indices, possibly
+ * beyond its end -- there is no defined behaviour to restate; the shipped value is 0 (putslammatcherOpenCVParameters.xml:77), and
+ * a host that wants the filter runs ps_exclude_device itself.  Other errors are those of the four calls, all found before the first
+ * launch; outputs untouched.  No block of `out` may overlap a block of `in` (ps_assemble_tracked's rule: the next call takes this
+ * call's rows as its previous rows and writes OTHER blocks). */
+int ps_track_vo_pairs(PsContext *ctx, const PsKltPyramids *pyr, const PsKltParams *klt, const PsTrackVoParams *tp,
+                      const PsRansacParams *params, const PsRansacConfig *cfg, const PsFrameGeometry *geometry, const PsDepthSet *depth,
+                      const PsTrackVoIn *in, int P, int capacity, const PsTrackVoOut *out);
+
+/* The same for one pair: HOST pointers, uploads and downloads included, synchronous.  prevImg / nextImg rows x cols x channels bytes
+ * with rowStride bytes between rows, depth (the current frame's) rows x cols uint16 with depthStep bytes between rows (0 = dense
+ * either; a region keeps its parent's -- the depth rule is the set's: what lies between the rows is not read).  in: prevXY n x 2,
+ * prevPts n x 3 and the carried columns of n rows (pairs, depthFrame and prevCounts are ignored); out: HOST arrays of n rows --
+ * nextPts, matches, keptIdx, inlierMask, pose (16) and stats (1) required, the others NULL = not wanted; nextPts is read under
+ * PS_KLT_USE_INITIAL_FLOW; a carried column is returned only where `in` has it.  *numKept = the rows kept (also written to
+ * out->numMatches and out->rows.counts where given); the tracker's arrays are written for all n points, the others for the kept
+ * rows.  n == 0 gives the identity and the statistics of the empty list.  n above PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; other errors
+ * as above and as ps_perform_tracking's. */
+int ps_track_vo_pair(PsContext *ctx, const uint8_t *prevImg, const uint8_t *nextImg, const uint16_t *depth, int rows, int cols, int channels,
+                     size_t rowStride, size_t depthStep, const PsKltParams *klt, const PsTrackVoParams *tp, const PsRansacParams *params,
+                     const PsRansacConfig *cfg, const PsFrameGeometry *geometry, const PsTrackVoIn *in, int n, const PsTrackVoOut *out,
+                     int *numKept);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,6 +256,42 @@ def front_end_params(detect=None, describe=None, dbscan_eps=10.0):
     return PsFrontEndParams(detect, describe, float(dbscan_eps))
 
 
+# The tracking VO step (include/putslam_hip.h)
+class PsPointSets(C.Structure):
+    _fields_ = [("pts", C.c_void_p), ("counts", C.c_void_p), ("numSets", C.c_int32), ("capacity", C.c_int32), ("setStride", C.c_size_t)]
+
+
+class PsTrackedCarry(C.Structure):
+    _fields_ = [("angle", C.c_void_p), ("response", C.c_void_p), ("octave", C.c_void_p), ("detDist", C.c_void_p)]
+
+
+class PsTrackedRows(C.Structure):
+    _fields_ = [("xy", C.c_void_p), ("xyUndist", C.c_void_p), ("pts", C.c_void_p), ("counts", C.c_void_p), ("angle", C.c_void_p),
+                ("response", C.c_void_p), ("octave", C.c_void_p), ("detDist", C.c_void_p)]
+
+
+class PsTrackVoParams(C.Structure):
+    _fields_ = [("trackingErrorThreshold", C.c_double), ("minimalReprojDistanceNewTrackingFeatures", C.c_double),
+                ("removeTooCloseFeatures", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PsTrackVoIn(C.Structure):
+    _fields_ = [("pairs", C.c_void_p), ("depthFrame", C.c_void_p), ("prevXY", C.c_void_p), ("prevPts", C.c_void_p),
+                ("prevCounts", C.c_void_p), ("prev", PsTrackedCarry)]
+
+
+class PsTrackVoOut(C.Structure):
+    _fields_ = [("nextPts", C.c_void_p), ("status", C.c_void_p), ("err", C.c_void_p), ("matches", C.c_void_p),
+                ("numMatches", C.c_void_p), ("keptIdx", C.c_void_p), ("rows", PsTrackedRows), ("inlierMask", C.c_void_p),
+                ("pose", C.c_void_p), ("stats", C.c_void_p)]
+
+
+def track_vo_params(tracking_error_threshold=25.0, min_reproj_distance=3.0, remove_too_close_features=0):
+    """PsTrackVoParams; the defaults are the shipped OpenCVParams (trackingErrorThreshold 25, minimalReprojDistanceNewTrackingFeatures
+    3, removeTooCloseFeatures 0 -- the only value ps_track_vo_pairs takes)."""
+    return PsTrackVoParams(float(tracking_error_threshold), float(min_reproj_distance), int(remove_too_close_features), 0)
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

@@ -9,7 +9,8 @@ import os
 from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch,
                    PsMapBatchF32, PsMapStore, PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPairResults, PsPoseSetOut,
                    PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams, PsOrbParams, PsOrbDetectParams,
-                   PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams)
+                   PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoParams,
+                   PsTrackVoIn, PsTrackVoOut)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -60,6 +61,9 @@ EXPORTED = [
     "ps_detect_features_orb", "ps_debug_orb_detect_level", "ps_debug_orb_detect_passes", "ps_abi_sizeof_orb_detect_params",
     "ps_gather_keypoints", "ps_assemble_frames", "ps_front_end_create", "ps_front_end_destroy", "ps_front_end_frames", "ps_front_end_frame",
     "ps_abi_sizeof_depth_set", "ps_abi_sizeof_frame_geometry", "ps_abi_sizeof_frame_rows_out", "ps_abi_sizeof_front_end_params",
+    "ps_ransac_match_lists", "ps_assemble_tracked", "ps_track_vo_pairs", "ps_track_vo_pair",
+    "ps_abi_sizeof_point_sets", "ps_abi_sizeof_tracked_carry", "ps_abi_sizeof_tracked_rows", "ps_abi_sizeof_track_vo_params",
+    "ps_abi_sizeof_track_vo_in", "ps_abi_sizeof_track_vo_out",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -81,6 +85,9 @@ ABI_STRUCTS_ORB_DETECT = dict(orb_detect_params=PsOrbDetectParams)
 # ... and of frame assembly and the front end (ps_gather_keypoints / ps_assemble_frames / ps_front_end_*)
 ABI_STRUCTS_FRAME_ASSEMBLY = dict(depth_set=PsDepthSet, frame_geometry=PsFrameGeometry, frame_rows_out=PsFrameRowsOut,
                                   front_end_params=PsFrontEndParams)
+# ... and of the tracking VO step (ps_ransac_match_lists / ps_assemble_tracked / ps_track_vo_pairs)
+ABI_STRUCTS_TRACK_VO = dict(point_sets=PsPointSets, tracked_carry=PsTrackedCarry, tracked_rows=PsTrackedRows,
+                            track_vo_params=PsTrackVoParams, track_vo_in=PsTrackVoIn, track_vo_out=PsTrackVoOut)
 
 _lib = None
 _by_path = {}
@@ -316,8 +323,18 @@ def load_path(path):
                                       C.POINTER(PsFrameRowsOut)]
     L.ps_front_end_frame.argtypes = [vp, vp, vp, i32, i32, i32, sz, sz, C.POINTER(PsFrontEndParams), vp, C.POINTER(PsFrameGeometry), vp,
                                      C.POINTER(PsFrameRowsOut), i32, C.POINTER(i32)]
+    L.ps_ransac_match_lists.argtypes = [vp, C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), vp, C.POINTER(PsPointSets),
+                                        C.POINTER(PsPointSets), vp, vp, vp, i32, i32, C.POINTER(PsPairResults)]
+    L.ps_assemble_tracked.argtypes = [vp, C.POINTER(PsFrameGeometry), C.POINTER(PsDepthSet), vp, vp, vp, vp, i32, i32, C.POINTER(PsTrackedCarry),
+                                      C.POINTER(PsTrackedRows)]
+    L.ps_track_vo_pairs.argtypes = [vp, vp, C.POINTER(PsKltParams), C.POINTER(PsTrackVoParams), C.POINTER(PsRansacParams),
+                                    C.POINTER(PsRansacConfig), C.POINTER(PsFrameGeometry), C.POINTER(PsDepthSet), C.POINTER(PsTrackVoIn), i32, i32,
+                                    C.POINTER(PsTrackVoOut)]
+    L.ps_track_vo_pair.argtypes = [vp, vp, vp, vp, i32, i32, i32, sz, sz, C.POINTER(PsKltParams), C.POINTER(PsTrackVoParams),
+                                   C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), C.POINTER(PsFrameGeometry), C.POINTER(PsTrackVoIn), i32,
+                                   C.POINTER(PsTrackVoOut), C.POINTER(i32)]
     for n in (list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT) + list(ABI_STRUCTS_DETECT)
-              + list(ABI_STRUCTS_ORB) + list(ABI_STRUCTS_ORB_DETECT) + list(ABI_STRUCTS_FRAME_ASSEMBLY)):
+              + list(ABI_STRUCTS_ORB) + list(ABI_STRUCTS_ORB_DETECT) + list(ABI_STRUCTS_FRAME_ASSEMBLY) + list(ABI_STRUCTS_TRACK_VO)):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -353,3 +370,7 @@ def struct_sizes_orb_detect():
 
 def struct_sizes_frame_assembly():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_FRAME_ASSEMBLY.items()}
+
+
+def struct_sizes_track_vo():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_TRACK_VO.items()}

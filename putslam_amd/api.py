@@ -13,7 +13,8 @@ from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, P
                    PsFrameSetF32, PsHostPairResults, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapBatch, PsMapBatchF32, PsPairResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config,
                    PsImageSet, PsKltParams, klt_params, PsDetectParams, detect_params, PsOrbParams, orb_params,
-                   PsOrbDetectParams, orb_detect_params, PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, front_end_params)
+                   PsOrbDetectParams, orb_detect_params, PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, front_end_params,
+                   PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoParams, PsTrackVoIn, PsTrackVoOut, track_vo_params)
 
 
 class PsError(RuntimeError):
@@ -744,6 +745,95 @@ class Context:
                                              depth.strides[0], C.byref(params), None if pat is None else _p(pat), C.byref(geometry),
                                              _p(a["desc"]), C.byref(out), cap, C.byref(n)))
         return {k: v[:n.value].copy() for k, v in a.items()}
+
+    # ---- the tracking VO step ----
+    def ransac_match_lists_device(self, params, cfg, K, prev: PsPointSets, cur: PsPointSets, pairs_ptr, matches_ptr, num_matches_ptr, P,
+                                  cap, out: "DeviceResults"):
+        """ps_ransac_match_lists on device pointers (asynchronous on the context's stream): device_batch.ransac_match_lists."""
+        K = None if K is None else np.ascontiguousarray(K, np.float32)
+        res = out.struct()
+        self._chk(self._L.ps_ransac_match_lists(self._h, C.byref(params), C.byref(cfg), _p(K), C.byref(prev), C.byref(cur), _v(pairs_ptr),
+                                                _v(matches_ptr), _v(num_matches_ptr), int(P), int(cap), C.byref(res)))
+
+    def assemble_tracked_device(self, geometry: PsFrameGeometry, depth: PsDepthSet, depth_frame_ptr, next_pts_ptr, kept_idx_ptr,
+                                num_kept_ptr, P, capacity, carry: PsTrackedCarry, out: PsTrackedRows):
+        """ps_assemble_tracked on device pointers (asynchronous on the context's stream): device_batch.assemble_tracked."""
+        self._chk(self._L.ps_assemble_tracked(self._h, C.byref(geometry), C.byref(depth), _v(depth_frame_ptr), _v(next_pts_ptr),
+                                              _v(kept_idx_ptr), _v(num_kept_ptr), int(P), int(capacity),
+                                              None if carry is None else C.byref(carry), C.byref(out)))
+
+    def track_vo_pairs_device(self, pyr, klt: PsKltParams, tp: PsTrackVoParams, params, cfg, geometry: PsFrameGeometry, depth: PsDepthSet,
+                              vin: PsTrackVoIn, P, capacity, out: PsTrackVoOut):
+        """ps_track_vo_pairs on device pointers (asynchronous on the context's stream): device_batch.track_vo_pairs."""
+        self._chk(self._L.ps_track_vo_pairs(self._h, pyr, C.byref(klt), C.byref(tp), C.byref(params), C.byref(cfg), C.byref(geometry),
+                                            C.byref(depth), C.byref(vin), int(P), int(capacity), C.byref(out)))
+
+    def track_vo_pair(self, prev_img, next_img, depth, geometry: PsFrameGeometry, rows, params, cfg, tp: PsTrackVoParams = None,
+                      klt: PsKltParams = None, next_pts=None):
+        """The tracking VO step of Matcher::trackKLT (matcher.cpp:147-211) for one pair on numpy arrays (ps_track_vo_pair), uploads
+        included, synchronous: images (rows, cols[, 3]) uint8, the current frame's depth (rows, cols) uint16, rows: a dict of the
+        previous frame's rows -- xy (n, 2), pts (n, 3) and any of angle, response, octave, det_dist (n,).  Returns a dict: next_pts /
+        status / err of all n points; matches (k,) DMATCH_DTYPE, kept_idx (k,), mask (k,); rows -- the frame's rows in the same
+        form, the previous rows of the next call --; pose (4, 4), stats."""
+        tp, klt = tp or track_vo_params(), klt or klt_params()
+        prev_img, cn = _host_image(prev_img)
+        next_img, cn2 = _host_image(next_img)
+        assert prev_img.shape == next_img.shape and cn == cn2
+        if next_img.strides[0] != prev_img.strides[0]:
+            prev_img, next_img = np.ascontiguousarray(prev_img), np.ascontiguousarray(next_img)
+        depth = np.asarray(depth)
+        assert depth.dtype == np.uint16 and depth.shape == prev_img.shape[:2]
+        if depth.strides[1] != 2 or depth.strides[0] < depth.shape[1] * 2:
+            depth = np.ascontiguousarray(depth)
+        xy = np.ascontiguousarray(rows["xy"], np.float32).reshape(-1, 2)
+        n, m = xy.shape[0], max(xy.shape[0], 1)
+        pts = np.ascontiguousarray(rows["pts"], np.float32).reshape(n, 3)
+        types = dict(angle=np.float32, response=np.float32, octave=np.int32, det_dist=np.float64)
+        carried = {k: np.ascontiguousarray(rows[k], t).reshape(n) for k, t in types.items() if k in rows}
+        o = dict(next_pts=np.zeros((m, 2), np.float32), status=np.zeros(m, np.uint8), err=np.zeros(m, np.float32), matches=np.zeros(m, DMATCH_DTYPE),
+                 kept_idx=np.zeros(m, np.int32), mask=np.zeros(m, np.uint8), pose=np.zeros(16, np.float32), stats=np.zeros(1, STATS_DTYPE),
+                 xy=np.zeros((m, 2), np.float32), xy_undist=np.zeros((m, 2), np.float32), pts=np.zeros((m, 3), np.float32))
+        o.update({k: np.zeros(m, t) for k, t in types.items() if k in carried})
+        if next_pts is not None:
+            o["next_pts"][:n] = np.asarray(next_pts, np.float32).reshape(n, 2)
+        ptr = lambda d, k: d[k].ctypes.data if k in d else None   # noqa: E731
+        vin = PsTrackVoIn(None, None, xy.ctypes.data, pts.ctypes.data, None,
+                          PsTrackedCarry(ptr(carried, "angle"), ptr(carried, "response"), ptr(carried, "octave"), ptr(carried, "det_dist")))
+        out = PsTrackVoOut(ptr(o, "next_pts"), ptr(o, "status"), ptr(o, "err"), ptr(o, "matches"), None, ptr(o, "kept_idx"),
+                           PsTrackedRows(ptr(o, "xy"), ptr(o, "xy_undist"), ptr(o, "pts"), None, ptr(o, "angle"), ptr(o, "response"),
+                                         ptr(o, "octave"), ptr(o, "det_dist")), ptr(o, "mask"), ptr(o, "pose"), ptr(o, "stats"))
+        k = C.c_int(0)
+        self._chk(self._L.ps_track_vo_pair(self._h, _p(prev_img), _p(next_img), _p(depth), prev_img.shape[0], prev_img.shape[1], cn,
+                                           prev_img.strides[0], depth.strides[0], C.byref(klt), C.byref(tp), C.byref(params), C.byref(cfg),
+                                           C.byref(geometry), C.byref(vin), n, C.byref(out), C.byref(k)))
+        k = k.value
+        new = {name: o[name][:k].copy() for name in ("xy", "xy_undist", "pts") + tuple(carried)}
+        return dict(next_pts=o["next_pts"][:n], status=o["status"][:n], err=o["err"][:n], matches=o["matches"][:k].copy(),
+                    kept_idx=o["kept_idx"][:k].copy(), mask=o["mask"][:k].copy(), rows=new, pose=o["pose"].reshape(4, 4).T.copy(),
+                    stats=o["stats"][0].copy())
+
+    def ransac_match_lists(self, params, cfg, K, prev, cur, matches, pairs=None):
+        """The estimator over P caller-supplied match lists (ps_ransac_match_lists) on numpy data, uploads and downloads included,
+        synchronous: prev / cur lists of (n, 3) float32 point sets, matches a list of P DMATCH_DTYPE arrays, pairs (P, 2) (previous
+        set, current set) or None for (p, p); pair p draws from cfg.seed + p.  Returns a dict: inlierMask (P, cap) uint8, pose
+        (P, 16), stats (P,) STATS_DTYPE.  (The data goes through device_batch, which allocates with torch.)"""
+        from . import device_batch as db
+        dev = "cuda:%d" % self._L.ps_context_device(self._h)
+        P = len(matches)
+        if P == 0:      # (ps_ransac_match_lists: P == 0 is PS_OK and writes nothing)
+            return dict(inlierMask=np.zeros((0, 1), np.uint8), pose=np.zeros((0, 16), np.float32), stats=np.zeros(0, STATS_DTYPE))
+        sets_p, sets_c = db.PointSets.from_host(prev, dev), db.PointSets.from_host(cur, dev)
+        cap = max([1] + [len(m) for m in matches])
+        block = np.zeros((max(P, 1), cap), DMATCH_DTYPE)
+        for p, m in enumerate(matches):
+            block[p, :len(m)] = np.asarray(m, DMATCH_DTYPE)
+        import torch
+        d_matches = torch.from_numpy(block.view(np.int32).reshape(max(P, 1), cap, 4)).to(dev)
+        d_num = torch.from_numpy(np.array([len(m) for m in matches] or [0], np.int32)).to(dev)
+        d_pairs = None if pairs is None else torch.from_numpy(np.ascontiguousarray(pairs, np.int32).reshape(P, 2)).to(dev)
+        out = db.ransac_match_lists(self, params, cfg, K, sets_p, sets_c, d_matches, d_num, d_pairs)
+        res = out.download()
+        return dict(inlierMask=res["inlierMask"], pose=res["pose"], stats=res["stats"])
 
     def points3Dto2D(self, xyz, K):
         xyz = np.ascontiguousarray(xyz, np.float32)

@@ -1469,6 +1469,126 @@ void FrameMatcherHIP::frontEnd(cv::Mat rgbImage, cv::Mat depthImage, double dept
     }
 }
 
+// Matcher::trackKLT, matcher.cpp:147-211
+bool FrameMatcherHIP::trackStep(cv::Mat prevRgbImage, cv::Mat rgbImage, cv::Mat depthImage, double depthImageScale,
+                                const std::vector<cv::Point2f> &prevFeaturesDistorted, const std::vector<Eigen::Vector3f> &prevFeatures3D,
+                                const std::vector<cv::KeyPoint> &prevKeyPoints, const std::vector<double> &prevDetDists,
+                                std::vector<cv::Point2f> &distorted, std::vector<cv::Point2f> &undistorted,
+                                std::vector<Eigen::Vector3f> &features3D, std::vector<cv::KeyPoint> &keyPoints, std::vector<double> &detDists,
+                                std::vector<cv::DMatch> &matches, std::vector<cv::DMatch> &inlierMatches,
+                                Eigen::Matrix4f &estimatedTransformation)
+{
+    const auto &cvp = matcherParameters.OpenCVParams;
+    const size_t n = prevFeaturesDistorted.size();
+    const bool initialFlow = cvp.useInitialFlow > 0 && distorted.size() == n; // (calcOpticalFlowPyrLK asserts the sizes agree)
+    std::vector<cv::Point2f> tracked = initialFlow ? distorted : std::vector<cv::Point2f>(n ? n : 1);
+    distorted.clear();
+    undistorted.clear();
+    features3D.clear();
+    keyPoints.clear();
+    detDists.clear();
+    matches.clear();
+    inlierMatches.clear();
+    estimatedTransformation = Eigen::Matrix4f::Identity();
+    if (cvp.removeTooCloseFeatures > 0) {
+        std::cerr << "putslam_hip: trackStep does not run removeTooCloseFeatures (the reference leaves the matches' trainIdx un-renumbered, "
+                     "matcher.cpp:960-963): set OpenCVParams.removeTooCloseFeatures to 0 and call removeTooCloseFeatures on the result" << std::endl;
+        return false;
+    }
+    const auto is8u = [](const cv::Mat &m) { return m.depth() == CV_8U && (m.channels() == 1 || m.channels() == 3); };
+    if (prevRgbImage.empty() || rgbImage.empty() || !is8u(prevRgbImage) || prevRgbImage.type() != rgbImage.type() ||
+        prevRgbImage.rows != rgbImage.rows || prevRgbImage.cols != rgbImage.cols || prevRgbImage.step != rgbImage.step || depthImage.empty() ||
+        depthImage.type() != CV_16U || depthImage.rows != rgbImage.rows || depthImage.cols != rgbImage.cols || prevFeatures3D.size() != n ||
+        prevKeyPoints.size() != n || prevDetDists.size() != n || (cvp.useInitialFlow > 0 && !initialFlow)) {
+        std::cerr << "putslam_hip: trackStep takes two CV_8UC1 / CV_8UC3 images of one size and step, a CV_16U depth image of that size, and "
+                     "one 3-D point, key point and detection distance per previous feature" << std::endl;
+        return false;
+    }
+    if (n == 0) return true; // matcher.cpp:147-148
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return false;
+    PsKltParams klt;
+    klt.eps = cvp.eps;
+    klt.minEigThreshold = cvp.trackingMinEigThreshold;
+    klt.winSize = cvp.winSize;
+    klt.maxLevels = cvp.maxLevels;
+    klt.maxCount = cvp.maxIter;
+    klt.flags = (cvp.useInitialFlow > 0 ? PS_KLT_USE_INITIAL_FLOW : 0) | (cvp.trackingErrorType > 0 ? PS_KLT_GET_MIN_EIGENVALS : 0);
+    PsTrackVoParams tp;
+    tp.trackingErrorThreshold = cvp.trackingErrorThreshold;
+    tp.minimalReprojDistanceNewTrackingFeatures = cvp.minimalReprojDistanceNewTrackingFeatures;
+    tp.removeTooCloseFeatures = 0;
+    tp.reserved = 0;
+    // RANSAC ransac(matcherParameters.RANSACParams with errorVersion = errorVersionVO, cameraMatrixMat), as Matcher::match builds it
+    RANSAC::parameters rp = matcherParameters.RANSACParams;
+    rp.errorVersion = rp.errorVersionVO; // matcher.cpp:190-191
+    rp.iterationCount = ransacIterations(0.20); // RANSAC.cpp:30
+    const PsRansacParams prm = toPs(rp);
+    int a = ransacIterations(0.20), b = ransacIterations(rp.minimalInlierRatioThreshold);
+    int H = a > b ? a : b;
+    H = H < 1 ? 1 : (H > PS_MAX_HYPOTHESES ? PS_MAX_HYPOTHESES : H);
+    PsRansacConfig cfg;
+    cfg.estimator = PS_EST_RANSAC;
+    cfg.numHypotheses = H;
+    cfg.seed = seeded_ ? seed_ + (uint64_t)frameCounter : (uint64_t)std::time(nullptr); // RANSAC.cpp:13
+    cfg.sampleIdx = nullptr;
+    PsFrameGeometry geo;
+    bool haveK;
+    cameraToK(matcherParameters.cameraMatrixMat, geo.K, haveK);
+    const cv::Mat &dc = matcherParameters.distortionCoeffsMat;
+    const int nd = dc.empty() ? 0 : dc.rows * dc.cols;
+    for (int i = 0; i < 5; ++i) geo.dist5[i] = i < nd ? (double)dc.at<float>(dc.rows == 1 ? 0 : i, dc.rows == 1 ? i : 0) : 0.0;
+    geo.depthImageScale = depthImageScale;
+    std::vector<cv::Point2f> xy(n), und(n);
+    std::vector<int32_t> keptIdx(n);
+    std::vector<uint8_t> mask(n);
+    matches.resize(n);
+    features3D.resize(n);
+    PsTrackVoIn in;
+    std::memset(&in, 0, sizeof in);
+    in.prevXY = reinterpret_cast<const float *>(prevFeaturesDistorted.data());
+    in.prevPts = reinterpret_cast<const float *>(prevFeatures3D.data());
+    PsTrackVoOut out;
+    std::memset(&out, 0, sizeof out);
+    out.nextPts = reinterpret_cast<float *>(tracked.data());
+    out.matches = reinterpret_cast<PsDMatch *>(matches.data());
+    out.keptIdx = keptIdx.data();
+    out.rows.xy = reinterpret_cast<float *>(xy.data());
+    out.rows.xyUndist = reinterpret_cast<float *>(und.data());
+    out.rows.pts = reinterpret_cast<float *>(features3D.data());
+    out.inlierMask = mask.data();
+    out.pose = estimatedTransformation.data();
+    PsRansacStats st;
+    out.stats = &st;
+    int k = 0;
+    status = ps_track_vo_pair(ctx, prevRgbImage.data, rgbImage.data, reinterpret_cast<const uint16_t *>(depthImage.data), rgbImage.rows,
+                              rgbImage.cols, rgbImage.channels(), (size_t)rgbImage.step, (size_t)depthImage.step, &klt, &tp, &prm, &cfg, &geo, &in,
+                              (int)n, &out, &k);
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        matches.clear();
+        features3D.clear();
+        estimatedTransformation = Eigen::Matrix4f::Identity();
+        return false;
+    }
+    matches.resize((size_t)k);
+    features3D.resize((size_t)k);
+    distorted.assign(xy.begin(), xy.begin() + k);
+    undistorted.assign(und.begin(), und.begin() + k);
+    keyPoints.reserve((size_t)k);
+    detDists.reserve((size_t)k);
+    for (int j = 0; j < k; ++j) { // matcherOpenCV.cpp:240-245, :267-290: the previous frame's key point with its pt moved
+        cv::KeyPoint kp = prevKeyPoints[(size_t)keptIdx[(size_t)j]];
+        kp.pt = xy[(size_t)j];
+        keyPoints.push_back(kp);
+        detDists.push_back(prevDetDists[(size_t)keptIdx[(size_t)j]]);
+        if (mask[(size_t)j]) inlierMatches.push_back(matches[(size_t)j]);
+    }
+    ++frameCounter;
+    return true;
+}
+
 // MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) with the matcher of matcherOpenCV.cpp:100-102, cv::BFMatcher(cv::NORM_L2,
 // true), on CV_32F descriptor Mats of 1 .. PS_MAX_L2_DIM columns (ps_match_l2_f32).
 std::vector<cv::DMatch> l2CrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors)

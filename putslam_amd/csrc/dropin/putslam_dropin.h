@@ -200,6 +200,7 @@ class FrameMatcher {
             float eps = 0.01f;
             double trackingErrorThreshold = 25.0, trackingMinEigThreshold = 0.0;
             int trackingErrorType = 0;
+            int removeTooCloseFeatures = 0; // putslammatcherOpenCVParameters.xml:77; trackStep below takes 0 only
             // the detector's block (matcher.h:40,43,51; putslammatcherOpenCVParameters.xml:64,67): detectFeatures below runs "ORB" and "FAST"
             std::string detector = "ORB";
             int gridRows = 1, gridCols = 1;
@@ -448,6 +449,23 @@ class FrameMatcherHIP : public FrameMatcher {
     // goes to std::cerr and every output comes back empty.
     void frontEnd(cv::Mat rgbImage, cv::Mat depthImage, double depthImageScale, cv::Mat &descriptors, std::vector<Eigen::Vector3f> &features3D,
                   std::vector<cv::KeyPoint> *keyPoints = nullptr, std::vector<cv::Point2f> *undistorted = nullptr);
+    // The first half of Matcher::trackKLT (matcher.cpp:147-211) as ONE call (ps_track_vo_pair): performTracking on (prevRgbImage,
+    // rgbImage) from prevFeaturesDistorted, removeImageDistortion of the tracked positions with cameraMatrixMat / distortionCoeffsMat,
+    // keypoints2Dto3D in depthImage with depthImageScale, keyPoints / detDists carried from the previous frame's by the kept index
+    // (a key point's pt is its tracked position), and RANSAC::estimateTransformation(prevFeatures3D, features3D, matches) with
+    // RANSACParams.errorVersionVO.  It reads the OpenCVParams tracking members performTracking reads.  The previous frame's four
+    // lists are left as they are; the five lists of this frame, `matches` (DMatch(i, j, 0)) and inlierMatches are replaced.  Under
+    // useInitialFlow `distorted` is the initial flow when it has one entry per previous feature.  Returns false -- one line on
+    // std::cerr, every output empty, the identity -- on an error and for OpenCVParams.removeTooCloseFeatures > 0: the reference
+    // erases the removed features from features3D and leaves the matches' trainIdx un-renumbered (matcher.cpp:960-963, recorded at
+    // removeTooCloseFeatures above), so its RANSAC reads stale indices; a host that wants the filter calls removeTooCloseFeatures
+    // on what this call returned.  No previous feature: true, the identity, nothing tracked (:147-148).
+    bool trackStep(cv::Mat prevRgbImage, cv::Mat rgbImage, cv::Mat depthImage, double depthImageScale,
+                   const std::vector<cv::Point2f> &prevFeaturesDistorted, const std::vector<Eigen::Vector3f> &prevFeatures3D,
+                   const std::vector<cv::KeyPoint> &prevKeyPoints, const std::vector<double> &prevDetDists,
+                   std::vector<cv::Point2f> &distorted, std::vector<cv::Point2f> &undistorted, std::vector<Eigen::Vector3f> &features3D,
+                   std::vector<cv::KeyPoint> &keyPoints, std::vector<double> &detDists, std::vector<cv::DMatch> &matches,
+                   std::vector<cv::DMatch> &inlierMatches, Eigen::Matrix4f &estimatedTransformation);
 };
 
 } // namespace putslam_hip

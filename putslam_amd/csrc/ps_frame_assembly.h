@@ -17,6 +17,23 @@ struct AssembleArgs {
     int rows, cols, firstFrame, cap;
 };
 
+// The undistorted position q of the distorted p and its 3-D point in the depth frame at `frame` (null: no depth image, depth 0 --
+// the keypoints2Dto3D result for no depth): ps_kernels.h's undistort_point, depth_rule_offset, depth_pixel and point_from_depth.
+PS_D void undistort_and_back_project(float2 p, const DistArgs &dist, double scale, const uint8_t *__restrict__ frame, size_t rowStride, int rows,
+                                     int cols, float2 &q, float &X, float &Y, float &Z)
+{
+    undistort_point(p.x, p.y, dist, q.x, q.y);
+    // the rule over the frame as the DENSE image the reference holds: u == cols in a row that is not the last is the next row's
+    // first pixel whatever the row stride -- a set's padding is alignment, not a parent image, and is never read
+    size_t off = 0;
+    unsigned dv = 0;
+    if (frame != nullptr && depth_rule_offset(q.x, q.y, rows, cols, (size_t)cols * 2, (size_t)rows * (size_t)cols * 2, off)) {
+        const unsigned pixel = (unsigned)(off >> 1), r = pixel / (unsigned)cols, c = pixel - r * (unsigned)cols;
+        dv = depth_pixel(frame + (size_t)r * rowStride + (size_t)c * 2);
+    }
+    point_from_depth(q.x, q.y, dv, dist.fx, dist.fy, dist.cx, dist.cy, scale, X, Y, Z);
+}
+
 // Output row j of frame f is input row idx[f][j], j < nidx[f]; a count outside 0 .. cap: -1 and nothing else; an index outside
 // 0 .. cap-1: a zero row
 __global__ __launch_bounds__(kBlock) void ps_gather_rows(const int32_t *__restrict__ idx, const int32_t *__restrict__ nidx, int cap,
@@ -58,16 +75,8 @@ __global__ __launch_bounds__(kBlock) void ps_assemble_rows(AssembleArgs a, const
     float X = 0.f, Y = 0.f, Z = 0.f, dist = 0.f;
     if (in) {
         p = xy[from];
-        undistort_point(p.x, p.y, a.dist, q.x, q.y);
-        // the rule over the frame as the DENSE image the reference holds: u == cols in a row that is not the last is the next row's
-        // first pixel whatever the row stride -- a set's padding is alignment, not a parent image, and is never read
-        size_t off = 0;
-        unsigned dv = 0;
-        if (depth_rule_offset(q.x, q.y, a.rows, a.cols, (size_t)a.cols * 2, (size_t)a.rows * (size_t)a.cols * 2, off)) {
-            const unsigned pixel = (unsigned)(off >> 1), r = pixel / (unsigned)a.cols, c = pixel - r * (unsigned)a.cols;
-            dv = depth_pixel(a.depth + (size_t)(a.firstFrame + f) * a.frameStride + (size_t)r * a.rowStride + (size_t)c * 2);
-        }
-        point_from_depth(q.x, q.y, dv, a.dist.fx, a.dist.fy, a.dist.cx, a.dist.cy, a.scale, X, Y, Z);
+        undistort_and_back_project(p, a.dist, a.scale, a.depth + (size_t)(a.firstFrame + f) * a.frameStride, a.rowStride, a.rows, a.cols, q,
+                                   X, Y, Z);
         // matcher.cpp:53-55: float products, float sums left to right, std::sqrt(float) -- ps_sqrt is the correctly rounded root
         // (__fsqrt_rn is not: without OCML's rounded operations HIP maps it to the native, one-ulp instruction)
         dist = ps_sqrt((X * X + Y * Y) + Z * Z);

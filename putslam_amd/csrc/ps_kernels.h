@@ -485,15 +485,18 @@ __global__ __launch_bounds__(BLOCK) void ps_crosscheck_prep(const float *__restr
     phase_stamp(stamps, 3); // bounds, split operands, counters cleared
 }
 
-// Depth filter + records for a caller-supplied match list (stand-alone RANSAC entry point).
-__global__ __launch_bounds__(kBlock) void ps_prep_from_matches(const float *__restrict__ prev,
-                                                               const float *__restrict__ cur,
-                                                               const PsDMatch *__restrict__ matches, int m, PrepArgs a,
-                                                               RecPtrs rec, int32_t *__restrict__ mvalid,
-                                                               float2 *__restrict__ cmaxOut)
+// Pair p's records from a caller-supplied list of m matches over the point blocks prev / cur, by one work-group of kBlock threads
+// in tiles of kBlock matches: the depth filter of RANSAC.cpp:65-74, the ordered compaction, write_records, then the pair's count,
+// bounds and cleared counters -- what ps_crosscheck_prep and ps_map_emit leave for their pairs.  CHECKED: the list comes from
+// device memory nobody has looked at: a match whose queryIdx lies outside 0 .. nprev-1 or whose trainIdx lies outside 0 .. ncur-1
+// is not followed and fails the filter, and `clean` receives the list with the trainIdx of every such match replaced by -1 (what
+// kernel 4 reads for pointInlierRatio: a train index it skips).
+template <bool CHECKED>
+PS_D void prep_match_list(const float *__restrict__ prev, int nprev, const float *__restrict__ cur, int ncur,
+                          const PsDMatch *__restrict__ matches, int m, const PrepArgs &a, const RecPtrs &rec, int p,
+                          int32_t *__restrict__ mvalid, float2 *__restrict__ cmaxOut, PsDMatch *__restrict__ clean, int *s_wsum,
+                          float *s_red)
 {
-    __shared__ int s_wsum[kBlock / 64];
-    __shared__ float s_red[kBlock / 64];
     float cm = 0.0f, um = 0.0f;
     int vbase = 0;
     const float fixedBound = a.mode != PS_ADAPTIVE_ERROR ? sq_bound_f32(a.thrE) : 0.0f;
@@ -503,16 +506,24 @@ __global__ __launch_bounds__(kBlock) void ps_prep_from_matches(const float *__re
         int q = 0, t = 0;
         bool ok = false;
         if (i < m) {
-            q = matches[i].queryIdx;
-            t = matches[i].trainIdx;
-            px = prev[3 * q]; py = prev[3 * q + 1]; pz = prev[3 * q + 2];
-            cx_ = cur[3 * t]; cy_ = cur[3 * t + 1]; cz_ = cur[3 * t + 2];
-            ok = depth_ok(px, py, pz) && depth_ok(cx_, cy_, cz_);
+            PsDMatch mt = matches[i];
+            q = mt.queryIdx;
+            t = mt.trainIdx;
+            const bool in = !CHECKED || (q >= 0 && q < nprev && t >= 0 && t < ncur);
+            if (CHECKED) {
+                if (!in) mt.trainIdx = -1;
+                clean[i] = mt;
+            }
+            if (in) {
+                px = prev[3 * q]; py = prev[3 * q + 1]; pz = prev[3 * q + 2];
+                cx_ = cur[3 * t]; cy_ = cur[3 * t + 1]; cz_ = cur[3 * t + 2];
+                ok = depth_ok(px, py, pz) && depth_ok(cx_, cy_, cz_);
+            }
         }
         int vtotal;
         int vpos = block_scan_flag(ok, vtotal, s_wsum);
         if (ok) {
-            um = fmaxf(um, write_records(a, rec, 0, vbase + vpos, i, q, t, px, py, pz, cx_, cy_, cz_, fixedBound));
+            um = fmaxf(um, write_records(a, rec, p, vbase + vpos, i, q, t, px, py, pz, cx_, cy_, cz_, fixedBound));
             cm = fmaxf(cm, fmaxf(fmaxf(fabsf(px), fabsf(py)), fmaxf(fabsf(pz), fmaxf(fabsf(cx_), fmaxf(fabsf(cy_), fabsf(cz_))))));
         }
         vbase += vtotal;
@@ -520,16 +531,62 @@ __global__ __launch_bounds__(kBlock) void ps_prep_from_matches(const float *__re
     float c = block_max(cm, s_red);
     float u = block_max(um, s_red);
     if (threadIdx.x == 0) {
-        mvalid[0] = vbase;
-        cmaxOut[0] = make_float2(c, u);
-        finish_pair_records(a, rec, 0, vbase);
+        mvalid[p] = vbase;
+        cmaxOut[p] = make_float2(c, u);
+        finish_pair_records(a, rec, p, vbase); // (block_max ends with a barrier: the records are visible)
     }
     if (a.zeroCounts)
-        for (int i = threadIdx.x; i < a.zeroH; i += kBlock) a.zeroCounts[i] = 0;
-    if (threadIdx.x == 0 && a.zeroSurvA) { // the staged scoring's survivor counters (one pair), as ps_crosscheck_prep does
-        a.zeroSurvA[0] = 0;
-        a.zeroSurvB[0] = 0;
+        for (int i = threadIdx.x; i < a.zeroH; i += kBlock) a.zeroCounts[(size_t)p * a.zeroStride + i] = 0;
+    if (threadIdx.x == 0 && a.zeroSurvA) { // the staged scoring's survivor counters, as ps_crosscheck_prep does
+        a.zeroSurvA[p] = 0;
+        a.zeroSurvB[p] = 0;
     }
+}
+
+// Depth filter + records for a caller-supplied match list (stand-alone RANSAC entry point; the host checked the indices).
+__global__ __launch_bounds__(kBlock) void ps_prep_from_matches(const float *__restrict__ prev,
+                                                               const float *__restrict__ cur,
+                                                               const PsDMatch *__restrict__ matches, int m, PrepArgs a,
+                                                               RecPtrs rec, int32_t *__restrict__ mvalid,
+                                                               float2 *__restrict__ cmaxOut)
+{
+    __shared__ int s_wsum[kBlock / 64];
+    __shared__ float s_red[kBlock / 64];
+    prep_match_list<false>(prev, 0, cur, 0, matches, m, a, rec, 0, mvalid, cmaxOut, nullptr, s_wsum, s_red);
+}
+
+// The point block of one set of a device-resident group of point sets (PsPointSets, include/putslam_hip.h)
+struct PointSetsArgs {
+    const float *pts;
+    const int32_t *counts;
+    int numSets, capacity;
+    int strideFloats; // floats between consecutive sets' blocks
+};
+
+// The batched form: one work-group per pair over device-resident lists (ps_ransac_match_lists).  Pair p matches set
+// pairs[2p] of `prev` with set pairs[2p + 1] of `cur` (pairs = null: set p of both).  numMatches[p] outside 0 .. cap, a set index
+// outside its group or a set count outside 0 .. capacity: the pair's list counts as empty -- numClean[p] = 0, what kernel 4 is
+// given as the pair's match count, so that it writes no mask byte.
+__global__ __launch_bounds__(kBlock) void ps_prep_match_lists(PointSetsArgs prev, PointSetsArgs cur, const int32_t *__restrict__ pairs,
+                                                              const PsDMatch *__restrict__ matches,
+                                                              const int32_t *__restrict__ numMatches, PrepArgs a, RecPtrs rec,
+                                                              int32_t *__restrict__ mvalid, float2 *__restrict__ cmaxOut,
+                                                              PsDMatch *__restrict__ clean, int32_t *__restrict__ numClean)
+{
+    __shared__ int s_wsum[kBlock / 64];
+    __shared__ float s_red[kBlock / 64];
+    const int p = blockIdx.x;
+    const int sq = pairs ? pairs[2 * p] : p, st = pairs ? pairs[2 * p + 1] : p;
+    const bool sets = sq >= 0 && sq < prev.numSets && st >= 0 && st < cur.numSets;
+    const int nq = sets ? prev.counts[sq] : -1, nt = sets ? cur.counts[st] : -1;
+    const int given = numMatches[p];
+    const bool ok = sets && nq >= 0 && nq <= prev.capacity && nt >= 0 && nt <= cur.capacity && given >= 0 && given <= a.cap;
+    const int m = ok ? given : 0;
+    if (threadIdx.x == 0) numClean[p] = m;
+    const size_t row = (size_t)p * (size_t)a.cap;
+    prep_match_list<true>(prev.pts + (size_t)(ok ? sq : 0) * (size_t)prev.strideFloats, nq,
+                          cur.pts + (size_t)(ok ? st : 0) * (size_t)cur.strideFloats, nt, matches + row, m, a, rec, p, mvalid, cmaxOut,
+                          clean + row, s_wsum, s_red);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@ from . import api
 from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
                    make_config, PsImageSet, klt_params, detect_params, orb_params, orb_detect_params, PsDepthSet, PsFrameRowsOut,
-                   front_end_params)
+                   front_end_params, PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoIn, PsTrackVoOut, track_vo_params)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -684,6 +684,201 @@ def run_image_sequence(ctx, fe: FrontEnd, images, depth, geometry, params, cfg, 
     if batch.P:
         run_pairs(ctx, params, cfg, np.array(list(geometry.K), np.float32), frames, batch, use_torch_stream)
     return frames, batch
+
+
+class PointSets:
+    """S sets of 3-D points in HBM (PsPointSets): pts a float32 device tensor (S, cap, 3) whose sets may lie any stride apart (a
+    view of a pitched block; a set itself is dense), counts (S,) int32."""
+
+    def __init__(self, pts, counts):
+        assert pts.dtype == torch.float32 and pts.dim() == 3 and pts.shape[2] == 3 and pts.stride()[1:] == (3, 1)
+        _expect(counts, torch.int32, (pts.shape[0],))
+        self.pts, self.counts, self.device = pts, counts, pts.device
+        self.num_sets, self.capacity = int(pts.shape[0]), int(pts.shape[1])
+
+    @classmethod
+    def from_host(cls, sets, device, capacity=None, pitch_floats=None):
+        """From a list of (n, 3) arrays: capacity rows a set (default the longest, at least 1), pitch_floats floats between sets
+        (default dense); rows beyond a set's count and the pitch's padding are NaN."""
+        cap = max([1] + [len(s) for s in sets]) if capacity is None else int(capacity)
+        pitch = cap * 3 if pitch_floats is None else int(pitch_floats)
+        block = np.full((max(len(sets), 1), pitch), np.nan, np.float32)
+        for i, s in enumerate(sets):
+            block[i, :len(s) * 3] = np.asarray(s, np.float32).reshape(-1)
+        d = torch.from_numpy(block).to(torch.device(device))
+        pts = d[:, :cap * 3].unflatten(1, (cap, 3))
+        counts = torch.from_numpy(np.array([len(s) for s in sets] or [0], np.int32)).to(torch.device(device))
+        return cls(pts, counts)
+
+    def view(self):
+        dense = self.num_sets == 1 or self.pts.stride(0) == self.capacity * 3
+        return PsPointSets(self.pts.data_ptr(), self.counts.data_ptr(), self.num_sets, self.capacity, 0 if dense else self.pts.stride(0) * 4)
+
+
+def ransac_match_lists(ctx, params, cfg, K, prev: PointSets, cur: PointSets, matches, num_matches, pairs=None, out=None,
+                       use_torch_stream=True):
+    """RANSAC / USAC over P caller-supplied device-resident match lists (ps_ransac_match_lists): matches (P, cap, 4) int32 words
+    of PsDMatch -- what select_tracked returns --, num_matches (P,) int32, pairs (P, 2) int32 (previous set, current set) or None
+    for (p, p).  Pair p draws from cfg.seed + p.  Returns a PairResultsDevice (mask, pose, stats; its matches / num_matches stay
+    zero), written asynchronously, ordered like run_pairs."""
+    P, cap = matches.shape[0], matches.shape[1]
+    _expect(matches, torch.int32, (P, cap, 4))
+    _expect(num_matches, torch.int32, (P,))
+    if pairs is not None:
+        _expect(pairs, torch.int32, (P, 2))
+    out = out or PairResultsDevice(P, cap, matches.device)
+    args = (params, cfg, K, prev.view(), cur.view(), None if pairs is None else pairs.data_ptr(), matches.data_ptr(), num_matches.data_ptr(),
+            P, cap, out.view())
+    _on_torch_stream(ctx, matches.device, lambda: ctx.ransac_match_lists_device(*args), use_torch_stream)
+    return out
+
+
+_TRACKED_ARRAYS = (("xy", torch.float32, (2,)), ("xy_undist", torch.float32, (2,)), ("pts", torch.float32, (3,)),
+                   ("angle", torch.float32, ()), ("response", torch.float32, ()), ("octave", torch.int32, ()),
+                   ("det_dist", torch.float64, ()))
+_CARRIED = ("angle", "response", "octave", "det_dist")
+
+
+class TrackedRows:
+    """The rows a tracked frame leaves for P sequences (PsTrackedRows) -- and the previous rows the next frame's tracking starts
+    from: xy, xy_undist (P, cap, 2), pts (P, cap, 3) float32, counts (P,) int32, and the carried columns named in `carried`
+    (default all): angle, response (P, cap) float32, octave (P, cap) int32, det_dist (P, cap) float64; the others are None.
+    track_vo_pairs takes one and returns one."""
+
+    def __init__(self, P, cap, device, carried=_CARRIED):
+        self.device, self.P, self.cap = torch.device(device), int(P), int(cap)
+        for n, dt, tail in _TRACKED_ARRAYS:
+            setattr(self, n, _zeros(self.device, (self.P, self.cap) + tail, dt) if n not in _CARRIED or n in carried else None)
+        self.counts = _zeros(self.device, (self.P,), torch.int32)
+
+    @property
+    def carried(self):
+        return tuple(n for n in _CARRIED if getattr(self, n) is not None)
+
+    @classmethod
+    def from_host(cls, device, xy, pts, counts, **columns):
+        """Previous rows from numpy: xy (P, cap, 2), pts (P, cap, 3), counts (P,), and the carried columns by name."""
+        xy = np.ascontiguousarray(xy, np.float32)
+        r = cls(xy.shape[0], xy.shape[1], device, tuple(columns))
+        r.xy.copy_(torch.from_numpy(xy))
+        r.pts.copy_(torch.from_numpy(np.ascontiguousarray(pts, np.float32)))
+        r.counts.copy_(torch.from_numpy(np.ascontiguousarray(counts, np.int32)))
+        for n, a in columns.items():
+            getattr(r, n).copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        return r
+
+    def carry_struct(self):
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        return PsTrackedCarry(ptr(self.angle), ptr(self.response), ptr(self.octave), ptr(self.det_dist))
+
+    def rows_struct(self):
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        return PsTrackedRows(ptr(self.xy), ptr(self.xy_undist), ptr(self.pts), ptr(self.counts), ptr(self.angle), ptr(self.response),
+                             ptr(self.octave), ptr(self.det_dist))
+
+    def download(self):
+        names = ["counts"] + [n for n, _, _ in _TRACKED_ARRAYS if getattr(self, n) is not None]
+        return {n: getattr(self, n).cpu().numpy() for n in names}
+
+
+def assemble_tracked(ctx, geometry, depth, depth_frame, next_pts, kept_idx, num_kept, prev: TrackedRows = None, out: TrackedRows = None,
+                     use_torch_stream=True):
+    """The rows of the tracked points (ps_assemble_tracked): geometry _abi.frame_geometry(...); depth a uint16 device tensor (D, rows,
+    cols), pair p reads depth frame depth_frame[p] ((P,) int32); next_pts (P, cap, 2) float32, kept_idx (P, cap) / num_kept (P,) int32
+    -- what track_klt_pairs and select_tracked returned; prev: the previous rows whose carried columns go along by index (None:
+    nothing is carried).  Returns a TrackedRows, written asynchronously."""
+    P, cap = next_pts.shape[0], next_pts.shape[1]
+    dev = next_pts.device
+    _expect(next_pts, torch.float32, (P, cap, 2))
+    _expect(kept_idx, torch.int32, (P, cap))
+    _expect(num_kept, torch.int32, (P,))
+    _expect(depth_frame, torch.int32, (P,))
+    out = out or TrackedRows(P, cap, dev, prev.carried if prev is not None else ())
+    ds = DepthSet(depth, depth.shape[1], depth.shape[2])
+    carry = None if prev is None else prev.carry_struct()
+    rows = out.rows_struct()
+    _on_torch_stream(ctx, dev, lambda: ctx.assemble_tracked_device(geometry, ds, depth_frame.data_ptr(), next_pts.data_ptr(),
+                                                                   kept_idx.data_ptr(), num_kept.data_ptr(), P, cap, carry, rows),
+                     use_torch_stream)
+    return out
+
+
+class TrackVoDevice(PairResultsDevice):
+    """Everything ps_track_vo_pairs writes for P pairs of `cap` rows: the tracker's next_pts (P, cap, 2) float32, status (P, cap)
+    uint8, err (P, cap) float32; the selection's matches / num_matches (PairResultsDevice's) and kept_idx (P, cap) int32; the
+    frame's rows (a TrackedRows); mask, pose, stats."""
+
+    def __init__(self, P, cap, device, carried=_CARRIED):
+        dev = torch.device(device)
+        self.next_pts = _zeros(dev, (P, cap, 2), torch.float32)
+        self.status = _zeros(dev, (P, cap), torch.uint8)
+        self.err = _zeros(dev, (P, cap), torch.float32)
+        self.kept_idx = _zeros(dev, (P, cap), torch.int32)
+        self.rows = TrackedRows(P, cap, dev, carried)
+        super().__init__(P, cap, dev)
+
+    def out_struct(self):
+        return PsTrackVoOut(self.next_pts.data_ptr(), self.status.data_ptr(), self.err.data_ptr(), self.matches.data_ptr(),
+                            self.num_matches.data_ptr(), self.kept_idx.data_ptr(), self.rows.rows_struct(), self.mask.data_ptr(),
+                            self.pose.data_ptr(), self.stats.data_ptr())
+
+    def download(self):
+        res = super().download()
+        res.update(next_pts=self.next_pts.cpu().numpy(), status=self.status.cpu().numpy(), err=self.err.cpu().numpy(),
+                   kept_idx=self.kept_idx.cpu().numpy(), rows=self.rows.download())
+        return res
+
+
+def track_vo_pairs(ctx, pyr: KltPyramids, depth, geometry, pairs, rows: TrackedRows, params, cfg, tp=None, klt=None, depth_frame=None,
+                   out: TrackVoDevice = None, use_torch_stream=True):
+    """The tracking VO step for P pairs of slots of `pyr` with no host step (ps_track_vo_pairs): track the previous rows' xy, select,
+    assemble the tracked rows in the pair's depth frame (depth_frame (P,) int32; None: the pair's current slot) and run the estimator
+    on (rows.pts, the new pts, the selection's matches).  pairs (P, 2) int32; rows: the previous frame's TrackedRows; params / cfg as
+    for run_pairs (params.errorVersion is used as given); tp _abi.track_vo_params(...), klt _abi.klt_params(...).  Returns a
+    TrackVoDevice, written asynchronously; its .rows are the `rows` of the next frame's call."""
+    P, cap = rows.P, rows.cap
+    _expect(pairs, torch.int32, (P, 2))
+    if depth_frame is not None:
+        _expect(depth_frame, torch.int32, (P,))
+    tp = tp or track_vo_params()
+    klt = klt or klt_params(pyr.win_size, pyr.max_levels)
+    out = out or TrackVoDevice(P, cap, rows.device, rows.carried)
+    ds = DepthSet(depth, depth.shape[1], depth.shape[2])
+    vin = PsTrackVoIn(pairs.data_ptr(), None if depth_frame is None else depth_frame.data_ptr(), rows.xy.data_ptr(), rows.pts.data_ptr(),
+                      rows.counts.data_ptr(), rows.carry_struct())
+    o = out.out_struct()
+    _on_torch_stream(ctx, rows.device, lambda: ctx.track_vo_pairs_device(pyr.handle, klt, tp, params, cfg, geometry, ds, vin, P, cap, o),
+                     use_torch_stream)
+    return out
+
+
+def run_tracked_sequences(ctx, pyr: KltPyramids, depth, rows0: TrackedRows, frames, geometry, params, cfg, tp=None, klt=None,
+                          minimal_tracked_features=150, use_torch_stream=True):
+    """S tracked sequences in lockstep with no host step: frames (S, K + 1) slots of `pyr` (and depth frames of `depth`), pair s of
+    step k = (frames[s][k], frames[s][k + 1]); rows0: the rows of every sequence's first frame.  Step k's rows are handed to step
+    k + 1 where they lie; every step's blocks are allocated first, then the K calls are queued, and the counts are read back once at
+    the end.  Returns (steps: K TrackVoDevice, refill: (S,) int64 -- the first step whose rows count fewer than
+    minimal_tracked_features points (OpenCVParams.minimalTrackedFeatures: where a host's refill is due), K where none does).  The
+    call does not refill: the steps behind a due refill continue from the thinned rows."""
+    frames = np.ascontiguousarray(frames, np.int32)
+    S, K = frames.shape[0], frames.shape[1] - 1
+    assert S == rows0.P
+    dev = rows0.device
+    pairs = [torch.from_numpy(np.ascontiguousarray(frames[:, k:k + 2])).to(dev) for k in range(K)]
+    steps = [TrackVoDevice(S, rows0.cap, dev, rows0.carried) for _ in range(K)]
+    rows = rows0
+    for k in range(K):
+        track_vo_pairs(ctx, pyr, depth, geometry, pairs[k], rows, params, cfg, tp, klt, None, steps[k], use_torch_stream)
+        rows = steps[k].rows
+    refill = np.full(S, K, np.int64)
+    if K:
+        if not use_torch_stream:
+            ctx.synchronize()
+        counts = torch.stack([s.rows.counts for s in steps]).cpu().numpy()   # (K, S): the one read-back
+        for s in range(S):
+            due = np.nonzero(counts[:, s] < int(minimal_tracked_features))[0]
+            refill[s] = due[0] if due.size else K
+    return steps, refill
 
 
 class MapBatchDevice(PairResultsDevice):
