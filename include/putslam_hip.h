@@ -1673,6 +1673,104 @@ int ps_track_vo_pair(PsContext *ctx, const uint8_t *prevImg, const uint8_t *next
                      const PsRansacConfig *cfg, const PsFrameGeometry *geometry, const PsTrackVoIn *in, int n, const PsTrackVoOut *out,
                      int *numKept);
 
+/* ---- Closing the tracking VO step: Matcher::trackKLT, src/Matcher/matcher.cpp:213-381 -- the refill when fewer than
+ * minimalTrackedFeatures rows survive (:213-279), the predicted pyramid level of every row (:281-301), the stable reordering by
+ * that level (:302-331), describeFeatures at the predicted level (:338) and the removal of the rows the descriptor extractor
+ * dropped (:343-381) -- for P pairs with no host step.  DESIGN.md section 8.15. */
+typedef struct PsTrackCandidates {  /* the sandbox of :218-246 for numFrames frames, DEVICE, numFrames x capacity rows each */
+    const float *xy, *xyUndist;  /* x 2 */
+    const float *pts;            /* x 3 */
+    const float *angle, *response;
+    const int32_t *octave;
+    const double *detDist;
+    const int32_t *counts;       /* numFrames */
+    int32_t numFrames, capacity; /* capacity 1 .. PS_EXCL_MAX_CAND */
+} PsTrackCandidates;
+typedef struct PsTrackCloseParams {
+    double minimalReprojDistanceNewTrackingFeatures; /* OpenCVParams.minimalReprojDistanceNewTrackingFeatures */
+    int32_t minimalTrackedFeatures;                  /* OpenCVParams.minimalTrackedFeatures */
+    int32_t removeTooCloseFeatures;                  /* must be 0, as for ps_track_vo_pairs (:274-277 is the same case) */
+} PsTrackCloseParams;
+typedef struct PsTrackCloseOut {    /* DEVICE, P x outCapacity rows each unless noted */
+    uint8_t *desc;               /* x 32 bytes: with rows.pts and rows.counts a dense PsFrameSet of maxKpts = outCapacity */
+    PsTrackedRows rows;          /* every column required; octave is the DETECTION octave (keyPoints, not descKeyPoints) */
+    int32_t *srcIdx;             /* the tracked row the output row was, or capacity + i for candidate i */
+    int32_t *refill;             /* P: 0 = not due, 1 = the candidates were merged, 2 = due but no candidates were given */
+} PsTrackCloseOut;
+typedef struct PsTrackClose PsTrackClose; /* every intermediate array of ps_track_close_pairs: merged rows, levels, keptIdx */
+size_t ps_abi_sizeof_track_candidates(void);
+size_t ps_abi_sizeof_track_close_params(void);
+size_t ps_abi_sizeof_track_close_out(void);
+
+/* The sandbox for every frame of a device-resident set, on a PsFrontEnd's detector and arrays: ps_orb_detect_frames,
+ * ps_dbscan_thin_device (minPts 2, featuresFromCluster 1) and ps_assemble_frames on DBScan's keptIdx with every side column --
+ * out->xy, xyUndist, pts, angle, response, octave, detDist and nkpts are all required (srcIdx optional, angleIn / responseIn /
+ * octaveIn ignored); nothing is described.  With counts = out->nkpts these are a PsTrackCandidates.  images, depth, geometry and
+ * capacity as for ps_front_end_frames, errors as there; outputs untouched.  Only the ORB detector has a handle of this layout: a
+ * FAST sandbox is not offered.  Asynchronous on the context's stream. */
+int ps_track_candidates(PsContext *ctx, PsFrontEnd *fe, const PsImageSet *images, const PsDepthSet *depth, const PsFrameGeometry *geometry,
+                        int capacity, const PsFrameRowsOut *out);
+
+/* Room for calls of up to maxPairs pairs x maxRows rows (maxPairs 1 .. 65535, maxRows 1 .. PS_MAX_KPTS), allocated here so that a
+ * call neither allocates nor waits.  Synchronous.  destroy waits for the device; NULL is harmless. */
+int ps_track_close_create(PsContext *ctx, int maxPairs, int maxRows, PsTrackClose **out);
+void ps_track_close_destroy(PsTrackClose *tc);
+
+/* matcher.cpp:213-381 for P pairs.  tracked: the rows a ps_track_vo_pairs call left, P x capacity, EVERY column (xy, xyUndist,
+ * pts, counts, angle, response, octave, detDist) required -- the level rule needs octave and detDist, the merge xyUndist.  cand:
+ * candidate rows (ps_track_candidates') or NULL; candFrame[p] names the frame of `cand` that is pair p's sandbox, a value outside
+ * 0 .. cand->numFrames-1 (-1) or cand == NULL (candFrame may then be NULL too) means none.  pyr: ORB pyramids the caller has
+ * built (ps_orb_pyramids_build_device); pair p is described in slot slots[p], and pairs that look at one image name one slot --
+ * one build serves all pairs.  Four launches on the context's stream:
+ *  1. per pair, n = tracked->counts[p]: the refill is DUE iff n < tp->minimalTrackedFeatures, evaluated on the device.  A due pair
+ *     with candidates runs mergeTrackedFeatures (:97-130): candidate i, in ascending index, is appended behind the tracked rows iff
+ *     no tracked row and no PREVIOUSLY APPENDED candidate is near it -- (double)du * du + (double)dv * dv <
+ *     ps_sqrt_bound_f64(minimalReprojDistanceNewTrackingFeatures) on the float differences of the undistorted positions (the
+ *     predicate of ps_exclusion_rule_merge_tracked; false with a NaN).  Candidates of a pair that is not due are ignored.  Then
+ *     every merged row's predicted level: curDist = the float root of ((x * x + y * y) + z * z) in floats (:287-290 as compiled:
+ *     ps_assemble_frames' detDist arithmetic), level = THE LEVEL RULE above on (octave, detDist, curDist) -- scaleFactor 1.2,
+ *     nLevels 8 (matcher.h:26-28); a quotient that is not finite (curDist 0) gives level 0; an octave outside
+ *     PS_LEVEL_OCTAVE_MIN .. MAX gives level -1, and the description then drops the row (an extension: the reference has no such
+ *     key point).
+ *  2. + 3. ps_describe_features_device's two launches on the merged xy, angle and the LEVEL as octave: its stable grouping by
+ *     octave is :302-331, its border rule (31 <= x < cols - 31, 31 <= y < rows - 31) the "unlucky case" of :343-381 -- the
+ *     position-matching walk of :359-375 selects exactly its keptIdx, the border test depending on the position alone.  A level
+ *     the pyramid set lacks drops the row.  out->desc receives the rows.
+ *  4. every column gathered by keptIdx into out->rows, out->srcIdx, out->rows.counts[p].
+ * out->refill[p]: 0 not due, 1 merged, 2 due with no candidates -- the rows are then closed without the refill, a departure the
+ * flag reports.  A tracked count outside 0 .. capacity, or (on a due pair with candidates) a candidate count outside 0 ..
+ * cand->capacity, gives out->rows.counts[p] = -1 and nothing else is written for the pair, refill[p] included.  Nothing is written beyond a pair's
+ * count.  outCapacity >= capacity + cand->capacity (0 without cand), at most the handle's maxRows; P at most its maxPairs.
+ * The closed rows, unchanged, are prevXY / prevPts / prevCounts / prev of the next ps_track_vo_pairs (capacity = outCapacity).
+ * tp->removeTooCloseFeatures != 0 -> PS_ERR_UNSUPPORTED (ps_track_vo_pairs' reason).  NULL where an argument or array is needed,
+ * a tracked or output column absent, P < 0 or above maxPairs, capacity < 1, outCapacity outside the range above, a cand with
+ * numFrames < 1 or a NULL column -> PS_ERR_BAD_ARG; outCapacity above PS_MAX_KPTS or cand->capacity above PS_EXCL_MAX_CAND ->
+ * PS_ERR_UNSUPPORTED.  Everything that can refuse the call is found before the first launch: outputs untouched.  P == 0 is PS_OK.
+ * Outputs must not overlap inputs.  Asynchronous; the call neither allocates nor waits (the level rule's table is uploaded at a
+ * context's first use of it, as for ps_frame_levels_device). */
+int ps_track_close_pairs(PsContext *ctx, PsTrackClose *tc, const PsOrbPyramids *pyr, const int32_t *slots, const PsTrackCloseParams *tp,
+                         const PsTrackedRows *tracked, const PsTrackCandidates *cand, const int32_t *candFrame, int P, int capacity,
+                         int outCapacity, const PsTrackCloseOut *out);
+
+/* The same for one pair: HOST pointers, uploads and downloads included, synchronous.  img rows x cols x channels bytes with
+ * rowStride bytes between rows, depth (the same frame's) rows x cols uint16 with depthStep bytes between rows (0 = dense either; a
+ * region keeps its parent's).  params: the detector of the sandbox and the descriptor's pyramid (PsFrontEndParams; pattern1024 as
+ * for ps_front_end_create); tracked: HOST arrays of n rows, every column (counts is ignored).  The pyramid is built here; the
+ * sandbox (ps_track_candidates) runs only when the refill is due, n < tp->minimalTrackedFeatures.  desc cap x 32 bytes, out: HOST
+ * arrays of cap rows (NULL = not wanted; counts, if given, receives the rows), srcIdx cap int32 -- a candidate's is max(n, 1) + i --,
+ * *nout the rows, *refill the flag.  Returns PS_ERR_BAD_ARG with *nout = required capacity if cap is too small (nothing else is
+ * written but *refill); n above PS_MAX_KPTS -> PS_ERR_UNSUPPORTED; other errors as above and as ps_front_end_create's. */
+int ps_track_close_pair(PsContext *ctx, const uint8_t *img, const uint16_t *depth, int rows, int cols, int channels, size_t rowStride,
+                        size_t depthStep, const PsFrontEndParams *params, const int8_t *pattern1024, const PsFrameGeometry *geometry,
+                        const PsTrackCloseParams *tp, const PsTrackedRows *tracked, int n, uint8_t *desc, const PsTrackedRows *out,
+                        int32_t *srcIdx, int cap, int *nout, int *refill);
+/* Diagnostic (no reference counterpart; profiles/scripts/track_close_times.py times the new launches alone with it):
+ * ps_track_close_pairs with only the launches of the mask queued -- 1 the merge with the levels, 2 the placement, 4 the
+ * descriptor rows, 8 the gather.  A launch reads what the launches before it left: call with 15 first. */
+int ps_debug_track_close_passes(PsContext *ctx, PsTrackClose *tc, const PsOrbPyramids *pyr, const int32_t *slots, const PsTrackCloseParams *tp,
+                                const PsTrackedRows *tracked, const PsTrackCandidates *cand, const int32_t *candFrame, int P, int capacity,
+                                int outCapacity, const PsTrackCloseOut *out, int passes);
+
 #ifdef __cplusplus
 }
 #endif

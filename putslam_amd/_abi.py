@@ -292,6 +292,27 @@ def track_vo_params(tracking_error_threshold=25.0, min_reproj_distance=3.0, remo
     return PsTrackVoParams(float(tracking_error_threshold), float(min_reproj_distance), int(remove_too_close_features), 0)
 
 
+# Closing the tracking VO step (include/putslam_hip.h)
+class PsTrackCandidates(C.Structure):
+    _fields_ = [("xy", C.c_void_p), ("xyUndist", C.c_void_p), ("pts", C.c_void_p), ("angle", C.c_void_p), ("response", C.c_void_p),
+                ("octave", C.c_void_p), ("detDist", C.c_void_p), ("counts", C.c_void_p), ("numFrames", C.c_int32), ("capacity", C.c_int32)]
+
+
+class PsTrackCloseParams(C.Structure):
+    _fields_ = [("minimalReprojDistanceNewTrackingFeatures", C.c_double), ("minimalTrackedFeatures", C.c_int32),
+                ("removeTooCloseFeatures", C.c_int32)]
+
+
+class PsTrackCloseOut(C.Structure):
+    _fields_ = [("desc", C.c_void_p), ("rows", PsTrackedRows), ("srcIdx", C.c_void_p), ("refill", C.c_void_p)]
+
+
+def track_close_params(minimal_tracked_features=150, min_reproj_distance=3.0, remove_too_close_features=0):
+    """PsTrackCloseParams; the defaults are the shipped OpenCVParams (minimalTrackedFeatures 150,
+    minimalReprojDistanceNewTrackingFeatures 3, removeTooCloseFeatures 0 -- the only value ps_track_close_pairs takes)."""
+    return PsTrackCloseParams(float(min_reproj_distance), int(minimal_tracked_features), int(remove_too_close_features))
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

@@ -10,7 +10,7 @@ from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostP
                    PsMapBatchF32, PsMapStore, PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPairResults, PsPoseSetOut,
                    PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams, PsOrbParams, PsOrbDetectParams,
                    PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoParams,
-                   PsTrackVoIn, PsTrackVoOut)
+                   PsTrackVoIn, PsTrackVoOut, PsTrackCandidates, PsTrackCloseParams, PsTrackCloseOut)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -64,6 +64,9 @@ EXPORTED = [
     "ps_ransac_match_lists", "ps_assemble_tracked", "ps_track_vo_pairs", "ps_track_vo_pair",
     "ps_abi_sizeof_point_sets", "ps_abi_sizeof_tracked_carry", "ps_abi_sizeof_tracked_rows", "ps_abi_sizeof_track_vo_params",
     "ps_abi_sizeof_track_vo_in", "ps_abi_sizeof_track_vo_out",
+    "ps_track_candidates", "ps_track_close_create", "ps_track_close_destroy", "ps_track_close_pairs",
+    "ps_track_close_pair", "ps_debug_track_close_passes",
+    "ps_abi_sizeof_track_candidates", "ps_abi_sizeof_track_close_params", "ps_abi_sizeof_track_close_out",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -88,6 +91,8 @@ ABI_STRUCTS_FRAME_ASSEMBLY = dict(depth_set=PsDepthSet, frame_geometry=PsFrameGe
 # ... and of the tracking VO step (ps_ransac_match_lists / ps_assemble_tracked / ps_track_vo_pairs)
 ABI_STRUCTS_TRACK_VO = dict(point_sets=PsPointSets, tracked_carry=PsTrackedCarry, tracked_rows=PsTrackedRows,
                             track_vo_params=PsTrackVoParams, track_vo_in=PsTrackVoIn, track_vo_out=PsTrackVoOut)
+# ... and of its second half (ps_track_candidates / ps_track_close_pairs)
+ABI_STRUCTS_TRACK_CLOSE = dict(track_candidates=PsTrackCandidates, track_close_params=PsTrackCloseParams, track_close_out=PsTrackCloseOut)
 
 _lib = None
 _by_path = {}
@@ -333,8 +338,20 @@ def load_path(path):
     L.ps_track_vo_pair.argtypes = [vp, vp, vp, vp, i32, i32, i32, sz, sz, C.POINTER(PsKltParams), C.POINTER(PsTrackVoParams),
                                    C.POINTER(PsRansacParams), C.POINTER(PsRansacConfig), C.POINTER(PsFrameGeometry), C.POINTER(PsTrackVoIn), i32,
                                    C.POINTER(PsTrackVoOut), C.POINTER(i32)]
+    L.ps_track_candidates.argtypes = [vp, vp, C.POINTER(PsImageSet), C.POINTER(PsDepthSet), C.POINTER(PsFrameGeometry), i32,
+                                      C.POINTER(PsFrameRowsOut)]
+    L.ps_track_close_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
+    L.ps_track_close_destroy.argtypes = [vp]
+    L.ps_track_close_destroy.restype = None
+    L.ps_track_close_pairs.argtypes = [vp, vp, vp, vp, C.POINTER(PsTrackCloseParams), C.POINTER(PsTrackedRows), C.POINTER(PsTrackCandidates),
+                                       vp, i32, i32, i32, C.POINTER(PsTrackCloseOut)]
+    L.ps_debug_track_close_passes.argtypes = L.ps_track_close_pairs.argtypes + [i32]
+    L.ps_track_close_pair.argtypes = [vp, vp, vp, i32, i32, i32, sz, sz, C.POINTER(PsFrontEndParams), vp, C.POINTER(PsFrameGeometry),
+                                      C.POINTER(PsTrackCloseParams), C.POINTER(PsTrackedRows), i32, vp, C.POINTER(PsTrackedRows), vp, i32,
+                                      C.POINTER(i32), C.POINTER(i32)]
     for n in (list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT) + list(ABI_STRUCTS_DETECT)
-              + list(ABI_STRUCTS_ORB) + list(ABI_STRUCTS_ORB_DETECT) + list(ABI_STRUCTS_FRAME_ASSEMBLY) + list(ABI_STRUCTS_TRACK_VO)):
+              + list(ABI_STRUCTS_ORB) + list(ABI_STRUCTS_ORB_DETECT) + list(ABI_STRUCTS_FRAME_ASSEMBLY) + list(ABI_STRUCTS_TRACK_VO)
+              + list(ABI_STRUCTS_TRACK_CLOSE)):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -374,3 +391,7 @@ def struct_sizes_frame_assembly():
 
 def struct_sizes_track_vo():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_TRACK_VO.items()}
+
+
+def struct_sizes_track_close():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_TRACK_CLOSE.items()}

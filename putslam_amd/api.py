@@ -14,7 +14,8 @@ from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, P
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, default_ransac_params, make_config,
                    PsImageSet, PsKltParams, klt_params, PsDetectParams, detect_params, PsOrbParams, orb_params,
                    PsOrbDetectParams, orb_detect_params, PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, front_end_params,
-                   PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoParams, PsTrackVoIn, PsTrackVoOut, track_vo_params)
+                   PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoParams, PsTrackVoIn, PsTrackVoOut, track_vo_params,
+                   PsTrackCandidates, PsTrackCloseParams, PsTrackCloseOut, track_close_params)
 
 
 class PsError(RuntimeError):
@@ -811,6 +812,58 @@ class Context:
         return dict(next_pts=o["next_pts"][:n], status=o["status"][:n], err=o["err"][:n], matches=o["matches"][:k].copy(),
                     kept_idx=o["kept_idx"][:k].copy(), mask=o["mask"][:k].copy(), rows=new, pose=o["pose"].reshape(4, 4).T.copy(),
                     stats=o["stats"][0].copy())
+
+    # ---- closing the tracking VO step ----
+    def track_candidates_device(self, fe, images: PsImageSet, depth: PsDepthSet, geometry: PsFrameGeometry, capacity, out: PsFrameRowsOut):
+        """ps_track_candidates on device pointers (asynchronous on the context's stream): device_batch.track_candidates."""
+        self._chk(self._L.ps_track_candidates(self._h, fe, C.byref(images), C.byref(depth), C.byref(geometry), int(capacity), C.byref(out)))
+
+    def track_close_create(self, max_pairs, max_rows):
+        """ps_track_close_create: the handle of the intermediates of ps_track_close_pairs (device_batch.TrackClose owns one)."""
+        h = C.c_void_p()
+        self._chk(self._L.ps_track_close_create(self._h, int(max_pairs), int(max_rows), C.byref(h)))
+        return h
+
+    def track_close_pairs_device(self, tc, pyr, slots_ptr, tp: PsTrackCloseParams, tracked: PsTrackedRows, cand: PsTrackCandidates,
+                                 cand_frame_ptr, P, capacity, out_capacity, out: PsTrackCloseOut, passes=15):
+        """ps_track_close_pairs on device pointers (asynchronous on the context's stream): device_batch.track_close_pairs.  passes
+        other than 15: ps_debug_track_close_passes (timing scripts)."""
+        args = (self._h, tc, pyr, _v(slots_ptr), C.byref(tp), C.byref(tracked), None if cand is None else C.byref(cand), _v(cand_frame_ptr),
+                int(P), int(capacity), int(out_capacity), C.byref(out))
+        self._chk(self._L.ps_track_close_pairs(*args) if passes == 15 else self._L.ps_debug_track_close_passes(*args, int(passes)))
+
+    def track_close_pair(self, image, depth, geometry: PsFrameGeometry, rows, params: PsFrontEndParams = None, tp: PsTrackCloseParams = None,
+                         pattern=None):
+        """The second half of Matcher::trackKLT (matcher.cpp:213-381) for one frame on numpy arrays (ps_track_close_pair), uploads
+        included, synchronous: image (rows, cols[, 3]) uint8 and its depth (rows, cols) uint16, rows: a dict of the tracked rows --
+        xy, xy_undist (n, 2), pts (n, 3), angle, response, octave, det_dist (n,) -- as Context.track_vo_pair returns them (with
+        xy_undist).  Returns a dict: desc (k, 32) uint8, rows -- the closed rows in the same form, the previous rows of the next
+        frame --, src_idx (k,) int32 (a candidate's is max(n, 1) + i) and refill (0 not due, 1 merged)."""
+        params, tp = params or front_end_params(), tp or track_close_params()
+        image, cn = _host_image(image)
+        depth = np.asarray(depth)
+        assert depth.dtype == np.uint16 and depth.ndim == 2 and depth.shape == image.shape[:2]
+        if depth.strides[1] != 2 or depth.strides[0] < depth.shape[1] * 2:
+            depth = np.ascontiguousarray(depth)
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8).reshape(1024)
+        types = (("xy", np.float32, (2,)), ("xy_undist", np.float32, (2,)), ("pts", np.float32, (3,)), ("angle", np.float32, ()),
+                 ("response", np.float32, ()), ("octave", np.int32, ()), ("det_dist", np.float64, ()))
+        n = len(np.asarray(rows["xy"]).reshape(-1, 2))
+        t = {k: np.ascontiguousarray(rows[k], dt).reshape((n,) + tail) for k, dt, tail in types}
+
+        def struct(d):
+            return PsTrackedRows(d["xy"].ctypes.data, d["xy_undist"].ctypes.data, d["pts"].ctypes.data, None, d["angle"].ctypes.data,
+                                 d["response"].ctypes.data, d["octave"].ctypes.data, d["det_dist"].ctypes.data)
+        cap = max(n, 1) + max(1, min(int(params.detect.maximalTrackedFeatures), PS_MAX_KPTS))
+        o = {k: np.zeros((cap,) + tail, dt) for k, dt, tail in types}
+        desc, src = np.zeros((cap, 32), np.uint8), np.zeros(cap, np.int32)
+        k, refill = C.c_int(0), C.c_int(0)
+        self._chk(self._L.ps_track_close_pair(self._h, _p(image), _p(depth), image.shape[0], image.shape[1], cn, image.strides[0],
+                                              depth.strides[0], C.byref(params), None if pat is None else _p(pat), C.byref(geometry),
+                                              C.byref(tp), C.byref(struct(t)), n, _p(desc), C.byref(struct(o)), _p(src), cap, C.byref(k),
+                                              C.byref(refill)))
+        k = k.value
+        return dict(desc=desc[:k].copy(), rows={name: a[:k].copy() for name, a in o.items()}, src_idx=src[:k].copy(), refill=refill.value)
 
     def ransac_match_lists(self, params, cfg, K, prev, cur, matches, pairs=None):
         """The estimator over P caller-supplied match lists (ps_ransac_match_lists) on numpy data, uploads and downloads included,

@@ -1589,6 +1589,131 @@ bool FrameMatcherHIP::trackStep(cv::Mat prevRgbImage, cv::Mat rgbImage, cv::Mat 
     return true;
 }
 
+// Matcher::trackKLT, matcher.cpp:133-449
+double FrameMatcherHIP::trackKLT(cv::Mat rgbImage, cv::Mat depthImage, double depthImageScale, Eigen::Matrix4f &estimatedTransformation,
+                                 std::vector<cv::DMatch> &inlierMatches)
+{
+    const auto &cvp = matcherParameters.OpenCVParams;
+    estimatedTransformation = Eigen::Matrix4f::Identity();
+    inlierMatches.clear();
+    if (cvp.detector != "ORB" || cvp.descriptor != "ORB" || cvp.removeTooCloseFeatures > 0 || cvp.maximalTrackedFeatures < 1) {
+        std::cerr << "putslam_hip: trackKLT runs detector \"ORB\" with descriptor \"ORB\", removeTooCloseFeatures 0 (trackStep) and at least one "
+                     "tracked feature allowed: nothing done" << std::endl;
+        return 0.0;
+    }
+    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3) || depthImage.empty() ||
+        depthImage.type() != CV_16U || depthImage.rows != rgbImage.rows || depthImage.cols != rgbImage.cols) {
+        std::cerr << "putslam_hip: trackKLT takes a CV_8UC1 or CV_8UC3 image and a CV_16U depth image of the same size" << std::endl;
+        return 0.0;
+    }
+    std::vector<cv::Point2f> distorted, undistorted;
+    std::vector<Eigen::Vector3f> features3D;
+    std::vector<cv::KeyPoint> keyPoints;
+    std::vector<double> detDists;
+    std::vector<cv::DMatch> matches;
+    if (!prevFeaturesUndistorted.empty() && !prevFeaturesDistorted.empty() && // :147
+        !trackStep(prevRgbImage, rgbImage, depthImage, depthImageScale, prevFeaturesDistorted, prevFeatures3D, prevKeyPoints, prevDetDists, distorted,
+                   undistorted, features3D, keyPoints, detDists, matches, inlierMatches, estimatedTransformation))
+        return 0.0;
+    int status;
+    PsContext *ctx = threadContext(&status);
+    if (!ctx) return 0.0;
+    // :213-381
+    PsFrontEndParams prm;
+    prm.detect.nFeatures = 500; // cv::ORB::create()'s defaults (matcherOpenCV.cpp:67, :90), as frontEnd has them
+    prm.detect.scaleFactor = 1.2f;
+    prm.detect.nLevels = 8;
+    prm.detect.fastThreshold = 20;
+    prm.detect.gridRows = cvp.gridRows;
+    prm.detect.gridCols = cvp.gridCols;
+    prm.detect.maximalTrackedFeatures = cvp.maximalTrackedFeatures;
+    prm.detect.reserved = 0;
+    prm.describe.scaleFactor = 1.2f;
+    prm.describe.nLevels = 8;
+    prm.describe.reserved[0] = prm.describe.reserved[1] = 0;
+    prm.DBScanEps = cvp.DBScanEps;
+    PsTrackCloseParams tp;
+    tp.minimalReprojDistanceNewTrackingFeatures = cvp.minimalReprojDistanceNewTrackingFeatures;
+    tp.minimalTrackedFeatures = cvp.minimalTrackedFeatures;
+    tp.removeTooCloseFeatures = 0;
+    PsFrameGeometry geo;
+    bool haveK;
+    cameraToK(matcherParameters.cameraMatrixMat, geo.K, haveK);
+    const cv::Mat &dc = matcherParameters.distortionCoeffsMat;
+    const int nd = dc.empty() ? 0 : dc.rows * dc.cols;
+    for (int i = 0; i < 5; ++i) geo.dist5[i] = i < nd ? (double)dc.at<float>(dc.rows == 1 ? 0 : i, dc.rows == 1 ? i : 0) : 0.0;
+    geo.depthImageScale = depthImageScale;
+    const size_t n = distorted.size(), base = n > 0 ? n : 1, cap = base + (size_t)cvp.maximalTrackedFeatures;
+    std::vector<float> angle(base), response(base), oAngle(cap), oResponse(cap);
+    std::vector<int32_t> octave(base), oOctave(cap), srcIdx(cap);
+    for (size_t i = 0; i < n; ++i) {
+        angle[i] = keyPoints[i].angle;
+        response[i] = keyPoints[i].response;
+        octave[i] = keyPoints[i].octave;
+    }
+    std::vector<cv::Point2f> oXy(cap), oUn(cap);
+    std::vector<Eigen::Vector3f> oPts(cap);
+    std::vector<double> oDist(cap);
+    std::vector<unsigned char> rows(cap * 32);
+    PsTrackedRows in;
+    std::memset(&in, 0, sizeof in);
+    in.xy = reinterpret_cast<float *>(distorted.data());
+    in.xyUndist = reinterpret_cast<float *>(undistorted.data());
+    in.pts = reinterpret_cast<float *>(features3D.data());
+    in.angle = angle.data();
+    in.response = response.data();
+    in.octave = octave.data();
+    in.detDist = detDists.data();
+    PsTrackedRows out;
+    std::memset(&out, 0, sizeof out);
+    out.xy = reinterpret_cast<float *>(oXy.data());
+    out.xyUndist = reinterpret_cast<float *>(oUn.data());
+    out.pts = reinterpret_cast<float *>(oPts.data());
+    out.angle = oAngle.data();
+    out.response = oResponse.data();
+    out.octave = oOctave.data();
+    out.detDist = oDist.data();
+    int k = 0, refill = 0;
+    status = ps_track_close_pair(ctx, rgbImage.data, reinterpret_cast<const uint16_t *>(depthImage.data), rgbImage.rows, rgbImage.cols,
+                                 rgbImage.channels(), (size_t)rgbImage.step, (size_t)depthImage.step, &prm, nullptr, &geo, &tp, &in, (int)n, rows.data(),
+                                 &out, srcIdx.data(), (int)cap, &k, &refill);
+    if (status != PS_OK) {
+        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        estimatedTransformation = Eigen::Matrix4f::Identity();
+        inlierMatches.clear();
+        return 0.0;
+    }
+    std::vector<cv::KeyPoint> closed((size_t)k);
+    for (int j = 0; j < k; ++j) {
+        cv::KeyPoint &kp = closed[(size_t)j];
+        const size_t s = (size_t)srcIdx[(size_t)j];
+        if (n > 0 && s < n) {
+            kp = keyPoints[s]; // the tracked key point (matcherOpenCV.cpp:240-245)
+        } else {               // a merged one: the key point detectFeaturesORB makes
+            kp.size = 31.f * (float)std::pow((double)prm.detect.scaleFactor, (double)oOctave[(size_t)j]);
+            kp.angle = oAngle[(size_t)j];
+            kp.response = oResponse[(size_t)j];
+            kp.octave = oOctave[(size_t)j];
+            kp.class_id = -1;
+        }
+        kp.pt = oXy[(size_t)j];
+    }
+    double inlierRatio = 0.0; // :404-406
+    if (matches.size() > 0) inlierRatio = RANSAC::pointInlierRatio(inlierMatches, matches);
+    // :436-445
+    prevFeaturesUndistorted.assign(oUn.begin(), oUn.begin() + k);
+    prevFeaturesDistorted.assign(oXy.begin(), oXy.begin() + k);
+    prevFeatures3D.assign(oPts.begin(), oPts.begin() + k);
+    prevDescriptors = k > 0 ? cv::Mat(k, 32, CV_8U) : cv::Mat();
+    if (k > 0) std::memcpy(prevDescriptors.data, rows.data(), (size_t)k * 32);
+    prevKeyPoints.swap(closed);
+    prevDetDists.assign(oDist.begin(), oDist.begin() + k);
+    prevRgbImage = rgbImage;
+    prevDepthImage = depthImage;
+    fusedSynced_ = false; // (the resident frame of match() is no longer prevDescriptors / prevFeatures3D)
+    return inlierRatio;
+}
+
 // MatcherOpenCV::performMatching (matcherOpenCV.cpp:198-206) with the matcher of matcherOpenCV.cpp:100-102, cv::BFMatcher(cv::NORM_L2,
 // true), on CV_32F descriptor Mats of 1 .. PS_MAX_L2_DIM columns (ps_match_l2_f32).
 std::vector<cv::DMatch> l2CrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descriptors)

@@ -205,6 +205,7 @@ class FrameMatcher {
             std::string detector = "ORB";
             int gridRows = 1, gridCols = 1;
             int maximalTrackedFeatures = 500;
+            int minimalTrackedFeatures = 150; // matcher.h:51; putslammatcherOpenCVParameters.xml:66 (trackKLT's refill)
             // the descriptor's name (matcher.h:40; putslammatcherOpenCVParameters.xml:64): describeFeatures below runs "ORB"
             std::string descriptor = "ORB";
             double DBScanEps = 1; // matcher.h:54; putslammatcherOpenCVParameters.xml:70 (frontEnd's thinning)
@@ -466,6 +467,24 @@ class FrameMatcherHIP : public FrameMatcher {
                    std::vector<cv::Point2f> &distorted, std::vector<cv::Point2f> &undistorted, std::vector<Eigen::Vector3f> &features3D,
                    std::vector<cv::KeyPoint> &keyPoints, std::vector<double> &detDists, std::vector<cv::DMatch> &matches,
                    std::vector<cv::DMatch> &inlierMatches, Eigen::Matrix4f &estimatedTransformation);
+    // Matcher::trackKLT (matcher.cpp:133-449) on what it reads of a SensorFrame (rgbImage, depthImage, depthImageScale), for detector
+    // and descriptor "ORB": trackStep above from the kept prev* state (the identity when there is none, :147-148), then :213-381 as
+    // ONE call (ps_track_close_pair) -- the refill when fewer than OpenCVParams.minimalTrackedFeatures rows survived (detectFeatures,
+    // DBScan(DBScanEps).run, removeImageDistortion, keypoints2Dto3D, the detection distances, mergeTrackedFeatures), the predicted
+    // level of every row, the reordering by level, describeFeatures at that level and the removal of the rows it dropped -- and the
+    // swap of :436-445: the closed rows, their descriptors and the two images (shallow, as the reference keeps them) are the prev*
+    // state of the next call.  A merged key point is the one detectFeaturesORB makes.  Returns RANSAC::pointInlierRatio(inlierMatches,
+    // matches), 0 with no matches (:404-406).  On an error and for removeTooCloseFeatures > 0: one line on std::cerr, 0, the identity,
+    // the state as it was.  Where the reference's position-matching walk (:359-375) would pair a dropped row's columns with its
+    // neighbour's descriptor (two rows within 0.0001 px across the border: DESIGN.md section 8.15), every descriptor stays with its row.
+    double trackKLT(cv::Mat rgbImage, cv::Mat depthImage, double depthImageScale, Eigen::Matrix4f &estimatedTransformation,
+                    std::vector<cv::DMatch> &inlierMatches);
+
+  protected: // Matcher's tracking state (matcher.h:379-391); prevDescriptors and prevFeatures3D are FrameMatcher's
+    cv::Mat prevRgbImage, prevDepthImage;
+    std::vector<cv::Point2f> prevFeaturesUndistorted, prevFeaturesDistorted;
+    std::vector<cv::KeyPoint> prevKeyPoints;
+    std::vector<double> prevDetDists;
 };
 
 } // namespace putslam_hip

@@ -10,7 +10,8 @@ from . import api
 from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBatch, PsLoopBatchF32, PsLoopResults, PsMapStore,
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
                    make_config, PsImageSet, klt_params, detect_params, orb_params, orb_detect_params, PsDepthSet, PsFrameRowsOut,
-                   front_end_params, PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoIn, PsTrackVoOut, track_vo_params)
+                   front_end_params, PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoIn, PsTrackVoOut, track_vo_params,
+                   PsTrackCandidates, PsTrackCloseOut, track_close_params)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -879,6 +880,140 @@ def run_tracked_sequences(ctx, pyr: KltPyramids, depth, rows0: TrackedRows, fram
             due = np.nonzero(counts[:, s] < int(minimal_tracked_features))[0]
             refill[s] = due[0] if due.size else K
     return steps, refill
+
+
+class TrackClose(_Handle):
+    """The intermediates of ps_track_close_pairs for calls of up to max_pairs pairs x max_rows rows (ps_track_close_create): the
+    merged rows, their levels and the description's keptIdx -- allocated once, so that a call neither allocates nor waits."""
+
+    _destroy = "ps_track_close_destroy"
+
+    def __init__(self, ctx, max_pairs, max_rows):
+        self.ctx, self.max_pairs, self.max_rows = ctx, int(max_pairs), int(max_rows)
+        self.handle = ctx.track_close_create(max_pairs, max_rows)
+
+
+def track_candidates(ctx, fe: FrontEnd, images, depth, geometry, capacity=None, out=None, use_torch_stream=True):
+    """The refill's sandbox for F frames (ps_track_candidates; matcher.cpp:218-246): detect, DBScan, undistort, back-project and the
+    detection distances, nothing described.  Arguments as front_end_frames_batch takes them.  Returns a FrameRowsDevice with every
+    side array (its desc stays zero; nkpts are the candidate counts), written asynchronously -- the `cand` of track_close_pairs."""
+    s = _image_set(images, fe.rows, fe.cols, fe.channels)
+    ds = DepthSet(depth, fe.rows, fe.cols)
+    F, dev = images.shape[0], images.device
+    cap = max(1, int(fe.params.detect.maximalTrackedFeatures)) if capacity is None else int(capacity)
+    out = out or FrameRowsDevice(F, cap, dev)
+    o = out.out_struct()
+    _on_torch_stream(ctx, dev, lambda: ctx.track_candidates_device(fe.handle, s, ds, geometry, cap, o), use_torch_stream)
+    return out
+
+
+class ClosedRows(FrameSet):
+    """What ps_track_close_pairs writes for P pairs of out_cap rows: desc (P, out_cap, 32) uint8, rows -- a TrackedRows with every
+    column, the previous rows of the next track_vo_pairs --, src_idx (P, out_cap) int32 (the tracked row, or capacity + i for
+    candidate i) and refill (P,) int32 (0 not due, 1 merged, 2 due without candidates).  desc, rows.pts and rows.counts are a dense
+    frame set (pts / nkpts name them): a ClosedRows is to run_pairs what a FrameSetDevice is."""
+
+    def __init__(self, P, out_cap, device):
+        self.device, self.num_frames, self.max_kpts = torch.device(device), int(P), int(out_cap)
+        self.P, self.cap = self.num_frames, self.max_kpts
+        self.rows = TrackedRows(self.P, self.cap, self.device)
+        self.desc = _zeros(self.device, (self.P, self.cap, 32), torch.uint8)
+        self.pts, self.nkpts = self.rows.pts, self.rows.counts
+        self.src_idx = _zeros(self.device, (self.P, self.cap), torch.int32)
+        self.refill = _zeros(self.device, (self.P,), torch.int32)
+        torch.cuda.current_stream(self.device).synchronize()   # (PairResultsDevice's reason: the blocks are ready when this returns)
+
+    def out_struct(self):
+        return PsTrackCloseOut(self.desc.data_ptr(), self.rows.rows_struct(), self.src_idx.data_ptr(), self.refill.data_ptr())
+
+    def download(self):
+        return dict(desc=self.desc.cpu().numpy(), src_idx=self.src_idx.cpu().numpy(), refill=self.refill.cpu().numpy(),
+                    rows=self.rows.download())
+
+
+def track_close_pairs(ctx, tc: TrackClose, pyr: OrbPyramids, slots, rows: TrackedRows, cand: FrameRowsDevice = None, cand_frame=None,
+                      tp=None, out_cap=None, out: ClosedRows = None, use_torch_stream=True, passes=15):
+    """matcher.cpp:213-381 for P pairs with no host step (ps_track_close_pairs): rows -- the TrackedRows a track_vo_pairs call left,
+    every column --, cand -- what track_candidates returned, or None -- with cand_frame (P,) int32 (-1: none for that pair), pyr /
+    slots (P,) int32: the built ORB pyramids and the slot of every pair's current image; tp _abi.track_close_params(...).  The refill
+    is decided on the device (rows.counts[p] < minimalTrackedFeatures).  Returns a ClosedRows of out_cap rows (default rows.cap +
+    cand's), written asynchronously; its .rows are the `rows` of the next track_vo_pairs.  passes: 15, or the mask of
+    ps_debug_track_close_passes (timing scripts)."""
+    P, cap = rows.P, rows.cap
+    _expect(slots, torch.int32, (P,))
+    tp = tp or track_close_params()
+    cs = None
+    if cand is not None:
+        _expect(cand_frame, torch.int32, (P,))
+        cs = PsTrackCandidates(cand.xy.data_ptr(), cand.xy_undist.data_ptr(), cand.pts.data_ptr(), cand.angle.data_ptr(),
+                               cand.response.data_ptr(), cand.octave.data_ptr(), cand.det_dist.data_ptr(), cand.nkpts.data_ptr(),
+                               cand.num_frames, cand.max_kpts)
+    need = cap + (cand.max_kpts if cand is not None else 0)
+    out_cap = (out.cap if out is not None else need) if out_cap is None else int(out_cap)
+    out = out or ClosedRows(P, out_cap, rows.device)
+    assert out.P == P and out.cap == out_cap
+    o, r = out.out_struct(), rows.rows_struct()
+    cf = None if cand is None else cand_frame.data_ptr()
+    _on_torch_stream(ctx, rows.device, lambda: ctx.track_close_pairs_device(tc.handle, pyr.handle, slots.data_ptr(), tp, r, cs, cf, P, cap,
+                                                                            out_cap, o, passes), use_torch_stream)
+    return out
+
+
+def run_tracked_vo(ctx, klt: KltPyramids, orb: OrbPyramids, fe: FrontEnd, tc: TrackClose, images, depth, rows0: TrackedRows, frames,
+                   geometry, params, cfg, tp=None, klt_p=None, close_tp=None, cand_capacity=None, candidates="always",
+                   use_torch_stream=True):
+    """S tracked sequences in lockstep for K frames with the refill done on the device (matcher.cpp:147-381 per frame): frames
+    (S, K + 1) name, for every sequence, the frames of `images` / `depth` -- device tensors (N, rows, cols[, channels]) uint8 and
+    (N, rows, cols) uint16 -- which are also the slots of `klt` and `orb`, both built from `images` by the caller (one build
+    serves every sequence and step).  rows0: the rows of every sequence's first frame, every column.  Per step: track_vo_pairs,
+    the candidates, track_close_pairs; the closed rows are the next step's previous rows where they lie.  Two policies, both on
+    the same calls: candidates="always" queues track_candidates for every sequence's current frame at every step and reads
+    nothing back until the end (the device ignores candidates of a pair that is not due); candidates="due" reads the tracked
+    counts back once a step and detects only for the sequences that are due.  A step's blocks hold cand_capacity rows more than
+    the step before (ps_track_close_pairs' out-capacity rule), so a chain is as long as the handle `tc` has rows for.  Returns
+    (steps: K TrackVoDevice -- poses, masks, statistics --, closed: K ClosedRows -- the frame sets --, counts (K, S), refill
+    (K, S) int32 numpy: the closed rows' counts and ps_track_close_pairs' flags)."""
+    assert candidates in ("always", "due")
+    frames = np.ascontiguousarray(frames, np.int32)
+    S, K = frames.shape[0], frames.shape[1] - 1
+    assert S == rows0.P and rows0.carried == _CARRIED
+    dev = rows0.device
+    ccap = max(1, int(fe.params.detect.maximalTrackedFeatures)) if cand_capacity is None else int(cand_capacity)
+    close_tp = close_tp or track_close_params()
+    pairs = [torch.from_numpy(np.ascontiguousarray(frames[:, k:k + 2])).to(dev) for k in range(K)]
+    slots = [torch.from_numpy(np.ascontiguousarray(frames[:, k + 1])).to(dev) for k in range(K)]
+    steps = [TrackVoDevice(S, rows0.cap + k * ccap, dev) for k in range(K)]
+    closed = [ClosedRows(S, rows0.cap + (k + 1) * ccap, dev) for k in range(K)]
+    every = torch.arange(S, dtype=torch.int32, device=dev)
+    rows = rows0
+    for k in range(K):
+        track_vo_pairs(ctx, klt, depth, geometry, pairs[k], rows, params, cfg, tp, klt_p, None, steps[k], use_torch_stream)
+        cand, cand_frame = None, None
+        if candidates == "always":
+            cur = slots[k].long()
+            cand, cand_frame = track_candidates(ctx, fe, images[cur], depth[cur], geometry, ccap, use_torch_stream=use_torch_stream), every
+        else:
+            if not use_torch_stream:
+                ctx.synchronize()
+            n = steps[k].rows.counts.cpu().numpy()      # (the step's one read-back)
+            due = np.nonzero((n >= 0) & (n < int(close_tp.minimalTrackedFeatures)))[0]
+            if due.size:
+                cur = torch.from_numpy(frames[due, k + 1].astype(np.int64)).to(dev)
+                cand = track_candidates(ctx, fe, images[cur], depth[cur], geometry, ccap, use_torch_stream=use_torch_stream)
+                where = np.full(S, -1, np.int32)
+                where[due] = np.arange(due.size, dtype=np.int32)
+                cand_frame = torch.from_numpy(where).to(dev)
+        if cand is None:    # nobody is due: the call still closes every sequence's rows
+            track_close_pairs(ctx, tc, orb, slots[k], steps[k].rows, None, None, close_tp, out=closed[k], use_torch_stream=use_torch_stream)
+        else:
+            track_close_pairs(ctx, tc, orb, slots[k], steps[k].rows, cand, cand_frame, close_tp, out=closed[k],
+                              use_torch_stream=use_torch_stream)
+        rows = closed[k].rows
+    if K and not use_torch_stream:
+        ctx.synchronize()
+    counts = torch.stack([c.rows.counts for c in closed]).cpu().numpy() if K else np.zeros((0, S), np.int32)
+    refill = torch.stack([c.refill for c in closed]).cpu().numpy() if K else np.zeros((0, S), np.int32)
+    return steps, closed, counts, refill
 
 
 class MapBatchDevice(PairResultsDevice):
