@@ -250,12 +250,9 @@ struct OrbKeepSink {
     }
 };
 
-// retainBest(q_l) by the Harris response in every level, then the ROI's ordering and its cut: one work-group per slot
-__global__ __launch_bounds__(kFastSelBlock) void ps_orbdet_roi(const OrbDetLevel *__restrict__ levels, int nLevels, OrbDetQuota qs, OrbDetLists L,
-                                                               OrbWindow win, int maxInRoi, OrbDetRoiLists R)
+// retainBest(q_l) by the Harris response in every level of one slot: keep1, by the threads of one work-group
+PS_D void orbdet_cut2(const OrbDetLevel *__restrict__ levels, int nLevels, const OrbDetQuota &qs, const OrbDetLists &L, int slot, int tid)
 {
-    __shared__ FastSortLds s;
-    const int slot = (int)blockIdx.x, tid = (int)threadIdx.x;
     const size_t sbase = (size_t)slot * L.listTotal;
     for (int l = 0; l < nLevels; ++l) {
         const OrbDetLevel D = levels[l];
@@ -268,6 +265,23 @@ __global__ __launch_bounds__(kFastSelBlock) void ps_orbdet_roi(const OrbDetLevel
             L.keep1[sbase + D.listOff + i] = greater < q; // at or above the q-th largest: ties stay
         }
     }
+}
+
+// The second cut alone, for a call that can emit nothing (maximalTrackedFeatures 0, or no quota on a live level): the diagnostic
+// read-back of the level lists finds `kept` written by this call, not what an earlier call or the allocation left there
+__global__ __launch_bounds__(kFastSelBlock) void ps_orbdet_cut2(const OrbDetLevel *__restrict__ levels, int nLevels, OrbDetQuota qs, OrbDetLists L)
+{
+    orbdet_cut2(levels, nLevels, qs, L, (int)blockIdx.x, (int)threadIdx.x);
+}
+
+// The second cut, then the ROI's ordering and its cut: one work-group per slot
+__global__ __launch_bounds__(kFastSelBlock) void ps_orbdet_roi(const OrbDetLevel *__restrict__ levels, int nLevels, OrbDetQuota qs, OrbDetLists L,
+                                                               OrbWindow win, int maxInRoi, OrbDetRoiLists R)
+{
+    __shared__ FastSortLds s;
+    const int slot = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const size_t sbase = (size_t)slot * L.listTotal;
+    orbdet_cut2(levels, nLevels, qs, L, slot, tid);
     __syncthreads();
     int m = 0;
     for (int l = 0; l < nLevels; ++l) {
@@ -507,7 +521,12 @@ int orbdet_launch(PsContext *ctx, PsOrbDetector *det, const uint8_t *pixels, siz
                            (const uint8_t *)det->planes, det->slotBytes, (const OrbDetLevel *)det->dLevels, det->L);
         PS_HIP(hipGetLastError());
     }
-    if (!pl.any()) { // nothing can come out: the counts alone are written
+    if (!pl.any()) { // nothing can come out: the second cut for the read-back of the level lists, and the counts
+        if (passes & kOrbDetPassRoi) {
+            hipLaunchKernelGGL(ps_orbdet_cut2, dim3((unsigned)slots), dim3(kFastSelBlock), 0, ctx->stream, (const OrbDetLevel *)det->dLevels,
+                               det->nLevels, pl.qs, det->L);
+            PS_HIP(hipGetLastError());
+        }
         if (passes & kOrbDetPassJoin) PS_HIP(hipMemsetAsync(counts, 0, (size_t)frames * sizeof(int32_t), ctx->stream));
         return PS_OK;
     }

@@ -348,6 +348,9 @@ PARAM_CASES = [("texture", 96, 128, 1, params(nf, sf, nl, t)) for nf, sf, nl, t 
     (12, 1.5, 3, 20), (12, 1.2, 1, 20), (24, 1.2, 8, 20), (12, 1.2, 3, 0), (12, 1.2, 3, 255), (0, 1.2, 3, 20), (1, 1.2, 3, 20),
     (2, 1.2, 3, 20),        # quotas 1, 1, 0: the last level's quota is 0
     (500, 1.2, 8, 20)]]     # no cut bites
+# maximalTrackedFeatures 0: nothing comes out, and the read-back of the levels still holds both cuts (a draw of tests/fuzz_front_end.py
+# found the second cut's flags unwritten by such a call)
+PARAM_CASES.append(("texture", 96, 128, 1, params(12, 1.2, 3, 20, 1, 1, 0)))
 EDGE_CASES = [("noise256", 63, 64, 1, params(20, 1.2, 8)),     # level 0 has a 1 x 2 interior
               ("noise256", 62, 90, 1, params(20, 1.2, 8))]     # nothing
 GRID_CASES = [("texture", 192, 256, cn, params(24, 1.2, 3, 20, gr, gc, mx)) for cn, gr, gc, mx in [

@@ -288,7 +288,8 @@ def describe_loops(pyr, xy, angle, octave, pattern=None, counters=None):
     return desc, kept
 
 
-def describe(pyr, xy, angle, octave, pattern=None):
+def describe(pyr, xy, angle, octave, pattern=None, counters=None):
+    """describe_loops as array operations; counters as there (tests/test_orb_ref_host.py holds the two to each other)"""
     pattern = default_pattern() if pattern is None else np.asarray(pattern, np.int8).reshape(256, 4)
     xy = np.asarray(xy, f32).reshape(-1, 2)
     angle = np.asarray(angle, f32).reshape(-1)
@@ -319,6 +320,17 @@ def describe(pyr, xy, angle, octave, pattern=None):
             y = cy + np.rint(px * b + py * a).astype(np.int64)
             inside = (x >= 0) & (x < c) & (y >= 0) & (y < r)
             xr, yr = reflect101_v(x, c), reflect101_v(y, r)
+            if counters is not None:
+                counters["samples"] += int(inside.size)
+                counters["outside"] += int((~inside).sum())
+                if not inside.all():
+                    reach = np.maximum(np.maximum(-x, x - (c - 1)), np.maximum(-y, y - (r - 1)))
+                    counters["reach"] = max(counters["reach"], int(reach[~inside].max()))
+                    once_x = np.where(x < 0, -x, np.where(x >= c, 2 * c - 2 - x, x))
+                    once_y = np.where(y < 0, -y, np.where(y >= r, 2 * r - 2 - y, y))
+                    ok_x = (once_x >= 0) & (once_x < c) if c > 1 else np.ones_like(inside)
+                    ok_y = (once_y >= 0) & (once_y < r) if r > 1 else np.ones_like(inside)
+                    counters["bounced"] += int((~inside & ~(ok_x & ok_y)).sum())
             vals.append(np.where(inside, blr[yr, xr], raw[yr, xr]).astype(np.int64))
         desc[rows_j] = np.packbits(vals[0] < vals[1], axis=1, bitorder="little")
     return desc, kept

@@ -75,7 +75,7 @@ def ordered(request, ctx, ballast):
             from putslam_amd.device_batch import _work_stream
             with torch.cuda.stream(_work_stream(torch.device("cuda:0"))):
                 _busy(ballast, 3)
-        with torch.cuda.stream(stream):
+        with S.quiet_collector(), torch.cuda.stream(stream):     # (no handle of an earlier test is destroyed inside the timed call)
             busy, first = _busy(ballast)
             for t, f in zip(inputs, finals):
                 t.copy_(f)
@@ -243,15 +243,16 @@ def _switch(ctx, ballast, first, second):
     import torch
     a, b = torch.cuda.Stream(), torch.cuda.Stream()
     torch.cuda.synchronize()
-    with torch.cuda.stream(a):
-        busy, start = _busy(ballast)
-    t0 = time.perf_counter()
-    ctx.set_stream(a.cuda_stream)
-    first()
-    ctx.set_stream(b.cuda_stream)
-    second()
-    t1 = time.perf_counter()
-    drained = busy.query()
+    with S.quiet_collector():
+        with torch.cuda.stream(a):
+            busy, start = _busy(ballast)
+        t0 = time.perf_counter()
+        ctx.set_stream(a.cuda_stream)
+        first()
+        ctx.set_stream(b.cuda_stream)
+        second()
+        t1 = time.perf_counter()
+        drained = busy.query()
     torch.cuda.synchronize()
     ctx.set_stream(0)
     _report("switch", start, busy, t1 - t0)
@@ -363,7 +364,7 @@ def test_chain_queued_without_a_host_step(ctx, ballast, chain, chain_stepwise, w
     final = torch.from_numpy(np.stack(S.chain_images())).to("cuda:0")
     images = torch.zeros_like(final)
     torch.cuda.synchronize()
-    with torch.cuda.stream(stream):
+    with S.quiet_collector(), torch.cuda.stream(stream):
         busy, start = _busy(ballast)
         images.copy_(final)
         t0 = time.perf_counter()

@@ -2,7 +2,8 @@
 of Matcher::trackKLT's second half (tests/track_close_ref.py), byte for byte -- floats as words; where the expected float is a NaN
 the device's is one too.  Every output block is filled with 0xEE before a call and must still hold it beyond every count, and
 everywhere for a pair the call refuses (counts -1).  The scene is the 150 x 200 images of tests/frame_assembly_ref.py; the thresholds
-are small (minimalTrackedFeatures 20, distance 5) so that every case fits 24 tracked rows and 260 candidates."""
+are small (minimalTrackedFeatures 20, distance 5) so that every case fits 24 tracked rows and 260 candidates; the seam cases of the
+merge (test_merge_seams_*) bring blocks of their own: 520 tracked rows and 1100 candidates."""
 import os
 import sys
 
@@ -272,6 +273,85 @@ def test_colour_pair_by_pair_and_no_candidates(ctx):
     none = run(ctx, tc, pyr, specs, slots, None, cap=CAP).download()
     check(none, [(t, -1) for t, _ in specs], slots, 3, "no candidates")
     assert none["refill"].tolist() == [2, 2, 2, 0, 2]
+    tc.close()
+    pyr.close()
+
+
+# ---- the seams of the merge: blocks of their own size (tests/track_close_ref.py: SEAM_*; the premises are asserted on the
+# restatement in tests/test_track_close_ref_host.py::test_seam_cases_cross_every_tile_seam_of_the_merge)
+SEAM_PAIRS = [(nt, nc) for nt in C.SEAM_TRACKED for nc in C.SEAM_CANDIDATES]
+SEAM_OCAP = C.SEAM_CAP + C.SEAM_CCAP
+
+
+def seam_want(nt, nc, slot):
+    key = ("seam", nt, nc, slot)
+    if key not in _WANT:
+        tracked, cand = C.seam_case(nt, nc)
+        _WANT[key] = C.close(tracked, cand, pyramids(1)[slot], C.SEAM_CAP, C.SEAM_MINIMAL, C.SEAM_MIN_DIST)
+    return _WANT[key]
+
+
+def seam_run(ctx, tc, pyr, pairs, slots):
+    """ps_track_close_pairs on the seam cases `pairs`, one candidate frame per pair, every block filled with 0xEE first"""
+    import torch
+    from putslam_amd import device_batch as db
+    from putslam_amd._abi import track_close_params
+    P = len(pairs)
+    t, c, out = db.TrackedRows(P, C.SEAM_CAP, "cuda:0"), db.FrameRowsDevice(P, C.SEAM_CCAP, "cuda:0"), closed_out(P, SEAM_OCAP)
+    fill_ee(*[getattr(t, n) for n in ROW_NAMES])
+    fill_ee(*[getattr(c, n) for n in ROW_NAMES])
+    for p, (nt, nc) in enumerate(pairs):
+        tracked, cand = C.seam_case(nt, nc)
+        put_rows(t, p, tracked, nt)
+        put_rows(c, p, cand, nc)
+    t.counts.copy_(dev(np.array([nt for nt, _ in pairs], np.int32)))
+    c.nkpts.copy_(dev(np.array([nc for _, nc in pairs], np.int32)))
+    torch.cuda.synchronize()
+    db.track_close_pairs(ctx, tc, pyr, dev(np.array(slots, np.int32)), t, c, dev(np.arange(P, dtype=np.int32)),
+                         track_close_params(C.SEAM_MINIMAL, C.SEAM_MIN_DIST), out=out)
+    torch.cuda.synchronize()
+    return out
+
+
+def seam_check(got, pairs, slots, what):
+    for p, ((nt, nc), slot) in enumerate(zip(pairs, slots)):
+        w = seam_want(nt, nc, slot)
+        k = len(w["xy"])
+        assert got["rows"]["counts"][p] == k and got["refill"][p] == w["refill"] == 1, (what, nt, nc, got["rows"]["counts"][p], k)
+        same_bits(got["src_idx"][p, :k], w["src_idx"], (what, nt, nc, "src_idx"))
+        same_bits(got["desc"][p, :k], w["desc"], (what, nt, nc, "desc"))
+        assert is_ee(got["desc"][p, k:]) and is_ee(got["src_idx"][p, k:]), (what, nt, nc)
+        for n, dt, _ in C.COLUMNS:
+            same_bits(got["rows"][n][p, :k], np.asarray(w[n], dt), (what, nt, nc, n))
+            assert is_ee(got["rows"][n][p, k:]), (what, nt, nc, n)
+
+
+@pytest.mark.parametrize("nt,nc", SEAM_PAIRS)
+def test_merge_seams_pair_by_pair(ctx, nt, nc):
+    """255 / 256 / 257 / 513 tracked rows against 513 / 1100 candidates, candidates 512 .. 600 copies of 0 .. 88 a pixel away: the
+    tracked-row loop and the accepted-candidate loop take their second and third trips, and a candidate of the third tile is
+    rejected because of one accepted in the first.  srcIdx, the closed rows, desc and refill equal the restatement."""
+    from putslam_amd import device_batch as db
+    tc, pyr = db.TrackClose(ctx, 1, SEAM_OCAP), device_pyramids(ctx, 1)
+    slot = (nt + nc) % 2
+    seam_check(seam_run(ctx, tc, pyr, [(nt, nc)], [slot]).download(), [(nt, nc)], [slot], "one pair")
+    tc.close()
+    pyr.close()
+
+
+def test_merge_seams_batch_equals_pair_by_pair(ctx):
+    """The eight seam cases as one call equal the restatement, and block for block the eight calls of one pair."""
+    import torch
+    from putslam_amd import device_batch as db
+    slots = [(nt + nc) % 2 for nt, nc in SEAM_PAIRS]
+    tc, pyr = db.TrackClose(ctx, len(SEAM_PAIRS), SEAM_OCAP), device_pyramids(ctx, 1)
+    whole = seam_run(ctx, tc, pyr, SEAM_PAIRS, slots)
+    seam_check(whole.download(), SEAM_PAIRS, slots, "batch")
+    for p, pair in enumerate(SEAM_PAIRS):
+        one = seam_run(ctx, tc, pyr, [pair], slots[p:p + 1])
+        for a, b in [(one.desc, whole.desc), (one.src_idx, whole.src_idx), (one.refill, whole.refill), (one.rows.counts, whole.rows.counts)] + \
+                [(getattr(one.rows, n), getattr(whole.rows, n)) for n in ROW_NAMES]:
+            assert torch.equal(a[0:1].view(torch.uint8), b[p:p + 1].view(torch.uint8)), pair
     tc.close()
     pyr.close()
 

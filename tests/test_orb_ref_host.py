@@ -78,7 +78,10 @@ def test_rotation_bar():
 
 def both(pyr, xy, angle, octave, pattern=None, counters=None):
     d1, k1 = R.describe_loops(pyr, xy, angle, octave, pattern, counters)
-    d2, k2 = R.describe(pyr, xy, angle, octave, pattern)
+    seen = None if counters is None else R.new_counters()
+    d2, k2 = R.describe(pyr, xy, angle, octave, pattern, seen)
+    if counters is not None:   # the vectorised form counts what the loops count (every caller passes new_counters())
+        assert seen == counters, (seen, counters)
     assert d1.tobytes() == d2.tobytes() and k1.tobytes() == k2.tobytes() and k1.dtype == k2.dtype == np.int32
     return d1, k1
 

@@ -122,6 +122,37 @@ def test_walk_differs_from_kept_only_for_a_dropped_row_within_its_tolerance_of_a
     assert out["kept"].tolist() == [1] and out["walk"].tolist() == [1]
 
 
+def test_seam_cases_cross_every_tile_seam_of_the_merge():
+    """The cases of tests/test_gpu_track_close.py::test_merge_seams_*: 255 / 256 / 257 / 513 tracked rows (one, one, two and three
+    trips of the tracked-row loop) against 513 and 1100 candidates (a third and a fifth tile).  With 1100: more than a tile of
+    candidates is accepted before the last tile (the accepted-candidate loop takes a second trip); of the copies 512 .. 600 of
+    candidates 0 .. 88 some are rejected though near no tracked row -- their original, accepted two tiles earlier, lies a pixel away
+    -- and some are accepted because the original was itself rejected.  With 513: candidate 512 is a third tile of its own."""
+    assert C.SEAM_CAP >= max(C.SEAM_TRACKED) and C.SEAM_CCAP >= max(C.SEAM_CANDIDATES) and C.SEAM_MINIMAL > max(C.SEAM_TRACKED)
+    lo, hi = C.SEAM_COPIES
+    for nt in C.SEAM_TRACKED:
+        for nc in C.SEAM_CANDIDATES:
+            tracked, cand = C.seam_case(nt, nc)
+            assert len(tracked["xy"]) == nt and len(cand["xy"]) == nc
+            copies = np.arange(lo, min(hi, nc))
+            assert (cand["xy_undist"][copies] == cand["xy_undist"][copies - lo] + f32([1, 0])).all()
+            s = C.merge_seams(tracked, cand, C.SEAM_MIN_DIST)
+            acc = set(s["accepted"].tolist())
+            out = C.close(tracked, cand, pyramid(), C.SEAM_CAP, C.SEAM_MINIMAL, C.SEAM_MIN_DIST)
+            assert out["refill"] == 1 and accepted(out, C.SEAM_CAP).tolist() == s["accepted"].tolist()
+            assert out["walk"].tolist() == out["kept"].tolist()
+            if nc == 513:
+                assert copies.tolist() == [512] and (nc - 1) // C.MERGE_TILE == 2
+                continue
+            rejected_by_original = [i for i in copies if i in s["earlier_only"] and i - lo in acc]
+            accepted_after_rejected_original = [i for i in copies if i in acc and i - lo not in acc]
+            print(nt, nc, "accepted", len(acc), "before the last tile", s["before_last"], "copies rejected by their original",
+                  len(rejected_by_original), "copies accepted", len(accepted_after_rejected_original))
+            assert len(rejected_by_original) > 0 and len(accepted_after_rejected_original) > 0
+            assert s["before_last"] > C.MERGE_TILE and (nc - 1) // C.MERGE_TILE == 4
+            assert len(s["second_trip_only"]) > 0      # rejected by an accepted candidate beyond the first 256 alone
+
+
 def test_walk_of_the_reference_selects_the_kept_rows():
     for seed, n, m in ((11, 60, 0), (12, 20, 70), (13, 0, 30), (14, 63, 1)):
         tracked = C.random_rows(n, seed)

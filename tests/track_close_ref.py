@@ -145,6 +145,65 @@ def near_and_far_candidates(tracked, n, seed, min_dist=MIN_DIST):
     return c
 
 
+def move_copies(cand, src, dst, step=(1.0, 0.0)):
+    """Candidates dst become candidates src moved by `step` pixels (image and undistorted position; every other column copied).
+    A copy is rejected because of its original where the original was accepted, and may be accepted where it was itself rejected."""
+    src, dst = np.asarray(src, np.int64), np.asarray(dst, np.int64)
+    for n, _, _ in COLUMNS:
+        cand[n][dst] = cand[n][src]
+    cand["xy"][dst] += np.asarray(step, f32)
+    cand["xy_undist"][dst] += np.asarray(step, f32)
+    return cand
+
+
+# The seams of the merge (ps_track_merge_rows passes candidates, and stages what it sweeps them against, MERGE_TILE at a time):
+# tracked rows that need a second and a third trip, candidates that fill a third and a fifth tile, more than a tile of accepted
+# candidates before the last one, and copies in the third tile of candidates of the first.
+MERGE_TILE = 256
+SEAM_CAP, SEAM_CCAP = 520, 1100                 # the capacities of the seam cases' own blocks
+SEAM_TRACKED, SEAM_CANDIDATES = (255, 256, 257, 513), (513, 1100)
+SEAM_MINIMAL = max(SEAM_TRACKED) + 1            # every case is due
+SEAM_COPIES = (512, 601)                        # candidates 512 .. 600 are candidates 0 .. 88 moved by one pixel
+# The distance of the seam cases.  near_and_far_candidates puts every other candidate at (1, 1) from a tracked row: 1.41 px, rejected;
+# its copy lies at (2, 1), 2.24 px: free of that row, accepted unless something else is near.  The copy of an accepted candidate lies
+# 1 px from it: rejected because of a candidate two tiles earlier.
+SEAM_MIN_DIST = 2.0
+
+
+def seam_case(n_tracked, n_cand):
+    """(tracked rows, candidates) of one seam case"""
+    tracked = random_rows(n_tracked, 50 + n_tracked)
+    cand = near_and_far_candidates(tracked, n_cand, 60 + n_tracked + n_cand)
+    dst = np.arange(SEAM_COPIES[0], min(SEAM_COPIES[1], n_cand))
+    return tracked, move_copies(cand, dst - SEAM_COPIES[0], dst)
+
+
+def merge_seams(tracked, cand, min_dist=MIN_DIST):
+    """What mergeTrackedFeatures goes through on these rows, from the restatement alone: dict(accepted -- the candidates merged --,
+    before_last -- how many of them lie before the last tile --, earlier_only -- the rejected candidates near no tracked row and
+    near no accepted candidate of their own tile: rejected only because of a candidate accepted in an EARLIER tile --,
+    second_trip_only -- those of them near none of the first MERGE_TILE accepted candidates either: a sweep that stops after one
+    trip over the accepted candidates would accept them)."""
+    und_t, und_c = np.asarray(tracked["xy_undist"], f32).reshape(-1, 2), np.asarray(cand["xy_undist"], f32).reshape(-1, 2)
+    nc = len(und_c)
+    acc = np.asarray(X.merge_tracked_features(und_t, und_c, min_dist), np.int64)
+    accepted = set(acc.tolist())
+    earlier_only, second_trip_only = [], []
+    for i in range(MERGE_TILE, nc):
+        if i in accepted or X.near_merge(und_t, und_c[i], min_dist).any():
+            continue
+        t0 = i // MERGE_TILE * MERGE_TILE
+        own = acc[(acc >= t0) & (acc < i)]
+        if len(own) and X.near_merge(und_c[own], und_c[i], min_dist).any():
+            continue
+        earlier_only.append(i)
+        first_trip = acc[acc < t0][:MERGE_TILE]
+        if not X.near_merge(und_c[first_trip], und_c[i], min_dist).any():
+            second_trip_only.append(i)
+    last = (nc - 1) // MERGE_TILE * MERGE_TILE if nc else 0
+    return dict(accepted=acc, before_last=int((acc < last).sum()), earlier_only=earlier_only, second_trip_only=second_trip_only)
+
+
 # ---- the whole tracked frame: matcher.cpp:147-381, and sequences of them ----
 def track_step(oracle, img_prev, img_cur, depth_cur, rows, seed, prm=None, K=A.K, dist5=A.DIST5, scale=A.DEPTH_SCALE):
     """:147-211 on any pair of images (track_vo_ref.step on its own scene): dict(rows -- the tracked rows, COLUMNS --, pose (4, 4),
