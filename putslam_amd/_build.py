@@ -27,7 +27,7 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-D__HIP_PLATFORM_AMD__", "
 DEVICE_TU = "ps_capi.hip"
 DEVICE_DEPS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.h")))  # every header directly under csrc/
 HOST_TUS = ["ps_context.cpp", "ps_env.cpp", "ps_batch_queue.cpp"]
-HOST_DEPS = ["ps_internal.h", "ps_queue_hazard.h"]
+HOST_DEPS = ["ps_internal.h", "ps_queue_hazard.h", "ps_score_plan.h"]
 HEADER = os.path.join(ROOT, "include", "putslam_hip.h")
 
 

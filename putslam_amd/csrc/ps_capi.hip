@@ -27,32 +27,11 @@
 using namespace psdev;
 
 static_assert(kPsReorderMargin == kReorderMargin && kPsReorderTopMax == kReorderTopMax, "ps_internal.h mirrors ps_score_fast.h");
+static_assert(kPlanBlock == kBlock && kPlanPrefixFixed == kPrefixFixed && kPlanPrefixAdaptive == kPrefixAdaptive && kPlanStages == kStages,
+              "ps_score_plan.h mirrors ps_kernels.h / ps_score_fast.h");
 
 namespace {
 
-constexpr int kWidePairs = 16; // batches of at most this many pairs run kernel 2 with 1024-thread work-groups
-// Tuning constants of the staged scoring that were per-context knobs until round 5 (debug.list_r3 / list_g3 / reorder_c2div /
-// reorder_gran); every A/B since round 3 put their other values within 1 % of these (profiles/r03n, r04b), so they are constants:
-// work-groups the last stage's match range is split over; where the stages' ranges are cut (multiples of kReorderGran matches, the
-// second cut at 1 / kReorderC2div of the range); stage 3 runs one looping work-group per eight possible ones (list_groups).
-constexpr int kListRsplit3 = 4, kReorderGran = 64, kReorderC2div = 16;
-// where the staged scoring takes over from complete scoring (prepare_score): batch size in work units = pairs x
-// (ceil(H / 256) - 1) x frame capacity, threshold = base + perRow x frame capacity (profiles/r05c/staged_crossover.txt)
-struct StagedFrom {
-    double base, perRow;
-};
-constexpr StagedFrom kStagedFromEuclidFixed = {7.8e5, 250.0}, kStagedFromReprojFixed = {1.3e6, 500.0},
-                     kStagedFromEuclidAdaptive = {6.0e4, 0.0}, kStagedFromReprojAdaptive = {4.5e4, 0.0};
-// ... and where it does when the context is one of several launch chains that run side by side (option "side_by_side": the
-// chains of a PsBatchQueue, the lanes of the pipelined stream): the other chains' kernels fill the gaps between the staged form's
-// dependent, chip-underfilling launches, so what is left of its price is the work of the extra launches -- the crossover lies
-// 2 - 5 times lower (profiles/r06u/concurrent_crossover.txt: four chains, 500 ... 4000 keypoints x H = 1024 ... 16384 x 2 ... 64
-// pairs on the C++ demo's frames, 73 % inliers; profiles/r06u/bench_data_crossover.txt: bench.py's kind of data with 70 % / 40 % true
-// correspondences, where the staged form abandons less -- the constants are set by the latter: batches of 32 / 64 pairs of the
-// bench workload's shape gain 1.26 / 1.58 x with the reprojection error, 1.27 / 1.58 x with the Euclidean one)
-constexpr StagedFrom kStagedFromEuclidFixedSbs = {4.5e5, 75.0}, kStagedFromReprojFixedSbs = {3.0e5, 90.0},
-                     kStagedFromEuclidAdaptiveSbs = {2.4e4, 0.0}, kStagedFromReprojAdaptiveSbs = {2.4e4, 0.0};
-constexpr int kGenPlainFrom = 2; // complete scoring generates its models by a launch of their own from this many pairs on (Plan::genPlain)
 constexpr int kMfmaTT = 4;       // train tiles per wave of the MFMA matcher (ps_hamming_mfma<TT>, ps_matcher_mfma.h)
 
 // The matcher forms that merge with atomicMin start from an all-ones keys block (see PsContext::keysCleanPtr).
@@ -144,11 +123,6 @@ int effective_mode(int errorVersion)
     }
 }
 
-// Which kernel 3 scores a call: the value-exact ps_ransac_score (option "score" = 0, and the Mahalanobis error), else the
-// decision-exact Euclidean ps_ransac_score_euclid (errorVersion 0 / 4) or reprojection ps_ransac_score_fast (1 / 2).  Kernel 2
-// writes the records that family reads (rec_ptrs, PrepArgs::skipE / skipF).
-enum class Scoring { Value, Euclid, Reproj };
-
 struct Plan {
     int mode = 0;
     Scoring score = Scoring::Value; // (make_plan)
@@ -160,17 +134,14 @@ struct Plan {
     PrepArgs pa{};
     SelectArgs sa{};
     ModelArgs ma{};
-    int msplit = 1;   // work-groups the match range of kernel 3 is split over (prepare_score)
-    bool genSplit = false; // staged scoring: stage 0 as two launches (models, then the sweep)
-    bool genPlain = false; // complete scoring with a split match range, two pairs or more: the same two launches over [0, H)
-    bool reorder = false; // staged scoring: stages 1+ sweep the reordered hot record (ps_stage_reorder)
-    bool prune = false; // staged scoring: hypotheses [0, prefix) completely (msplit applies to it), the rest in pruned stages
+    ScoreDecision d;        // how the scoring stage runs (prepare_score; decide_score, ps_score_plan.h)
     bool bailWatch = false; // this staged call feeds the "nothing to gain" policy (PsContext::bailHost)
-    int bailSlot = 0;       // ... for this kind of call (PsContext::bailKinds)
-    int prefix = 0;     // 256 (fixed schedule) or 64 (adaptive schedules)
-    int lastStage = 0;  // staged scoring: 1 = ONE stage after the prefix (adaptive schedules without reordering), else kStages
-    bool big0 = false;  // Scoring::Reproj: stage 0 or the complete scoring runs the build for big launches (prepare_score)
+    int bailSlot = 0;       // ... for this kind of call (PsContext::bailTracker)
 };
+
+// directed roundings to float
+float round_up(double v) { float f = (float)v; return (double)f < v ? std::nextafterf(f, INFINITY) : f; }
+float round_down(double v) { float f = (float)v; return (double)f > v ? std::nextafterf(f, -INFINITY) : f; }
 
 int make_plan(PsContext *ctx, const PsRansacParams *prm, const PsRansacConfig *cfg, const float *K, int cap,
               int trainRange, Plan &pl)
@@ -209,16 +180,14 @@ int make_plan(PsContext *ctx, const PsRansacParams *prm, const PsRansacConfig *c
         fc.enabled = (bR >= 1e-12 && bR <= 1e12 && fm <= 1e6 && cm <= 1e6) ? 1 : 0; // false for NaN
         if (fc.enabled) {
             const double T = std::sqrt(bR);
-            auto up = [](double v) { float f = (float)v; return (double)f < v ? std::nextafterf(f, INFINITY) : f; };
-            auto down = [](double v) { float f = (float)v; return (double)f > v ? std::nextafterf(f, -INFINITY) : f; };
-            fc.fmaxK = up(fm);
-            fc.cmaxK = up(cm);
-            fc.thrUp = up(T * (1.0 + 1e-5));
-            fc.bIn0 = down(bR * (1.0 - 20.0 * 5.9604644775390625e-08));
-            fc.cIn = up(2.0 * std::sqrt(2.0) * T * (1.0 + 1e-5));
+            fc.fmaxK = round_up(fm);
+            fc.cmaxK = round_up(cm);
+            fc.thrUp = round_up(T * (1.0 + 1e-5));
+            fc.bIn0 = round_down(bR * (1.0 - 20.0 * 5.9604644775390625e-08));
+            fc.cIn = round_up(2.0 * std::sqrt(2.0) * T * (1.0 + 1e-5));
             const double c = std::sqrt(2.0) * (1.0 + 1e-5);
-            fc.thr2Up = up((double)fc.thrUp * (double)fc.thrUp);
-            fc.cHi = up((2.0 * c + c * c) * (double)fc.thrUp);
+            fc.thr2Up = round_up((double)fc.thrUp * (double)fc.thrUp);
+            fc.cHi = round_up((2.0 * c + c * c) * (double)fc.thrUp);
         }
     }
     // constants of the decision-exact Euclidean path (ps_score_euclid.h): the threshold in the root domain, pushed
@@ -231,15 +200,13 @@ int make_plan(PsContext *ctx, const PsRansacParams *prm, const PsRansacConfig *c
         ec.tbLo = ec.tbHi = 0.0f;
         if (ec.enabled) {
             const double u = 5.9604644775390625e-08;
-            auto up = [](double v) { float f = (float)v; return (double)f < v ? std::nextafterf(f, INFINITY) : f; };
-            auto down = [](double v) { float f = (float)v; return (double)f > v ? std::nextafterf(f, -INFINITY) : f; };
             if (pl.mode == PS_ADAPTIVE_ERROR) {
-                ec.tbLo = down(thr * (1.0 - 7.0 * u));
-                ec.tbHi = up(thr * (1.0 + 7.0 * u));
+                ec.tbLo = round_down(thr * (1.0 - 7.0 * u));
+                ec.tbHi = round_up(thr * (1.0 + 7.0 * u));
             } else {
                 const double Tb = std::sqrt((double)sq_bound_f32(thr));
-                ec.tbLo = down(Tb * (1.0 - 6.0 * u));
-                ec.tbHi = up(Tb * (1.0 + 6.0 * u));
+                ec.tbLo = round_down(Tb * (1.0 - 6.0 * u));
+                ec.tbHi = round_up(Tb * (1.0 + 6.0 * u));
             }
         }
     }
@@ -300,17 +267,6 @@ RecPtrs rec_ptrs(PsContext *ctx, Scoring score)
     return r;
 }
 
-int pick_split(long long blocksWithout, int maxSplit, int minChunkOf, int total)
-{
-    // Few pairs and many CUs: split the inner range so that ~8 workgroups per CU are in flight.
-    const long long want = 2048;
-    if (blocksWithout >= want) return 1;
-    long long s = (want + blocksWithout - 1) / (blocksWithout > 0 ? blocksWithout : 1);
-    if (s > maxSplit) s = maxSplit;
-    while (s > 1 && total / s < minChunkOf) --s;
-    return (int)(s < 1 ? 1 : s);
-}
-
 template <int MODE>
 void launch_score(PsContext *ctx, dim3 grid, const Plan &pl, int cap, int msplit)
 {
@@ -319,181 +275,92 @@ void launch_score(PsContext *ctx, dim3 grid, const Plan &pl, int cap, int msplit
                        (const float2 *)ctx->cmax.p, pl.ma, pl.sc, pl.H, cap, pl.minRun, msplit, (int32_t *)ctx->counts.p);
 }
 
-// launches of the reprojection kernels with more work-groups than this use the packed match record (ps_score_fast.h, BIG)
-unsigned big_limit(int mode) { return mode == PS_REPROJECTION_ERROR ? 1536u : 1280u; }
+// The options the scoring plan reads, as they stand now (ScoreOptions, ps_score_plan.h).
+ScoreOptions score_options(const PsContext *ctx)
+{
+    ScoreOptions o;
+    o.prune = ctx->prune; o.sideBySide = ctx->sideBySide; o.reorder = ctx->reorder; o.genSplit = ctx->genSplit;
+    o.singleRest = ctx->singleRest; o.pretest = ctx->pretest; o.listGroups2 = ctx->listGroups2; o.forcePrefix = ctx->forcePrefix;
+    o.forceMsplit = ctx->forceMsplit; o.modelRoomMiB = ctx->modelRoomMiB; o.bail = ctx->bail; o.reorderMargin = ctx->reorderMargin;
+    return o;
+}
 
-// Decisions of the scoring stage that the preceding kernels need to know: how the match range is split (kernel 2 then
-// clears the counts, instead of a memset launch), whether kernel 3 parks its models for kernel 4 and which records it reads.
+ScoreShape score_shape(const Plan &pl, int P, int cap, bool complete = false, bool adaptive = false)
+{
+    ScoreShape s;
+    s.P = P; s.cap = cap; s.H = pl.H; s.mode = pl.mode; s.score = pl.score; s.estimator = pl.sa.estimator;
+    s.complete = complete; s.adaptive = adaptive;
+    return s;
+}
+
+// The "nothing to gain" policy's side of a staged call of kind `key` (BailTracker, ps_score_plan.h, is the state machine; here its
+// counters: the device block, the mapped host mirror kernel 4 forwards them to).  Returns whether the call scores completely instead.
+bool bail_consult(PsContext *ctx, Plan &pl, const BailKey &key)
+{
+    if (!ctx->bailHost) {
+        const size_t nb = (size_t)BailTracker::kKinds * 2 * sizeof(unsigned);
+        if (hipHostMalloc((void **)&ctx->bailHost, nb, hipHostMallocMapped) == hipSuccess &&
+            hipHostGetDevicePointer((void **)&ctx->bailHostDev, ctx->bailHost, 0) == hipSuccess) {
+            memset(ctx->bailHost, 0, nb);
+            if (ensure(ctx, ctx->bailCnt, nb) == PS_OK) (void)hipMemsetAsync(ctx->bailCnt.p, 0, nb, ctx->stream);
+        } else {
+            (void)hipGetLastError();
+            ctx->bailHostDev = nullptr; // (no mapped memory here: the policy stays off)
+        }
+    }
+    if (!(ctx->bailHostDev && ctx->bailCnt.p)) return false;
+    BailTracker &t = ctx->bailTracker;
+    const volatile unsigned *host = (volatile unsigned *)ctx->bailHost;
+    bool recycled = false;
+    const int slot = t.find(key, recycled);
+    if (recycled) {
+        // (the slot's counters are monotonic: what its previous kind left there is simply "seen" -- once it HAS landed:
+        // a call of the previous kind may still be in flight, and counts arriving after the snapshot would read as an
+        // observation of the new kind.  Recycling is rare -- more than eight kinds alternating on one context -- and
+        // drains the stream first.)
+        (void)hipStreamSynchronize(ctx->stream);
+        t.adopt(slot, host[2 * slot], host[2 * slot + 1]);
+    }
+    ctx->hopeless = t.observe(slot, host[2 * slot], host[2 * slot + 1]);
+    const bool veto = t.veto(slot);
+    pl.bailWatch = !veto;
+    pl.bailSlot = slot;
+    ctx->bailSlot = slot;
+    return veto;
+}
+
+// Decisions of the scoring stage that the preceding kernels need to know (decide_score, ps_score_plan.h), and the arena blocks they ask for.
 // complete = true: every hypothesis is scored completely whatever the batch size (ps_debug_ransac_counts returns the counts
 // themselves: the staged scoring leaves lower bounds for abandoned hypotheses)
 int prepare_score(PsContext *ctx, Plan &pl, int P, int cap, bool complete = false, bool adaptive = false, const void *dataKey = nullptr)
 {
-    const int H = pl.H;
-    const int hb = (H + kBlock - 1) / kBlock;
-    // pruned scoring: worth its second launch when the hypotheses beyond the prefix fill the chip by themselves
-    const bool prunable = pl.score != Scoring::Value;
-    // (the later stages read the models back from HBM, 48 B per hypothesis: ps_score_fast.h)
-    const size_t mbytes = (size_t)P * H * 12 * sizeof(float);
-    pl.prefix = pl.sa.estimator == PS_EST_FIXED ? kPrefixFixed : kPrefixAdaptive;
-    if (ctx->forcePrefix > 0 && pl.sa.estimator == PS_EST_FIXED) pl.prefix = ctx->forcePrefix; // (tuning knob)
-    // (the staged form is six or seven dependent launches, 0.23 ms at the least with the reprojection kernels and 0.08 ms with
-    // the Euclidean ones: it pays from about 48 / 16 pairs of H = 4096 on, profiles/r03p/small_batches.txt)
-    // (adaptive schedules: the trip limit the prefix leaves cuts most of the work whatever the batch size)
-    // Cost model (round 5): the staged form trades six or seven dependent launches for the evaluations it abandons, and an
-    // evaluation's worth of work is a (hypothesis, match) pair -- so the batch is sized in work-groups of 256 hypotheses beyond the
-    // first one x rows of the frame capacity (matches <= keypoints), and the crossover is where (1 - share of evaluations left)
-    // of that pays for the launches: base + perRow x capacity, fitted on profiles/r05c/staged_crossover.txt over 500 ... 4000
-    // keypoints x H = 1024 ... 16384 (rounds 3 - 4 counted work-groups only, with constants from 2000 keypoints that DESIGN
-    // section 8 knew to be 2 - 14 % off on either side; adaptive schedules gain from far smaller batches than they were given).
-    // Option "prune" = 2 takes the staged form whenever the kernels have it (tests; A/B).
-    const double units = (double)P * (double)(hb - 1) * (double)cap;
-    const StagedFrom sf = pl.score == Scoring::Euclid ? (pl.sa.estimator == PS_EST_FIXED ? kStagedFromEuclidFixed : kStagedFromEuclidAdaptive)
-                                                      : (pl.sa.estimator == PS_EST_FIXED ? kStagedFromReprojFixed : kStagedFromReprojAdaptive);
-    double stagedFrom = sf.base + sf.perRow * (double)cap;
-    if (ctx->sideBySide >= 2) {
-        const StagedFrom sb = pl.score == Scoring::Euclid ? (pl.sa.estimator == PS_EST_FIXED ? kStagedFromEuclidFixedSbs : kStagedFromEuclidAdaptiveSbs)
-                                                          : (pl.sa.estimator == PS_EST_FIXED ? kStagedFromReprojFixedSbs : kStagedFromReprojAdaptiveSbs);
-        const double sbs = sb.base + sb.perRow * (double)cap;
-        // (two chains hide half of one another's gaps: half way between the two crossovers, on the logarithmic scale)
-        stagedFrom = ctx->sideBySide >= 3 ? sbs : std::sqrt(sbs * stagedFrom);
-    }
-    pl.prune = !complete && ctx->prune != 0 && prunable && H > kPrefixFixed && (ctx->prune == 2 || units >= stagedFrom);
+    const ScoreOptions opts = score_options(ctx);
+    const ScoreShape shape = score_shape(pl, P, cap, complete, adaptive);
+    bool staged = wants_staged(shape, opts);
     pl.bailWatch = false;
     pl.bailSlot = 0;
-    const bool willReorder = ctx->reorder == 1 || (ctx->reorder == 2 && pl.sa.estimator == PS_EST_FIXED);
-    if (adaptive && pl.prune && willReorder && ctx->bail != 0 && pl.score == Scoring::Euclid && pl.sa.estimator == PS_EST_FIXED) {
-        if (!ctx->bailHost) {
-            const size_t nb = (size_t)PsContext::kBailKinds * 2 * sizeof(unsigned);
-            if (hipHostMalloc((void **)&ctx->bailHost, nb, hipHostMallocMapped) == hipSuccess &&
-                hipHostGetDevicePointer((void **)&ctx->bailHostDev, ctx->bailHost, 0) == hipSuccess) {
-                memset(ctx->bailHost, 0, nb);
-                if (ensure(ctx, ctx->bailCnt, nb) == PS_OK) (void)hipMemsetAsync(ctx->bailCnt.p, 0, nb, ctx->stream);
-            } else {
-                (void)hipGetLastError();
-                ctx->bailHostDev = nullptr; // (no mapped memory here: the policy stays off)
-            }
-        }
-        if (ctx->bailHostDev && ctx->bailCnt.p) {
-            // the kind of this call: its own slot (a new kind takes the least recently used one and starts from "staged")
-            int pclass = 0;
-            for (int q = P; q > 1; q >>= 1) ++pclass;
-            int slot = -1, lru = 0;
-            for (int i = 0; i < PsContext::kBailKinds; ++i) {
-                const PsContext::BailKind &b = ctx->bailKinds[i];
-                if (b.mode == pl.mode && b.estimator == pl.sa.estimator && b.H == H && b.pclass == pclass && b.cap == cap && b.frames == dataKey) slot = i;
-                if (b.used < ctx->bailKinds[lru].used) lru = i;
-            }
-            if (slot < 0) {
-                slot = lru;
-                PsContext::BailKind &b = ctx->bailKinds[slot];
-                b.mode = pl.mode; b.estimator = pl.sa.estimator; b.H = H; b.pclass = pclass; b.cap = cap; b.frames = dataKey;
-                b.hopeless = 0;
-                b.calls = 0;
-                // (the slot's counters are monotonic: what its previous kind left there is simply "seen" -- once it HAS landed:
-                // a call of the previous kind may still be in flight, and counts arriving after the snapshot would read as an
-                // observation of the new kind.  Recycling is rare -- more than eight kinds alternating on one context -- and
-                // drains the stream first.)
-                (void)hipStreamSynchronize(ctx->stream);
-                b.seen[0] = ((volatile unsigned *)ctx->bailHost)[2 * slot];
-                b.seen[1] = ((volatile unsigned *)ctx->bailHost)[2 * slot + 1];
-            }
-            PsContext::BailKind &b = ctx->bailKinds[slot];
-            b.used = ++ctx->bailClock;
-            const unsigned s0 = ((volatile unsigned *)ctx->bailHost)[2 * slot], s1 = ((volatile unsigned *)ctx->bailHost)[2 * slot + 1];
-            if (s0 != b.seen[0]) { // a new observation of this kind has landed
-                const unsigned d0 = s0 - b.seen[0], d1 = s1 - b.seen[1];
-                const int was = b.hopeless;
-                b.hopeless = (2ull * d1 > d0) ? 1 : 0;
-                if (b.hopeless != was) b.calls = 0;
-                b.seen[0] = s0;
-                b.seen[1] = s1;
-            }
-            if (b.hopeless && (++b.calls & 15) != 0)
-                pl.prune = false; // complete scoring while nothing can be abandoned; every 16th call looks again
-            pl.bailWatch = pl.prune;
-            pl.bailSlot = slot;
-            ctx->bailSlot = slot;
-            ctx->hopeless = b.hopeless;
-        }
-    }
-    // Complete scoring of a batch under a long cap is the reference's own worst case times P (850 000 iterations over every
-    // match, USAC_wrapper.cpp:70): minutes of GPU time behind an asynchronous call.  It is refused -- here, before the counts
-    // block (4 bytes per pair and hypothesis: hundreds of GB for such a batch) is asked for; the staged scoring (option "prune",
-    // the default) takes the same batch in milliseconds whenever the schedules end early.
-    if (adaptive && !pl.prune && (double)P * (double)H * (double)cap > 2.0e14)
-        return fail(ctx, PS_ERR_UNSUPPORTED, "complete scoring of this batch (pairs x hypotheses x matches > 2e14) would run for minutes: "
-                                             "leave the staged scoring on (option \"prune\") or pass fewer pairs per call");
-    PS_ENSURE(ctx->counts, (size_t)P * H * sizeof(int32_t));
-    pl.msplit = pick_split((long long)P * (pl.prune ? 1 : hb), 32, 64, cap);
-    pl.genSplit = pl.prune && ctx->genSplit != 0 && pl.msplit > 1;
-    if (pl.genSplit) pl.msplit = pl.msplit * 2 < 32 ? pl.msplit * 2 : 32; // (the parts no longer repeat the prologue)
-    if (ctx->forceMsplit > 0) pl.msplit = ctx->forceMsplit;
-    if (pl.msplit <= 1) pl.genSplit = false;
-    pl.pa.zeroCounts = pl.msplit > 1 ? (int32_t *)ctx->counts.p : nullptr;
-    pl.pa.zeroH = pl.prune ? pl.prefix : H;
-    pl.pa.zeroStride = H;
-    pl.ma.models = nullptr;
-    pl.ma.modelH = H;
-    // adaptive schedules without reordering: ONE stage after the prefix (all matches, hypotheses below the trip limit only)
-    pl.lastStage = (pl.sa.estimator != PS_EST_FIXED && !willReorder && ctx->singleRest != 0) ? 1 : kStages;
-    if (pl.prune) {
-        // Parked models in proportion to the work, not to the cap: under a long cap (USAC's 850 000, USAC_wrapper.cpp:70) the
-        // schedules end after a handful of iterations (USAC.h:944-971), and 48 bytes per pair and cap entry would be 20 GB for
-        // 499 pairs.  Only the leading hypotheses get a slot (256 MB under the adaptive schedules, 2 GiB under the fixed one,
-        // whose stages do read the models back); a hypothesis beyond is swept in one piece by stage 1 and, if it wins, rebuilt
-        // by kernel 4.
-        const size_t room = ctx->modelRoomMiB > 0 ? ((size_t)ctx->modelRoomMiB << 20)
-                                                  : (pl.sa.estimator == PS_EST_FIXED ? ((size_t)2 << 30) : ((size_t)256 << 20));
-        if (mbytes > room) {
-            long long fit = (long long)(room / ((size_t)P * 12 * sizeof(float))) & ~(long long)(kBlock - 1);
-            pl.ma.modelH = (int)(fit < kPrefixFixed ? kPrefixFixed : fit);
-        }
-    }
-    if ((P <= kWidePairs && mbytes <= ((size_t)64 << 20)) || pl.prune) {
-        PS_ENSURE(ctx->models, (size_t)P * pl.ma.modelH * 12 * sizeof(float));
-        pl.ma.models = (float *)ctx->models.p;
-    }
-    // Complete scoring with the match range split over msplit work-groups repeats the sample -> SVD chain in every part (16
-    // pairs, H = 4096, errorVersion 1: 23 M of the launch's 45 M instructions).  From two pairs on the models are generated
-    // once by a launch of their own, as stage 0 of the staged scoring does, and the sweep reads them back: 4 to 15 % of the
-    // call for 2 ... 48 pairs (profiles/r04h/ab_gen_plain.txt).  A single pair keeps one launch: the chain's latency is all
-    // there is, and a second launch costs 3 - 5 us more than it saves.
-    pl.genPlain = false;
-    if (!pl.prune && pl.score != Scoring::Value && ctx->genSplit != 0 && pl.msplit > 1 && P >= kGenPlainFrom && mbytes <= ((size_t)1 << 30)) {
-        PS_ENSURE(ctx->models, mbytes);
-        pl.ma.models = (float *)ctx->models.p;
-        PS_ENSURE(ctx->validMask, (size_t)P * ((H + 63) / 64) * sizeof(unsigned long long));
-        pl.genPlain = true;
-    }
-    pl.pa.zeroSurvA = pl.pa.zeroSurvB = nullptr;
-    // which record form of the reprojection kernels the launches of this call read (kernel 2 writes only those: 16 + 40 bytes
-    // per match otherwise): the packed form F for launches that fill the chip (the build for big launches, BIG) and every stage
-    // after the prefix, the three-record form (A, B, E) for small ones
-    pl.big0 = (unsigned)pl.msplit * (unsigned)P * (pl.prune ? 1u : (unsigned)hb) > big_limit(pl.mode);
-    pl.pa.skipF = !(pl.score == Scoring::Reproj && (pl.prune || pl.big0));
-    pl.pa.skipE = !(pl.score == Scoring::Reproj && !pl.big0);
-    if (pl.prune) {
-        if (pl.lastStage > 1) { // (only hypotheses with a model slot are ever listed)
-            PS_ENSURE(ctx->survA, (size_t)P * pl.ma.modelH * sizeof(int32_t));
-            PS_ENSURE(ctx->survB, (size_t)P * pl.ma.modelH * sizeof(int32_t));
-        }
-        PS_ENSURE(ctx->survN, (size_t)2 * P * sizeof(int32_t));
-        if (pl.genSplit) PS_ENSURE(ctx->validMask, (size_t)P * ((pl.prefix + 63) / 64) * sizeof(unsigned long long));
-        pl.reorder = ctx->reorder == 1 || (ctx->reorder == 2 && pl.sa.estimator == PS_EST_FIXED);
-        if (pl.reorder) {
-            const size_t n = (size_t)P * cap;
-            PS_ENSURE(ctx->recF2, n * 40 > (size_t)P * ((cap + 1) / 2) * 64 ? n * 40 : (size_t)P * ((cap + 1) / 2) * 64);
-            PS_ENSURE(ctx->permBuf, n * sizeof(int32_t));
-            PS_ENSURE(ctx->prefInfo, (size_t)4 * P * sizeof(int32_t));
-            PS_ENSURE(ctx->frontRec, (size_t)P * ((cap + 1) / 2) * 10 * sizeof(float));
-        }
-        pl.pa.zeroSurvA = (int32_t *)ctx->survN.p;       // cleared by kernel 2, one counter per pair and stage
-        pl.pa.zeroSurvB = (int32_t *)ctx->survN.p + P;
-    }
-    ctx->lastModelH = pl.ma.models ? pl.ma.modelH : 0;
-    ctx->stagedP = pl.prune ? P : 0;
-    ctx->stagedCap = pl.prune ? cap : 0;
-    ctx->reorderedP = (pl.prune && pl.reorder) ? P : 0;
+    if (bail_applies(shape, opts, staged) && bail_consult(ctx, pl, bail_key(shape, dataKey))) staged = false;
+    const ScoreDecision &d = pl.d = decide_score(shape, opts, staged);
+    if (d.status != PS_OK)
+        return fail(ctx, d.status, "complete scoring of this batch (pairs x hypotheses x matches > 2e14) would run for minutes: "
+                                   "leave the staged scoring on (option \"prune\") or pass fewer pairs per call");
+    Buf *const blocks[kScoreBlocks] = {&ctx->counts, &ctx->models, &ctx->survA, &ctx->survB, &ctx->survN,
+                                       &ctx->validMask, &ctx->recF2, &ctx->permBuf, &ctx->prefInfo, &ctx->frontRec}; // (ScoreBlock's order)
+    for (int i = 0; i < kScoreBlocks; ++i)
+        if (d.bytes[i]) PS_ENSURE(*blocks[i], d.bytes[i]);
+    pl.pa.zeroCounts = d.zeroCounts ? (int32_t *)ctx->counts.p : nullptr;
+    pl.pa.zeroH = d.zeroH;
+    pl.pa.zeroStride = pl.H;
+    pl.pa.zeroSurvA = d.staged ? (int32_t *)ctx->survN.p : nullptr; // cleared by kernel 2, one counter per pair and stage
+    pl.pa.zeroSurvB = d.staged ? (int32_t *)ctx->survN.p + P : nullptr;
+    pl.pa.skipE = d.skipE;
+    pl.pa.skipF = d.skipF;
+    pl.ma.models = d.parkModels ? (float *)ctx->models.p : nullptr;
+    pl.ma.modelH = d.modelH;
+    ctx->lastModelH = d.parkModels ? d.modelH : 0;
+    ctx->stagedP = d.staged ? P : 0;
+    ctx->stagedCap = d.staged ? cap : 0;
+    ctx->reorderedP = d.reorder ? P : 0;
     return PS_OK;
 }
 
@@ -536,11 +403,11 @@ template <int MODE> struct ReprojK3 {
                            msplit, (int32_t *)ctx->counts.p, c.dbg);
     }
     // more work-groups than fit at once (256 CUs x 6): the build for big launches (ps_score_fast.h) -- for stage 0 and the
-    // complete scoring as prepare_score decided (Plan::big0), always for the stages after the prefix
+    // complete scoring as prepare_score decided (ScoreDecision::big0), always for the stages after the prefix
     template <int KIND, bool LOOP> void operator()(Kind<KIND, LOOP>, const StageArgs &st, unsigned groups, int msplit) const
     {
         if constexpr (KIND == 0) {
-            if (!c.pl.big0) return launch<false, KIND, LOOP>(st, groups, msplit);
+            if (!c.pl.d.big0) return launch<false, KIND, LOOP>(st, groups, msplit);
         }
         launch<true, KIND, LOOP>(st, groups, msplit);
     }
@@ -553,101 +420,46 @@ template <int MODE, class K3> void score_schedule(const K3Call &c, const K3 &k3)
 {
     PsContext *ctx = c.ctx;
     const Plan &pl = c.pl;
+    const ScoreDecision &d = pl.d;
     const int P = c.P;
-    auto groups = [](int hCount) { return (unsigned)((hCount + kBlock - 1) / kBlock); };
-    if (!pl.prune) {
-        StageArgs st{}; // the plain launch: every hypothesis of [0, H) completely
-        st.hCount = pl.H;
-        if (pl.genPlain) { // the same as two launches (Plan::genPlain): models, then the sweep
-            st.validMask = (unsigned long long *)ctx->validMask.p;
-            st.genOnly = 1;
-            k3(Kind<0>{}, st, groups(pl.H), 1);
-            st.genOnly = 0;
-        }
-        k3(Kind<0>{}, st, groups(pl.H), pl.msplit);
-        return;
-    }
-    // stages 2+: work-groups per pair (they loop over longer lists; after the reordered stage 1 few hypotheses are left)
-    auto list_groups = [&](int stage) {
-        const int listed = (pl.H < pl.ma.modelH ? pl.H : pl.ma.modelH) - pl.prefix; // hypotheses that can be on a survivor list
-        const int all = ((listed > 0 ? listed : 1) + kBlock - 1) / kBlock;
-        // (stage 3 by default: one looping group per eight possible ones -- 1 for H = 4096, where 21 of 3840 hypotheses per
-        // pair are left, 48 for the stress configuration's H = 100 000, which one group swept in 4.3 ms instead of 1.0)
-        const int auto3 = all / 8 > 1 ? all / 8 : 1;
-        // (stage 2 by default: every possible group with the reprojection kernels -- a fifth of the hypotheses survives stage 1
-        // there --, two looping groups with the Euclidean ones, whose counts saturate: hardly anything survives and the
-        // launch is mostly work-groups that find nothing, 2 - 3 % of the step at every inlier share tried,
-        // profiles/r04b/ab_euclid_list_groups.txt)
-        const int auto2 = pl.score == Scoring::Euclid ? (all / 8 > 2 ? all / 8 : 2) : 64; // (many hypotheses: lists can be long)
-        const int want = pl.reorder ? (stage == 2 ? (ctx->listGroups2 > 0 ? ctx->listGroups2 : auto2)
-                                                  : auto3) : all;
-        return want < all ? want : all;
-    };
-    // the last stage: work-groups its match range is split over (their counts add up in counts[]; a short survivor list
-    // swept by one wavefront per SIMD pays the full latency of every record load, 0.25 us per match)
-    auto list_rsplit = [&](int stage) { return (pl.reorder && stage == kStages) ? kListRsplit3 : 1; };
-    // stage 1's one-direction pre-test on the far-off front of the reordered record: the reprojection metrics (ps_score_fast.h)
-    const bool usePretest = pl.reorder && ctx->pretest != 0 &&
-                            (pl.mode == PS_EUCLIDEAN_AND_REPROJECTION_ERROR || pl.mode == PS_REPROJECTION_ERROR);
-    // Stage 1 of an adaptive schedule with a long cap (USAC's 850 000 = 3320 blocks of 256 hypotheses per pair, of which the
-    // trip limit leaves a handful): one work-group per block is hundreds of thousands of work-groups that look at the limit and
-    // leave -- 0.9 ms per 210 pairs.  From 64 blocks per pair on a fixed number of work-groups per pair walks the blocks and
-    // stops at the first one beyond the limit (enough of them to fill the chip when the limit does stay at the cap).
-    const int blocks1 = (pl.H - pl.prefix + kBlock - 1) / kBlock;
-    int loopGroups = 0;
-    if (pl.sa.estimator != PS_EST_FIXED && blocks1 > 64) {
-        // (64 per pair at the least until round 5: 32 000 work-groups per 499 pairs that read the limit and leave, a third of the
-        // scoring step under USAC's cap; 4096 in all still fill the chip when the limits do stay at the cap)
-        loopGroups = (4096 + P - 1) / P;
-        loopGroups = loopGroups < 4 ? 4 : loopGroups;
-        loopGroups = loopGroups > blocks1 ? blocks1 : loopGroups;
-    }
-    // stage_args(i) describes launch i
-    auto stage_args = [&](int stage) {
+    const ScoreOptions opts = score_options(ctx);
+    const StageSchedule sch = stage_schedule(score_shape(pl, P, c.cap), opts, d);
+    int32_t *const list[3] = {nullptr, (int32_t *)ctx->survA.p, (int32_t *)ctx->survB.p};
+    int32_t *const count[3] = {nullptr, (int32_t *)ctx->survN.p, (int32_t *)ctx->survN.p + P};
+    for (int i = 0; i < sch.n; ++i) {
+        const StageLaunch &l = sch.launch[i];
+        if (i == sch.reorderBefore)
+            hipLaunchKernelGGL(ps_stage_reorder<MODE>, dim3((unsigned)P), dim3(kBlock), 0, ctx->stream, (const float4 *)ctx->recA.p,
+                               (const float4 *)ctx->recB.p, (const float4 *)ctx->recC.p, (const float2 *)ctx->recF.p,
+                               (const int32_t *)ctx->mvalid.p, pl.ma, pl.sc, pl.sa, d.prefix, ctx->reorderTop,
+                               (ctx->bail != 0 && pl.score == Scoring::Euclid) ? 64 : 0, ctx->reorderMargin, pl.H, c.cap, pl.minRun,
+                               (const int32_t *)ctx->counts.p, (float2 *)ctx->recF2.p, (int32_t *)ctx->permBuf.p,
+                               (int32_t *)ctx->prefInfo.p, sch.pretest ? (float2 *)ctx->frontRec.p : (float2 *)nullptr,
+                               pl.bailWatch ? (unsigned *)ctx->bailCnt.p + 2 * pl.bailSlot : (unsigned *)nullptr);
         StageArgs st{};
-        st.stage = stage;
-        st.hBase = stage == 0 ? 0 : pl.prefix;
-        st.hCount = stage == 0 ? pl.prefix : pl.H - pl.prefix;
-        if (stage >= 2) st.hCount = list_groups(stage) * kBlock; // work-groups per pair that sweep the survivor list
-        int32_t *nA = (int32_t *)ctx->survN.p, *nB = nA + P;
-        if (stage == 1) { st.listOut = (int32_t *)ctx->survA.p; st.countOut = nA; }
-        if (stage == 2) { st.listIn = (const int32_t *)ctx->survA.p; st.countIn = nA; st.listOut = (int32_t *)ctx->survB.p; st.countOut = nB; }
-        if (stage == 3) { st.listIn = (const int32_t *)ctx->survB.p; st.countIn = nB; }
-        if (stage >= 1 && pl.reorder) st.perm = (const int32_t *)ctx->permBuf.p;
-        if (stage >= 1 && pl.reorder) st.prefInfo = (const int32_t *)ctx->prefInfo.p;
-        if (stage == 1 && usePretest) st.frontRec = (const float2 *)ctx->frontRec.p;
-        st.listStride = pl.ma.modelH;
-        st.loopGroups = stage == 1 ? loopGroups : 0;
-        st.single = pl.lastStage == 1 ? 1 : 0;
-        st.margin = ctx->reorderMargin;
-        st.gran = kReorderGran;
-        st.c2div = kReorderC2div;
-        return st;
-    };
-    // stage 0 as two launches: models + validity, then the sweep reading them back
-    auto stage0_args = [&](bool gen) {
-        StageArgs st = stage_args(0);
-        if (pl.genSplit) {
-            st.validMask = (unsigned long long *)ctx->validMask.p;
-            st.genOnly = gen ? 1 : 0;
+        st.stage = l.stage;
+        st.hBase = l.hBase;
+        st.hCount = l.hCount;
+        st.genOnly = l.genOnly;
+        st.listIn = list[l.listIn]; st.countIn = count[l.listIn];
+        st.listOut = list[l.listOut]; st.countOut = count[l.listOut];
+        if (l.validMask) st.validMask = (unsigned long long *)ctx->validMask.p;
+        if (l.perm) st.perm = (const int32_t *)ctx->permBuf.p;
+        if (l.perm) st.prefInfo = (const int32_t *)ctx->prefInfo.p;
+        if (l.frontRec) st.frontRec = (const float2 *)ctx->frontRec.p;
+        st.loopGroups = l.loopGroups;
+        st.single = l.single;
+        if (d.staged) {
+            st.listStride = d.modelH;
+            st.margin = opts.reorderMargin;
+            st.gran = kReorderGran;
+            st.c2div = kReorderC2div;
         }
-        return st;
-    };
-    if (pl.genSplit) k3(Kind<0>{}, stage0_args(true), groups(pl.prefix), 1);
-    k3(Kind<0>{}, stage0_args(false), groups(pl.prefix), pl.msplit);
-    if (pl.reorder)
-        hipLaunchKernelGGL(ps_stage_reorder<MODE>, dim3((unsigned)P), dim3(kBlock), 0, ctx->stream, (const float4 *)ctx->recA.p,
-                           (const float4 *)ctx->recB.p, (const float4 *)ctx->recC.p, (const float2 *)ctx->recF.p,
-                           (const int32_t *)ctx->mvalid.p, pl.ma, pl.sc, pl.sa, pl.prefix, ctx->reorderTop,
-                           (ctx->bail != 0 && pl.score == Scoring::Euclid) ? 64 : 0, ctx->reorderMargin, pl.H, c.cap, pl.minRun,
-                           (const int32_t *)ctx->counts.p, (float2 *)ctx->recF2.p, (int32_t *)ctx->permBuf.p,
-                           (int32_t *)ctx->prefInfo.p, usePretest ? (float2 *)ctx->frontRec.p : (float2 *)nullptr,
-                           pl.bailWatch ? (unsigned *)ctx->bailCnt.p + 2 * pl.bailSlot : (unsigned *)nullptr);
-    if (loopGroups > 0)
-        k3(Kind<1, true>{}, stage_args(1), (unsigned)loopGroups, 1);
-    else
-        k3(Kind<1>{}, stage_args(1), groups(pl.H - pl.prefix), 1);
-    for (int sg = 2; sg <= pl.lastStage; ++sg) k3(Kind<2>{}, stage_args(sg), (unsigned)list_groups(sg), list_rsplit(sg));
+        if (l.kind == 0) k3(Kind<0>{}, st, l.groups, l.msplit);
+        else if (l.kind == 2) k3(Kind<2>{}, st, l.groups, l.msplit);
+        else if (l.loop) k3(Kind<1, true>{}, st, l.groups, l.msplit);
+        else k3(Kind<1>{}, st, l.groups, l.msplit);
+    }
 }
 
 // Kernel 3 of one call under error MODE: the family the plan chose (Plan::score).
@@ -660,8 +472,8 @@ template <int MODE> void launch_k3(const K3Call &c)
         if (c.pl.score == Scoring::Reproj) return score_schedule<MODE>(c, ReprojK3<MODE>{c});
     }
     // counts were cleared by kernel 2 when the range is split (prepare_score)
-    launch_score<MODE>(c.ctx, dim3((unsigned)((c.pl.H + kBlock - 1) / kBlock) * (unsigned)c.pl.msplit * (unsigned)c.P), c.pl, c.cap,
-                       c.pl.msplit);
+    launch_score<MODE>(c.ctx, dim3((unsigned)((c.pl.H + kBlock - 1) / kBlock) * (unsigned)c.pl.d.msplit * (unsigned)c.P), c.pl, c.cap,
+                       c.pl.d.msplit);
 }
 
 // Kernels 3 + 4 over records already in the arena.
@@ -678,7 +490,7 @@ int run_ransac_stage(PsContext *ctx, const Plan &pl, int P, int cap, const PsDMa
         PS_HIP(hipMemsetAsync(ctx->dbgCnt.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
         dbg = (unsigned long long *)ctx->dbgCnt.p;
     }
-    const K3Call c{ctx, pl, P, cap, (const float2 *)(pl.reorder ? ctx->recF2.p : ctx->recF.p), dbg};
+    const K3Call c{ctx, pl, P, cap, (const float2 *)(pl.d.reorder ? ctx->recF2.p : ctx->recF.p), dbg};
     switch (pl.mode) {
     case PS_EUCLIDEAN_ERROR: launch_k3<PS_EUCLIDEAN_ERROR>(c); break;
     case PS_REPROJECTION_ERROR: launch_k3<PS_REPROJECTION_ERROR>(c); break;
@@ -703,8 +515,8 @@ int run_ransac_stage(PsContext *ctx, const Plan &pl, int P, int cap, const PsDMa
                        (const int4 *)ctx->recD.p, (const int32_t *)ctx->mvalid.p, (const int32_t *)ctx->counts.p,
                        dMatches, dNumMatches, matchStride, pl.ma, pl.sc, sa, (int32_t *)ctx->idxList.p, dPose,
                        dMask, dStats, ctx->stampsOn ? (unsigned long long *)ctx->stamps.p : (unsigned long long *)nullptr,
-                       (pl.bailWatch && pl.reorder) ? (const unsigned *)ctx->bailCnt.p + 2 * pl.bailSlot : (const unsigned *)nullptr,
-                       (pl.bailWatch && pl.reorder) ? ctx->bailHostDev + 2 * pl.bailSlot : (unsigned *)nullptr);
+                       (pl.bailWatch && pl.d.reorder) ? (const unsigned *)ctx->bailCnt.p + 2 * pl.bailSlot : (const unsigned *)nullptr,
+                       (pl.bailWatch && pl.d.reorder) ? ctx->bailHostDev + 2 * pl.bailSlot : (unsigned *)nullptr);
     tick(ctx, slot0 + 1, true);
     PS_HIP(hipGetLastError());
     return PS_OK;
@@ -719,7 +531,7 @@ int ensure_records(PsContext *ctx, size_t P, size_t cap)
     PS_ENSURE(ctx->recD, n * 16);
     PS_ENSURE(ctx->recE, n * 16);
     // 40 B per match (reprojection kernels) or up to 64 B per match pair (Euclidean kernel, ps_score_euclid.h)
-    PS_ENSURE(ctx->recF, n * 40 > P * ((cap + 1) / 2) * 64 ? n * 40 : P * ((cap + 1) / 2) * 64);
+    PS_ENSURE(ctx->recF, record_f_bytes(P, cap));
 #ifdef PS_STREAM_DIAG
     static const bool shadow = std::getenv("PUTSLAM_HIP_DIAG_SHADOW_RECORDS") != nullptr && std::atoi(std::getenv("PUTSLAM_HIP_DIAG_SHADOW_RECORDS")) != 0;
     if (shadow) PS_ENSURE(ctx->recShadow, n * 7 * 16);

@@ -309,7 +309,7 @@ int ps_context_set_option(PsContext *ctx, const char *name, int value)
     if (!option_value_ok(*o, value)) return fail(ctx, PS_ERR_BAD_ARG, o->what);
     ctx->*(o->field) = value;
     if (strcmp(name, "bail") == 0) { // (setting the option also forgets what the policy has observed: every kind starts staged)
-        for (PsContext::BailKind &b : ctx->bailKinds) b = PsContext::BailKind();
+        ctx->bailTracker.reset();
         ctx->hopeless = 0;
         ctx->bailSlot = -1;
     }

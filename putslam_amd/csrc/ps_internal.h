@@ -4,6 +4,7 @@
 // The library is ONE device translation unit (ps_capi.hip and the headers it includes: the kernels, the plan and every launch) and host-only ones compiled
 // as plain C++ (ps_context.cpp: context, scratch arena, option table, stop-table builders, timing record; ps_batch_queue.cpp;
 // ps_env.cpp).  A change to the option table or to the queue recompiles in a second, not with the kernels.
+// ps_score_plan.h: the scoring step's plan -- every decision of prepare_score / score_schedule (ps_capi.hip) --, pure, run on a CPU by the tests.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "putslam_hip.h"
+#include "ps_score_plan.h"
 
 struct Buf {
     void *p = nullptr;
@@ -136,19 +138,10 @@ struct PsContext {
     // kinds at a time: a context that alternates a mostly failing batch (loop-closure candidates) with good VO batches keeps
     // the staged form for the good ones (round 4 kept ONE flag per context: ADVICE round 4).  Adaptive schedules never drop the
     // staged form: under a long cap complete scoring is the minutes-long path.
-    struct BailKind {
-        int mode = -1, estimator = 0, H = 0, pclass = 0, cap = 0;
-        const void *frames = nullptr;
-        unsigned seen[2] = {0, 0};
-        int hopeless = 0, calls = 0;
-        unsigned long long used = 0; // (least recently used slot is recycled)
-    };
-    static constexpr int kBailKinds = 8;
-    BailKind bailKinds[kBailKinds];
-    unsigned long long bailClock = 0;
+    BailTracker bailTracker;      // (ps_score_plan.h: the state machine; the counters below are prepare_score's to read)
     int bailSlot = -1;            // slot of the last call the policy looked at
-    Buf bailCnt;                  // device: [kBailKinds]{pairs replayed, pairs with nothing to gain}, monotonic per slot
-    unsigned *bailHost = nullptr; // mapped host mirror [kBailKinds][2]
+    Buf bailCnt;                  // device: [BailTracker::kKinds]{pairs replayed, pairs with nothing to gain}, monotonic per slot
+    unsigned *bailHost = nullptr; // mapped host mirror [BailTracker::kKinds][2]
     unsigned *bailHostDev = nullptr;
     int hopeless = 0;             // state of the last call's kind (option "hopeless", read only)
     // The keys block is all-ones at rest: kernel 2 puts kNoKey back into every entry it reads, so the matcher forms that merge

@@ -5,12 +5,18 @@ its count, iterations run, inlier mask, pose bytes, ratios -- must equal both th
 three schedules, good and bad data, and batches large enough for the pruned launch to be used -- with the stages sweeping
 the matches in the reordered record (ps_stage_reorder: what the prefix's best hypotheses reject first) and in the original
 order."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from putslam_amd import api, synth
 from putslam_amd._abi import (ADAPTIVE_ERROR, EST_FIXED, EST_RANSAC, EST_USAC, EUCLIDEAN_AND_REPROJECTION_ERROR,
                               EUCLIDEAN_ERROR, REPROJECTION_ERROR, TUM_FR1_K, default_ransac_params, make_config)
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from score_plan_rows import COST_MODEL_ROWS, COST_MODEL_SBS_ROWS  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -440,13 +446,7 @@ def test_batch_under_the_reference_usac_cap_in_one_call(oracle):
             assert x == y or (np.isnan(x) and np.isnan(y)), (p, f, x, y)
 
 
-@pytest.mark.parametrize("mode,est,H,kpts,below,above", [
-    # threshold = base + perRow x capacity in units of pairs x (ceil(H / 256) - 1) x capacity (ps_capi.hip: kStagedFrom*)
-    (EUCLIDEAN_ERROR, EST_FIXED, 4096, 500, 100, 140),       # 7.8e5 + 250 x 500 = 9.05e5: 121 pairs
-    (REPROJECTION_ERROR, EST_FIXED, 4096, 400, 230, 270),    # 1.3e6 + 500 x 400 = 1.5e6: 250 pairs
-    (EUCLIDEAN_ERROR, EST_RANSAC, 1157, 300, 40, 60),        # 6.0e4: 50 pairs (hb - 1 = 4)
-    (REPROJECTION_ERROR, EST_USAC, 3000, 300, 10, 18),       # 4.5e4: 14 pairs (hb - 1 = 11)
-])
+@pytest.mark.parametrize("mode,est,H,kpts,below,above", COST_MODEL_ROWS)   # (tests/score_plan_rows.py: the host test runs them too)
 def test_cost_model_picks_the_form_by_batch_size_and_both_forms_agree(mode, est, H, kpts, below, above):
     """Round 5: the default (option prune = 1) takes the staged form from the cost model's batch size on -- pairs x work-groups of
     hypotheses x frame capacity against base + perRow x capacity (profiles/r05c/staged_crossover.txt) -- and complete scoring
@@ -467,15 +467,7 @@ def test_cost_model_picks_the_form_by_batch_size_and_both_forms_agree(mode, est,
         _same(g, _run(seq, prm, cfg, 0 if expect_staged else 1), P)
 
 
-@pytest.mark.parametrize("mode,est,H,kpts,sbs,below,above", [
-    # a context that shares the chip with other launch chains (option "side_by_side": the chains of a PsBatchQueue, the lanes of
-    # the pipelined stream) takes the staged form from far smaller batches on (ps_capi.hip: kStagedFrom*Sbs); with TWO chains the
-    # point lies half way, on the logarithmic scale
-    (EUCLIDEAN_ERROR, EST_FIXED, 4096, 500, 4, 56, 74),      # 4.5e5 + 75 x 500 = 4.875e5: 65 pairs (alone: 121)
-    (REPROJECTION_ERROR, EST_FIXED, 4096, 400, 4, 48, 64),   # 3.0e5 + 90 x 400 = 3.36e5: 56 pairs (alone: 250)
-    (REPROJECTION_ERROR, EST_FIXED, 4096, 400, 2, 104, 134), # sqrt(3.36e5 x 1.5e6) = 7.1e5: 119 pairs
-    (EUCLIDEAN_ERROR, EST_RANSAC, 1157, 300, 3, 14, 26),     # 2.4e4: 20 pairs (hb - 1 = 4; alone: 50)
-])
+@pytest.mark.parametrize("mode,est,H,kpts,sbs,below,above", COST_MODEL_SBS_ROWS)
 def test_cost_model_side_by_side_takes_the_staged_form_earlier(mode, est, H, kpts, sbs, below, above):
     """Round 6: chains that run side by side hide one another's launch gaps, so the staged form's dependent launches cost throughput
     little and it pays from 2 - 5 times smaller batches on (profiles/r06u/concurrent_crossover.txt, bench_data_crossover.txt).  The form taken just below /
