@@ -5,16 +5,12 @@
 // the loop-closure thread (featuresMap.cpp:650-652): contexts are never shared between threads.
 #include "putslam_dropin.h"
 
-#include <algorithm>
-#include <cmath>
 #include <cstdio>
-#include <cstring>
-#include <ctime>
 #include <iostream>
 #include <sstream>
 #include <iomanip>
 
-#include "putslam_hip.h"
+#include "putslam_dropin_host.h" // the pure parts: image checks, parameter blocks, key points (and <algorithm>, <cmath>, <cstring>, <ctime>)
 
 #include <hip/hip_runtime_api.h> // device block of matchXYZLadder (the C ABI takes device pointers there)
 
@@ -24,14 +20,23 @@ static_assert(sizeof(cv::Point2f) == 8, "cv::Point2f storage");
 
 namespace {
 
+// a context on the device PUTSLAM_HIP_DEVICE names (0 without it)
+int createContext(PsContext **ctx)
+{
+    int dev = 0;
+    if (const char *e = std::getenv("PUTSLAM_HIP_DEVICE")) dev = std::atoi(e);
+    return ps_context_create(dev, ctx);
+}
+
+// the text of the C ABI call that just failed on ctx, on std::cerr
+void reportError(const PsContext *ctx) { std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl; }
+
 struct ThreadContext {
     PsContext *ctx = nullptr;
     int status = PS_OK;
     ThreadContext()
     {
-        int dev = 0;
-        if (const char *e = std::getenv("PUTSLAM_HIP_DEVICE")) dev = std::atoi(e);
-        status = ps_context_create(dev, &ctx);
+        status = createContext(&ctx);
         if (status != PS_OK)
             std::cerr << "putslam_hip: no usable HIP device (status " << status << "); the GPU path has no CPU fallback"
                       << std::endl;
@@ -44,33 +49,6 @@ PsContext *threadContext(int *status)
     static thread_local ThreadContext tc;
     if (status) *status = tc.status;
     return tc.ctx;
-}
-
-void cameraToK(const cv::Mat &cameraMatrix, float K[9], bool &have)
-{
-    have = !cameraMatrix.empty() && cameraMatrix.rows >= 3 && cameraMatrix.cols >= 3;
-    for (int i = 0; i < 9; ++i) K[i] = 0.0f;
-    if (have)
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) K[3 * r + c] = cameraMatrix.at<float>(r, c);
-}
-
-PsRansacParams toPs(const RANSAC::parameters &p)
-{
-    PsRansacParams q;
-    std::memset(&q, 0, sizeof q); // padding bytes too: the C ABI may compare parameter blocks bytewise
-    q.verbose = p.verbose;
-    q.errorVersion = p.errorVersion;
-    q.errorVersionVO = p.errorVersionVO;
-    q.errorVersionMap = p.errorVersionMap;
-    q.inlierThresholdEuclidean = p.inlierThresholdEuclidean;
-    q.inlierThresholdReprojection = p.inlierThresholdReprojection;
-    q.inlierThresholdMahalanobis = p.inlierThresholdMahalanobis;
-    q.minimalInlierRatioThreshold = p.minimalInlierRatioThreshold;
-    q.minimalNumberOfMatches = p.minimalNumberOfMatches;
-    q.usedPairs = p.usedPairs;
-    q.iterationCount = p.iterationCount;
-    return q;
 }
 
 Eigen::Matrix4f runEstimator(int estimator, int H, uint64_t seed, const PsRansacParams &prm, const cv::Mat &cameraMatrix,
@@ -87,11 +65,7 @@ Eigen::Matrix4f runEstimator(int estimator, int H, uint64_t seed, const PsRansac
     float K[9];
     bool haveK;
     cameraToK(cameraMatrix, K, haveK);
-    PsRansacConfig cfg;
-    cfg.estimator = estimator;
-    cfg.numHypotheses = H;
-    cfg.seed = seed;
-    cfg.sampleIdx = nullptr;
+    const PsRansacConfig cfg = ransacConfig(estimator, H, seed);
     std::vector<cv::DMatch> out(matches.size() ? matches.size() : 1);
     int n = 0;
     PsRansacStats st;
@@ -100,7 +74,7 @@ Eigen::Matrix4f runEstimator(int estimator, int H, uint64_t seed, const PsRansac
                                reinterpret_cast<const PsDMatch *>(matches.data()), (int)matches.size(), pose.data(),
                                reinterpret_cast<PsDMatch *>(out.data()), &n, nullptr, &st);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         pose = Eigen::Matrix4f::Identity();
         if (clearOnFail) inliers.clear();
         return pose;
@@ -115,14 +89,6 @@ Eigen::Matrix4f runEstimator(int estimator, int H, uint64_t seed, const PsRansac
     return pose;
 }
 
-int ransacIterations(double inlierRatio, double successProbability = 0.98, int numberOfPairs = 3)
-{
-    // RANSAC::computeRANSACIteration, RANSAC.cpp:457-461 (saturating instead of UB)
-    double v = std::log(1 - successProbability) / std::log(1 - std::pow(inlierRatio, numberOfPairs));
-    if (!(v < 2147483647.0)) return 2147483647;
-    return v < 0 ? 0 : (int)v;
-}
-
 } // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -131,7 +97,7 @@ RANSAC::RANSAC(RANSAC::parameters _RANSACParameters, cv::Mat _cameraMatrix)
     seed_ = (uint64_t)std::time(nullptr); // the reference: srand(time(0)), RANSAC.cpp:13
     cameraMatrix = _cameraMatrix;
     RANSACParams = _RANSACParameters;
-    RANSACParams.iterationCount = ransacIterations(0.20); // RANSAC.cpp:30
+    RANSACParams.iterationCount = defaultIterationCount();
     if (RANSACParams.verbose > 0) {
         std::cout << "RANSACParams.verbose --> " << RANSACParams.verbose << std::endl;
         std::cout << "RANSACParams.usedPairs --> " << RANSACParams.usedPairs << std::endl;
@@ -149,14 +115,8 @@ Eigen::Matrix4f RANSAC::estimateTransformation(std::vector<Eigen::Vector3f> prev
     if (RANSACParams.errorVersion != EUCLIDEAN_ERROR && RANSACParams.errorVersion != REPROJECTION_ERROR &&
         RANSACParams.errorVersion != EUCLIDEAN_AND_REPROJECTION_ERROR && RANSACParams.errorVersion != ADAPTIVE_ERROR)
         std::cout << "RANSAC: incorrect error version" << std::endl; // RANSAC.cpp:134-135 (once per call here, not per iteration)
-    // enough samples for the longest schedule the reference can run: max(iters(0.2), iters(minRatio))
-    int a = ransacIterations(0.20), b = ransacIterations(RANSACParams.minimalInlierRatioThreshold);
-    int H = a > b ? a : b;
-    if (H < 1) H = 1;
-    if (H > PS_MAX_HYPOTHESES) H = PS_MAX_HYPOTHESES;
-    PsRansacParams prm = toPs(RANSACParams);
-    return runEstimator(PS_EST_RANSAC, H, seed_, prm, cameraMatrix, prevFeatures, features, matches, bestInlierMatches, true,
-                        lastStatus_);
+    return runEstimator(PS_EST_RANSAC, hypothesisCount(RANSACParams.minimalInlierRatioThreshold), seed_, toPs(RANSACParams), cameraMatrix,
+                        prevFeatures, features, matches, bestInlierMatches, true, lastStatus_);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -171,18 +131,7 @@ RANSAC_USAC::~RANSAC_USAC() {}
 Eigen::Matrix4f RANSAC_USAC::estimateTransformation(std::vector<Eigen::Vector3f> prevFeatures, std::vector<Eigen::Vector3f> features,
                                                     std::vector<cv::DMatch> matches, std::vector<cv::DMatch> &bestInlierMatches)
 {
-    PsRansacParams prm;
-    std::memset(&prm, 0, sizeof prm);
-    prm.verbose = params_.verbose;
-    prm.errorVersion = params_.errorVersion;
-    prm.errorVersionVO = params_.errorVersionVO;
-    prm.errorVersionMap = params_.errorVersionMap;
-    prm.inlierThresholdEuclidean = params_.inlierThresholdEuclidean;
-    prm.inlierThresholdReprojection = params_.inlierThresholdReprojection;
-    prm.inlierThresholdMahalanobis = params_.inlierThresholdMahalanobis;
-    prm.minimalInlierRatioThreshold = params_.minimalInlierRatioThreshold;
-    prm.minimalNumberOfMatches = 8; // USAC_wrapper.cpp:120
-    prm.usedPairs = params_.usedPairs;
+    const PsRansacParams prm = toPs(params_, 8, 0); // minimalNumberOfMatches 8: USAC_wrapper.cpp:120; no iteration count
     return runEstimator(PS_EST_USAC, maxHyp_, seed_, prm, cameraMatrix, prevFeatures, features, matches, bestInlierMatches, false,
                         lastStatus_);
 }
@@ -212,7 +161,7 @@ std::vector<Eigen::Vector3f> RGBD::keypoints2Dto3D(std::vector<cv::Point2f> f2d,
     status = ps_keypoints2Dto3D(ctx, reinterpret_cast<const float *>(f2d.data() + startingID), (int)n,
                                 reinterpret_cast<const uint16_t *>(depthImage.data), depthImage.rows, depthImage.cols,
                                 (size_t)depthImage.step, K, depthImageScale, reinterpret_cast<float *>(out.data()));
-    if (status != PS_OK) std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+    if (status != PS_OK) reportError(ctx);
     return out;
 }
 
@@ -233,7 +182,7 @@ void DBScan::run(std::vector<cv::KeyPoint> &clusteringSet)
     status = ps_dbscan_thin(ctx, &clusteringSet[0].pt.x, sizeof(cv::KeyPoint), &clusteringSet[0].octave, sizeof(cv::KeyPoint),
                             (int)n, eps, minPts, featuresFromCluster, kept.data(), &nkept);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         return;
     }
     // kept[] ascends and kept[j] >= j: compacting in place never overwrites a survivor before it is moved
@@ -262,7 +211,7 @@ bool excludeCall(const PsExclusionRule &rule, const std::vector<Eigen::Vector3f>
                         exist3 && m ? reinterpret_cast<const float *>(exist3->data()) : nullptr,
                         m ? reinterpret_cast<const float *>(exist2.data()) : nullptr, (int)m, kept.data(), &nkept);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         kept.clear();
         return false;
     }
@@ -377,13 +326,12 @@ std::vector<cv::Point2f> RGBD::removeImageDistortion(std::vector<cv::Point2f> &f
     float K[9];
     bool haveK;
     cameraToK(cameraMatrix, K, haveK);
-    double d[5] = {0, 0, 0, 0, 0};
-    const int nd = distCoeffs.empty() ? 0 : distCoeffs.rows * distCoeffs.cols;
-    for (int i = 0; i < 5 && i < nd; ++i) d[i] = (double)distCoeffs.at<float>(distCoeffs.rows == 1 ? 0 : i, distCoeffs.rows == 1 ? i : 0);
+    double d[5];
+    distortion5(distCoeffs, d);
     if (!ctx) return out;
     status = ps_remove_image_distortion(ctx, reinterpret_cast<const float *>(features.data()), (int)features.size(), K, d,
                                         reinterpret_cast<float *>(out.data()));
-    if (status != PS_OK) std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+    if (status != PS_OK) reportError(ctx);
     return out;
 }
 
@@ -399,7 +347,7 @@ std::vector<cv::Point2f> RGBD::points3Dto2D(std::vector<Eigen::Vector3f> f3d, cv
     if (!ctx) return out;
     status = ps_points3Dto2D(ctx, reinterpret_cast<const float *>(f3d.data()), (int)f3d.size(), K,
                              reinterpret_cast<float *>(out.data()));
-    if (status != PS_OK) std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+    if (status != PS_OK) reportError(ctx);
     return out;
 }
 
@@ -421,7 +369,7 @@ Mat34 &KabschEst::computeTransformation(const Eigen::MatrixXd &setA, const Eigen
     double T[16];
     status = ps_kabsch_f64(ctx, setA.data(), setB.data(), (int)setA.rows(), (int)setA.rows(), T);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         return transformation;
     }
 #if PUTSLAM_HAVE_CV_EIGEN
@@ -505,13 +453,9 @@ bool FrameMatcher::fusedMatchCall(const cv::Mat &descriptors, const std::vector<
         return false; // float descriptors / inconsistent sizes: the generic sequence reports them
     if (!fused_) fused_.reset(new Fused());
     Fused &f = *fused_;
-    if (!f.ctx) {
-        int dev = 0;
-        if (const char *e = std::getenv("PUTSLAM_HIP_DEVICE")) dev = std::atoi(e);
-        if (ps_context_create(dev, &f.ctx) != PS_OK) {
-            f.ctx = nullptr;
-            return false;
-        }
+    if (!f.ctx && createContext(&f.ctx) != PS_OK) {
+        f.ctx = nullptr;
+        return false;
     }
     const int need = std::max(std::max(n, np), 1);
     if (!f.stream || f.cap < need) {
@@ -524,17 +468,7 @@ bool FrameMatcher::fusedMatchCall(const cv::Mat &descriptors, const std::vector<
         }
         fusedSynced_ = false;
     }
-    RANSAC::parameters rp = matcherParameters.RANSACParams;
-    rp.iterationCount = ransacIterations(0.20); // RANSAC.cpp:30
-    const PsRansacParams prm = toPs(rp);
-    int a = ransacIterations(0.20), b = ransacIterations(rp.minimalInlierRatioThreshold);
-    int H = a > b ? a : b;
-    H = std::max(1, std::min(H, PS_MAX_HYPOTHESES));
-    PsRansacConfig cfg;
-    cfg.estimator = PS_EST_RANSAC;
-    cfg.numHypotheses = H;
-    cfg.seed = seeded_ ? seed_ + (uint64_t)frameCounter : (uint64_t)std::time(nullptr); // RANSAC.cpp:13
-    cfg.sampleIdx = nullptr;
+    const VoRansac vo = voRansac(matcherParameters.RANSACParams, sampleSeed(seeded_, seed_, (uint64_t)frameCounter));
     float K[9];
     bool haveK;
     cameraToK(matcherParameters.cameraMatrixMat, K, haveK);
@@ -545,18 +479,18 @@ bool FrameMatcher::fusedMatchCall(const cv::Mat &descriptors, const std::vector<
     int nm = 0;
     if (!fusedSynced_) { // (re)load the previous frame as the resident one
         ps_vo_stream_reset(f.stream);
-        int rc = ps_vo_stream_push(f.stream, &prm, &cfg, haveK ? K : nullptr, prevDescriptors.data,
+        int rc = ps_vo_stream_push(f.stream, &vo.prm, &vo.cfg, haveK ? K : nullptr, prevDescriptors.data,
                                    np > 0 ? (size_t)prevDescriptors.step : (size_t)PS_DESC_BYTES,
                                    reinterpret_cast<const float *>(prevFeatures3D.data()), np,
                                    reinterpret_cast<PsDMatch *>(m.data()), &nm, mask.data(), pose.data(), &st);
         if (rc != PS_OK) return false;
     }
-    int rc = ps_vo_stream_push(f.stream, &prm, &cfg, haveK ? K : nullptr, descriptors.data,
+    int rc = ps_vo_stream_push(f.stream, &vo.prm, &vo.cfg, haveK ? K : nullptr, descriptors.data,
                                n > 0 ? (size_t)descriptors.step : (size_t)PS_DESC_BYTES,
                                reinterpret_cast<const float *>(features3D.data()), n, reinterpret_cast<PsDMatch *>(m.data()),
                                &nm, mask.data(), pose.data(), &st);
     if (rc != PS_OK || nm < 0) {
-        if (rc != PS_OK) std::cerr << "putslam_hip: " << ps_last_error(f.ctx) << std::endl;
+        if (rc != PS_OK) reportError(f.ctx);
         fusedSynced_ = false;
         return false;
     }
@@ -605,28 +539,19 @@ bool FrameMatcher::buildPipeline(int cap, uint64_t pairsSoFar)
         return false;
     }
     matcherParameters.RANSACParams.errorVersion = matcherParameters.RANSACParams.errorVersionVO; // matcher.cpp:491-492
-    RANSAC::parameters rp = matcherParameters.RANSACParams;
-    rp.iterationCount = ransacIterations(0.20); // RANSAC.cpp:30
-    const PsRansacParams prm = toPs(rp);
-    int a = ransacIterations(0.20), b = ransacIterations(rp.minimalInlierRatioThreshold);
-    int H = std::max(1, std::min(a > b ? a : b, PS_MAX_HYPOTHESES));
-    PsRansacConfig cfg;
-    cfg.estimator = PS_EST_RANSAC;
-    cfg.numHypotheses = H;
     // pair k of the pipeline draws from seed + k: runVO's seeding (seed_ + frameCounter, the counter starting at 0 with the
     // initial frame)
     if (!pipeSeeded_) {
-        pipeSeed_ = seeded_ ? seed_ : (uint64_t)std::time(nullptr); // RANSAC.cpp:13
+        pipeSeed_ = sampleSeed(seeded_, seed_, 0);
         pipeSeeded_ = true;
     }
-    cfg.seed = pipeSeed_ + pairsSoFar;
-    cfg.sampleIdx = nullptr;
+    const VoRansac vo = voRansac(matcherParameters.RANSACParams, pipeSeed_ + pairsSoFar);
     float K[9];
     bool haveK;
     cameraToK(matcherParameters.cameraMatrixMat, K, haveK);
     // what comes back per frame is what Matcher::match returns: the inlier matches in input order + the pose (matcher.cpp:452-516)
     ps_vo_stream_set_result_mode(f.pipe, PS_RESULTS_INLIERS);
-    if (ps_vo_stream_configure_async(f.pipe, &prm, &cfg, haveK ? K : nullptr, pipeChunk_, pipeLanes_) != PS_OK) {
+    if (ps_vo_stream_configure_async(f.pipe, &vo.prm, &vo.cfg, haveK ? K : nullptr, pipeChunk_, pipeLanes_) != PS_OK) {
         lastError_ = std::string("ps_vo_stream_configure_async: ") + ps_last_error(f.ctx);
         ps_vo_stream_destroy(f.pipe);
         f.pipe = nullptr;
@@ -653,14 +578,10 @@ int FrameMatcher::enqueueFrameStatus(cv::Mat descriptors, std::vector<Eigen::Vec
     }
     if (!fused_) fused_.reset(new Fused());
     Fused &f = *fused_;
-    if (!f.ctx) {
-        int dev = 0;
-        if (const char *e = std::getenv("PUTSLAM_HIP_DEVICE")) dev = std::atoi(e);
-        if (ps_context_create(dev, &f.ctx) != PS_OK) {
-            f.ctx = nullptr;
-            lastError_ = "ps_context_create failed (no usable HIP device; there is no CPU fallback)";
-            return -1;
-        }
+    if (!f.ctx && createContext(&f.ctx) != PS_OK) {
+        f.ctx = nullptr;
+        lastError_ = "ps_context_create failed (no usable HIP device; there is no CPU fallback)";
+        return -1;
     }
     if (!f.pipe) {
         // room for a quarter more keypoints than the first frame has; a later frame with more rebuilds the pipeline (below)
@@ -731,7 +652,7 @@ int FrameMatcher::dequeueResult(Eigen::Matrix4f &estimatedTransformation, std::v
     for (int attempt = 0; attempt < 2; ++attempt) {
         int rc = ps_vo_stream_pop(f.pipe, wait ? 1 : 0, reinterpret_cast<PsDMatch *>(f.pm.data()), &nm, f.pmask.data(), pose.data(), &st);
         if (rc != PS_OK) {
-            std::cerr << "putslam_hip: " << ps_last_error(f.ctx) << std::endl;
+            reportError(f.ctx);
             return -1;
         }
         if (nm >= 0 || !wait) break;
@@ -806,26 +727,16 @@ double FrameMatcher::matchXYZ(const std::vector<MapFeatureXYZ> &mapFeatures, cv:
     int dim;
     if (!mapDescriptorKind(mapFeatures, currentPoseDescriptors, isFloat, dim, "matchXYZ")) return -1.0;
     const size_t rowBytes = isFloat ? (size_t)dim * 4 : 32; // 1 x 32 CV_8U, or 1 x D CV_32F
-    double matchingXYZSphereRadius = matcherParameters.OpenCVParams.matchingXYZSphereRadius; // matcher.cpp:616-622
-    double matchingXYZacceptRatioOfBestMatch = matcherParameters.OpenCVParams.matchingXYZacceptRatioOfBestMatch;
-    if (computationNumber > 1) {
-        matchingXYZSphereRadius += 0.02 * (computationNumber - 1);
-        matchingXYZacceptRatioOfBestMatch = std::max(0.1, matchingXYZacceptRatioOfBestMatch - 0.05 * (computationNumber - 1));
-    }
+    const MapTry t = mapTry(matcherParameters, computationNumber);
     const size_t nmap = mapFeatures.size(), ncur = currentPoseFeatures3D.size();
     std::vector<int32_t> curLevels(ncur), mapLevels(nmap);
-    for (size_t i = 0; i < ncur; ++i) { // :639-652; curDist = Eigen float norm()
-        const Eigen::Vector3f &p = currentPoseFeatures3D[i];
-        float nrm = std::sqrt(p[0] * p[0] + (p[1] * p[1] + p[2] * p[2]));
-        curLevels[i] = ps_predicted_level(currentPoseOctaves[i], currentPoseDetDists[i], (double)nrm);
-    }
+    for (size_t i = 0; i < ncur; ++i) curLevels[i] = frameFeatureLevel(currentPoseFeatures3D[i], currentPoseOctaves[i], currentPoseDetDists[i]);
     std::vector<Eigen::Vector3f> mapFeaturePositions3D(nmap);
     std::vector<unsigned char> mapDesc(nmap * rowBytes);
     for (size_t j = 0; j < nmap; ++j) { // :681-692,701-702
         const MapFeatureXYZ &f = mapFeatures[j];
-        double curDist = std::sqrt(f.position[0] * f.position[0] + f.position[1] * f.position[1] + f.position[2] * f.position[2]);
-        mapLevels[j] = ps_predicted_level(f.octave, f.detDist, curDist);
-        mapFeaturePositions3D[j] = Eigen::Vector3f((float)f.position[0], (float)f.position[1], (float)f.position[2]);
+        mapLevels[j] = mapFeatureLevel(f);
+        mapFeaturePositions3D[j] = mapFeaturePosition(f);
         if (!f.descriptor.empty()) std::memcpy(&mapDesc[j * rowBytes], f.descriptor.data, rowBytes);
     }
     std::vector<cv::DMatch> matches;
@@ -840,19 +751,18 @@ double FrameMatcher::matchXYZ(const std::vector<MapFeatureXYZ> &mapFeatures, cv:
                                          reinterpret_cast<const float *>(mapDesc.data()), rowBytes, mapLevels.data(), (int)nmap,
                                          reinterpret_cast<const float *>(currentPoseFeatures3D.data()),
                                          reinterpret_cast<const float *>(currentPoseDescriptors.data), (size_t)currentPoseDescriptors.step,
-                                         curLevels.data(), (int)ncur, dim, matchingXYZSphereRadius, matchingXYZacceptRatioOfBestMatch,
+                                         curLevels.data(), (int)ncur, dim, t.sphereRadius, t.acceptRatio,
                                          reinterpret_cast<PsDMatch *>(matches.data()), cap, &n);
         else
             status = ps_match_xyz(ctx, reinterpret_cast<const float *>(mapFeaturePositions3D.data()), mapDesc.data(), 32,
                                   mapLevels.data(), (int)nmap, reinterpret_cast<const float *>(currentPoseFeatures3D.data()),
                                   currentPoseDescriptors.data, (size_t)currentPoseDescriptors.step, curLevels.data(), (int)ncur,
-                                  matchingXYZSphereRadius, matchingXYZacceptRatioOfBestMatch,
-                                  reinterpret_cast<PsDMatch *>(matches.data()), cap, &n);
+                                  t.sphereRadius, t.acceptRatio, reinterpret_cast<PsDMatch *>(matches.data()), cap, &n);
         if (status == PS_OK || n <= cap) break;
         cap = n;
     }
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         return -1.0;
     }
     matches.resize((size_t)n);
@@ -922,47 +832,29 @@ double FrameMatcher::matchXYZLadder(const std::vector<MapFeatureXYZ> &mapFeature
     std::vector<unsigned char> in(inBytes, 0);
     for (size_t j = 0; j < nmap; ++j) { // matcher.cpp:681-692,701-702
         const MapFeatureXYZ &f = mapFeatures[j];
-        const double curDist = std::sqrt(f.position[0] * f.position[0] + f.position[1] * f.position[1] + f.position[2] * f.position[2]);
-        const int32_t lvl = ps_predicted_level(f.octave, f.detDist, curDist);
-        const float pos[3] = {(float)f.position[0], (float)f.position[1], (float)f.position[2]};
+        const int32_t lvl = mapFeatureLevel(f);
+        const Eigen::Vector3f pos = mapFeaturePosition(f);
         std::memcpy(&in[oMapLvl + j * 4], &lvl, 4);
-        std::memcpy(&in[oMapPts + j * 12], pos, 12);
+        std::memcpy(&in[oMapPts + j * 12], &pos, 12);
         if (!f.descriptor.empty()) std::memcpy(&in[oMapDesc + j * rowBytes], f.descriptor.data, rowBytes);
     }
-    for (size_t i = 0; i < ncur; ++i) { // :639-652; curDist = Eigen float norm()
-        const Eigen::Vector3f &p = currentPoseFeatures3D[i];
-        const float nrm = std::sqrt(p[0] * p[0] + (p[1] * p[1] + p[2] * p[2]));
-        const int32_t lvl = ps_predicted_level(currentPoseOctaves[i], currentPoseDetDists[i], (double)nrm);
+    for (size_t i = 0; i < ncur; ++i) {
+        const int32_t lvl = frameFeatureLevel(currentPoseFeatures3D[i], currentPoseOctaves[i], currentPoseDetDists[i]);
         std::memcpy(&in[oCurLvl + i * 4], &lvl, 4);
         std::memcpy(&in[oCurDesc + i * rowBytes], currentPoseDescriptors.data + i * (size_t)currentPoseDescriptors.step, rowBytes);
     }
     std::memcpy(&in[oCurPts], currentPoseFeatures3D.data(), ncur * 12);
     const int32_t counts[2] = {(int32_t)nmap, (int32_t)ncur};
     std::memcpy(&in[oCounts], counts, 8);
-    for (int k = 1; k <= T; ++k) { // matcher.cpp:616-622 for computationNumber = k; the pairs all name view 0, frame 0
-        double radius = matcherParameters.OpenCVParams.matchingXYZSphereRadius;
-        double ratio = matcherParameters.OpenCVParams.matchingXYZacceptRatioOfBestMatch;
-        if (k > 1) {
-            radius += 0.02 * (k - 1);
-            ratio = std::max(0.1, ratio - 0.05 * (k - 1));
-        }
-        const float bound = ps_map_sphere_bound(radius);
+    for (int k = 1; k <= T; ++k) { // the pairs all name view 0, frame 0
+        const MapTry t = mapTry(matcherParameters, k);
+        const float bound = ps_map_sphere_bound(t.sphereRadius);
         std::memcpy(&in[oBound + (size_t)(k - 1) * 4], &bound, 4);
-        std::memcpy(&in[oRatio + (size_t)(k - 1) * 8], &ratio, 8);
+        std::memcpy(&in[oRatio + (size_t)(k - 1) * 8], &t.acceptRatio, 8);
     }
     matcherParameters.RANSACParams.errorVersion = matcherParameters.RANSACParams.errorVersionMap; // :760-761
-    RANSAC::parameters rp = matcherParameters.RANSACParams;
-    rp.iterationCount = ransacIterations(0.20); // RANSAC.cpp:30
-    const PsRansacParams prm = toPs(rp);
-    int a = ransacIterations(0.20), b = ransacIterations(rp.minimalInlierRatioThreshold); // (RANSAC::estimateTransformation above)
-    int H = a > b ? a : b;
-    if (H < 1) H = 1;
-    if (H > PS_MAX_HYPOTHESES) H = PS_MAX_HYPOTHESES;
-    PsRansacConfig cfg;
-    cfg.estimator = PS_EST_RANSAC;
-    cfg.numHypotheses = H;
-    cfg.seed = seeded_ ? seed_ + 0x51ED270B0B5ull + (uint64_t)frameCounter : (uint64_t)std::time(nullptr); // try k: + (k - 1)
-    cfg.sampleIdx = nullptr;
+    const VoRansac vo = voRansac(matcherParameters.RANSACParams, // (the seed is try 1's; try k: + (k - 1))
+                                 sampleSeed(seeded_, seed_, 0x51ED270B0B5ull + (uint64_t)frameCounter));
     float K[9];
     bool haveK;
     cameraToK(matcherParameters.cameraMatrixMat, K, haveK);
@@ -1016,20 +908,20 @@ double FrameMatcher::matchXYZLadder(const std::vector<MapFeatureXYZ> &mapFeature
             mb.maps.desc = reinterpret_cast<const float *>(d + oMapDesc);
             mb.frames.desc = reinterpret_cast<const float *>(d + oCurDesc);
             mb.maps.dim = mb.frames.dim = dim;
-            status = ps_map_pairs_l2_device(ctx, &prm, &cfg, haveK ? K : nullptr, &mb, &res);
+            status = ps_map_pairs_l2_device(ctx, &vo.prm, &vo.cfg, haveK ? K : nullptr, &mb, &res);
         } else {
             PsMapBatch mb;
             fill(mb);
             mb.maps.desc = d + oMapDesc;
             mb.frames.desc = d + oCurDesc;
-            status = ps_map_pairs_device(ctx, &prm, &cfg, haveK ? K : nullptr, &mb, &res);
+            status = ps_map_pairs_device(ctx, &vo.prm, &vo.cfg, haveK ? K : nullptr, &mb, &res);
         }
         out.resize(outBytes);
         const bool copied = status == PS_OK && hipMemcpyAsync(out.data(), o, outBytes, hipMemcpyDeviceToHost, stream) == hipSuccess;
         const int sync = ps_context_synchronize(ctx); // (also after a failed call: the upload may still be reading `in`)
         if (status == PS_OK) status = sync;
         if (status != PS_OK) {
-            std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+            reportError(ctx);
             return -1.0;
         }
         if (!copied) return -1.0;
@@ -1176,10 +1068,7 @@ std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &m
     features.clear();
     keyPoints.clear();
     detDists.clear();
-    const auto is8u = [](const cv::Mat &m) { return m.depth() == CV_8U && (m.channels() == 1 || m.channels() == 3); };
-    if (prevImg.empty() || img.empty() || !is8u(prevImg) || prevImg.type() != img.type() || prevImg.rows != img.rows ||
-        prevImg.cols != img.cols || prevImg.step != img.step || prevKeyPoints.size() != n || prevDetDists.size() != n ||
-        (cvp.useInitialFlow > 0 && !initialFlow)) {
+    if (!imagePair8u(prevImg, img) || prevKeyPoints.size() != n || prevDetDists.size() != n || (cvp.useInitialFlow > 0 && !initialFlow)) {
         std::cerr << "putslam_hip: performTracking takes two CV_8UC1 / CV_8UC3 images of one size and step, and one key point and "
                      "detection distance per previous feature" << std::endl;
         return matches;
@@ -1188,13 +1077,7 @@ std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &m
     int status;
     PsContext *ctx = threadContext(&status);
     if (!ctx) return matches;
-    PsKltParams prm;
-    prm.eps = cvp.eps;                                   // :220-222, TermCriteria(ITER | EPS, maxIter, eps)
-    prm.minEigThreshold = cvp.trackingMinEigThreshold;   // :238
-    prm.winSize = cvp.winSize;                           // :234-235
-    prm.maxLevels = cvp.maxLevels;                       // :236
-    prm.maxCount = cvp.maxIter;
-    prm.flags = (cvp.useInitialFlow > 0 ? PS_KLT_USE_INITIAL_FLOW : 0) | (cvp.trackingErrorType > 0 ? PS_KLT_GET_MIN_EIGENVALS : 0); // :225-229
+    const PsKltParams prm = kltParams(matcherParameters);
     matches.resize(n);
     std::vector<cv::Point2f> keptPts(n);
     std::vector<int32_t> keptIdx(n);
@@ -1204,7 +1087,7 @@ std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &m
                                  &prm, cvp.trackingErrorThreshold, cvp.minimalReprojDistanceNewTrackingFeatures, nullptr, nullptr,
                                  reinterpret_cast<PsDMatch *>(matches.data()), &k, reinterpret_cast<float *>(keptPts.data()), keptIdx.data());
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         matches.clear();
         return matches;
     }
@@ -1213,12 +1096,7 @@ std::vector<cv::DMatch> trackFeaturesLK(const FrameMatcher::MatcherParameters &m
     features.assign(keptPts.begin(), keptPts.begin() + k);
     keyPoints.reserve((size_t)k);
     detDists.reserve((size_t)k);
-    for (int j = 0; j < k; ++j) {
-        cv::KeyPoint kp = prevKeyPoints[(size_t)keptIdx[(size_t)j]];
-        kp.pt = keptPts[(size_t)j];
-        keyPoints.push_back(kp);
-        detDists.push_back(prevDetDists[(size_t)keptIdx[(size_t)j]]);
-    }
+    for (int j = 0; j < k; ++j) carryKeyPoint(prevKeyPoints, prevDetDists, keptIdx[(size_t)j], keptPts[(size_t)j], keyPoints, detDists);
     if (matcherParameters.verbose > 0)
         std::cout << "MatcherOpenCV::performTracking -- features tracked " << matches.size() << " ("
                   << (float)matches.size() * 100.0 / (float)prevFeatures.size() << "%)" << std::endl;
@@ -1241,22 +1119,14 @@ std::vector<cv::KeyPoint> detectFeaturesORB(const FrameMatcher::MatcherParameter
 {
     std::vector<cv::KeyPoint> keypoints;
     const auto &cvp = matcherParameters.OpenCVParams;
-    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3)) {
+    if (!image8u(rgbImage)) {
         std::cerr << "putslam_hip: detectFeatures takes a CV_8UC1 or CV_8UC3 image" << std::endl;
         return keypoints;
     }
     int status;
     PsContext *ctx = threadContext(&status);
     if (!ctx) return keypoints;
-    PsOrbDetectParams prm;
-    prm.nFeatures = 500; // cv::ORB::create()'s defaults (:67)
-    prm.scaleFactor = 1.2f;
-    prm.nLevels = 8;
-    prm.fastThreshold = 20;
-    prm.gridRows = cvp.gridRows;
-    prm.gridCols = cvp.gridCols;
-    prm.maximalTrackedFeatures = cvp.maximalTrackedFeatures;
-    prm.reserved = 0;
+    const PsOrbDetectParams prm = orbDetectParams(matcherParameters);
     const int cap = cvp.maximalTrackedFeatures > 0 ? cvp.maximalTrackedFeatures : 0;
     std::vector<cv::Point2f> xy((size_t)cap);
     std::vector<float> response((size_t)cap), angle((size_t)cap);
@@ -1265,19 +1135,11 @@ std::vector<cv::KeyPoint> detectFeaturesORB(const FrameMatcher::MatcherParameter
     status = ps_detect_features_orb(ctx, rgbImage.data, rgbImage.rows, rgbImage.cols, rgbImage.channels(), (size_t)rgbImage.step, &prm,
                                     reinterpret_cast<float *>(xy.data()), response.data(), angle.data(), octave.data(), cap, &n);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         return keypoints;
     }
     keypoints.resize((size_t)n);
-    for (int j = 0; j < n; ++j) { // size = patchSize * scale of the level, class_id -1
-        cv::KeyPoint &kp = keypoints[(size_t)j];
-        kp.pt = xy[(size_t)j];
-        kp.size = 31.f * (float)std::pow((double)prm.scaleFactor, (double)octave[(size_t)j]);
-        kp.angle = angle[(size_t)j];
-        kp.response = response[(size_t)j];
-        kp.octave = octave[(size_t)j];
-        kp.class_id = -1;
-    }
+    for (int j = 0; j < n; ++j) keypoints[(size_t)j] = orbKeyPoint(xy[(size_t)j], angle[(size_t)j], response[(size_t)j], octave[(size_t)j]);
     if (matcherParameters.verbose > 1) std::cout << "MatcherOpenCV: After joining we have " << keypoints.size() << " keypoints" << std::endl;
     return keypoints;
 }
@@ -1292,7 +1154,7 @@ std::vector<cv::KeyPoint> detectFeaturesFAST(const FrameMatcher::MatcherParamete
                   << std::endl;
         return keypoints;
     }
-    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3)) {
+    if (!image8u(rgbImage)) {
         std::cerr << "putslam_hip: detectFeatures takes a CV_8UC1 or CV_8UC3 image" << std::endl;
         return keypoints;
     }
@@ -1313,7 +1175,7 @@ std::vector<cv::KeyPoint> detectFeaturesFAST(const FrameMatcher::MatcherParamete
     status = ps_detect_features(ctx, rgbImage.data, rgbImage.rows, rgbImage.cols, rgbImage.channels(), (size_t)rgbImage.step, &prm,
                                 reinterpret_cast<float *>(xy.data()), response.data(), cap, &n);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         return keypoints;
     }
     keypoints.resize((size_t)n);
@@ -1346,7 +1208,7 @@ cv::Mat describeFeaturesORB(const FrameMatcher::MatcherParameters &matcherParame
                   << "\"): no descriptors; SURF / SIFT description stays with OpenCV on the host" << std::endl;
         return cv::Mat();
     }
-    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3)) {
+    if (!image8u(rgbImage)) {
         std::cerr << "putslam_hip: describeFeatures takes a CV_8UC1 or CV_8UC3 image" << std::endl;
         return cv::Mat();
     }
@@ -1354,10 +1216,7 @@ cv::Mat describeFeaturesORB(const FrameMatcher::MatcherParameters &matcherParame
     int status;
     PsContext *ctx = threadContext(&status);
     if (!ctx) return cv::Mat();
-    PsOrbParams prm;
-    prm.scaleFactor = 1.2f; // cv::ORB::create()'s defaults
-    prm.nLevels = 8;
-    prm.reserved[0] = prm.reserved[1] = 0;
+    const PsOrbParams prm = orbDescribeParams();
     const size_t n = in.size();
     std::vector<cv::Point2f> xy(n);
     std::vector<float> angle(n);
@@ -1373,7 +1232,7 @@ cv::Mat describeFeaturesORB(const FrameMatcher::MatcherParameters &matcherParame
                                   reinterpret_cast<const float *>(xy.data()), angle.data(), octave.data(), (int)n, rows.data(), keptIdx.data(),
                                   &k);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         return cv::Mat();
     }
     if (k == 0) return cv::Mat();
@@ -1398,8 +1257,7 @@ void FrameMatcherHIP::frontEnd(cv::Mat rgbImage, cv::Mat depthImage, double dept
                   << cvp.descriptor << "\"): nothing detected; the separate calls or OpenCV on the host serve the others" << std::endl;
         return;
     }
-    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3) || depthImage.empty() ||
-        depthImage.type() != CV_16U || depthImage.rows != rgbImage.rows || depthImage.cols != rgbImage.cols) {
+    if (!image8u(rgbImage) || !depth16uOf(depthImage, rgbImage)) {
         std::cerr << "putslam_hip: frontEnd takes a CV_8UC1 or CV_8UC3 image and a CV_16U depth image of the same size" << std::endl;
         return;
     }
@@ -1408,26 +1266,8 @@ void FrameMatcherHIP::frontEnd(cv::Mat rgbImage, cv::Mat depthImage, double dept
     int status;
     PsContext *ctx = threadContext(&status);
     if (!ctx) return;
-    PsFrontEndParams prm;
-    prm.detect.nFeatures = 500; // cv::ORB::create()'s defaults (matcherOpenCV.cpp:67, :90)
-    prm.detect.scaleFactor = 1.2f;
-    prm.detect.nLevels = 8;
-    prm.detect.fastThreshold = 20;
-    prm.detect.gridRows = cvp.gridRows;
-    prm.detect.gridCols = cvp.gridCols;
-    prm.detect.maximalTrackedFeatures = cvp.maximalTrackedFeatures;
-    prm.detect.reserved = 0;
-    prm.describe.scaleFactor = 1.2f;
-    prm.describe.nLevels = 8;
-    prm.describe.reserved[0] = prm.describe.reserved[1] = 0;
-    prm.DBScanEps = cvp.DBScanEps;
-    PsFrameGeometry geo;
-    bool haveK;
-    cameraToK(matcherParameters.cameraMatrixMat, geo.K, haveK);
-    const cv::Mat &dc = matcherParameters.distortionCoeffsMat;
-    const int nd = dc.empty() ? 0 : dc.rows * dc.cols;
-    for (int i = 0; i < 5; ++i) geo.dist5[i] = i < nd ? (double)dc.at<float>(dc.rows == 1 ? 0 : i, dc.rows == 1 ? i : 0) : 0.0;
-    geo.depthImageScale = depthImageScale;
+    const PsFrontEndParams prm = frontEndParams(matcherParameters);
+    const PsFrameGeometry geo = frameGeometry(matcherParameters, depthImageScale);
     const size_t room = (size_t)cap;
     std::vector<unsigned char> rows(room * 32);
     std::vector<cv::Point2f> xy(room), und(room);
@@ -1446,7 +1286,7 @@ void FrameMatcherHIP::frontEnd(cv::Mat rgbImage, cv::Mat depthImage, double dept
     status = ps_front_end_frame(ctx, rgbImage.data, reinterpret_cast<const uint16_t *>(depthImage.data), rgbImage.rows, rgbImage.cols,
                                 rgbImage.channels(), (size_t)rgbImage.step, (size_t)depthImage.step, &prm, nullptr, &geo, rows.data(), &out, cap, &n);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         features3D.clear();
         return;
     }
@@ -1457,15 +1297,7 @@ void FrameMatcherHIP::frontEnd(cv::Mat rgbImage, cv::Mat depthImage, double dept
     if (undistorted) undistorted->assign(und.begin(), und.begin() + n);
     if (keyPoints) {
         keyPoints->resize((size_t)n);
-        for (int j = 0; j < n; ++j) { // the key point detectFeaturesORB makes
-            cv::KeyPoint &kp = (*keyPoints)[(size_t)j];
-            kp.pt = xy[(size_t)j];
-            kp.size = 31.f * (float)std::pow((double)prm.detect.scaleFactor, (double)octave[(size_t)j]);
-            kp.angle = angle[(size_t)j];
-            kp.response = response[(size_t)j];
-            kp.octave = octave[(size_t)j];
-            kp.class_id = -1;
-        }
+        for (int j = 0; j < n; ++j) (*keyPoints)[(size_t)j] = orbKeyPoint(xy[(size_t)j], angle[(size_t)j], response[(size_t)j], octave[(size_t)j]);
     }
 }
 
@@ -1495,11 +1327,8 @@ bool FrameMatcherHIP::trackStep(cv::Mat prevRgbImage, cv::Mat rgbImage, cv::Mat 
                      "matcher.cpp:960-963): set OpenCVParams.removeTooCloseFeatures to 0 and call removeTooCloseFeatures on the result" << std::endl;
         return false;
     }
-    const auto is8u = [](const cv::Mat &m) { return m.depth() == CV_8U && (m.channels() == 1 || m.channels() == 3); };
-    if (prevRgbImage.empty() || rgbImage.empty() || !is8u(prevRgbImage) || prevRgbImage.type() != rgbImage.type() ||
-        prevRgbImage.rows != rgbImage.rows || prevRgbImage.cols != rgbImage.cols || prevRgbImage.step != rgbImage.step || depthImage.empty() ||
-        depthImage.type() != CV_16U || depthImage.rows != rgbImage.rows || depthImage.cols != rgbImage.cols || prevFeatures3D.size() != n ||
-        prevKeyPoints.size() != n || prevDetDists.size() != n || (cvp.useInitialFlow > 0 && !initialFlow)) {
+    if (!imagePair8u(prevRgbImage, rgbImage) || !depth16uOf(depthImage, rgbImage) || prevFeatures3D.size() != n || prevKeyPoints.size() != n ||
+        prevDetDists.size() != n || (cvp.useInitialFlow > 0 && !initialFlow)) {
         std::cerr << "putslam_hip: trackStep takes two CV_8UC1 / CV_8UC3 images of one size and step, a CV_16U depth image of that size, and "
                      "one 3-D point, key point and detection distance per previous feature" << std::endl;
         return false;
@@ -1508,13 +1337,7 @@ bool FrameMatcherHIP::trackStep(cv::Mat prevRgbImage, cv::Mat rgbImage, cv::Mat 
     int status;
     PsContext *ctx = threadContext(&status);
     if (!ctx) return false;
-    PsKltParams klt;
-    klt.eps = cvp.eps;
-    klt.minEigThreshold = cvp.trackingMinEigThreshold;
-    klt.winSize = cvp.winSize;
-    klt.maxLevels = cvp.maxLevels;
-    klt.maxCount = cvp.maxIter;
-    klt.flags = (cvp.useInitialFlow > 0 ? PS_KLT_USE_INITIAL_FLOW : 0) | (cvp.trackingErrorType > 0 ? PS_KLT_GET_MIN_EIGENVALS : 0);
+    const PsKltParams klt = kltParams(matcherParameters);
     PsTrackVoParams tp;
     tp.trackingErrorThreshold = cvp.trackingErrorThreshold;
     tp.minimalReprojDistanceNewTrackingFeatures = cvp.minimalReprojDistanceNewTrackingFeatures;
@@ -1523,23 +1346,8 @@ bool FrameMatcherHIP::trackStep(cv::Mat prevRgbImage, cv::Mat rgbImage, cv::Mat 
     // RANSAC ransac(matcherParameters.RANSACParams with errorVersion = errorVersionVO, cameraMatrixMat), as Matcher::match builds it
     RANSAC::parameters rp = matcherParameters.RANSACParams;
     rp.errorVersion = rp.errorVersionVO; // matcher.cpp:190-191
-    rp.iterationCount = ransacIterations(0.20); // RANSAC.cpp:30
-    const PsRansacParams prm = toPs(rp);
-    int a = ransacIterations(0.20), b = ransacIterations(rp.minimalInlierRatioThreshold);
-    int H = a > b ? a : b;
-    H = H < 1 ? 1 : (H > PS_MAX_HYPOTHESES ? PS_MAX_HYPOTHESES : H);
-    PsRansacConfig cfg;
-    cfg.estimator = PS_EST_RANSAC;
-    cfg.numHypotheses = H;
-    cfg.seed = seeded_ ? seed_ + (uint64_t)frameCounter : (uint64_t)std::time(nullptr); // RANSAC.cpp:13
-    cfg.sampleIdx = nullptr;
-    PsFrameGeometry geo;
-    bool haveK;
-    cameraToK(matcherParameters.cameraMatrixMat, geo.K, haveK);
-    const cv::Mat &dc = matcherParameters.distortionCoeffsMat;
-    const int nd = dc.empty() ? 0 : dc.rows * dc.cols;
-    for (int i = 0; i < 5; ++i) geo.dist5[i] = i < nd ? (double)dc.at<float>(dc.rows == 1 ? 0 : i, dc.rows == 1 ? i : 0) : 0.0;
-    geo.depthImageScale = depthImageScale;
+    const VoRansac vo = voRansac(rp, sampleSeed(seeded_, seed_, (uint64_t)frameCounter));
+    const PsFrameGeometry geo = frameGeometry(matcherParameters, depthImageScale);
     std::vector<cv::Point2f> xy(n), und(n);
     std::vector<int32_t> keptIdx(n);
     std::vector<uint8_t> mask(n);
@@ -1563,10 +1371,10 @@ bool FrameMatcherHIP::trackStep(cv::Mat prevRgbImage, cv::Mat rgbImage, cv::Mat 
     out.stats = &st;
     int k = 0;
     status = ps_track_vo_pair(ctx, prevRgbImage.data, rgbImage.data, reinterpret_cast<const uint16_t *>(depthImage.data), rgbImage.rows,
-                              rgbImage.cols, rgbImage.channels(), (size_t)rgbImage.step, (size_t)depthImage.step, &klt, &tp, &prm, &cfg, &geo, &in,
+                              rgbImage.cols, rgbImage.channels(), (size_t)rgbImage.step, (size_t)depthImage.step, &klt, &tp, &vo.prm, &vo.cfg, &geo, &in,
                               (int)n, &out, &k);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         matches.clear();
         features3D.clear();
         estimatedTransformation = Eigen::Matrix4f::Identity();
@@ -1578,11 +1386,8 @@ bool FrameMatcherHIP::trackStep(cv::Mat prevRgbImage, cv::Mat rgbImage, cv::Mat 
     undistorted.assign(und.begin(), und.begin() + k);
     keyPoints.reserve((size_t)k);
     detDists.reserve((size_t)k);
-    for (int j = 0; j < k; ++j) { // matcherOpenCV.cpp:240-245, :267-290: the previous frame's key point with its pt moved
-        cv::KeyPoint kp = prevKeyPoints[(size_t)keptIdx[(size_t)j]];
-        kp.pt = xy[(size_t)j];
-        keyPoints.push_back(kp);
-        detDists.push_back(prevDetDists[(size_t)keptIdx[(size_t)j]]);
+    for (int j = 0; j < k; ++j) {
+        carryKeyPoint(prevKeyPoints, prevDetDists, keptIdx[(size_t)j], xy[(size_t)j], keyPoints, detDists);
         if (mask[(size_t)j]) inlierMatches.push_back(matches[(size_t)j]);
     }
     ++frameCounter;
@@ -1601,8 +1406,7 @@ double FrameMatcherHIP::trackKLT(cv::Mat rgbImage, cv::Mat depthImage, double de
                      "tracked feature allowed: nothing done" << std::endl;
         return 0.0;
     }
-    if (rgbImage.empty() || rgbImage.depth() != CV_8U || (rgbImage.channels() != 1 && rgbImage.channels() != 3) || depthImage.empty() ||
-        depthImage.type() != CV_16U || depthImage.rows != rgbImage.rows || depthImage.cols != rgbImage.cols) {
+    if (!image8u(rgbImage) || !depth16uOf(depthImage, rgbImage)) {
         std::cerr << "putslam_hip: trackKLT takes a CV_8UC1 or CV_8UC3 image and a CV_16U depth image of the same size" << std::endl;
         return 0.0;
     }
@@ -1619,30 +1423,12 @@ double FrameMatcherHIP::trackKLT(cv::Mat rgbImage, cv::Mat depthImage, double de
     PsContext *ctx = threadContext(&status);
     if (!ctx) return 0.0;
     // :213-381
-    PsFrontEndParams prm;
-    prm.detect.nFeatures = 500; // cv::ORB::create()'s defaults (matcherOpenCV.cpp:67, :90), as frontEnd has them
-    prm.detect.scaleFactor = 1.2f;
-    prm.detect.nLevels = 8;
-    prm.detect.fastThreshold = 20;
-    prm.detect.gridRows = cvp.gridRows;
-    prm.detect.gridCols = cvp.gridCols;
-    prm.detect.maximalTrackedFeatures = cvp.maximalTrackedFeatures;
-    prm.detect.reserved = 0;
-    prm.describe.scaleFactor = 1.2f;
-    prm.describe.nLevels = 8;
-    prm.describe.reserved[0] = prm.describe.reserved[1] = 0;
-    prm.DBScanEps = cvp.DBScanEps;
+    const PsFrontEndParams prm = frontEndParams(matcherParameters);
     PsTrackCloseParams tp;
     tp.minimalReprojDistanceNewTrackingFeatures = cvp.minimalReprojDistanceNewTrackingFeatures;
     tp.minimalTrackedFeatures = cvp.minimalTrackedFeatures;
     tp.removeTooCloseFeatures = 0;
-    PsFrameGeometry geo;
-    bool haveK;
-    cameraToK(matcherParameters.cameraMatrixMat, geo.K, haveK);
-    const cv::Mat &dc = matcherParameters.distortionCoeffsMat;
-    const int nd = dc.empty() ? 0 : dc.rows * dc.cols;
-    for (int i = 0; i < 5; ++i) geo.dist5[i] = i < nd ? (double)dc.at<float>(dc.rows == 1 ? 0 : i, dc.rows == 1 ? i : 0) : 0.0;
-    geo.depthImageScale = depthImageScale;
+    const PsFrameGeometry geo = frameGeometry(matcherParameters, depthImageScale);
     const size_t n = distorted.size(), base = n > 0 ? n : 1, cap = base + (size_t)cvp.maximalTrackedFeatures;
     std::vector<float> angle(base), response(base), oAngle(cap), oResponse(cap);
     std::vector<int32_t> octave(base), oOctave(cap), srcIdx(cap);
@@ -1678,7 +1464,7 @@ double FrameMatcherHIP::trackKLT(cv::Mat rgbImage, cv::Mat depthImage, double de
                                  rgbImage.channels(), (size_t)rgbImage.step, (size_t)depthImage.step, &prm, nullptr, &geo, &tp, &in, (int)n, rows.data(),
                                  &out, srcIdx.data(), (int)cap, &k, &refill);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         estimatedTransformation = Eigen::Matrix4f::Identity();
         inlierMatches.clear();
         return 0.0;
@@ -1687,15 +1473,10 @@ double FrameMatcherHIP::trackKLT(cv::Mat rgbImage, cv::Mat depthImage, double de
     for (int j = 0; j < k; ++j) {
         cv::KeyPoint &kp = closed[(size_t)j];
         const size_t s = (size_t)srcIdx[(size_t)j];
-        if (n > 0 && s < n) {
+        if (n > 0 && s < n)
             kp = keyPoints[s]; // the tracked key point (matcherOpenCV.cpp:240-245)
-        } else {               // a merged one: the key point detectFeaturesORB makes
-            kp.size = 31.f * (float)std::pow((double)prm.detect.scaleFactor, (double)oOctave[(size_t)j]);
-            kp.angle = oAngle[(size_t)j];
-            kp.response = oResponse[(size_t)j];
-            kp.octave = oOctave[(size_t)j];
-            kp.class_id = -1;
-        }
+        else               // a merged one
+            kp = orbKeyPoint(oXy[(size_t)j], oAngle[(size_t)j], oResponse[(size_t)j], oOctave[(size_t)j]);
         kp.pt = oXy[(size_t)j];
     }
     double inlierRatio = 0.0; // :404-406
@@ -1733,7 +1514,7 @@ std::vector<cv::DMatch> l2CrossCheckMatch(cv::Mat prevDescriptors, cv::Mat descr
                              reinterpret_cast<const float *>(descriptors.data), descriptors.rows, (size_t)descriptors.step,
                              prevDescriptors.cols, reinterpret_cast<PsDMatch *>(matches.data()), &n);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         n = 0;
     }
     matches.resize((size_t)n);
@@ -1759,7 +1540,7 @@ std::vector<cv::DMatch> hammingCrossCheckMatch(cv::Mat prevDescriptors, cv::Mat 
     status = ps_match_hamming256(ctx, prevDescriptors.data, prevDescriptors.rows, (size_t)prevDescriptors.step, descriptors.data,
                                  descriptors.rows, (size_t)descriptors.step, reinterpret_cast<PsDMatch *>(matches.data()), &n);
     if (status != PS_OK) {
-        std::cerr << "putslam_hip: " << ps_last_error(ctx) << std::endl;
+        reportError(ctx);
         n = 0;
     }
     matches.resize((size_t)n);
