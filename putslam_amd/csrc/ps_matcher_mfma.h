@@ -29,7 +29,8 @@
 // (that form left the tree in round 4; the A/B is on file in profiles/r02h).
 // Any consistent assignment of descriptor bits to (k-step, lane half, element) is valid because both
 // operands use the same one: lane (r = lane & 31, h = lane >> 5) holds, for k-step s, the 32 bits of dword
-// 2s + h of row r.
+// 2s + h of row r, and fp4_word below -- the one expansion rule of every form and both sides -- puts bit 4 i + j of that
+// dword into nibble i of the lane's operand register j.
 //
 // The integer VALU kernel ps_hamming_nn (ps_kernels.h) is kept as the tested twin
 // (PUTSLAM_HIP_MATCHER=valu / ps_context_set_option("matcher", 0)).
@@ -47,21 +48,53 @@ constexpr int kTileRows = 32;            // rows of one MFMA tile
 constexpr int kTileU4 = 256;             // uint4 (16 B) pieces of one expanded tile: 4 k-steps x 64 lanes = 4 KiB
 constexpr int kWavesPerWG = kBlock / 64; // 4
 
-// 8 descriptor bits -> 8 FP4 nibbles (bit i -> nibble i): 0 -> 0x6 = +4.0, 1 -> 0xE = -4.0
-PS_D uint32_t fp4_from_byte(uint32_t x)
+// The one expansion rule, table-free: descriptor dword w -> its 32 FP4 values in four dwords.  Nibble i of output dword j
+// takes descriptor bit 4 i + j as its sign (bit 3 of e2m1); the low three bits are 0b110 = 4.0: 0 -> 0x6 = +4.0,
+// 1 -> 0xE = -4.0.  No bit is spread: one shift and one bit-field insert (v_bfi_b32: (mask & a) | (~mask & b)) per output
+// dword, 7 vector instructions per descriptor dword (j = 3 needs no shift).  Both operand sides of every form go through
+// this function, which is all the contraction needs (see the header).
+// (sign / fill: the two constants; a hot loop hands them in from registers, where the compiler then takes ONE three-operand
+// instruction per output dword -- v_bfi_b32 or, as it stands, v_and_or_b32; as literals they cost a v_and and a v_or, gfx950's
+// three-operand encodings take no literal)
+PS_HD constexpr uint32_t fp4_word(uint32_t w, int j, uint32_t sign = 0x88888888u, uint32_t fill = 0x66666666u)
 {
-    x = (x | (x << 12)) & 0x000F000Fu;
-    x = (x | (x << 6)) & 0x03030303u;
-    x = (x | (x << 3)) & 0x11111111u;
-    return (x << 3) | 0x66666666u;
+    return (sign & (w << (3 - j))) | (~sign & fill);
 }
+constexpr bool fp4_word_checks(uint32_t w)
+{
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t o = fp4_word(w, j);
+        if ((o & 0x77777777u) != 0x66666666u) return false; // magnitude 4.0 in every nibble
+        for (int i = 0; i < 8; ++i)
+            if (((o >> (4 * i + 3)) & 1u) != ((w >> (4 * i + j)) & 1u)) return false; // sign of nibble i = bit 4 i + j
+    }
+    return true;
+}
+constexpr bool fp4_single_bits_check()
+{
+    for (int b = 0; b < 32; ++b) { // bit b lands in bit 3 of exactly one nibble of exactly one output dword
+        int hits = 0;
+        for (int j = 0; j < 4; ++j)
+            for (int i = 0; i < 8; ++i)
+                if ((fp4_word(1u << b, j) >> (4 * i + 3)) & 1u) hits += (4 * i + j == b) ? 1 : 100;
+        if (hits != 1 || !fp4_word_checks(1u << b) || !fp4_word_checks(~(1u << b))) return false;
+    }
+    return true;
+}
+static_assert(fp4_single_bits_check(), "every descriptor bit is the sign of exactly one nibble");
+static_assert(fp4_word_checks(0u) && fp4_word_checks(0xFFFFFFFFu) && fp4_word_checks(0x80000001u) &&
+                  fp4_word_checks(0xDEADBEEFu) && fp4_word_checks(0x01234567u) && fp4_word_checks(0xA5A5C3C3u) &&
+                  fp4_word_checks(0x0F0F00FFu) && fp4_word_checks(0x13579BDFu),
+              "fp4_word: sign of nibble i of dword j = bit 4 i + j, magnitude 0b110");
+static_assert(fp4_word(0u, 0) == 0x66666666u && fp4_word(0xFFFFFFFFu, 2) == 0xEEEEEEEEu && fp4_word(0x10u, 0) == 0x000000E0u + 0x66666606u,
+              "fp4_word: 0 -> +4.0, 1 -> -4.0");
 PS_D v4i_t fp4_from_dword(uint32_t w)
 {
     v4i_t r;
-    r.x = (int)fp4_from_byte(w & 0xFFu);
-    r.y = (int)fp4_from_byte((w >> 8) & 0xFFu);
-    r.z = (int)fp4_from_byte((w >> 16) & 0xFFu);
-    r.w = (int)fp4_from_byte(w >> 24);
+    r.x = (int)fp4_word(w, 0);
+    r.y = (int)fp4_word(w, 1);
+    r.z = (int)fp4_word(w, 2);
+    r.w = (int)fp4_word(w, 3);
     return r;
 }
 
@@ -247,18 +280,26 @@ __global__ __launch_bounds__(kBlock, PS_MFMA_WAVES) void ps_hamming_mfma(const u
 // tiles itself, kFuseChunk tiles at a time, into a double-buffered LDS image in the same fragment-major layout
 // (thread o of the group writes piece o of every tile of the chunk: one descriptor dword -> 32 nibbles -> one
 // ds_write_b128), and all four waves read their A operands from it (four ds_read_b128 per tile, conflict-free).  One barrier
-// per chunk -- the first LDS form of this kernel had one per tile and lost 14 % to it (profiles/r02h); the expansion of
-// chunk c + 1 is issued before the MFMAs of chunk c, so its vector work sits in their shadow.  Every work-group of a
-// pair expands the whole query range it sweeps (28 vector instructions per tile and wave): the four groups of a
-// 2000-row frame repeat each other's expansion, which costs about what the separate launch did (0.036 ms per 499 pairs)
-// and removes 0.29 GB of traffic per step and one launch.
+// per chunk -- the first LDS form of this kernel had one per tile and lost 14 % to it (profiles/r02h).
+// The expansion is software-pipelined over chunks: a thread loads the four descriptor dwords of chunk c + 2 with four
+// independent loads through a running pointer at the top of chunk c (whole tiles only: no row guard), and expands them with
+// fp4_word (7 vector instructions per dword, no table) at the top of chunk c + 1, so the one wait for them (one vmcnt per
+// chunk) comes after a chunk's 64 MFMAs and its barrier.  Until profiles/r23a every tile of the next chunk was a round trip
+// of its own -- load, wait, four table reads from LDS, wait, write -- in front of the chunk's first MFMA; the in-order wave
+// stood through four global and four LDS latencies per chunk, and the kernel ran well above the matrix time its pattern
+// needs (profiles/microbench/mfma_fp4_rate_mi355x.txt).  What is left over after the whole chunks -- up to three whole tiles
+// and the frame's partial last tile -- is one tail chunk with guarded loads, loaded and expanded ahead in the same way.
+// Every work-group of a pair expands the whole query range it sweeps (7 vector instructions per tile and wave): the four
+// groups of a 2000-row frame repeat each other's expansion and save 0.29 GB of traffic per step and one launch.
 // ------------------------------------------------------------------------------------------
-// The MFMA runs in its block-scaled form with an add/max epilogue (10 instead of 13 vector instructions per 32 x 32 tile);
-// the 8 bits -> 8 nibbles expansion goes through a 256-entry table in LDS (2 vector instructions + one LDS read per byte
-// instead of 7).  (The unscaled / table-free sub-forms measured in profiles/r03h left the tree in round 4.)  On gfx950 MFMA and vector instructions of a SIMD do not overlap -- not across waves and, as the
-// software-pipelined epilogue tried here showed (profiles/r03h: 0.232 ms either way), not inside one wave either -- so this
-// kernel's time is its 512 matrix cycles PLUS its ~90 vector instructions per query tile and wave, and only removing
-// vector instructions shortens it.
+// The MFMA runs in its block-scaled form with a max-only epilogue: the running best is carried relative to the tile and
+// enters the v_max3 chain (8 v_max3 + 1 add = 9 vector instructions per 32 x 32 tile; 37 per query tile and wave with the
+// LDS address, beside 16 MFMAs and 4 ds_read_b128).  (The unscaled sub-form measured in profiles/r03h left the tree in
+// round 4.)  MFMAs and vector instructions of DIFFERENT waves of a SIMD do overlap: the kernel's own pattern -- chains of four
+// FP4 MFMAs and the 16-register max epilogue -- runs at 41.5 cycles per MFMA at three waves per SIMD against 38.8 for bare
+// MFMAs (profiles/microbench/mfma_fp4_rate_mi355x.txt).  Inside ONE wave they do not (the software-pipelined epilogue of
+// profiles/r03h: 0.232 ms either way), and a wave that waits for memory or LDS issues nothing: what this kernel lost above
+// that pace was waiting, not vector work.  The measured pace before and after is in profiles/r23a/README.md.
 constexpr int kFuseChunk = 4; // query tiles per chunk: 2 x 4 x 4 KiB = 32 KiB of LDS per work-group
 
 // (Round 4 tried eight wavefronts per work-group -- twice the train rows per work-group, half as many work-groups expanding
@@ -271,8 +312,6 @@ __global__ __launch_bounds__(kBlock, PS_MFMA_WAVES) void ps_hamming_mfma_fused(c
                                                                 int groups, int qsplit, uint32_t *__restrict__ keys)
 {
     __shared__ uint4 s_a[2][kFuseChunk][kTileU4];
-    __shared__ uint32_t s_lut[256]; // byte -> its 8 FP4 nibbles
-    s_lut[threadIdx.x] = fp4_from_byte(threadIdx.x);
     const unsigned perPair = (unsigned)(groups * qsplit);
     const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
     const int p = (int)(L / perPair);
@@ -300,9 +339,12 @@ __global__ __launch_bounds__(kBlock, PS_MFMA_WAVES) void ps_hamming_mfma_fused(c
     v16f_t C;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) C[reg] = kMfmaBase + (float)((1 << 21) + 31 - tile_row(reg, h));
-    int best[TT];
+    // Running best of every train column, carried RELATIVE to the tile it meets next: rel = best - cT(T), cT(T) = 16352 - 32 T
+    // (see tile_body).  It starts below every valid entry (their patterns are >= 0x4B000000) and grows by 32 per tile, so
+    // with at most 512 tiles "no query row seen" stays recognisable as a small value.
+    int rel[TT];
 #pragma unroll
-    for (int i = 0; i < TT; ++i) best[i] = 0; // below every valid entry (their patterns are >= 0x4B000000)
+    for (int i = 0; i < TT; ++i) rel[i] = 0;
 
     // expansion role of this thread: piece o = s * 64 + h * 32 + r of a tile = dword 2 s + h of row r
     const uint32_t *__restrict__ q32 = desc + (size_t)fq * fstride;
@@ -312,26 +354,38 @@ __global__ __launch_bounds__(kBlock, PS_MFMA_WAVES) void ps_hamming_mfma_fused(c
     // EVERY tile (50 of the 126 vector instructions per tile this kernel had, profiles/r03h).
     const int lastT = (nq & (kTileRows - 1)) ? nqTiles - 1 : -1;
     const bool hasPartial = lastT >= T0 && lastT < T1;
-    const int Tm = hasPartial ? lastT : T1; // main loop: whole tiles [T0, Tm)
-    auto expand_tile = [&](uint4 *dst, int T) {
-        const int row = T * kTileRows + er;
-        v4i_t e = {0, 0, 0, 0}; // rows beyond the frame: 0.0 in FP4 (masked by the accumulator start anyway)
-        if (row < nq) {
-            const uint32_t w = q32[(size_t)row * 8 + 2 * es + eh];
-            e.x = (int)s_lut[w & 0xFFu];
-            e.y = (int)s_lut[(w >> 8) & 0xFFu];
-            e.z = (int)s_lut[(w >> 16) & 0xFFu];
-            e.w = (int)s_lut[w >> 24];
+    const int Tm = hasPartial ? lastT : T1; // whole tiles [T0, Tm)
+    // The sweep is cut into nFull chunks of kFuseChunk WHOLE tiles (the main loop: unguarded loads through a running pointer)
+    // and one tail chunk of the 0..3 whole tiles left over plus the partial tile (guarded loads, outside the loop).
+    const int nFull = (Tm - T0) / kFuseChunk;
+    const int rem = (Tm - T0) - nFull * kFuseChunk;
+    const int nTail = rem + (hasPartial ? 1 : 0);
+    const int nChunks = nFull + (nTail > 0 ? 1 : 0);
+    const uint32_t *__restrict__ qp = q32 + ((size_t)T0 * kTileRows + er) * 8 + 2 * es + eh; // this thread's dword of the next chunk to load
+    // the four descriptor dwords of chunk k, as four independent loads (k ascends by one from call to call)
+    auto load_chunk = [&](int k, uint32_t (&W)[kFuseChunk]) {
+        if (k < nFull) { // (work-group uniform)
+#pragma unroll
+            for (int j = 0; j < kFuseChunk; ++j) W[j] = qp[j * (kTileRows * 8)];
+            qp += kFuseChunk * kTileRows * 8;
+        } else { // the tail: rows beyond the frame are not read (their accumulators start from -1e30 whatever the operand)
+#pragma unroll
+            for (int j = 0; j < kFuseChunk; ++j) {
+                W[j] = 0;
+                if (j < nTail && (T0 + nFull * kFuseChunk + j) * kTileRows + er < nq) W[j] = qp[j * (kTileRows * 8)];
+            }
         }
-        dst[tid] = make_uint4((uint32_t)e.x, (uint32_t)e.y, (uint32_t)e.z, (uint32_t)e.w);
     };
-    auto expand_chunk = [&](int buf, int Tc) {
+    uint32_t kSign = 0x88888888u, kFill = 0x66666666u; // (in registers: see fp4_word)
+    asm volatile("" : "+s"(kSign), "+v"(kFill));
+    auto expand_chunk = [&](int buf, const uint32_t (&W)[kFuseChunk]) {
 #pragma unroll
         for (int j = 0; j < kFuseChunk; ++j)
-            if (Tc + j < Tm) expand_tile(s_a[buf][j], Tc + j);
+            s_a[buf][j][tid] = make_uint4(fp4_word(W[j], 0, kSign, kFill), fp4_word(W[j], 1, kSign, kFill),
+                                          fp4_word(W[j], 2, kSign, kFill), fp4_word(W[j], 3, kSign, kFill));
     };
     // one query tile against this wave's TT train tiles
-    auto tile_body = [&](int T, const uint4 *__restrict__ tile, const v16f_t &Cin) {
+    auto tile_body = [&](const uint4 *__restrict__ tile, const v16f_t &Cin) {
         v4i_t A[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -339,46 +393,59 @@ __global__ __launch_bounds__(kBlock, PS_MFMA_WAVES) void ps_hamming_mfma_fused(c
             A[s].x = (int)a.x; A[s].y = (int)a.y; A[s].z = (int)a.z; A[s].w = (int)a.w;
         }
         // block-scaled MFMA: every product carries 2^9, the accumulator's mantissa is 2^14 (256 - hamming) + (31 - row);
-        // adding the tile's 16352 - 32 T turns it into 2^14 (256 - hamming) + (16383 - query row), whose maximum over rows
-        // AND tiles is the nearest query, lowest index first: 8 v_max3 + add + max per 32 x 32 tile
-        const int cT = 16352 - 32 * T;
+        // adding the tile's cT = 16352 - 32 T would turn it into 2^14 (256 - hamming) + (16383 - query row), whose maximum over
+        // rows AND tiles is the nearest query, lowest index first.  The add is not made: the running best is carried less
+        // cT instead, enters the v_max3 chain as its 17th value, and moves on to the next tile (cT falls by 32) with one add:
+        // 8 v_max3 + 1 add per 32 x 32 tile.
 #pragma unroll
         for (int i = 0; i < TT; ++i) {
             v16f_t acc = mfma_fp4s(A[0], B[i][0], Cin);
             acc = mfma_fp4s(A[1], B[i][1], acc);
             acc = mfma_fp4s(A[2], B[i][2], acc);
             acc = mfma_fp4s(A[3], B[i][3], acc);
-            best[i] = max(best[i], max16(acc) + cT);
+            int m = imax3(rel[i], fbits(acc[0]), fbits(acc[1]));
+#pragma unroll
+            for (int e = 2; e < 16; e += 2) m = imax3(m, fbits(acc[e]), fbits(acc[e + 1]));
+            rel[i] = m + kTileRows;
         }
     };
-    __syncthreads(); // the table is complete
-    if (T0 < Tm) expand_chunk(0, T0);
+    // Software pipeline over chunks: W holds the dwords of the chunk that is expanded NEXT.  At the top of the round of chunk
+    // k, chunk k + 1 (loaded a round ago) is expanded into the other LDS buffer; then -- W is free -- chunk k + 2 is loaded
+    // with the round's 64 MFMAs and its barrier still ahead: the only wait for it is the first use of W in the next round.
+    uint32_t W[kFuseChunk] = {0, 0, 0, 0};
+    if (nChunks > 0) {
+        load_chunk(0, W);
+        expand_chunk(0, W);
+    }
+    if (nChunks > 1) load_chunk(1, W);
     __syncthreads();
-    int c = 0;
-    for (int Tc = T0; Tc < Tm; Tc += kFuseChunk, ++c) {
-        if (Tc + kFuseChunk < Tm) expand_chunk((c + 1) & 1, Tc + kFuseChunk);
+    for (int k = 0; k < nFull; ++k) {
+        // (chunk k + 1; in the last round without a tail this writes a buffer nobody reads again)
+        expand_chunk((k + 1) & 1, W);
+        if (k + 2 < nChunks) load_chunk(k + 2, W);
 #pragma unroll 1
-        for (int j = 0; j < kFuseChunk; ++j) {
-            if (Tc + j >= Tm) break;
-            tile_body(Tc + j, s_a[c & 1][j], C);
-        }
-        __syncthreads(); // chunk c + 1 is complete, chunk c may be overwritten
+        for (int j = 0; j < kFuseChunk; ++j) tile_body(s_a[k & 1][j], C);
+        __syncthreads(); // chunk k + 1 is complete, chunk k may be overwritten
     }
-    if (hasPartial) { // (work-group uniform)
-        expand_tile(s_a[0][0], lastT);
-        __syncthreads();
-        v16f_t Cin = C;
+    if (nTail > 0) { // (work-group uniform) the tail chunk lies expanded in buffer nFull & 1
+#pragma unroll 1
+        for (int j = 0; j < rem; ++j) tile_body(s_a[nFull & 1][j], C);
+        if (hasPartial) {
+            v16f_t Cin = C;
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg)
-            if (lastT * kTileRows + tile_row(reg, h) >= nq) Cin[reg] = kMfmaNoRow;
-        tile_body(lastT, s_a[0][0], Cin);
+            for (int reg = 0; reg < 16; ++reg)
+                if (lastT * kTileRows + tile_row(reg, h) >= nq) Cin[reg] = kMfmaNoRow;
+            tile_body(s_a[nFull & 1][rem], Cin);
+        }
     }
+    // the tiles [T0, T1) were met in ascending order: rel is relative to tile T1
+    const int cEnd = 16352 - kTileRows * T1;
 #pragma unroll
     for (int i = 0; i < TT; ++i) {
         const int t = (tile0 + i) * kTileRows + r;
         uint32_t key = kNoKey;
-        if (best[i] > 0) {
-            const int d = best[i] & 0x7FFFFF; // 2^14 (256 - hamming) + (16383 - query row)
+        if (rel[i] >= 0x4B000000) { // a query row was seen (otherwise rel is at most 32 * 513)
+            const int d = (rel[i] + cEnd) & 0x7FFFFF; // 2^14 (256 - hamming) + (16383 - query row)
             key = ((uint32_t)(256 - (d >> 14)) << 16) | (uint32_t)(16383 - (d & 0x3FFF));
         }
         const uint32_t other = (uint32_t)__shfl_xor((int)key, 32, 64); // the other half's 16 rows of every tile
