@@ -1065,7 +1065,7 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
 #include "ps_stream_async.h" // ... and the pipelined one, on the PsVoStream of the former
 #include "ps_map_match.h"    // map_sweep<F, D>, its launcher and entry bodies; ps_match_xyz_device / ps_map_pairs_device (the plan and the stages above)
 #include "ps_dbscan.h"       // ps_dbscan_thin(_device)
-#include "ps_exclusion.h"    // ps_exclude(_device) and the three rules (DBScan's bound and union-find)
+#include "ps_exclusion.h"    // ps_exclude(_device) and the three rules (DBScan's bound)
 #include "ps_map_view.h"     // ps_map_views_device / ps_frame_levels_device
 #include "ps_loop_closure.h" // ps_pose_sets_device / ps_loop_pairs_device (the plan and the stages above)
 #include "ps_match_l2.h"     // ps_match_l2_f32 / ps_match_l2_device / ps_vo_pairs_l2_device (the plan and the stages above)

@@ -23,6 +23,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "ps_block.h" // uf_find / uf_union (here at work-group scope: comp[] lies in LDS)
 #include "ps_glue.h"
 
 namespace psdev {
@@ -45,36 +46,6 @@ __device__ __forceinline__ bool db_nb(float2 a, float2 b, double sstar)
     const float dx = a.x - b.x, dy = a.y - b.y;
     const double s = (double)dx * (double)dx + (double)dy * (double)dy;
     return s < sstar;
-}
-
-// union-find with every root the least index of its tree (a root is only ever hooked under a smaller one)
-__device__ __forceinline__ int db_find(int *par, int x)
-{
-    int p = __hip_atomic_load(&par[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (p != x) {
-        const int g = __hip_atomic_load(&par[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (g != p) __hip_atomic_store(&par[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); // path halving
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-__device__ __forceinline__ void db_union(int *par, int a, int b)
-{
-    for (;;) {
-        a = db_find(par, a);
-        b = db_find(par, b);
-        if (a == b) return;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicCAS(&par[b], b, a);
-        if (old == b) return;
-        b = old; // b was hooked meanwhile: retry from where it went
-    }
 }
 
 // wave 0: sRed[j][w] (per-wave counts of chunk j) -> exclusive prefix in (j, w) order; *total = the sum
@@ -236,14 +207,14 @@ __global__ __launch_bounds__(kDbBlock) void ps_dbscan_kernel(const float2 *__res
         const float2 pi = xy[i < n ? i : i0];
         for (int k = i0 + 1; k < n; ++k) {
             const float2 pk = xy[k];
-            if (i < k && i < n && db_nb(pi, pk, sstar)) db_union(comp, i, k);
+            if (i < k && i < n && db_nb(pi, pk, sstar)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(comp, i, k);
         }
     }
     __syncthreads();
-    // Flatten.  db_find's path-halving stores may land late and put a non-root ancestor back into comp[x] after x's own root
+    // Flatten.  uf_find's path-halving stores may land late and put a non-root ancestor back into comp[x] after x's own root
     // was written there, so the roots go to lab[] first (every find still ends at the true root: a stale store only ever writes
     // an ancestor) and are copied into comp[] after a barrier.  From here on comp[i] is the least index of i's component.
-    for (int i = tid; i < n; i += kDbBlock) lab[i] = db_find(comp, i);
+    for (int i = tid; i < n; i += kDbBlock) lab[i] = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(comp, i);
     __syncthreads();
     for (int i = tid; i < n; i += kDbBlock) {
         comp[i] = lab[i];

@@ -11,7 +11,7 @@
 //     over blockIdx.z where the batch is small; writes flag[j] = 1 for a candidate that is blocked or fails the depth gate.
 //     The all-earlier rule runs the same sweep once more against the candidates themselves (<1>: k < j) and is done.
 //  2. ps_excl_sweep<2>: every pair of unflagged candidates once; a near pair is joined in a union-find in global memory whose
-//     roots are the least index of their tree (the lock-free form of ps_dbscan.h at agent scope).  Connected components of the
+//     roots are the least index of their tree (ps_block.h's lock-free form, DBScan's, at agent scope).  Connected components of the
 //     conflict graph never interact: the greedy choice of one does not depend on another.
 //  3. ps_excl_resolve, one work-group per frame: components of up to 32 members are replayed one per lane in index order; larger
 //     ones cooperatively -- the least undecided index is accepted, every thread rejects its own undecided members near it, one
@@ -23,6 +23,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "ps_block.h" // uf_union (here at agent scope)
 #include "ps_dbscan.h"
 #include "ps_device_math.h"
 #include "ps_glue.h"
@@ -87,36 +88,6 @@ __device__ __forceinline__ bool ex_near(const PsExclusionRule &r, const ExPt &a,
     return hit;
 }
 
-// union-find in global memory, shared by the work-groups of a frame; every root is the least index of its tree
-__device__ __forceinline__ int ex_find(int32_t *par, int x)
-{
-    int p = __hip_atomic_load(&par[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) {
-        const int g = __hip_atomic_load(&par[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g != p) __hip_atomic_store(&par[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // path halving
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-__device__ __forceinline__ void ex_union(int32_t *par, int a, int b)
-{
-    for (;;) {
-        a = ex_find(par, a);
-        b = ex_find(par, b);
-        if (a == b) return;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicCAS(&par[b], b, a);
-        if (old == b) return;
-        b = old; // b was hooked meanwhile: retry from where it went
-    }
-}
-
 // Work-group (chunk c of frame f, split z): the 256 candidates c * 256 ... against
 //   MODE 0: the existing set of the frame             -> flag (also: depth gate; par[i] = i)
 //   MODE 1: every earlier candidate                   -> flag
@@ -172,7 +143,7 @@ __global__ __launch_bounds__(kExTile) void ps_excl_sweep(PsExclusionRule rule, c
                 const ExPt b = {q3.x, q3.y, q3.z, q2.x, q2.y};
                 const bool nr = active && (MODE == 0 || t * kExTile + kk < i) && ex_near(rule, b, a);
                 if (MODE == 2) {
-                    if (nr) ex_union(pr, i, t * kExTile + kk);
+                    if (nr) uf_union<__HIP_MEMORY_SCOPE_AGENT>(pr, i, t * kExTile + kk); // (par[] is shared by the work-groups of a frame)
                 } else {
                     hit = hit || nr;
                 }

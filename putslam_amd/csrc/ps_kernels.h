@@ -13,15 +13,21 @@
 // Kernel 2  ps_crosscheck_prep OpenCV cross-check, ordered compaction, depth filter, records
 // Kernel 3  ps_ransac_score    one lane = one 3-point hypothesis: Umeyama fit + score all M matches
 // Kernel 4  ps_select_refit    replay of the sequential best-model rule, refit, final inliers
+//
+// Two parts of the device side have a header of their own, included here: ps_block.h (the work-group and wave primitives: flag
+// and integer scans, the maximum, wave minima, union-find) and ps_pair_records.h (what kernel 2 and the other routes into RANSAC
+// leave for kernels 3 and 4: PrepArgs, RecPtrs, write_records, PairRecords; the match-list kernels ps_prep_from_matches and
+// ps_prep_match_lists).
 #pragma once
 
+#include "ps_block.h"        // kBlock; the flag and integer scans, maxima, wave minima, union-find
 #include "ps_device_math.h"
+#include "ps_pair_records.h" // PrepArgs, RecPtrs, PairRecords; ps_prep_from_matches / ps_prep_match_lists
 
 #include "../../include/putslam_hip.h"
 
 namespace psdev {
 
-constexpr int kBlock = 256;
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 
 // XCD-aware work-group order.  Work-groups are dealt round-robin over the 8 XCDs (each with its own
@@ -138,234 +144,6 @@ __global__ __launch_bounds__(kBlock) void ps_hamming_nn(const uint4 *__restrict_
     }
 }
 
-// ---- workgroup-wide ordered compaction helper (4 waves) ----
-// Returns the exclusive prefix of `flag` over the 256 threads; `total` = number of set flags.
-template <int BLOCK = kBlock> PS_D int block_scan_flag(bool flag, int &total, int *wsum)
-{
-    unsigned long long bal = __ballot(flag);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int pre = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int off = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < BLOCK / 64; ++i) {
-        int s = wsum[i];
-        if (i < w) off += s;
-        total += s;
-    }
-    __syncthreads();
-    return off + pre;
-}
-
-// Two ordered compactions with one pair of barriers: exclusive prefixes of flagA and flagB over the work-group
-// (flagB implies nothing about flagA); the wave sums travel packed (A in the low 16 bits, B in the high ones).
-template <int BLOCK = kBlock>
-PS_D void block_scan_flags2(bool flagA, bool flagB, int &posA, int &totalA, int &posB, int &totalB, int *wsum)
-{
-    const unsigned long long ba = __ballot(flagA), bb = __ballot(flagB);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (lane == 0) wsum[w] = __popcll(ba) | (__popcll(bb) << 16);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < BLOCK / 64; ++i) {
-        const int sv = wsum[i];
-        if (i < w) off += sv;
-        tot += sv;
-    }
-    __syncthreads();
-    posA = (off & 0xFFFF) + __popcll(ba & below);
-    posB = (off >> 16) + __popcll(bb & below);
-    totalA = tot & 0xFFFF;
-    totalB = tot >> 16;
-}
-
-// The same scans with ONE barrier per call: the wave sums alternate between two slots (`parity` = the call's number, uniform
-// over the work-group).  A slot is written again two calls later, behind the barrier of the call in between, which every
-// thread reaches only after it has read the slot.
-template <int BLOCK = kBlock> PS_D int block_scan_flag_alt(bool flag, int &total, int *wsum2, int parity)
-{
-    int *wsum = wsum2 + (parity & 1) * (BLOCK / 64);
-    unsigned long long bal = __ballot(flag);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int pre = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int off = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < BLOCK / 64; ++i) {
-        int s = wsum[i];
-        if (i < w) off += s;
-        total += s;
-    }
-    return off + pre;
-}
-
-template <int BLOCK = kBlock>
-PS_D void block_scan_flags2_alt(bool flagA, bool flagB, int &posA, int &totalA, int &posB, int &totalB, int *wsum2, int parity)
-{
-    int *wsum = wsum2 + (parity & 1) * (BLOCK / 64);
-    const unsigned long long ba = __ballot(flagA), bb = __ballot(flagB);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (lane == 0) wsum[w] = __popcll(ba) | (__popcll(bb) << 16);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < BLOCK / 64; ++i) {
-        const int sv = wsum[i];
-        if (i < w) off += sv;
-        tot += sv;
-    }
-    posA = (off & 0xFFFF) + __popcll(ba & below);
-    posB = (off >> 16) + __popcll(bb & below);
-    totalA = tot & 0xFFFF;
-    totalB = tot >> 16;
-}
-
-// workgroup-wide maxima of two non-negative floats with one pair of barriers
-template <int BLOCK = kBlock> PS_D void block_max2(float &a, float &b, float2 *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a = fmaxf(a, __shfl_down(a, o, 64));
-        b = fmaxf(b, __shfl_down(b, o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = make_float2(a, b);
-    __syncthreads();
-    float2 r = red[0];
-#pragma unroll
-    for (int i = 1; i < BLOCK / 64; ++i) {
-        r.x = fmaxf(r.x, red[i].x);
-        r.y = fmaxf(r.y, red[i].y);
-    }
-    __syncthreads();
-    a = r.x;
-    b = r.y;
-}
-
-// workgroup-wide maximum of a non-negative float (4 waves)
-template <int BLOCK = kBlock> PS_D float block_max(float v, float *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-#pragma unroll
-    for (int i = 1; i < BLOCK / 64; ++i) r = fmaxf(r, red[i]);
-    __syncthreads();
-    return r;
-}
-
-struct PrepArgs {
-    float fx, fy, cx, cy;   // camera matrix entries (cv::Mat CV_32FC1, RGBD.cpp:93-96)
-    double thrE;            // inlierThresholdEuclidean
-    int mode;               // RANSAC::ERROR_VERSION
-    int cap;
-    int ptsStride;          // floats between consecutive frames' point blocks (PsFrameSet::ptsFrameStride / 4; cap * 3 when dense)
-    int32_t *zeroCounts;    // optional: the first zeroH counts of every pair (row stride zeroStride) to clear for kernel 3's
-    int zeroH;              // split-range atomics (saves a memset launch)
-    int zeroStride;
-    int32_t *zeroSurvA, *zeroSurvB; // optional: per-pair survivor counters of the staged scoring to clear (ps_score_fast.h)
-    int skipE, skipF;       // the reprojection kernels' record forms no launch of this call will read (RecPtrs::E / ::F)
-};
-
-// Where kernel 2 puts the records of the depth-valid matches (scratch arena, [P][cap] each unless noted).
-struct RecPtrs {
-    float4 *A;  // prev xyz + squared Euclid bound
-    float4 *B;  // cur xyz, w = 1
-    float4 *C;  // projections of prev and cur (realOld u v, realNew u v)
-    int4 *D;    // (index in the match list, queryIdx, trainIdx, 0)
-    float4 *E;  // offsets c - real of the decision-exact scoring paths: (cx - uOld, cx - uNew, cy - vOld, cy - vNew)
-#ifdef PS_STREAM_DIAG
-    float4 *S;  // -DPS_STREAM_DIAG builds only: a shadow block kernel 2 writes every record a second time into (7 x 16 B per match;
-                // nothing reads it): doubles kernel 2's write traffic for the A/B of profiles/r06*/records_traffic_ab.txt
-#endif
-    float2 *F;  // the fast scoring kernel's packed match record for large launches, 40 B = 5 float2 per match, laid out as
-                // the SGPR pairs its packed instructions take (one s_load_dwordx8 + one dwordx2, no repacking; 8 B less
-                // scalar-cache footprint per match than prev + cur + offsets):
-                // (cur.x, prev.x) (cur.y, prev.y) (cur.z, prev.z) (cx - uOld, cx - uNew) (cy - vOld, cy - vNew)
-    float *G;   // the Euclidean fast scoring kernel's pair-interleaved record (ps_score_euclid.h), [P][ceil(cap/2)][12 or 16]:
-                // match 2k in the even floats, match 2k+1 in the odd ones; null unless that kernel will run (it then
-                // replaces E and F, which only the reprojection kernels read)
-};
-
-// Builds the records of depth-valid match number v of pair p; returns the largest |offset| of E.
-// `fixedBound` = sq_bound_f32(inlierThresholdEuclidean), the same for every match unless the mode is ADAPTIVE (the caller
-// computes it once: the exact squared-domain bound costs two or three square roots).
-PS_D float write_records(const PrepArgs &a, const RecPtrs &r, int p, int v, int srcIdx, int q, int t, float px, float py,
-                         float pz, float cx_, float cy_, float cz_, float fixedBound)
-{
-    // Euclid rule of RANSAC.cpp:268-272: thr = inlierThresholdEuclidean (* prev.z in ADAPTIVE mode),
-    // turned into its exact squared-domain bound.
-    const float bound = a.mode == PS_ADAPTIVE_ERROR ? sq_bound_f32(a.thrE * (double)pz) : fixedBound;
-    const size_t slot = (size_t)p * a.cap + (size_t)v;
-    r.A[slot] = make_float4(px, py, pz, bound);
-    r.B[slot] = make_float4(cx_, cy_, cz_, 1.0f);
-    r.D[slot] = make_int4(srcIdx, q, t, 0);
-    // the projections (four divisions) are read by the reprojection metrics only
-    const bool euclidOnly = a.mode == PS_EUCLIDEAN_ERROR || a.mode == PS_ADAPTIVE_ERROR;
-    float ou = 0.0f, ov = 0.0f, nu = 0.0f, nv = 0.0f;
-    if (!euclidOnly) {
-        project(px, py, pz, a.fx, a.fy, a.cx, a.cy, ou, ov);    // realOld  (RANSAC.cpp:357-358)
-        project(cx_, cy_, cz_, a.fx, a.fy, a.cx, a.cy, nu, nv); // realNew  (RANSAC.cpp:352-353)
-        r.C[slot] = make_float4(ou, ov, nu, nv);
-    }
-    if (r.G != nullptr) {
-        // Euclidean metrics: the pair-interleaved operands of ps_ransac_score_euclid; errorVersion 4 normalises the match
-        // by its own depth (the adaptive threshold thr * prev.z becomes the constant thr, ps_score_euclid.h)
-        const bool adaptive = a.mode == PS_ADAPTIVE_ERROR;
-        const int rf = adaptive ? 16 : 12;
-        float *g = r.G + ((size_t)p * (size_t)((a.cap + 1) >> 1) + (size_t)(v >> 1)) * rf + (v & 1);
-        if (adaptive) {
-            const float w = 1.0f / pz;
-            g[0] = cx_ * w; g[2] = cy_ * w; g[4] = cz_ * w; g[6] = w;
-            g[8] = px * w; g[10] = py * w; g[12] = pz * w; g[14] = 0.0f;
-        } else {
-            g[0] = cx_; g[2] = cy_; g[4] = cz_;
-            g[6] = px; g[8] = py; g[10] = pz;
-        }
-        return 0.0f;
-    }
-    if (euclidOnly) return 0.0f;
-    // offsets of the decision-exact scoring paths (ps_score_fast.h): predicted - real = quotient + (c - real)
-    // (laid out as the two v_pk_fma_f32 operand pairs: u offsets of both directions, then v offsets)
-    const float4 e = make_float4(a.cx - ou, a.cx - nu, a.cy - ov, a.cy - nv);
-    if (!a.skipE) r.E[slot] = e;
-    if (!a.skipF) {
-        float2 *f = r.F + 5 * slot;
-        f[0] = make_float2(cx_, px); f[1] = make_float2(cy_, py); f[2] = make_float2(cz_, pz);
-        f[3] = make_float2(e.x, e.y); f[4] = make_float2(e.z, e.w);
-    }
-#ifdef PS_STREAM_DIAG
-    if (r.S != nullptr) { // (diagnostic build: every record once more, into a block nothing reads)
-        float4 *sh = r.S + 7 * slot;
-        sh[0] = make_float4(px, py, pz, bound); sh[1] = make_float4(cx_, cy_, cz_, 1.0f); sh[2] = make_float4(ou, ov, nu, nv);
-        sh[3] = make_float4((float)srcIdx, (float)q, (float)t, 0.0f); sh[4] = make_float4(cx_, px, cy_, py);
-        sh[5] = make_float4(cz_, pz, e.x, e.y); sh[6] = make_float4(e.z, e.w, 0.0f, 0.0f);
-    }
-#endif
-    // (a NaN offset reports an infinite bound: the decision-exact kernels then leave the pair to the value-exact code)
-    const bool num = e.x == e.x && e.y == e.y && e.z == e.z && e.w == e.w;
-    return num ? fmaxf(fmaxf(fabsf(e.x), fabsf(e.y)), fmaxf(fabsf(e.z), fabsf(e.w))) : INFINITY;
-}
-
-// An odd number of depth-valid matches leaves the second half of the last pair record unwritten: it repeats the first
-// (finite, inside the pair's bounds; the scoring kernel does not count it).  Called by one thread after the records of
-// the pair are visible to it.
-PS_D void finish_pair_records(const PrepArgs &a, const RecPtrs &r, int p, int M)
-{
-    if (r.G == nullptr || !(M & 1)) return;
-    const int rf = a.mode == PS_ADAPTIVE_ERROR ? 16 : 12;
-    float *g = r.G + ((size_t)p * (size_t)((a.cap + 1) >> 1) + (size_t)(M >> 1)) * rf;
-    for (int i = 0; i < rf; i += 2) g[i + 1] = g[i];
-}
-
 // ------------------------------------------------------------------------------------------
 // Kernel 2.  Cross-check + ordered compaction (BFMatcher with crossCheck=true) followed by the
 // depth filter of RANSAC::estimateTransformation (RANSAC.cpp:65-74) and record building.
@@ -386,8 +164,6 @@ __global__ __launch_bounds__(BLOCK) void ps_crosscheck_prep(const float *__restr
     phase_stamp(stamps, 0);
     __shared__ int s_wsum[2 * (BLOCK / 64)];
     __shared__ float2 s_red[BLOCK / 64];
-    float cm = 0.0f; // largest |coordinate| among this pair's depth-valid matches
-    float um = 0.0f; // largest |c - projection| among them (NaN offsets are skipped by fmaxf; they only ever score "out")
     const int p = blockIdx.x;
     const int cap = a.cap;
     const int fq = pairs[2 * p], ft = pairs[2 * p + 1];
@@ -412,7 +188,7 @@ __global__ __launch_bounds__(BLOCK) void ps_crosscheck_prep(const float *__restr
     phase_stamp(stamps, 1); // best[q] built
     const float *pp = pts + (size_t)fq * a.ptsStride; // (floats between consecutive frames' point blocks: cap * 3 when dense)
     const float *cp = pts + (size_t)ft * a.ptsStride;
-    int base = 0, vbase = 0;
+    int base = 0;
     // one candidate per thread and trip; the next trip's key and points are fetched before this trip's scan, so that the
     // gather's latency (the points were written by another launch: nothing is cached) runs beside it instead of in front of
     // every trip (a single pair with 1024 threads makes two trips)
@@ -429,7 +205,7 @@ __global__ __launch_bounds__(BLOCK) void ps_crosscheck_prep(const float *__restr
             c.cx = cp[3 * t]; c.cy = cp[3 * t + 1]; c.cz = cp[3 * t + 2];
         }
     };
-    const float fixedBound = (WITH_RECORDS && a.mode != PS_ADAPTIVE_ERROR) ? sq_bound_f32(a.thrE) : 0.0f;
+    PairRecords pr(a, rec, p, WITH_RECORDS);
     Cand cur;
     fetch((int)threadIdx.x, cur);
     int trip = 0;
@@ -443,10 +219,10 @@ __global__ __launch_bounds__(BLOCK) void ps_crosscheck_prep(const float *__restr
         const bool has = key != kNoKey;
         const int t = (int)(key & 0xFFFFu);
         const float px = cur.px, py = cur.py, pz = cur.pz, cx_ = cur.cx, cy_ = cur.cy, cz_ = cur.cz;
-        const bool ok = WITH_RECORDS && has && depth_ok(px, py, pz) && depth_ok(cx_, cy_, cz_);
+        const bool ok = WITH_RECORDS && has && match_depth_ok(px, py, pz, cx_, cy_, cz_);
         // both ordered compactions (cross-check survivors; depth-valid ones among them) with one barrier
         int pos, total, vpos, vtotal;
-        block_scan_flags2_alt<BLOCK>(has, ok, pos, total, vpos, vtotal, s_wsum, trip);
+        block_scan_flags2<BLOCK, false>(has, ok, pos, total, vpos, vtotal, s_wsum, trip);
         if (has) {
             PsDMatch m;
             m.queryIdx = q;
@@ -455,138 +231,14 @@ __global__ __launch_bounds__(BLOCK) void ps_crosscheck_prep(const float *__restr
             m.distance = (float)(key >> 16);
             matches[(size_t)p * cap + base + pos] = m;
         }
-        if (WITH_RECORDS) {
-            if (ok) {
-                um = fmaxf(um, write_records(a, rec, p, vbase + vpos, base + pos, q, t, px, py, pz, cx_, cy_, cz_, fixedBound));
-                cm = fmaxf(cm, fmaxf(fmaxf(fabsf(px), fabsf(py)), fmaxf(fabsf(pz), fmaxf(fabsf(cx_), fmaxf(fabsf(cy_), fabsf(cz_))))));
-            }
-            vbase += vtotal;
-        }
+        if (WITH_RECORDS) pr.add(ok, vpos, vtotal, base + pos, q, t, px, py, pz, cx_, cy_, cz_);
         base += total;
         cur = nxt;
     }
     phase_stamp(stamps, 2); // matches compacted, records written
-    if (WITH_RECORDS) {
-        float c = cm, u = um;
-        block_max2<BLOCK>(c, u, s_red);
-        if (threadIdx.x == 0) cmaxOut[p] = make_float2(c, u);
-        if (threadIdx.x == 0) finish_pair_records(a, rec, p, vbase); // (block_max ends with a barrier: the records are visible)
-        if (a.zeroCounts)
-            for (int i = threadIdx.x; i < a.zeroH; i += BLOCK) a.zeroCounts[(size_t)p * a.zeroStride + i] = 0;
-    }
-    if (threadIdx.x == 0) {
-        numMatches[p] = base;
-        if (WITH_RECORDS) mvalid[p] = vbase;
-        if (WITH_RECORDS && a.zeroSurvA) {
-            a.zeroSurvA[p] = 0;
-            a.zeroSurvB[p] = 0;
-        }
-    }
+    if (WITH_RECORDS) pr.finish<BLOCK>(s_red, mvalid, cmaxOut);
+    if (threadIdx.x == 0) numMatches[p] = base;
     phase_stamp(stamps, 3); // bounds, split operands, counters cleared
-}
-
-// Pair p's records from a caller-supplied list of m matches over the point blocks prev / cur, by one work-group of kBlock threads
-// in tiles of kBlock matches: the depth filter of RANSAC.cpp:65-74, the ordered compaction, write_records, then the pair's count,
-// bounds and cleared counters -- what ps_crosscheck_prep and ps_map_emit leave for their pairs.  CHECKED: the list comes from
-// device memory nobody has looked at: a match whose queryIdx lies outside 0 .. nprev-1 or whose trainIdx lies outside 0 .. ncur-1
-// is not followed and fails the filter, and `clean` receives the list with the trainIdx of every such match replaced by -1 (what
-// kernel 4 reads for pointInlierRatio: a train index it skips).
-template <bool CHECKED>
-PS_D void prep_match_list(const float *__restrict__ prev, int nprev, const float *__restrict__ cur, int ncur,
-                          const PsDMatch *__restrict__ matches, int m, const PrepArgs &a, const RecPtrs &rec, int p,
-                          int32_t *__restrict__ mvalid, float2 *__restrict__ cmaxOut, PsDMatch *__restrict__ clean, int *s_wsum,
-                          float *s_red)
-{
-    float cm = 0.0f, um = 0.0f;
-    int vbase = 0;
-    const float fixedBound = a.mode != PS_ADAPTIVE_ERROR ? sq_bound_f32(a.thrE) : 0.0f;
-    for (int i0 = 0; i0 < m; i0 += kBlock) {
-        const int i = i0 + threadIdx.x;
-        float px = 0, py = 0, pz = 0, cx_ = 0, cy_ = 0, cz_ = 0;
-        int q = 0, t = 0;
-        bool ok = false;
-        if (i < m) {
-            PsDMatch mt = matches[i];
-            q = mt.queryIdx;
-            t = mt.trainIdx;
-            const bool in = !CHECKED || (q >= 0 && q < nprev && t >= 0 && t < ncur);
-            if (CHECKED) {
-                if (!in) mt.trainIdx = -1;
-                clean[i] = mt;
-            }
-            if (in) {
-                px = prev[3 * q]; py = prev[3 * q + 1]; pz = prev[3 * q + 2];
-                cx_ = cur[3 * t]; cy_ = cur[3 * t + 1]; cz_ = cur[3 * t + 2];
-                ok = depth_ok(px, py, pz) && depth_ok(cx_, cy_, cz_);
-            }
-        }
-        int vtotal;
-        int vpos = block_scan_flag(ok, vtotal, s_wsum);
-        if (ok) {
-            um = fmaxf(um, write_records(a, rec, p, vbase + vpos, i, q, t, px, py, pz, cx_, cy_, cz_, fixedBound));
-            cm = fmaxf(cm, fmaxf(fmaxf(fabsf(px), fabsf(py)), fmaxf(fabsf(pz), fmaxf(fabsf(cx_), fmaxf(fabsf(cy_), fabsf(cz_))))));
-        }
-        vbase += vtotal;
-    }
-    float c = block_max(cm, s_red);
-    float u = block_max(um, s_red);
-    if (threadIdx.x == 0) {
-        mvalid[p] = vbase;
-        cmaxOut[p] = make_float2(c, u);
-        finish_pair_records(a, rec, p, vbase); // (block_max ends with a barrier: the records are visible)
-    }
-    if (a.zeroCounts)
-        for (int i = threadIdx.x; i < a.zeroH; i += kBlock) a.zeroCounts[(size_t)p * a.zeroStride + i] = 0;
-    if (threadIdx.x == 0 && a.zeroSurvA) { // the staged scoring's survivor counters, as ps_crosscheck_prep does
-        a.zeroSurvA[p] = 0;
-        a.zeroSurvB[p] = 0;
-    }
-}
-
-// Depth filter + records for a caller-supplied match list (stand-alone RANSAC entry point; the host checked the indices).
-__global__ __launch_bounds__(kBlock) void ps_prep_from_matches(const float *__restrict__ prev,
-                                                               const float *__restrict__ cur,
-                                                               const PsDMatch *__restrict__ matches, int m, PrepArgs a,
-                                                               RecPtrs rec, int32_t *__restrict__ mvalid,
-                                                               float2 *__restrict__ cmaxOut)
-{
-    __shared__ int s_wsum[kBlock / 64];
-    __shared__ float s_red[kBlock / 64];
-    prep_match_list<false>(prev, 0, cur, 0, matches, m, a, rec, 0, mvalid, cmaxOut, nullptr, s_wsum, s_red);
-}
-
-// The point block of one set of a device-resident group of point sets (PsPointSets, include/putslam_hip.h)
-struct PointSetsArgs {
-    const float *pts;
-    const int32_t *counts;
-    int numSets, capacity;
-    int strideFloats; // floats between consecutive sets' blocks
-};
-
-// The batched form: one work-group per pair over device-resident lists (ps_ransac_match_lists).  Pair p matches set
-// pairs[2p] of `prev` with set pairs[2p + 1] of `cur` (pairs = null: set p of both).  numMatches[p] outside 0 .. cap, a set index
-// outside its group or a set count outside 0 .. capacity: the pair's list counts as empty -- numClean[p] = 0, what kernel 4 is
-// given as the pair's match count, so that it writes no mask byte.
-__global__ __launch_bounds__(kBlock) void ps_prep_match_lists(PointSetsArgs prev, PointSetsArgs cur, const int32_t *__restrict__ pairs,
-                                                              const PsDMatch *__restrict__ matches,
-                                                              const int32_t *__restrict__ numMatches, PrepArgs a, RecPtrs rec,
-                                                              int32_t *__restrict__ mvalid, float2 *__restrict__ cmaxOut,
-                                                              PsDMatch *__restrict__ clean, int32_t *__restrict__ numClean)
-{
-    __shared__ int s_wsum[kBlock / 64];
-    __shared__ float s_red[kBlock / 64];
-    const int p = blockIdx.x;
-    const int sq = pairs ? pairs[2 * p] : p, st = pairs ? pairs[2 * p + 1] : p;
-    const bool sets = sq >= 0 && sq < prev.numSets && st >= 0 && st < cur.numSets;
-    const int nq = sets ? prev.counts[sq] : -1, nt = sets ? cur.counts[st] : -1;
-    const int given = numMatches[p];
-    const bool ok = sets && nq >= 0 && nq <= prev.capacity && nt >= 0 && nt <= cur.capacity && given >= 0 && given <= a.cap;
-    const int m = ok ? given : 0;
-    if (threadIdx.x == 0) numClean[p] = m;
-    const size_t row = (size_t)p * (size_t)a.cap;
-    prep_match_list<true>(prev.pts + (size_t)(ok ? sq : 0) * (size_t)prev.strideFloats, nq,
-                          cur.pts + (size_t)(ok ? st : 0) * (size_t)cur.strideFloats, nt, matches + row, m, a, rec, p, mvalid, cmaxOut,
-                          clean + row, s_wsum, s_red);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1339,7 +991,7 @@ __global__ __launch_bounds__(BLOCK) void ps_select_refit(const float4 *__restric
                 }
             }
             int total;
-            int pos = block_scan_flag_alt<BLOCK>(in, total, s_wsum, trip);
+            int pos = block_scan_flag<BLOCK, false>(in, total, s_wsum, trip);
             if (in) {
                 const int slot = kin + pos;
                 list[slot] = i;
@@ -1614,29 +1266,15 @@ __global__ __launch_bounds__(kBlock) void ps_exclusive_scan(const int32_t *__res
                                                             int32_t *__restrict__ offsets)
 {
     __shared__ int s_w[kBlock / 64];
-    __shared__ int s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int carry = 0; // (uniform: every thread adds the same sums)
     for (int i0 = 0; i0 < n; i0 += kBlock) {
         const int i = i0 + threadIdx.x;
-        int v = i < n ? counts[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            int t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        int off = s_carry;
-        for (int w = 0; w < wv; ++w) off += s_w[w];
-        if (i < n) offsets[i] = off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == kBlock - 1) s_carry = off + incl;
-        __syncthreads();
+        int sum;
+        const int ex = block_scan_int<kBlock>(i < n ? counts[i] : 0, sum, s_w);
+        if (i < n) offsets[i] = carry + ex;
+        carry += sum;
     }
-    if (threadIdx.x == 0) offsets[n] = s_carry;
+    if (threadIdx.x == 0) offsets[n] = carry;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2164,7 +1802,7 @@ __global__ __launch_bounds__(kBlock) void ps_pack_results_to_host(const PsDMatch
         const int i = i0 + tid;
         const bool in = i < n && mk[i] != 0;
         int pos, total, posB, totalB;
-        block_scan_flags2_alt<kBlock>(in, false, pos, total, posB, totalB, s_w, trip);
+        block_scan_flags2<kBlock, false>(in, false, pos, total, posB, totalB, s_w, trip);
         if (in) dst[base + pos] = src[i];
         base += total;
     }

@@ -25,8 +25,8 @@
 #include <cstdint>
 
 #include "ps_glue.h"
+#include "ps_block.h" // block_scan_int, block_scan_flag
 #include "ps_kernels.h"
-#include "ps_map_match.h" // block_scan_int
 
 namespace psdev {
 

@@ -67,26 +67,6 @@ PS_D int map_count(const int32_t *__restrict__ n, int frame, int frames, int cap
     return v < 0 ? 0 : (v > cap ? cap : v);
 }
 
-PS_D unsigned long long wave_min_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        unsigned long long other = __shfl_down(v, o, 64);
-        v = other < v ? other : v;
-    }
-    return __shfl(v, 0, 64);
-}
-
-PS_D uint32_t wave_min_u32(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t other = (uint32_t)__shfl_down((int)v, o, 64);
-        v = other < v ? other : v;
-    }
-    return (uint32_t)__shfl((int)v, 0, 64);
-}
-
 // One map feature against the pair's frame: what a sweep from global memory needs
 struct MapSphere {
     float mx, my, mz;
@@ -320,30 +300,6 @@ struct MapBinRows {
 
 template <int F> __global__ __launch_bounds__(kMapBlock) void ps_map_sweep(MapBinArgs b) { map_sweep<F, MapBinRows>(b); }
 
-// exclusive prefix of v over the work-group, in thread order; total = the sum
-template <int BLOCK> PS_D int block_scan_int(int v, int &total, int *wsum)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int off = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < BLOCK / 64; ++i) {
-        const int s = wsum[i];
-        if (i < w) off += s;
-        total += s;
-    }
-    __syncthreads();
-    return off + incl - v;
-}
-
 // One work-group per pair: the chunks' matches in (j, i) order, the signed and the clamped count, and (REC) the scoring
 // records of the depth-valid ones as ps_prep_from_matches builds them for a single pair.
 template <bool REC, int BLOCK>
@@ -352,8 +308,8 @@ __global__ __launch_bounds__(BLOCK) void ps_map_emit(MapArgs a, PrepArgs pa, Rec
                                                      int32_t *__restrict__ mvalid, float2 *__restrict__ cmaxOut)
 {
     extern __shared__ __align__(16) int s_off[]; // chunks + 1 exclusive offsets
-    __shared__ int s_wsum[BLOCK / 64];
-    __shared__ float s_red[BLOCK / 64];
+    __shared__ int s_wsum[(REC ? 2 : 1) * (BLOCK / 64)]; // (the one-barrier flag scan of the record stage takes two sets)
+    __shared__ float2 s_red[BLOCK / 64];
     const int p = blockIdx.x;
     const int view = a.pairs[2 * p], frame = a.pairs[2 * p + 1];
     const int nmap = map_count(a.mapN, view, a.mapFrames, a.mapCap);
@@ -378,10 +334,9 @@ __global__ __launch_bounds__(BLOCK) void ps_map_emit(MapArgs a, PrepArgs pa, Rec
     PsDMatch *__restrict__ out = matches + (size_t)p * a.maxMatches;
     const float *__restrict__ prev = a.mapPts + (size_t)(m > 0 ? view : 0) * a.mapPtsStride;
     const float *__restrict__ cur = a.curPts + (size_t)(m > 0 ? frame : 0) * a.curPtsStride;
-    float cm = 0.0f, um = 0.0f;
-    int vbase = 0;
-    const float fixedBound = (REC && pa.mode != PS_ADAPTIVE_ERROR) ? sq_bound_f32(pa.thrE) : 0.0f;
-    for (int i0 = 0; i0 < m; i0 += BLOCK) {
+    PairRecords pr(pa, rec, p, REC);
+    int trip = 0;
+    for (int i0 = 0; i0 < m; i0 += BLOCK, ++trip) {
         const int i = i0 + threadIdx.x;
         float px = 0, py = 0, pz = 0, cx_ = 0, cy_ = 0, cz_ = 0;
         int q = 0, t = 0;
@@ -401,34 +356,16 @@ __global__ __launch_bounds__(BLOCK) void ps_map_emit(MapArgs a, PrepArgs pa, Rec
             if (REC) {
                 px = prev[3 * q]; py = prev[3 * q + 1]; pz = prev[3 * q + 2];
                 cx_ = cur[3 * t]; cy_ = cur[3 * t + 1]; cz_ = cur[3 * t + 2];
-                ok = depth_ok(px, py, pz) && depth_ok(cx_, cy_, cz_);
+                ok = match_depth_ok(px, py, pz, cx_, cy_, cz_);
             }
         }
         if (REC) {
             int vtotal;
-            const int vpos = block_scan_flag<BLOCK>(ok, vtotal, s_wsum);
-            if (ok) {
-                um = fmaxf(um, write_records(pa, rec, p, vbase + vpos, i, q, t, px, py, pz, cx_, cy_, cz_, fixedBound));
-                cm = fmaxf(cm, fmaxf(fmaxf(fabsf(px), fabsf(py)), fmaxf(fabsf(pz), fmaxf(fabsf(cx_), fmaxf(fabsf(cy_), fabsf(cz_))))));
-            }
-            vbase += vtotal;
+            const int vpos = block_scan_flag<BLOCK, false>(ok, vtotal, s_wsum, trip);
+            pr.add(ok, vpos, vtotal, i, q, t, px, py, pz, cx_, cy_, cz_);
         }
     }
-    if (REC) {
-        const float cc = block_max<BLOCK>(cm, s_red);
-        const float uu = block_max<BLOCK>(um, s_red);
-        if (threadIdx.x == 0) {
-            mvalid[p] = vbase;
-            cmaxOut[p] = make_float2(cc, uu);
-            finish_pair_records(pa, rec, p, vbase); // (block_max ends with a barrier: the records are visible)
-        }
-        if (pa.zeroCounts)
-            for (int i = threadIdx.x; i < pa.zeroH; i += BLOCK) pa.zeroCounts[(size_t)p * pa.zeroStride + i] = 0;
-        if (threadIdx.x == 0 && pa.zeroSurvA) { // the staged scoring's survivor counters, as ps_crosscheck_prep does
-            pa.zeroSurvA[p] = 0;
-            pa.zeroSurvB[p] = 0;
-        }
-    }
+    if (REC) pr.finish<BLOCK>(s_red, mvalid, cmaxOut);
     if (threadIdx.x == 0) {
         numMatches[p] = over ? -total : total;
         if (numClamped) numClamped[p] = m;

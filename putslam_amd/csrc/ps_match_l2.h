@@ -366,9 +366,8 @@ __global__ __launch_bounds__(BLOCK) void ps_l2_crosscheck(L2Args a, const float 
     // step 3, and what ps_crosscheck_prep does with its matches
     const float *pp = REC ? pts + (size_t)(nq > 0 ? fq : 0) * pa.ptsStride : nullptr; // (a match implies both frames lie in the set)
     const float *cp = REC ? pts + (size_t)(nq > 0 && nt > 0 ? ft : 0) * pa.ptsStride : nullptr;
-    const float fixedBound = (REC && pa.mode != PS_ADAPTIVE_ERROR) ? sq_bound_f32(pa.thrE) : 0.0f;
-    float cm = 0.0f, um = 0.0f;
-    int base = 0, vbase = 0, trip = 0;
+    PairRecords pr(pa, rec, p, REC);
+    int base = 0, trip = 0;
     for (int q0 = 0; q0 < nq; q0 += BLOCK, ++trip) {
         const int q = q0 + (int)threadIdx.x;
         const unsigned long long key = q < nq ? s_l2best[q] : kNoKeyL2;
@@ -379,10 +378,10 @@ __global__ __launch_bounds__(BLOCK) void ps_l2_crosscheck(L2Args a, const float 
         if (REC && has) {
             px = pp[3 * q]; py = pp[3 * q + 1]; pz = pp[3 * q + 2];
             cx_ = cp[3 * t]; cy_ = cp[3 * t + 1]; cz_ = cp[3 * t + 2];
-            ok = depth_ok(px, py, pz) && depth_ok(cx_, cy_, cz_);
+            ok = match_depth_ok(px, py, pz, cx_, cy_, cz_);
         }
         int pos, total, vpos, vtotal;
-        block_scan_flags2_alt<BLOCK>(has, ok, pos, total, vpos, vtotal, s_wsum, trip);
+        block_scan_flags2<BLOCK, false>(has, ok, pos, total, vpos, vtotal, s_wsum, trip);
         if (has) {
             PsDMatch m;
             m.queryIdx = q;
@@ -391,29 +390,10 @@ __global__ __launch_bounds__(BLOCK) void ps_l2_crosscheck(L2Args a, const float 
             m.distance = __uint_as_float((uint32_t)(key >> 32));
             matches[(size_t)p * cap + base + pos] = m;
         }
-        if (REC) {
-            if (ok) {
-                um = fmaxf(um, write_records(pa, rec, p, vbase + vpos, base + pos, q, t, px, py, pz, cx_, cy_, cz_, fixedBound));
-                cm = fmaxf(cm, fmaxf(fmaxf(fabsf(px), fabsf(py)), fmaxf(fabsf(pz), fmaxf(fabsf(cx_), fmaxf(fabsf(cy_), fabsf(cz_))))));
-            }
-            vbase += vtotal;
-        }
+        if (REC) pr.add(ok, vpos, vtotal, base + pos, q, t, px, py, pz, cx_, cy_, cz_);
         base += total;
     }
-    if (REC) {
-        block_max2<BLOCK>(cm, um, s_red);
-        if (threadIdx.x == 0) {
-            cmaxOut[p] = make_float2(cm, um);
-            mvalid[p] = vbase;
-            finish_pair_records(pa, rec, p, vbase); // (block_max2 ends with a barrier: the records are visible)
-            if (pa.zeroSurvA) {
-                pa.zeroSurvA[p] = 0;
-                pa.zeroSurvB[p] = 0;
-            }
-        }
-        if (pa.zeroCounts)
-            for (int i = threadIdx.x; i < pa.zeroH; i += BLOCK) pa.zeroCounts[(size_t)p * pa.zeroStride + i] = 0;
-    }
+    if (REC) pr.finish<BLOCK>(s_red, mvalid, cmaxOut);
     if (threadIdx.x == 0) numMatches[p] = base;
 }
 

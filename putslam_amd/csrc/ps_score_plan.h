@@ -12,7 +12,7 @@
 
 #include "putslam_hip.h"
 
-// (mirrors of psdev::kBlock, ps_kernels.h, and psdev::kPrefixFixed / kPrefixAdaptive / kStages, ps_score_fast.h: the device
+// (mirrors of psdev::kBlock, ps_block.h, and psdev::kPrefixFixed / kPrefixAdaptive / kStages, ps_score_fast.h: the device
 // translation unit checks them with static_asserts)
 constexpr int kPlanBlock = 256, kPlanPrefixFixed = kPlanBlock, kPlanPrefixAdaptive = 64, kPlanStages = 3;
 

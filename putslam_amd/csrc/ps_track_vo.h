@@ -1,8 +1,8 @@
 // ps_track_vo.h -- the tracking VO step without a host step (include/putslam_hip.h: "The tracking VO step"; Matcher::trackKLT,
 // matcher.cpp:147-211): the estimator over caller-supplied device-resident match lists, the rows a tracked frame leaves, and the
 // queue of launches that is the whole step.  Part of the device translation unit (ps_capi.hip), after ps_klt.h and
-// ps_frame_assembly.h, whose launches and checks it uses.  The record builder ps_prep_match_lists stands in ps_kernels.h beside
-// the single-pair kernel it shares its body with.
+// ps_frame_assembly.h, whose launches and checks it uses.  The record builder ps_prep_match_lists stands in ps_pair_records.h
+// beside the single-pair kernel it shares its body with.
 #pragma once
 
 namespace psdev {

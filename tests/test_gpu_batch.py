@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 
 from putslam_amd import synth
-from putslam_amd._abi import (EST_FIXED, EST_RANSAC, EST_USAC, EUCLIDEAN_ERROR, REPROJECTION_ERROR, TUM_FR1_K,
+from putslam_amd._abi import (ADAPTIVE_ERROR, EST_FIXED, EST_RANSAC, EST_USAC, EUCLIDEAN_ERROR, REPROJECTION_ERROR, TUM_FR1_K,
                               default_ransac_params, make_config)
 
 pytestmark = pytest.mark.gpu
@@ -109,6 +109,47 @@ def test_ragged_frames_and_arbitrary_pairs(ctx, oracle):
     g = pb.download()
     c = oracle.vo_pairs(prm, cfg, TUM_FR1_K, seq["desc"], seq["pts"], nk, pairs, threads=2)
     _compare(g, c, len(pairs))
+
+
+@pytest.mark.parametrize("P", [1, 17])
+@pytest.mark.parametrize("mode,prune", [(EUCLIDEAN_ERROR, 0), (ADAPTIVE_ERROR, 2), (REPROJECTION_ERROR, 0), (REPROJECTION_ERROR, 2)])
+def test_record_stage_at_its_edges(oracle, mode, prune, P):
+    """Kernel 2's record stage for both of its work-group sizes (at most 16 pairs: 1024 threads, more: 256) on frames of 1100 key
+    points, so that either size makes more than one trip: an odd number of depth-valid matches under both Euclidean error versions
+    (the pair-interleaved record's tail), depth-invalid matches on both sides of every tile seam, a pair without a depth-valid
+    match, both record forms of the reprojection kernels (complete scoring of a small batch: the three-record form; staged: the
+    packed one), and the staged scoring's counters cleared for call after call on one context.  Against the oracle."""
+    from putslam_amd import api
+    from putslam_amd.device_batch import FrameSetDevice, PairBatchDevice, run_pairs
+    seq = synth.make_sequence(2, 1100, config=3, index=3100)
+    desc, pts = np.concatenate([seq["desc"], seq["desc"][:1]]), np.concatenate([seq["pts"], seq["pts"][:1]])
+    pts[2, :, 2] = 0                                              # frame 2: frame 0 with every depth missing
+    nk = np.full(3, 1100, np.int32)
+    three = [(0, 1), (2, 1), (1, 0)]
+    prm = default_ransac_params(mode)
+    cfg, _ = make_config(EST_FIXED, 1024, seed=3)
+    c2 = api.Context(0)
+    c2.set_option("prune", prune)                                 # 2: the staged form whatever the batch size; 0: complete scoring
+    fs = FrameSetDevice(desc, pts, nk)
+    valid = []
+    for pairs in ([[pr] for pr in three] if P == 1 else [(three * 6)[:P]] * 2):   # three calls in a row, or the batch twice
+        pairs = np.array(pairs, np.int32)
+        pb = PairBatchDevice(pairs, fs.max_kpts)
+        run_pairs(c2, prm, cfg, TUM_FR1_K, fs, pb)
+        g = pb.download()
+        if pairs[0][0] != 2:
+            assert (c2.get_option("last_staged_pairs") > 0) == (prune == 2)
+        c = oracle.vo_pairs(prm, cfg, TUM_FR1_K, desc, pts, nk, pairs, threads=4)
+        _compare(g, c, len(pairs))
+        for p, (a, b) in enumerate(pairs[:3]):                    # what the inputs are meant to hold
+            m = c["matches"][p, :int(c["numMatches"][p])]
+            z0, z1 = pts[a][m["queryIdx"], 2], pts[b][m["trainIdx"], 2]
+            bad = ~((z0 >= 0.1) & (z0 <= 6) & (z1 >= 0.1) & (z1 <= 6))
+            for seam in (256, 512, 768, 1024):
+                assert (bad & (m["queryIdx"] >= seam - 256) & (m["queryIdx"] < seam)).any() and (bad & (m["queryIdx"] >= seam)).any()
+            valid.append((int(c["stats"][p]["numMatchesValid"]), int(c["stats"][p]["accepted"])))
+    c2.close()
+    assert valid[1] == (0, 0) and any(v % 2 == 1 and ok for v, ok in valid)
 
 
 def test_full_size_properties(ctx, oracle):

@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import l2_match_ref as ref  # noqa: E402
 
 from putslam_amd import synth  # noqa: E402
-from putslam_amd._abi import (DMATCH_DTYPE, EST_FIXED, EST_RANSAC, EUCLIDEAN_ERROR, REPROJECTION_ERROR, TUM_FR1_K,  # noqa: E402
+from putslam_amd._abi import (ADAPTIVE_ERROR, DMATCH_DTYPE, EST_FIXED, EST_RANSAC, EUCLIDEAN_ERROR, REPROJECTION_ERROR, TUM_FR1_K,  # noqa: E402
                               default_ransac_params, make_config)
 
 pytestmark = pytest.mark.gpu
@@ -341,6 +341,54 @@ def test_vo_pairs(ctx, oracle, mode, est, H, kind, form):
             assert x == y or (np.isnan(x) and np.isnan(y)), (p, fld, x, y)
         accepted += int(g["stats"][p]["accepted"])
     assert accepted >= 3
+
+
+@pytest.mark.parametrize("P", [1, 17])
+@pytest.mark.parametrize("mode,prune", [(EUCLIDEAN_ERROR, 0), (ADAPTIVE_ERROR, 2), (REPROJECTION_ERROR, 0), (REPROJECTION_ERROR, 2)])
+def test_vo_pairs_record_stage_at_its_edges(oracle, mode, prune, P):
+    """The record stage of ps_l2_crosscheck for both of its work-group sizes (at most 16 pairs: 1024 threads, more: 256) on frames
+    of 1100 key points, so that either size makes more than one trip: an odd number of depth-valid matches under both Euclidean
+    error versions, depth-invalid matches on both sides of every tile seam, a pair without a depth-valid match, both record forms
+    of the reprojection kernels (complete scoring of a small batch, staged scoring), the staged scoring's counters cleared for
+    call after call on one context.  Against the restated matches and oracle.ransac_rigid3d with seed + p."""
+    from putslam_amd import api
+    from putslam_amd.device_batch import FrameSetF32Device, PairBatchDevice, run_vo_pairs_l2
+    seq = synth.make_float_sequence(2, 1100, kind="surf", index=31)
+    fdesc, pts = np.concatenate([seq["fdesc"], seq["fdesc"][:1]]), np.concatenate([seq["pts"], seq["pts"][:1]])
+    pts[2, :, 2] = 0                                              # frame 2: frame 0 with every depth missing
+    fs = FrameSetF32Device(fdesc, pts, np.full(3, 1100, np.int32))
+    three = [(0, 1), (2, 1), (1, 0)]
+    want = {pr: ref.match_l2(fdesc[pr[0]], fdesc[pr[1]]) for pr in three}
+    prm = default_ransac_params(mode)
+    seed = 3
+    cfg, _ = make_config(EST_FIXED, 1024, seed=seed)
+    c2 = api.Context(0)
+    c2.set_option("prune", prune)                                 # 2: the staged form whatever the batch size; 0: complete scoring
+    valid = {}
+    for pairs in ([[pr] for pr in three] if P == 1 else [(three * 6)[:P]] * 2):   # three calls in a row, or the batch twice
+        batch = PairBatchDevice(np.array(pairs, np.int32), 1100)
+        run_vo_pairs_l2(c2, prm, cfg, TUM_FR1_K, fs, batch)
+        g = batch.download()
+        if pairs[0][0] != 2:
+            assert (c2.get_option("last_staged_pairs") > 0) == (prune == 2)
+        for p, (a, b) in enumerate(pairs):
+            m, n = want[(a, b)], int(g["numMatches"][p])
+            assert n == len(m) and g["matches"][p, :n].tobytes() == m.tobytes(), p
+            cfgp, _ = make_config(EST_FIXED, 1024, seed=seed + p)
+            c = oracle.ransac_rigid3d(prm, cfgp, TUM_FR1_K, pts[a], pts[b], m)
+            assert np.array_equal(c["mask"], g["inlierMask"][p, :n]), p
+            assert c["pose"].T.astype(f32).tobytes() == g["pose"][p].tobytes(), p
+            for fld in STAT_FIELDS:
+                x, y = g["stats"][p][fld], c["stats"][fld]
+                assert x == y or (np.isnan(x) and np.isnan(y)), (p, fld, x, y)
+            valid[(a, b)] = (int(c["stats"]["numMatchesValid"]), int(c["stats"]["accepted"]))
+    c2.close()
+    for (a, b), m in want.items():                                # what the inputs are meant to hold
+        z0, z1 = pts[a][m["queryIdx"], 2], pts[b][m["trainIdx"], 2]
+        bad = ~((z0 >= 0.1) & (z0 <= 6) & (z1 >= 0.1) & (z1 <= 6))
+        for seam in (256, 512, 768, 1024):
+            assert (bad & (m["queryIdx"] >= seam - 256) & (m["queryIdx"] < seam)).any() and (bad & (m["queryIdx"] >= seam)).any()
+    assert valid[(2, 1)] == (0, 0) and any(v % 2 == 1 and ok for v, ok in valid.values())
 
 
 # ---------------------------------------------------------------- argument errors leave the outputs untouched

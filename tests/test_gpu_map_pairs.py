@@ -102,6 +102,46 @@ def test_large_frames(ctx, oracle):
     mref.compare(g, want, what="5000")
 
 
+@pytest.mark.parametrize("P", [1, 17])
+@pytest.mark.parametrize("mode,prune", [(EUCLIDEAN_ERROR, 0), (ADAPTIVE_ERROR, 2), (REPROJECTION_ERROR, 0), (REPROJECTION_ERROR, 2)])
+def test_record_stage_at_its_edges(oracle, mode, prune, P):
+    """The record stage of ps_map_emit for both of its work-group sizes (at most 16 pairs: 1024 threads, more: 256) on lists of more
+    than 1024 matches, so that either size makes more than one trip: an odd number of depth-valid matches under both Euclidean error
+    versions, depth-invalid matches (features beyond 6 m) on both sides of every tile seam, a pair without a depth-valid match, both
+    record forms of the reprojection kernels (complete scoring of a small batch, staged scoring), the staged scoring's counters
+    cleared for call after call on one context."""
+    from putslam_amd import api
+    rng = np.random.default_rng(41)
+    cap = 1800
+    frames = mref.make_frames(rng, oracle, [cap, cap], cap)
+    frames["pos"][0, rng.random(cap) < 0.15, 2] += 4.5            # some key points of frame 0 and all of frame 1 beyond the depth filter
+    frames["pos"][1, :, 2] += 5.5
+    views = mref.make_views(rng, frames, [cap, cap], cap, source=[0, 1], sigma=0.01)
+    ref = mref.Ref(oracle, views, frames)
+    two = [(0, 0), (1, 1)]
+    prm = default_ransac_params(mode)
+    prm.errorVersionMap = mode
+    c2 = api.Context(0)
+    c2.set_option("prune", prune)                                 # 2: the staged form whatever the batch size; 0: complete scoring
+    for pairs in ([[pr] for pr in two + two[:1]] if P == 1 else [(two * 9)[:P]] * 2):   # three calls in a row, or the batch twice
+        pairs = np.array(pairs, np.int32)
+        want = ref.batch(prm, EST_FIXED, 1024, SEED, TUM_FR1_K, pairs, 0.12, 0.55, 4 * cap)
+        g = _run(c2, prm, EST_FIXED, 1024, SEED, _dev(views, frames, pairs, 4 * cap))
+        if pairs[0][0] == 0:
+            assert (c2.get_option("last_staged_pairs") > 0) == (prune == 2)
+        mref.compare(g, want, what=(mode, prune, P))
+    c2.close()
+    valid = []
+    for (v, f), w in zip(two, ref.batch(prm, EST_FIXED, 1024, SEED, TUM_FR1_K, two, 0.12, 0.55, 4 * cap)):   # what the inputs hold
+        m, at = w["matches"], np.arange(w["numMatches"])
+        z0, z1 = views["pos"][v][m["queryIdx"], 2], frames["pos"][f][m["trainIdx"], 2]
+        bad = ~((z0 >= 0.1) & (z0 <= 6) & (z1 >= 0.1) & (z1 <= 6))
+        for seam in (256, 512, 768, 1024):
+            assert (bad & (at >= seam - 256) & (at < seam)).any() and (bad & (at >= seam)).any()
+        valid.append((int(w["stats"]["numMatchesValid"]), int(w["stats"]["accepted"])))
+    assert valid[0][0] % 2 == 1 and valid[0][1] == 1 and valid[1] == (0, 0)
+
+
 def test_one_by_one_and_sub_batches(ctx, ragged):
     """The same pairs through ctx.match_xyz + ctx.ransac_rigid3d one by one are identical; a sub-batch [a, b) seeded
     seed + a equals its slice of the whole batch."""

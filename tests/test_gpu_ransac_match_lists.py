@@ -18,7 +18,7 @@ from putslam_amd._abi import (ADAPTIVE_ERROR, DMATCH_DTYPE, EST_FIXED, EST_RANSA
 
 pytestmark = pytest.mark.gpu
 
-KBLOCK = 256          # the tile of ps_prep_match_lists (kBlock, ps_kernels.h)
+KBLOCK = 256          # the tile of ps_prep_match_lists (kBlock, ps_block.h)
 SENT = 0xA5
 SEED = 11
 MODES = [EUCLIDEAN_ERROR, REPROJECTION_ERROR, EUCLIDEAN_AND_REPROJECTION_ERROR, ADAPTIVE_ERROR]

@@ -21,7 +21,7 @@ from putslam_amd._abi import TUM_FR1_K  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-K_BLOCK = 256       # kBlock of ps_kernels.h: the work-group size of the per-point kernels
+K_BLOCK = 256       # kBlock of ps_block.h: the work-group size of the per-point kernels
 
 
 def same_bits(got, want):
