@@ -1771,6 +1771,107 @@ int ps_debug_track_close_passes(PsContext *ctx, PsTrackClose *tc, const PsOrbPyr
                                 const PsTrackedRows *tracked, const PsTrackCandidates *cand, const int32_t *candFrame, int P, int capacity,
                                 int outCapacity, const PsTrackCloseOut *out, int passes);
 
+/* ---- Measurement uncertainty: the two per-feature steps of the frame loop before the data passes to the graph optimiser --
+ * matcher->computeNormals / computeRGBGradients (src/PUTSLAM/PUTSLAM.cpp:826-837 for the measurements, :871-884 for the new
+ * features) and the 3 x 3 information matrix FeaturesMap::addMeasurements (src/Map/featuresMap.cpp:251-285) and addFeatures
+ * (:110-128) give every Edge3D.  The arithmetic is RGBD::computeNormal / computeRGBGradient (src/RGBD/RGBD.cpp:100-187, the
+ * templates of RGBD.h:91-106), DepthSensorModel::computeCov (src/Grabber/depthSensorModel.cpp:27-36),
+ * informationMatrixFromImageCoordinates (:55-59), uncertinatyFromNormal (:62-76), uncertinatyFromRGBGradient (:79-95) and
+ * normalizeVector (:98-101), restated sequentially in tests/uncertainty_ref.py; every output is byte for byte the restatement's
+ * (DESIGN.md section 8.16).  Eigen's fixed-size 3 x 3 inverse is RESTATED, not compiled against an Eigen: no Eigen was at hand,
+ * so that reading is unpinned.
+ * The rules, for a row with undistorted position (u, v) and point (X, Y, Z):
+ *   pixel = ((int)u, (int)v), truncation (RGBD.h:93,104).  A NaN coordinate, or one whose truncation or its two neighbours do not
+ *     fit an int, is undefined in the reference: here every double output of the row is NaN.  Every NaN written is the one pattern
+ *     0x7FF8000000000000.
+ *   point2Dto3D is ps_assemble_frames' arithmetic on a frame of the depth set as the dense image the reference holds.
+ *   normal: the centre and its eight neighbours in the order of uidx / vidx; the neighbours with Z > 0 kept (the centre is not
+ *     tested); differences in float, widened; cross products of cyclically adjacent kept vectors in double; their sum in list
+ *     order divided by the count; norm = sqrt((x x + y y) + z z), three divisions.  Fewer than two kept neighbours: 0 / 0, NaN.
+ *   gradient: 3-channel images only.  Outside the guard (u-1 > 0 && v-1 > 0 && u+1 < cols && v+1 < rows) the unnormalised
+ *     (1, 1, 1).  The 3 x 3 patch is read as the reference reads it, at<uint16_t> on the 8-bit COLOUR image: the value at (r, c)
+ *     is the little-endian 16-bit word at byte (v-1+r) x rowStride + (u-1) x 3 + 2 c of the frame.  gradx / grady are exact
+ *     integers; the direction coord1 = (int(sqrt 2 sin a), int(sqrt 2 cos a)), a = atan2(grady, gradx) + pi / 2, and coord2 (a +
+ *     pi) is taken by an integer rule off the diagonals -- coord1 = (sgn gradx if |gradx| > |grady| else 0, -sgn grady if |grady| >
+ *     |gradx| else 0), coord2 = -coord1 -- and on the five ties ((0, 0) and |gradx| == |grady| in the four quadrants) from a table
+ *     the HOST evaluates with its libm by the literal expression; then the selection ladder of :170-183 as written and the
+ *     normalisation.
+ *   info: model -1 the identity (useUncertainty off, or an uncertaintyModel the reference ignores); 0
+ *     informationMatrixFromImageCoordinates(u, v, Z): computeCov((unsigned long)u, (unsigned long)v, Z).inverse(), a u or v that
+ *     is negative, NaN or not below 2^64 giving a NaN matrix, z^2 = z z and z^3 = z z z (the correctly rounded powers of a float
+ *     z; a libm's pow(z, 3.0) need not be); 1 uncertinatyFromNormal(normal).inverse(); 2
+ *     uncertinatyFromRGBGradient(gradient).inverse().  Every 3 x 3 product is dense, (a0 b0 + a1 b1) + a2 b2, left to right;
+ *     inverse(): cof(i, j) = m(i1, j1) m(i2, j2) - m(i1, j2) m(i2, j1), det = (cof(0,0) m(0,0) + cof(1,0) m(1,0)) + cof(2,0) m(2,0),
+ *     result(i, j) = cof(j, i) x (1 / det).  Matrices are stored row-major, 9 doubles.
+ * PsSensorModel: DepthSensorModel::Config (depthSensorModel.h:53-58).  The reference's file constructor never reads c1 and c0
+ * (distVarCoefs[2], [3]): they are uninitialised there; the shipped Kinect file carries all four. */
+typedef struct PsSensorModel {
+    double fu, fv, cu, cv;       /* focalLength, focalAxis */
+    double varU, varV;
+    double c3, c2, c1, c0;       /* distVarCoefs[0 .. 3]: var(depth) = c3 z^3 + c2 z^2 + c1 z + c0 */
+    double scaleUncertaintyNormal, scaleUncertaintyGradient;
+} PsSensorModel;
+typedef struct PsUncertaintyOut {  /* DEVICE pointers, F x capacity rows each; NULL = not wanted */
+    double *normal;              /* x 3 */
+    double *gradient;            /* x 3 */
+    double *info;                /* x 9, row-major */
+} PsUncertaintyOut;
+typedef struct PsMeasurementEdgesOut {  /* DEVICE pointers, P x maxMatches rows each (count: P); NULL = not wanted */
+    int32_t *count;              /* pair p's final inliers */
+    int32_t *mapRow, *curRow;    /* queryIdx, trainIdx */
+    float *uv;                   /* x 2: xyUndist of the frame's row (MapFeature::u, v) */
+    double *position;            /* x 3: the frame's point widened -- the Edge3D measurement */
+    double *normal, *gradient, *info;
+} PsMeasurementEdgesOut;
+size_t ps_abi_sizeof_sensor_model(void);
+size_t ps_abi_sizeof_uncertainty_out(void);
+size_t ps_abi_sizeof_measurement_edges_out(void);
+
+/* DepthSensorModel::Config()'s defaults (depthSensorModel.h:53-58).  The two scale factors are 0: the reference's default
+ * constructor leaves them unset.  Pure host; PS_ERR_BAD_ARG for NULL. */
+int ps_sensor_model_default(PsSensorModel *out);
+
+/* The addFeatures side (PUTSLAM.cpp:871-884, featuresMap.cpp:110-128) for F sets of rows, everything DEVICE resident: xy F x
+ * capacity x 2 floats (the undistorted u, v: PsFrameRowsOut::xyUndist), pts F x capacity x 3 floats, counts F; imageFrame[f]
+ * names the frame of `images` and of `depth` that row set f belongs to.  out->info with model 1 or 2 needs no normal / gradient
+ * output; images may be NULL when neither the gradient nor model 2 is wanted.  A count outside 0 .. capacity: nothing written for
+ * that set; imageFrame[f] outside either set: that set's rows are NaN; nothing is written beyond a count.  images->channels != 3
+ * -> PS_ERR_UNSUPPORTED; NULL where an argument or array is needed, model outside -1 .. 2, strides that do not resolve, images of
+ * another shape than the depth, capacity < 1, F outside 0 .. 65535 -> PS_ERR_BAD_ARG; capacity above PS_MAX_KPTS ->
+ * PS_ERR_UNSUPPORTED; F == 0 is PS_OK.  One launch, asynchronous on the context's stream; uses no scratch of the context. */
+int ps_feature_uncertainty(PsContext *ctx, const PsFrameGeometry *geometry, const PsSensorModel *sensor, int model,
+                           const PsImageSet *images, const PsDepthSet *depth, const int32_t *imageFrame, const float *xy, const float *pts,
+                           const int32_t *counts, int F, int capacity, const PsUncertaintyOut *out);
+
+/* The addMeasurements side (matcher.cpp:769-794, then featuresMap.cpp:255-282) for the P pairs of a ps_map_pairs_device call: b
+ * the PsMapBatch given to it, res its PsPairResults, xyUndist b->frames.numFrames x b->frames.maxKpts x 2 floats.  Pair p's final
+ * inliers in match-list order (res->inlierMask's order is the order of inlierMatches) fill the first count[p] rows of every
+ * wanted member of `out`; nothing is written beyond them.  The images' and the depth's frame is imageFrame[pairs[p][1]]
+ * (imageFrame: b->frames.numFrames entries).  A pair with numMatches[p] <= 0 (no matches, or an overflow) or above b->maxMatches,
+ * and a pair that names a frame outside its set, has count[p] = 0; a trainIdx outside 0 .. b->frames.maxKpts - 1 is not followed:
+ * that row is NaN.  Errors as above (b's frame set by the rule of PsFrameSet, its points alone); P == 0 is PS_OK.  One launch, one
+ * work-group per pair, no atomics -- the order is part of the result; asynchronous; no scratch. */
+int ps_measurement_edges(PsContext *ctx, const PsFrameGeometry *geometry, const PsSensorModel *sensor, int model, const PsImageSet *images,
+                         const PsDepthSet *depth, const int32_t *imageFrame, const PsMapBatch *b, const PsPairResults *res,
+                         const float *xyUndist, const PsMeasurementEdgesOut *out);
+
+/* The same for one frame: HOST pointers, uploads and downloads included, synchronous.  depth rows x cols uint16 with depthStep
+ * bytes between rows, img rows x cols x 3 bytes with rowStride bytes between rows (0 = dense either); xy n x 2 floats, pts n x 3
+ * floats; normal / gradient n x 3 doubles, info n x 9.  img may be NULL for models other than 2.  n above PS_MAX_KPTS ->
+ * PS_ERR_UNSUPPORTED; n == 0 is PS_OK. */
+int ps_compute_normals(PsContext *ctx, const PsFrameGeometry *geometry, const uint16_t *depth, int rows, int cols, size_t depthStep,
+                       const float *xy, int n, double *normal);
+int ps_compute_rgb_gradients(PsContext *ctx, const PsFrameGeometry *geometry, const uint8_t *img, int channels, size_t rowStride,
+                             const uint16_t *depth, int rows, int cols, size_t depthStep, const float *xy, int n, double *gradient);
+int ps_information_matrices(PsContext *ctx, const PsFrameGeometry *geometry, const PsSensorModel *sensor, int model, const uint8_t *img,
+                            int channels, size_t rowStride, const uint16_t *depth, int rows, int cols, size_t depthStep, const float *xy,
+                            const float *pts, int n, double *info);
+/* Diagnostic (no reference counterpart; a CPU test holds the library's libm to the restatement's with it): the 5 x 4 table of the
+ * gradient's ties -- rows (gradx, grady) = (0,0), (1,1), (-1,1), (-1,-1), (1,-1); columns coord1[0],
+ * coord1[1], coord2[0], coord2[1] -- by the literal expression with this host's libm at magnitude k (the table the kernels get
+ * is k = 1).  Pure host; k < 1 or NULL -> PS_ERR_BAD_ARG. */
+int ps_debug_gradient_tie_table(int k, int32_t *table20);
+
 #ifdef __cplusplus
 }
 #endif

@@ -313,6 +313,35 @@ def track_close_params(minimal_tracked_features=150, min_reproj_distance=3.0, re
     return PsTrackCloseParams(float(min_reproj_distance), int(minimal_tracked_features), int(remove_too_close_features))
 
 
+# Measurement uncertainty (include/putslam_hip.h)
+UNCERTAINTY_OFF, UNCERTAINTY_IMAGE_COORDINATES, UNCERTAINTY_NORMAL, UNCERTAINTY_RGB_GRADIENT = -1, 0, 1, 2
+NAN_BITS = 0x7FF8000000000000     # the one NaN the uncertainty kernels write
+
+
+class PsSensorModel(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("fu", "fv", "cu", "cv", "varU", "varV", "c3", "c2", "c1", "c0", "scaleUncertaintyNormal",
+                                          "scaleUncertaintyGradient")]
+
+
+class PsUncertaintyOut(C.Structure):
+    _fields_ = [("normal", C.c_void_p), ("gradient", C.c_void_p), ("info", C.c_void_p)]
+
+
+class PsMeasurementEdgesOut(C.Structure):
+    _fields_ = [("count", C.c_void_p), ("mapRow", C.c_void_p), ("curRow", C.c_void_p), ("uv", C.c_void_p), ("position", C.c_void_p),
+                ("normal", C.c_void_p), ("gradient", C.c_void_p), ("info", C.c_void_p)]
+
+
+def sensor_model(**fields):
+    """PsSensorModel: DepthSensorModel::Config()'s defaults (ps_sensor_model_default's numbers; the two scale factors 0, which the
+    reference leaves unset) with the named fields replaced."""
+    s = PsSensorModel(582.64, 586.97, 320.17, 260.0, 1.1046, 0.64160, -8.9997e-06, 3.069e-003, 3.6512e-006, -0.0017512e-3, 0.0, 0.0)
+    for k, v in fields.items():
+        assert hasattr(s, k), k
+        setattr(s, k, float(v))
+    return s
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

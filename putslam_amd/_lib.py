@@ -10,7 +10,8 @@ from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostP
                    PsMapBatchF32, PsMapStore, PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPairResults, PsPoseSetOut,
                    PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams, PsOrbParams, PsOrbDetectParams,
                    PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoParams,
-                   PsTrackVoIn, PsTrackVoOut, PsTrackCandidates, PsTrackCloseParams, PsTrackCloseOut)
+                   PsTrackVoIn, PsTrackVoOut, PsTrackCandidates, PsTrackCloseParams, PsTrackCloseOut, PsSensorModel, PsUncertaintyOut,
+                   PsMeasurementEdgesOut)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -67,6 +68,9 @@ EXPORTED = [
     "ps_track_candidates", "ps_track_close_create", "ps_track_close_destroy", "ps_track_close_pairs",
     "ps_track_close_pair", "ps_debug_track_close_passes",
     "ps_abi_sizeof_track_candidates", "ps_abi_sizeof_track_close_params", "ps_abi_sizeof_track_close_out",
+    "ps_sensor_model_default", "ps_debug_gradient_tie_table", "ps_feature_uncertainty", "ps_measurement_edges", "ps_compute_normals",
+    "ps_compute_rgb_gradients", "ps_information_matrices",
+    "ps_abi_sizeof_sensor_model", "ps_abi_sizeof_uncertainty_out", "ps_abi_sizeof_measurement_edges_out",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -93,6 +97,8 @@ ABI_STRUCTS_TRACK_VO = dict(point_sets=PsPointSets, tracked_carry=PsTrackedCarry
                             track_vo_params=PsTrackVoParams, track_vo_in=PsTrackVoIn, track_vo_out=PsTrackVoOut)
 # ... and of its second half (ps_track_candidates / ps_track_close_pairs)
 ABI_STRUCTS_TRACK_CLOSE = dict(track_candidates=PsTrackCandidates, track_close_params=PsTrackCloseParams, track_close_out=PsTrackCloseOut)
+# ... and of the measurement uncertainty (ps_feature_uncertainty / ps_measurement_edges)
+ABI_STRUCTS_UNCERTAINTY = dict(sensor_model=PsSensorModel, uncertainty_out=PsUncertaintyOut, measurement_edges_out=PsMeasurementEdgesOut)
 
 _lib = None
 _by_path = {}
@@ -349,9 +355,20 @@ def load_path(path):
     L.ps_track_close_pair.argtypes = [vp, vp, vp, i32, i32, i32, sz, sz, C.POINTER(PsFrontEndParams), vp, C.POINTER(PsFrameGeometry),
                                       C.POINTER(PsTrackCloseParams), C.POINTER(PsTrackedRows), i32, vp, C.POINTER(PsTrackedRows), vp, i32,
                                       C.POINTER(i32), C.POINTER(i32)]
+    L.ps_sensor_model_default.argtypes = [C.POINTER(PsSensorModel)]
+    L.ps_debug_gradient_tie_table.argtypes = [i32, vp]
+    L.ps_feature_uncertainty.argtypes = [vp, C.POINTER(PsFrameGeometry), C.POINTER(PsSensorModel), i32, C.POINTER(PsImageSet),
+                                         C.POINTER(PsDepthSet), vp, vp, vp, vp, i32, i32, C.POINTER(PsUncertaintyOut)]
+    L.ps_measurement_edges.argtypes = [vp, C.POINTER(PsFrameGeometry), C.POINTER(PsSensorModel), i32, C.POINTER(PsImageSet),
+                                       C.POINTER(PsDepthSet), vp, C.POINTER(PsMapBatch), C.POINTER(PsPairResults), vp,
+                                       C.POINTER(PsMeasurementEdgesOut)]
+    L.ps_compute_normals.argtypes = [vp, C.POINTER(PsFrameGeometry), vp, i32, i32, sz, vp, i32, vp]
+    L.ps_compute_rgb_gradients.argtypes = [vp, C.POINTER(PsFrameGeometry), vp, i32, sz, vp, i32, i32, sz, vp, i32, vp]
+    L.ps_information_matrices.argtypes = [vp, C.POINTER(PsFrameGeometry), C.POINTER(PsSensorModel), i32, vp, i32, sz, vp, i32, i32, sz,
+                                          vp, vp, i32, vp]
     for n in (list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT) + list(ABI_STRUCTS_DETECT)
               + list(ABI_STRUCTS_ORB) + list(ABI_STRUCTS_ORB_DETECT) + list(ABI_STRUCTS_FRAME_ASSEMBLY) + list(ABI_STRUCTS_TRACK_VO)
-              + list(ABI_STRUCTS_TRACK_CLOSE)):
+              + list(ABI_STRUCTS_TRACK_CLOSE) + list(ABI_STRUCTS_UNCERTAINTY)):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -395,3 +412,7 @@ def struct_sizes_track_vo():
 
 def struct_sizes_track_close():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_TRACK_CLOSE.items()}
+
+
+def struct_sizes_uncertainty():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_UNCERTAINTY.items()}

@@ -15,7 +15,8 @@ from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, P
                    PsImageSet, PsKltParams, klt_params, PsDetectParams, detect_params, PsOrbParams, orb_params,
                    PsOrbDetectParams, orb_detect_params, PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, front_end_params,
                    PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoParams, PsTrackVoIn, PsTrackVoOut, track_vo_params,
-                   PsTrackCandidates, PsTrackCloseParams, PsTrackCloseOut, track_close_params)
+                   PsTrackCandidates, PsTrackCloseParams, PsTrackCloseOut, track_close_params, PsSensorModel, PsUncertaintyOut,
+                   PsMeasurementEdgesOut, sensor_model)
 
 
 class PsError(RuntimeError):
@@ -747,6 +748,66 @@ class Context:
                                              _p(a["desc"]), C.byref(out), cap, C.byref(n)))
         return {k: v[:n.value].copy() for k, v in a.items()}
 
+    # ---- measurement uncertainty (ps_uncertainty.h) ----
+    @staticmethod
+    def _host_depth(depth):
+        depth = np.asarray(depth)
+        assert depth.dtype == np.uint16 and depth.ndim == 2
+        if depth.strides[1] != 2 or depth.strides[0] < depth.shape[1] * 2:
+            depth = np.ascontiguousarray(depth)
+        return depth
+
+    def compute_normals(self, xy, depth, geometry: PsFrameGeometry):
+        """RGBD::computeNormal (RGBD.cpp:101-144) at n undistorted positions xy (n, 2) float32 of a depth image (rows, cols) uint16
+        whose rows may lie any stride apart (ps_compute_normals): (n, 3) float64."""
+        xy, depth = np.ascontiguousarray(xy, np.float32).reshape(-1, 2), self._host_depth(depth)
+        out = np.zeros((len(xy), 3), np.float64)
+        self._chk(self._L.ps_compute_normals(self._h, C.byref(geometry), _p(depth), depth.shape[0], depth.shape[1], depth.strides[0], _p(xy),
+                                             len(xy), _p(out)))
+        return out
+
+    def compute_rgb_gradients(self, xy, image, depth, geometry: PsFrameGeometry):
+        """RGBD::computeRGBGradient (RGBD.cpp:147-187) at n positions of a 3-channel image (rows, cols, 3) uint8 and its depth image
+        (ps_compute_rgb_gradients): (n, 3) float64."""
+        xy, depth = np.ascontiguousarray(xy, np.float32).reshape(-1, 2), self._host_depth(depth)
+        image, cn = _host_image(image)
+        assert image.shape[:2] == depth.shape
+        out = np.zeros((len(xy), 3), np.float64)
+        self._chk(self._L.ps_compute_rgb_gradients(self._h, C.byref(geometry), _p(image), cn, image.strides[0], _p(depth), depth.shape[0],
+                                                   depth.shape[1], depth.strides[0], _p(xy), len(xy), _p(out)))
+        return out
+
+    def information_matrices(self, xy, pts, depth, geometry: PsFrameGeometry, sensor: PsSensorModel = None, model=0, image=None):
+        """The 3 x 3 information matrix FeaturesMap::addFeatures / addMeasurements give every Edge3D (featuresMap.cpp:110-121,261-274)
+        for n features at xy (n, 2) float32 with points pts (n, 3) float32 (ps_information_matrices): (n, 3, 3) float64.  model -1 the
+        identity, 0 the image coordinates, 1 the normal, 2 the colour gradient (needs the 3-channel image); sensor: a PsSensorModel,
+        default _abi.sensor_model()."""
+        sensor = sensor or sensor_model()
+        xy, depth = np.ascontiguousarray(xy, np.float32).reshape(-1, 2), self._host_depth(depth)
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        assert len(pts) == len(xy)
+        img, cn = (None, 3) if image is None else _host_image(image)
+        out = np.zeros((len(xy), 3, 3), np.float64)
+        self._chk(self._L.ps_information_matrices(self._h, C.byref(geometry), C.byref(sensor), int(model), _p(img), cn,
+                                                  0 if img is None else img.strides[0], _p(depth), depth.shape[0], depth.shape[1],
+                                                  depth.strides[0], _p(xy), _p(pts), len(xy), _p(out)))
+        return out
+
+    def feature_uncertainty_device(self, geometry: PsFrameGeometry, sensor: PsSensorModel, model, images: PsImageSet, depth: PsDepthSet,
+                                   image_frame_ptr, xy_ptr, pts_ptr, counts_ptr, F, capacity, out: PsUncertaintyOut):
+        """ps_feature_uncertainty on device pointers (asynchronous on the context's stream): device_batch.feature_uncertainty."""
+        self._chk(self._L.ps_feature_uncertainty(self._h, C.byref(geometry), None if sensor is None else C.byref(sensor), int(model),
+                                                 None if images is None else C.byref(images), C.byref(depth), _v(image_frame_ptr),
+                                                 _v(xy_ptr), _v(pts_ptr), _v(counts_ptr), int(F), int(capacity), C.byref(out)))
+
+    def measurement_edges_device(self, geometry: PsFrameGeometry, sensor: PsSensorModel, model, images: PsImageSet, depth: PsDepthSet,
+                                 image_frame_ptr, batch: "DeviceMapBatch", res: "DeviceResults", xy_undist_ptr, out: PsMeasurementEdgesOut):
+        """ps_measurement_edges on device pointers (asynchronous on the context's stream): device_batch.measurement_edges."""
+        mb, rs = batch.struct(), res.struct()
+        self._chk(self._L.ps_measurement_edges(self._h, C.byref(geometry), None if sensor is None else C.byref(sensor), int(model),
+                                               None if images is None else C.byref(images), C.byref(depth), _v(image_frame_ptr),
+                                               C.byref(mb), C.byref(rs), _v(xy_undist_ptr), C.byref(out)))
+
     # ---- the tracking VO step (DESIGN.md section 8.14) ----
     def ransac_match_lists_device(self, params, cfg, K, prev: PsPointSets, cur: PsPointSets, pairs_ptr, matches_ptr, num_matches_ptr, P,
                                   cap, out: "DeviceResults"):
@@ -1451,3 +1512,12 @@ def kernel_names():
 
 def algorithmic_bytes(nkpts, matches_in, matches_valid, H):
     return int(_lib.load().ps_algorithmic_bytes(int(nkpts), int(matches_in), int(matches_valid), int(H)))
+
+
+def gradient_tie_table(k=1):
+    """ps_debug_gradient_tie_table: the 5 x 4 table of the colour gradient's ties at magnitude k, by this host's libm (no device)."""
+    t = np.zeros((5, 4), np.int32)
+    rc = _lib.load().ps_debug_gradient_tie_table(int(k), _p(t))
+    if rc != PS_OK:
+        raise PsError(rc, "ps_debug_gradient_tie_table")
+    return t

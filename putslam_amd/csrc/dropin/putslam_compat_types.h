@@ -20,6 +20,10 @@
 namespace putslam {
 typedef Eigen::Transform<double, 3, Eigen::Affine> Mat34; // reference include/putslam/Defs/putslam_defs.h:34
 }
+namespace putslam_hip { // putslam::Vec3 / putslam::Mat33 (putslam_defs.h:28,31), named here so that a host's own stand-ins may keep those names
+typedef Eigen::Translation<double, 3> Vec3;
+typedef Eigen::Matrix<double, 3, 3> Mat33;
+}
 #else
 #define PUTSLAM_HAVE_CV_EIGEN 0
 
@@ -153,4 +157,35 @@ struct Mat34 {
     const double *data() const { return m; }
 };
 } // namespace putslam
+namespace putslam_hip { // (not putslam::Vec3 / ::Mat33: a program shaped like the reference may define those names itself)
+// stand-in for Eigen::Translation<double, 3> (putslam_defs.h:28): three doubles
+struct Vec3 {
+    double t[3];
+    Vec3() : t{0, 0, 0} {}
+    Vec3(double x, double y, double z) : t{x, y, z} {}
+    double &x() { return t[0]; }
+    double &y() { return t[1]; }
+    double &z() { return t[2]; }
+    double x() const { return t[0]; }
+    double y() const { return t[1]; }
+    double z() const { return t[2]; }
+};
+// stand-in for Eigen::Matrix<double, 3, 3> (putslam_defs.h:31): column-major; inverse() is defined with the drop-in
+// (putslam_dropin.cpp: the project's reading of Eigen's fixed-size inverse)
+struct Mat33 {
+    double m[9];
+    Mat33() { std::memset(m, 0, sizeof m); }
+    static Mat33 Identity()
+    {
+        Mat33 r;
+        r.m[0] = r.m[4] = r.m[8] = 1.0;
+        return r;
+    }
+    double &operator()(int r, int c) { return m[3 * c + r]; }
+    const double &operator()(int r, int c) const { return m[3 * c + r]; }
+    double *data() { return m; }
+    const double *data() const { return m; }
+    Mat33 inverse() const;
+};
+} // namespace putslam_hip
 #endif

@@ -1548,3 +1548,9 @@ std::vector<cv::DMatch> hammingCrossCheckMatch(cv::Mat prevDescriptors, cv::Mat 
 }
 
 } // namespace putslam_hip
+
+namespace putslam_hip {
+// the calling thread's context and the error line, for the drop-in's other translation unit (putslam_dropin_uncertainty.cpp)
+PsContext *dropinThreadContext(int *status) { return threadContext(status); }
+void dropinReportError(const PsContext *ctx) { reportError(ctx); }
+} // namespace putslam_hip

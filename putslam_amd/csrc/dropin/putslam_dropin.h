@@ -118,6 +118,61 @@ class RGBD {
     // distCoeffs: 1x5 (or 5x1) CV_32F/CV_64F-like access through at<float>: (k1, k2, p1, p2, k3)
     static std::vector<cv::Point2f> removeImageDistortion(std::vector<cv::Point2f> &features, cv::Mat cameraMatrix,
                                                           cv::Mat distCoeffs);
+    // RGBD::computeNormal / computeRGBGradient (RGBD.cpp:100-187) with the reference's signatures, and their templates
+    // (RGBD.h:91-106) over anything with u, v, normal, RGBgradient: ps_compute_normals / ps_compute_rgb_gradients (DESIGN.md section
+    // 8.16).  The templates make ONE device call for the whole list (normalsAt / gradientsAt: pixel (px[i].x, px[i].y), truncated);
+    // the single-feature forms make one call a feature.  depthImage CV_16U, rgbImage CV_8UC3 of the same size, any steps.  On an
+    // error: one line on std::cerr, NaN vectors.  Nothing runs on the CPU instead.
+    static putslam_hip::Vec3 computeNormal(const cv::Mat &depthImage, int u, int v, const cv::Mat &cameraMatrix, double depthImageScale);
+    static putslam_hip::Vec3 computeRGBGradient(const cv::Mat &rgbImage, const cv::Mat &depthImage, int u, int v, const cv::Mat &cameraMatrix,
+                                            double depthImageScale);
+    static std::vector<putslam_hip::Vec3> normalsAt(const cv::Mat &depthImage, const std::vector<cv::Point2f> &px, const cv::Mat &cameraMatrix,
+                                                double depthImageScale);
+    static std::vector<putslam_hip::Vec3> gradientsAt(const cv::Mat &rgbImage, const cv::Mat &depthImage, const std::vector<cv::Point2f> &px,
+                                                  const cv::Mat &cameraMatrix, double depthImageScale);
+    template <class T> static void computeNormals(const cv::Mat &depthImage, T &features, const cv::Mat &cameraMatrix, double depthImageScale)
+    {
+        std::vector<cv::Point2f> px;
+        for (auto it = features.begin(); it != features.end(); it++) px.push_back(cv::Point2f((float)(int)it->u, (float)(int)it->v));
+        const std::vector<putslam_hip::Vec3> n = normalsAt(depthImage, px, cameraMatrix, depthImageScale);
+        size_t i = 0;
+        for (auto it = features.begin(); it != features.end(); it++) it->normal = n[i++];
+    }
+    template <class T>
+    static void computeRGBGradients(const cv::Mat &rgbImage, const cv::Mat &depthImage, T &features, const cv::Mat &cameraMatrix,
+                                    double depthImageScale)
+    {
+        std::vector<cv::Point2f> px;
+        for (auto it = features.begin(); it != features.end(); it++) px.push_back(cv::Point2f((float)(int)it->u, (float)(int)it->v));
+        const std::vector<putslam_hip::Vec3> g = gradientsAt(rgbImage, depthImage, px, cameraMatrix, depthImageScale);
+        size_t i = 0;
+        for (auto it = features.begin(); it != features.end(); it++) it->RGBgradient = g[i++];
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// DepthSensorModel (include/putslam/Grabber/depthSensorModel.h, src/Grabber/depthSensorModel.cpp:27-36,55-101): the four members
+// the uncertainty models read, signature-identical (putslam_hip::Vec3 / ::Mat33 ARE putslam::Vec3 / ::Mat33 where Eigen is installed).  They return COVARIANCES, which the C ABI does not export (it returns the
+// information matrices): these four run on the calling thread, on the sequential restatement csrc/ps_uncertainty_host.h -- 3 x 3
+// arithmetic, no loop over features -- and informationMatrixFromImageCoordinates(u, v, z), uncertinatyFromNormal(n).inverse() and
+// uncertinatyFromRGBGradient(g).inverse() are byte for byte ps_information_matrices' models 0, 1 and 2
+// (tests/cpp/test_dropin_uncertainty.cpp).  A whole list goes through FrameMatcherHIP::measurementEdges instead.  Config carries
+// the reference's members and defaults (depthSensorModel.h:53-58; the two scale factors, unset there, are 0); the XML constructor
+// is the host's.
+class DepthSensorModel {
+  public:
+    class Config {
+      public:
+        Config();
+        double focalLength[2], focalAxis[2], varU, varV, distVarCoefs[4], scaleUncertaintyNormal, scaleUncertaintyGradient;
+    };
+    DepthSensorModel() {}
+    explicit DepthSensorModel(const Config &c) : config(c) {}
+    void computeCov(uint_fast16_t u, uint_fast16_t v, double depth, putslam_hip::Mat33 &cov);
+    putslam_hip::Mat33 informationMatrixFromImageCoordinates(double u, double v, double z);
+    putslam_hip::Mat33 uncertinatyFromNormal(const putslam_hip::Vec3 &normal);
+    putslam_hip::Mat33 uncertinatyFromRGBGradient(const putslam_hip::Vec3 &grad);
+    Config config;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -479,6 +534,22 @@ class FrameMatcherHIP : public FrameMatcher {
     // neighbour's descriptor (two rows within 0.0001 px across the border: DESIGN.md section 8.15), every descriptor stays with its row.
     double trackKLT(cv::Mat rgbImage, cv::Mat depthImage, double depthImageScale, Eigen::Matrix4f &estimatedTransformation,
                     std::vector<cv::DMatch> &inlierMatches);
+    // What PUTSLAM.cpp:826-837 and FeaturesMap::addMeasurements (featuresMap.cpp:255-282) make of matchXYZ's inliers, as the data of
+    // Edge3D(position, info, poseId, featureId): per inlier match, in inlierMatches' order, the map row (queryIdx), the frame's row
+    // (trainIdx), (u, v) = undistorted[trainIdx], position = features3D[trainIdx] widened, the normal, the colour gradient and the
+    // information matrix of `uncertaintyModel` (-1: the identity, useUncertainty off; 0, 1, 2: config.uncertaintyModel) under
+    // `sensor` -- ps_compute_normals, ps_compute_rgb_gradients and ps_information_matrices on the gathered rows, byte for byte
+    // ps_measurement_edges' on a device-resident batch.  rgbImage CV_8UC3, depthImage CV_16U.  On an error, or a trainIdx outside
+    // the two lists: one line on std::cerr and an empty result.
+    struct MeasurementEdge {
+        int mapRow, curRow;
+        float u, v;
+        putslam_hip::Vec3 position, normal, RGBgradient;
+        putslam_hip::Mat33 info;
+    };
+    std::vector<MeasurementEdge> measurementEdges(const std::vector<cv::DMatch> &inlierMatches, const std::vector<cv::Point2f> &undistorted,
+                                                  const std::vector<Eigen::Vector3f> &features3D, cv::Mat rgbImage, cv::Mat depthImage,
+                                                  double depthImageScale, DepthSensorModel &sensor, int uncertaintyModel);
 
   protected: // Matcher's tracking state (matcher.h:379-391); prevDescriptors and prevFeatures3D are FrameMatcher's
     cv::Mat prevRgbImage, prevDepthImage;

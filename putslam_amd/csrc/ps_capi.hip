@@ -1077,6 +1077,7 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
 #include "ps_orb_detect.h"   // ps_orb_detector_* / ps_orb_detect_frames / ps_detect_features_orb (ps_fast.h's tile body, ps_orb.h's levels)
 #include "ps_frame_assembly.h" // ps_gather_keypoints / ps_assemble_frames / ps_front_end_* (the launches of ps_dbscan.h, ps_orb.h, ps_orb_detect.h)
 #include "ps_track_vo.h"     // ps_ransac_match_lists / ps_assemble_tracked / ps_track_vo_pairs (the plan and the stages above, ps_klt.h's launches, ps_frame_assembly.h's body)
+#include "ps_uncertainty.h"  // ps_feature_uncertainty / ps_measurement_edges / ps_compute_normals / ps_compute_rgb_gradients / ps_information_matrices (ps_frame_assembly.h's back-projection)
 #include "ps_track_close.h"  // ps_track_candidates / ps_track_close_* (ps_exclusion.h's predicate, ps_map_view.h's level rule, the launches of ps_orb.h and ps_frame_assembly.h)
 
 // Launch attributes of the kernels that need them (ps_internal.h; called once per context).

@@ -19,10 +19,10 @@ struct AssembleArgs {
 
 // The undistorted position q of the distorted p and its 3-D point in the depth frame at `frame` (null: no depth image, depth 0 --
 // the keypoints2Dto3D result for no depth): ps_kernels.h's undistort_point, depth_rule_offset, depth_pixel and point_from_depth.
-PS_D void undistort_and_back_project(float2 p, const DistArgs &dist, double scale, const uint8_t *__restrict__ frame, size_t rowStride, int rows,
-                                     int cols, float2 &q, float &X, float &Y, float &Z)
+// point2Dto3D of q in one frame of a depth set (ps_uncertainty.h back-projects pixels with it too)
+PS_D void back_project_in_frame(float2 q, float fx, float fy, float cx, float cy, double scale, const uint8_t *__restrict__ frame, size_t rowStride,
+                                int rows, int cols, float &X, float &Y, float &Z)
 {
-    undistort_point(p.x, p.y, dist, q.x, q.y);
     // the rule over the frame as the DENSE image the reference holds: u == cols in a row that is not the last is the next row's
     // first pixel whatever the row stride -- a set's padding is alignment, not a parent image, and is never read
     size_t off = 0;
@@ -31,7 +31,14 @@ PS_D void undistort_and_back_project(float2 p, const DistArgs &dist, double scal
         const unsigned pixel = (unsigned)(off >> 1), r = pixel / (unsigned)cols, c = pixel - r * (unsigned)cols;
         dv = depth_pixel(frame + (size_t)r * rowStride + (size_t)c * 2);
     }
-    point_from_depth(q.x, q.y, dv, dist.fx, dist.fy, dist.cx, dist.cy, scale, X, Y, Z);
+    point_from_depth(q.x, q.y, dv, fx, fy, cx, cy, scale, X, Y, Z);
+}
+
+PS_D void undistort_and_back_project(float2 p, const DistArgs &dist, double scale, const uint8_t *__restrict__ frame, size_t rowStride, int rows,
+                                     int cols, float2 &q, float &X, float &Y, float &Z)
+{
+    undistort_point(p.x, p.y, dist, q.x, q.y);
+    back_project_in_frame(q, dist.fx, dist.fy, dist.cx, dist.cy, scale, frame, rowStride, rows, cols, X, Y, Z);
 }
 
 // Output row j of frame f is input row idx[f][j], j < nidx[f]; a count outside 0 .. cap: -1 and nothing else; an index outside

@@ -11,7 +11,7 @@ from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBat
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
                    make_config, PsImageSet, klt_params, detect_params, orb_params, orb_detect_params, PsDepthSet, PsFrameRowsOut,
                    front_end_params, PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoIn, PsTrackVoOut, track_vo_params,
-                   PsTrackCandidates, PsTrackCloseOut, track_close_params)
+                   PsTrackCandidates, PsTrackCloseOut, track_close_params, PsUncertaintyOut, PsMeasurementEdgesOut, sensor_model)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -1074,6 +1074,94 @@ def run_match_xyz(ctx, batch: MapBatchDevice, use_torch_stream=True):
     _on_torch_stream(ctx, batch.device,
                      lambda: ctx.match_xyz_device(batch.batch_view(), batch.matches.data_ptr(), batch.num_matches.data_ptr()),
                      use_torch_stream)
+
+
+# ---- measurement uncertainty (ps_uncertainty.h) ----
+_EDGE_ARRAYS = (("map_row", torch.int32, ()), ("cur_row", torch.int32, ()), ("uv", torch.float32, (2,)), ("position", torch.float64, (3,)),
+                ("normal", torch.float64, (3,)), ("gradient", torch.float64, (3,)), ("info", torch.float64, (9,)))
+
+
+class MeasurementEdges:
+    """What ps_feature_uncertainty / ps_measurement_edges write for S row sets of `cap` rows: count (S,) int32 and the members
+    named in `want` -- map_row, cur_row (S, cap) int32, uv (S, cap, 2) float32, position, normal, gradient (S, cap, 3) float64,
+    info (S, cap, 9) float64, row-major --; the others are None.  The Edge3D(position, info, poseId, featureId) data of a batch.
+    image_frame: the (frames,) int32 device tensor the call that wrote it read, kept alive here."""
+
+    image_frame = None
+
+    def __init__(self, S, cap, device, want=None, count=None):
+        self.device, self.S, self.cap = torch.device(device), int(S), int(cap)
+        names = [n for n, _, _ in _EDGE_ARRAYS] if want is None else list(want)
+        self.count = _zeros(self.device, (max(self.S, 1),), torch.int32) if count is None else count
+        for n, dt, tail in _EDGE_ARRAYS:
+            setattr(self, n, _zeros(self.device, (max(self.S, 1), self.cap) + tail, dt) if n in names else None)
+
+    def rows_struct(self):
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        return PsUncertaintyOut(ptr(self.normal), ptr(self.gradient), ptr(self.info))
+
+    def edges_struct(self):
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        return PsMeasurementEdgesOut(ptr(self.count), ptr(self.map_row), ptr(self.cur_row), ptr(self.uv), ptr(self.position), ptr(self.normal),
+                                     ptr(self.gradient), ptr(self.info))
+
+    def download(self):
+        """dict of numpy arrays: count and every member that is there."""
+        names = ["count"] + [n for n, _, _ in _EDGE_ARRAYS if getattr(self, n) is not None]
+        return {n: getattr(self, n).cpu().numpy()[:self.S] for n in names}
+
+
+def _uncertainty_sets(images, depth, image_frame, frames, device):
+    ds = DepthSet(depth, depth.shape[1], depth.shape[2])
+    s = None if images is None else _image_set(images, depth.shape[1], depth.shape[2], 3)
+    if not isinstance(image_frame, torch.Tensor):
+        # uploaded on torch's current stream and waited for: a call made with use_torch_stream=False is ordered with nothing of torch's
+        image_frame = to_device_tensor(np.arange(frames, dtype=np.int32) if image_frame is None else image_frame, torch.int32, device)
+        torch.cuda.current_stream(device).synchronize()
+    _expect(image_frame, torch.int32, (frames,))
+    return s, ds, image_frame
+
+
+def feature_uncertainty(ctx, rows, geometry, depth, images=None, sensor=None, model=-1, image_frame=None, want=("normal", "gradient", "info"),
+                        out=None, use_torch_stream=True):
+    """Normals, colour-gradient directions and information matrices of the rows of a FrameRowsDevice -- FrontEnd rows, or the
+    survivors of exclude_device after gather_keypoints: anything with xy_undist (F, cap, 2), pts (F, cap, 3) and nkpts (F,) --
+    with no host step (ps_feature_uncertainty; the addFeatures side, PUTSLAM.cpp:871-884).  depth a uint16 device tensor (D,
+    rows, cols), images a uint8 device tensor (D, rows, cols, 3) or None where neither the gradient nor model 2 is wanted;
+    image_frame (F,) int32: the frame of both that row set f belongs to (default f).  sensor: _abi.sensor_model(...).  Returns a
+    MeasurementEdges with the members of `want`, written asynchronously, ordered like run_pairs."""
+    F, cap, dev = rows.num_frames, rows.max_kpts, rows.device
+    want = [w for w in want if not (w == "gradient" and images is None)]
+    out = out or MeasurementEdges(F, cap, dev, want, count=rows.nkpts)
+    s, ds, image_frame = _uncertainty_sets(images, depth, image_frame, F, dev)
+    sensor = sensor or sensor_model()
+    out.image_frame = image_frame      # (held: the queued kernel reads it)
+    o = out.rows_struct()
+    _on_torch_stream(ctx, dev, lambda: ctx.feature_uncertainty_device(geometry, sensor, model, s, ds, image_frame.data_ptr(),
+                                                                       rows.xy_undist.data_ptr(), rows.pts.data_ptr(), rows.nkpts.data_ptr(),
+                                                                       F, cap, o), use_torch_stream)
+    return out
+
+
+def measurement_edges(ctx, batch, xy_undist, geometry, depth, images=None, sensor=None, model=-1, image_frame=None, want=None, out=None,
+                      use_torch_stream=True):
+    """The measurements of a map batch as Edge3D data (ps_measurement_edges; the addMeasurements side, matcher.cpp:769-794 and
+    featuresMap.cpp:255-282): batch a MapBatchDevice that run_map_pairs has filled (or is queued to fill: the call is ordered
+    behind it), xy_undist (frames, maxKpts, 2) float32 -- the xy_undist of the FrameRowsDevice the batch's frames are.  Pair p's
+    final inliers, in match-list order, fill the first count[p] rows.  Other arguments as feature_uncertainty.  Returns a
+    MeasurementEdges of batch.P sets of batch.cap rows."""
+    dev, frames = batch.device, batch.frames.num_frames
+    _expect(xy_undist, torch.float32, (frames, batch.frames.max_kpts, 2))
+    if want is None:
+        want = [n for n, _, _ in _EDGE_ARRAYS if not (n == "gradient" and images is None)]
+    out = out or MeasurementEdges(batch.P, batch.cap, dev, want)
+    s, ds, image_frame = _uncertainty_sets(images, depth, image_frame, frames, dev)
+    sensor = sensor or sensor_model()
+    out.image_frame = image_frame      # (held: the queued kernel reads it)
+    o = out.edges_struct()
+    _on_torch_stream(ctx, dev, lambda: ctx.measurement_edges_device(geometry, sensor, model, s, ds, image_frame.data_ptr(), batch.batch_view(),
+                                                                     batch.view(), xy_undist.data_ptr(), o), use_torch_stream)
+    return out
 
 
 class MapBatchF32Device(MapBatchDevice):
