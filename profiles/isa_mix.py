@@ -22,7 +22,8 @@ from collections import Counter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-mllvm", "-amdgpu-mfma-vgpr-form",
-         "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-S", "--cuda-device-only"]
+         "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-S", "--cuda-device-only",
+         "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "putslam_amd", "csrc")]
 
 
 def asm_of(src, td, name):
@@ -59,7 +60,7 @@ def main():
     # ---- decision-exact reprojection kernels: evaluation block (ends in v_addc) and pre-test block (packed, no v_addc) ----
     for mode in (1, 2):
         for kind, label in ((0, "stage0"), (1, "stage1")):
-            bl = blocks_of(body_of(s, "_ZN5psdev20ps_ransac_score_fastILi%dELb1ELi%dEE" % (mode, kind)))
+            bl = blocks_of(body_of(s, "_ZN5psdev20ps_ransac_score_fastILi%dELb1ELi%dELb0EE" % (mode, kind)))
             evals = [valu(t) for _, t in bl if "v_addc_co_u32" in t and t.count("v_pk_") >= 8]
             pre = [valu(t) for _, t in bl if "v_addc_co_u32" not in t and t.count("v_pk_") >= 12 and "ds_" not in t]
             e = {"unit": "(hypothesis, match) evaluation per wave"}
@@ -76,7 +77,7 @@ def main():
             out["ps_ransac_score_fast<%d> %s" % (mode, label)] = e
     # ---- decision-exact Euclidean kernels: the block with the clamped indicator FMAs ----
     for mode in (0, 4):
-        bl = blocks_of(body_of(s, "_ZN5psdev22ps_ransac_score_euclidILi%dELi1EE" % mode))
+        bl = blocks_of(body_of(s, "_ZN5psdev22ps_ransac_score_euclidILi%dELi1ELb0EE" % mode))
         hot = [(t.count("clamp"), valu(t)) for _, t in bl if "clamp" in t]
         hot.sort(key=lambda x: -x[0])
         steps = hot[0][0]   # packed steps in the block (one clamp each), two matches per step

@@ -9,6 +9,7 @@
 // points) in dependency order, and psi_kernel_attributes last.
 #include "ps_kernels.h"
 #include "ps_matcher_mfma.h"
+#include "ps_score_pass.h"
 #include "ps_score_fast.h"
 #include "ps_score_euclid.h"
 #include "ps_internal.h"
@@ -26,9 +27,9 @@
 
 using namespace psdev;
 
-static_assert(kPsReorderMargin == kReorderMargin && kPsReorderTopMax == kReorderTopMax, "ps_internal.h mirrors ps_score_fast.h");
+static_assert(kPsReorderMargin == kReorderMargin && kPsReorderTopMax == kReorderTopMax, "ps_internal.h mirrors ps_score_pass.h");
 static_assert(kPlanBlock == kBlock && kPlanPrefixFixed == kPrefixFixed && kPlanPrefixAdaptive == kPrefixAdaptive && kPlanStages == kStages,
-              "ps_score_plan.h mirrors ps_kernels.h / ps_score_fast.h");
+              "ps_score_plan.h mirrors ps_kernels.h / ps_score_pass.h");
 
 namespace {
 

@@ -25,7 +25,7 @@ struct Buf {
 constexpr int kMaxTimed = 8;   // kernels timed per call
 constexpr int kTimingRing = 128; // calls kept (HIP events on the launch stream around every kernel)
 
-// (mirrors of psdev::kReorderMargin / kReorderTopMax, ps_score_fast.h: the device translation unit checks them with static_asserts)
+// (mirrors of psdev::kReorderMargin / kReorderTopMax, ps_score_pass.h: the device translation unit checks them with static_asserts)
 constexpr int kPsReorderMargin = 16, kPsReorderTopMax = 16;
 constexpr unsigned kUsacMaxHyp = 850000u; // USAC_wrapper.cpp:70
 

@@ -23,7 +23,7 @@ struct PrepArgs {
     int32_t *zeroCounts;    // optional: the first zeroH counts of every pair (row stride zeroStride) to clear for kernel 3's
     int zeroH;              // split-range atomics (saves a memset launch)
     int zeroStride;
-    int32_t *zeroSurvA, *zeroSurvB; // optional: per-pair survivor counters of the staged scoring to clear (ps_score_fast.h)
+    int32_t *zeroSurvA, *zeroSurvB; // optional: per-pair survivor counters of the staged scoring to clear (ps_score_pass.h)
     int skipE, skipF;       // the reprojection kernels' record forms no launch of this call will read (RecPtrs::E / ::F)
 };
 

@@ -54,9 +54,12 @@
 // A wavefront whose bounds do not hold (non-finite model, coordinates beyond 1e15, threshold outside [1e-10, 1e10]) runs
 // the value-exact loop.  Counts equal ps_ransac_score<0/4>'s for every hypothesis (tests/test_gpu_score_variants.py,
 // tests/test_gpu_band_edges.py, the fuzz slice).
+//
+// The staged-scoring protocol around the sweep -- whose hypotheses, which matches, where the model comes from, where counts, survivors
+// and their models go, the walk of a work-group over its passes -- is ps_score_pass.h's, shared with ps_score_fast.h.
 #pragma once
 
-#include "ps_score_fast.h"
+#include "ps_score_pass.h"
 
 namespace psdev {
 
@@ -79,9 +82,10 @@ template <int MODE> PS_D EuclidRec<MODE> load_euclid_rec(const float2 *__restric
     return r;
 }
 
-// KIND (ps_score_fast.h): 0 = the hypotheses [hBase, hBase + hCount) completely (plain launch, stage 0), 1 = stage 1,
+// KIND (ps_score_pass.h): 0 = the hypotheses [hBase, hBase + hCount) completely (plain launch, stage 0), 1 = stage 1,
 // 2 = stages 2+ of the staged scoring.
-// One pass of a work-group (ps_score_fast.h, score_fast_pass): 256 hypotheses, or one pass over the survivor list.
+// One pass of a work-group in the frame of ps_score_pass.h: 256 hypotheses, or one pass over the survivor list.  Around the frame:
+// an idle wavefront leaves at once (no drain to come), and kind 0 requests its bound and records before the sample -> SVD chain.
 template <int MODE, int KIND>
 PS_D bool score_euclid_pass(const float4 *__restrict__ recA, const float4 *__restrict__ recB, const float2 *__restrict__ recG,
                             const float2 *__restrict__ pairBound, const ModelArgs &ma, const ScoreConsts &k,
@@ -90,76 +94,18 @@ PS_D bool score_euclid_pass(const float4 *__restrict__ recA, const float4 *__res
                             const unsigned by, const int p, const int M)
 {
     constexpr int RF = MODE == PS_ADAPTIVE_ERROR ? kEuclidRecFloats4 : kEuclidRecFloats0;
-    __shared__ float s_mdl[12][kBlock];
+    __shared__ LdsModels s_mdl;
     __shared__ int s_tot[kBlock]; // kind 2, split match range: the counts of the range's parts meet here
     __shared__ int s_pref[2];
 
-    int tid = threadIdx.x;
-    // (kind 2 calls this in a loop: without the empty asm the compiler computes everything that hangs on the thread index --
-    // a dozen LDS row addresses -- once before the loop and, short of registers, keeps it in scratch memory, the inlier
-    // counter of the hot loop with it)
-    if (KIND == 2) asm volatile("" : "+v"(tid));
-    const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6); // (wave-uniform by construction: keep it and what hangs on it scalar)
     const size_t rbase = (size_t)p * cap;
     int32_t *__restrict__ cout = counts + (size_t)p * H;
-    int h = st.hBase + (int)bx * kBlock + tid;
-    int hEnd = st.hBase + st.hCount; // this lane scores hypothesis h if h < hEnd
-    // the match range is split on match PAIRS (the packed loop takes two matches per step)
-    const int npair = (M + 1) >> 1;
-    int m0 = 2 * (int)(((long long)npair * by) / msplit);
-    int m1 = 2 * (int)(((long long)npair * (by + 1)) / msplit);
-    m1 = m1 < M ? m1 : M;
-    int best0 = 0;
-    constexpr bool LIST = KIND == 2; // stage >= 2: hypotheses from the survivor list, models from HBM
     constexpr bool pruned = KIND >= 1;
-    int cover = kBlock, slot = tid, part = 0; // kind 2: hypotheses per pass, the lane's place, its part of the match range
-    int mStageEnd = m1;
-    if (LIST) {
-        s_tot[tid] = 0;
-        __syncthreads(); // (a part with a short range must not add into a slot another wavefront has yet to clear)
-    }
-    if (pruned) { // (msplit == 1 in these stages; the cuts are multiples of 64)
-        int hLimit;
-        stage_prefix(cout, st.hBase, sa, M, s_pref, best0, hLimit, // (stage >= 1: hBase = size of the prefix)
-                     st.prefInfo != nullptr ? st.prefInfo + 4 * p : nullptr);
-        stage_range(st, M, best0, m0, m1);
-        // a block with hypotheses that have no model slot (ModelArgs::modelH: long caps) is swept in one piece: nothing of it
-        // is parked or listed
-        {
-            const int blockEnd = st.hBase + ((int)bx + 1) * kBlock;
-            if (!LIST && ma.models != nullptr && (blockEnd < hEnd ? blockEnd : hEnd) > ma.modelH) m1 = M;
-        }
-        mStageEnd = m1;
-        if (m0 >= m1) return true; // an earlier stage finished the pair's matches
-        if (!LIST) {
-            hEnd = hEnd < hLimit ? hEnd : hLimit; // beyond the trip limit: never consumed by the selection
-            if (st.hBase + (int)bx * kBlock >= hEnd) return true;
-        } else {
-            if (msplit > 1) { // the LAST stage may split its range over work-groups too: their counts meet in counts[]
-                const int blen = (((m1 - m0 + msplit - 1) / msplit) + 63) & ~63;
-                m0 += (int)by * blen;
-                m1 = m1 < m0 + blen ? m1 : m0 + blen;
-                if (m0 >= m1) return false;
-            }
-            const int n = st.countIn[p];
-            cover = list_cover(n);
-            part = __builtin_amdgcn_readfirstlane(tid / cover);
-            slot = tid - part * cover;
-            const int i = (int)bx * cover + slot;
-            hEnd = 0x7FFFFFFF;
-            h = i < n ? st.listIn[(size_t)p * st.listStride + i] : 0x7FFFFFFF; // (h >= hEnd: idle lane)
-            // this wavefront's part of the stage's match range (whole blocks of 64 matches; a part may be empty)
-            const int parts = kBlock / cover;
-            const int plen = ((m1 - m0 + parts * 64 - 1) / (parts * 64)) * 64;
-            m0 += part * plen;
-            m1 = m1 < m0 + plen ? m1 : m0 + plen;
-            m1 = m1 < m0 ? m0 : m1; // (an empty part: nothing to sweep, no odd last match either)
-        }
-    }
+    PassState ps;
+    if (const PassGo go = pass_begin<KIND>(ps, ma, sa, st, cout, s_tot, s_pref, msplit, bx, by, p, M)) return go == kPassDone;
+    const int tid = ps.tid, lane = ps.lane, wv = ps.wv, m0 = ps.m0, m1 = ps.m1;
 
-    // a wavefront without a hypothesis of its own (ps_score_fast.h; not in a pass with a split match range: barrier to come)
-    if (cover == kBlock && hFirstOfWave(h, lane) >= hEnd) return false;
+    if (wave_idle(ps)) return false; // (not in a pass with a split match range: barrier to come)
 
     // A launch with a split match range is a small one (a handful of pairs): one wavefront per SIMD, nothing hides a load.
     // The pair's bound and this work-group's records were written by the previous launch (HBM latency, 2 x 1.5 us exposed
@@ -180,36 +126,9 @@ PS_D bool score_euclid_pass(const float4 *__restrict__ recA, const float4 *__res
     set_identity(mdl);
     set_identity(inv);
     bool valid = false;
-    if (LIST) {
-        if (h < hEnd) {
-            load_model(ma, (size_t)p * ma.modelH + h, mdl); // parked by stage 1 (only valid samples survive it; h < modelH: a
-                                                            // hypothesis beyond is swept completely by stage 1 and never listed)
-            valid = true;
-        }
-    } else if (KIND == 0 && st.validMask != nullptr && !st.genOnly) {
-        // stage 0, second launch: models and validity read back (ps_score_fast.h)
-        const unsigned long long vm = uniform64(st.validMask[(size_t)p * ((st.hCount + 63) >> 6) + (bx * (kBlock / 64) + wv)]);
-        valid = h < hEnd && lane_in(vm);
-        if (h < hEnd) load_model(ma, (size_t)p * ma.modelH + h, mdl); // (launches of this form have a slot for every hypothesis)
-    } else {
-        if (h < hEnd) valid = gen_model(recA, recB, rbase, (uint32_t)M, ma, base_seed(ma) + (uint64_t)p, (uint32_t)h, mdl);
-        // (stage 1 parks only the models of its survivors, at the end: the abandoned majority is never read again)
-        if (ma.models && by == 0 && !pruned) {
-            const int hs = stage_hypothesis_again(false, st, (int)bx * kBlock, tid, p, H); // (ps_score_fast.h)
-            if (hs < hEnd && hs < ma.modelH) store_model(ma, (size_t)p * ma.modelH + hs, mdl);
-        }
-        if (KIND == 0 && st.genOnly) { // stage 0, first launch: models and validity only
-            const unsigned long long vm = __builtin_amdgcn_ballot_w64(valid);
-            if (lane == 0) st.validMask[(size_t)p * ((st.hCount + 63) >> 6) + (bx * (kBlock / 64) + wv)] = vm;
-            return false;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) s_mdl[3 * i + j][tid] = mdl.R[i][j];
-        s_mdl[9 + i][tid] = mdl.t[i];
-    }
+    pass_model<KIND>(ps, recA, recB, rbase, ma, st, H, bx, by, p, M, mdl, valid);
+    if (KIND == 0 && st.genOnly) return false; // (stage 0, first launch: models and validity only)
+    lds_put_model(s_mdl, tid, mdl);
 
     const float4 *__restrict__ pa = recA + rbase;
     const float4 *__restrict__ pb = recB + rbase;
@@ -301,12 +220,7 @@ PS_D bool score_euclid_pass(const float4 *__restrict__ recA, const float4 *__res
                 todo &= todo - 1ull;
                 const int t = wv * 64 + l;
                 Rigid md;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) md.R[i][j] = s_mdl[3 * i + j][t];
-                    md.t[i] = s_mdl[9 + i][t];
-                }
+                lds_get_model(s_mdl, t, md);
                 const int mm = blk + lane;
                 bool in = false;
                 if (mm < bend) {
@@ -329,46 +243,7 @@ PS_D bool score_euclid_pass(const float4 *__restrict__ recA, const float4 *__res
             atomicAdd(&dbg[1], (unsigned long long)(m1 - m0) * 64ull);
         }
     }
-    int tidE = tid; // (a fresh copy for the epilogue's LDS addresses: kept alive across the loops they went to scratch memory)
-    asm volatile("" : "+v"(tidE));
-    if (LIST && cover < kBlock) { // (work-group uniform) the parts of the match range add up
-        if (part > 0 && h < hEnd) atomicAdd(&s_tot[slot], cnt);
-        __syncthreads();
-        if (part == 0) cnt += s_tot[slot];
-    }
-    if (pruned) {
-        h = stage_hypothesis_again(LIST, st, (int)bx * cover, slot, p, H);
-        const bool mine = h < hEnd && part == 0;
-        if (LIST && msplit > 1) { // (last stage, range split over work-groups: nothing survives it, the counts add up)
-            if (mine && valid && cnt) atomicAdd(&cout[h], cnt);
-            return false;
-        }
-        const int cnt0 = (LIST && mine) ? cout[h] : 0; // count so far
-        const int total = valid ? cnt0 + cnt : 0; // model not computed -> iteration skipped (RANSAC.cpp:107)
-        if (mine) cout[h] = total;
-        // still able to become a record?  (count so far + matches left > best count of the earlier hypotheses)
-        const bool alive = mine && valid && total + (M - mStageEnd) > best0;
-        if (!LIST && ma.models && h < ma.modelH && (alive || (mine && mStageEnd >= M))) { // survivors (or: this stage was the whole sweep)
-            Rigid md;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) md.R[i][j] = s_mdl[3 * i + j][tidE];
-                md.t[i] = s_mdl[9 + i][tidE];
-            }
-            store_model(ma, (size_t)p * ma.modelH + h, md);
-        }
-        if (st.stage < kStages && mStageEnd < M) stage_append(alive, h, st.listOut, st.countOut, p, st.listStride);
-        return false;
-    }
-    h = stage_hypothesis_again(false, st, (int)bx * kBlock, tid, p, H);
-    if (h < hEnd) {
-        if (!valid) cnt = 0; // model not computed -> iteration skipped (RANSAC.cpp:107)
-        if (msplit == 1)
-            cout[h] = cnt;
-        else if (cnt)
-            atomicAdd(&cout[h], cnt);
-    }
+    pass_finish<KIND>(ps, s_mdl, s_tot, cout, ma, st, H, msplit, bx, p, M, valid, cnt);
     return false;
 }
 
@@ -384,31 +259,9 @@ __global__ __launch_bounds__(kBlock, (KIND == 2 || LOOP) ? 5 : (KIND == 0 ? 7 : 
     unsigned long long *__restrict__ dbg)
 {
     static_assert(MODE == PS_EUCLIDEAN_ERROR || MODE == PS_ADAPTIVE_ERROR, "the Euclidean metrics");
-    // hypotheses of this launch: [hBase, hBase + hCount) (plain launch: [0, H); stages 0 / 1), or a survivor list swept by
-    // hCount / 256 work-groups per pair (stages 2+)
-    static_assert(!LOOP || KIND == 1, "the looping form is stage 1's");
-    const unsigned blocks = (unsigned)((st.hCount + kBlock - 1) / kBlock);
-    const unsigned hb = LOOP ? (unsigned)st.loopGroups : blocks; // work-groups per pair and part of the match range
-    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned bx = L % hb, by = (L / hb) % (unsigned)msplit;
-    const int p = (int)(L / (hb * (unsigned)msplit));
-    const int M = mvalid[p];
-    if (M < minRun) return; // too few matches: kernel 4 returns identity (RANSAC.cpp:77-80)
-    if (LOOP) {
-        for (unsigned b = bx; b < blocks; b += hb) {
-            if (b != bx) __syncthreads(); // (the pass before is done with the work-group's LDS)
-            if (score_euclid_pass<MODE, KIND>(recA, recB, recG, pairBound, ma, k, ec, sa, st, H, cap, msplit, counts, dbg, b, by, p, M))
-                break; // (uniform over the work-group)
-        }
-    } else if (KIND == 2) {
-        const int n = st.countIn[p];
-        const int cover = list_cover(n);
-        for (unsigned b = bx; (int)b * cover < n; b += hb) {
-            if (b != bx) __syncthreads(); // (the pass before is done with the work-group's LDS)
-            score_euclid_pass<MODE, KIND>(recA, recB, recG, pairBound, ma, k, ec, sa, st, H, cap, msplit, counts, dbg, b, by, p, M);
-        }
-    } else
-        score_euclid_pass<MODE, KIND>(recA, recB, recG, pairBound, ma, k, ec, sa, st, H, cap, msplit, counts, dbg, bx, by, p, M);
+    score_kernel_body<KIND, LOOP>(mvalid, st, minRun, msplit, [&](unsigned bx, unsigned by, int p, int M) __attribute__((always_inline)) {
+        return score_euclid_pass<MODE, KIND>(recA, recB, recG, pairBound, ma, k, ec, sa, st, H, cap, msplit, counts, dbg, bx, by, p, M);
+    });
 }
 
 } // namespace psdev

@@ -45,9 +45,13 @@
 //
 // A wavefront whose bounds do not hold (non-finite model, S fmaxK > 2^40, threshold outside [1e-10, 1e15]) runs
 // the value-exact loop of ps_kernels.h instead.
+//
+// The staged-scoring protocol around the sweep (StageArgs, the replay of the prefix, the frame of a pass and the walk of a work-group
+// over its passes) is ps_score_pass.h's, shared with ps_score_euclid.h; ps_stage_reorder, which runs between stage 0 and stage 1 of
+// either family, is at the end of this file.
 #pragma once
 
-#include "ps_kernels.h"
+#include "ps_score_pass.h"
 
 namespace psdev {
 
@@ -62,18 +66,7 @@ struct FastConsts {
     int enabled;  // thresholds and camera constants inside the range the bounds were derived for
 };
 
-// Limits of the decision-exact Euclidean test (derivation: ps_score_euclid.h), used by ps_ransac_score_euclid<0/4> and by
-// the Euclidean term of ps_ransac_score_fast<2>.
-struct EuclidConsts {
-    float tbLo;  // errorVersion 0 / 2: sqrt(B) (1 - 6u) rounded down; errorVersion 4: thr (1 - 7u) rounded down
-    float tbHi;  // ... (1 + 6u) / (1 + 7u) rounded up
-    int enabled; // threshold inside the range the bounds were derived for
-};
-
 constexpr int kQueueCap = 256; // parked evaluations per wave (drained by the wave itself when full)
-constexpr float kEpsU = 5.9604644775390625e-08f; // 2^-24
-
-typedef float v2f_t __attribute__((ext_vector_type(2)));
 
 // Both folded models of one hypothesis, packed across the two directions for v_pk_fma_f32:
 // .x = current point -> previous image (model), .y = previous point -> current image (inverse model).
@@ -101,19 +94,6 @@ PS_D void make_fast(const Rigid &m, const Rigid &inv, float fx, float fy, FastMo
     f.t2 = v2f_t{m.t[2], inv.t[2]};
 }
 
-// largest row sum of |R| and largest |t| (NaN anywhere makes the sums NaN: the caller's comparison then fails)
-PS_D void model_norms(const Rigid &m, float &rho, float &tau)
-{
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float rs = (fabsf(m.R[i][0]) + fabsf(m.R[i][1])) + fabsf(m.R[i][2]);
-        rho = rs > rho ? rs : (rs == rs ? rho : rs); // propagate NaN
-        const float ta = fabsf(m.t[i]);
-        tau = ta > tau ? ta : (ta == ta ? tau : ta);
-    }
-}
-
-PS_D v2f_t pk_fma(v2f_t a, v2f_t b, v2f_t c) { return __builtin_elementwise_fma(a, b, c); }
 // The two limits of the reprojection test from TWO register pairs, K = (kLo, kHi) and G = (G2p, -G2p), with the halves
 // broadcast by op_sel:   lower = kLo * q - G2p   (K.x, q, G.y)      upper = kHi * q + G2p   (K.y, q, G.x)
 // (inline asm: left to the register allocator the broadcasts became v_mov pairs inside the hot loop in two of the builds)
@@ -146,215 +126,6 @@ PS_D v2f_t fast_sq2(const FastModel &f, v2f_t px, v2f_t py, v2f_t pz, v2f_t kx, 
 }
 
 
-// ------------------------------------------------------------------------------------------
-// Staged scoring: hypotheses that provably cannot matter are abandoned between launches.
-//
-// The selection of kernel 4 consumes the counts sequentially: hypothesis i matters only if its count is a RECORD,
-// count_i > max_{j<i} count_j (strict '>' first-best, RANSAC.cpp:438-455; the arg-max of the fixed schedule takes the
-// lowest index among equals, the same rule), and only while i is below the adaptive trip limit, which from record to
-// record only shrinks (RANSAC.cpp:450-453, USAC.h:944-971).  So a large batch is scored in stages:
-//   stage 0   the first 256 hypotheses of every pair (64 for the adaptive schedules, whose limit after a few dozen
-//             hypotheses is usually below that already), all matches (the plain launch);
-//   stage 1   every later hypothesis below the trip limit L0 the prefix leaves, matches [0, c1);
-//   stage 2   the SURVIVORS of stage 1, matches [c1, c2);        stage 3   the survivors of stage 2, matches [c2, M).
-// Every work-group of stages 1-3 first replays the selection over the prefix (wave_replay_prefix: the record walk of
-// ps_select_refit) and gets B0 = the best count so far and L0.  After its match range a hypothesis survives if
-// count so far + matches left > B0; otherwise it can no longer become a record and keeps its partial count
-// (<= B0: never selected, never a record).  Survivors are appended (one atomic per wavefront) to the next stage's
-// per-pair list, which the next launch reads back densely: 256 live hypotheses per work-group again, full wavefronts,
-// no barrier and no re-packing inside the hot loops -- they are the plain loops.  The models travel through HBM
-// (ma.models, 48 B per hypothesis), the partial counts through counts[].
-//   c1 = about 1.15 (M - B0) + 32 matches: where a hypothesis without inliers has run out of chances (with 75 % inliers
-//   a bad sample is abandoned after a quarter of the matches); c2 halves the rest.  With the reference's own <= 487-iteration
-//   schedule L0 is typically 2 ... 30, far below the prefix: stages 1-3 return at once.
-// An in-kernel form (checkpoints + re-packing of live lanes through LDS inside one launch) was built first and kept
-// the wave-steps it saved (29 %) from showing up as time: barriers, rebuilds and 300 bytes of scratch per lane made the
-// loop 20 % slower before anything was abandoned (profiles/r03c/README.md).
-// Outputs of kernel 4 are unchanged bit for bit (tests/test_gpu_prune.py: staged vs complete vs oracle); what changes is
-// the meaning of counts[] for abandoned hypotheses (a lower bound <= B0 instead of the count), which is why the
-// diagnostic ps_debug_ransac_counts and small batches score completely.
-// ------------------------------------------------------------------------------------------
-constexpr int kPrefixFixed = kBlock; // hypotheses scored completely by stage 0: fixed schedule (arg-max over all H) ...
-constexpr int kPrefixAdaptive = 64;  // ... and RANSAC / USAC schedules (the reference consumes 3 of 487 on good data)
-constexpr int kStages = 3;      // pruned stages after the prefix
-constexpr int kReorderTopMax = 16; // ps_stage_reorder: at most this many of the prefix's best hypotheses vote on the order
-constexpr int kReorderMargin = 16; // reordered sweep: stage 1 ends this many matches (rounded up to 64) after the point where
-                                   // a hypothesis that rejects all the leading matches is out
-
-struct StageArgs {
-    int stage;                 // 0 = the hypotheses [hBase, hBase + hCount) completely (the plain launch: [0, H)); 1 .. kStages
-                               // = pruned stages
-    int hBase, hCount;         // stage 0 / 1: the hypothesis range of this launch
-    int listStride;            // entries per pair of the survivor lists (= hypotheses with a model slot: only those are listed)
-    const int32_t *listIn;     // stage >= 2: survivors of the previous stage, [P][listStride] hypothesis indices ...
-    const int32_t *countIn;    //             ... and how many per pair
-    int32_t *listOut;          // stage < kStages: where this stage's survivors go
-    int32_t *countOut;
-    const int32_t *perm;       // stage >= 1 after ps_stage_reorder: [P][cap], match of the ORIGINAL record arrays at each position
-                               // of the reordered hot record (null: the hot record is in the original order)
-    const float2 *frontRec;    // after ps_stage_reorder (reprojection metrics): [P][cap / 2][5] the matches ALL voters reject, two
-                               // per record: (cur.x) (cur.y) (cur.z) (cx - uOld) (cy - vOld) of matches 2k | 2k + 1 -- the
-                               // operands of the one-direction pre-test of stage 1 (null: no pre-test)
-    int margin, c2div;         // reordered sweep: where stages 1 and 2 end (stage_range)
-    unsigned long long *validMask; // stage 0 in two launches (models once, then the sweep split over many work-groups): [P][hCount/64]
-    int genOnly;               // 1 = this launch only generates the models of [hBase, hBase + hCount), parks them and writes
-                               // validMask; 0 with validMask set = this launch reads both back instead of generating
-    int single;                // 1 = stage 1 sweeps ALL matches and is the only stage after the prefix (adaptive schedules
-                               // without reordering: what their trip limit leaves is little, two more launches cost more)
-    int gran;                  // the stage cuts are multiples of this (64: the Euclidean kernel recounts blocks of 64 matches;
-                               // 8 for the reprojection kernels, which only need even cuts)
-    int loopGroups;            // stage 1 of an adaptive schedule with a long cap (USAC's 850 000: 3320 blocks of 256 hypotheses per
-                               // pair, of which the trip limit leaves a handful): this many work-groups per pair take the blocks
-                               // bx, bx + loopGroups, ... and stop at the first block beyond the limit (0: one work-group per block)
-    const int32_t *prefInfo;   // after ps_stage_reorder: [P][4] = (best count, trip limit) the prefix leaves, how many matches at
-                               // the front of the reordered record ALL voters reject, reserved (null: every work-group of
-                               // the stages replays the prefix itself)
-};
-
-// Replay of the sequential selection over counts[0 .. n) by one wavefront (the rule of ps_select_refit part (1)):
-// best = the best count among the consumed ones, limit = the trip limit afterwards (a.H for the fixed schedule).
-// bestIdx = the hypothesis that holds `best` (the first of equals), -1 without a record.
-PS_D void wave_replay_prefix(const int32_t *__restrict__ cnts, int n, const SelectArgs &a, int M, int &best, int &limit,
-                             int &bestIdx)
-{
-    const int lane = threadIdx.x & 63;
-    bestIdx = -1;
-    if (a.estimator == PS_EST_FIXED) {
-        // (count, lowest index first) as one key: counts are <= PS_MAX_KPTS < 2^15, prefixes <= 2^16 hypotheses
-        int b = 0;
-        for (int i = lane; i < n; i += 64) b = max(b, (cnts[i] << 16) | (0xFFFF - i));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) b = max(b, __shfl_xor(b, o, 64));
-        best = b >> 16;
-        if (best > 0) bestIdx = 0xFFFF - (b & 0xFFFF);
-        limit = a.H;
-        return;
-    }
-    int pos = 0;
-    best = 0;
-    limit = a.iter0;
-    for (;;) {
-        const int lim = limit < n ? limit : n;
-        unsigned found = 0xFFFFFFFFu;
-        for (int i = pos + lane; i < lim; i += 64)
-            if (cnts[i] > best) {
-                found = (unsigned)i;
-                break;
-            }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned other = (unsigned)__shfl_xor((int)found, o, 64);
-            found = other < found ? other : found;
-        }
-        if (found == 0xFFFFFFFFu) break;
-        best = cnts[found];
-        bestIdx = (int)found;
-        pos = (int)found + 1;
-        limit = a.estimator == PS_EST_USAC ? usac_limit(a, (unsigned)best, (unsigned)M)
-                                           : ransac_limit(a, (float)best / (float)M); // ratio as RANSAC.cpp:280
-    }
-}
-
-// Match range [lo, hi) of pruned stage `stage` (1 .. kStages) for a pair with M matches whose prefix reached best0.
-// reordered: the stages sweep the record ps_stage_reorder wrote -- the matches the prefix's best hypothesis rejects first.
-// Every hypothesis that is not better than that one rejects (almost all of) them too and is out a few matches later.
-PS_D void stage_range(const StageArgs &st, int M, int best0, int &lo, int &hi)
-{
-    const int stage = st.stage;
-    const bool reordered = st.perm != nullptr;
-    int c1 = M, c2 = M;
-    if (best0 > 0 && !st.single) {
-        const int miss = M - best0; // a hypothesis is out once it has missed this many matches
-        if (reordered) {
-            const int g1 = st.gran - 1; // (gran is a power of two)
-            c1 = (miss + st.margin + g1) & ~g1;
-            if (c1 >= M - M / 8) c1 = M;
-            if (c1 < M) {
-                // (stage 2 ends where it would with stage 1 cut at a multiple of 64, whatever stage 1's granularity)
-                const int c64 = (c1 + 63) & ~63;
-                const int step = ((M - c64) / st.c2div + 63) & ~63;
-                c2 = c64 + (step > 0 ? step : 64); // (never an empty stage 2: it hands the survivors on)
-                if (c2 >= M - M / 16) c2 = M;
-            }
-        } else {
-            c1 = (miss + miss / 7 + 32 + 63) & ~63;
-            if (c1 >= M - M / 8) c1 = M; // nothing worth a second launch
-            if (c1 < M) {
-                c2 = (c1 + (M - c1) / 2 + 63) & ~63;
-                if (c2 >= M - M / 16) c2 = M;
-            }
-        }
-    }
-    static_assert(kStages == 3, "three pruned stages");
-    lo = stage == 1 ? 0 : (stage == 2 ? c1 : c2); // (selects, not an indexed array: that would live in scratch memory)
-    hi = stage == 1 ? c1 : (stage == 2 ? c2 : M);
-}
-
-// hypothesis of lane 0 of the calling lane's wavefront (h is consecutive over the lanes, or 0x7FFFFFFF for an idle lane
-// of a survivor list: the wave's first lane then tells whether the whole wave is idle)
-PS_D int hFirstOfWave(int h, int lane) { return __builtin_amdgcn_readfirstlane(h); }
-
-// What every work-group of a pruned stage needs before it starts: the prefix's best count and trip limit (work-group
-// uniform, in SGPRs) -- wave 0 replays, the others wait.
-PS_D void stage_prefix(const int32_t *__restrict__ cnts, int nPrefix, const SelectArgs &sa, int M, int *s_pref, int &best0,
-                       int &hLimit, const int32_t *__restrict__ prefInfo = nullptr)
-{
-    if (prefInfo != nullptr) { // replayed once per pair by ps_stage_reorder (scalar loads, no barrier)
-        best0 = prefInfo[0];
-        hLimit = best0 > 0 ? prefInfo[1] : sa.H;
-        return;
-    }
-    if ((threadIdx.x >> 6) == 0) {
-        int b, l, bi;
-        wave_replay_prefix(cnts, nPrefix, sa, M, b, l, bi);
-        if ((threadIdx.x & 63) == 0) {
-            s_pref[0] = b;
-            s_pref[1] = l;
-        }
-    }
-    __syncthreads();
-    // (LDS loads count as divergent for the compiler: readfirstlane keeps the values in SGPRs and the branches scalar)
-    best0 = __builtin_amdgcn_readfirstlane(s_pref[0]);
-    // the limit only shrinks from record to record, but the FIRST record may raise it above its initial value
-    // (RANSAC.cpp:30 starts from computeRANSACIteration(0.20); a first ratio below 0.2 gives more): without a record in
-    // the prefix nothing can be cut
-    hLimit = best0 > 0 ? __builtin_amdgcn_readfirstlane(s_pref[1]) : sa.H;
-}
-
-// Appends the hypotheses of the lanes with `alive` to the next stage's list of pair p (one atomic per wavefront).
-PS_D void stage_append(bool alive, int h, int32_t *__restrict__ listOut, int32_t *__restrict__ countOut, int p, int stride)
-{
-    const unsigned long long am = __builtin_amdgcn_ballot_w64(alive);
-    if (am == 0ull) return;
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == __builtin_ctzll(am)) base = atomicAdd(&countOut[p], __popcll(am));
-    base = __builtin_amdgcn_readlane(base, __builtin_ctzll(am));
-    if (alive) listOut[(size_t)p * stride + base + lanes_below(am)] = h;
-}
-
-// The hypothesis of a lane, derived AGAIN at the end of a staged launch from values that cost no vector register in between
-// (the scalar work-group offset passes through an empty asm, so that the compiler cannot keep the first derivation -- or
-// the 64-bit addresses built on it -- alive across the loops: with the vectorisers on, at seven waves per SIMD, it kept
-// them in scratch memory; kept for the registers it still saves).
-// base = first hypothesis (or list entry) of the work-group's pass, slot = the lane's place in it.
-PS_D int stage_hypothesis_again(bool list, const StageArgs &st, int base, int slot, int p, int H)
-{
-    asm volatile("" : "+s"(base));
-    if (!list) return st.hBase + base + slot;
-    const int i = base + slot;
-    return i < st.countIn[p] ? st.listIn[(size_t)p * st.listStride + i] : 0x7FFFFFFF;
-}
-
-// Stages 2+: hypotheses one pass of a work-group takes from the survivor list.  After the reordered stage 1 the lists are
-// short and the ranges left are long: a pair with at most 64 (128) survivors is swept by ONE work-group whose four
-// wavefronts each take a quarter (two halves) of the match range for the same hypotheses and add their counts up in LDS --
-// a single wavefront alone on its SIMD waits out every record load (stage 3 of the bench step: 21 survivors per pair, 157 us
-// that way, profiles/r03k).  Longer lists: 256 hypotheses per pass as before.  The launches carry a few work-groups per
-// pair (StageArgs::hCount / 256) that loop over the list: thousands of work-groups that find nothing to do still cost
-// their launch (30 ... 50 us per empty stage of 7485 work-groups).
-PS_D int list_cover(int n) { return n <= 64 ? 64 : (n <= 128 ? 128 : kBlock); }
-
 // Two record forms.  BIG (launches that fill the chip several times over): the packed 40-byte match record (RecPtrs::F: the
 // loop is sensitive to the scalar-cache footprint of the records every wave streams).  Small launches are bound by the
 // latency of ONE prologue and of cold record loads: the three 16-byte records, whose loads go out side by side.
@@ -363,15 +134,14 @@ PS_D int list_cover(int n) { return n <= 64 ? 64 : (n <= 128 ? 128 : kBlock); }
 // three FMA chains (plain instructions: only one direction has a Euclidean test), the squared residual against the same
 // per-lane limits lo / hi; "inlier" needs both certain, one certain "outlier" suffices, anything else is parked and decided by
 // inlier_test<2>().  40 vector instructions per evaluation instead of 61 + the Euclidean part of the value-exact kernel.
-// KIND: what the launch scores (StageArgs).  0 = the hypotheses [hBase, hBase + hCount) completely -- the plain launch over
-// [0, H) and stage 0 of the staged scoring; 1 = stage 1 (generates its models, first match range); 2 = stages 2+ (models and
-// hypothesis list read back, a loop over the list).
+// KIND: what the launch scores (StageArgs, ps_score_pass.h).
 // Registers: the library is built with the SLP vectoriser and VectorCombine off (Makefile).  With them the scalar prologue
 // (sample -> Umeyama -> SVD -> general inverse) was turned into packed instructions whose aligned register pairs and
 // shuffles cost 20 registers: 72 VGPRs + 12 ... 19 values per lane in scratch memory at seven waves per SIMD (0.4 GB of HBM
 // traffic per 499 pairs, profiles/r03i) against 56 VGPRs, no scratch memory and eight waves without (profiles/r03l).  The
 // epilogues still derive the hypothesis index again instead of keeping it across the loops.
-// One pass of a work-group: the hypotheses [hBase + bx * 256, + 256) (kinds 0 / 1) or one pass over the survivor list (kind 2).
+// One pass of a work-group in the frame of ps_score_pass.h.  Around the frame: a wavefront without a hypothesis skips the sweep but
+// goes on to the work-group's final drain; the pair's bound is read after the model is parked; s_cnt is this kernel's own.
 template <int MODE, bool BIG, int KIND>
 PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restrict__ recB, const float4 *__restrict__ recC,
                           const float4 *__restrict__ recE, const float2 *__restrict__ recF,
@@ -381,7 +151,7 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
                           const unsigned by, const int p, const int M)
 {
     constexpr bool EUCLID = MODE == PS_EUCLIDEAN_AND_REPROJECTION_ERROR;
-    __shared__ float s_mdl[12][kBlock];
+    __shared__ LdsModels s_mdl;
     __shared__ uint32_t s_q[kBlock / 64][kQueueCap];
     __shared__ int s_cnt[kBlock];
     __shared__ int s_tot[kBlock]; // kind 2, split match range: the counts of the range's parts meet here
@@ -389,74 +159,16 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
     __shared__ int s_qn[kBlock / 64]; // what each wave leaves to the work-group's final drain
     static_assert(kBlock / 64 == 4, "the final drain finds an entry's wave among four");
 
-    int tid = threadIdx.x;
-    // (kind 2 calls this in a loop: without the empty asm the compiler computes everything that hangs on the thread index --
-    // a dozen LDS row addresses -- once before the loop and, short of registers, keeps it in scratch memory, the inlier
-    // counter of the hot loop with it)
-    if (KIND == 2) asm volatile("" : "+v"(tid));
-    const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6); // (wave-uniform by construction: keep it and what hangs on it scalar)
     const size_t rbase = (size_t)p * cap;
     int32_t *__restrict__ cout = counts + (size_t)p * H;
-    int h = st.hBase + (int)bx * kBlock + tid;
-    int hEnd = st.hBase + st.hCount; // this lane scores hypothesis h if h < hEnd
-    // (the match range is split on match PAIRS: the loop takes two matches per trip, only the pair's last range can be odd)
-    const int npair = (M + 1) >> 1;
-    int m0 = 2 * (int)(((long long)npair * by) / msplit);
-    int m1 = 2 * (int)(((long long)npair * (by + 1)) / msplit);
-    m1 = m1 < M ? m1 : M;
-    int best0 = 0;
-    constexpr bool LIST = KIND == 2; // stage >= 2: hypotheses from the survivor list, models from HBM
     constexpr bool pruned = KIND >= 1;
-    int cover = kBlock, slot = tid, part = 0; // kind 2: hypotheses per pass, the lane's place, its part of the match range
-    int mStageEnd = m1;
-    if (LIST) {
-        s_tot[tid] = 0;
-        __syncthreads(); // (a part with a short range must not add into a slot another wavefront has yet to clear)
-    }
-    if (pruned) { // (msplit == 1 in these stages)
-        int hLimit;
-        stage_prefix(cout, st.hBase, sa, M, s_pref, best0, hLimit, // (stage >= 1: hBase = size of the prefix)
-                     st.prefInfo != nullptr ? st.prefInfo + 4 * p : nullptr);
-        stage_range(st, M, best0, m0, m1);
-        // a block with hypotheses that have no model slot (ModelArgs::modelH: long caps) is swept in one piece: nothing of it
-        // is parked or listed
-        {
-            const int blockEnd = st.hBase + ((int)bx + 1) * kBlock;
-            if (!LIST && ma.models != nullptr && (blockEnd < hEnd ? blockEnd : hEnd) > ma.modelH) m1 = M;
-        }
-        mStageEnd = m1;
-        if (m0 >= m1) return true; // an earlier stage finished the pair's matches
-        if (!LIST) {
-            hEnd = hEnd < hLimit ? hEnd : hLimit; // beyond the trip limit: never consumed by the selection
-        } else {
-            if (msplit > 1) { // the LAST stage may split its range over work-groups too: their counts meet in counts[]
-                const int blen = (((m1 - m0 + msplit - 1) / msplit) + 63) & ~63;
-                m0 += (int)by * blen;
-                m1 = m1 < m0 + blen ? m1 : m0 + blen;
-                if (m0 >= m1) return false;
-            }
-            const int n = st.countIn[p];
-            cover = list_cover(n);
-            part = __builtin_amdgcn_readfirstlane(tid / cover);
-            slot = tid - part * cover;
-            const int i = (int)bx * cover + slot;
-            hEnd = 0x7FFFFFFF;
-            h = i < n ? st.listIn[(size_t)p * st.listStride + i] : 0x7FFFFFFF; // (h >= hEnd: idle lane)
-            // this wavefront's part of the stage's match range (whole blocks of 64 matches; a part may be empty)
-            const int parts = kBlock / cover;
-            const int plen = ((m1 - m0 + parts * 64 - 1) / (parts * 64)) * 64;
-            m0 += part * plen;
-            m1 = m1 < m0 + plen ? m1 : m0 + plen;
-            m1 = m1 < m0 ? m0 : m1; // (an empty part: nothing to sweep, no odd last match either)
-        }
-        if (!LIST && st.hBase + (int)bx * kBlock >= hEnd) return true;
-    }
+    PassState ps;
+    if (const PassGo go = pass_begin<KIND>(ps, ma, sa, st, cout, s_tot, s_pref, msplit, bx, by, p, M)) return go == kPassDone;
+    const int tid = ps.tid, lane = ps.lane, wv = ps.wv, m0 = ps.m0, m1 = ps.m1;
 
-    // (a wavefront without a hypothesis of its own has nothing to sweep -- the 64-hypothesis prefix of the adaptive
-    // schedules fills one of the four; a pass with a split match range has no such wavefront -- but it goes to the barriers
-    // of the work-group's final drain and takes its share of the entries; the models-only launch has neither)
-    const bool idle = cover == kBlock && hFirstOfWave(h, lane) >= hEnd; // (wave-uniform)
+    // (a wavefront without a hypothesis of its own goes to the barriers of the work-group's final drain and takes its share of
+    // the entries; the models-only launch has neither)
+    const bool idle = wave_idle(ps);
     if (KIND == 0 && st.genOnly && idle) return false;
 
     const float4 *__restrict__ pa = recA + rbase;
@@ -477,37 +189,9 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
     if (!idle) { // (not indented: down to the final drain)
     Rigid mdl;
     set_identity(mdl);
-    if (LIST) {
-        if (h < hEnd) {
-            load_model(ma, (size_t)p * ma.modelH + h, mdl); // parked by stage 1 (only valid samples survive it; h < modelH: a
-                                                            // hypothesis beyond is swept completely by stage 1 and never listed)
-            valid = true;
-        }
-    } else if (KIND == 0 && st.validMask != nullptr && !st.genOnly) {
-        // stage 0, second launch: the models were generated once by the first (the sweep is split over msplit work-groups,
-        // each of which would otherwise repeat the sample -> SVD chain: 63 % of stage 0's instructions with four parts)
-        const unsigned long long vm = uniform64(st.validMask[(size_t)p * ((st.hCount + 63) >> 6) + (bx * (kBlock / 64) + wv)]);
-        valid = h < hEnd && lane_in(vm);
-        if (h < hEnd) load_model(ma, (size_t)p * ma.modelH + h, mdl); // (launches of this form have a slot for every hypothesis)
-    } else {
-        if (h < hEnd) valid = gen_model(recA, recB, rbase, (uint32_t)M, ma, base_seed(ma) + (uint64_t)p, (uint32_t)h, mdl);
-        // (stage 1 parks only the models of its survivors, at the end: the abandoned majority is never read again)
-        if (ma.models && by == 0 && !pruned) {
-            const int hs = stage_hypothesis_again(false, st, (int)bx * kBlock, tid, p, H);
-            if (hs < hEnd && hs < ma.modelH) store_model(ma, (size_t)p * ma.modelH + hs, mdl);
-        }
-        if (KIND == 0 && st.genOnly) { // stage 0, first launch: models and validity only
-            const unsigned long long vm = __builtin_amdgcn_ballot_w64(valid);
-            if (lane == 0) st.validMask[(size_t)p * ((st.hCount + 63) >> 6) + (bx * (kBlock / 64) + wv)] = vm;
-            return false;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) s_mdl[3 * i + j][tid] = mdl.R[i][j];
-        s_mdl[9 + i][tid] = mdl.t[i];
-    }
+    pass_model<KIND>(ps, recA, recB, rbase, ma, st, H, bx, by, p, M, mdl, valid);
+    if (KIND == 0 && st.genOnly) return false; // (stage 0, first launch: models and validity only)
+    lds_put_model(s_mdl, tid, mdl);
     s_cnt[tid] = 0;
 
     const float2 pbnd = pairBound[p];
@@ -532,12 +216,7 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
         const float g = 1.4143f * lam + 8.0f * kEpsU * fc.thrUp;
         auto rebuild = [&]() {
             Rigid md, iv;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) md.R[i][j] = s_mdl[3 * i + j][tid];
-                md.t[i] = s_mdl[9 + i][tid];
-            }
+            lds_get_model(s_mdl, tid, md);
             // md: current point -> previous image (estimatedOldPosition, RANSAC.cpp:346);
             // iv: previous point -> current image (estimatedNewPosition, RANSAC.cpp:348)
             inverse_rigid_general(md, iv);
@@ -586,12 +265,7 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
                               (!EUCLID || (ec.enabled != 0 && cmax <= 1.0e15f));
         if (!wave_all(boundsOk)) {
             Rigid md, iv;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) md.R[i][j] = s_mdl[3 * i + j][tid];
-                md.t[i] = s_mdl[9 + i][tid];
-            }
+            lds_get_model(s_mdl, tid, md);
             inverse_rigid_general(md, iv);
             for (int m = m0; m < m1; ++m) {
                 const int mo = orig(m);
@@ -607,12 +281,7 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
                 const uint32_t ent = s_q[wv][e];
                 const int t = wv * 64 + (int)(ent & 63u), m = orig((int)(ent >> 6));
                 Rigid md, iv;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) md.R[i][j] = s_mdl[3 * i + j][t];
-                    md.t[i] = s_mdl[9 + i][t];
-                }
+                lds_get_model(s_mdl, t, md);
                 inverse_rigid_general(md, iv);
                 const float4 A = pa[m], B = pb[m], C = pc[m];
                 if (inlier_test<MODE>(md, iv, k, A, B, C)) atomicAdd(&s_cnt[t], 1);
@@ -712,7 +381,7 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
         // vector loads of one address by 64 lanes)
         const float2 *__restrict__ pfr = reinterpret_cast<const float2 *>(recE) + (size_t)p * ((size_t)((cap + 1) >> 1) * 5);
         if (PRE && st.frontRec != nullptr && st.prefInfo != nullptr) {
-            const int f = __builtin_amdgcn_readfirstlane(st.prefInfo[4 * p + 2]); // (uniform: keep the loop's branch scalar)
+            const int f = __builtin_amdgcn_readfirstlane(st.prefInfo[ps.prefRow + 2]); // (uniform: keep the loop's branch scalar)
             mFront = f < m1 ? f : m1;
         }
         // Two matches per trip, both records requested before the first is used: a wavefront that is alone on its SIMD (the
@@ -788,12 +457,7 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
             const uint32_t ent = s_q[w][i];
             const int t = w * 64 + (int)(ent & 63u), m = orig((int)(ent >> 6));
             Rigid md, iv;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int b = 0; b < 3; ++b) md.R[a][b] = s_mdl[3 * a + b][t];
-                md.t[a] = s_mdl[9 + a][t];
-            }
+            lds_get_model(s_mdl, t, md);
             inverse_rigid_general(md, iv);
             const float4 A = pa[m], B = pb[m], C = pc[m];
             if (inlier_test<MODE>(md, iv, k, A, B, C)) atomicAdd(&s_cnt[t], 1);
@@ -813,53 +477,13 @@ PS_D bool score_fast_pass(const float4 *__restrict__ recA, const float4 *__restr
             }
         }
     }
-    int tidE = tid; // (a fresh copy for the epilogue's LDS addresses: kept alive across the loops they went to scratch memory)
-    asm volatile("" : "+v"(tidE));
-    if (LIST && cover < kBlock) { // (work-group uniform) the parts of the match range add up
-        if (part > 0 && h < hEnd) atomicAdd(&s_tot[slot], cnt);
-        __syncthreads();
-        if (part == 0) cnt += s_tot[slot];
-    }
-    if (pruned) {
-        h = stage_hypothesis_again(LIST, st, (int)bx * cover, slot, p, H);
-        const bool mine = h < hEnd && part == 0;
-        if (LIST && msplit > 1) { // (last stage, range split over work-groups: nothing survives it, the counts add up)
-            if (mine && valid && cnt) atomicAdd(&cout[h], cnt);
-            return false;
-        }
-        const int cnt0 = (LIST && mine) ? cout[h] : 0; // count so far
-        const int total = valid ? cnt0 + cnt : 0; // model not computed -> iteration skipped (RANSAC.cpp:107)
-        if (mine) cout[h] = total;
-        // still able to become a record?  (count so far + matches left > best count of the earlier hypotheses)
-        const bool alive = mine && valid && total + (M - mStageEnd) > best0;
-        if (!LIST && ma.models && h < ma.modelH && (alive || (mine && mStageEnd >= M))) { // survivors (or: this stage was the whole sweep)
-            Rigid md;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) md.R[i][j] = s_mdl[3 * i + j][tidE];
-                md.t[i] = s_mdl[9 + i][tidE];
-            }
-            store_model(ma, (size_t)p * ma.modelH + h, md);
-        }
-        if (st.stage < kStages && mStageEnd < M) stage_append(alive, h, st.listOut, st.countOut, p, st.listStride);
-        return false;
-    }
-    h = stage_hypothesis_again(false, st, (int)bx * kBlock, tid, p, H);
-    if (h < hEnd) {
-        if (!valid) cnt = 0; // model not computed -> iteration skipped (RANSAC.cpp:107)
-        if (msplit == 1)
-            cout[h] = cnt;
-        else if (cnt)
-            atomicAdd(&cout[h], cnt);
-    }
+    pass_finish<KIND>(ps, s_mdl, s_tot, cout, ma, st, H, msplit, bx, p, M, valid, cnt);
     return false;
 }
 
 // (kind 2 sweeps short lists with few wavefronts: five per SIMD are plenty, and its loop over the list keeps the kernel
 // arguments alive across the passes -- at seven or eight they went to scratch memory and the inlier counter with them)
-// LOOP (kind 1 only): StageArgs::loopGroups work-groups per pair walk the blocks of 256 hypotheses and stop at the first one beyond
-// the trip limit -- a pass returns true when its block, and with it every later one, has nothing to do.
+// (LOOP, kind 1 only: the work-groups walk the blocks of 256 hypotheses, score_kernel_body in ps_score_pass.h)
 template <int MODE, bool BIG, int KIND = 0, bool LOOP = false>
 __global__ __launch_bounds__(kBlock, (KIND == 2 || LOOP) ? 5 : 8) void ps_ransac_score_fast(
     const float4 *__restrict__ recA, const float4 *__restrict__ recB, const float4 *__restrict__ recC,
@@ -870,34 +494,10 @@ __global__ __launch_bounds__(kBlock, (KIND == 2 || LOOP) ? 5 : 8) void ps_ransac
 {
     static_assert(MODE == PS_REPROJECTION_ERROR || MODE == PS_EUCLIDEAN_AND_REPROJECTION_ERROR,
                   "the metrics with a reprojection test");
-    // hypotheses of this launch: [hBase, hBase + hCount) (plain launch: [0, H); stages 0 / 1), or a survivor list swept by
-    // hCount / 256 work-groups per pair (stages 2+)
-    static_assert(!LOOP || KIND == 1, "the looping form is stage 1's");
-    const unsigned blocks = (unsigned)((st.hCount + kBlock - 1) / kBlock);
-    const unsigned hb = LOOP ? (unsigned)st.loopGroups : blocks; // work-groups per pair and part of the match range
-    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned bx = L % hb, by = (L / hb) % (unsigned)msplit;
-    const int p = (int)(L / (hb * (unsigned)msplit));
-    const int M = mvalid[p];
-    if (M < minRun) return; // too few matches: kernel 4 returns identity (RANSAC.cpp:77-80)
-    if (LOOP) {
-        for (unsigned b = bx; b < blocks; b += hb) {
-            if (b != bx) __syncthreads(); // (the pass before is done with the work-group's LDS)
-            if (score_fast_pass<MODE, BIG, KIND>(recA, recB, recC, recE, recF, pairBound, ma, k, fc, ec, sa, st, H, cap, msplit,
-                                                 counts, dbg, b, by, p, M))
-                break; // (uniform over the work-group: the exits that return true are taken by all of its waves)
-        }
-    } else if (KIND == 2) {
-        const int n = st.countIn[p];
-        const int cover = list_cover(n);
-        for (unsigned b = bx; (int)b * cover < n; b += hb) {
-            if (b != bx) __syncthreads(); // (the pass before is done with the work-group's LDS)
-            score_fast_pass<MODE, BIG, KIND>(recA, recB, recC, recE, recF, pairBound, ma, k, fc, ec, sa, st, H, cap, msplit, counts,
-                                             dbg, b, by, p, M);
-        }
-    } else
-        score_fast_pass<MODE, BIG, KIND>(recA, recB, recC, recE, recF, pairBound, ma, k, fc, ec, sa, st, H, cap, msplit, counts, dbg,
-                                         bx, by, p, M);
+    score_kernel_body<KIND, LOOP>(mvalid, st, minRun, msplit, [&](unsigned bx, unsigned by, int p, int M) __attribute__((always_inline)) {
+        return score_fast_pass<MODE, BIG, KIND>(recA, recB, recC, recE, recF, pairBound, ma, k, fc, ec, sa, st, H, cap, msplit, counts, dbg,
+                                                bx, by, p, M);
+    });
 }
 
 // ------------------------------------------------------------------------------------------

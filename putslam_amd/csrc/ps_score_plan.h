@@ -1,6 +1,7 @@
 // ps_score_plan.h -- the plan of the RANSAC scoring step (kernels 3, ps_score_fast.h / ps_score_euclid.h), each decision once: staged
 // or complete scoring (wants_staged), what a call's launches and arena blocks look like (decide_score), the "nothing to gain" policy's
-// state machine (BailTracker) and the kernel-3 launches in order (stage_schedule).
+// state machine (BailTracker), the kernel-3 launches in order (stage_schedule) and the match range of every work-group and wavefront
+// of such a launch (pair_split, stage_range, group_part, wave_part: host and device, ps_score_pass.h calls them).
 // Pure -- no HIP header, no runtime call, no PsContext, no pointer into the arena, no heap: ps_capi.hip's prepare_score and
 // score_schedule are the shells that allocate and launch what this header decides, and tests/cpp/test_score_plan.cpp includes it
 // into a plain C++ program (tests/test_score_plan_host.py; tests/golden/score_plan_parent.json holds what the code decided before
@@ -12,7 +13,7 @@
 
 #include "putslam_hip.h"
 
-// (mirrors of psdev::kBlock, ps_block.h, and psdev::kPrefixFixed / kPrefixAdaptive / kStages, ps_score_fast.h: the device
+// (mirrors of psdev::kBlock, ps_block.h, and psdev::kPrefixFixed / kPrefixAdaptive / kStages, ps_score_pass.h: the device
 // translation unit checks them with static_asserts)
 constexpr int kPlanBlock = 256, kPlanPrefixFixed = kPlanBlock, kPlanPrefixAdaptive = 64, kPlanStages = 3;
 
@@ -23,6 +24,97 @@ constexpr int kWidePairs = 16; // batches of at most this many pairs run kernel 
 // second cut at 1 / kReorderC2div of the range); stage 3 runs one looping work-group per eight possible ones (list_groups).
 constexpr int kListRsplit3 = 4, kReorderGran = 64, kReorderC2div = 16;
 constexpr int kGenPlainFrom = 2; // complete scoring generates its models by a launch of their own from this many pairs on (ScoreDecision::genPlain)
+
+// ------------------------------------------------------------------------------------------
+// The match ranges of kernel 3's work-groups and wavefronts (ps_score_pass.h runs them on the device, tests/cpp/test_score_plan.cpp
+// on a CPU): integer arithmetic on (M, by, msplit, stage, best0, cover, part) and nothing else.
+// ------------------------------------------------------------------------------------------
+#if defined(__HIPCC__)
+#define PS_PLAN_HD __host__ __device__ __attribute__((always_inline)) inline
+#else
+#define PS_PLAN_HD inline
+#endif
+
+// Kinds 0 / 1: part `by` of msplit of a pair's M matches.  The range is split on match PAIRS (the loops take two matches per trip):
+// only the pair's last part can be odd.
+PS_PLAN_HD void pair_split(int M, unsigned by, int msplit, int &m0, int &m1)
+{
+    const int npair = (M + 1) >> 1;
+    m0 = 2 * (int)(((long long)npair * by) / msplit);
+    m1 = 2 * (int)(((long long)npair * (by + 1)) / msplit);
+    m1 = m1 < M ? m1 : M;
+}
+
+// Where the pruned stages' match ranges are cut (StageArgs, ps_score_pass.h, carries one to every launch).
+struct StageCuts {
+    bool reordered; // the stages sweep the record ps_stage_reorder wrote -- the matches the prefix's best hypothesis rejects first
+    int single;     // 1 = stage 1 sweeps ALL matches and is the only stage after the prefix
+    int gran;       // reordered: stage 1 ends on a multiple of this (a power of two) ...
+    int margin;     // ... this many matches after the point where a hypothesis that rejects all the leading matches is out
+    int c2div;      // reordered: stage 2 takes 1 / c2div of what stage 1 leaves
+};
+
+// Match range [lo, hi) of pruned stage `stage` (1 .. kPlanStages) for a pair with M matches whose prefix reached best0.
+// Reordered: every hypothesis that is not better than the prefix's best one rejects (almost all of) the leading matches too and is
+// out a few matches later.
+PS_PLAN_HD void stage_range(const StageCuts &sc, int stage, int M, int best0, int &lo, int &hi)
+{
+    int c1 = M, c2 = M;
+    if (best0 > 0 && !sc.single) {
+        const int miss = M - best0; // a hypothesis is out once it has missed this many matches
+        if (sc.reordered) {
+            const int g1 = sc.gran - 1;
+            c1 = (miss + sc.margin + g1) & ~g1;
+            if (c1 >= M - M / 8) c1 = M;
+            if (c1 < M) {
+                // (stage 2 ends where it would with stage 1 cut at a multiple of 64, whatever stage 1's granularity)
+                const int c64 = (c1 + 63) & ~63;
+                const int step = ((M - c64) / sc.c2div + 63) & ~63;
+                c2 = c64 + (step > 0 ? step : 64); // (never an empty stage 2: it hands the survivors on)
+                if (c2 >= M - M / 16) c2 = M;
+            }
+        } else {
+            c1 = (miss + miss / 7 + 32 + 63) & ~63;
+            if (c1 >= M - M / 8) c1 = M; // nothing worth a second launch
+            if (c1 < M) {
+                c2 = (c1 + (M - c1) / 2 + 63) & ~63;
+                if (c2 >= M - M / 16) c2 = M;
+            }
+        }
+    }
+    static_assert(kPlanStages == 3, "three pruned stages");
+    lo = stage == 1 ? 0 : (stage == 2 ? c1 : c2); // (selects, not an indexed array: that would live in scratch memory)
+    hi = stage == 1 ? c1 : (stage == 2 ? c2 : M);
+}
+
+// Stages 2+: hypotheses one pass of a work-group takes from the survivor list.  After the reordered stage 1 the lists are
+// short and the ranges left are long: a pair with at most 64 (128) survivors is swept by ONE work-group whose four
+// wavefronts each take a quarter (two halves) of the match range for the same hypotheses and add their counts up in LDS --
+// a single wavefront alone on its SIMD waits out every record load (stage 3 of the bench step: 21 survivors per pair, 157 us
+// that way, profiles/r03k).  Longer lists: 256 hypotheses per pass as before.  The launches carry a few work-groups per
+// pair (StageArgs::hCount / 256) that loop over the list: thousands of work-groups that find nothing to do still cost
+// their launch (30 ... 50 us per empty stage of 7485 work-groups).
+PS_PLAN_HD int list_cover(int n) { return n <= 64 ? 64 : (n <= 128 ? 128 : kPlanBlock); }
+
+// Part `by` of msplit of a stage's range [m0, m1), in whole blocks of 64 matches from m0 (the LAST stage may split its range over
+// work-groups: their counts meet in counts[]).  A part beyond the range's end comes out with m0 >= m1.
+PS_PLAN_HD void group_part(unsigned by, int msplit, int &m0, int &m1)
+{
+    const int blen = (((m1 - m0 + msplit - 1) / msplit) + 63) & ~63;
+    m0 += (int)by * blen;
+    m1 = m1 < m0 + blen ? m1 : m0 + blen;
+}
+
+// ... and within it the part of one of the kPlanBlock / cover groups of wavefronts that sweep the same `cover` hypotheses (whole
+// blocks of 64 matches again; a part may be empty)
+PS_PLAN_HD void wave_part(int part, int cover, int &m0, int &m1)
+{
+    const int parts = kPlanBlock / cover;
+    const int plen = ((m1 - m0 + parts * 64 - 1) / (parts * 64)) * 64;
+    m0 += part * plen;
+    m1 = m1 < m0 + plen ? m1 : m0 + plen;
+    m1 = m1 < m0 ? m0 : m1; // (an empty part: nothing to sweep, no odd last match either)
+}
 
 // Which kernel 3 scores a call: the value-exact ps_ransac_score (option "score" = 0, and the Mahalanobis error), else the
 // decision-exact Euclidean ps_ransac_score_euclid (errorVersion 0 / 4) or reprojection ps_ransac_score_fast (1 / 2).  Kernel 2
@@ -105,7 +197,7 @@ inline bool wants_staged(const ScoreShape &s, const ScoreOptions &o)
         // (two chains hide half of one another's gaps: half way between the two crossovers, on the logarithmic scale)
         stagedFrom = o.sideBySide >= 3 ? sbs : std::sqrt(sbs * stagedFrom);
     }
-    // (pruned scoring: the decision-exact kernels have it; the later stages read the models back from HBM, ps_score_fast.h)
+    // (pruned scoring: the decision-exact kernels have it; the later stages read the models back from HBM, ps_score_pass.h)
     return !s.complete && o.prune != 0 && s.score != Scoring::Value && s.H > kPlanPrefixFixed && (o.prune == 2 || units >= stagedFrom);
 }
 
@@ -146,7 +238,7 @@ inline ScoreDecision decide_score(const ScoreShape &s, const ScoreOptions &o, bo
         return d;
     }
     d.staged = staged;
-    // (the later stages read the models back from HBM, 48 B per hypothesis: ps_score_fast.h)
+    // (the later stages read the models back from HBM, 48 B per hypothesis: ps_score_pass.h)
     const size_t mbytes = (size_t)P * H * 12 * sizeof(float);
     d.prefix = s.estimator == PS_EST_FIXED ? kPlanPrefixFixed : kPlanPrefixAdaptive;
     if (o.forcePrefix > 0 && s.estimator == PS_EST_FIXED) d.prefix = o.forcePrefix; // (tuning knob)
@@ -294,7 +386,7 @@ struct BailTracker {
 };
 
 // One launch of kernel 3 of KIND `kind`: 0 (stage 0 / the complete scoring), 1 (stage 1; loop: looping work-groups) or 2 (stages 2+),
-// over groups x msplit x P work-groups; the rest is what its StageArgs (ps_score_fast.h) holds, an arena block named by its use.
+// over groups x msplit x P work-groups; the rest is what its StageArgs (ps_score_pass.h) holds, an arena block named by its use.
 struct StageLaunch {
     int kind = 0;
     bool loop = false;
@@ -306,7 +398,7 @@ struct StageLaunch {
     int single = 0, loopGroups = 0;
 };
 
-// Kernel 3 of the decision-exact scoring (ps_score_fast.h, ps_score_euclid.h).  Staged scoring: stage 0 = the prefix completely,
+// Kernel 3 of the decision-exact scoring (ps_score_fast.h, ps_score_euclid.h; the staged protocol: ps_score_pass.h).  Staged scoring: stage 0 = the prefix completely,
 // stages 1 .. lastStage = the rest with hypotheses abandoned between the launches; otherwise every hypothesis of [0, H) completely.
 struct StageSchedule {
     int n = 0;

@@ -85,7 +85,7 @@ STAT_FIELDS = ("numMatchesIn", "numMatchesValid", "bestHypothesis", "bestInlierC
 
 
 def run_batch(iters, seed, verbose=True, modes=(0, 1, 2, 4), oracle_pairs=3):
-    """Random BATCHES large enough for the staged scoring (ps_score_fast.h): the staged run with the reordered match record
+    """Random BATCHES large enough for the staged scoring (ps_score_pass.h): the staged run with the reordered match record
     (options prune = 1, reorder = 1) against the staged run in the original order (reorder = 0) and the complete one
     (prune = 0: the launch form the single-pair soak above checks against the oracle) on every pair and every output
     field, and against the oracle on a few pairs of each batch.  Returns the number of batches with a difference."""

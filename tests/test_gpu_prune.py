@@ -1,4 +1,4 @@
-"""Pruned scoring (ps_score_euclid.h / ps_score_fast.h, launch B): hypotheses that provably cannot become records of the
+"""Pruned scoring (ps_score_pass.h: the protocol; ps_score_euclid.h / ps_score_fast.h: the sweeps; launch B): hypotheses that provably cannot become records of the
 sequential selection (RANSAC.cpp:438-455: strict '>' first-best; adaptive trip limit :450-453, USAC.h:944-971) are
 abandoned early and hypotheses beyond the trip limit are never scored.  Every OUTPUT of the path -- selected hypothesis,
 its count, iterations run, inlier mask, pose bytes, ratios -- must equal both the unpruned run's and the oracle's, for all
@@ -177,6 +177,10 @@ TWIN_CASES = [  # (errorVersion, estimator, H, frames, kpts, inlier_frac, noise)
     (REPROJECTION_ERROR, EST_USAC, 3000, 80, 500, 0.30, 0.01),
     (REPROJECTION_ERROR, EST_FIXED, 1161, 200, 270, 0.94, 0.0014),   # cuts close to each other and to M
     (EUCLIDEAN_ERROR, EST_FIXED, 2000, 40, 500, 0.12, 0.02),         # hopeless data: the one-stage exit of the reorder launch
+    # an adaptive schedule with more than 64 blocks of 256 hypotheses after the prefix, under the combined metric: stage 1 is walked
+    # by looping work-groups (ps_ransac_score_fast<2, true, 1, true>; 69 pairs x 60 work-groups walk 67 blocks: some take two and
+    # stop at the second, beyond the trip limit)
+    (EUCLIDEAN_AND_REPROJECTION_ERROR, EST_USAC, 17000, 70, 300, 0.12, 0.02),
 ]
 _FULL = {}
 

@@ -1,4 +1,4 @@
-"""Race / determinism net for the staged scoring (ps_score_fast.h): seven dependent launches per step, survivor lists appended
+"""Race / determinism net for the staged scoring (ps_score_pass.h): seven dependent launches per step, survivor lists appended
 by per-wavefront atomics, LDS meeting slots, (B0, L0) published between launches.  A data race there would show as a result
 that differs from run to run once in thousands of steps -- so the SAME staged batch is run many times on three concurrent
 chains (three contexts, three HIP streams, the bench's submission) while a fourth context keeps the chip busy with a different

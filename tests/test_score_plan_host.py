@@ -2,6 +2,7 @@
 call, the "nothing to gain" policy's state machine) compiled into a plain C++ program -- no HIP header, no GPU -- and run
 (tests/cpp/test_score_plan.cpp): the state machine against its documented rule; every decision against what the code decided before it
 moved into the header (tests/golden/score_plan_parent.json, recorded from the parent commit: tests/golden/make_score_plan_parent.py);
+the match ranges of the kernels' work-groups and wavefronts against their tiling properties and their earlier expressions;
 the cost model against the rows the GPU tests run (tests/score_plan_rows.py)."""
 import json
 import os
@@ -41,6 +42,14 @@ def _run(exe, mode, text):
 
 def test_bail_tracker_holds_the_documented_rule(program):
     assert _run(program, None, "").strip() == "score plan ok"
+
+
+def test_match_ranges_tile_and_equal_the_parent_commit(program):
+    """pair_split, stage_range, group_part and wave_part (the range arithmetic of ps_score_pass.h's pass_begin): the stages tile [0, M),
+    the work-group and wavefront parts tile every stage range in blocks of 64, the pair split tiles [0, M) in even parts -- over M = 0 ..
+    600 and PS_MAX_KPTS, every best0, msplit = 1 .. 32, both orders, both granularities, every list_cover -- and each equals the
+    expressions the kernels held before the arithmetic moved into the header (restated in the program)."""
+    assert _run(program, "ranges", "").strip() == "match ranges ok"
 
 
 def test_the_parent_table_covers_every_decision(parent):
