@@ -1,6 +1,7 @@
 // ps_stream_async.h -- the PIPELINED streaming form of Matcher::match (include/putslam_hip.h: ps_vo_stream_configure_async,
 // _push_async, _push_many, _flush, _pop_many, _pop).  Included by ps_capi.hip behind ps_stream_push.h (it uses that header's
-// PsVoStream and ps_capi.hip's plan and stages).
+// PsVoStream and ps_capi.hip's plan and stages).  Layout of this file: the state (shared, ring form, mini form), a chunk's launch
+// (begin, the form's launches, commit), the one push path, configure, the C entry points.
 //
 // Call shape served: reference src/Matcher/matcher.cpp:452-516 (one frame per call, the previous frame kept as state) in the
 // loop of src/PUTSLAM/PUTSLAM.cpp:677-740.  The synchronous ps_vo_stream_push pays a copy in, four kernels, a copy out and a
@@ -22,11 +23,12 @@
 //     chunk if it has one.  With one place per lane a lane idled from the end of its chunk's last kernel through the download,
 //     the host's pop, the next chunk's upload and the copy-stream -> lane dependency (300 - 500 us of a chunk's ~ 800,
 //     profiles/r05h/timeline_ahead0.txt); now its next chunk's launches are already in its stream.
-//   * ring: (lanes + ahead + 2) x chunkFrames frame slots.  A chunk's frames are contiguous in it (a chunk that would not fit
-//     before the end starts at slot 0 again); the frame before the chunk's first one is still resident, so pair (previous
-//     chunk's last frame, this chunk's first frame) needs no second upload.  The chunks alive (running or queued on a lane) read at most the
-//     (lanes + ahead - 1) x chunkFrames + 1 slots written last, a jump to slot 0 skips fewer than chunkFrames, the new chunk
-//     writes at most chunkFrames: no slot that is still read is overwritten, with no device-side wait.
+//   * ring: (lanes + ahead + 2) x chunkFrames + lanes + ahead frame slots.  A chunk's frames are contiguous in it (a chunk that
+//     would not fit before the end starts at slot 0 again); the frame before the chunk's first one is still resident, so pair
+//     (previous chunk's last frame, this chunk's first frame) needs no second upload.  No slot that is still read is overwritten,
+//     with no device-side wait: the count is ps_stream_ledger.h's (THE REUSE INVARIANT), which also keeps every integer of the
+//     pipeline -- places, the staging areas' rotation, the ring cursor, pair numbers, epochs -- and changes them in one place,
+//     when a chunk has been queued completely.
 //   * lane = a private PsContext (stream + scratch arena).  Consecutive chunks go to consecutive lanes, so one chunk's matrix-core
 //     Hamming sweep runs beside another's vector scoring sweep, as bench.py's sub-batch chains do.  The pinned result block of a
 //     place changes hands at the pop: the caller reads it until the next pop, the place continues with the spare one -- so a
@@ -35,163 +37,150 @@
 //     in stream order, so the halo frame needs no event of its own.
 //   * results are those of ONE ps_vo_pairs_device call over the whole sequence: pair k draws from cfg->seed + k.
 #pragma once
+#include "ps_stream_ledger.h" // every integer of the pipeline and the rule that makes reuse safe; the result block's layout
 
 // One chunk's place in the pipeline: meta block, device and pinned result blocks, events.  There are lanes + ahead of them; a
 // chunk takes the next one and runs on the next LANE (a private PsContext: stream + scratch arena) in turn, so each lane's
-// stream can hold a chunk that runs and further ones queued behind it.
+// stream can hold a chunk that runs and further ones queued behind it.  (Whether a place is taken, and by which pairs: the ledger.)
 struct AsyncLane {
     PsContext *ctx = nullptr; // the lane context this place's chunk was launched on (not owned)
-    Buf meta;                 // device: int32 [2 * B] pair list, then [ringFrames] row counts
+    Buf meta;                 // device: int32 [2 * B] pair list, then [ringFrames] row counts (mini: a psdev::MiniMeta)
     int32_t *hmeta = nullptr; // pinned mirror of it
-    Buf res;                  // device: [matches B x cap x 16][mask B x cap][pose B x 64][stats B x 40][numMatches B x 4]
+    Buf res;                  // device: the chunk's result block (psledger::ResLayout)
     uint8_t *hres = nullptr;  // pinned mirror of it
     int32_t *hmetaDev = nullptr; // device views of the pinned blocks (hipHostGetDevicePointer)
     uint8_t *hresDev = nullptr;
-    hipEvent_t evRun = nullptr, evDone = nullptr; // behind the chunk's kernels / its download
-    // small chunks (PsVoAsync::mini): the place's private frames [1 + B] in the packed layout (slot 0 = the frame before the
-    // chunk's first one), its chunk as a captured graph, and the arena generation of its lane the graph's pointers belong to
+    hipEvent_t evDone = nullptr; // behind the chunk's download
+    // ---- ring form
+    hipEvent_t evRun = nullptr;  // behind the chunk's kernels
+    // ---- mini form: the place's private frames [1 + B] in the packed layout (slot 0 = the frame before the chunk's first
+    // one), its chunk as a captured graph, and the arena generation of its lane the graph's pointers belong to
     Buf frames;
     hipGraphExec_t gexec = nullptr;
     unsigned long long gexecGen = 0;
     Plan plan;                  // the plan of the place's full chunk (parameters are fixed per configure), valid while ...
     unsigned long long planGen = 0; // ... its lane's arena is the one it was made with (0 = none)
-    int state = 0;            // 0 free, 1 chunk in flight
-    long long firstPair = 0;
-    int pairs = 0;
-    int epoch = 0;
 };
 
-// A chunk whose frames are in the ring (or on their way: `up` is recorded behind its uploads), about to be launched.
-struct AsyncChunk {
-    int pos0 = 0, n = 0;       // ring slots [pos0, pos0 + n)
-    int first = 0;             // 1: the chunk's first frame has no predecessor (the stream's first frame, or after a reset)
-    int prevPos = -1;          // slot of the frame before the chunk's first one
-    long long firstPair = 0;   // index of its first pair in the stream (-> seed)
-    int epoch = 0;
-    hipEvent_t up = nullptr;   // (owned by PsVoAsync::upEv)
-};
-
-struct PsVoAsync {
-    int B = 0, lanes = 0, ringFrames = 0;
-    int ahead = 0;                        // places beyond one per lane: chunks queued on the lanes' streams behind the running ones
-    std::vector<PsContext *> laneCtx;     // the lanes (owned)
-    long long launchSeq = 0;              // chunks launched so far (chunk k runs on lane k % lanes)
-    long long diagLaunches = 0;           // launches attempted since configure (fault injection of -DPS_STREAM_DIAG builds counts these)
-    std::vector<hipEvent_t> upEv;         // lanes + ahead + 1 events, one per chunk alive, by chunk number
-    std::vector<uint8_t *> stagePool;     // lanes + ahead + 1 pinned staging areas for frames that arrive one at a time / in
-                                          // pageable memory: [B x cap x 32 descriptors][B x cap x 12 points], by chunk number;
-                                          // allocated when first needed
-    long long chunkSeq = 0;               // chunks uploaded so far
-    PsRansacParams prm{};
-    PsRansacConfig cfg{};
-    float K[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    bool haveK = false;
-    Buf ringDesc, ringPts;
-    // Small chunks (chunkFrames <= 4, the reference's own call shape at 1: src/Matcher/matcher.cpp:452-516): a chunk is launch-bound
-    // -- two uploads, a meta kernel, six or seven launches, an event pair and a download, 85 us of host and queue time for 55 us of
-    // kernels: round 5's pipeline was no faster than the synchronous push there.  In this form every place owns a private frame set
-    // and its whole chunk is ONE captured hipGraph (frames in by a copy kernel from the pinned staging area, kernels 1 - 4, results
-    // out by a kernel into the place's pinned block); what changes between chunks -- row counts, the seed, where the frames lie --
-    // travels as data (psdev::MiniMeta).  No ring, no copy streams, no cross-lane dependency: the halo frame is read again from
-    // the previous chunk's staging slot.
-    bool mini = false;
-    // Replaying a place's chunk from its graph is OFF by default: on this runtime hipGraphLaunch of the seven-node graph costs the
-    // host more than the seven launches and the lanes' graphs run less side by side -- 20.9 k frames/s at 322 us of lag against
-    // 25.1 k at 209 us with ordinary launches (demos/cpp/demo_latency (d), profiles/r06h/mini_chunks.txt).  PUTSLAM_HIP_STREAM_GRAPH=1
-    // turns it on (tests run both).
-    bool miniGraphs = false;
-    std::vector<uint8_t *> stagePoolDev;  // device views of the staging areas (mini chunks read them from kernels)
-    const uint8_t *haloDev = nullptr;     // device view of the stream's latest frame in its staging slot (or in the caller's pinned memory)
-    const uint8_t *inPlaceDev = nullptr;  // set for ONE mini_submit_body call: the chunk's frames lie in the caller's pinned memory
-    uint8_t *loneHost = nullptr, *loneDev = nullptr; // a lone first frame's own pinned block (it takes no place, so no staging area)
-    hipEvent_t loneReadEv = nullptr;      // behind the chunk that read that block as its previous frame
-    bool loneReadPending = false, haloIsLone = false;
-    int haloNk = 0;
-    std::vector<unsigned long long> laneWarmGen; // per lane: arena generation an un-captured full chunk has run with (0 = none)
-    std::vector<uint8_t> viewBuf;         // pop_many's copy of a mini chunk's results (its place is free at once)
-    long long graphLaunches = 0;          // chunks replayed from a graph (option "stream_graph_launches", read only)
-    bool packed = false;                  // PS_FRAMES_PACKED: a frame's descriptors and points lie together, in the ring (ringDesc holds
-    size_t packStride = 0;                // ringFrames x packStride bytes, ringPts is unused) as on the host: ONE upload per chunk
-    std::vector<int32_t> nkRing; // row counts of the ring's slots (host-authoritative; every chunk uploads a snapshot)
+// The ring form's own: frames travel host -> ring over the copy stream, results come back over the copy-out stream.
+struct AsyncRing {
+    std::vector<hipEvent_t> upEv; // one upload event per staging area (Ledger::next_area)
+    Buf desc, pts;                // the ring (packed frames: `desc` holds ringFrames x packStride bytes, `pts` is unused)
+    std::vector<int32_t> nk;      // row counts of the ring's slots (host-authoritative; every chunk uploads a snapshot)
     hipStream_t copyStream = nullptr;    // uploads
     hipStream_t copyOutStream = nullptr; // downloads
-    std::vector<AsyncLane> lane;         // the lanes + ahead places, taken in ring order
-    size_t offMask = 0, offPose = 0, offStats = 0, offNum = 0, resBytes = 0;
-    int head = 0, tail = 0, inFlight = 0; // oldest chunk in flight, next lane to submit to
+    bool downloadsOnLane = false; // downloads queued on the lane's own stream instead of the copy-out stream: when the
+                                  // process has few hardware queues (GPU_MAX_HW_QUEUES < lanes + 6), or forced either
+                                  // way by PUTSLAM_HIP_STREAM_DOWNLOADS_ON_LANE=0|1
     // The block a pop hands to the caller changes hands instead of keeping its lane busy: the lane takes the spare pinned block
     // and is free at once (round 5's first form held the lane until the NEXT pop: of four lanes three computed).  Pops are in
     // order and a view lives until the next pop, so one block is held at any time.
     uint8_t *spareHres = nullptr, *spareHresDev = nullptr; // free pinned result block (+ its device view)
     uint8_t *heldHres = nullptr, *heldHresDev = nullptr;   // the block the caller's view points into (null: no view)
-    int ringPos = 0;                      // slot the next frame goes to
-    int prevPos = -1;                     // slot of the stream's latest frame (-1: the next frame has no predecessor)
-    long long pairCounter = 0;
-    int epoch = 0;
-    int staged = 0;                       // frames collected in the next chunk's staging area by push_async
-    std::vector<int32_t> stagedNk;
-    int resultMode = 0;                   // PsStreamResults
-    bool downloadsOnLane = false;         // downloads queued on the lane's own stream instead of the copy-out stream: when the
-                                          // process has few hardware queues (GPU_MAX_HW_QUEUES < lanes + 6), or forced either
-                                          // way by PUTSLAM_HIP_STREAM_DOWNLOADS_ON_LANE=0|1
-    int cursor = 0;                       // ps_vo_stream_pop: next pair of the held view
-    bool haveView = false;                // pop_many has handed out a block that has not been released yet
+};
+
+// Small chunks (chunkFrames <= 4, the reference's own call shape at 1: src/Matcher/matcher.cpp:452-516): a chunk is launch-bound
+// -- two uploads, a meta kernel, six or seven launches, an event pair and a download, 85 us of host and queue time for 55 us of
+// kernels: round 5's pipeline was no faster than the synchronous push there.  In this form every place owns a private frame set
+// and its whole chunk is ONE captured hipGraph (frames in by a copy kernel from the pinned staging area, kernels 1 - 4, results
+// out by a kernel into the place's pinned block); what changes between chunks -- row counts, the seed, where the frames lie --
+// travels as data (psdev::MiniMeta).  No ring, no copy streams, no cross-lane dependency: the halo frame is read again from
+// the previous chunk's staging slot.
+struct AsyncMini {
+    // Replaying a place's chunk from its graph is OFF by default: on this runtime hipGraphLaunch of the seven-node graph costs the
+    // host more than the seven launches and the lanes' graphs run less side by side -- 20.9 k frames/s at 322 us of lag against
+    // 25.1 k at 209 us with ordinary launches (demos/cpp/demo_latency (d), profiles/r06h/mini_chunks.txt).  PUTSLAM_HIP_STREAM_GRAPH=1
+    // turns it on (tests run both).
+    bool graphs = false;
+    long long graphLaunches = 0;         // chunks replayed from a graph (option "stream_graph_launches", read only)
+    std::vector<uint8_t *> stagePoolDev; // device views of the staging areas (the copy-in kernel reads them)
+    // the stream's latest frame, which the next chunk reads as its previous one: in its chunk's staging slot, in the caller's
+    // pinned memory, or -- a lone first frame, which takes no place and therefore no area -- in a pinned block of its own, written
+    // again only behind the chunk that read it
+    const uint8_t *haloDev = nullptr;
+    int haloNk = 0;
+    bool haloIsLone = false;
+    uint8_t *loneHost = nullptr, *loneDev = nullptr;
+    hipEvent_t loneReadEv = nullptr; // behind the chunk that read that block as its previous frame
+    bool loneReadPending = false;
+    std::vector<unsigned long long> laneWarmGen; // per lane: arena generation an un-captured full chunk has run with (0 = none)
+    std::vector<uint8_t> viewBuf;                // pop_many's copy of a chunk's results (its place is free at once)
+};
+
+struct PsVoAsync {
+    psledger::Ledger led;
+    // ---- both forms
+    psledger::ResLayout res;
+    PsRansacParams prm{};
+    PsRansacConfig cfg{};
+    float K[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool haveK = false;
+    int resultMode = 0;               // PsStreamResults
+    bool packed = false;              // PS_FRAMES_PACKED: a frame's descriptors and points lie together, in the ring as on the
+    size_t packStride = 0;            // host: ONE upload per chunk (mini chunks: always, one block per frame for the copy-in kernel)
+    std::vector<PsContext *> laneCtx; // the lanes (owned)
+    std::vector<AsyncLane> lane;      // the lanes + ahead places, taken in ring order
+    std::vector<uint8_t *> stagePool; // one pinned staging area per Ledger::next_area for frames that arrive one at a time / in
+                                      // pageable memory: [B x cap x 32 descriptors][B x cap x 12 points], or B packed frames;
+                                      // allocated when first needed
+    std::vector<int32_t> stagedNk;    // row counts of the frames push_async has staged
+    int cursor = 0;                   // ps_vo_stream_pop: next pair of the held view
+    bool haveView = false;            // pop_many has handed out a block that has not been released yet
     PsHostPairResults view{};
-    double dbgT[3] = {0, 0, 0};        // PUTSLAM_HIP_STREAM_DEBUG=1: host seconds inside the uploads' / the batched call's /
-    long long dbgN = 0;                   // the downloads' submission, printed when the pipeline is released
+    long long diagLaunches = 0;       // launches attempted since configure (fault injection of -DPS_STREAM_DIAG builds counts these)
+    double dbgT[3] = {0, 0, 0};       // PUTSLAM_HIP_STREAM_DEBUG=1: host seconds inside the uploads' / the batched call's /
+    long long dbgN = 0;               // the downloads' submission, printed when the pipeline is released
+    AsyncRing ring;
+    AsyncMini mini;
 };
 
 namespace {
 
 using psdev::CopySegs;
+using psdev::MiniMeta;
 using psdev::ps_copy_segments;
+using psdev::ps_mini_copy_in;
 using psdev::ps_pack_results_to_host;
+using psledger::Chunk;
+using psledger::ResLayout;
 
 int async_fail(PsVoStream *s, int code, const char *what, hipError_t e = hipSuccess) { return fail(s->ctx, code, what, e); }
 
-#define PSA_HIP(call)                                                      \
-    do {                                                                   \
-        hipError_t e_ = (call);                                            \
-        if (e_ != hipSuccess) return async_fail(s, PS_ERR_HIP, #call, e_); \
-    } while (0)
-
-void async_drain(PsVoAsync *a)
-{
-    if (a->copyStream) (void)hipStreamSynchronize(a->copyStream);
-    for (PsContext *c : a->laneCtx)
-        if (c) (void)hipStreamSynchronize(c->stream);
-    if (a->copyOutStream) (void)hipStreamSynchronize(a->copyOutStream);
-}
+double async_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 void async_free(PsVoAsync *a)
 {
-    async_drain(a);
+    if (a->ring.copyStream) (void)hipStreamSynchronize(a->ring.copyStream); // drain: uploads, lanes, downloads
+    for (PsContext *c : a->laneCtx)
+        if (c) (void)hipStreamSynchronize(c->stream);
+    if (a->ring.copyOutStream) (void)hipStreamSynchronize(a->ring.copyOutStream);
     if (a->dbgN > 0 && std::getenv("PUTSLAM_HIP_STREAM_DEBUG"))
         fprintf(stderr, "[ps stream] %lld chunks of <= %d frames on %d lanes (+ %d ahead): host us per chunk: upload %.1f, batched call %.1f, download %.1f\n",
-                a->dbgN, a->B, a->lanes, a->ahead, 1e6 * a->dbgT[0] / a->dbgN, 1e6 * a->dbgT[1] / a->dbgN, 1e6 * a->dbgT[2] / a->dbgN);
+                a->dbgN, a->led.B, a->led.lanes, a->led.ahead, 1e6 * a->dbgT[0] / a->dbgN, 1e6 * a->dbgT[1] / a->dbgN, 1e6 * a->dbgT[2] / a->dbgN);
     for (AsyncLane &l : a->lane) {
         release(l.meta);
         release(l.res);
         if (l.hmeta) (void)hipHostFree(l.hmeta);
         if (l.hres) (void)hipHostFree(l.hres);
+        if (l.evDone) (void)hipEventDestroy(l.evDone);
+        if (l.evRun) (void)hipEventDestroy(l.evRun);
         release(l.frames);
         if (l.gexec) (void)hipGraphExecDestroy(l.gexec);
-        if (l.evRun) (void)hipEventDestroy(l.evRun);
-        if (l.evDone) (void)hipEventDestroy(l.evDone);
     }
     for (PsContext *c : a->laneCtx)
         if (c) ps_context_destroy(c);
-    if (a->loneHost) (void)hipHostFree(a->loneHost);
-    if (a->loneReadEv) (void)hipEventDestroy(a->loneReadEv);
-    if (a->spareHres) (void)hipHostFree(a->spareHres);
-    if (a->heldHres) (void)hipHostFree(a->heldHres);
-    for (hipEvent_t e : a->upEv)
-        if (e) (void)hipEventDestroy(e);
     for (uint8_t *h : a->stagePool)
         if (h) (void)hipHostFree(h);
-    release(a->ringDesc);
-    release(a->ringPts);
-    if (a->copyStream) (void)hipStreamDestroy(a->copyStream);
-    if (a->copyOutStream) (void)hipStreamDestroy(a->copyOutStream);
+    for (hipEvent_t e : a->ring.upEv)
+        if (e) (void)hipEventDestroy(e);
+    release(a->ring.desc);
+    release(a->ring.pts);
+    if (a->ring.spareHres) (void)hipHostFree(a->ring.spareHres);
+    if (a->ring.heldHres) (void)hipHostFree(a->ring.heldHres);
+    if (a->ring.copyStream) (void)hipStreamDestroy(a->ring.copyStream);
+    if (a->ring.copyOutStream) (void)hipStreamDestroy(a->ring.copyOutStream);
+    if (a->mini.loneHost) (void)hipHostFree(a->mini.loneHost);
+    if (a->mini.loneReadEv) (void)hipEventDestroy(a->mini.loneReadEv);
     delete a;
 }
 
@@ -206,201 +195,231 @@ bool is_pinned_host(const void *p)
     return at.type == hipMemoryTypeHost;
 }
 
-// chunks that can be accepted now: the free places (they are taken in ring order: free ones are contiguous from `tail`)
-int async_room(const PsVoAsync *a)
+// frames on the device as the batched call takes them: two arrays, or (pts null) packed frames of the stream's stride
+PsFrameSet frame_set(const PsVoStream *s, const void *desc, const void *pts, const int32_t *nk, int frames)
 {
-    const int S = (int)a->lane.size();
-    int freePlaces = 0;
-    for (int i = 0; i < S && a->lane[(size_t)((a->tail + i) % S)].state == 0; ++i) ++freePlaces;
-    return freePlaces;
+    PsFrameSet fs;
+    fs.desc = (const uint8_t *)desc;
+    fs.pts = (const float *)(pts ? pts : (const uint8_t *)desc + (size_t)s->cap * 32);
+    fs.nkpts = nk;
+    fs.numFrames = frames;
+    fs.maxKpts = s->cap;
+    fs.descFrameStride = fs.ptsFrameStride = pts ? 0 : s->async->packStride;
+    return fs;
 }
 
-// the pinned staging area of the chunk that will be uploaded next (chunk number chunkSeq): a chunk's area is used again
-// lanes + ahead + 1 chunks later, and a chunk is only accepted while fewer than lanes + ahead chunks are alive (async_room) --
-// by then the earlier user of the area has been popped, so its upload is long done
-int stage_area(PsVoStream *s, uint8_t **out)
+// inliers / poses only: a kernel writes just those of P pairs from the device block into the mapped pinned one
+void launch_pack_results(const ResLayout &res, hipStream_t stream, int P, int mode, uint8_t *dres, uint8_t *hresDev)
 {
-    PsVoAsync *a = s->async;
-    uint8_t *&h = a->stagePool[(size_t)(a->chunkSeq % (long long)a->stagePool.size())];
-    if (!h) {
-        PSA_HIP(hipHostMalloc((void **)&h, a->packed ? (size_t)a->B * a->packStride : (size_t)a->B * s->cap * 44, hipHostMallocDefault));
-        if (a->mini) PSA_HIP(hipHostGetDevicePointer((void **)&a->stagePoolDev[(size_t)(a->chunkSeq % (long long)a->stagePool.size())], h, 0));
-    }
-    *out = h;
-    return PS_OK;
+    const PsPairResults d = res.device(dres), h = res.device(hresDev);
+    hipLaunchKernelGGL(ps_pack_results_to_host, dim3((unsigned)P), dim3(kBlock), 0, stream, (const PsDMatch *)d.matches,
+                       (const int32_t *)d.numMatches, (const uint8_t *)d.inlierMask, (const float *)d.pose, (const PsRansacStats *)d.stats,
+                       (int)res.cap, mode, h.matches, h.pose, h.stats, h.numMatches);
 }
 
-// One chunk on lane[tail] (free, checked by the caller): meta block, the batched call's launches behind the chunk's uploads,
-// the download.
-int async_launch(PsVoStream *s, const AsyncChunk &c)
+// A chunk's frames as a submit takes them: host pointers for the ring's uploads (packed: `desc` alone), and for a mini chunk the
+// device view its copy-in kernel reads them through.  inPlace: they lie in the caller's pinned memory, not in a staging area.
+struct ChunkFrames {
+    const uint8_t *desc = nullptr;
+    const float *pts = nullptr;
+    const uint8_t *dev = nullptr;
+    bool inPlace = false;
+};
+
+// the pinned staging area of the chunk that will be submitted next (Ledger::next_area: written again only when every chunk
+// that read it has been popped)
+int stage_area(PsVoStream *s, ChunkFrames *out)
 {
     PsVoAsync *a = s->async;
     PsContext *ctx = s->ctx;
-    const size_t cap = (size_t)s->cap;
-    AsyncLane &l = a->lane[(size_t)a->tail];
-    // consecutive chunks on consecutive lanes; a lane's stream orders the chunks it is given (its scratch arena is theirs in turn)
-    // (launchSeq, the place's state, tail and inFlight are committed at the END of this function: a chunk that could not be
-    // queued completely leaves the pipeline's bookkeeping as it found it -- async_abort_chunk does the rest)
-    PsContext *lc = l.ctx = a->laneCtx[(size_t)(a->launchSeq % (long long)a->lanes)];
-    a->diagLaunches++;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t1 = now();
-    const int P = c.n - c.first;
-    int32_t *pm = l.hmeta;
-    for (int i = c.first; i < c.n; ++i) { // query = previous frame, train = current (matcher.cpp:470-471)
-        pm[2 * (i - c.first)] = i == 0 ? c.prevPos : c.pos0 + i - 1;
-        pm[2 * (i - c.first) + 1] = c.pos0 + i;
+    const size_t k = (size_t)a->led.next_area(), cap = (size_t)s->cap;
+    uint8_t *&h = a->stagePool[k];
+    if (!h) {
+        PS_HIP(hipHostMalloc((void **)&h, a->packed ? (size_t)a->led.B * a->packStride : (size_t)a->led.B * cap * 44, hipHostMallocDefault));
+        if (a->led.mini) PS_HIP(hipHostGetDevicePointer((void **)&a->mini.stagePoolDev[k], h, 0));
     }
+    *out = ChunkFrames{h, a->packed ? nullptr : reinterpret_cast<const float *>(h + (size_t)a->led.B * cap * 32),
+                       a->led.mini ? a->mini.stagePoolDev[k] : nullptr, false};
+    return PS_OK;
+}
+
+// n rows of one frame (descriptors `descStep` bytes apart) into slot k of a staging area, in the stream's layout
+void stage_frame(const PsVoStream *s, const ChunkFrames &area, int k, const uint8_t *desc, size_t descStep, const void *pts, int n)
+{
+    const PsVoAsync *a = s->async;
+    const size_t cap = (size_t)s->cap;
+    uint8_t *h = const_cast<uint8_t *>(area.desc);
+    uint8_t *hd = h + (size_t)k * (a->packed ? a->packStride : cap * 32);
+    uint8_t *hp = a->packed ? hd + cap * 32 : h + (size_t)a->led.B * cap * 32 + (size_t)k * cap * 12;
+    if (n <= 0) return;
+    if (descStep == PS_DESC_BYTES) {
+        memcpy(hd, desc, (size_t)n * 32);
+    } else {
+        for (int i = 0; i < n; ++i) memcpy(hd + (size_t)i * 32, desc + (size_t)i * descStep, 32);
+    }
+    memcpy(hp, pts, (size_t)n * 12);
+}
+
+// ---- a chunk's launch: begin, the form's own launches, commit ----
+
+// The chunk the next n frames make, on the place and lane the ledger gives it.  Nothing is taken yet: a chunk that cannot be
+// queued completely leaves the ledger as it found it (async_abort_chunk does the rest).
+int chunk_begin(PsVoStream *s, const Chunk &c)
+{
+    PsVoAsync *a = s->async;
+    a->lane[(size_t)c.place].ctx = a->laneCtx[(size_t)c.lane];
+    a->diagLaunches++;
+#ifdef PS_STREAM_DIAG
+    // fault injection (tests/test_gpu_stream_async.py builds the library with -DPS_STREAM_DIAG; the shipped one does not contain
+    // this): the N-th chunk since configure fails before it has queued anything / behind its launches (chunk_commit)
+    static const char *diagFail = std::getenv("PUTSLAM_HIP_STREAM_DIAG_FAIL_CHUNK");
+    if (diagFail && std::atoll(diagFail) == a->diagLaunches - 1) return async_fail(s, PS_ERR_HIP, "pipelined chunk: injected failure (PS_STREAM_DIAG)");
+#endif
+    return PS_OK;
+}
+
+// The chunk's launches are queued on `stream`: evDone (and `alsoBehind`) behind them, and the chunk takes its place.
+int chunk_commit(PsVoStream *s, const Chunk &c, AsyncLane &l, hipStream_t stream, hipEvent_t alsoBehind = nullptr)
+{
+    PsVoAsync *a = s->async;
+    PsContext *ctx = s->ctx;
+#ifdef PS_STREAM_DIAG
+    static const char *diagFailAfter = std::getenv("PUTSLAM_HIP_STREAM_DIAG_FAIL_AFTER");
+    if (diagFailAfter && std::atoll(diagFailAfter) == a->diagLaunches - 1)
+        return fail(ctx, PS_ERR_HIP, "pipelined chunk: injected failure behind the batched call (PS_STREAM_DIAG)");
+#endif
+    PS_HIP(hipEventRecord(l.evDone, stream));
+    if (alsoBehind) PS_HIP(hipEventRecord(alsoBehind, stream));
+    a->led.commit(c);
+    a->dbgN++;
+    return PS_OK;
+}
+
+// (experiment of -DPS_STREAM_DIAG builds, results meaningless: PUTSLAM_HIP_STREAM_DIAG_NO_UPLOAD=1 skips the frames' way to the
+// device after the first 64 chunks -- the chunks then run on whatever frames the device holds; it told what the pipeline does when
+// the link costs nothing, profiles/r05h/stream_limits.txt.  The shipped library does not contain it.)
+bool diag_no_upload(const PsVoAsync *a)
+{
+    bool skip = false;
+#ifdef PS_STREAM_DIAG
+    static const bool diagNoUpload = std::getenv("PUTSLAM_HIP_STREAM_DIAG_NO_UPLOAD") != nullptr;
+    skip = diagNoUpload && a->led.chunkSeq >= 64;
+#endif
+    (void)a;
+    return skip;
+}
+
+int chunk_failed(PsVoStream *s, PsContext *lc, int rc)
+{
+    s->ctx->err = std::string("pipelined chunk: ") + lc->err;
+    return rc;
+}
+
+// One chunk of the ring form: n frames (pinned host memory: desc n x cap x 32, pts n x cap x 3, or n packed frames; row counts
+// nk) -> ring -> the next place, launched on the next lane's stream: meta block, the batched call's launches behind the
+// chunk's uploads, the download.  The caller has checked the ledger's room().
+int ring_submit_body(PsVoStream *s, const ChunkFrames &fr, const int32_t *nk, int n)
+{
+    PsVoAsync *a = s->async;
+    AsyncRing &r = a->ring;
+    PsContext *ctx = s->ctx;
+    const size_t cap = (size_t)s->cap;
+    const Chunk c = a->led.next(n);
+    const double t0 = async_now();
+    hipEvent_t up = r.upEv[(size_t)c.area];
+    if (!diag_no_upload(a)) {
+        // (packed: `desc` = the chunk's packed frames: ONE transfer, no idle link between a descriptor and a point upload)
+        const size_t step = a->packed ? a->packStride : cap * 32;
+        PS_HIP(hipMemcpyAsync((uint8_t *)r.desc.p + (size_t)c.pos0 * step, fr.desc, (size_t)n * step, hipMemcpyHostToDevice, r.copyStream));
+        if (!a->packed)
+            PS_HIP(hipMemcpyAsync((uint8_t *)r.pts.p + (size_t)c.pos0 * cap * 12, fr.pts, (size_t)n * cap * 12, hipMemcpyHostToDevice, r.copyStream));
+    }
+    PS_HIP(hipEventRecord(up, r.copyStream));
+    // (the slots are this chunk's to write: no chunk alive reads them, whether this one is committed or not)
+    for (int i = 0; i < n; ++i) r.nk[(size_t)(c.pos0 + i)] = nk[i];
+    a->dbgT[0] += async_now() - t0;
+    const int P = c.pairs();
+    if (P <= 0) {
+        // a lone first frame: nothing to run, no place taken; its staging area (if it came through one) is reused by the
+        // next push, so the upload is waited for here
+        PS_HIP(hipStreamSynchronize(r.copyStream));
+        a->led.lone_first_frame(c);
+        return PS_OK;
+    }
+    // consecutive chunks on consecutive lanes; a lane's stream orders the chunks it is given (its scratch arena is theirs in turn)
+    int rc = chunk_begin(s, c);
+    if (rc != PS_OK) return rc;
+    AsyncLane &l = a->lane[(size_t)c.place];
+    PsContext *lc = l.ctx;
+    const double t1 = async_now();
+    int32_t *pm = l.hmeta;
+    c.pair_list(pm);
     // (a snapshot of the ring's row counts as they are NOW: it may already hold those of later chunks, never other values for
     // the slots this chunk reads -- those are not written again while it is alive)
-    memcpy(pm + 2 * (size_t)a->B, a->nkRing.data(), (size_t)a->ringFrames * sizeof(int32_t));
-    CopySegs up{};
-    up.src[0] = l.hmetaDev;
-    up.dst[0] = l.meta.p;
-    up.bytes[0] = ((unsigned long long)2 * a->B + a->ringFrames) * sizeof(int32_t);
-    up.n = 1;
-    hipLaunchKernelGGL(ps_copy_segments, dim3(1), dim3(256), 0, lc->stream, up); // (a few KB: beside the previous chunk's kernels)
+    memcpy(pm + 2 * (size_t)a->led.B, r.nk.data(), (size_t)a->led.ringFrames * sizeof(int32_t));
+    CopySegs meta{};
+    meta.src[0] = l.hmetaDev;
+    meta.dst[0] = l.meta.p;
+    meta.bytes[0] = ((unsigned long long)2 * a->led.B + a->led.ringFrames) * sizeof(int32_t);
+    meta.n = 1;
+    hipLaunchKernelGGL(ps_copy_segments, dim3(1), dim3(256), 0, lc->stream, meta); // (a few KB: beside the previous chunk's kernels)
     PS_HIP(hipGetLastError());
 #ifdef PS_STREAM_DIAG
     // (experiment, results meaningless: the chunk's kernels do not wait for its upload -- what the upload -> lane dependency costs)
     static const bool diagNoUpWait = std::getenv("PUTSLAM_HIP_STREAM_DIAG_NO_UPWAIT") != nullptr;
     if (!diagNoUpWait)
 #endif
-    PS_HIP(hipStreamWaitEvent(lc->stream, c.up, 0));
-    PsFrameSet fs;
-    fs.desc = (const uint8_t *)a->ringDesc.p;
-    fs.pts = a->packed ? (const float *)((const uint8_t *)a->ringDesc.p + cap * 32) : (const float *)a->ringPts.p;
-    fs.nkpts = (const int32_t *)l.meta.p + 2 * (size_t)a->B;
-    fs.numFrames = a->ringFrames;
-    fs.maxKpts = s->cap;
-    fs.descFrameStride = fs.ptsFrameStride = a->packed ? a->packStride : 0;
+    PS_HIP(hipStreamWaitEvent(lc->stream, up, 0));
+    const PsFrameSet fs = frame_set(s, r.desc.p, a->packed ? nullptr : r.pts.p, (const int32_t *)l.meta.p + 2 * (size_t)a->led.B, a->led.ringFrames);
     uint8_t *dres = (uint8_t *)l.res.p;
-    PsPairResults out;
-    out.matches = (PsDMatch *)dres;
-    out.inlierMask = dres + a->offMask;
-    out.pose = (float *)(dres + a->offPose);
-    out.stats = (PsRansacStats *)(dres + a->offStats);
-    out.numMatches = (int32_t *)(dres + a->offNum);
+    PsPairResults out = a->res.device(dres);
     PsRansacConfig c2 = a->cfg;
     c2.seed = a->cfg.seed + (uint64_t)c.firstPair;
-    int rc = PS_OK;
-#ifdef PS_STREAM_DIAG
-    // fault injection (tests/test_gpu_stream_async.py builds the library with -DPS_STREAM_DIAG; the shipped one does not contain
-    // this): the batched call of the N-th chunk since configure fails before / after it has queued its launches
-    static const char *diagFail = std::getenv("PUTSLAM_HIP_STREAM_DIAG_FAIL_CHUNK");
-    static const char *diagFailAfter = std::getenv("PUTSLAM_HIP_STREAM_DIAG_FAIL_AFTER");
-    if (diagFail && std::atoll(diagFail) == a->diagLaunches - 1) {
-        lc->err = "injected failure (PS_STREAM_DIAG)";
-        rc = PS_ERR_HIP;
-    }
-#endif
-    if (rc == PS_OK) rc = ps_vo_pairs_device(lc, &a->prm, &c2, a->haveK ? a->K : nullptr, &fs, (const int32_t *)l.meta.p, P, &out);
-    if (rc != PS_OK) {
-        ctx->err = std::string("pipelined chunk: ") + lc->err;
-        return rc;
-    }
-#ifdef PS_STREAM_DIAG
-    if (diagFailAfter && std::atoll(diagFailAfter) == a->diagLaunches - 1)
-        return fail(ctx, PS_ERR_HIP, "pipelined chunk: injected failure behind the batched call (PS_STREAM_DIAG)");
-#endif
-    const double t2 = now();
+    rc = ps_vo_pairs_device(lc, &a->prm, &c2, a->haveK ? a->K : nullptr, &fs, (const int32_t *)l.meta.p, P, &out);
+    if (rc != PS_OK) return chunk_failed(s, lc, rc);
+    const double t2 = async_now();
     // The download goes out on a stream of its own, behind an event, when the process has hardware queues to spare (async_build):
     // this runtime executes a device -> host hipMemcpyAsync as a blit kernel whatever stream it is queued on
     // (profiles/r05e/timeline_tail.txt), and on the lane's own stream that kernel sat between the lane's launches (29 % of the
     // time one was running, profiles/r05d); on the copy-out stream it overlaps the lane's NEXT chunk instead: + 11 ... 18 % with
     // six lanes.
-    hipStream_t ds = a->downloadsOnLane ? lc->stream : a->copyOutStream;
-    if (!a->downloadsOnLane) {
+    hipStream_t ds = r.downloadsOnLane ? lc->stream : r.copyOutStream;
+    if (!r.downloadsOnLane) {
         PS_HIP(hipEventRecord(l.evRun, lc->stream));
         PS_HIP(hipStreamWaitEvent(ds, l.evRun, 0));
     }
     if (a->resultMode != PS_RESULTS_FULL) {
-        // inliers / poses only: a kernel writes just those into the mapped pinned block, behind kernel 4 (on the download stream
-        // too: on the lane's own stream the lane's next chunk waited behind its writes over the link)
-        hipLaunchKernelGGL(ps_pack_results_to_host, dim3((unsigned)P), dim3(kBlock), 0, ds, (const PsDMatch *)dres,
-                           (const int32_t *)(dres + a->offNum), (const uint8_t *)(dres + a->offMask), (const float *)(dres + a->offPose),
-                           (const PsRansacStats *)(dres + a->offStats), s->cap, a->resultMode, (PsDMatch *)l.hresDev,
-                           (float *)(l.hresDev + a->offPose), (PsRansacStats *)(l.hresDev + a->offStats),
-                           (int32_t *)(l.hresDev + a->offNum));
+        // behind kernel 4 (on the download stream too: on the lane's own stream the lane's next chunk waited behind its writes
+        // over the link)
+        launch_pack_results(a->res, ds, P, a->resultMode, dres, l.hresDev);
         PS_HIP(hipGetLastError());
-    }
-    if (a->resultMode != PS_RESULTS_FULL) {
-        // (written by ps_pack_results_to_host above)
-    } else if (P == a->B) {
-        PS_HIP(hipMemcpyAsync(l.hres, dres, a->resBytes, hipMemcpyDeviceToHost, ds));
+    } else if (P == a->led.B) {
+        PS_HIP(hipMemcpyAsync(l.hres, dres, a->res.bytes, hipMemcpyDeviceToHost, ds));
     } else {
-        const size_t p = (size_t)P;
-        PS_HIP(hipMemcpyAsync(l.hres, dres, p * cap * sizeof(PsDMatch), hipMemcpyDeviceToHost, ds));
-        PS_HIP(hipMemcpyAsync(l.hres + a->offMask, dres + a->offMask, p * cap, hipMemcpyDeviceToHost, ds));
-        PS_HIP(hipMemcpyAsync(l.hres + a->offPose, dres + a->offPose, p * 64, hipMemcpyDeviceToHost, ds));
-        PS_HIP(hipMemcpyAsync(l.hres + a->offStats, dres + a->offStats, p * sizeof(PsRansacStats), hipMemcpyDeviceToHost, ds));
-        PS_HIP(hipMemcpyAsync(l.hres + a->offNum, dres + a->offNum, p * sizeof(int32_t), hipMemcpyDeviceToHost, ds));
+        ResLayout::Seg seg[5];
+        a->res.segments((size_t)P, 1, seg);
+        for (int k = 0; k < 5; ++k) PS_HIP(hipMemcpyAsync(l.hres + seg[k].off, dres + seg[k].off, seg[k].bytes, hipMemcpyDeviceToHost, ds));
     }
-    PS_HIP(hipEventRecord(l.evDone, ds));
-    const double t3 = now();
+    rc = chunk_commit(s, c, l, ds);
+    if (rc != PS_OK) return rc;
+    const double t3 = async_now();
     if (const char *v = std::getenv("PUTSLAM_HIP_STREAM_DEBUG"))
         if (v[0] == '2')
-            fprintf(stderr, "[chunk at pair %lld lane %d P %d] call %.1f download %.1f\n", c.firstPair, a->tail, P, 1e6 * (t2 - t1),
+            fprintf(stderr, "[chunk at pair %lld lane %d P %d] call %.1f download %.1f\n", c.firstPair, c.place, P, 1e6 * (t2 - t1),
                     1e6 * (t3 - t2));
     a->dbgT[1] += t2 - t1;
     a->dbgT[2] += t3 - t2;
-    a->dbgN++;
-    l.state = 1;
-    l.firstPair = c.firstPair;
-    l.pairs = P;
-    l.epoch = c.epoch;
-    a->launchSeq++;
-    a->tail = (a->tail + 1) % (int)a->lane.size();
-    a->inFlight++;
     return PS_OK;
 }
-
-// A chunk could not be queued (an allocation or a HIP call failed somewhere between its upload and its download).  Whatever
-// part of it WAS queued is drained -- nothing is in flight on a place that is still marked free --, the chunk's frames are
-// dropped as a unit, and the stream continues as after ps_vo_stream_reset: the next frame has no predecessor, pair numbering
-// restarts at 0, the epoch advances (include/putslam_hip.h).  Chunks submitted before keep their place, numbering and epoch.
-int async_abort_chunk(PsVoStream *s, int rc)
-{
-    PsVoAsync *a = s->async;
-    const std::string why = s->ctx->err;
-    if (a->copyStream) (void)hipStreamSynchronize(a->copyStream);
-    PsContext *lc = a->laneCtx.empty() ? nullptr : a->laneCtx[(size_t)((a->mini ? (long long)a->tail : a->launchSeq) % (long long)a->lanes)];
-    if (lc) (void)hipStreamSynchronize(lc->stream);
-    a->haloDev = nullptr;
-    a->haloIsLone = false;
-    if (a->copyOutStream) (void)hipStreamSynchronize(a->copyOutStream);
-    (void)hipGetLastError();
-    a->prevPos = -1;
-    a->pairCounter = 0;
-    a->epoch++;
-    a->staged = 0;
-    s->ctx->err = why + " -- pipelined stream: the chunk's frames were dropped; the next frame starts a new epoch (pair numbering from 0)";
-    return rc;
-}
-
-// One chunk: n frames (pinned host memory: desc n x cap x 32, pts n x cap x 3; row counts nk) -> ring -> the next place, launched
-// on the next lane's stream.  The caller has checked async_room().
-int async_submit_body(PsVoStream *s, const uint8_t *desc, const float *pts, const int32_t *nk, int n);
-
-using psdev::MiniMeta;
-using psdev::ps_mini_copy_in;
 
 // The launches of one mini chunk on its lane's stream: frames in, kernels 1 - 4, results out (what a place's graph holds).
 int mini_enqueue(PsVoStream *s, AsyncLane &l, PsContext *lc, const Plan &pl, int P)
 {
     PsVoAsync *a = s->async;
     PsContext *ctx = s->ctx;
-    const size_t cap = (size_t)s->cap;
     MiniMeta *dm = (MiniMeta *)l.meta.p;
     const int groups = 8;
-    unsigned copyGrid = (unsigned)((a->B + 1) * groups);
-#ifdef PS_STREAM_DIAG
-    // (experiment: what the lanes do when the frames cost nothing -- the meta block alone travels, the kernels run on whatever the
-    // place's frames hold; results are meaningless)
-    static const bool diagNoUpload = std::getenv("PUTSLAM_HIP_STREAM_DIAG_NO_UPLOAD") != nullptr;
-    if (diagNoUpload && a->diagLaunches > 64) copyGrid = 0;
-#endif
-    if (copyGrid == 0) {
+    if (diag_no_upload(a)) { // (the meta block alone travels)
         CopySegs up{};
         up.src[0] = l.hmetaDev;
         up.dst[0] = dm;
@@ -408,169 +427,137 @@ int mini_enqueue(PsVoStream *s, AsyncLane &l, PsContext *lc, const Plan &pl, int
         up.n = 1;
         hipLaunchKernelGGL(ps_copy_segments, dim3(1), dim3(64), 0, lc->stream, up);
     } else
-        hipLaunchKernelGGL(ps_mini_copy_in, dim3(copyGrid), dim3(256), 0, lc->stream, (const MiniMeta *)l.hmetaDev, dm,
+        hipLaunchKernelGGL(ps_mini_copy_in, dim3((unsigned)((a->led.B + 1) * groups)), dim3(256), 0, lc->stream, (const MiniMeta *)l.hmetaDev, dm,
                            (uint8_t *)l.frames.p, s->cap, (unsigned long long)a->packStride, groups);
     PS_HIP(hipGetLastError());
-    PsFrameSet fs;
-    fs.desc = (const uint8_t *)l.frames.p;
-    fs.pts = (const float *)((const uint8_t *)l.frames.p + cap * 32);
-    fs.nkpts = dm->nk;
-    fs.numFrames = a->B + 1;
-    fs.maxKpts = s->cap;
-    fs.descFrameStride = fs.ptsFrameStride = a->packStride;
+    const PsFrameSet fs = frame_set(s, l.frames.p, nullptr, dm->nk, a->led.B + 1);
     uint8_t *dres = (uint8_t *)l.res.p;
-    int rc = run_match_stage(lc, fs, dm->pairs, P, &pl, (PsDMatch *)dres, (int32_t *)(dres + a->offNum), 0);
-    if (rc == PS_OK)
-        rc = run_ransac_stage(lc, pl, P, s->cap, (const PsDMatch *)dres, (const int32_t *)(dres + a->offNum), s->cap, (float *)(dres + a->offPose),
-                              dres + a->offMask, (PsRansacStats *)(dres + a->offStats), 2);
-    if (rc != PS_OK) {
-        ctx->err = std::string("pipelined chunk: ") + lc->err;
-        return rc;
-    }
+    const PsPairResults out = a->res.device(dres);
+    int rc = run_match_stage(lc, fs, dm->pairs, P, &pl, out.matches, out.numMatches, 0);
+    if (rc == PS_OK) rc = run_ransac_stage(lc, pl, P, s->cap, out.matches, out.numMatches, s->cap, out.pose, out.inlierMask, out.stats, 2);
+    if (rc != PS_OK) return chunk_failed(s, lc, rc);
     if (a->resultMode != PS_RESULTS_FULL) {
-        hipLaunchKernelGGL(ps_pack_results_to_host, dim3((unsigned)P), dim3(kBlock), 0, lc->stream, (const PsDMatch *)dres,
-                           (const int32_t *)(dres + a->offNum), (const uint8_t *)(dres + a->offMask), (const float *)(dres + a->offPose),
-                           (const PsRansacStats *)(dres + a->offStats), s->cap, a->resultMode, (PsDMatch *)l.hresDev,
-                           (float *)(l.hresDev + a->offPose), (PsRansacStats *)(l.hresDev + a->offStats), (int32_t *)(l.hresDev + a->offNum));
+        launch_pack_results(a->res, lc->stream, P, a->resultMode, dres, l.hresDev);
     } else {
-        const size_t p = (size_t)P;
+        ResLayout::Seg seg[5];
+        a->res.segments((size_t)P, 4, seg);
         CopySegs down{};
-        const size_t off[5] = {0, a->offMask, a->offPose, a->offStats, a->offNum};
-        const size_t len[5] = {p * cap * sizeof(PsDMatch), (p * cap + 3) & ~(size_t)3, p * 64, p * sizeof(PsRansacStats), p * sizeof(int32_t)};
         for (int k = 0; k < 5; ++k) {
-            down.src[k] = dres + off[k];
-            down.dst[k] = l.hresDev + off[k];
-            down.bytes[k] = len[k];
+            down.src[k] = dres + seg[k].off;
+            down.dst[k] = l.hresDev + seg[k].off;
+            down.bytes[k] = seg[k].bytes;
         }
         down.n = 5;
-        const unsigned groupsOut = (unsigned)((len[0] / 16 + 255) / 256);
+        const unsigned groupsOut = (unsigned)((seg[0].bytes / 16 + 255) / 256);
         hipLaunchKernelGGL(ps_copy_segments, dim3(groupsOut < 1 ? 1 : (groupsOut > 32 ? 32 : groupsOut)), dim3(256), 0, lc->stream, down);
     }
     PS_HIP(hipGetLastError());
     return PS_OK;
 }
 
-// One mini chunk: the n frames staged in `h` (packed layout) -> the next place, on that place's lane.  The caller has checked
-// async_room().
-int mini_submit_body(PsVoStream *s, uint8_t *h, const int32_t *nk, int n)
+// the plan of a mini chunk of P pairs on lane lc: the seed is read from the place's meta block
+int mini_plan(PsVoStream *s, AsyncLane &l, PsContext *lc, int P, Plan &pl)
+{
+    PsVoAsync *a = s->async;
+    int rc = make_plan(lc, &a->prm, &a->cfg, a->haveK ? a->K : nullptr, s->cap, s->cap, pl);
+    if (rc == PS_OK) {
+        pl.ma.seedDev = reinterpret_cast<const uint64_t *>(&((MiniMeta *)l.meta.p)->seed);
+        rc = prepare_score(lc, pl, P, s->cap);
+    }
+    return rc == PS_OK ? PS_OK : chunk_failed(s, lc, rc);
+}
+
+// the place's full chunk as a graph, once an un-captured full chunk has sized its lane's arena (no graph and no error: capture
+// is not available here, ordinary launches from now on)
+int mini_capture(PsVoStream *s, AsyncLane &l, PsContext *lc, int laneIdx, int P)
 {
     PsVoAsync *a = s->async;
     PsContext *ctx = s->ctx;
-    // the chunk's frames as the copy-in kernel sees them: the staging area they were collected in, or -- pinned packed frames
-    // handed over by ps_vo_stream_push_many_packed (PsVoAsync::inPlaceDev) -- the caller's own memory, read in place
-    const bool inPlace = a->inPlaceDev != nullptr;
-    const uint8_t *hDev = inPlace ? a->inPlaceDev : a->stagePoolDev[(size_t)(a->chunkSeq % (long long)a->stagePool.size())];
-    a->inPlaceDev = nullptr;
-    const int first = a->prevPos >= 0 ? 0 : 1;
-    const int P = n - first;
-    const uint8_t *haloWas = a->haloDev;
-    const int haloNkWas = a->haloNk;
-    const bool haloWasLone = a->haloIsLone;
+    Plan pl;
+    int rc = mini_plan(s, l, lc, P, pl);
+    if (rc != PS_OK) return rc;
+    PS_ENSURE(lc->keys, (size_t)P * s->cap * sizeof(uint32_t));
+    rc = keys_clean(lc, (size_t)P * s->cap * sizeof(uint32_t)); // (outside the capture: a replay finds the block as its capture did)
+    if (rc != PS_OK) return chunk_failed(s, lc, rc);
+    if (lc->arenaGen != a->mini.laneWarmGen[(size_t)laneIdx]) return PS_OK;
+    hipGraph_t graph = nullptr;
+    if (hipStreamBeginCapture(lc->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        const int r = mini_enqueue(s, l, lc, pl, P);
+        const hipError_t e2 = hipStreamEndCapture(lc->stream, &graph);
+        if (r == PS_OK && e2 == hipSuccess && graph && hipGraphInstantiate(&l.gexec, graph, nullptr, nullptr, 0) != hipSuccess) l.gexec = nullptr;
+        if (r != PS_OK || e2 != hipSuccess) l.gexec = nullptr;
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+    if (!l.gexec) {
+        s->graphsEnabled = false;
+        (void)hipGetLastError();
+        ctx->err.clear();
+    } else {
+        l.gexecGen = lc->arenaGen;
+    }
+    return PS_OK;
+}
+
+// One mini chunk: n frames (fr.desc on the host, fr.dev as the copy-in kernel sees them: a staging area, or pinned packed
+// frames of the caller's, read in place) -> the next place, on that place's lane.  The caller has checked the ledger's room().
+int mini_submit_body(PsVoStream *s, const ChunkFrames &fr, const int32_t *nk, int n)
+{
+    PsVoAsync *a = s->async;
+    AsyncMini &m = a->mini;
+    PsContext *ctx = s->ctx;
+    const Chunk c = a->led.next(n);
+    const int P = c.pairs();
     if (P <= 0) {
         // A lone first frame (the stream's first, or the first after a reset): nothing to run, no place taken -- and therefore no
-        // staging area either: the areas rotate with the LAUNCHED chunks, which is what makes their reuse safe (an area is written
-        // again lanes + ahead + 1 launched chunks later: by then its chunk AND the successor that reads its last frame as the
-        // previous one have been popped).  Round 6's first form let such a frame keep its area and advance the rotation: every
-        // reset moved the reuse one chunk closer, until a new frame could be staged over a frame an in-flight chunk had not read
-        // yet (found by the stream fuzz: 17 of 15 000 configurations, all with a reset and chunks of one or two frames).  The frame
-        // moves to a buffer of its own instead; that buffer is written again only after the chunk that read it has finished.
-        if (inPlace) {
-            a->haloDev = hDev; // (the caller's pinned memory: untouched until the pair it is the previous frame of has been popped)
-            a->haloIsLone = false;
-        } else {
-            if (!a->loneHost) {
-                PS_HIP(hipHostMalloc((void **)&a->loneHost, a->packStride, hipHostMallocDefault));
-                PS_HIP(hipHostGetDevicePointer((void **)&a->loneDev, a->loneHost, 0));
-                PS_HIP(hipEventCreateWithFlags(&a->loneReadEv, hipEventDisableTiming));
+        // staging area either (the ledger's reuse invariant).  The frame stays where the caller keeps it, or moves to a buffer
+        // of its own; that buffer is written again only after the chunk that read it has finished.
+        if (!fr.inPlace) {
+            if (!m.loneHost) {
+                PS_HIP(hipHostMalloc((void **)&m.loneHost, a->packStride, hipHostMallocDefault));
+                PS_HIP(hipHostGetDevicePointer((void **)&m.loneDev, m.loneHost, 0));
+                PS_HIP(hipEventCreateWithFlags(&m.loneReadEv, hipEventDisableTiming));
             }
-            if (a->loneReadPending) {
-                PS_HIP(hipEventSynchronize(a->loneReadEv));
-                a->loneReadPending = false;
+            if (m.loneReadPending) {
+                PS_HIP(hipEventSynchronize(m.loneReadEv));
+                m.loneReadPending = false;
             }
-            const size_t cap = (size_t)s->cap;
-            memcpy(a->loneHost, h, (size_t)nk[0] * 32);
-            memcpy(a->loneHost + cap * 32, h + cap * 32, (size_t)nk[0] * 12);
-            a->haloDev = a->loneDev;
-            a->haloIsLone = true;
+            stage_frame(s, ChunkFrames{m.loneHost}, 0, fr.desc, PS_DESC_BYTES, fr.desc + (size_t)s->cap * 32, nk[0]);
         }
-        a->haloNk = nk[0];
-        a->prevPos = 0;
+        // (the caller's pinned memory: untouched until the pair it is the previous frame of has been popped)
+        m.haloDev = fr.inPlace ? fr.dev : m.loneDev;
+        m.haloIsLone = !fr.inPlace;
+        m.haloNk = nk[0];
+        a->led.lone_first_frame(c);
         return PS_OK;
     }
-    a->chunkSeq++;
-    // (the stream's latest frame from now on: the next chunk reads it from this staging slot -- or from the caller's pinned block)
-    a->haloDev = hDev + (size_t)(n - 1) * a->packStride;
-    a->haloNk = nk[n - 1];
-    a->haloIsLone = false;
-    a->prevPos = 0;
-    const int place = a->tail;
-    AsyncLane &l = a->lane[(size_t)place];
-    const int laneIdx = place % a->lanes; // (fixed per place: the place's graph holds its lane's arena pointers)
-    PsContext *lc = l.ctx = a->laneCtx[(size_t)laneIdx];
-    a->diagLaunches++;
+    int rc = chunk_begin(s, c);
+    if (rc != PS_OK) return rc;
+    AsyncLane &l = a->lane[(size_t)c.place];
+    PsContext *lc = l.ctx;
     MiniMeta *hm = (MiniMeta *)l.hmeta;
     memset(hm, 0, sizeof *hm);
-    for (int i = 0; i < P; ++i) { // query = previous frame, train = current (matcher.cpp:470-471)
-        hm->pairs[2 * i] = first + i;
-        hm->pairs[2 * i + 1] = first + i + 1;
-    }
-    hm->nk[0] = first ? 0 : haloNkWas;
+    c.pair_list(hm->pairs);
+    hm->nk[0] = c.first ? 0 : m.haloNk;
     for (int i = 0; i < n; ++i) hm->nk[1 + i] = nk[i];
     hm->n = n;
-    hm->first = first;
-    hm->seed = a->cfg.seed + (uint64_t)a->pairCounter;
-    hm->src[0] = first ? nullptr : haloWas;
-    for (int i = 0; i < n; ++i) hm->src[1 + i] = hDev + (size_t)i * a->packStride;
-    int rc = PS_OK;
-#ifdef PS_STREAM_DIAG
-    static const char *diagFail = std::getenv("PUTSLAM_HIP_STREAM_DIAG_FAIL_CHUNK");
-    static const char *diagFailAfter = std::getenv("PUTSLAM_HIP_STREAM_DIAG_FAIL_AFTER");
-    if (diagFail && std::atoll(diagFail) == a->diagLaunches - 1) return fail(ctx, PS_ERR_HIP, "pipelined chunk: injected failure (PS_STREAM_DIAG)");
-#endif
-    const bool full = P == a->B && !first;
+    hm->first = c.first;
+    hm->seed = a->cfg.seed + (uint64_t)c.firstPair;
+    hm->src[0] = c.first ? nullptr : m.haloDev;
+    for (int i = 0; i < n; ++i) hm->src[1 + i] = fr.dev + (size_t)i * a->packStride;
+    const bool full = P == a->led.B && !c.first;
     bool launched = false;
-    if (full && a->miniGraphs && s->graphsEnabled) { // (PUTSLAM_HIP_STREAM_GRAPH=1; PUTSLAM_HIP_NO_GRAPH=1 at ps_vo_stream_create wins)
+    if (full && m.graphs && s->graphsEnabled) { // (PUTSLAM_HIP_STREAM_GRAPH=1; PUTSLAM_HIP_NO_GRAPH=1 at ps_vo_stream_create wins)
         if (l.gexec && l.gexecGen != lc->arenaGen) { // the lane's arena has moved since the capture
             (void)hipGraphExecDestroy(l.gexec);
             l.gexec = nullptr;
         }
-        if (!l.gexec && a->laneWarmGen[(size_t)laneIdx] == lc->arenaGen && lc->arenaGen != 0) {
-            // an un-captured full chunk has sized this lane's arena: capture the place's chunk
-            Plan pl;
-            rc = make_plan(lc, &a->prm, &a->cfg, a->haveK ? a->K : nullptr, s->cap, s->cap, pl);
-            if (rc == PS_OK) {
-                pl.ma.seedDev = reinterpret_cast<const uint64_t *>(&((MiniMeta *)l.meta.p)->seed);
-                rc = prepare_score(lc, pl, P, s->cap);
-            }
-            if (rc == PS_OK) {
-                PS_ENSURE(lc->keys, (size_t)P * s->cap * sizeof(uint32_t));
-                rc = keys_clean(lc, (size_t)P * s->cap * sizeof(uint32_t)); // (outside the capture: a replay finds the block as its capture did)
-            }
-            if (rc != PS_OK) {
-                ctx->err = std::string("pipelined chunk: ") + lc->err;
-                return rc;
-            }
-            if (lc->arenaGen == a->laneWarmGen[(size_t)laneIdx]) {
-                hipGraph_t graph = nullptr;
-                if (hipStreamBeginCapture(lc->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    const int r = mini_enqueue(s, l, lc, pl, P);
-                    const hipError_t e2 = hipStreamEndCapture(lc->stream, &graph);
-                    if (r == PS_OK && e2 == hipSuccess && graph && hipGraphInstantiate(&l.gexec, graph, nullptr, nullptr, 0) != hipSuccess) l.gexec = nullptr;
-                    if (r != PS_OK || e2 != hipSuccess) l.gexec = nullptr;
-                    if (graph) (void)hipGraphDestroy(graph);
-                }
-                if (!l.gexec) {
-                    s->graphsEnabled = false; // capture is not available here: ordinary launches from now on
-                    (void)hipGetLastError();
-                    ctx->err.clear();
-                } else {
-                    l.gexecGen = lc->arenaGen;
-                }
-            }
+        if (!l.gexec && m.laneWarmGen[(size_t)c.lane] == lc->arenaGen && lc->arenaGen != 0) {
+            rc = mini_capture(s, l, lc, c.lane, P);
+            if (rc != PS_OK) return rc;
         }
         if (l.gexec) {
             PS_HIP(hipGraphLaunch(l.gexec, lc->stream));
-            a->graphLaunches++;
+            m.graphLaunches++;
             launched = true;
         }
     }
@@ -582,157 +569,167 @@ int mini_submit_body(PsVoStream *s, uint8_t *h, const int32_t *nk, int n)
         Plan &pl = full ? l.plan : local;
         if (!cached) {
             l.planGen = 0;
-            rc = make_plan(lc, &a->prm, &a->cfg, a->haveK ? a->K : nullptr, s->cap, s->cap, pl);
-            if (rc == PS_OK) {
-                pl.ma.seedDev = reinterpret_cast<const uint64_t *>(&((MiniMeta *)l.meta.p)->seed);
-                rc = prepare_score(lc, pl, P, s->cap);
-            }
-            if (rc != PS_OK) {
-                ctx->err = std::string("pipelined chunk: ") + lc->err;
-                return rc;
-            }
+            rc = mini_plan(s, l, lc, P, pl);
+            if (rc != PS_OK) return rc;
         }
         rc = mini_enqueue(s, l, lc, pl, P);
         if (rc != PS_OK) return rc;
         if (full) {
-            a->laneWarmGen[(size_t)laneIdx] = lc->arenaGen;
+            m.laneWarmGen[(size_t)c.lane] = lc->arenaGen;
             l.planGen = lc->arenaGen; // (the plan points at the blocks prepare_score sized -- counts, parked models, stop tables --;
                                       // the launches above only grow OTHER blocks, so the plan stays good for the arena as it is now)
         }
     }
-#ifdef PS_STREAM_DIAG
-    if (diagFailAfter && std::atoll(diagFailAfter) == a->diagLaunches - 1)
-        return fail(ctx, PS_ERR_HIP, "pipelined chunk: injected failure behind the batched call (PS_STREAM_DIAG)");
-#endif
-    PS_HIP(hipEventRecord(l.evDone, lc->stream));
-    if (haloWasLone && !first) { // this chunk read the lone-frame buffer as its previous frame: the buffer is free again behind it
-        PS_HIP(hipEventRecord(a->loneReadEv, lc->stream));
-        a->loneReadPending = true;
-    }
-    a->dbgN++;
-    l.state = 1;
-    l.firstPair = a->pairCounter;
-    l.pairs = P;
-    l.epoch = a->epoch;
-    a->pairCounter += P;
-    a->launchSeq++;
-    a->tail = (a->tail + 1) % (int)a->lane.size();
-    a->inFlight++;
+    // (a chunk that read the lone-frame buffer as its previous frame: the buffer is free again behind it)
+    const bool readLone = m.haloIsLone && !c.first;
+    rc = chunk_commit(s, c, l, lc->stream, readLone ? m.loneReadEv : nullptr);
+    if (rc != PS_OK) return rc;
+    if (readLone) m.loneReadPending = true;
+    // the stream's latest frame from now on: the next chunk reads it from this staging slot -- or from the caller's pinned block
+    m.haloDev = fr.dev + (size_t)(n - 1) * a->packStride;
+    m.haloNk = nk[n - 1];
+    m.haloIsLone = false;
     return PS_OK;
 }
 
-int async_submit(PsVoStream *s, const uint8_t *desc, const float *pts, const int32_t *nk, int n)
+// A chunk could not be queued (an allocation or a HIP call failed somewhere between its upload and its download).  Whatever
+// part of it WAS queued is drained -- nothing is in flight on a place that is still marked free --, the chunk's frames are
+// dropped as a unit, and the stream continues as after ps_vo_stream_reset: the next frame has no predecessor, pair numbering
+// restarts at 0, the epoch advances (include/putslam_hip.h).  Chunks submitted before keep their place, numbering and epoch.
+int async_abort_chunk(PsVoStream *s, int rc)
 {
-    const int rc = s->async->mini ? mini_submit_body(s, const_cast<uint8_t *>(desc), nk, n) : async_submit_body(s, desc, pts, nk, n);
+    PsVoAsync *a = s->async;
+    const std::string why = s->ctx->err;
+    if (a->ring.copyStream) (void)hipStreamSynchronize(a->ring.copyStream);
+    PsContext *lc = a->laneCtx.empty() ? nullptr : a->laneCtx[(size_t)a->led.next_lane()];
+    if (lc) (void)hipStreamSynchronize(lc->stream);
+    a->mini.haloDev = nullptr;
+    a->mini.haloIsLone = false;
+    if (a->ring.copyOutStream) (void)hipStreamSynchronize(a->ring.copyOutStream);
+    (void)hipGetLastError();
+    a->led.abort();
+    s->ctx->err = why + " -- pipelined stream: the chunk's frames were dropped; the next frame starts a new epoch (pair numbering from 0)";
+    return rc;
+}
+
+int async_submit(PsVoStream *s, const ChunkFrames &fr, const int32_t *nk, int n)
+{
+    const int rc = s->async->led.mini ? mini_submit_body(s, fr, nk, n) : ring_submit_body(s, fr, nk, n);
     return rc == PS_OK ? PS_OK : async_abort_chunk(s, rc);
 }
 
-int async_submit_body(PsVoStream *s, const uint8_t *desc, const float *pts, const int32_t *nk, int n)
-{
-    PsVoAsync *a = s->async;
-    PsContext *ctx = s->ctx;
-    const size_t cap = (size_t)s->cap;
-    const int pos0 = (a->ringPos + n <= a->ringFrames) ? a->ringPos : 0;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
-    hipEvent_t ev = a->upEv[(size_t)(a->chunkSeq % (long long)a->upEv.size())];
-    a->chunkSeq++;
-    // (a build with -DPS_STREAM_DIAG and PUTSLAM_HIP_STREAM_DIAG_NO_UPLOAD=1 skips the uploads after the first 64 chunks -- the chunks
-    // then run on whatever frames the ring holds and the results are meaningless; it told what the pipeline does when the link
-    // costs nothing, profiles/r05h/stream_limits.txt.  The shipped library does not contain it.)
-#ifdef PS_STREAM_DIAG
-    static const bool diagNoUpload = std::getenv("PUTSLAM_HIP_STREAM_DIAG_NO_UPLOAD") != nullptr;
-    if (!(diagNoUpload && a->chunkSeq > 64))
-#endif
-    {
-        if (a->packed) { // (`desc` = the chunk's packed frames: ONE transfer, no idle link between a descriptor and a point upload)
-            PS_HIP(hipMemcpyAsync((uint8_t *)a->ringDesc.p + (size_t)pos0 * a->packStride, desc, (size_t)n * a->packStride,
-                                  hipMemcpyHostToDevice, a->copyStream));
-        } else {
-            PS_HIP(hipMemcpyAsync((uint8_t *)a->ringDesc.p + (size_t)pos0 * cap * 32, desc, (size_t)n * cap * 32, hipMemcpyHostToDevice,
-                                  a->copyStream));
-            PS_HIP(hipMemcpyAsync((uint8_t *)a->ringPts.p + (size_t)pos0 * cap * 12, pts, (size_t)n * cap * 12, hipMemcpyHostToDevice,
-                                  a->copyStream));
-        }
-    }
-    PS_HIP(hipEventRecord(ev, a->copyStream));
-    for (int i = 0; i < n; ++i) a->nkRing[(size_t)(pos0 + i)] = nk[i];
-    AsyncChunk c;
-    c.pos0 = pos0;
-    c.n = n;
-    c.first = a->prevPos >= 0 ? 0 : 1; // the stream's first frame has no predecessor (matcher.cpp:17-64)
-    c.prevPos = a->prevPos;
-    c.firstPair = a->pairCounter;
-    c.epoch = a->epoch;
-    c.up = ev;
-    const int P = n - c.first;
-    a->ringPos = pos0 + n;
-    a->prevPos = pos0 + n - 1;
-    a->dbgT[0] += now() - t0;
-    if (P <= 0) {
-        // a lone first frame: nothing to run, no lane taken; its staging area (if it came through one) is reused by the
-        // next push, so the upload is waited for here -- and the areas' rotation does not advance: it follows the LAUNCHED chunks
-        // (an area is written again lanes + ahead + 1 launched chunks later, when its own chunk has been popped)
-        PS_HIP(hipStreamSynchronize(a->copyStream));
-        a->chunkSeq--;
-        return PS_OK;
-    }
-    a->pairCounter += P;
-    return async_launch(s, c);
-}
-
+// the frames push_async has collected, as a chunk (its place was reserved when the first of them was taken)
 int async_submit_staged(PsVoStream *s)
 {
     PsVoAsync *a = s->async;
-    if (a->staged == 0) return PS_OK;
-    const size_t cap = (size_t)s->cap;
-    const int n = a->staged;
-    // (the staging area is the one push_async has been filling: that of chunk number chunkSeq)
-    uint8_t *h = nullptr;
-    int rc = stage_area(s, &h);
+    if (a->led.staged == 0) return PS_OK;
+    ChunkFrames area; // (the one push_async has been filling: the next chunk's)
+    int rc = stage_area(s, &area);
     if (rc) return rc;
-    a->staged = 0; // (whatever happens below, these frames are not submitted a second time)
-    return async_submit(s, h, a->packed ? nullptr : reinterpret_cast<const float *>(h + (size_t)a->B * cap * 32), a->stagedNk.data(), n);
+    const int n = a->led.take_staged();
+    return async_submit(s, area, a->stagedNk.data(), n);
+}
+
+// ---- one push path ----
+
+// Frames as a push call names them: base pointers and per-frame strides of the descriptors and the points, row counts.
+struct FrameSource {
+    const uint8_t *desc, *pts;
+    size_t descStride, ptsStride;
+    const int32_t *nk;
+    int frames;
+};
+
+// What a push reads in place -- pinned memory, which the caller leaves untouched until the results of its frames (for a chunk's
+// last frame: of the NEXT pair, which reads it as its previous frame) have been popped -- and not through a staging area:
+//   ring, two arrays                  both pointers pinned (uploaded from there)
+//   ring, packed, fed two arrays      never (the frames are packed on their way through the staging area)
+//   ring, packed, fed packed          pinned
+//   mini                              pinned, packed, contiguous, and a device view of it exists (*dev): the copy-in kernel reads
+//                                     it (88 KB less for the host to copy per 2000-keypoint frame)
+bool reads_in_place(const PsVoStream *s, const FrameSource &src, const uint8_t **dev)
+{
+    const PsVoAsync *a = s->async;
+    const bool fedPacked = src.descStride == a->packStride && src.pts == src.desc + (size_t)s->cap * 32;
+    *dev = nullptr;
+    if (!a->packed) return is_pinned_host(src.desc) && is_pinned_host(src.pts);
+    if (!fedPacked || !is_pinned_host(src.desc)) return false;
+    if (!a->led.mini) return true;
+    if (hipHostGetDevicePointer((void **)dev, const_cast<uint8_t *>(src.desc), 0) == hipSuccess && *dev) return true;
+    (void)hipGetLastError();
+    *dev = nullptr;
+    return false;
+}
+
+// Several frames into the stream (push_many / push_many_packed): frames staged by push_async before go first, as a chunk of
+// their own; these follow in chunks of at most chunkFrames, the last one included -- everything is submitted when the call
+// returns.  All or nothing: a place for every one of those chunks.
+int push_frames(PsVoStream *s, const FrameSource &src, const char *who)
+{
+    PsVoAsync *a = s->async;
+    auto refuse = [&](int code, const char *why) { return async_fail(s, code, (std::string(who) + why).c_str()); }; // (no string on the way through)
+    for (int i = 0; i < src.frames; ++i)
+        if (src.nk[i] < 0 || src.nk[i] > s->cap) return refuse(PS_ERR_BAD_ARG, ": row count out of range");
+    if (src.frames == 0) return PS_OK;
+    if (a->led.chunks_for(src.frames) > a->led.room()) return refuse(PS_ERR_BUSY, ": not enough room for these frames (pop results first, or push fewer)");
+    int rc = async_submit_staged(s);
+    if (rc) return rc;
+    const uint8_t *dev = nullptr;
+    const bool inPlace = reads_in_place(s, src, &dev);
+    for (int f0 = 0; f0 < src.frames; f0 += a->led.B) {
+        const int n = src.frames - f0 < a->led.B ? src.frames - f0 : a->led.B;
+        ChunkFrames fr;
+        if (inPlace) {
+            fr = ChunkFrames{src.desc + (size_t)f0 * src.descStride, reinterpret_cast<const float *>(src.pts + (size_t)f0 * src.ptsStride),
+                             dev ? dev + (size_t)f0 * a->packStride : nullptr, true};
+        } else { // pageable frames, or another layout than the stream's: through the chunk's pinned staging area, frame by frame
+            rc = stage_area(s, &fr);
+            if (rc) return rc;
+            for (int i = 0; i < n; ++i)
+                stage_frame(s, fr, i, src.desc + (size_t)(f0 + i) * src.descStride, PS_DESC_BYTES, src.pts + (size_t)(f0 + i) * src.ptsStride,
+                            src.nk[f0 + i]);
+        }
+        rc = async_submit(s, fr, src.nk + f0, n);
+        if (rc) return rc;
+    }
+    return PS_OK;
 }
 
 // device / pinned blocks, streams, events and lane contexts of a freshly configured pipeline
-int async_build(PsVoStream *s)
+int async_build(PsVoStream *s, int chunkFrames, int lanes, int ahead)
 {
     PsVoAsync *a = s->async;
+    AsyncRing &r = a->ring;
     PsContext *ctx = s->ctx;
-    const size_t cap = (size_t)s->cap, B = (size_t)a->B;
-    a->offMask = B * cap * sizeof(PsDMatch);
-    a->offPose = a->offMask + ((B * cap + 63) & ~(size_t)63);
-    a->offStats = a->offPose + B * 64;
-    a->offNum = a->offStats + ((B * sizeof(PsRansacStats) + 63) & ~(size_t)63);
-    a->resBytes = a->offNum + B * sizeof(int32_t);
-    a->nkRing.assign((size_t)a->ringFrames, 0);
+    const size_t cap = (size_t)s->cap, B = (size_t)chunkFrames;
+    // small chunks as one graph per place (AsyncMini); PUTSLAM_HIP_STREAM_MINI=0 keeps round 5's form for them (A/B, tests)
+    const char *m = std::getenv("PUTSLAM_HIP_STREAM_MINI");
+    a->led.configure(chunkFrames, lanes, ahead, chunkFrames <= psdev::kMiniFrames && !(m && std::atoi(m) == 0));
+    const char *g = std::getenv("PUTSLAM_HIP_STREAM_GRAPH");
+    a->mini.graphs = g && std::atoi(g) != 0;
+    a->res = ResLayout(B, cap);
     a->stagedNk.assign(B, 0);
-    a->upEv.assign((size_t)(a->lanes + a->ahead + 1), nullptr);
-    a->stagePool.assign((size_t)(a->lanes + a->ahead + 1), nullptr);
-    for (hipEvent_t &e : a->upEv) PS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    a->packed = s->asyncFrameLayout == PS_FRAMES_PACKED;
+    a->stagePool.assign((size_t)a->led.areas(), nullptr);
+    a->packed = a->led.mini || s->asyncFrameLayout == PS_FRAMES_PACKED;
     a->packStride = (cap * 44 + 15) & ~(size_t)15;
-    {
-        // small chunks as one graph per place (PsVoAsync::mini); PUTSLAM_HIP_STREAM_MINI=0 keeps round 5's form for them (A/B, tests)
-        const char *m = std::getenv("PUTSLAM_HIP_STREAM_MINI");
-        a->mini = a->B <= psdev::kMiniFrames && !(m && std::atoi(m) == 0);
-        const char *g = std::getenv("PUTSLAM_HIP_STREAM_GRAPH");
-        a->miniGraphs = g && std::atoi(g) != 0;
-    }
-    if (a->mini) {
-        a->packed = true; // (the staging areas: one block per frame, as the copy-in kernel reads them)
-        a->laneWarmGen.assign((size_t)a->lanes, 0);
-        a->stagePoolDev.assign(a->stagePool.size(), nullptr);
-        a->viewBuf.assign((a->resBytes + 15) & ~(size_t)15, 0);
-    } else if (a->packed) {
-        PS_ENSURE(a->ringDesc, (size_t)a->ringFrames * a->packStride);
+    if (a->led.mini) {
+        a->mini.laneWarmGen.assign((size_t)lanes, 0);
+        a->mini.stagePoolDev.assign(a->stagePool.size(), nullptr);
+        a->mini.viewBuf.assign(a->res.alloc_bytes(), 0);
     } else {
-        PS_ENSURE(a->ringDesc, (size_t)a->ringFrames * cap * 32);
-        PS_ENSURE(a->ringPts, (size_t)a->ringFrames * cap * 12);
+        const size_t ringFrames = (size_t)a->led.ringFrames;
+        r.nk.assign(ringFrames, 0);
+        r.upEv.assign(a->stagePool.size(), nullptr);
+        for (hipEvent_t &e : r.upEv) PS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        PS_ENSURE(r.desc, a->packed ? ringFrames * a->packStride : ringFrames * cap * 32);
+        if (!a->packed) PS_ENSURE(r.pts, ringFrames * cap * 12);
+        PS_HIP(hipHostMalloc((void **)&r.spareHres, a->res.alloc_bytes(), hipHostMallocDefault));
+        PS_HIP(hipHostGetDevicePointer((void **)&r.spareHresDev, r.spareHres, 0));
     }
-    PS_HIP(hipStreamCreateWithFlags(&a->copyStream, hipStreamNonBlocking));
-    PS_HIP(hipStreamCreateWithFlags(&a->copyOutStream, hipStreamNonBlocking));
+    // (mini streams create the two copy streams too and leave them idle: the process's streams meet its hardware queues in the
+    // order measured)
+    PS_HIP(hipStreamCreateWithFlags(&r.copyStream, hipStreamNonBlocking));
+    PS_HIP(hipStreamCreateWithFlags(&r.copyOutStream, hipStreamNonBlocking));
     // A stream of its own for the downloads pays only when it also gets a hardware queue of its own: with the runtime's
     // default of four queues (or eight shared with the host's other streams) it lands on a lane's or the upload stream's queue
     // and serialises with it -- 130 k instead of 390 k frame-pairs/s in bench.py's process (profiles/r05f/hw_queues.txt).  The
@@ -740,12 +737,10 @@ int async_build(PsVoStream *s)
     {
         int queues = 4; // (ROCclr's default)
         if (const char *q = std::getenv("GPU_MAX_HW_QUEUES")) queues = std::atoi(q);
-        a->downloadsOnLane = queues < a->lanes + 6;
+        r.downloadsOnLane = queues < lanes + 6;
     }
-    if (const char *v = std::getenv("PUTSLAM_HIP_STREAM_DOWNLOADS_ON_LANE")) a->downloadsOnLane = std::atoi(v) != 0;
-    PS_HIP(hipHostMalloc((void **)&a->spareHres, (a->resBytes + 15) & ~(size_t)15, hipHostMallocDefault));
-    PS_HIP(hipHostGetDevicePointer((void **)&a->spareHresDev, a->spareHres, 0));
-    a->laneCtx.assign((size_t)a->lanes, nullptr);
+    if (const char *v = std::getenv("PUTSLAM_HIP_STREAM_DOWNLOADS_ON_LANE")) r.downloadsOnLane = std::atoi(v) != 0;
+    a->laneCtx.assign((size_t)lanes, nullptr);
     for (PsContext *&c : a->laneCtx) {
         int rc = ps_context_create(ctx->device, &c);
         if (rc != PS_OK) {
@@ -758,16 +753,16 @@ int async_build(PsVoStream *s)
         // three lanes, E1 / fixed / H = 4096: complete 204 k / 251 k, staged 156 k / 301 k frame-pairs/s, profiles/r06u/stream_small_chunks.txt)
         // (the decision is the stream's own: below 48 frames per chunk the lanes run as lone contexts whatever the stream's context says)
         if (B < 48) c->sideBySide = 0;
-        else if (a->lanes > 1 && c->sideBySide < a->lanes) c->sideBySide = a->lanes;
+        else if (lanes > 1 && c->sideBySide < lanes) c->sideBySide = lanes;
     }
-    a->lane.resize((size_t)(a->lanes + a->ahead));
-    const size_t metaBytes = std::max(((size_t)2 * B + a->ringFrames) * sizeof(int32_t), sizeof(psdev::MiniMeta));
+    a->lane.resize((size_t)a->led.places());
+    const size_t metaBytes = std::max(((size_t)2 * B + a->led.ringFrames) * sizeof(int32_t), sizeof(psdev::MiniMeta));
     for (AsyncLane &l : a->lane) {
-        if (a->mini) PS_ENSURE(l.frames, (B + 1) * a->packStride);
+        if (a->led.mini) PS_ENSURE(l.frames, (B + 1) * a->packStride);
         PS_ENSURE(l.meta, metaBytes);
-        PS_ENSURE(l.res, (a->resBytes + 15) & ~(size_t)15);
+        PS_ENSURE(l.res, a->res.alloc_bytes());
         PS_HIP(hipHostMalloc((void **)&l.hmeta, metaBytes, hipHostMallocDefault));
-        PS_HIP(hipHostMalloc((void **)&l.hres, (a->resBytes + 15) & ~(size_t)15, hipHostMallocDefault));
+        PS_HIP(hipHostMalloc((void **)&l.hres, a->res.alloc_bytes(), hipHostMallocDefault));
         PS_HIP(hipHostGetDevicePointer((void **)&l.hmetaDev, l.hmeta, 0));
         PS_HIP(hipHostGetDevicePointer((void **)&l.hresDev, l.hres, 0));
         PS_HIP(hipEventCreateWithFlags(&l.evRun, hipEventDisableTiming));
@@ -778,58 +773,24 @@ int async_build(PsVoStream *s)
 
 void release_view(PsVoAsync *a)
 {
-    if (a->heldHres) { // the block goes back to being the spare one
-        a->spareHres = a->heldHres;
-        a->spareHresDev = a->heldHresDev;
-        a->heldHres = a->heldHresDev = nullptr;
+    AsyncRing &r = a->ring;
+    if (r.heldHres) { // the block goes back to being the spare one
+        r.spareHres = r.heldHres;
+        r.spareHresDev = r.heldHresDev;
+        r.heldHres = r.heldHresDev = nullptr;
     }
     a->cursor = 0;
     a->haveView = false;
     memset(&a->view, 0, sizeof a->view);
 }
 
-// Several frames into a stream of mini chunks (push_many / push_many_packed), with push_many's contract: frames staged by
-// push_async before go first, as a chunk of their own; these frames follow in chunks of at most chunkFrames, the last one
-// included -- everything is submitted when the call returns.  All or nothing: a place for every one of those chunks.
-int mini_push_frames(PsVoStream *s, const uint8_t *desc, size_t descStride, const uint8_t *pts, size_t ptsStride, const int32_t *nkpts, int numFrames)
+// what every push call checks first: the stream, its device, that the pipeline is configured
+int push_enter(PsVoStream *s, const char *who)
 {
-    PsVoAsync *a = s->async;
-    const size_t cap = (size_t)s->cap;
-    const int need = (a->staged > 0 ? 1 : 0) + (numFrames + a->B - 1) / a->B;
-    if (need > async_room(a)) return async_fail(s, PS_ERR_BUSY, "ps_vo_stream_push_many: not enough room for these frames (pop results first, or push fewer)");
-    int rc = async_submit_staged(s);
+    if (!s) return PS_ERR_BAD_ARG;
+    int rc = bind(s->ctx);
     if (rc) return rc;
-    // Pinned packed frames are read in place by the copy-in kernel (88 KB less for the host to copy per 2000-keypoint frame): as
-    // with the ring form they stay untouched until the results of their frames -- for a chunk's last frame: of the NEXT pair,
-    // which reads it as its previous frame -- have been popped.
-    if (descStride == a->packStride && pts == desc + cap * 32 && is_pinned_host(desc)) {
-        uint8_t *dev = nullptr;
-        if (hipHostGetDevicePointer((void **)&dev, const_cast<uint8_t *>(desc), 0) == hipSuccess && dev) {
-            for (int f0 = 0; f0 < numFrames; f0 += a->B) {
-                const int n = numFrames - f0 < a->B ? numFrames - f0 : a->B;
-                a->inPlaceDev = dev + (size_t)f0 * a->packStride;
-                rc = async_submit(s, desc + (size_t)f0 * a->packStride, nullptr, nkpts + f0, n);
-                a->inPlaceDev = nullptr;
-                if (rc) return rc;
-            }
-            return PS_OK;
-        }
-        (void)hipGetLastError();
-    }
-    for (int f = 0; f < numFrames; ++f) {
-        uint8_t *h = nullptr;
-        rc = stage_area(s, &h);
-        if (rc) return rc;
-        uint8_t *hd = h + (size_t)a->staged * a->packStride;
-        memcpy(hd, desc + (size_t)f * descStride, (size_t)nkpts[f] * 32);
-        memcpy(hd + cap * 32, pts + (size_t)f * ptsStride, (size_t)nkpts[f] * 12);
-        a->stagedNk[(size_t)a->staged] = nkpts[f];
-        a->staged++;
-        if (a->staged == a->B || f == numFrames - 1) {
-            rc = async_submit_staged(s);
-            if (rc) return rc;
-        }
-    }
+    if (!s->async) return async_fail(s, PS_ERR_BAD_ARG, (std::string(who) + ": call ps_vo_stream_configure_async first").c_str());
     return PS_OK;
 }
 
@@ -845,16 +806,11 @@ static void async_release(PsVoStream *s)
 
 static int async_reset(PsVoStream *s)
 {
-    PsVoAsync *a = s->async;
     int rc = bind(s->ctx);
     if (rc) return rc;
-    if (a->staged > 0) { // (its place was reserved when push_async took the chunk's first frame)
-        rc = async_submit_staged(s);
-        if (rc) return rc;
-    }
-    a->prevPos = -1;
-    a->pairCounter = 0;
-    a->epoch++;
+    rc = async_submit_staged(s); // (its place was reserved when push_async took the chunk's first frame)
+    if (rc) return rc;
+    s->async->led.reset();
     return PS_OK;
 }
 
@@ -874,7 +830,7 @@ int ps_vo_stream_configure_async(PsVoStream *s, const PsRansacParams *params, co
     // three lanes): chunks of a hundred frames and more fill the chip by themselves and run best as TWO launch chains with ONE more
     // chunk queued behind them -- 417 / 504 / 550 k frame-pairs/s at 125 / 250 / 500 frames per chunk against 398 / 474 / 445 k
     // with six places -- the same finding as the batch queue's (whole batches to two chains in turn); chunks of 48 .. 95 frames two
-    // lanes and four places; smaller ones three lanes and six places; one to four frames six lanes (PsVoAsync::mini).
+    // lanes and four places; smaller ones three lanes and six places; one to four frames six lanes (AsyncMini).
     if (lanes == 0) lanes = chunkFrames >= 48 ? 2 : (chunkFrames > psdev::kMiniFrames ? 3 : 6);
     if (chunkFrames < 1 || chunkFrames > 1024 || lanes < 2 || lanes > 8)
         return fail(ctx, PS_ERR_BAD_ARG, "ps_vo_stream_configure_async: chunkFrames 1..1024, lanes 2..8");
@@ -890,17 +846,14 @@ int ps_vo_stream_configure_async(PsVoStream *s, const PsRansacParams *params, co
     }
     PsVoAsync *a = new PsVoAsync();
     s->async = a;
-    a->B = chunkFrames;
-    a->lanes = lanes;
-    a->ahead = ctx->streamAhead >= 0 ? ctx->streamAhead : (chunkFrames >= 96 ? 1 : (chunkFrames >= 48 ? 2 : (lanes < 6 ? 6 - lanes : 0)));
-    a->ringFrames = (lanes + a->ahead + 2) * chunkFrames;
     a->prm = *params;
     a->cfg = *cfg;
     a->cfg.sampleIdx = nullptr;
     a->haveK = K != nullptr;
     if (K) memcpy(a->K, K, sizeof a->K);
     a->resultMode = s->asyncResultMode;
-    rc = async_build(s);
+    rc = async_build(s, chunkFrames, lanes,
+                     ctx->streamAhead >= 0 ? ctx->streamAhead : (chunkFrames >= 96 ? 1 : (chunkFrames >= 48 ? 2 : (lanes < 6 ? 6 - lanes : 0))));
     if (rc != PS_OK) { // (the error text stays in the stream's context)
         const std::string why = ctx->err;
         async_free(a);
@@ -920,93 +873,37 @@ int ps_vo_stream_set_result_mode(PsVoStream *s, int mode)
 
 int ps_vo_stream_push_async(PsVoStream *s, const uint8_t *desc, size_t descStep, const float *pts, int n)
 {
-    if (!s) return PS_ERR_BAD_ARG;
-    int rc = bind(s->ctx);
+    int rc = push_enter(s, "ps_vo_stream_push_async");
     if (rc) return rc;
     PsVoAsync *a = s->async;
-    if (!a) return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_push_async: call ps_vo_stream_configure_async first");
     if (n < 0 || n > s->cap || (n > 0 && (!desc || !pts)) || descStep < PS_DESC_BYTES)
         return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_push_async: bad argument");
     // (the first frame of a chunk reserves the chunk's place; the later ones ride on it)
-    if (a->staged == 0 && async_room(a) < 1) return async_fail(s, PS_ERR_BUSY, "ps_vo_stream_push_async: no room (pop results first)");
-    uint8_t *h = nullptr;
-    rc = stage_area(s, &h);
+    if (a->led.staged == 0 && a->led.room() < 1) return async_fail(s, PS_ERR_BUSY, "ps_vo_stream_push_async: no room (pop results first)");
+    ChunkFrames area;
+    rc = stage_area(s, &area);
     if (rc) return rc;
-    const size_t cap = (size_t)s->cap;
-    uint8_t *hd = a->packed ? h + (size_t)a->staged * a->packStride : h + (size_t)a->staged * cap * 32;
-    uint8_t *hp = a->packed ? hd + cap * 32 : h + (size_t)a->B * cap * 32 + (size_t)a->staged * cap * 12;
-    if (descStep == PS_DESC_BYTES) {
-        if (n > 0) memcpy(hd, desc, (size_t)n * 32);
-    } else {
-        for (int i = 0; i < n; ++i) memcpy(hd + (size_t)i * 32, desc + (size_t)i * descStep, 32);
-    }
-    if (n > 0) memcpy(hp, pts, (size_t)n * 12);
-    a->stagedNk[(size_t)a->staged] = n;
-    a->staged++;
-    if (a->staged == a->B) return async_submit_staged(s);
+    stage_frame(s, area, a->led.staged, desc, descStep, pts, n);
+    a->stagedNk[(size_t)a->led.staged] = n;
+    if (a->led.stage_one() == a->led.B) return async_submit_staged(s);
     return PS_OK;
 }
 
 int ps_vo_stream_flush(PsVoStream *s)
 {
-    if (!s) return PS_ERR_BAD_ARG;
-    int rc = bind(s->ctx);
+    int rc = push_enter(s, "ps_vo_stream_flush");
     if (rc) return rc;
-    PsVoAsync *a = s->async;
-    if (!a) return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_flush: call ps_vo_stream_configure_async first");
     return async_submit_staged(s); // (the partly filled chunk's place was reserved by its first frame)
 }
 
 int ps_vo_stream_push_many(PsVoStream *s, const uint8_t *desc, const float *pts, const int32_t *nkpts, int numFrames)
 {
-    if (!s) return PS_ERR_BAD_ARG;
-    int rc = bind(s->ctx);
+    int rc = push_enter(s, "ps_vo_stream_push_many");
     if (rc) return rc;
-    PsVoAsync *a = s->async;
-    if (!a) return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_push_many: call ps_vo_stream_configure_async first");
     if (numFrames < 0 || (numFrames > 0 && (!desc || !pts || !nkpts)))
         return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_push_many: bad argument");
-    for (int i = 0; i < numFrames; ++i)
-        if (nkpts[i] < 0 || nkpts[i] > s->cap) return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_push_many: row count out of range");
-    if (numFrames == 0) return PS_OK;
-    if (a->mini) return mini_push_frames(s, desc, (size_t)s->cap * 32, reinterpret_cast<const uint8_t *>(pts), (size_t)s->cap * 12, nkpts, numFrames);
-    // places needed: one for the frames push_async has staged, one per chunk of these frames -- all or nothing
-    const int chunks = (numFrames + a->B - 1) / a->B;
-    const int need = chunks + (a->staged > 0 ? 1 : 0);
-    if (need > async_room(a))
-        return async_fail(s, PS_ERR_BUSY, "ps_vo_stream_push_many: not enough room for these frames (pop results first, or push fewer)");
-    rc = async_submit_staged(s);
-    if (rc) return rc;
     const size_t cap = (size_t)s->cap;
-    // pinned frames are uploaded in place; pageable ones go through the lane's pinned staging area first
-    const bool inPlace = !a->packed && is_pinned_host(desc) && is_pinned_host(pts);
-    for (int f0 = 0; f0 < numFrames; f0 += a->B) {
-        const int n = numFrames - f0 < a->B ? numFrames - f0 : a->B;
-        const uint8_t *d = desc + (size_t)f0 * cap * 32;
-        const float *p = pts + (size_t)f0 * cap * 3;
-        if (a->packed) { // two host arrays into a packed ring: through the staging area, frame by frame
-            uint8_t *h = nullptr;
-            rc = stage_area(s, &h);
-            if (rc) return rc;
-            for (int i = 0; i < n; ++i) {
-                memcpy(h + (size_t)i * a->packStride, d + (size_t)i * cap * 32, (size_t)nkpts[f0 + i] * 32);
-                memcpy(h + (size_t)i * a->packStride + cap * 32, p + (size_t)i * cap * 3, (size_t)nkpts[f0 + i] * 12);
-            }
-            d = h;
-            p = nullptr;
-        } else if (!inPlace) {
-            uint8_t *h = nullptr;
-            rc = stage_area(s, &h);
-            if (rc) return rc;
-            memcpy(h, d, (size_t)n * cap * 32);
-            memcpy(h + (size_t)a->B * cap * 32, p, (size_t)n * cap * 12);
-            d = h;
-            p = reinterpret_cast<const float *>(h + (size_t)a->B * cap * 32);
-        }
-        rc = async_submit(s, d, p, nkpts + f0, n);
-        if (rc) return rc;
-    }
-    return PS_OK;
+    return push_frames(s, FrameSource{desc, reinterpret_cast<const uint8_t *>(pts), cap * 32, cap * 12, nkpts, numFrames}, "ps_vo_stream_push_many");
 }
 
 int ps_vo_stream_set_frame_layout(PsVoStream *s, int layout)
@@ -1022,41 +919,15 @@ size_t ps_vo_stream_packed_stride(const PsVoStream *s) { return s ? (((size_t)s-
 
 int ps_vo_stream_push_many_packed(PsVoStream *s, const uint8_t *frames, size_t frameStride, const int32_t *nkpts, int numFrames)
 {
-    if (!s) return PS_ERR_BAD_ARG;
-    int rc = bind(s->ctx);
+    int rc = push_enter(s, "ps_vo_stream_push_many_packed");
     if (rc) return rc;
     PsVoAsync *a = s->async;
-    if (!a) return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_push_many_packed: call ps_vo_stream_configure_async first");
     if (!a->packed)
         return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_push_many_packed: the stream was configured for two arrays (ps_vo_stream_set_frame_layout "
                                              "before ps_vo_stream_configure_async)");
     if (numFrames < 0 || (numFrames > 0 && (!frames || !nkpts)) || frameStride != a->packStride)
         return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_push_many_packed: bad argument (frameStride must be ps_vo_stream_packed_stride())");
-    for (int i = 0; i < numFrames; ++i)
-        if (nkpts[i] < 0 || nkpts[i] > s->cap) return async_fail(s, PS_ERR_BAD_ARG, "ps_vo_stream_push_many_packed: row count out of range");
-    if (numFrames == 0) return PS_OK;
-    if (a->mini) return mini_push_frames(s, frames, a->packStride, frames + (size_t)s->cap * 32, a->packStride, nkpts, numFrames);
-    const int chunks = (numFrames + a->B - 1) / a->B;
-    const int need = chunks + (a->staged > 0 ? 1 : 0);
-    if (need > async_room(a))
-        return async_fail(s, PS_ERR_BUSY, "ps_vo_stream_push_many_packed: not enough room for these frames (pop results first, or push fewer)");
-    rc = async_submit_staged(s);
-    if (rc) return rc;
-    const bool inPlace = is_pinned_host(frames);
-    for (int f0 = 0; f0 < numFrames; f0 += a->B) {
-        const int n = numFrames - f0 < a->B ? numFrames - f0 : a->B;
-        const uint8_t *d = frames + (size_t)f0 * a->packStride;
-        if (!inPlace) {
-            uint8_t *h = nullptr;
-            rc = stage_area(s, &h);
-            if (rc) return rc;
-            memcpy(h, d, (size_t)n * a->packStride);
-            d = h;
-        }
-        rc = async_submit(s, d, nullptr, nkpts + f0, n);
-        if (rc) return rc;
-    }
-    return PS_OK;
+    return push_frames(s, FrameSource{frames, frames + (size_t)s->cap * 32, a->packStride, a->packStride, nkpts, numFrames}, "ps_vo_stream_push_many_packed");
 }
 
 int ps_vo_stream_pop_many(PsVoStream *s, int wait, PsHostPairResults *out)
@@ -1069,10 +940,11 @@ int ps_vo_stream_pop_many(PsVoStream *s, int wait, PsHostPairResults *out)
     release_view(a);
     memset(out, 0, sizeof *out);
     out->maxKpts = s->cap;
-    if (a->inFlight == 0) return PS_OK;
-    AsyncLane &l = a->lane[(size_t)a->head];
+    if (a->led.inFlight == 0) return PS_OK;
+    AsyncLane &l = a->lane[(size_t)a->led.head];
     if (wait) {
-        PSA_HIP(hipEventSynchronize(l.evDone));
+        hipError_t e = hipEventSynchronize(l.evDone);
+        if (e != hipSuccess) return async_fail(s, PS_ERR_HIP, "hipEventSynchronize(l.evDone)", e);
     } else {
         hipError_t q = hipEventQuery(l.evDone);
         if (q == hipErrorNotReady) {
@@ -1081,37 +953,30 @@ int ps_vo_stream_pop_many(PsVoStream *s, int wait, PsHostPairResults *out)
         }
         if (q != hipSuccess) return async_fail(s, PS_ERR_HIP, "hipEventQuery", q);
     }
+    const psledger::Place done = a->led.pop();
     uint8_t *blk = l.hres;
-    if (a->mini) {
+    if (a->led.mini) {
         // a mini chunk's results are a few tens of KB: copied out, so that the place keeps its pinned block (its graph writes
         // there) and is free at once
-        const size_t p = (size_t)l.pairs, cap = (size_t)s->cap;
-        blk = a->viewBuf.data();
-        if (a->resultMode != PS_RESULTS_POSES) memcpy(blk, l.hres, p * cap * sizeof(PsDMatch));
-        if (a->resultMode == PS_RESULTS_FULL) memcpy(blk + a->offMask, l.hres + a->offMask, p * cap);
-        memcpy(blk + a->offPose, l.hres + a->offPose, p * 64);
-        memcpy(blk + a->offStats, l.hres + a->offStats, p * sizeof(PsRansacStats));
-        memcpy(blk + a->offNum, l.hres + a->offNum, p * sizeof(int32_t));
+        blk = a->mini.viewBuf.data();
+        ResLayout::Seg seg[5];
+        a->res.segments((size_t)done.pairs, 1, seg);
+        for (int k = 0; k < 5; ++k) // (the matches unless poses only, the mask only with full results)
+            if (k >= 2 || (k == 0 ? a->resultMode != PS_RESULTS_POSES : a->resultMode == PS_RESULTS_FULL))
+                memcpy(blk + seg[k].off, l.hres + seg[k].off, seg[k].bytes);
     } else {
         // the lane's block becomes the held one, the spare one the lane's: the lane is free now
-        a->heldHres = l.hres;
-        a->heldHresDev = l.hresDev;
-        l.hres = a->spareHres;
-        l.hresDev = a->spareHresDev;
-        a->spareHres = a->spareHresDev = nullptr;
+        AsyncRing &r = a->ring;
+        r.heldHres = l.hres;
+        r.heldHresDev = l.hresDev;
+        l.hres = r.spareHres;
+        l.hresDev = r.spareHresDev;
+        r.spareHres = r.spareHresDev = nullptr;
     }
-    out->matches = a->resultMode == PS_RESULTS_POSES ? nullptr : (const PsDMatch *)blk;
-    out->inlierMask = a->resultMode == PS_RESULTS_FULL ? blk + a->offMask : nullptr;
-    out->resultMode = a->resultMode;
-    out->pose = (const float *)(blk + a->offPose);
-    out->stats = (const PsRansacStats *)(blk + a->offStats);
-    out->numMatches = (const int32_t *)(blk + a->offNum);
-    out->firstPair = l.firstPair;
-    out->count = l.pairs;
-    out->epoch = l.epoch;
-    l.state = 0;
-    a->head = (a->head + 1) % (int)a->lane.size();
-    a->inFlight--;
+    a->res.host(blk, a->resultMode, out);
+    out->firstPair = done.firstPair;
+    out->count = done.pairs;
+    out->epoch = done.epoch;
     a->view = *out;
     a->haveView = true;
     return PS_OK;
@@ -1156,18 +1021,13 @@ int ps_vo_stream_pending(const PsVoStream *s)
 {
     if (!s || !s->async) return PS_ERR_BAD_ARG;
     const PsVoAsync *a = s->async;
-    int n = 0;
-    for (const AsyncLane &l : a->lane)
-        if (l.state == 1) n += l.pairs;
-    if (a->haveView) n += a->view.count - a->cursor;
-    if (a->staged > 0) n += a->staged - (a->prevPos >= 0 ? 0 : 1);
-    return n;
+    return a->led.pending() + (a->haveView ? a->view.count - a->cursor : 0);
 }
 
 long long ps_vo_stream_graph_launches(const PsVoStream *s)
 {
     if (!s) return PS_ERR_BAD_ARG;
-    return s->graphLaunches + (s->async ? s->async->graphLaunches : 0);
+    return s->graphLaunches + (s->async ? s->async->mini.graphLaunches : 0);
 }
 
 void *ps_host_alloc(size_t bytes)

@@ -2,7 +2,10 @@
 built with -DPS_STREAM_DIAG (PUTSLAM_HIP_LIB names it) whose N-th chunk fails -- before its batched call has queued anything
 (PUTSLAM_HIP_STREAM_DIAG_FAIL_CHUNK) or behind it (..._FAIL_AFTER).  What the header promises: the failing push returns an
 error, the chunk's frames are dropped as a unit, no place is lost, and the stream goes on in a new epoch whose pair numbering
-(= hypothesis seeds) starts at 0.  Everything popped is compared with the oracle.  Exit code 0 = all of that held."""
+(= hypothesis seeds) starts at 0.  Everything popped is compared with the oracle (= the batched call's bytes).  The new epoch
+begins with chunks of one and two frames, more of them than there are staging areas and popped only when the pipeline is full:
+the areas rotate with the chunks that were launched, so the failed one must not have moved the rotation -- one step ahead, a
+chunk would be staged over the frame a chunk in flight still reads as its previous one.  Exit code 0 = all of that held."""
 import os
 import sys
 
@@ -25,8 +28,10 @@ def main():
     prm = default_ransac_params(REPROJECTION_ERROR)
     cfg, _ = make_config(EST_FIXED, 512, seed=0xFA17)
     ctx = api.Context(0)
-    st = api.VoStream(ctx, 500)
+    st = api.VoStream(ctx, 600)
     st.configure_async(prm, cfg, TUM_FR1_K, chunk_frames=B, lanes=2)
+    places = 6                                         # two lanes -> four more places ahead
+    small = [1] + [1, 2] * ((places + 2 + 1) // 2)     # after the failure: a lone first frame, then lanes + ahead + 2 small chunks
     blocks, failed_at_frame = [], None
     f = 0
     while f < F:
@@ -44,6 +49,12 @@ def main():
             blocks.append(blk)
             continue
         f += 1
+        if failed_at_frame is not None and small:
+            small[0] -= 1
+            if small[0] == 0:
+                small.pop(0)
+                st.flush()
+    assert not small
     st.flush()
     while True:
         blk = st.pop_many(wait=True)
@@ -68,11 +79,11 @@ def main():
     assert got == {0: max(lost_lo - 1, 0), 1: n1 - 1}, got
     # no place was lost: the pipeline still takes its full complement of chunks without a pop (two lanes -> six places)
     taken = 0
-    for k in range(6 * B):
+    for k in range(places * B):
         if not st.push_async(seq["desc"][k % F], seq["pts"][k % F]):
             break
         taken += 1
-    assert taken == 6 * B, taken
+    assert taken == places * B, taken
     st.close()
     ctx.close()
     print("ok: chunk %d failed, frames [%d, %d) dropped, %d + %d pairs equal the oracle" % (fail_at, lost_lo, lost_hi, got[0], got[1]))
