@@ -1771,6 +1771,89 @@ int ps_debug_track_close_passes(PsContext *ctx, PsTrackClose *tc, const PsOrbPyr
                                 const PsTrackedRows *tracked, const PsTrackCandidates *cand, const int32_t *candFrame, int P, int capacity,
                                 int outCapacity, const PsTrackCloseOut *out, int passes);
 
+/* ---- Sub-pixel matching on patches: MatchingOnPatches (include/putslam/Matcher/MatchingOnPatches.h,
+ * src/Matcher/MatchingOnPatches.cpp:14-246; configured by MatcherParameters::PatchesParams, matcher.h:295-304,362) -- the
+ * Gauss-Newton alignment of a feature's patch from an old image in a new one.  Restated sequentially in tests/patches_ref.py;
+ * every output is byte for byte the restatement's.  Eigen's Matrix3f::inverse(), its lazy 3 x 3 products
+ * and cv::cvtColor are RESTATED, not compiled against the libraries: that reading is unpinned.
+ * With h = (patchSize - 1) / 2, E = patchSize^2, element k running over rows i = int(y) - h .. int(y) + h and inside a row over
+ * j = int(x) - h .. int(x) + h (int() truncates), I the grey image (one channel as it is, three by CV_RGB2GRAY: (c0 4899 +
+ * c1 9617 + c2 1868 + 8192) >> 14), no multiply-add contracted:
+ *   patch (:14-51), double: xs = x - int(x), ys = y - int(y); tl = (1-xs)(1-ys), tr = xs(1-ys), bl = (1-xs)ys, br = xs ys;
+ *     patch[k] = ((tl I[i][j] + tr I[i][j+1]) + bl I[i+1][j]) + br I[i+1][j+1].
+ *   gradient (:53-99), float: gx[k] = 0.5f (float)(I[i][j+1] - I[i][j-1]), gy[k] = 0.5f (float)(I[i+1][j] - I[i-1][j]), J = (gx, gy,
+ *     1.f); H[a][b] += J[a] J[b] in k order from zero; invHessian = H^-1 by cof(i, j) = m(i1, j1) m(i2, j2) - m(i1, j2) m(i2, j1),
+ *     det = (cof(0,0) m(0,0) + cof(1,0) m(1,0)) + cof(2,0) m(2,0), result(i, j) = cof(j, i) x (1.f / det); a zero determinant takes
+ *     its IEEE course (NaN).  Row-major, 9 floats.
+ *   alignment (:101-200): NaN invHessian[0] fails at once.  From (newX, newY), mean = 0.0, for up to maxIter steps: the gate
+ *     isnan(newX) || isnan(newY) || newX < h || newX > cols - h || newY < h || newY > rows - h; the patch at (newX, newY); in k
+ *     order diff = (float)((newPatch[k] - patch[k]) + mean), t0 -= diff gx[k], t1 -= diff gy[k], t2 -= diff (floats from 0.f);
+ *     inc_r = (Inv[r][0] t0 + Inv[r][1] t1) + Inv[r][2] t2 for r = 0, 1; newX += (double)inc0, newY += (double)inc1; if
+ *     (double)(inc0 inc0 + inc1 inc1) < minSqrtIncrement the point stops: moved too far if its squared distance from the start
+ *     exceeds h h, else converged.
+ * Two places where the reference reads outside its images are decided here: an OLD position must be finite with every tap inside
+ * (int(x) - h - 1 >= 0, int(x) + h + 1 <= cols - 1, the same for y), else status 5; a NEW position that passes the gate while
+ * int(newX) + h + 1 > cols - 1 or int(newY) + h + 1 > rows - 1 gets status 6.  `warping` (parsed, read nowhere) is not carried;
+ * the narration to std::cout is not reproduced. */
+enum {
+    PS_PATCH_MAX_ITERATIONS = 0,    /* "Maximum iterations reached" (:193) */
+    PS_PATCH_CONVERGED = 1,         /* the reference's true (:187) */
+    PS_PATCH_NAN_HESSIAN = 2,       /* isnan(InvHessian(0,0)) (:108); position untouched */
+    PS_PATCH_OUT_OF_IMAGE = 3,      /* the reference's gate (:139-154) */
+    PS_PATCH_MOVED_TOO_FAR = 4,     /* (:176-180) */
+    PS_PATCH_OLD_TAPS_OUTSIDE = 5,  /* this build: the old position's taps leave the old image, or a slot outside the set; position untouched */
+    PS_PATCH_NEW_TAPS_OUTSIDE = 6   /* this build: the gate passed but the taps leave the new image */
+};
+enum { PS_PATCH_GIVEN_MODEL = 1 };  /* ps_patch_align reads the model arrays instead of building them from the old image */
+typedef struct PsPatchParams {
+    double minSqrtIncrement;     /* PatchesParams.minSqrtIncrement (the XML's minSqrtError) */
+    int32_t patchSize;           /* odd, 3 .. 31 */
+    int32_t maxIter;             /* 0 .. 1000 */
+    int32_t flags;               /* PS_PATCH_GIVEN_MODEL */
+    int32_t reserved;            /* 0 */
+} PsPatchParams;
+typedef struct PsPatchModel {    /* DEVICE pointers, P x capacity points each; NULL = not wanted */
+    double *patch;               /* x E */
+    float *gx, *gy;              /* x E */
+    float *invHessian;           /* x 9, row-major */
+} PsPatchModel;
+size_t ps_abi_sizeof_patch_params(void);
+size_t ps_abi_sizeof_patch_model(void);
+
+/* computePatch + computeGradient (:14-99) for P sets of points, set p on frame slots[p] of `images`: pts P x capacity x 2 doubles
+ * (x, y), counts P, status P x capacity bytes, all DEVICE.  status: 5 for a point whose taps leave the image (nothing of its
+ * model is written), 2 for a NaN invHessian[0], else 1.  Nothing beyond a set's count is written; a count outside 0 .. capacity
+ * leaves the set alone; a slot outside the set fails the set's points with status 5.  Bad params, NULL images / slots / pts /
+ * counts / status (`model` itself may be NULL, as for ps_patch_align: the statuses alone), capacity < 1, P < 0, channels other than 1 or 3, an image above 8192 rows or columns: PS_ERR_BAD_ARG,
+ * outputs untouched; P == 0 is PS_OK.  One wavefront per point.  Asynchronous on the context's stream; no scratch of the context. */
+int ps_patch_models(PsContext *ctx, const PsImageSet *images, const int32_t *slots, const double *pts, const int32_t *counts, int P,
+                    int capacity, const PsPatchParams *params, const PsPatchModel *model, uint8_t *status);
+/* optimizeLocation (:101-200) for P pairs of frames: pairs P x 2 int32 (old slot, new slot; a pair may name one slot twice),
+ * oldPts / newPts P x capacity x 2 doubles, counts P, status P x capacity bytes, iterations P x capacity int32 (the steps
+ * applied), all DEVICE.  newPts is read as the starting guess and written as the reference leaves it: updated through the last
+ * completed step, untouched for status 2 and 5.  Without PS_PATCH_GIVEN_MODEL the model is built from the old slot at oldPts and
+ * written to the non-NULL arrays of `model` (which may itself be NULL); with it the four arrays are read, and neither the old
+ * slot nor oldPts (may be NULL) is looked at.  Counts, slots (the ones read) and errors as for ps_patch_models.  Asynchronous. */
+int ps_patch_align(PsContext *ctx, const PsImageSet *images, const int32_t *pairs, const double *oldPts, double *newPts,
+                   const int32_t *counts, int P, int capacity, const PsPatchParams *params, const PsPatchModel *model, uint8_t *status,
+                   int32_t *iterations);
+/* The same for one image or one image pair and n points: HOST pointers, uploads and downloads included, synchronous.  Images
+ * rows x cols x channels bytes, rowStride bytes apart (0 = dense); pts n x 2 doubles; patch n x E doubles; gx / gy n x E floats;
+ * invHessian n x 9 floats; status n bytes; iterations n int32.  n == 0 is PS_OK.
+ * ps_compute_patch: computePatch (:14-51); ps_compute_patch_gradient: computeGradient (:53-99), any of gx / gy / invHessian may
+ * be NULL; ps_optimize_location: optimizeLocation (:101-200) on a given model (oldImg is not read, as in the reference, and may
+ * be NULL); ps_optimize_locations: the three calls fused for n points. */
+int ps_compute_patch(PsContext *ctx, const uint8_t *img, int rows, int cols, int channels, size_t rowStride, const double *pts, int n,
+                     const PsPatchParams *params, double *patch, uint8_t *status);
+int ps_compute_patch_gradient(PsContext *ctx, const uint8_t *img, int rows, int cols, int channels, size_t rowStride, const double *pts,
+                              int n, const PsPatchParams *params, float *gx, float *gy, float *invHessian, uint8_t *status);
+int ps_optimize_location(PsContext *ctx, const uint8_t *oldImg, const double *oldPatch, const uint8_t *newImg, int rows, int cols,
+                         int channels, size_t rowStride, double *newPts, int n, const float *gx, const float *gy, const float *invHessian,
+                         const PsPatchParams *params, uint8_t *status, int32_t *iterations);
+int ps_optimize_locations(PsContext *ctx, const uint8_t *oldImg, const uint8_t *newImg, int rows, int cols, int channels,
+                          size_t rowStride, const double *oldPts, double *newPts, int n, const PsPatchParams *params, uint8_t *status,
+                          int32_t *iterations);
+
 /* ---- Measurement uncertainty: the two per-feature steps of the frame loop before the data passes to the graph optimiser --
  * matcher->computeNormals / computeRGBGradients (src/PUTSLAM/PUTSLAM.cpp:826-837 for the measurements, :871-884 for the new
  * features) and the 3 x 3 information matrix FeaturesMap::addMeasurements (src/Map/featuresMap.cpp:251-285) and addFeatures

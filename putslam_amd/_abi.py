@@ -342,6 +342,26 @@ def sensor_model(**fields):
     return s
 
 
+# Sub-pixel matching on patches (include/putslam_hip.h)
+PATCH_MAX_ITERATIONS, PATCH_CONVERGED, PATCH_NAN_HESSIAN, PATCH_OUT_OF_IMAGE, PATCH_MOVED_TOO_FAR = 0, 1, 2, 3, 4
+PATCH_OLD_TAPS_OUTSIDE, PATCH_NEW_TAPS_OUTSIDE = 5, 6
+PATCH_GIVEN_MODEL = 1
+
+
+class PsPatchParams(C.Structure):
+    _fields_ = [("minSqrtIncrement", C.c_double), ("patchSize", C.c_int32), ("maxIter", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class PsPatchModel(C.Structure):
+    _fields_ = [("patch", C.c_void_p), ("gx", C.c_void_p), ("gy", C.c_void_p), ("invHessian", C.c_void_p)]
+
+
+def patch_params(patch_size=13, max_iter=50, min_sqrt_increment=0.04, flags=0):
+    """PsPatchParams; the defaults are the shipped PatchesParams (patchSize 13, maxIterationCount 50, minSqrtError 0.04)."""
+    return PsPatchParams(float(min_sqrt_increment), int(patch_size), int(max_iter), int(flags), 0)
+
+
 class PsHostPairResults(C.Structure):
     _fields_ = [("matches", C.c_void_p), ("numMatches", C.c_void_p), ("inlierMask", C.c_void_p),
                 ("pose", C.c_void_p), ("stats", C.c_void_p), ("firstPair", C.c_int64), ("count", C.c_int32),

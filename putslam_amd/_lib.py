@@ -11,7 +11,7 @@ from ._abi import (PsDMatch, PsExclusionRule, PsFrameSet, PsFrameSetF32, PsHostP
                    PsPoseSetOutF32, PsPoseSetRequest, PsRansacConfig, PsRansacParams, PsRansacStats, PsImageSet, PsKltParams, PsDetectParams, PsOrbParams, PsOrbDetectParams,
                    PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoParams,
                    PsTrackVoIn, PsTrackVoOut, PsTrackCandidates, PsTrackCloseParams, PsTrackCloseOut, PsSensorModel, PsUncertaintyOut,
-                   PsMeasurementEdgesOut)
+                   PsMeasurementEdgesOut, PsPatchParams, PsPatchModel)
 
 # Hardware queues: the library's launch chains (batch queue, pipelined stream) want one each, the HIP runtime reads
 # GPU_MAX_HW_QUEUES once, at its first call.  The library sets its default (16) from a constructor when it is loaded -- too late
@@ -71,6 +71,8 @@ EXPORTED = [
     "ps_sensor_model_default", "ps_debug_gradient_tie_table", "ps_feature_uncertainty", "ps_measurement_edges", "ps_compute_normals",
     "ps_compute_rgb_gradients", "ps_information_matrices",
     "ps_abi_sizeof_sensor_model", "ps_abi_sizeof_uncertainty_out", "ps_abi_sizeof_measurement_edges_out",
+    "ps_patch_models", "ps_patch_align", "ps_compute_patch", "ps_compute_patch_gradient", "ps_optimize_location", "ps_optimize_locations",
+    "ps_abi_sizeof_patch_params", "ps_abi_sizeof_patch_model",
 ]
 
 # ps_abi_sizeof_<name>: the ctypes mirror (_abi.py) of every struct that crosses the C ABI
@@ -99,6 +101,8 @@ ABI_STRUCTS_TRACK_VO = dict(point_sets=PsPointSets, tracked_carry=PsTrackedCarry
 ABI_STRUCTS_TRACK_CLOSE = dict(track_candidates=PsTrackCandidates, track_close_params=PsTrackCloseParams, track_close_out=PsTrackCloseOut)
 # ... and of the measurement uncertainty (ps_feature_uncertainty / ps_measurement_edges)
 ABI_STRUCTS_UNCERTAINTY = dict(sensor_model=PsSensorModel, uncertainty_out=PsUncertaintyOut, measurement_edges_out=PsMeasurementEdgesOut)
+# ... and of the matching on patches (ps_patch_models / ps_patch_align)
+ABI_STRUCTS_PATCHES = dict(patch_params=PsPatchParams, patch_model=PsPatchModel)
 
 _lib = None
 _by_path = {}
@@ -366,9 +370,15 @@ def load_path(path):
     L.ps_compute_rgb_gradients.argtypes = [vp, C.POINTER(PsFrameGeometry), vp, i32, sz, vp, i32, i32, sz, vp, i32, vp]
     L.ps_information_matrices.argtypes = [vp, C.POINTER(PsFrameGeometry), C.POINTER(PsSensorModel), i32, vp, i32, sz, vp, i32, i32, sz,
                                           vp, vp, i32, vp]
+    L.ps_patch_models.argtypes = [vp, C.POINTER(PsImageSet), vp, vp, vp, i32, i32, C.POINTER(PsPatchParams), C.POINTER(PsPatchModel), vp]
+    L.ps_patch_align.argtypes = [vp, C.POINTER(PsImageSet), vp, vp, vp, vp, i32, i32, C.POINTER(PsPatchParams), C.POINTER(PsPatchModel), vp, vp]
+    L.ps_compute_patch.argtypes = [vp, vp, i32, i32, i32, sz, vp, i32, C.POINTER(PsPatchParams), vp, vp]
+    L.ps_compute_patch_gradient.argtypes = [vp, vp, i32, i32, i32, sz, vp, i32, C.POINTER(PsPatchParams), vp, vp, vp, vp]
+    L.ps_optimize_location.argtypes = [vp, vp, vp, vp, i32, i32, i32, sz, vp, i32, vp, vp, vp, C.POINTER(PsPatchParams), vp, vp]
+    L.ps_optimize_locations.argtypes = [vp, vp, vp, i32, i32, i32, sz, vp, vp, i32, C.POINTER(PsPatchParams), vp, vp]
     for n in (list(ABI_STRUCTS) + list(ABI_STRUCTS_F32) + list(ABI_STRUCTS_STORE_F32) + list(ABI_STRUCTS_KLT) + list(ABI_STRUCTS_DETECT)
               + list(ABI_STRUCTS_ORB) + list(ABI_STRUCTS_ORB_DETECT) + list(ABI_STRUCTS_FRAME_ASSEMBLY) + list(ABI_STRUCTS_TRACK_VO)
-              + list(ABI_STRUCTS_TRACK_CLOSE) + list(ABI_STRUCTS_UNCERTAINTY)):
+              + list(ABI_STRUCTS_TRACK_CLOSE) + list(ABI_STRUCTS_UNCERTAINTY) + list(ABI_STRUCTS_PATCHES)):
         getattr(L, "ps_abi_sizeof_" + n).restype = sz
     _by_path[path] = real
     return real
@@ -416,3 +426,7 @@ def struct_sizes_track_close():
 
 def struct_sizes_uncertainty():
     return {n: C.sizeof(t) for n, t in ABI_STRUCTS_UNCERTAINTY.items()}
+
+
+def struct_sizes_patches():
+    return {n: C.sizeof(t) for n, t in ABI_STRUCTS_PATCHES.items()}

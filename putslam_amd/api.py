@@ -16,7 +16,7 @@ from ._abi import (DMATCH_DTYPE, STATS_DTYPE, PS_ERR_BUSY, PS_MAX_KPTS, PS_OK, P
                    PsOrbDetectParams, orb_detect_params, PsDepthSet, PsFrameGeometry, PsFrameRowsOut, PsFrontEndParams, front_end_params,
                    PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoParams, PsTrackVoIn, PsTrackVoOut, track_vo_params,
                    PsTrackCandidates, PsTrackCloseParams, PsTrackCloseOut, track_close_params, PsSensorModel, PsUncertaintyOut,
-                   PsMeasurementEdgesOut, sensor_model)
+                   PsMeasurementEdgesOut, sensor_model, PsPatchParams, PsPatchModel, patch_params)
 
 
 class PsError(RuntimeError):
@@ -756,6 +756,76 @@ class Context:
         if depth.strides[1] != 2 or depth.strides[0] < depth.shape[1] * 2:
             depth = np.ascontiguousarray(depth)
         return depth
+
+    # ---- sub-pixel matching on patches (MatchingOnPatches)
+    def compute_patch(self, img, pts, params=None):
+        """MatchingOnPatches::computePatch (ps_compute_patch) for n points of one image: img (rows, cols) or (rows, cols, 3) uint8,
+        pts (n, 2) float64.  params: _abi.patch_params(...), default the shipped PatchesParams.  Returns (patch (n, E) float64,
+        status (n,) uint8: 5 where the taps leave the image -- that row is zero --, else 2 or 1)."""
+        params = params or patch_params()
+        img, cn = _host_image(img)
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 2)
+        n, E = pts.shape[0], params.patchSize ** 2
+        patch, status = np.zeros((max(n, 1), E), np.float64), np.zeros(max(n, 1), np.uint8)
+        self._chk(self._L.ps_compute_patch(self._h, _p(img), img.shape[0], img.shape[1], cn, img.strides[0], _p(pts), n, C.byref(params),
+                                           _p(patch), _p(status)))
+        return patch[:n], status[:n]
+
+    def compute_patch_gradient(self, img, pts, params=None):
+        """MatchingOnPatches::computeGradient (ps_compute_patch_gradient): returns (gx (n, E) float32, gy (n, E) float32, invHessian
+        (n, 3, 3) float32, status (n,) uint8)."""
+        params = params or patch_params()
+        img, cn = _host_image(img)
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 2)
+        n, E, m = pts.shape[0], params.patchSize ** 2, max(pts.shape[0], 1)
+        gx, gy, inv, status = np.zeros((m, E), np.float32), np.zeros((m, E), np.float32), np.zeros((m, 3, 3), np.float32), np.zeros(m, np.uint8)
+        self._chk(self._L.ps_compute_patch_gradient(self._h, _p(img), img.shape[0], img.shape[1], cn, img.strides[0], _p(pts), n,
+                                                    C.byref(params), _p(gx), _p(gy), _p(inv), _p(status)))
+        return gx[:n], gy[:n], inv[:n], status[:n]
+
+    def optimize_location(self, old_patch, new_img, new_pts, gx, gy, inv_hessian, params=None, old_img=None):
+        """MatchingOnPatches::optimizeLocation (ps_optimize_location) on a given model, for n points: old_patch (n, E) float64, gx /
+        gy (n, E) float32, inv_hessian (n, 3, 3) float32, new_pts (n, 2) float64 the starting guesses.  old_img is not read (the
+        reference reads it nowhere either).  Returns (newPts (n, 2) float64, status (n,) uint8, iterations (n,) int32)."""
+        params = params or patch_params()
+        img, cn = _host_image(new_img)
+        E = params.patchSize ** 2
+        nxt = np.array(new_pts, np.float64).reshape(-1, 2)
+        n, m = nxt.shape[0], max(nxt.shape[0], 1)
+        old_patch = np.ascontiguousarray(old_patch, np.float64).reshape(n, E)
+        gx, gy = np.ascontiguousarray(gx, np.float32).reshape(n, E), np.ascontiguousarray(gy, np.float32).reshape(n, E)
+        inv = np.ascontiguousarray(inv_hessian, np.float32).reshape(n, 9)
+        status, iters = np.zeros(m, np.uint8), np.zeros(m, np.int32)
+        self._chk(self._L.ps_optimize_location(self._h, None, _p(old_patch), _p(img), img.shape[0], img.shape[1], cn, img.strides[0], _p(nxt),
+                                               n, _p(gx), _p(gy), _p(inv), C.byref(params), _p(status), _p(iters)))
+        return nxt, status[:n], iters[:n]
+
+    def optimize_locations(self, old_img, new_img, old_pts, new_pts, params=None):
+        """The three calls fused for n points of one image pair (ps_optimize_locations): old_pts / new_pts (n, 2) float64.  Returns
+        (newPts (n, 2) float64, status (n,) uint8 -- _abi.PATCH_* --, iterations (n,) int32)."""
+        params = params or patch_params()
+        (old, cn), (new, _) = _host_image(old_img), _host_image(new_img)
+        assert old.shape == new.shape
+        if new.strides[0] != old.strides[0]:   # (the call takes one row stride for both)
+            old, new = np.ascontiguousarray(old), np.ascontiguousarray(new)
+        old_pts = np.ascontiguousarray(old_pts, np.float64).reshape(-1, 2)
+        n, m = old_pts.shape[0], max(old_pts.shape[0], 1)
+        nxt = np.array(new_pts, np.float64).reshape(n, 2)
+        status, iters = np.zeros(m, np.uint8), np.zeros(m, np.int32)
+        self._chk(self._L.ps_optimize_locations(self._h, _p(old), _p(new), old.shape[0], old.shape[1], cn, old.strides[0], _p(old_pts),
+                                                _p(nxt), n, C.byref(params), _p(status), _p(iters)))
+        return nxt, status[:n], iters[:n]
+
+    def patch_models(self, images: PsImageSet, slots_ptr, pts_ptr, counts_ptr, P, capacity, params, model: PsPatchModel, status_ptr):
+        """ps_patch_models on device pointers (asynchronous on the context's stream): device_batch.patch_models."""
+        self._chk(self._L.ps_patch_models(self._h, C.byref(images), slots_ptr, pts_ptr, counts_ptr, int(P), int(capacity), C.byref(params),
+                                          C.byref(model) if model is not None else None, status_ptr))
+
+    def patch_align(self, images: PsImageSet, pairs_ptr, old_pts_ptr, new_pts_ptr, counts_ptr, P, capacity, params, model, status_ptr,
+                    iterations_ptr):
+        """ps_patch_align on device pointers (asynchronous on the context's stream): device_batch.align_patches."""
+        self._chk(self._L.ps_patch_align(self._h, C.byref(images), pairs_ptr, old_pts_ptr, new_pts_ptr, counts_ptr, int(P), int(capacity),
+                                         C.byref(params), C.byref(model) if model is not None else None, status_ptr, iterations_ptr))
 
     def compute_normals(self, xy, depth, geometry: PsFrameGeometry):
         """RGBD::computeNormal (RGBD.cpp:101-144) at n undistorted positions xy (n, 2) float32 of a depth image (rows, cols) uint16

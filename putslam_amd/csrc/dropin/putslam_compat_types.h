@@ -109,6 +109,16 @@ struct Vector3f { // 12 bytes, like Eigen::Vector3f
     float z() const { return v[2]; }
 };
 
+struct Matrix3f { // column-major 3x3, like Eigen::Matrix3f (MatchingOnPatches' InvHessian); carries data, no arithmetic
+    float m[9];
+    Matrix3f() { std::memset(m, 0, sizeof m); }
+    static Matrix3f Zero() { return Matrix3f(); }
+    float &operator()(int r, int c) { return m[3 * c + r]; }
+    const float &operator()(int r, int c) const { return m[3 * c + r]; }
+    float *data() { return m; }
+    const float *data() const { return m; }
+};
+
 struct Matrix4f { // column-major 4x4, like Eigen::Matrix4f
     float m[16];
     Matrix4f() { std::memset(m, 0, sizeof m); }

@@ -199,6 +199,59 @@ class DBScan {
 };
 #endif
 
+// ---------------------------------------------------------------------------------------------
+// MatchingOnPatches (include/putslam/Matcher/MatchingOnPatches.h, src/Matcher/MatchingOnPatches.cpp:14-246): the sub-pixel alignment
+// of a feature's patch, with the reference's constructors, parameter block, three calls and getters, signature-identical, over
+// ps_compute_patch / ps_compute_patch_gradient / ps_optimize_location on the calling thread's context (one
+// device call each, uploads included), and the batch form optimizeLocations over ps_optimize_locations: one call for a whole list.
+// Images CV_8UC1 or CV_8UC3 (grey by CV_RGB2GRAY, as assertGrayscale does), any step.  `verbose` and `warping` are carried and read
+// nowhere; the narration to std::cout is not reproduced.  Where the reference reads outside its images this class does not:
+// computePatch returns an EMPTY vector and computeGradient a NaN InvHessian with empty gradients for a position whose taps leave the
+// image, so the following optimizeLocation returns false with the position untouched; a new position that passes the reference's
+// gate with taps outside stops with status 6.  optimizeLocation's bool is status == PS_PATCH_CONVERGED; lastStatus() /
+// lastIterations() give the calling thread's last optimizeLocation in full (static: the object keeps the reference's layout, behind
+// the reference header's own include guard, as DBScan does).  On an error: one line on std::cerr, false / empty / NaN.  Nothing runs
+// on the CPU instead.
+#ifndef _PATCHES
+#define _PATCHES
+class MatchingOnPatches {
+  public:
+    struct parameters {
+        int verbose;
+        bool warping;
+        int patchSize, halfPatchSize;
+        int maxIter;
+        double minSqrtIncrement;
+    };
+    // (size, step limit, stopping threshold, verbosity; the half size follows from the size, whatever a caller's block says)
+    MatchingOnPatches(int size, int stepLimit = 20, double threshold = 0.04, int verbosity = 0);
+    MatchingOnPatches(parameters block);
+    std::vector<double> computePatch(cv::Mat img, double x, double y);
+    void computeGradient(cv::Mat img, double x, double y, Eigen::Matrix3f &InvHessian, std::vector<float> &gradientX,
+                         std::vector<float> &gradientY);
+    bool optimizeLocation(cv::Mat oldImg, std::vector<double> oldPatch, cv::Mat newImg, double &newX, double &newY,
+                          std::vector<float> gradientX, std::vector<float> gradientY, Eigen::Matrix3f &InvHessian);
+    int getPatchSize() { return params.patchSize; }
+    int getHalfPatchSize() { return params.halfPatchSize; }
+    // The three calls fused for a list (no reference counterpart): oldXY / newXY hold x0, y0, x1, y1, ...; newXY is read as the
+    // starting guesses and written as the reference leaves each position.  Returns the PS_PATCH_* status of every point (empty on
+    // an error); iterations, where given, receives the steps applied.
+    std::vector<int> optimizeLocations(cv::Mat oldImg, cv::Mat newImg, const std::vector<double> &oldXY, std::vector<double> &newXY,
+                                       std::vector<int> *iterations = nullptr);
+    static int lastStatus();
+    static int lastIterations();
+
+  private:
+    parameters params;
+};
+#endif
+
+namespace putslam_hip {
+// MatcherParameters::PatchesParams as every shipped matcher XML sets it: <MatchingOnPatches verbose="0" warping="false"
+// patchSize="13" maxIterationCount="50" minSqrtError="0.04"/> (matcher.h:295-304,362)
+inline MatchingOnPatches::parameters shippedPatchesParams() { return MatchingOnPatches::parameters{0, false, 13, 6, 50, 0.04}; }
+} // namespace putslam_hip
+
 namespace putslam {
 
 // ---------------------------------------------------------------------------------------------
@@ -265,6 +318,7 @@ class FrameMatcher {
             std::string descriptor = "ORB";
             double DBScanEps = 1; // matcher.h:54; putslammatcherOpenCVParameters.xml:70 (frontEnd's thinning)
         } OpenCVParams;
+        MatchingOnPatches::parameters PatchesParams = shippedPatchesParams(); // matcher.h:362; MatchingOnPatches(PatchesParams) takes it
         MatcherParameters();
     };
 

@@ -1079,6 +1079,7 @@ int ps_vo_pairs_device(PsContext *ctx, const PsRansacParams *params, const PsRan
 #include "ps_frame_assembly.h" // ps_gather_keypoints / ps_assemble_frames / ps_front_end_* (the launches of ps_dbscan.h, ps_orb.h, ps_orb_detect.h)
 #include "ps_track_vo.h"     // ps_ransac_match_lists / ps_assemble_tracked / ps_track_vo_pairs (the plan and the stages above, ps_klt.h's launches, ps_frame_assembly.h's body)
 #include "ps_uncertainty.h"  // ps_feature_uncertainty / ps_measurement_edges / ps_compute_normals / ps_compute_rgb_gradients / ps_information_matrices (ps_frame_assembly.h's back-projection)
+#include "ps_patches.h"      // ps_patch_models / ps_patch_align / ps_compute_patch(_gradient) / ps_optimize_location(s) (ps_image_rule.h's set rule)
 #include "ps_track_close.h"  // ps_track_candidates / ps_track_close_* (ps_exclusion.h's predicate, ps_map_view.h's level rule, the launches of ps_orb.h and ps_frame_assembly.h)
 
 // Launch attributes of the kernels that need them (ps_internal.h; called once per context).
@@ -1092,4 +1093,5 @@ extern "C" void psi_kernel_attributes(void)
     exclusion_kernel_attributes();
     l2_kernel_attributes();
     klt_kernel_attributes();
+    patch_kernel_attributes();
 }

@@ -11,7 +11,8 @@ from ._abi import (DMATCH_DTYPE, PS_VIEW_REQUIRE_VISIBLE, STATS_DTYPE, PsLoopBat
                    PsMapStoreF32, PsMapViewOut, PsMapViewOutF32, PsMapViewRequest, PsPoseSetOut, PsPoseSetOutF32, PsPoseSetRequest,
                    make_config, PsImageSet, klt_params, detect_params, orb_params, orb_detect_params, PsDepthSet, PsFrameRowsOut,
                    front_end_params, PsPointSets, PsTrackedCarry, PsTrackedRows, PsTrackVoIn, PsTrackVoOut, track_vo_params,
-                   PsTrackCandidates, PsTrackCloseOut, track_close_params, PsUncertaintyOut, PsMeasurementEdgesOut, sensor_model)
+                   PsTrackCandidates, PsTrackCloseOut, track_close_params, PsUncertaintyOut, PsMeasurementEdgesOut, sensor_model,
+                   PsPatchModel, PsPatchParams, patch_params, PATCH_GIVEN_MODEL)
 
 
 _NUMPY_OF = {torch.int32: np.int32, torch.float64: np.float64}
@@ -1162,6 +1163,71 @@ def measurement_edges(ctx, batch, xy_undist, geometry, depth, images=None, senso
     _on_torch_stream(ctx, dev, lambda: ctx.measurement_edges_device(geometry, sensor, model, s, ds, image_frame.data_ptr(), batch.batch_view(),
                                                                      batch.view(), xy_undist.data_ptr(), o), use_torch_stream)
     return out
+
+
+class PatchModels:
+    """The model arrays of P x cap points (PsPatchModel): patch (P, cap, E) float64, gx / gy (P, cap, E) float32, inv (P, cap, 9)
+    float32, on `device`; `want` names the arrays to keep (the others are NULL: not written)."""
+
+    def __init__(self, P, cap, patch_size, device, want=("patch", "gx", "gy", "inv")):
+        E = int(patch_size) ** 2
+        self.P, self.cap, self.E, self.device = P, cap, E, device
+        self.patch = _zeros(device, (P, cap, E), torch.float64) if "patch" in want else None
+        self.gx = _zeros(device, (P, cap, E), torch.float32) if "gx" in want else None
+        self.gy = _zeros(device, (P, cap, E), torch.float32) if "gy" in want else None
+        self.inv = _zeros(device, (P, cap, 9), torch.float32) if "inv" in want else None
+
+    def struct(self):
+        return PsPatchModel(*[t.data_ptr() if t is not None else None for t in (self.patch, self.gx, self.gy, self.inv)])
+
+
+def _patch_images(images):
+    assert images.dtype == torch.uint8 and images.dim() in (3, 4)
+    return _image_set(images, images.shape[1], images.shape[2], 1 if images.dim() == 3 else images.shape[3])
+
+
+def patch_models(ctx, images, slots, pts, counts, params=None, model: PatchModels = None, status=None, use_torch_stream=True):
+    """computePatch + computeGradient for P sets of points (ps_patch_models): images a uint8 device tensor (F, rows, cols[, 3]) whose
+    rows and frames may lie any stride apart, slots (P,) int32 the frame of each set, pts (P, cap, 2) float64, counts (P,) int32.
+    Returns (model, status (P, cap) uint8), written asynchronously: nothing beyond a set's count."""
+    params = params or patch_params()
+    P, cap = pts.shape[0], pts.shape[1]
+    dev = pts.device
+    _expect(pts, torch.float64, (P, cap, 2))
+    _expect(slots, torch.int32, (P,))
+    _expect(counts, torch.int32, (P,))
+    model = model or PatchModels(P, cap, params.patchSize, dev)
+    status = _block(status, dev, (P, cap), torch.uint8)
+    s = _patch_images(images)
+    args = (s, slots.data_ptr(), pts.data_ptr(), counts.data_ptr(), P, cap, params, model.struct(), status.data_ptr())
+    _on_torch_stream(ctx, dev, lambda: ctx.patch_models(*args), use_torch_stream)
+    return model, status
+
+
+def align_patches(ctx, images, pairs, old_pts, new_pts, counts, params=None, model: PatchModels = None, given=False, status=None,
+                  iterations=None, use_torch_stream=True):
+    """optimizeLocation for P pairs of frames (ps_patch_align): pairs (P, 2) int32 (old, new), old_pts / new_pts (P, cap, 2)
+    float64 -- new_pts the starting guesses, refined IN PLACE --, counts (P,) int32.  model: where the fused call writes the model
+    (None: nowhere); given=True: the model is read from it instead (PS_PATCH_GIVEN_MODEL; old_pts may be None).  Returns (new_pts,
+    status (P, cap) uint8, iterations (P, cap) int32), written asynchronously: nothing beyond a pair's count."""
+    params = params or patch_params()
+    P, cap = new_pts.shape[0], new_pts.shape[1]
+    dev = new_pts.device
+    _expect(new_pts, torch.float64, (P, cap, 2))
+    if old_pts is not None:
+        _expect(old_pts, torch.float64, (P, cap, 2))
+    _expect(pairs, torch.int32, (P, 2))
+    _expect(counts, torch.int32, (P,))
+    if given:
+        assert model is not None
+        params = PsPatchParams(params.minSqrtIncrement, params.patchSize, params.maxIter, params.flags | PATCH_GIVEN_MODEL, 0)
+    status = _block(status, dev, (P, cap), torch.uint8)
+    iterations = _block(iterations, dev, (P, cap), torch.int32)
+    s = _patch_images(images)
+    args = (s, pairs.data_ptr(), old_pts.data_ptr() if old_pts is not None else None, new_pts.data_ptr(), counts.data_ptr(), P, cap, params,
+            model.struct() if model is not None else None, status.data_ptr(), iterations.data_ptr())
+    _on_torch_stream(ctx, dev, lambda: ctx.patch_align(*args), use_torch_stream)
+    return new_pts, status, iterations
 
 
 class MapBatchF32Device(MapBatchDevice):
