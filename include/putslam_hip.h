@@ -356,7 +356,9 @@ int ps_exclude_device(PsContext *ctx, const PsExclusionRule *rule, const float *
  * difference (:719-721); every candidate with acceptRatio * value <= best value is emitted (:734-746) as
  * DMatch(queryIdx = j, trainIdx = i, imgIdx = -1, distance = value), ordered by (j, i).
  * mapPos: (float) casts of MapFeature::position (:701-702); levels from ps_predicted_level.
- * Returns PS_ERR_BAD_ARG with *nout = required capacity if cap is too small.  Host pointers. */
+ * Returns PS_ERR_BAD_ARG with *nout = required capacity if cap is too small; out is then not written.  Host pointers,
+ * synchronous.  A row pitch below 32 bytes or more than PS_MAX_KPTS rows on either side -> PS_ERR_UNSUPPORTED; NULL where an
+ * array is needed -> PS_ERR_BAD_ARG; *nout = 0 on those errors.  An empty side gives no matches (PS_OK). */
 int ps_match_xyz(PsContext *ctx, const float *mapPos, const uint8_t *mapDesc, size_t mapDescStep,
                  const int32_t *mapLevel, int nmap, const float *curPos, const uint8_t *curDesc,
                  size_t curDescStep, const int32_t *curLevel, int ncur, double sphereRadius,

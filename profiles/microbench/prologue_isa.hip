@@ -1,6 +1,6 @@
 // Stand-alone instantiations of the per-hypothesis prologue (sample -> float Umeyama + Jacobi SVD -> general inverse) for
 // profiles/isa_mix.py: compiled to assembly only (never run), one kernel per part, so that the parts can be counted.
-#include "../../putslam_amd/csrc/ps_kernels.h"
+#include "../../putslam_amd/csrc/ps_device_math.h"
 using namespace psdev;
 extern "C" __global__ void k_sample(uint64_t seed, uint32_t M, uint32_t *out)
 {

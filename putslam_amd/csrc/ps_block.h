@@ -1,8 +1,11 @@
 // ps_block.h -- the work-group and wave primitives of the kernel headers, once: ordered compaction (flag scans), the integer
-// scan, the maximum, wave minima and the lock-free union-find.  Nothing here knows a kernel; every LDS scratch block is the caller's.
+// scan, the maximum, wave minima, the lock-free union-find, the XCD-aware work-group order, the phase stamp and the wave-uniform
+// mask helpers.  Nothing here knows a kernel; every LDS scratch block is the caller's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "ps_device_math.h" // PS_D
 
 namespace psdev {
 
@@ -159,6 +162,59 @@ template <int SCOPE> __device__ __forceinline__ void uf_union(int *par, int a, i
         if (old == b) return;
         b = old; // b was hooked meanwhile: retry from where it went
     }
+}
+
+// ---- work-group order, phase stamps ----
+// XCD-aware work-group order.  Work-groups are dealt round-robin over the 8 XCDs (each with its own
+// 4 MiB L2), so linear ids L and L+8 share an L2.  This bijection gives every XCD a CONTIGUOUS range of
+// logical ids, so the work-groups that sweep the same frame pair (same query rows / same match records)
+// run on one XCD and re-read them from its L2 instead of each XCD fetching its own copy.  Speed only:
+// nothing depends on where a work-group actually lands.
+PS_D unsigned xcd_remap(unsigned L, unsigned total)
+{
+    const unsigned xcd = L & 7u, idx = L >> 3;
+    const unsigned q = total >> 3, r = total & 7u;
+    return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + idx;
+}
+
+// Phase stamps of the latency study (option "stamps", ps_debug_stamps): thread 0 of work-group 0 writes the shader clock
+// (s_memtime) at the phase boundaries of kernels 2 and 4 into a private buffer -- never into outputs.  stamps == nullptr in
+// every ordinary launch (one scalar compare per boundary).
+PS_D void phase_stamp(unsigned long long *stamps, int i)
+{
+    if (stamps != nullptr && threadIdx.x == 0 && blockIdx.x == 0) stamps[i] = __builtin_readcyclecounter();
+}
+
+// ---- wave-uniform masks ----
+// wave-uniform "every active lane satisfies p": compares the ballot with the exec mask directly, so the
+// predicate never has to be materialised in a VGPR (hipcc's __all() costs a v_cndmask + v_cmp_ne)
+PS_D bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_ballot_w64(true); }
+
+// Lanes of a wave-uniform 64-bit mask without lane masks in vector registers ((1 << lane) - 1 and its complement are four
+// registers the compiler hoists out of every loop): how many set bits lie below the calling lane (v_mbcnt_lo / _hi),
+// and whether the calling lane's own bit is set (v_cndmask with the mask as the selector).
+PS_D int lanes_below(unsigned long long mask)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+// a 64-bit value that is the same in every lane, moved to scalar registers (loaded through a pointer the compiler cannot
+// prove uniform it sits in vector registers)
+PS_D unsigned long long uniform64(unsigned long long v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+PS_D bool lane_in(unsigned long long mask)
+{
+    int x;
+    asm("v_cndmask_b32 %0, 0, 1, %1" : "=v"(x) : "s"(mask));
+    return x != 0;
+}
+// cnt += 1 in the lanes of `mask` (v_addc_co_u32 with the mask as carry-in: one VALU op)
+PS_D void add_mask(int &cnt, unsigned long long mask)
+{
+    asm volatile("v_addc_co_u32 %0, vcc, 0, %0, %1" : "+v"(cnt) : "s"(mask) : "vcc");
 }
 
 } // namespace psdev

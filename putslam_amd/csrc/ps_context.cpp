@@ -21,6 +21,23 @@ int ransac_iterations_host(double inlierRatio, double successProbability, int nu
     return (int)v;
 }
 
+// Hypotheses the sequential schedule can ever consume, of the numHypotheses a call offers: RANSAC never looks beyond the larger
+// of its initial trip limit (ratio 0.20, RANSAC.cpp:30) and the limit at minimalInlierRatioThreshold; USAC stops at its cap; the
+// fixed schedule takes them all.  What kernel 3 scores (Plan::H) and what ps_debug_ransac_counts returns counts for.
+int scored_hypotheses(int estimator, int numHypotheses, double minRatio)
+{
+    int H = numHypotheses;
+    if (estimator == PS_EST_RANSAC) {
+        int a = ransac_iterations_host(0.20), b = ransac_iterations_host(minRatio);
+        int most = a > b ? a : b;
+        if (most < H) H = most;
+        if (H < 1) H = 1;
+    } else if (estimator == PS_EST_USAC) {
+        if (H > (int)kUsacMaxHyp) H = (int)kUsacMaxHyp;
+    }
+    return H;
+}
+
 // USAC<T>::updateStandardStopping (reference include/putslam/USAC/USAC.h:944-971) as a function of the
 // good-model probability, with confThreshold 0.99 and maxHypotheses 850000 (USAC_wrapper.cpp:66,70).
 unsigned usac_stopping_host(double prob_good_model)

@@ -47,7 +47,7 @@ PS_HD float ps_rint(float x) { return rintf(x); }
 // correction's compares are false for it; NaN stays NaN), so the nine instructions below ARE the compiler's sequence and
 // return the same bits.  Every square root of the Jacobi SVD has the form sqrt(v * v + 1).  Likewise a correctly rounded
 // a / b is div_scale x 2, rcp, 3 + 3 FMA / MUL, div_fmas, div_fixup: with numerator and denominator inside the window
-// where neither div_scale rescales and div_fixup passes its first operand through (ps_kernels.h, div2_shared) the plain
+// where neither div_scale rescales and div_fixup passes its first operand through (ps_score_value.h, div2_shared) the plain
 // FMA chain below is that sequence.  ps_debug_mathcheck compares each of these with the operator bit for bit
 // (tests/test_gpu_parity.py: every float >= 1 for the square root, every float of [1, 2] for the reciprocal, 10^9 random
 // operands for the quotients).

@@ -1,8 +1,140 @@
 // ps_diag.h -- the diagnostics of the C ABI (ps_debug_*, include/putslam_hip.h): what the parity tests read beyond the outputs
 // -- per-hypothesis counts, stop tables, the exactness checks of the short division / root forms, staged-scoring survivors,
-// stamps.  No reference counterpart.  Included by ps_capi.hip behind ransac_host_entry (the kernels and that function are that
-// file's).
+// stamps.  No reference counterpart.  Included by ps_capi.hip behind the stages: ransac_host_entry and prepare_tables are
+// ps_ransac_stage.h's, the keys block is ps_match_stage.h's.
 #pragma once
+#include "ps_match_stage.h"
+#include "ps_ransac_stage.h"
+
+namespace psdev {
+
+// Diagnostic: counts inputs inside the division window for which div2_shared differs from the '/' operator.
+__global__ __launch_bounds__(kBlock) void ps_fastdiv_check(uint64_t seed, int perThread, unsigned long long *mismatch,
+                                                           unsigned long long *tested)
+{
+    const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    unsigned long long bad = 0, n = 0;
+    for (int i = 0; i < perThread; ++i) {
+        uint64_t r0 = mix64(seed ^ mix64(tid * 0x10001ull + (uint64_t)i));
+        uint64_t r1 = mix64(r0);
+        // random sign, exponent in [2^-40, 2^40), random mantissa
+        auto mk = [](uint32_t bits) {
+            uint32_t sign = bits & 0x80000000u;
+            uint32_t ex = 87u + ((bits >> 23) & 0xFFu) % 80u;
+            uint32_t v = sign | (ex << 23) | (bits & 0x007FFFFFu);
+            float f;
+            memcpy(&f, &v, 4);
+            return f;
+        };
+        float a0 = mk((uint32_t)r0), a1 = mk((uint32_t)(r0 >> 32)), b = mk((uint32_t)r1);
+        if (i & 1) { // the regime of the kernel: metres times focal length over depth
+            a0 = a0 * 0.0f + (float)((int)((r0 >> 8) & 0xFFFF) - 32768) * 0.37f;
+            b = 0.1f + (float)((r1 >> 8) & 0xFFFF) * 1e-4f;
+        }
+        if (!div_window_ok(a0, a1, b, a0, a1, b)) continue;
+        float q0, q1;
+        div2_shared(a0, a1, b, q0, q1);
+        float e0 = a0 / b, e1 = a1 / b;
+        uint32_t x0, y0, x1, y1;
+        memcpy(&x0, &q0, 4); memcpy(&y0, &e0, 4); memcpy(&x1, &q1, 4); memcpy(&y1, &e1, 4);
+        bad += (x0 != y0) + (x1 != y1);
+        n += 2;
+    }
+    atomicAdd(mismatch, bad);
+    atomicAdd(tested, n);
+}
+
+// Diagnostic (ps_debug_mathcheck): the exact short forms of ps_device_math.h against the operators, bit for bit.
+//   mode 0  sqrt_ge1(x) vs sqrtf(x) for EVERY float pattern from 1.0f up to +inf and the NaN patterns just above it
+//           (element e of the sweep = pattern 0x3F800000 + e; 0x40001000 elements cover them)
+//   mode 1  rcp_exact_in_window(x) vs 1.0f / x for every float of [1, 2] (0x00800001 elements)
+//   mode 2  unit_sign(y) vs y / |y| for random y of every exponent (+-inf and NaN included; NaN == NaN here)
+//   mode 3  JacobiSVD's pair 1 / d, u / d with d = sqrt(1 + u * u): div_with on random u inside the window
+//   mode 4  nine numerators over one denominator (scale_down3 / inverse_rigid_general): div_with on random operands of
+//           the window [2^-40, 2^40]
+__global__ __launch_bounds__(kBlock) void ps_mathcheck(int mode, uint64_t seed, int perThread, unsigned long long total,
+                                                       unsigned long long *mismatch, unsigned long long *tested)
+{
+    const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t nthreads = (uint64_t)gridDim.x * kBlock;
+    unsigned long long bad = 0, n = 0;
+    auto bits = [](float f) { return __builtin_bit_cast(uint32_t, f); };
+    auto same = [&](float a, float b) { return bits(a) == bits(b) || (a != a && b != b); };
+    auto in_window = [](uint32_t r) { // random sign, exponent in [2^-40, 2^40), random mantissa
+        const uint32_t ex = 87u + ((r >> 23) & 0xFFu) % 80u;
+        return __builtin_bit_cast(float, (r & 0x80000000u) | (ex << 23) | (r & 0x007FFFFFu));
+    };
+    for (int i = 0; i < perThread; ++i) {
+        const uint64_t e = (uint64_t)i * nthreads + tid; // (consecutive threads take consecutive elements)
+        if (mode <= 1 && e >= total) break;
+        const uint64_t r0 = mix64(seed ^ mix64(e));
+        const uint64_t r1 = mix64(r0);
+        if (mode == 0) {
+            const float x = __builtin_bit_cast(float, (uint32_t)(0x3F800000ull + e));
+            bad += same(sqrt_ge1(x), sqrtf(x)) ? 0 : 1;
+            n += 1;
+        } else if (mode == 1) {
+            const float x = __builtin_bit_cast(float, (uint32_t)(0x3F800000ull + e));
+            bad += same(rcp_exact_in_window(x), 1.0f / x) ? 0 : 1;
+            n += 1;
+        } else if (mode == 2) {
+            float y = __builtin_bit_cast(float, (uint32_t)r0);
+            if (!(fabsf(y) >= 5.877471754111438e-39f) && y == y) y = 1.0f; // (the caller's guard: 2 |y| >= FLT_MIN)
+            bad += same(unit_sign(y), y / fabsf(y)) ? 0 : 1;
+            n += 1;
+        } else if (mode == 3) {
+            float u = in_window((uint32_t)r0);
+            if (i & 1) u = (float)((int)((r0 >> 40) & 0xFFFF) - 32768) * 1.0e-3f + 1.0e-6f; // the regime of the SVD: |u| ~ 0 .. 30
+            const float d = sqrt_ge1(u * u + 1.0f);
+            if (!(fabsf(u) >= kExactDivLo && d <= kExactDivHi)) continue;
+            const float q = rcp_refined(d);
+            bad += (same(div_with(1.0f, d, q), 1.0f / d) ? 0 : 1) + (same(div_with(u, d, q), u / d) ? 0 : 1);
+            n += 2;
+        } else {
+            const float b = in_window((uint32_t)r1);
+            const float q = rcp_refined(b);
+            uint64_t r = r0;
+#pragma unroll 1
+            for (int k = 0; k < 9; ++k) {
+                const float a = in_window((uint32_t)r);
+                bad += same(div_with(a, b, q), a / b) ? 0 : 1;
+                r = mix64(r);
+            }
+            n += 9;
+        }
+    }
+    atomicAdd(mismatch, bad);
+    atomicAdd(tested, n);
+}
+
+// Diagnostic: words of the keys block that are not kNoKey (the matcher's atomicMin merge relies on an all-ones block at rest).
+__global__ void ps_count_not_ones(const uint32_t *__restrict__ keys, size_t n, unsigned long long *__restrict__ bad)
+{
+    unsigned long long c = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) c += keys[i] != kNoKey;
+    if (c) atomicAdd(bad, c);
+}
+
+// Diagnostic: tabulates the device-side trip limits so tests can compare them with the direct
+// libm evaluation (RANSAC.cpp:457-461, USAC.h:944-971) for every (count, M).
+// (the limit functions search their table as a wavefront with uniform arguments, as the replays call them: the wave takes
+// its 64 counts one after the other)
+__global__ void ps_limits_table(SelectArgs a, int M, int32_t *__restrict__ out)
+{
+    const int c0 = (int)(blockIdx.x * blockDim.x + (threadIdx.x & ~63u)) + 1; // the wave's first count
+    const int lane = threadIdx.x & 63;
+    int mine = 0;
+    for (int j = 0; j < 64; ++j) {
+        const int c = c0 + j;
+        if (c > M) break; // (uniform)
+        const int lim = (a.estimator == PS_EST_USAC) ? usac_limit(a, (unsigned)c, (unsigned)M)
+                                                     : ransac_limit(a, (float)c / (float)M);
+        if (lane == j) mine = lim;
+    }
+    if (c0 + lane <= M) out[c0 + lane - 1] = mine;
+}
+
+} // namespace psdev
 
 extern "C" {
 // Diagnostic twin of ps_ransac_rigid3d that also returns the per-hypothesis inlier counts the
@@ -16,16 +148,8 @@ int ps_debug_ransac_counts(PsContext *ctx, const PsRansacParams *params, const P
     float pose[16];
     int ninl = 0;
     PsRansacStats st;
-    // the number of scored hypotheses follows the same rule as make_plan
-    int H = cfg->numHypotheses;
-    if (cfg->estimator == PS_EST_RANSAC && params) {
-        int a = ransac_iterations_host(0.20), b = ransac_iterations_host(params->minimalInlierRatioThreshold);
-        int most = a > b ? a : b;
-        if (most < H) H = most;
-        if (H < 1) H = 1;
-    } else if (cfg->estimator == PS_EST_USAC && H > (int)kUsacMaxHyp)
-        H = (int)kUsacMaxHyp;
-    *numScored = H;
+    // (without params the call below fails; the count is then the offered one)
+    *numScored = params ? scored_hypotheses(cfg->estimator, cfg->numHypotheses, params->minimalInlierRatioThreshold) : cfg->numHypotheses;
     return ransac_host_entry(ctx, params, cfg, K, prev, nprev, cur, ncur, matches, m, pose, inl.data(), &ninl, nullptr,
                              &st, counts);
 }

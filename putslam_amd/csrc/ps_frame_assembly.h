@@ -2,9 +2,10 @@
 // of DBScan's survivors, the undistortion and back-projection of the described key points in the described order with the
 // detection distances, and the PsFrontEnd handle that runs detect, thin, gather, pyramid build, describe and assemble on one stream.
 // Part of the device translation unit (ps_capi.hip), after ps_dbscan.h, ps_orb.h and ps_orb_detect.h, whose launches it queues.
-// Both kernels: one thread per output row, a grid of row blocks x frames, no LDS; the arithmetic is ps_kernels.h's undistort_point,
+// Both kernels: one thread per output row, a grid of row blocks x frames, no LDS; the arithmetic is ps_geometry.h's undistort_point,
 // depth_rule_offset and point_from_depth, stated there once.
 #pragma once
+#include "ps_geometry.h" // DistArgs, undistort_point, depth_rule_offset, depth_pixel, point_from_depth
 
 namespace psdev {
 
@@ -18,7 +19,7 @@ struct AssembleArgs {
 };
 
 // The undistorted position q of the distorted p and its 3-D point in the depth frame at `frame` (null: no depth image, depth 0 --
-// the keypoints2Dto3D result for no depth): ps_kernels.h's undistort_point, depth_rule_offset, depth_pixel and point_from_depth.
+// the keypoints2Dto3D result for no depth): ps_geometry.h's undistort_point, depth_rule_offset, depth_pixel and point_from_depth.
 // point2Dto3D of q in one frame of a depth set (ps_uncertainty.h back-projects pixels with it too)
 PS_D void back_project_in_frame(float2 q, float fx, float fy, float cx, float cy, double scale, const uint8_t *__restrict__ frame, size_t rowStride,
                                 int rows, int cols, float &X, float &Y, float &Z)

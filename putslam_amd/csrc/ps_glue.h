@@ -49,6 +49,21 @@ inline void begin_timed_call(PsContext *ctx)
     ctx->slotMask[ctx->curCall] = 0;
 }
 
+void tick(PsContext *ctx, int slot, bool stop)
+{
+    if (!ctx->timing || slot >= kMaxTimed || ctx->ev.empty()) return;
+    (void)hipEventRecord(ctx->ev[((size_t)ctx->curCall * kMaxTimed + slot) * 2 + (stop ? 1 : 0)], ctx->stream);
+    if (stop) {
+        ctx->slotMask[ctx->curCall] |= 1u << slot;
+        if (slot + 1 > ctx->nTimed) ctx->nTimed = slot + 1;
+    }
+}
+
+void identity16(float *T)
+{
+    for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+}
+
 // Bytes between consecutive frames of a PsFrameSet, resolved, and the same in the units the kernels index with.
 struct FrameStrides {
     size_t desc = 0, pts = 0;

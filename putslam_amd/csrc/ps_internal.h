@@ -219,6 +219,7 @@ inline int bind(PsContext *ctx)
 // RANSAC::computeRANSACIteration (RANSAC.cpp:457-461) / USAC<T>::updateStandardStopping (USAC.h:944-971) with the host's libm, and the
 // threshold tables the device binary-searches instead of evaluating log / pow
 int ransac_iterations_host(double inlierRatio, double successProbability = 0.98, int numberOfPairs = 3);
+int scored_hypotheses(int estimator, int numHypotheses, double minRatio);
 unsigned usac_stopping_host(double prob_good_model);
 void build_ransac_table(double minRatio, int H, std::vector<float> &tab, int &iter0, float &tiny);
 void build_usac_table(int H, std::vector<double> &tab);

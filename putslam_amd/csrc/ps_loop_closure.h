@@ -26,7 +26,7 @@
 
 #include "ps_glue.h"
 #include "ps_block.h" // block_scan_int, block_scan_flag
-#include "ps_kernels.h"
+#include "ps_ransac_stage.h"
 
 namespace psdev {
 

@@ -1,7 +1,15 @@
-// ps_map_match.h -- batched, device-resident guided map matching: Matcher::matchXYZ (reference src/Matcher/matcher.cpp:694-746)
-// for P (map view, frame) pairs in two launches, no host step, for 32-byte binary rows (ps_match_xyz_device /
-// ps_map_pairs_device, include/putslam_hip.h) and, through ps_map_match_l2.h, for SURF / SIFT float rows.
-// The rule is ps_match_xyz_kernel's (ps_kernels.h), which sweeps a frame twice between a count, a scan and a write launch:
+// ps_map_match.h -- guided map matching: Matcher::matchXYZ (reference src/Matcher/matcher.cpp:694-746) for P (map view, frame)
+// pairs of a device-resident batch in two launches, no host step, for 32-byte binary rows (ps_match_xyz_device /
+// ps_map_pairs_device, include/putslam_hip.h) and, through ps_map_match_l2.h, for SURF / SIFT float rows; the host-pointer
+// forms (ps_match_xyz here, ps_match_xyz_l2_f32 there) stage one pair and take the same two launches (match_xyz_host).
+// The rule, per map feature j:
+//   candidate i : |mapPos[j] - curPos[i]| < sphereRadius (float norm against a double radius, exact
+//                 squared-domain bound) and |predictedLevel[i] - level[j]| <= 1          (:699-711)
+//   value(i)    : popcount of the per-byte SATURATING difference mapDesc[j] - curDesc[i]
+//                 (cv::Mat subtraction of CV_8U + NORM_HAMMING, :719-721 -- not XOR Hamming; float rows: ps_map_match_l2.h)
+//   best        : smallest value, first index on ties                                      (:714-727)
+//   accepted    : acceptRatio * value <= best (double)                                     (:734-746)
+// and the output is ordered by (j, i) like the reference's push_back loop.
 //
 //   map_sweep<F, D>   THE sweep, once, for a descriptor policy D; the kernels ps_map_sweep<F> (MapBinRows, below) and
 //                     ps_map_sweep_l2<F> (MapL2Rows, ps_map_match_l2.h) are its two instantiations.
@@ -10,8 +18,7 @@
 //                     read serves F sphere tests.  Candidates are rare (0 - 3 per feature at the first try of the retry ladder,
 //                     up to 14 at the tenth): a feature's candidates (i, value bits) are appended in ballot order -- ascending
 //                     i -- to a stash of kMapStash entries in LDS, and best / ratio / emit work on that list.  A feature with
-//                     more candidates than the stash holds is swept again from global memory (map_resweep, the old kernel's
-//                     second sweep).  The chunk's accepted matches, ordered by (j, i), go to a place in the pair's row of a
+//                     more candidates than the stash holds is swept again from global memory (map_resweep).  The chunk's accepted matches, ordered by (j, i), go to a place in the pair's row of a
 //                     staging block that the chunk reserves with ONE atomic add; (start, count) are kept per chunk.
 //   ps_map_emit       grid P.  Scans the pair's chunk counts and moves the chunks to the output row in chunk order -- the
 //                     (j, i) order of the reference's push_back loop whatever order the chunks ran in -- and, in the same pass
@@ -29,8 +36,10 @@
 //   best_value(best, list, cnt, s)  bestVal of a feature with cnt > 0 candidates
 //   value(j, i)                  one lane, one candidate, from global memory: map_resweep's value
 #pragma once
+#include "ps_block.h" // the integer and flag scans, wave minima
 #include "ps_glue.h"
-#include "ps_kernels.h"
+#include "ps_pair_records.h" // PrepArgs, RecPtrs, PairRecords
+#include "ps_ransac_stage.h" // Plan, make_plan, prepare_score, ensure_records, rec_ptrs, run_ransac_stage
 
 namespace psdev {
 
@@ -267,6 +276,23 @@ template <int F, class D> PS_D void map_sweep(const typename D::Args &b)
     }
 }
 
+// popcount of the per-byte saturating difference a - b of two 32-byte rows
+PS_D uint32_t satdiff_popc256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
+{
+    const uint32_t aw[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+    const uint32_t bw[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+    uint32_t v = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int d = (int)((aw[w] >> (8 * k)) & 0xFFu) - (int)((bw[w] >> (8 * k)) & 0xFFu);
+            d = d < 0 ? 0 : d;
+            v += (uint32_t)__popc((unsigned)d);
+        }
+    return v;
+}
+
 // The binary policy: 32-byte rows, the value is the popcount of the difference -- cheap enough to evaluate inside the hit branch,
 // where each lane also keeps its least (value << 32 | i), so that bestVal is one wave minimum.
 struct MapBinArgs {
@@ -374,11 +400,13 @@ __global__ __launch_bounds__(BLOCK) void ps_map_emit(MapArgs a, PrepArgs pa, Rec
 
 } // namespace psdev
 
-// Host side: Matcher::matchXYZ, matcher.cpp:606-798, for a device-resident batch.  Part of the device translation unit: included
-// by ps_capi.hip behind the plan and the stages (Plan, make_plan, prepare_score, ensure_records, rec_ptrs, tick, run_ransac_stage).
+// Host side: Matcher::matchXYZ, matcher.cpp:606-798, for a device-resident batch.  Part of the device translation unit, on the
+// plan and the stages of ps_ransac_stage.h (Plan, make_plan, prepare_score, ensure_records, rec_ptrs, run_ransac_stage).
 // A batch KIND names what differs between PsMapBatch and PsMapBatchF32 -- Batch, Args (the policy's argument block), what (the
 // prefix of the messages), sweeps() (the kernel per F) and sets(ctx, b, l): the rule of the two frame sets, which leaves the
-// descriptor arguments and the point strides of a batch that passed in l.  MapBinKind is below, MapL2Kind in ps_map_match_l2.h.
+// descriptor arguments and the point strides of a batch that passed in l -- and, for the host-pointer form, Elem (what a row is
+// made of), host_rows (the rule of dim and of the row pitches, with the entry's own texts) and set_dim.  MapBinKind is below,
+// MapL2Kind in ps_map_match_l2.h.
 namespace {
 
 // Map features per wave of the sweep: eight when that still gives every CU several work-groups, fewer for a handful of pairs
@@ -514,10 +542,83 @@ int map_pairs_body(PsContext *ctx, const char *who, const PsRansacParams *params
     return run_ransac_stage(ctx, pl, P, cap, out->matches, clamped, cap, out->pose, out->inlierMask, out->stats, 2);
 }
 
+// ps_match_xyz / ps_match_xyz_l2_f32: host arrays, rows of dim Kind::Elem.  One pair is staged in the context's scratch and
+// goes through the batch's check and launches; a negative count from the device is the needed capacity.
+template <class Kind>
+int match_xyz_host(PsContext *ctx, const std::string &who, const float *mapPos, const typename Kind::Elem *mapDesc, size_t mapDescStep,
+                   const int32_t *mapLevel, int nmap, const float *curPos, const typename Kind::Elem *curDesc, size_t curDescStep,
+                   const int32_t *curLevel, int ncur, int dim, double sphereRadius, double acceptRatio, PsDMatch *out, int cap, int *nout)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    TimingOff toff(ctx);
+    if (nout) *nout = 0;
+    if (!nout || nmap < 0 || ncur < 0 || cap < 0 || dim < 1 || (cap > 0 && !out) || (nmap > 0 && (!mapPos || !mapDesc || !mapLevel)) ||
+        (ncur > 0 && (!curPos || !curDesc || !curLevel)))
+        return fail(ctx, PS_ERR_BAD_ARG, (who + ": bad argument").c_str());
+    const size_t row = (size_t)dim * sizeof(typename Kind::Elem);
+    rc = Kind::host_rows(ctx, dim, (nmap > 0 && mapDescStep < row) || (ncur > 0 && curDescStep < row));
+    if (rc) return rc;
+    if (nmap > PS_MAX_KPTS || ncur > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, (who + ": more than PS_MAX_KPTS rows").c_str());
+    if (nmap == 0 || ncur == 0) return PS_OK;
+    const int devCap = cap < 1 ? 1 : (cap > (1 << 22) ? (1 << 22) : cap);
+    PS_ENSURE(ctx->sMisc0, (size_t)nmap * 12);
+    PS_ENSURE(ctx->sMisc1, (size_t)ncur * 12);
+    PS_ENSURE(ctx->sDesc, (size_t)(nmap + ncur) * row);
+    PS_ENSURE(ctx->sNk, (size_t)(nmap + ncur + 4) * sizeof(int32_t));
+    PS_ENSURE(ctx->sMask, (size_t)devCap * sizeof(PsDMatch)); // (the device rows of `out`: sMatches is the batch's staging)
+    PS_ENSURE(ctx->sNumM, sizeof(int32_t));
+    uint8_t *dDesc = (uint8_t *)ctx->sDesc.p;
+    int32_t *dLvl = (int32_t *)ctx->sNk.p, *dMeta = dLvl + nmap + ncur;
+    PS_HIP(hipMemcpyAsync(ctx->sMisc0.p, mapPos, (size_t)nmap * 12, hipMemcpyHostToDevice, ctx->stream));
+    PS_HIP(hipMemcpyAsync(ctx->sMisc1.p, curPos, (size_t)ncur * 12, hipMemcpyHostToDevice, ctx->stream));
+    PS_HIP(hipMemcpy2DAsync(dDesc, row, mapDesc, mapDescStep, row, (size_t)nmap, hipMemcpyHostToDevice, ctx->stream));
+    PS_HIP(hipMemcpy2DAsync(dDesc + (size_t)nmap * row, row, curDesc, curDescStep, row, (size_t)ncur, hipMemcpyHostToDevice, ctx->stream));
+    PS_HIP(hipMemcpyAsync(dLvl, mapLevel, (size_t)nmap * 4, hipMemcpyHostToDevice, ctx->stream));
+    PS_HIP(hipMemcpyAsync(dLvl + nmap, curLevel, (size_t)ncur * 4, hipMemcpyHostToDevice, ctx->stream));
+    const int32_t hostMeta[4] = {nmap, ncur, 0, 0}; // the two counts, the pair (view 0, frame 0)
+    PS_HIP(hipMemcpyAsync(dMeta, hostMeta, sizeof hostMeta, hipMemcpyHostToDevice, ctx->stream));
+    PS_HIP(hipStreamSynchronize(ctx->stream)); // hostMeta goes out of scope
+    typename Kind::Batch b{};
+    b.maps.desc = (const typename Kind::Elem *)dDesc; b.maps.pts = (const float *)ctx->sMisc0.p; b.maps.nkpts = dMeta;
+    b.maps.numFrames = 1; b.maps.maxKpts = nmap;
+    b.frames.desc = (const typename Kind::Elem *)(dDesc + (size_t)nmap * row); b.frames.pts = (const float *)ctx->sMisc1.p; b.frames.nkpts = dMeta + 1;
+    b.frames.numFrames = 1; b.frames.maxKpts = ncur;
+    Kind::set_dim(b, dim);
+    b.mapLevel = dLvl; b.curLevel = dLvl + nmap;
+    b.pairs = dMeta + 2;
+    b.P = 1;
+    b.maxMatches = devCap;
+    b.radiusBound = sq_bound_f32(sphereRadius); // (float)norm < (double)radius  <=>  squared sum < bound
+    b.acceptRatio = acceptRatio;
+    typename Kind::Args l{};
+    rc = check_map_batch<Kind>(ctx, &b, l);
+    if (rc) return rc;
+    rc = run_map_match<Kind>(ctx, b, l, nullptr, (PsDMatch *)ctx->sMask.p, (int32_t *)ctx->sNumM.p, nullptr, 0);
+    if (rc) return rc;
+    int32_t n = 0;
+    PS_HIP(hipMemcpyAsync(&n, ctx->sNumM.p, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
+    PS_HIP(hipStreamSynchronize(ctx->stream));
+    const int total = n < 0 ? -n : n;
+    *nout = total;
+    if (total > cap) return fail(ctx, PS_ERR_BAD_ARG, (who + ": output capacity too small (*nout = needed)").c_str());
+    if (total > 0) {
+        PS_HIP(hipMemcpyAsync(out, ctx->sMask.p, (size_t)total * sizeof(PsDMatch), hipMemcpyDeviceToHost, ctx->stream));
+        PS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PS_OK;
+}
+
 struct MapBinKind {
     using Batch = PsMapBatch;
     using Args = MapBinArgs;
+    using Elem = uint8_t;
     static constexpr const char *what = "map batch";
+    static int host_rows(PsContext *ctx, int, bool shortPitch)
+    {
+        return shortPitch ? fail(ctx, PS_ERR_UNSUPPORTED, "descriptor rows must be 32 bytes (ORB/LDB)") : PS_OK;
+    }
+    static void set_dim(Batch &, int) {}
     static MapSweeps<Args> sweeps() { return {ps_map_sweep<1>, ps_map_sweep<2>, ps_map_sweep<4>, ps_map_sweep<8>}; }
     static int sets(PsContext *ctx, const Batch &b, Args &l)
     {
@@ -538,6 +639,14 @@ extern "C" {
 float ps_map_sphere_bound(double sphereRadius) { return sq_bound_f32(sphereRadius); }
 
 size_t ps_abi_sizeof_map_batch(void) { return sizeof(PsMapBatch); }
+
+int ps_match_xyz(PsContext *ctx, const float *mapPos, const uint8_t *mapDesc, size_t mapDescStep, const int32_t *mapLevel,
+                 int nmap, const float *curPos, const uint8_t *curDesc, size_t curDescStep, const int32_t *curLevel, int ncur,
+                 double sphereRadius, double acceptRatio, PsDMatch *out, int cap, int *nout)
+{
+    return match_xyz_host<MapBinKind>(ctx, "ps_match_xyz", mapPos, mapDesc, mapDescStep, mapLevel, nmap, curPos, curDesc, curDescStep, curLevel,
+                                      ncur, PS_DESC_BYTES, sphereRadius, acceptRatio, out, cap, nout);
+}
 
 int ps_match_xyz_device(PsContext *ctx, const PsMapBatch *b, PsDMatch *matches, int32_t *numMatches)
 {

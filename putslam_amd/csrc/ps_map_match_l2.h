@@ -25,7 +25,6 @@
 //                       (least value, count, write), evaluating values on the way: slow and correct.
 #pragma once
 #include "ps_glue.h"
-#include "ps_kernels.h"
 #include "ps_map_match.h"
 
 namespace psdev {
@@ -140,7 +139,14 @@ namespace {
 struct MapL2Kind {
     using Batch = PsMapBatchF32;
     using Args = MapL2Args;
+    using Elem = float;
     static constexpr const char *what = "float map batch";
+    static int host_rows(PsContext *ctx, int dim, bool shortPitch)
+    {
+        if (dim > PS_MAX_L2_DIM) return fail(ctx, PS_ERR_UNSUPPORTED, "ps_match_xyz_l2_f32: more than PS_MAX_L2_DIM elements per descriptor");
+        return shortPitch ? fail(ctx, PS_ERR_BAD_ARG, "ps_match_xyz_l2_f32: row pitch below dim x 4 bytes") : PS_OK;
+    }
+    static void set_dim(Batch &b, int dim) { b.maps.dim = b.frames.dim = dim; }
     static MapSweeps<Args> sweeps() { return {ps_map_sweep_l2<1>, ps_map_sweep_l2<2>, ps_map_sweep_l2<4>, ps_map_sweep_l2<8>}; }
     static int sets(PsContext *ctx, const Batch &b, Args &l)
     {
@@ -171,64 +177,8 @@ int ps_match_xyz_l2_f32(PsContext *ctx, const float *mapPos, const float *mapDes
                         const float *curPos, const float *curDesc, size_t curDescStep, const int32_t *curLevel, int ncur, int dim,
                         double sphereRadius, double acceptRatio, PsDMatch *out, int cap, int *nout)
 {
-    int rc = bind(ctx);
-    if (rc) return rc;
-    TimingOff toff(ctx);
-    if (nout) *nout = 0;
-    if (!nout || nmap < 0 || ncur < 0 || cap < 0 || dim < 1 || (cap > 0 && !out) || (nmap > 0 && (!mapPos || !mapDesc || !mapLevel)) ||
-        (ncur > 0 && (!curPos || !curDesc || !curLevel)))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_match_xyz_l2_f32: bad argument");
-    if (dim > PS_MAX_L2_DIM) return fail(ctx, PS_ERR_UNSUPPORTED, "ps_match_xyz_l2_f32: more than PS_MAX_L2_DIM elements per descriptor");
-    const size_t row = (size_t)dim * 4;
-    if ((nmap > 0 && mapDescStep < row) || (ncur > 0 && curDescStep < row))
-        return fail(ctx, PS_ERR_BAD_ARG, "ps_match_xyz_l2_f32: row pitch below dim x 4 bytes");
-    if (nmap > PS_MAX_KPTS || ncur > PS_MAX_KPTS) return fail(ctx, PS_ERR_UNSUPPORTED, "ps_match_xyz_l2_f32: more than PS_MAX_KPTS rows");
-    if (nmap == 0 || ncur == 0) return PS_OK;
-    const int devCap = cap < 1 ? 1 : (cap > (1 << 22) ? (1 << 22) : cap);
-    PS_ENSURE(ctx->sMisc0, (size_t)nmap * 12);
-    PS_ENSURE(ctx->sMisc1, (size_t)ncur * 12);
-    PS_ENSURE(ctx->sDesc, (size_t)(nmap + ncur) * row);
-    PS_ENSURE(ctx->sNk, (size_t)(nmap + ncur + 4) * sizeof(int32_t));
-    PS_ENSURE(ctx->sMask, (size_t)devCap * sizeof(PsDMatch)); // (the device rows of `out`: sMatches is the batch's staging)
-    PS_ENSURE(ctx->sNumM, sizeof(int32_t));
-    uint8_t *dDesc = (uint8_t *)ctx->sDesc.p;
-    int32_t *dLvl = (int32_t *)ctx->sNk.p, *dMeta = dLvl + nmap + ncur;
-    PS_HIP(hipMemcpyAsync(ctx->sMisc0.p, mapPos, (size_t)nmap * 12, hipMemcpyHostToDevice, ctx->stream));
-    PS_HIP(hipMemcpyAsync(ctx->sMisc1.p, curPos, (size_t)ncur * 12, hipMemcpyHostToDevice, ctx->stream));
-    PS_HIP(hipMemcpy2DAsync(dDesc, row, mapDesc, mapDescStep, row, (size_t)nmap, hipMemcpyHostToDevice, ctx->stream));
-    PS_HIP(hipMemcpy2DAsync(dDesc + (size_t)nmap * row, row, curDesc, curDescStep, row, (size_t)ncur, hipMemcpyHostToDevice, ctx->stream));
-    PS_HIP(hipMemcpyAsync(dLvl, mapLevel, (size_t)nmap * 4, hipMemcpyHostToDevice, ctx->stream));
-    PS_HIP(hipMemcpyAsync(dLvl + nmap, curLevel, (size_t)ncur * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int32_t hostMeta[4] = {nmap, ncur, 0, 0}; // the two counts, the pair (view 0, frame 0)
-    PS_HIP(hipMemcpyAsync(dMeta, hostMeta, sizeof hostMeta, hipMemcpyHostToDevice, ctx->stream));
-    PS_HIP(hipStreamSynchronize(ctx->stream)); // hostMeta goes out of scope
-    PsMapBatchF32 b{};
-    b.maps.desc = (const float *)dDesc; b.maps.pts = (const float *)ctx->sMisc0.p; b.maps.nkpts = dMeta;
-    b.maps.numFrames = 1; b.maps.maxKpts = nmap; b.maps.dim = dim;
-    b.frames.desc = (const float *)(dDesc + (size_t)nmap * row); b.frames.pts = (const float *)ctx->sMisc1.p; b.frames.nkpts = dMeta + 1;
-    b.frames.numFrames = 1; b.frames.maxKpts = ncur; b.frames.dim = dim;
-    b.mapLevel = dLvl; b.curLevel = dLvl + nmap;
-    b.pairs = dMeta + 2;
-    b.P = 1;
-    b.maxMatches = devCap;
-    b.radiusBound = sq_bound_f32(sphereRadius); // (float)norm < (double)radius  <=>  squared sum < bound
-    b.acceptRatio = acceptRatio;
-    MapL2Args l{};
-    rc = check_map_batch<MapL2Kind>(ctx, &b, l);
-    if (rc) return rc;
-    rc = run_map_match<MapL2Kind>(ctx, b, l, nullptr, (PsDMatch *)ctx->sMask.p, (int32_t *)ctx->sNumM.p, nullptr, 0);
-    if (rc) return rc;
-    int32_t n = 0;
-    PS_HIP(hipMemcpyAsync(&n, ctx->sNumM.p, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
-    PS_HIP(hipStreamSynchronize(ctx->stream));
-    const int total = n < 0 ? -n : n;
-    *nout = total;
-    if (total > cap) return fail(ctx, PS_ERR_BAD_ARG, "ps_match_xyz_l2_f32: output capacity too small (*nout = needed)");
-    if (total > 0) {
-        PS_HIP(hipMemcpyAsync(out, ctx->sMask.p, (size_t)total * sizeof(PsDMatch), hipMemcpyDeviceToHost, ctx->stream));
-        PS_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return PS_OK;
+    return match_xyz_host<MapL2Kind>(ctx, "ps_match_xyz_l2_f32", mapPos, mapDesc, mapDescStep, mapLevel, nmap, curPos, curDesc, curDescStep,
+                                     curLevel, ncur, dim, sphereRadius, acceptRatio, out, cap, nout);
 }
 
 int ps_match_xyz_l2_device(PsContext *ctx, const PsMapBatchF32 *b, PsDMatch *matches, int32_t *numMatches)

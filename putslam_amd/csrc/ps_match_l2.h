@@ -23,7 +23,8 @@
 //                       prefilter in front of the value-exact code (described with its error band further down); the same keys.
 #pragma once
 #include "ps_glue.h"
-#include "ps_kernels.h"
+#include "ps_match_stage.h"
+#include "ps_ransac_stage.h"
 #include "ps_map_match.h"
 #include "ps_matcher_mfma.h"
 

@@ -32,13 +32,17 @@
 // 2s + h of row r, and fp4_word below -- the one expansion rule of every form and both sides -- puts bit 4 i + j of that
 // dword into nibble i of the lane's operand register j.
 //
-// The integer VALU kernel ps_hamming_nn (ps_kernels.h) is kept as the tested twin
+// The integer VALU kernel ps_hamming_nn (ps_match_stage.h) is kept as the tested twin
 // (PUTSLAM_HIP_MATCHER=valu / ps_context_set_option("matcher", 0)).
 #pragma once
 
-#include "ps_kernels.h"
+#include "ps_block.h" // kBlock, xcd_remap
+#include "ps_device_math.h"
 
 namespace psdev {
+
+// a keys entry no train row has written: both matchers' blocks are all-ones at rest (kernel 2 puts it back)
+constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v8i_t __attribute__((ext_vector_type(8)));

@@ -2,7 +2,7 @@
 // A route walks the pair's match list in order, drops the matches whose points fail the depth filter (RANSAC.cpp:65-74),
 // compacts the survivors in order and hands each to PairRecords, which writes the scoring records (write_records), keeps
 // the pair's bounds and, at the end, writes the valid count and the bounds and clears the scoring stage's counters.
-// The routes: ps_crosscheck_prep (ps_kernels.h), ps_l2_crosscheck (ps_match_l2.h), ps_map_emit (ps_map_match.h) and the
+// The routes: ps_crosscheck_prep (ps_match_stage.h), ps_l2_crosscheck (ps_match_l2.h), ps_map_emit (ps_map_match.h) and the
 // caller's lists below (ps_prep_from_matches, ps_prep_match_lists).  A route keeps only what is its own: how it finds match
 // i, its compaction scan, and how it writes matches / numMatches.
 #pragma once

@@ -3,7 +3,7 @@
 // RANSAC::computeMatchInlierRatioEuclidean (reference src/TransformEst/RANSAC.cpp:251-281) decides, for every
 // (hypothesis, match), whether  |R cur + t - prev|  stays below inlierThresholdEuclidean (times prev.z when errorVersion
 // is ADAPTIVE_ERROR, :268-271).  Every configuration the reference ships runs this metric (errorVersionVO = 0 in
-// resources/putslammatcherOpenCVParameters.xml:30-31 and in all configs/*).  ps_ransac_score<0/4> (ps_kernels.h)
+// resources/putslammatcherOpenCVParameters.xml:30-31 and in all configs/*).  ps_ransac_score<0/4> (ps_score_value.h)
 // reproduces every intermediate value bit for bit: 19 vector instructions per evaluation.  Only the DECISION has to
 // equal the reference's; this kernel takes it from a cheap evaluation with a proven error band and hands the evaluations
 // inside the band to the value-exact inlier_test<MODE>():

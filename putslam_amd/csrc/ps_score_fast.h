@@ -2,7 +2,7 @@
 //
 // RANSAC::computeInlierRatioReprojection (reference src/TransformEst/RANSAC.cpp:325-375) decides, for every
 // (hypothesis, match), whether two reprojection errors stay below inlierThresholdReprojection.  Only that
-// DECISION has to equal the reference's; ps_ransac_score<1> (ps_kernels.h) reproduces every intermediate VALUE
+// DECISION has to equal the reference's; ps_ransac_score<1> (ps_score_value.h) reproduces every intermediate VALUE
 // bit for bit (two rigid transforms without FMA, four IEEE quotients, two cv::norm tests: 61 VALU instructions
 // per evaluation).  This kernel takes the decision from a cheap evaluation with a proven error band and hands the
 // evaluations that fall inside the band to the value-exact code:
@@ -44,7 +44,7 @@
 //   for every hypothesis (tests: test_hypothesis_counts_bit_exact, test_score_variants_*, the fuzz slice).
 //
 // A wavefront whose bounds do not hold (non-finite model, S fmaxK > 2^40, threshold outside [1e-10, 1e15]) runs
-// the value-exact loop of ps_kernels.h instead.
+// the value-exact loop of ps_score_value.h instead.
 //
 // The staged-scoring protocol around the sweep (StageArgs, the replay of the prefix, the frame of a pass and the walk of a work-group
 // over its passes) is ps_score_pass.h's, shared with ps_score_euclid.h; ps_stage_reorder, which runs between stage 0 and stage 1 of

@@ -9,7 +9,8 @@
 // ps_score_plan.h, where a CPU test runs it.
 #pragma once
 
-#include "ps_kernels.h"
+#include "ps_score_value.h"
+#include "ps_select_refit.h"
 #include "ps_score_plan.h"
 
 namespace psdev {

@@ -38,6 +38,90 @@
 //   * results are those of ONE ps_vo_pairs_device call over the whole sequence: pair k draws from cfg->seed + k.
 #pragma once
 #include "ps_stream_ledger.h" // every integer of the pipeline and the rule that makes reuse safe; the result block's layout
+#include "ps_stream_push.h"   // PsVoStream, ps_copy_segments
+
+namespace psdev {
+
+// Small chunks of the pipelined stream (chunkFrames <= 4: ps_stream_async.h, "mini" chunks): everything that changes from chunk to
+// chunk travels as DATA through this block, so that a place's whole chunk -- frames in, kernels 1 - 4, results out -- is one
+// captured hipGraph.  The host fills it in the place's pinned meta block; ps_mini_copy_in copies it to the device meta block,
+// which the kernels behind it read (row counts, pair list, seed).
+constexpr int kMiniFrames = 4;
+struct MiniMeta {
+    int32_t pairs[2 * kMiniFrames]; // the chunk's pairs in the place's private frame set: slot 0 = the previous frame (halo), 1 .. n = the chunk's
+    int32_t nk[kMiniFrames + 1];    // row counts of the private frames
+    int32_t n, first, pad;          // frames in the chunk; 1 = its first frame has no predecessor (slot 0 is not copied)
+    unsigned long long seed;        // hypothesis seed of the chunk's first pair (cfg->seed + its number in the stream)
+    const uint8_t *src[kMiniFrames + 1]; // device views of the pinned packed frames [cap x 32 B][cap x 12 B]: [0] the halo, [1 .. n] the chunk's
+};
+
+// Frames of a mini chunk from pinned host memory into the place's private frame set (packed layout, `stride` bytes per frame),
+// and the meta block with them.  grid = (kMiniFrames + 1) x groups work-groups: frame f is swept by `groups` of them.  The reads go
+// over the link: 88 KB per 2000-keypoint frame, a few microseconds (the synchronous ps_vo_stream_push moves its frame the same way).
+__global__ void __launch_bounds__(256) ps_mini_copy_in(const MiniMeta *__restrict__ hm, MiniMeta *__restrict__ dm, uint8_t *__restrict__ frames,
+                                                       int cap, unsigned long long stride, int groups)
+{
+    if (blockIdx.x == 0 && threadIdx.x < sizeof(MiniMeta) / 4)
+        reinterpret_cast<uint32_t *>(dm)[threadIdx.x] = reinterpret_cast<const uint32_t *>(hm)[threadIdx.x];
+    const int f = (int)(blockIdx.x / (unsigned)groups), g = (int)(blockIdx.x % (unsigned)groups);
+    const int n = hm->n, first = hm->first;
+    if (f > n || (f == 0 && first)) return;
+    const int rows = hm->nk[f];
+    // (the frame's address comes out of memory: told to be a global address, or the compiler emits FLAT loads for it)
+    typedef unsigned __attribute__((ext_vector_type(4))) u4v_t;
+    typedef const u4v_t __attribute__((address_space(1))) *gu4_t;
+    typedef const uint32_t __attribute__((address_space(1))) *gu32_t;
+    const uintptr_t src = reinterpret_cast<uintptr_t>(hm->src[f]);
+    uint8_t *__restrict__ dst = frames + (size_t)f * stride;
+    const size_t t0 = (size_t)g * blockDim.x + threadIdx.x, step = (size_t)groups * blockDim.x;
+    { // descriptors: rows x 32 bytes, 16 per lane
+        gu4_t sv = (gu4_t)src;
+        u4v_t *__restrict__ dv = reinterpret_cast<u4v_t *>(dst);
+        for (size_t i = t0; i < (size_t)rows * 2; i += step) dv[i] = sv[i];
+    }
+    { // points: rows x 12 bytes behind the cap x 32 descriptor bytes, 4 per lane
+        gu32_t sv = (gu32_t)(src + (size_t)cap * 32);
+        uint32_t *__restrict__ dv = reinterpret_cast<uint32_t *>(dst + (size_t)cap * 32);
+        for (size_t i = t0; i < (size_t)rows * 3; i += step) dv[i] = sv[i];
+    }
+}
+
+// Results of a chunk of the pipelined stream written straight into the lane's mapped pinned block, only what the caller asked
+// for (PsStreamResults): mode 1 = the INLIER matches of every pair in input order (what Matcher::match hands back,
+// matcher.cpp:452-516: `inlierMatches`) + pose + stats + match count; mode 2 = pose + stats + match count.  One work-group per
+// pair; ordered compaction by one ballot-prefix scan per 256 matches.  The writes go over the host link: 12 KB instead of 34 KB
+// per 2000-keypoint pair in mode 1, 108 bytes in mode 2.
+__global__ __launch_bounds__(kBlock) void ps_pack_results_to_host(const PsDMatch *__restrict__ matches,
+                                                                  const int32_t *__restrict__ numMatches,
+                                                                  const uint8_t *__restrict__ mask, const float *__restrict__ pose,
+                                                                  const PsRansacStats *__restrict__ stats, int cap, int mode,
+                                                                  PsDMatch *__restrict__ hMatches, float *__restrict__ hPose,
+                                                                  PsRansacStats *__restrict__ hStats, int32_t *__restrict__ hNum)
+{
+    __shared__ int s_w[2 * (kBlock / 64)];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int n = numMatches[p];
+    if (tid < 16) hPose[(size_t)p * 16 + tid] = pose[(size_t)p * 16 + tid];
+    if (tid == 0) {
+        hStats[p] = stats[p];
+        hNum[p] = n;
+    }
+    if (mode != 1) return;
+    const uint4 *__restrict__ src = reinterpret_cast<const uint4 *>(matches + (size_t)p * cap);
+    uint4 *__restrict__ dst = reinterpret_cast<uint4 *>(hMatches + (size_t)p * cap);
+    const uint8_t *__restrict__ mk = mask + (size_t)p * cap;
+    int base = 0, trip = 0;
+    for (int i0 = 0; i0 < n; i0 += kBlock, ++trip) {
+        const int i = i0 + tid;
+        const bool in = i < n && mk[i] != 0;
+        int pos, total, posB, totalB;
+        block_scan_flags2<kBlock, false>(in, false, pos, total, posB, totalB, s_w, trip);
+        if (in) dst[base + pos] = src[i];
+        base += total;
+    }
+}
+
+} // namespace psdev
 
 // One chunk's place in the pipeline: meta block, device and pinned result blocks, events.  There are lanes + ahead of them; a
 // chunk takes the next one and runs on the next LANE (a private PsContext: stream + scratch arena) in turn, so each lane's

@@ -1,7 +1,43 @@
 // ps_stream_push.h -- the synchronous streaming form of Matcher::match (ps_vo_stream_create / _destroy / _reset / _push,
-// include/putslam_hip.h).  Included by ps_capi.hip after the stages (it uses that file's Plan, run_match_stage and run_ransac_stage);
-// the pipelined form (ps_stream_async.h) builds on the PsVoStream defined here.
+// include/putslam_hip.h), on the plan and the stages (Plan, run_match_stage, run_ransac_stage); the pipelined form
+// (ps_stream_async.h) builds on the PsVoStream and the copy kernel defined here.
 #pragma once
+#include "ps_match_stage.h"
+#include "ps_ransac_stage.h"
+
+namespace psdev {
+
+// ------------------------------------------------------------------------------------------
+// Host <-> device transfers as a kernel over mapped pinned host memory (the streaming entry points: ps_vo_stream_push's frame in /
+// results out, the pipelined form's meta block).
+constexpr int kCopySegs = 5;
+struct CopySegs {
+    const void *src[kCopySegs];
+    void *dst[kCopySegs];
+    unsigned long long bytes[kCopySegs]; // multiples of 4
+    int n;
+};
+
+// Host <-> device transfer as a kernel: every segment is swept grid-stride, 16 bytes per lane where source, destination and
+// length allow it, 4 bytes otherwise.  One side of every segment is mapped pinned host memory: the accesses go over the link.
+__global__ void __launch_bounds__(256) ps_copy_segments(CopySegs cs)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int k = 0; k < cs.n; ++k) {
+        const size_t bytes = cs.bytes[k];
+        if ((((size_t)cs.src[k] | (size_t)cs.dst[k] | bytes) & 15) == 0) {
+            const uint4 *__restrict__ s = (const uint4 *)cs.src[k];
+            uint4 *__restrict__ d = (uint4 *)cs.dst[k];
+            for (size_t i = t0; i < bytes / 16; i += stride) d[i] = s[i];
+        } else {
+            const uint32_t *__restrict__ s = (const uint32_t *)cs.src[k];
+            uint32_t *__restrict__ d = (uint32_t *)cs.dst[k];
+            for (size_t i = t0; i < bytes / 4; i += stride) d[i] = s[i];
+        }
+    }
+}
+
+} // namespace psdev
 
 // ---------------------------------------------------------------------------------------------
 // Streaming form of Matcher::match (reference src/Matcher/matcher.cpp:452-516): the previous frame's

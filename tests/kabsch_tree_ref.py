@@ -1,7 +1,7 @@
 """The summation tree of ps_kabsch_f64 restated in numpy (no GPU), plus the point-cloud families and the extended-precision
 reference that tests/test_kabsch_tree_host.py and tests/test_gpu_standalone_geometry.py share.
 
-kabsch_tree(A, B, ld) performs, operation for operation, what the kernels of putslam_amd/csrc/ps_kernels.h perform:
+kabsch_tree(A, B, ld) performs, operation for operation, what the kernels of putslam_amd/csrc/ps_geometry.h perform:
 
   n <= 16384 (ps_kabsch_f64_kernel, one wavefront, G = 1) and n > 16384 (ps_kabsch_f64_sums / _cov / _finish, G =
   min(ceil(n / 4096), 1024) wavefronts) share the shape

@@ -536,3 +536,18 @@ def test_argument_errors_leave_the_outputs_alone(ctx, ragged):
     assert host(8, mpos=None) == BAD
     assert host(8, nout=None) == BAD
     assert host(8) == 0 and n.value == 16         # (zero positions, levels and rows: every row is a candidate of every row)
+
+    # ... and the binary host call's (ps_match_xyz, the same host form): more than PS_MAX_KPTS rows on a side; a capacity that
+    # is too small reports the needed one and leaves `out` alone
+    def host_bin(nmap, ncur, cap, outbuf):
+        zp, zd, zl = np.zeros((max(nmap, ncur), 3), np.float32), np.zeros((max(nmap, ncur), 32), np.uint8), np.zeros(max(nmap, ncur), np.int32)
+        return ctx._L.ps_match_xyz(ctx._h, p(zp), p(zd), 32, p(zl), nmap, p(zp), p(zd), 32, p(zl), ncur, C.c_double(0.12), C.c_double(0.55),
+                                   p(outbuf), cap, C.byref(n))
+
+    n.value = 5
+    assert host_bin(16385, 1, 16, out) == UNSUP and n.value == 0
+    assert host_bin(1, 16385, 16, out) == UNSUP and n.value == 0
+    kept = np.full(16 * DMATCH_DTYPE.itemsize, 0xA5, np.uint8).view(DMATCH_DTYPE)
+    before = kept.tobytes()
+    assert host_bin(2, 2, 0, kept) == BAD and n.value == 4  # (every row is a candidate of every row)
+    assert kept.tobytes() == before
