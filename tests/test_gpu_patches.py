@@ -18,7 +18,13 @@ pytestmark = pytest.mark.gpu
 
 POISON = 0xA5
 SHIFTS = [(0, 0), (1, -1), (0, 1)]      # frame k is the texture read at this offset (rows, cols)
-WAVES = 4                               # of a work-group, for every patch size below 23
+
+
+def block_waves(ps):
+    """patch_block_waves (ps_patches_rule.h): the waves of a work-group -- as many as 64 KiB of LDS hold, four at most, at 28 bytes
+    for each of a wave's E rounded up to a multiple of four elements"""
+    return min(4, 65536 // (((ps * ps + 3) & ~3) * 28))
+
 
 
 @pytest.fixture(scope="module")
@@ -152,13 +158,14 @@ def drawn(shape, ps, n, seed, flat=True):
 SHAPES = [(48, 64, 1), (61, 97, 3)]
 
 
-@pytest.mark.parametrize("ps", [3, 5, 13, 15, 17, 31])
+@pytest.mark.parametrize("ps", [3, 5, 7, 9, 13, 15, 17, 23, 25, 27, 29, 31])
 @pytest.mark.parametrize("shape", SHAPES, ids=["64x48x1", "97x61x3"])
 def test_align_equals_the_specification(ctx, shape, ps):
-    """P = 3 pairs -- one names a slot twice --, 65 / 9 / 1 points, fused, the model written: every byte"""
+    """P = 3 pairs -- one names a slot twice --, 65 / 2 x waves + 1 / 1 points (waves: 4 up to 23, 3 at 25 and 27, 2 from 29), fused,
+    the model written: every byte"""
     pairs = [(0, 1), (1, 1), (2, 0)]
     params = prm(ps, 50, 0.04 if ps >= 13 else 5e-7)
-    lists = [drawn(shape, ps, 65, 10 * ps), drawn(shape, ps, 2 * WAVES + 1, 10 * ps + 1, flat=False), drawn(shape, ps, 13, 10 * ps + 2)[11:12]]
+    lists = [drawn(shape, ps, 65, 10 * ps), drawn(shape, ps, 2 * block_waves(ps) + 1, 10 * ps + 1, flat=False), drawn(shape, ps, 13, 10 * ps + 2)[11:12]]
     res = run_align(ctx, shape, pairs, lists, params)
     seen = check_align(shape, pairs, res, params)
     assert {R.CONVERGED, R.OUT_OF_IMAGE, R.OLD_TAPS_OUTSIDE, R.NEW_TAPS_OUTSIDE} <= seen, seen
@@ -169,7 +176,7 @@ def test_align_equals_the_specification(ctx, shape, ps):
 @pytest.mark.parametrize("P", [1, 6])
 def test_counts_around_the_wave_and_the_work_group(ctx, P):
     shape, params = SHAPES[0], prm(13, 50, 0.04)
-    ns = [64] if P == 1 else [0, 1, 63, 64, 65, 2 * WAVES + 1]
+    ns = [64] if P == 1 else [0, 1, 63, 64, 65, 2 * block_waves(13) + 1]
     lists = [drawn(shape, 13, n, 300 + n) for n in ns]
     pairs = [(k % 3, (k + 1) % 3) for k in range(P)]
     res = run_align(ctx, shape, pairs, lists, params, padded=(P == 1))
@@ -240,8 +247,8 @@ def test_model_pass_and_given_model_equal_the_fused_call(ctx, ps):
         assert mst[p, :n].tolist() == [s if s in (2, 5) else 1 for s in fst[p, :n].tolist()]
     # ... and without a model block at all: the statuses alone
     st0 = poisoned((P, cap), np.uint8)
-    ctx.patch_models(D._patch_images(fused["images"]), slots.data_ptr(), dev(old, np.float64).data_ptr(), dev(cnt, np.int32).data_ptr(), P, cap, params,
-                     None, st0.data_ptr())
+    old_t, cnt_t = dev(old, np.float64), dev(cnt, np.int32)           # (held: a tensor dropped after data_ptr() lends its block to the next one)
+    ctx.patch_models(D._patch_images(fused["images"]), slots.data_ptr(), old_t.data_ptr(), cnt_t.data_ptr(), P, cap, params, None, st0.data_ptr())
     torch.cuda.synchronize()
     assert host(st0).tobytes() == mst.tobytes()
     # the alignment on the given model: the old slot (here: outside the set) and oldPts are not looked at

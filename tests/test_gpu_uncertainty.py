@@ -346,6 +346,54 @@ def test_measurement_edges_equal_numpy_and_the_restatement(ctx, model):
     assert all((got[m][4, k].view(np.uint64) == U.NAN_BITS).all() for m in MEMBERS)
 
 
+TRAIN_OUTSIDE = (-1, MAP_CAP, -2 ** 31, 2 ** 31 - 1)
+
+
+def test_a_train_index_outside_the_frame_is_not_followed(ctx):
+    """include/putslam_hip.h: "a trainIdx outside 0 .. b->frames.maxKpts - 1 is not followed: that row is NaN".  Inliers of two
+    lists carry -1, maxKpts, INT32_MIN and INT32_MAX: uv, position and every member of those rows are NaN, mapRow and curRow are the
+    list's own values, the counts include the rows, and every other row is what it was."""
+    import torch
+    from putslam_amd import device_batch as D
+    deps, imgs = scene()
+    batch, dxyu, host = edge_batch()
+    P = len(EDGE_PAIRS)
+    matches = host["matches"].copy()
+    planted = {}
+    for p in (3, 4):
+        inl = np.flatnonzero(host["mask"][p, :host["num"][p]])
+        at = [k for k in (0, len(inl) // 3, len(inl) // 2, len(inl) - 1)]       # the first and the last inlier among them
+        for k, t in zip(at, TRAIN_OUTSIDE if p == 3 else TRAIN_OUTSIDE[::-1]):
+            matches["trainIdx"][p, inl[k]] = t
+            planted[p, k] = t
+    batch.matches.copy_(dev(matches.view(np.uint8).reshape(P, MAX_MATCHES, 16)))
+    out = edge_sentinels(P)
+    torch.cuda.synchronize()
+    D.measurement_edges(ctx, batch, dxyu, geometry(), padded_depth(deps), padded_images(imgs), sensor_struct("scaled"), 2,
+                        np.array(EDGE_FRAME, np.int32), out=out)
+    torch.cuda.synchronize()
+    got = out.download()
+    want = U.measurement_edges(matches, host["num"], host["mask"], EDGE_PAIRS, 2, host["pts"], host["xyu"], EDGE_FRAME, list(deps), list(imgs), K,
+                               SCALE, U.sensor(**SENSORS["scaled"]), 2, MAX_MATCHES)
+    assert got["count"].tolist() == EDGE_INLIERS + [0, 0] == [w["count"] for w in want]
+    for (p, k), t in planted.items():
+        assert got["cur_row"][p, k] == t and got["map_row"][p, k] == want[p]["mapRow"][k]
+        assert (got["uv"][p, k].view(np.uint32) == 0x7FC00000).all(), (p, k, got["uv"][p, k])
+        for m in ("position",) + MEMBERS:
+            assert (got[m][p, k].view(np.uint64) == U.NAN_BITS).all(), (m, p, k, got[m][p, k])
+    for p, w in enumerate(want):
+        n = w["count"]
+        if n:
+            assert np.array_equal(got["map_row"][p, :n], w["mapRow"]) and np.array_equal(got["cur_row"][p, :n], w["curRow"])
+            assert got["uv"][p, :n].tobytes() == w["uv"].tobytes(), p
+            for m in ("position",) + MEMBERS:
+                same_rows(got[m][p, :n], w[m], (m, p))
+        for name in ("map_row", "cur_row", "uv", "position") + MEMBERS:
+            assert untouched(got[name][p, n:]), (name, p)
+    # the rows beside the planted ones are not all NaN: the rule touched its rows alone
+    assert np.isfinite(got["position"][3, 1]).all() and np.isfinite(got["position"][4, 1]).all()
+
+
 TILE_MATCHES = 640                              # three tiles of 256 mask bytes
 TILE_INLIERS = [255, 256, 257, 600, 1, 513]
 TILE_NUM = [600, 610, 640, 600, 300, 640]

@@ -301,8 +301,12 @@ def measurement_edges(matches, num_matches, mask, pairs, num_maps, frame_pts, xy
             continue
         idx = np.flatnonzero(mask[p, :m] != 0)
         q, t = matches["queryIdx"][p, idx].astype(np.int32), matches["trainIdx"][p, idx].astype(np.int32)
-        assert ((t >= 0) & (t < cap)).all()
-        uv, pt = xy_undist[fr, t], frame_pts[fr, t]
+        # include/putslam_hip.h: a trainIdx outside 0 .. maxKpts - 1 is not followed: that row's uv and position are NaN (the
+        # float NaN 0x7FC00000), and so every member; mapRow and curRow still carry the list's values
+        follow = (t >= 0) & (t < cap)
+        at = np.where(follow, t, 0)
+        uv, pt = np.array(xy_undist[fr, at], f32), np.array(frame_pts[fr, at], f32)
+        uv[~follow], pt[~follow] = np.nan, np.nan
         g = int(image_frame[fr])
         inside = 0 <= g < len(depths) and (images is None or g < len(images))
         r = rows(uv, pt, depths[g] if inside else None, images[g] if inside and images is not None else None, K, scale, s, model, want=want)
